@@ -23,6 +23,12 @@ Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (ptl_rend
 against HBM peak: tiny by construction.  `cpu_baseline` times the same generated source compiled for the host (oracle/host_build.py, "port") on a
 bounded sample.  `workloads`: every other BASELINE.json config, the Panini variant and two deep views, each timed and checked the same way (N = 1).
 `python bench.py --gpus N` without a launcher starts its own N ranks (torch.distributed.run, 127.0.0.1).
+
+A plain run (no `--full`) does only what the headline needs: set-up (candidate builds, the fastest kept), warm-up, the K timed steps and the
+line (`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, ...).  `--full` adds everything else described above: the kernel's
+own launch time and rooflines, the trip count, C5 and the other workloads, CPU baselines, the checker's verdicts, the other builds, the
+peer transports at N > 1 and the detail record (`bench_detail.json`).  `--dump-outputs DIR` writes the frame of the last timed step as
+float32 `.npy` files (the whole RGBA8 frame, or a fixed seeded sample of its pixels when the frame is larger than 64 MB as float32).
 """
 from __future__ import annotations
 
@@ -194,6 +200,9 @@ def parse_args():
                    "ptl_render_kernel are then exactly the timed ones)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the cpu_baseline sample")
     p.add_argument("--save-png", default="")
+    p.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline (rooflines, other workloads and builds, "
+                   "CPU baselines, oracle checks, peer transports) and write the detail record; a plain run times the headline only")
+    p.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32)")
     p.add_argument("--lanes", type=int, default=2, help="frames in flight in the timed region at ONE GPU: consecutive frames go to alternating internal streams of the "
                    "renderer (options concurrent_draws K + lane_fence 0), a target per lane, joined at the end; 1 = one stream, one frame at a time (rounds 1-5)")
     args = p.parse_args()
@@ -467,7 +476,7 @@ def _pick(d, keys):
     return {k: d[k] for k in keys if isinstance(d, dict) and k in d and d[k] is not None}
 
 
-def compact_line(out):
+def compact_line(out, detail=True):
     """The ONE stdout line (<= 4 KB): the contract's keys, `roofline` + `cpu_baseline`, the checker's verdicts on the timed build and one short
     object per workload.  Everything else -- notes, tuning, contract distances, JIT detail, per-workload rooflines -- stays in the detail record
     (`bench_detail.json`, also one stderr line).  A test bounds the size (tests/test_host_logic.py, tests/test_gpu_parity.py)."""
@@ -480,6 +489,8 @@ def compact_line(out):
                       "parallelism": str(cfg.get("parallelism", ""))[:60], "jit_specialisation": cfg.get("jit_specialisation"),
                       "hiprtc_version": version.split("hiprtc_version=")[-1] if "hiprtc_version=" in version else None}
     line.update(_pick(out, ("kernel_ms", "kernel_ms_per_rank", "transport_ms", "segments_per_frame", "segment_mray_s", "jit_seconds")))
+    if "roofline" not in out:  # (a plain run measures no roofline)
+        return _finish_line(line, detail)
     roof = out.get("roofline") or {}
     line["roofline"] = _pick(roof, ("bound", "achieved", "peak", "unit", "frac", "traffic", "hw_arith_frac", "frac_counted_by_the_oracle", "lane_utilisation",
                                     "valu_insts_per_launch", "pmc_code_object_sha256", "pmc_kernel_source_sha256", "pmc_match"))
@@ -528,7 +539,12 @@ def compact_line(out):
         rows.append({k: v for k, v in row.items() if v is not None})
     if rows:
         line["workloads"] = rows
-    line["detail"] = "bench_detail.json (and one `[bench detail]` line on stderr): notes, tuning, every roofline in full"
+    return _finish_line(line, detail)
+
+
+def _finish_line(line, detail):
+    if detail:
+        line["detail"] = "bench_detail.json (and one `[bench detail]` line on stderr): notes, tuning, every roofline in full"
     text = json.dumps(line, separators=(",", ":"))
     # belt: whatever a future field adds, the line that reaches the driver stays parseable
     for drop in ("other_builds_kernel_ms", "cpu_baseline_reference_text", "roofline_hbm", "workloads"):
@@ -540,8 +556,29 @@ def compact_line(out):
     return text
 
 
-def emit(out):
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much float32 data
+DUMP_SAMPLE_PIXELS = 1 << 21  # pixels of the seeded sample of a frame above that (float32 RGBA + float64 index: 48 MiB)
+
+
+def dump_outputs(directory, image):
+    """--dump-outputs: the frame of the last timed step -- the (H, W, 4) RGBA8 array a caller of the timed path receives -- as float32 .npy in
+    `directory`: `frame_rgba8.npy` whole when it fits in DUMP_LIMIT_BYTES, otherwise `frame_rgba8_sample.npy` (pixels x 4) at a fixed seeded sample of
+    pixels whose flat indices (y * W + x) are `frame_rgba8_sample_pixels.npy`.  Same arguments, same files: two builds compare output for output."""
+    os.makedirs(directory, exist_ok=True)
+    h, w = image.shape[:2]
+    if image.size * 4 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(directory, "frame_rgba8.npy"), image.astype(np.float32))
+        return
+    pixels = np.sort(np.random.default_rng(0).choice(h * w, size=DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(directory, "frame_rgba8_sample.npy"), image.reshape(-1, 4)[pixels].astype(np.float32))
+    np.save(os.path.join(directory, "frame_rgba8_sample_pixels.npy"), pixels.astype(np.float64))
+
+
+def emit(out, full=True):
     """detail record -> bench_detail.json (+ gpurun_out/ when that exists: it travels back from the GPU box) and stderr; compact line -> stdout (last)."""
+    if not full:  # a plain run: the line alone
+        print(compact_line(out, detail=False), flush=True)
+        return
     detail = json.dumps(out)
     for d in (HERE, os.path.join(HERE, "gpurun_out")):
         if os.path.isdir(d):
@@ -756,6 +793,8 @@ def main():
         transports["rccl-gather"] = parallel.GatherTransport(H, W, rank, world, dev, depth=3, stage_through_host=staged)  # two gathers in flight behind the trace
     peer_kinds = {"p2p-stores": parallel.PeerTransport, "p2p-copy": parallel.CopyTransport}
     wanted = {"p2p": ["p2p-stores"], "copy": ["p2p-copy"], "auto": ["p2p-stores", "p2p-copy"]}.get(mode, [])
+    if mode == "auto" and not (args.full or keep_fastest):
+        wanted = []  # a plain run: the timed value goes through the gather, and the peer transports are --full's extras
     for kind in (wanted if world > 1 else []):
         stage(f"transport set-up {kind}")
         ok, peer = 1, None
@@ -910,6 +949,7 @@ def main():
     events["group"] = every
     in_flight = None
     lanes_failed = None
+    final_image = None  # the frame of the last timed step on rank 0 (numpy), for --save-png / --dump-outputs
     if world == 1 and args.lanes > 1:
         try:
             # Round 6: TWO FRAMES IN FLIGHT.  A launch of this kernel ramps up for ~10 us and drains for as long (the last workgroups of a
@@ -922,20 +962,24 @@ def main():
             for t in targets:
                 t.zero_()
             elapsed = timed_in_flight(renderer, frame, targets, max(args.warmup, lanes), args.steps)
-            # ... and the SAME K steps one at a time on one stream, right behind it, between two synchronisations and between one pair of HIP events:
-            # `kernel_ms` (the launch duration rocprofv3's per-dispatch average agrees with: what `roofline` divides by) and what a step costs with
-            # one frame in flight (`ms_per_step_one_frame_in_flight`, rounds 1-5's figure)
-            n_k = max(args.steps, 64)
-            ev_k = {0: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), n_k), "group": n_k}
-            one_elapsed, last = timed_steps(transport, n_k, ev_k)
-            kernel_ms = float(ev_k[0][0].elapsed_time(ev_k[0][1]) / n_k)
-            kernel_ms_from = (f"HIP events around ONE group of {n_k} consecutive launches on one stream, right behind the timed region (same kernel, same frame): elapsed / launches; "
-                              f"the timed region itself has {lanes} frames in flight on {lanes} streams, where a launch's own duration is not the time a frame costs")
-            same_bytes = bool(all(torch.equal(t[: last.shape[0]], last) for t in targets))
-            in_flight = {"frames_in_flight": lanes, "frames_identical_to_one_in_flight": same_bytes,
-                         "ms_per_step_one_frame_in_flight": round(one_elapsed / n_k * 1e3, 4), "steps_one_frame_in_flight": n_k}
-            if not same_bytes:
-                raise SystemExit("bench: a frame drawn with two frames in flight differs from the frame drawn alone")
+            last = targets[(args.steps - 1) % lanes][:H]  # the frame of the last timed step
+            in_flight = {"frames_in_flight": lanes}
+            kernel_ms = kernel_ms_from = None
+            if args.full:
+                # ... and the SAME K steps one at a time on one stream, right behind it, between two synchronisations and between one pair of HIP events:
+                # `kernel_ms` (the launch duration rocprofv3's per-dispatch average agrees with: what `roofline` divides by) and what a step costs with
+                # one frame in flight (`ms_per_step_one_frame_in_flight`, rounds 1-5's figure)
+                n_k = max(args.steps, 64)
+                ev_k = {0: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), n_k), "group": n_k}
+                one_elapsed, one_last = timed_steps(transport, n_k, ev_k)
+                kernel_ms = float(ev_k[0][0].elapsed_time(ev_k[0][1]) / n_k)
+                kernel_ms_from = (f"HIP events around ONE group of {n_k} consecutive launches on one stream, right behind the timed region (same kernel, same frame): elapsed / launches; "
+                                  f"the timed region itself has {lanes} frames in flight on {lanes} streams, where a launch's own duration is not the time a frame costs")
+                same_bytes = bool(all(torch.equal(t[: one_last.shape[0]], one_last) for t in targets))
+                in_flight.update({"frames_identical_to_one_in_flight": same_bytes,
+                                  "ms_per_step_one_frame_in_flight": round(one_elapsed / n_k * 1e3, 4), "steps_one_frame_in_flight": n_k})
+                if not same_bytes:
+                    raise SystemExit("bench: a frame drawn with two frames in flight differs from the frame drawn alone")
             del targets
         except Exception as e:  # (streams or kernel instances could not be had: the line must still come out -- one frame at a time, and it says so)
             lanes_failed = str(e)[:200]
@@ -958,24 +1002,32 @@ def main():
         # the transport too: the timed region runs without any event, and every rank's kernel time comes from a pass of its own right behind
         # it (same frames, same transport, one pair per launch)
         elapsed, last = timed_steps(transport, args.steps)
-        n_k = max(16, min(args.steps, 64))
-        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_k)]
-        run_steps(transport, n_k, pairs)
-        torch.cuda.synchronize(dev)
-        kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in pairs]))
-        kernel_ms_from = f"HIP events around each of {n_k} launches of an untimed pass right behind the timed region (same frames, same transport)"
+        kernel_ms = kernel_ms_from = None
+        if args.full:
+            n_k = max(16, min(args.steps, 64))
+            pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_k)]
+            # (the frame of the last timed step first: this pass reuses the transport's buffers)
+            final_image = transport.download(last) if rank == 0 and (args.save_png or args.dump_outputs) else None
+            run_steps(transport, n_k, pairs)
+            torch.cuda.synchronize(dev)
+            kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in pairs]))
+            kernel_ms_from = f"HIP events around each of {n_k} launches of an untimed pass right behind the timed region (same frames, same transport)"
+    if rank == 0 and (args.save_png or args.dump_outputs) and final_image is None:
+        final_image = transport.download(last) if in_flight is None else last.cpu().numpy()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, final_image)
     per_rank_ms = [kernel_ms]
-    if world > 1:  # every rank's own kernel time: load balance of the interleave, and the slowest sets the frame
+    if world > 1 and kernel_ms is not None:  # every rank's own kernel time: load balance of the interleave, and the slowest sets the frame
         gathered = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
         dist.all_gather(gathered, torch.tensor([kernel_ms], dtype=torch.float64, device=dev))
         per_rank_ms = [float(t.item()) for t in gathered]
-    kernel_ms = max(per_rank_ms)
+    kernel_ms = max(per_rank_ms) if kernel_ms is not None else None
 
     # untimed, N > 1: the LAST frame of the timed region, as assembled on rank 0 by the kept transport, against the same frame
     # rendered by rank 0 alone (one launch, no sharding, no transport).  On one GPU the transports were rehearsed with every rank on
     # the same device; this is the check that a fence / visibility problem on real xGMI cannot get past.
     frame_check = None
-    if world > 1:
+    if world > 1 and args.full:
         assembled = transport.download(last) if rank == 0 else None
         ok = torch.tensor([1], dtype=torch.int32, device=dev)
         if rank == 0:
@@ -993,7 +1045,7 @@ def main():
     # one collective's latency, so its scaling curve is flat by construction; C5's 16 ms per frame is the workload whose curve says
     # something about the sharding.  Run at every N (the N = 1 line is the reference the driver computes efficiency against).
     second = None
-    if not args.no_second_workload and workload_key(args) == "portal_in_portal_3840x2160_d40":
+    if args.full and not args.no_second_workload and workload_key(args) == "portal_in_portal_3840x2160_d40":
         try:
             stage("second workload: c5")
             w2 = WORKLOADS["c5"]
@@ -1069,7 +1121,7 @@ def main():
     # synchronisations, the kernel's launches between HIP events -- with its trips per ray, its roofline, a bounded CPU baseline and the
     # checker's verdict on the frame of the build that was timed.  (one driver-run line for every workload.)
     others = []
-    if world == 1 and not args.no_second_workload and not args.no_cpu_baseline and workload_key(args) == "portal_in_portal_3840x2160_d40":
+    if args.full and world == 1 and not args.no_second_workload and not args.no_cpu_baseline and workload_key(args) == "portal_in_portal_3840x2160_d40":
         import argparse as _ap
 
         extra = [("c2", WORKLOADS["c2"]), ("c3", WORKLOADS["c3"]), ("c4-panini", dict(WORKLOADS["c4"], panini=1.0, fov=140.0)), ("c4-deep", WORKLOADS["c4-deep"]),
@@ -1144,20 +1196,21 @@ def main():
 
     # bounce-loop trips per frame (untimed, separate kernel variant with the counter compiled in)
     segments = None
-    try:
-        if args.no_segments:
-            raise RuntimeError("--no-segments")
-        counting = pa.SceneRenderer(scene, device=local_rank, flags=pa.FLAG_COUNT_SEGMENTS | spec_flags, **scene_kw)
-        configure(counting, args)
-        seg = torch.zeros(1, dtype=torch.int64, device=dev)
-        counting.draw_device(frame, out_rgba8=shard.data_ptr(), segments=seg.data_ptr(), stream=stream.cuda_stream)
-        torch.cuda.synchronize(dev)
-        if world > 1:
-            dist.all_reduce(seg)
-        segments = int(seg.item())
-        del counting
-    except Exception as e:  # the headline number does not depend on it
-        print(f"[bench] segment count unavailable: {e}", file=sys.stderr)
+    if args.full:
+        try:
+            if args.no_segments:
+                raise RuntimeError("--no-segments")
+            counting = pa.SceneRenderer(scene, device=local_rank, flags=pa.FLAG_COUNT_SEGMENTS | spec_flags, **scene_kw)
+            configure(counting, args)
+            seg = torch.zeros(1, dtype=torch.int64, device=dev)
+            counting.draw_device(frame, out_rgba8=shard.data_ptr(), segments=seg.data_ptr(), stream=stream.cuda_stream)
+            torch.cuda.synchronize(dev)
+            if world > 1:
+                dist.all_reduce(seg)
+            segments = int(seg.item())
+            del counting
+        except Exception as e:  # the headline number does not depend on it
+            print(f"[bench] segment count unavailable: {e}", file=sys.stderr)
 
     # untimed, N = 1 only: the same frame with NO JIT specialisation (every scene uniform read at run time), for the record.
     # (Skipped together with the CPU baseline, i.e. in the profiling runs: their per-kernel statistics are about the timed launches.)
@@ -1166,7 +1219,7 @@ def main():
     # ... and with NO value baked but the zero patterns of the matrices and the renderer's mode switches compiled in (FLAG_SPECIALIZE_PATTERNS):
     # valid while the patterns hold, i.e. for every frame of a clip whose portals move without leaving their planes' axes.
     dynamic_ms = ints_ms = patterns_ms = dynamic_build = ints_build = patterns_build = None
-    if world == 1 and args.specialize != 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and args.specialize != 0 and not args.no_cpu_baseline:
         try:
             for base_flags in (0, pa.FLAG_SPECIALIZE_INTS, pa.FLAG_SPECIALIZE_PATTERNS):
                 timings = []
@@ -1203,7 +1256,7 @@ def main():
     # `portal-amd render` does with the blur sub-frames of a clip frame).  The ramp and tail of one launch are shared by the frames in it,
     # which is what a small frame (C2: 50 us) loses most of its time to.  Same build otherwise, same frames (compared below).
     batched = None
-    if world == 1 and not args.no_segments and args.specialize == 2:  # (--no-segments: the profiling passes, whose statistics are about the timed launches)
+    if args.full and world == 1 and not args.no_segments and args.specialize == 2:  # (--no-segments: the profiling passes, whose statistics are about the timed launches)
         try:
             nsl = 8 if W * H <= 1920 * 1080 else 4
             sl_r = pa.SceneRenderer(scene, device=local_rank, flags=spec_flags | pa.FLAG_SLICES, **scene_kw)
@@ -1231,7 +1284,7 @@ def main():
 
     # untimed, N = 1 only: the tolerance mode (FLAG_FAST_MATH) on the same frame: kernel time and how far its picture is from the exact one
     fast = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             f32 = torch.empty((2, H, W, 4), dtype=torch.float32, device=dev)
             exact_r = pa.SceneRenderer(scene, device=local_rank, flags=spec_flags, **scene_kw)
@@ -1253,7 +1306,7 @@ def main():
     # untimed, N = 1 only: what the JIT of the timed build costs on a cold cache (child process, private empty cache, comgr cache off)
     jit_seconds = None
     jit_detail = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         try:
             import subprocess
             import tempfile
@@ -1282,12 +1335,10 @@ def main():
 
     if rank == 0:
         if args.save_png:
-            pa.png_write(args.save_png, transport.download(last))
+            pa.png_write(args.save_png, final_image)
         rays = W * H * args.aa
         ms_per_step = elapsed / args.steps * 1e3
         value = rays * args.steps / elapsed / 1e6
-        launch_bytes = rows * W * 4  # RGBA8 stored by this rank's launch
-        achieved = launch_bytes / (kernel_ms * 1e-3) / 1e9
         out = {
             "metric": f"Mray/s (primary rays) + ms/frame at {W}x{H}, {args.scene} depth={args.depth}" + (f" aa={args.aa}" if args.aa != 1 else ""),
             "value": round(value, 3),
@@ -1318,13 +1369,16 @@ def main():
                 **({"candidates_excluded": frames_differ} if frames_differ else {}),
                 **({"transport": transport.name, "transport_ms_per_frame": transport_ms, "transport_notes": transport_notes} if world > 1 else {}),
             },
-            "kernel_ms": round(kernel_ms, 4),
-            "kernel_ms_from": kernel_ms_from,
-            # per rank: the interleave's load balance; ms_per_step - max(kernel_ms_per_rank) = what assembling the frame costs on top of tracing
-            "kernel_ms_per_rank": [round(x, 4) for x in per_rank_ms],
-            "kernel_ms_min_max": [round(min(per_rank_ms), 4), round(max(per_rank_ms), 4)],
-            "transport_ms": round(max(0.0, ms_per_step - max(per_rank_ms)), 4),
         }
+        if kernel_ms is not None:  # (a plain run with frames in flight or N > 1 does not time the kernel's launches on their own)
+            out.update({
+                "kernel_ms": round(kernel_ms, 4),
+                "kernel_ms_from": kernel_ms_from,
+                # per rank: the interleave's load balance; ms_per_step - max(kernel_ms_per_rank) = what assembling the frame costs on top of tracing
+                "kernel_ms_per_rank": [round(x, 4) for x in per_rank_ms],
+                "kernel_ms_min_max": [round(min(per_rank_ms), 4), round(max(per_rank_ms), 4)],
+                "transport_ms": round(max(0.0, ms_per_step - max(per_rank_ms)), 4),
+            })
         if frame_check is not None:
             out["frame_check"] = frame_check
         if second is not None:
@@ -1354,58 +1408,61 @@ def main():
         out["config"]["affine_rays"] = renderer.affine_rays()
         out["config"]["toolchain"] = pa.version()
         out["config"]["kernel_source_sha256"] = source_sha256(renderer)
-        pmc, pmc_why = stored_pmc(args, best, timed_sha, out["config"]["kernel_source_sha256"])
-        hbm = {
-            "bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-            "traffic": pmc["traffic"] if pmc else None,
-            "note": "algorithmic bytes = the RGBA8 framebuffer store (4 B/pixel); constants and textures are cache-resident",
-        }
-        if segments is not None:
-            out["config"]["trips_per_primary_ray"] = round(segments / rays, 4)
-            out["segments_per_frame"] = segments
-            out["segment_mray_s"] = round(segments / (ms_per_step * 1e-3) / 1e6, 3)
-        fl = flops_per_segment(args, renderer.affine_rays())
-        if segments is not None and fl:
-            roof = valu_roofline(fl, pmc, segments, world, kernel_ms, hbm["traffic"], args.specialize)
-            if pmc is None:
-                roof["pmc_unavailable"] = pmc_why
-            out["roofline"] = roof
-            out["roofline_hbm"] = hbm
-            if batched is not None:  # the same instructions in less time: fraction and ceiling scale alike
-                ratio = kernel_ms / batched["kernel_ms_per_frame"]
-                batched["frac"] = round(roof["frac"] * ratio, 5)
-                if "frac_ceiling_valu_plus_fma" in roof:
-                    batched["frac_ceiling_valu_plus_fma"] = round(roof["frac_ceiling_valu_plus_fma"] * ratio, 4)
-        else:
-            out["roofline"] = hbm
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                out["cpu_baseline"] = cpu_baseline(args, pa)
-            except Exception as e:
-                out["cpu_baseline"] = {"error": str(e)[:300]}
-            kept = []
-            try:
-                out["cpu_baseline_reference_text"] = reference_text_baseline(args, pa, keep=kept)
-            except Exception as e:
-                out["cpu_baseline_reference_text"] = {"error": str(e)[:300]}
-            try:
-                if kept:
-                    out["reference_text_check_of_the_timed_build"] = reference_text_check(args, pa, renderer, torch, dev, stream, kept)
-            except Exception as e:
-                out["reference_text_check_of_the_timed_build"] = {"error": str(e)[:300]}
-            try:
-                which = {"headline": dict(scene=args.scene, width=W, height=H, depth=args.depth, aa=args.aa)} if not (args.scene_file or args.camera or args.panini >= 0) else {}
-                if workload_key(args) == "portal_in_portal_3840x2160_d40" and not args.no_second_workload:
-                    which["c5"] = WORKLOADS["c5"]
-                if which and args.specialize == 2:
-                    out["contract1_vs_contract2"] = contract_distance(args, pa, torch, dev, stream, local_rank, spec_flags, which)
-            except Exception as e:
-                out["contract1_vs_contract2"] = {"error": str(e)[:300]}
-            try:
-                out["oracle_check_of_the_timed_build"] = oracle_check(args, pa, renderer, torch, dev, stream)
-            except Exception as e:
-                out["oracle_check_of_the_timed_build"] = {"error": str(e)[:300]}
-        emit(out)
+        if args.full:  # rooflines, CPU baselines and the checkers: --full only
+            launch_bytes = rows * W * 4  # RGBA8 stored by this rank's launch
+            achieved = launch_bytes / (kernel_ms * 1e-3) / 1e9
+            pmc, pmc_why = stored_pmc(args, best, timed_sha, out["config"]["kernel_source_sha256"])
+            hbm = {
+                "bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                "traffic": pmc["traffic"] if pmc else None,
+                "note": "algorithmic bytes = the RGBA8 framebuffer store (4 B/pixel); constants and textures are cache-resident",
+            }
+            if segments is not None:
+                out["config"]["trips_per_primary_ray"] = round(segments / rays, 4)
+                out["segments_per_frame"] = segments
+                out["segment_mray_s"] = round(segments / (ms_per_step * 1e-3) / 1e6, 3)
+            fl = flops_per_segment(args, renderer.affine_rays())
+            if segments is not None and fl:
+                roof = valu_roofline(fl, pmc, segments, world, kernel_ms, hbm["traffic"], args.specialize)
+                if pmc is None:
+                    roof["pmc_unavailable"] = pmc_why
+                out["roofline"] = roof
+                out["roofline_hbm"] = hbm
+                if batched is not None:  # the same instructions in less time: fraction and ceiling scale alike
+                    ratio = kernel_ms / batched["kernel_ms_per_frame"]
+                    batched["frac"] = round(roof["frac"] * ratio, 5)
+                    if "frac_ceiling_valu_plus_fma" in roof:
+                        batched["frac_ceiling_valu_plus_fma"] = round(roof["frac_ceiling_valu_plus_fma"] * ratio, 4)
+            else:
+                out["roofline"] = hbm
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    out["cpu_baseline"] = cpu_baseline(args, pa)
+                except Exception as e:
+                    out["cpu_baseline"] = {"error": str(e)[:300]}
+                kept = []
+                try:
+                    out["cpu_baseline_reference_text"] = reference_text_baseline(args, pa, keep=kept)
+                except Exception as e:
+                    out["cpu_baseline_reference_text"] = {"error": str(e)[:300]}
+                try:
+                    if kept:
+                        out["reference_text_check_of_the_timed_build"] = reference_text_check(args, pa, renderer, torch, dev, stream, kept)
+                except Exception as e:
+                    out["reference_text_check_of_the_timed_build"] = {"error": str(e)[:300]}
+                try:
+                    which = {"headline": dict(scene=args.scene, width=W, height=H, depth=args.depth, aa=args.aa)} if not (args.scene_file or args.camera or args.panini >= 0) else {}
+                    if workload_key(args) == "portal_in_portal_3840x2160_d40" and not args.no_second_workload:
+                        which["c5"] = WORKLOADS["c5"]
+                    if which and args.specialize == 2:
+                        out["contract1_vs_contract2"] = contract_distance(args, pa, torch, dev, stream, local_rank, spec_flags, which)
+                except Exception as e:
+                    out["contract1_vs_contract2"] = {"error": str(e)[:300]}
+                try:
+                    out["oracle_check_of_the_timed_build"] = oracle_check(args, pa, renderer, torch, dev, stream)
+                except Exception as e:
+                    out["oracle_check_of_the_timed_build"] = {"error": str(e)[:300]}
+        emit(out, full=args.full)
     transport.close()
     if world > 1:
         dist.destroy_process_group()

@@ -3,7 +3,7 @@
 usage: gpu_fuzz_hunt.py [SEED_BASE [N_SCENES [N_GLSL]]] -- e.g. `1000 240 120` was run after the sqrt / reciprocal change: no mismatch
 in 240 scenes and 5 760 expressions."""
 import sys, os, tempfile, numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import portal_amd as pa
 from tests.test_scene_fuzz import random_scene
 from tests.test_glsl_fuzz import fuzz_scene, fuzz_scene_with_uniforms, N_EXPR

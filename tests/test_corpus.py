@@ -1,7 +1,7 @@
 """The reference's whole scene corpus (84 .ron files) through the product and the oracle.
 
-Only runs where the reference checkout is mounted (/root/reference: the build container); the
-GPU box has no copy, there the five BASELINE scenes under scenes/ are what is tested.
+The scene files and their textures are the copies under tests/corpus/ (see its README), so the test runs
+wherever the repository is checked out.
 For every scene: load -> generate the kernel source -> compile it for the host -> render a small
 frame -> compare bit for bit with the independent numpy oracle.  A sample is also compiled with
 hiprtc for gfx950 (no GPU needed).
@@ -12,8 +12,8 @@ import os
 import numpy as np
 import pytest
 
-CORPUS = "/root/reference/scenes"
-pytestmark = pytest.mark.skipif(not os.path.isdir(CORPUS), reason="reference scene corpus not mounted")
+ASSET_ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "corpus")
+CORPUS = os.path.join(ASSET_ROOT, "scenes")
 
 OUT_OF_SCOPE = set()  # nothing: all 82 non-empty scene files go through
 
@@ -51,7 +51,7 @@ def test_corpus_scene_product_equals_oracle(pa, path, build):
     source = scene.generate_source(0 if build == "plain" else pa.FLAG_SPECIALIZE_INTS)
     layout, size = scene.uniform_layout()
     hk = hb.HostKernel(source, layout, size, opt="-O0")  # tiny frames: compile time dominates
-    o = Oracle(path, asset_root="/root/reference")
+    o = Oracle(path, asset_root=ASSET_ROOT)
     o.options["render_depth"] = depth
     # uniform values: the product's (scene + builtins) go into the host kernel; the oracle computes its own
     from oracle.scene_eval import builtin_uniforms
@@ -70,7 +70,7 @@ def test_corpus_scene_product_equals_oracle(pa, path, build):
     from PIL import Image
 
     for tex_name, rel in scene.textures().items():
-        full = os.path.join("/root/reference", rel)
+        full = os.path.join(ASSET_ROOT, rel)
         if os.path.exists(full):
             hk.set_texture(tex_name + "_tex", np.array(Image.open(full).convert("RGBA")))
     got = hk.render(w, h, threads=2)
@@ -87,7 +87,7 @@ def test_builtin_uniform_values_used_above_are_the_products(pa):
 
     for name in ("cone", "room", "zeno_portal"):
         path = os.path.join(CORPUS, name + ".ron")
-        r = pa.SceneRenderer(pa.Scene.from_file(path), device=-1, asset_root="/root/reference")
+        r = pa.SceneRenderer(pa.Scene.from_file(path), device=-1, asset_root=ASSET_ROOT)
         r.set_option("render_depth", 12)
         for k, v in builtin_uniforms(OracleScene(path), 24, 14, render_depth=12).items():
             g = r.uniform_value(k, 24, 14)
@@ -101,12 +101,12 @@ def test_corpus_scene_compiles_for_gfx950(pa, path, tmp_path, monkeypatch):
     subspaces, DebugMatrix, scene-defined inverse(), video samplers, `const in`, Trefoil ... all become gfx950 code objects."""
     monkeypatch.setenv("PTL_CACHE_DIR", str(tmp_path))  # keep 82 code objects out of the repository's cache
     scene = pa.Scene.from_file(path)
-    r = pa.SceneRenderer(scene, device=-1, asset_root="/root/reference", flags=pa.FLAG_SPECIALIZE_STATIC)
+    r = pa.SceneRenderer(scene, device=-1, asset_root=ASSET_ROOT, flags=pa.FLAG_SPECIALIZE_STATIC)
     assert r.code_object()[:4] == b"\x7fELF"
     # ... and with only Bool / Int uniforms baked: every matrix stays a run-time value and the generator rewrites the products with the
     # masked ones by their shape (`X_mat * <operand>`, `transform(X_mat, ..)`) -- whatever the scene's authors wrote has to survive that
     if path in masked_build_sample():
-        r = pa.SceneRenderer(pa.Scene.from_file(path), device=-1, asset_root="/root/reference", flags=pa.FLAG_SPECIALIZE_INTS)
+        r = pa.SceneRenderer(pa.Scene.from_file(path), device=-1, asset_root=ASSET_ROOT, flags=pa.FLAG_SPECIALIZE_INTS)
         assert r.code_object()[:4] == b"\x7fELF"
 
 

@@ -162,6 +162,37 @@ def test_the_stdout_line_stays_small_enough_for_the_driver():
     assert len(text) <= bench.COMPACT_LINE_LIMIT and "workloads" in json.loads(text)["dropped_for_size"] and "roofline" in json.loads(text)
 
 
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run's record (no --full: no roofline, no detail record) still gives the contract's keys and no pointer to a detail file; --dump-outputs
+    writes a frame that fits in 64 MB of float32 whole and a 4K frame as the same seeded pixel sample every time, its values those of the frame."""
+    import sys
+
+    import numpy as np
+
+    sys.path.insert(0, HERE)
+    import bench
+
+    plain = {"metric": "Mray/s (primary rays) + ms/frame at 3840x2160, portal_in_portal depth=40", "value": 46000.0, "unit": "Mray/s", "n_gpus": 1, "steps": 20,
+             "warmup": 5, "ms_per_step": 0.18, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+             "config": {"workload": "scenes/portal_in_portal.ron 3840x2160 aa=1 depth=40", "build": "w0", "frames_in_flight": 2}}
+    line = json.loads(bench.compact_line(plain, detail=False))
+    assert {k: line[k] for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "steps")} == {k: plain[k] for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "steps")}
+    assert "roofline" not in line and "detail" not in line and line["config"]["frames_in_flight"] == 2
+    rng = np.random.default_rng(5)
+    small = rng.integers(0, 256, (720, 1280, 4), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert os.listdir(tmp_path / "small") == ["frame_rgba8.npy"] and np.array_equal(np.load(tmp_path / "small" / "frame_rgba8.npy"), small.astype(np.float32))
+    big = rng.integers(0, 256, (2160, 3840, 4), dtype=np.uint8)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["frame_rgba8_sample.npy", "frame_rgba8_sample_pixels.npy"] and sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    got, pixels = np.load(tmp_path / "a" / files[0]), np.load(tmp_path / "a" / files[1])
+    assert got.dtype == np.float32 and pixels.dtype == np.float64 and got.shape == (bench.DUMP_SAMPLE_PIXELS, 4) and len(np.unique(pixels)) == len(pixels)
+    assert np.array_equal(got, big.reshape(-1, 4)[pixels.astype(np.int64)].astype(np.float32))
+    assert all(np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in files)
+
+
 R06 = os.path.join(HERE, "profiles", "r06")
 
 
