@@ -231,6 +231,33 @@ int ptl_scene_cam(ptl_scene* s, double out7[7]);
  * Returns 1 when index is past the end. */
 int ptl_scene_texture(ptl_scene* s, int index, char* name, size_t name_cap, char* path, size_t path_cap);
 
+/* ---- generation / renderer flags (the bits are described below, at ptl_scene_generate_source) ---- */
+#define PTL_FLAG_SPECIALIZE_INTS (1u << 0)
+#define PTL_FLAG_COUNT_SEGMENTS (1u << 1)
+#define PTL_FLAG_SPECIALIZE_ALL (1u << 2)
+#define PTL_FLAG_SPECIALIZE_STATIC (1u << 3)
+#define PTL_FLAG_ANAGLYPH (1u << 4)
+#define PTL_FLAG_NO_DERIVED_UNIFORMS (1u << 5)
+#define PTL_FLAG_FAST_MATH (1u << 6)
+#define PTL_FLAG_NO_DEFERRED_UPDATES (1u << 7)
+#define PTL_FLAG_WAVES_SHIFT 8 /* bits 8-11: occupancy hint n, (n & 0xF) << PTL_FLAG_WAVES_SHIFT */
+#define PTL_FLAG_NO_UNIFORM_HOIST (1u << 12)
+#define PTL_FLAG_NO_FIRST_TRIP (1u << 13)
+#define PTL_FLAG_EXACT_CR (1u << 14)
+#define PTL_FLAG_NO_UNROLL (1u << 15)
+#define PTL_FLAG_NO_FIRST_TRIP_PLANES (1u << 16)
+#define PTL_FLAG_ASYNC_REJIT (1u << 17)
+#define PTL_FLAG_QUICK_JIT (1u << 18)
+#define PTL_FLAG_NO_ZERO_MASKS (1u << 19)
+#define PTL_FLAG_SPECIALIZE_PATTERNS (1u << 20)
+#define PTL_FLAG_BOUNDED_SNIPPETS (1u << 21)
+#define PTL_FLAG_SLICES (1u << 22)
+#define PTL_FLAG_NO_AFFINE_RAYS (1u << 23)
+#define PTL_FLAG_KEEP_TRANSFORM_DODGES (1u << 24)
+#define PTL_FLAG_CHECK_AFFINE (1u << 25)
+#define PTL_FLAG_MATERIAL_TABLE_LDS (1u << 26)
+#define PTL_FLAG_MATERIAL_TABLE_SCALAR (1u << 27)
+
 /* Scene::generate_shader_code: returns a malloc'ed NUL-terminated HIP C++ source (free with
  * ptl_free).  flags: bit0 = bake Bool/Int scene uniforms as literals, bit1 = count segments,
  * bit2 = bake every scene uniform (ints, floats, matrices; camera and other builtins stay dynamic),

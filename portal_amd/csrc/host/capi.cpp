@@ -85,6 +85,31 @@ void copy_str(char* dst, size_t cap, const std::string& s) {
 
 ptl_type to_c_type(UniformType t) { return (ptl_type)(int)t; }
 
+// The renderer's plain options (set_plain_option): SceneRenderer defaults, src/main.rs:1021-1040
+struct RenderOptions {
+    double offset_after_material = 0.005, gray_t_start = 10.0, gray_t_size = 200.0;
+    int render_depth = 100, aa_count = 1, aa_start = 0;
+    bool draw_side_by_side = false, draw_depth_map = false, angle_color_disable = false, grid_disable = false,
+         black_border_disable = false, darken_by_distance = true;
+    double depth_map_min = 0.0, depth_map_max = 10.0, anaglyph_p = 0.29, anaglyph_q = 0.06;
+    bool draw_anaglyph = false, anaglyph_mode = false;  // anaglyph_mode = "colorful" (src/main.rs:1551-1556)
+    double eye_distance = 0.07;  // src/main.rs:1028-1029
+    bool swap_eyes = false;
+};
+
+// What a specialised renderer has learnt about the states of the current stage / clip; another stage judges afresh (decide_rebuild).
+struct StageMemory {
+    std::set<std::string> keep_dynamic;   // clip-constant values that moved after all: run-time uniforms
+    std::set<std::string> keep_unmasked;  // run-time matrices whose zero pattern did not hold: full products
+    bool full_chains = false;             // a run-time matrix turned non-finite under a kernel with shortened products: keep the full chains
+    // Affine rays (codegen.h KernelOptions::affine_rays) hold while every matrix that meets a ray -- the scene's (checked where the zero patterns
+    // are, and by the generator) and the CAMERA's (a run-time value in every build: checked before every draw) -- has the bottom row 0 0 0 1.
+    // One that does not switches the assumption off for this stage.
+    bool no_affine = false;
+    int affine_returns = 0;           // returns to affine rays in this stage (at most one: decide_rebuild)
+    bool no_affine_just_set = false;  // the rebuild in progress is the one that switches them off
+};
+
 }  // namespace
 
 struct ptl_scene {
@@ -100,15 +125,7 @@ struct ptl_renderer {
     std::shared_ptr<Scene> scene;
     ptl_kernel* kernel = nullptr;
     Camera cam;
-    // SceneRenderer defaults, src/main.rs:1021-1040
-    double offset_after_material = 0.005, gray_t_start = 10.0, gray_t_size = 200.0;
-    int render_depth = 100, aa_count = 1, aa_start = 0;
-    bool draw_side_by_side = false, draw_depth_map = false, angle_color_disable = false, grid_disable = false,
-         black_border_disable = false, darken_by_distance = true;
-    double depth_map_min = 0.0, depth_map_max = 10.0, anaglyph_p = 0.29, anaglyph_q = 0.06;
-    bool draw_anaglyph = false, anaglyph_mode = false;  // anaglyph_mode = "colorful" (src/main.rs:1551-1556)
-    double eye_distance = 0.07;  // src/main.rs:1028-1029
-    bool swap_eyes = false;
+    RenderOptions opt;
     // draw-to-draw caching of the uploads: the reference re-evaluates and re-uploads every uniform on
     // every draw (src/main.rs:1413-1414); the values only change when the scene, an option, the camera
     // or the frame size does, so a draw of an unchanged state is just the kernel launch
@@ -120,31 +137,23 @@ struct ptl_renderer {
     std::string asset_root;
     unsigned long long kernel_scene_version = 0;
     std::string kernel_source;
-    std::map<std::string, int> kernel_switches;  // the mode switches the current specialised kernel has compiled in (KernelOptions::baked_options)
-    std::vector<std::pair<std::string, MatrixPattern>> masked;  // run-time matrices whose pattern (zeros, +-1) the current kernel has compiled in (GeneratedKernel::masked)
-    std::set<std::string> keep_unmasked;                   // ... and those whose pattern did not hold (clip-constant builds: demoted like keep_dynamic)
-    bool shortened = false;    // the current kernel skips zero terms of matrix products (PTL_DROP_ZERO_TERMS and / or masks): exact for finite vectors
-    bool full_chains = false;  // a run-time matrix turned non-finite under such a kernel: every later build of this stage keeps the full chains
-    // Affine rays (codegen.h KernelOptions::affine_rays): the current kernel assumes o.w = 1 / d.w = 0, which holds while every matrix that
-    // meets a ray -- the scene's (checked where the zero patterns are, and by the generator) and the CAMERA's (a run-time value in every
-    // build: checked before every draw) -- has the bottom row 0 0 0 1.  One that does not switches the assumption off for this stage.
-    bool affine_rays = false;  // the current kernel was generated with PTL_AFFINE_RAYS
-    bool no_affine = false;    // ... and must not be any more
+    // What the wanted specialised build (the current kernel's, without PTL_FLAG_ASYNC_REJIT) has compiled in, and for which stage:
+    std::map<std::string, int> kernel_switches;  // the mode switches (KernelOptions::baked_options)
+    std::vector<std::pair<std::string, MatrixPattern>> masked;  // run-time matrices whose pattern (zeros, +-1) is compiled in (GeneratedKernel::masked)
+    bool shortened = false;    // it skips zero terms of matrix products (PTL_DROP_ZERO_TERMS and / or masks): exact for finite vectors
+    bool affine_rays = false;  // it was generated with PTL_AFFINE_RAYS
+    std::vector<UniformUpload> baked;  // the scene values it has as literals
+    StageRef kernel_stage;
+    StageMemory stage;
     // Round 6: option "check_affine" (or PTL_CHECK_AFFINE=1 in the environment): the first draw with every NEW affine-rays source first runs the
     // checking build of the same state at 64 x 36 (ptl_renderer_check_affine); a ray that met a product with another w switches the assumption off.
-    int affine_returns = 0;           // returns to affine rays in this stage (at most one: build_kernel)
-    bool no_affine_just_set = false;  // the rebuild in progress is the one that switches them off
     bool check_affine_on_new_source = false;
     std::string checked_source;
-    unsigned long long affine_violations_seen = 0;
+    unsigned long long affine_violations_seen = 0;  // the most any check counted: above zero, affine rays stay off in every later stage
     // SceneRenderer::update state (src/main.rs:1430-1538)
     Camera prev_cam;
     bool has_prev_cam = false;
     CalculatedCam original_cam;  // egui memory "OriginalCam"
-    // FLAG_SPECIALIZE_STATIC: what the current kernel has compiled in, for which stage, and what had to be demoted
-    std::vector<UniformUpload> baked;
-    std::set<std::string> keep_dynamic;
-    StageRef kernel_stage;
     int rejit_count = 0;
     // PTL_FLAG_ASYNC_REJIT (bit 17): a specialised renderer whose baked values went stale does not stall the draw for the 1-3 s of a rebuild.
     // It keeps two kernels -- `spec_kernel` (the specialised build of some scene state) and `dyn_kernel` (the un-specialised build: valid
@@ -167,7 +176,7 @@ struct ptl_renderer {
     ptl_kernel* spec_kernel = nullptr;
     ptl_kernel* dyn_kernel = nullptr;
     std::string spec_source, failed_source;
-    Build want;                 // the specialised build of the scene state seen by the last draw
+    Build want;                 // the build decide_rebuild generated last: compiled at once without PTL_FLAG_ASYNC_REJIT, by the worker with it
     std::shared_ptr<Job> job;
     // "concurrent_draws" K > 1: draws on the caller's default stream go round-robin to K internal streams, each with its OWN instance of the
     // kernel (ptl_kernel_clone: the same code object, another uniform block), so that consecutive draws with different uniforms -- the blur
@@ -233,7 +242,7 @@ bool camera_is_affine(const ptl_renderer& r) {
     float f[16];
     r.cam.matrix().to_f32(f);
     if (!matrix_is_affine(f)) return false;
-    if (r.draw_side_by_side || r.draw_anaglyph) {
+    if (r.opt.draw_side_by_side || r.opt.draw_anaglyph) {
         r.cam.left_eye_matrix.to_f32(f);
         if (!matrix_is_affine(f)) return false;
         r.cam.right_eye_matrix.to_f32(f);
@@ -286,27 +295,28 @@ std::vector<UniformUpload> builtin_uniforms(const ptl_renderer& r, int width, in
     i1("_use_panini_projection", r.cam.use_panini_projection ? 1 : 0);
     i1("_use_360_camera", r.cam.use_360_camera ? 1 : 0);
     i1("_use_180_camera", r.cam.use_180_camera ? 1 : 0);
-    i1("_ray_tracing_depth", r.render_depth);
-    i1("_aa_count", r.aa_count);
-    i1("_aa_start", r.aa_start);
-    i1("_draw_side_by_side", r.draw_side_by_side ? 1 : 0);
-    i1("_draw_anaglyph", r.draw_anaglyph ? 1 : 0);
-    f1("_anaglyph_p", r.anaglyph_p);
-    f1("_anaglyph_q", r.anaglyph_q);
-    i1("_anaglyph_mode", r.anaglyph_mode ? 1 : 0);
-    i1("_draw_depth_map", r.draw_depth_map ? 1 : 0);
-    f1("_depth_map_min", r.depth_map_min);
-    f1("_depth_map_max", r.depth_map_max);
-    f1("_offset_after_material", r.offset_after_material);
-    f1("_t_start", r.gray_t_start);
-    f1("_t_end", r.gray_t_start + r.gray_t_size);
+    const RenderOptions& o = r.opt;
+    i1("_ray_tracing_depth", o.render_depth);
+    i1("_aa_count", o.aa_count);
+    i1("_aa_start", o.aa_start);
+    i1("_draw_side_by_side", o.draw_side_by_side ? 1 : 0);
+    i1("_draw_anaglyph", o.draw_anaglyph ? 1 : 0);
+    f1("_anaglyph_p", o.anaglyph_p);
+    f1("_anaglyph_q", o.anaglyph_q);
+    i1("_anaglyph_mode", o.anaglyph_mode ? 1 : 0);
+    i1("_draw_depth_map", o.draw_depth_map ? 1 : 0);
+    f1("_depth_map_min", o.depth_map_min);
+    f1("_depth_map_max", o.depth_map_max);
+    f1("_offset_after_material", o.offset_after_material);
+    f1("_t_start", o.gray_t_start);
+    f1("_t_end", o.gray_t_start + o.gray_t_size);
     f1("_camera_scale", calc_scale(cam));
     f1("_left_eye_scale", calc_scale(r.cam.left_eye_matrix));
     f1("_right_eye_scale", calc_scale(r.cam.right_eye_matrix));
-    i1("_angle_color_disable", r.angle_color_disable ? 1 : 0);
-    i1("_grid_disable", r.grid_disable ? 1 : 0);
-    i1("_black_border_disable", r.black_border_disable ? 1 : 0);
-    i1("_darken_by_distance", r.darken_by_distance ? 1 : 0);
+    i1("_angle_color_disable", o.angle_color_disable ? 1 : 0);
+    i1("_grid_disable", o.grid_disable ? 1 : 0);
+    i1("_black_border_disable", o.black_border_disable ? 1 : 0);
+    i1("_darken_by_distance", o.darken_by_distance ? 1 : 0);
     i1("_teleport_external_ray", 0);
     return out;
 }
@@ -480,25 +490,39 @@ extern "C" int ptl_scene_texture(ptl_scene* s, int index, char* name, size_t nam
     return PTL_OK;
 }
 
+// The kinds of build a renderer tells apart.  Specialised: compiles in something a later state can invalidate -- values (bits 0 / 2 / 3) or, with
+// PTL_FLAG_SPECIALIZE_PATTERNS, only what survives while values move (the zero patterns of the matrices, the mode switches, the scene's switches).
+constexpr unsigned kSpecialisation = PTL_FLAG_SPECIALIZE_INTS | PTL_FLAG_SPECIALIZE_ALL | PTL_FLAG_SPECIALIZE_STATIC | PTL_FLAG_SPECIALIZE_PATTERNS;
+static bool specialised(unsigned flags) { return (flags & kSpecialisation) != 0; }
+// the current values as literals: every change of the scene is a rebuild
+static bool bakes_values(unsigned flags) { return (flags & (PTL_FLAG_SPECIALIZE_INTS | PTL_FLAG_SPECIALIZE_ALL)) != 0; }
+// what stays constant while a clip plays: valid while every compiled-in value and zero pattern still holds (checked before every draw)
+static bool clip_constant(unsigned flags) {
+    return (flags & (PTL_FLAG_SPECIALIZE_STATIC | PTL_FLAG_SPECIALIZE_PATTERNS)) != 0 && !bakes_values(flags);
+}
+// PTL_FLAG_ASYNC_REJIT on a specialised renderer with a device: rebuilds are compiled by a worker thread (ptl_renderer::Job)
+static bool async_rejit(const ptl_renderer& r) { return (r.flags & PTL_FLAG_ASYNC_REJIT) != 0 && specialised(r.flags) && r.device >= 0; }
+
 static KernelOptions options_from_flags(unsigned flags) {
+    auto on = [flags](unsigned bit) { return (flags & bit) != 0; };
     KernelOptions o;
-    o.specialize_ints = (flags & 1u) != 0;
-    o.count_segments = (flags & 2u) != 0;
-    o.specialize_all = (flags & 4u) != 0;
-    o.anaglyph = (flags & 16u) != 0;
-    o.specialize_static = (flags & 8u) != 0;
-    o.specialize_static_ints = (flags & (1u << 20)) != 0;  // PTL_FLAG_SPECIALIZE_PATTERNS: + the scene's own switches (Bool / Int uniforms that read no per-frame input)
-    o.derived_uniforms = (flags & 32u) == 0;  // PTL_FLAG_NO_DERIVED_UNIFORMS: the plain plane tests (A/B measurements, tests)
-    o.fast_math = (flags & 64u) != 0;         // PTL_FLAG_FAST_MATH: tolerance mode
-    o.exact_cr = (flags & 16384u) != 0;       // PTL_FLAG_EXACT_CR: numerics contract 1 (IEEE / and sqrt on every input), `--exact-cr`
+    o.specialize_ints = on(PTL_FLAG_SPECIALIZE_INTS);
+    o.count_segments = on(PTL_FLAG_COUNT_SEGMENTS);
+    o.specialize_all = on(PTL_FLAG_SPECIALIZE_ALL);
+    o.anaglyph = on(PTL_FLAG_ANAGLYPH);
+    o.specialize_static = on(PTL_FLAG_SPECIALIZE_STATIC);
+    o.specialize_static_ints = on(PTL_FLAG_SPECIALIZE_PATTERNS);  // + the scene's own switches (Bool / Int uniforms that read no per-frame input)
+    o.derived_uniforms = !on(PTL_FLAG_NO_DERIVED_UNIFORMS);  // the plain plane tests (A/B measurements, tests)
+    o.fast_math = on(PTL_FLAG_FAST_MATH);  // tolerance mode
+    o.exact_cr = on(PTL_FLAG_EXACT_CR);  // numerics contract 1 (IEEE / and sqrt on every input), `--exact-cr`
     // PTL_FLAG_QUICK_JIT: -O1 instead of -O3 (a build that is wanted now and used briefly).  Not for a clip-constant build (bit 3 /
     // "specialize_static"): that one is asked for because many frames will run on it, so it keeps the full optimisation level
-    o.quick_jit = (flags & 262144u) != 0 && !o.specialize_static;
+    o.quick_jit = on(PTL_FLAG_QUICK_JIT) && !o.specialize_static;
     // zero patterns of the matrices that stay run-time values: with any specialisation (the un-specialised kernel has to be valid for every
     // state of the scene -- the background re-JIT draws with it meanwhile); PTL_FLAG_NO_ZERO_MASKS (bit 19) for A/B measurements and tests
-    o.mask_zero_elements = (flags & (13u | (1u << 20))) != 0 && (flags & 524288u) == 0;
-    o.slices_entry = (flags & (1u << 22)) != 0;  // PTL_FLAG_SLICES: the render entry reads its uniform block from a buffer of blocks, one per blockIdx.z
-    o.bound_snippets = (flags & (1u << 21)) != 0;  // PTL_FLAG_BOUNDED_SNIPPETS: scene_intersect first, its distance bounds the intersection-material snippets (opt-in: measured, no gain)
+    o.mask_zero_elements = specialised(flags) && !on(PTL_FLAG_NO_ZERO_MASKS);
+    o.slices_entry = on(PTL_FLAG_SLICES);  // the render entry reads its uniform block from a buffer of blocks, one per blockIdx.z
+    o.bound_snippets = on(PTL_FLAG_BOUNDED_SNIPPETS);  // scene_intersect first, its distance bounds the intersection-material snippets (opt-in: measured, no gain)
     // Round 6: the first-trip forms -- a second copy of scene_intersect and of every intersection-material snippet for the trip on which all rays of a
     // wave still start at the camera -- are OPT-IN IN THE UN-SPECIALISED KERNEL (bit 24, PTL_FLAG_KEEP_TRANSFORM_DODGES) and stay the default of the
     // specialised builds (where a kernel with affine rays drops the snippet copies by itself, codegen.cpp).  Round 3 measured +4 % for them on kernels
@@ -506,20 +530,20 @@ static KernelOptions options_from_flags(unsigned flags) {
     // 0.434, mobius 1.108 -> 1.046, monoportal equal (profiles/r06/ab_unspec_code_size*.jsonl) -- and that kernel is 12 535 instead of 17 090
     // instructions, compiles in 3.5 s instead of 15.8 on this container's cores and needs no occupancy retry; the specialised builds that keep run-time
     // matrices (patterns, Int-baked) still gain 1 ... 4 % from the plane form (profiles/r06/ab_first_trip_planes.jsonl).  Identical frames either way.
-    const bool first_trip_forms = (flags & (1u << 24)) != 0 || (flags & (13u | (1u << 20))) != 0;
-    o.first_trip_planes = first_trip_forms && (flags & 65536u) == 0;   // PTL_FLAG_NO_FIRST_TRIP_PLANES: one scene_intersect for every trip
-    if (const char* ab = std::getenv("PTL_AB_FIRST_TRIP_PLANES"); ab && (ab[0] == '0' || ab[0] == '1')) o.first_trip_planes = ab[0] == '1' && (flags & 65536u) == 0;  // (A/B hook)
+    const bool first_trip_forms = on(PTL_FLAG_KEEP_TRANSFORM_DODGES) || specialised(flags);
+    o.first_trip_planes = first_trip_forms && !on(PTL_FLAG_NO_FIRST_TRIP_PLANES);  // one scene_intersect for every trip
+    if (const char* ab = std::getenv("PTL_AB_FIRST_TRIP_PLANES"); ab && (ab[0] == '0' || ab[0] == '1')) o.first_trip_planes = ab[0] == '1' && !on(PTL_FLAG_NO_FIRST_TRIP_PLANES);  // (A/B hook)
     // PTL_FLAG_NO_UNROLL: keep snippet loops with baked bounds as loops (A/B measurements).  The quick build keeps them too: unrolling
     // is half of its hiprtc time for the headline scene (3.4 -> 1.8 s on this container's cores) and buys 0.05 ms of kernel
-    o.unroll_baked_loops = (flags & 32768u) == 0 && !o.quick_jit;
-    o.keep_transform_dodges = (flags & (1u << 24)) != 0;  // PTL_FLAG_KEEP_TRANSFORM_DODGES: deferred updates + first-trip snippet copies also with affine rays (A/B)
+    o.unroll_baked_loops = !on(PTL_FLAG_NO_UNROLL) && !o.quick_jit;
+    o.keep_transform_dodges = on(PTL_FLAG_KEEP_TRANSFORM_DODGES);  // deferred updates + first-trip snippet copies also with affine rays (A/B)
     // the Simple materials' literals from a table instead of one inlined material_simple2 per material (A/B: measured slower, off by default -- codegen.h):
     // PTL_FLAG_MATERIAL_TABLE_LDS (bit 26) staged in LDS, PTL_FLAG_MATERIAL_TABLE_SCALAR (bit 27) in constant memory behind scalar loads
-    o.material_table = (flags & (1u << 27)) != 0 ? 2 : ((flags & (1u << 26)) != 0 ? 1 : 0);
-    o.check_affine = (flags & (1u << 25)) != 0;   // PTL_FLAG_CHECK_AFFINE: general products, and `segments` counts the ray halves whose w is not 1 / 0
-    o.affine_rays = (flags & (1u << 23)) == 0;    // PTL_FLAG_NO_AFFINE_RAYS: matrix-times-ray products never assume o.w = 1 / d.w = 0 (A/B measurements, tests)
-    o.first_trip = first_trip_forms && (flags & 8192u) == 0;  // PTL_FLAG_NO_FIRST_TRIP: no first-trip copies of the intersection-material snippets
-    o.hoist_uniform_work = (flags & 4096u) == 0;  // PTL_FLAG_NO_UNIFORM_HOIST: snippets evaluate their uniform-only expressions per ray
+    o.material_table = on(PTL_FLAG_MATERIAL_TABLE_SCALAR) ? 2 : (on(PTL_FLAG_MATERIAL_TABLE_LDS) ? 1 : 0);
+    o.check_affine = on(PTL_FLAG_CHECK_AFFINE);  // general products, and `segments` counts the ray halves whose w is not 1 / 0
+    o.affine_rays = !on(PTL_FLAG_NO_AFFINE_RAYS);  // matrix-times-ray products never assume o.w = 1 / d.w = 0 (A/B measurements, tests)
+    o.first_trip = first_trip_forms && !on(PTL_FLAG_NO_FIRST_TRIP);  // no first-trip copies of the intersection-material snippets
+    o.hoist_uniform_work = !on(PTL_FLAG_NO_UNIFORM_HOIST);  // snippets evaluate their uniform-only expressions per ray
     return o;
 }
 
@@ -529,21 +553,23 @@ static std::map<std::string, int> mode_switches(const ptl_renderer& r) {
     // `teleport_light_u` compiled in as well: 10 % fewer static instructions (every scalar load with its address arithmetic and wait inside the headline's ~20
     // inlined portal tests gone), 0.1873 -> 0.1869 ms: nothing -- the kernel is bound by VALU issue, scalar work hides behind it.  profiles/r06/README.md)
     return {{"_use_panini_projection", r.cam.use_panini_projection ? 1 : 0}, {"_use_360_camera", r.cam.use_360_camera ? 1 : 0},
-            {"_use_180_camera", r.cam.use_180_camera ? 1 : 0},               {"_draw_depth_map", r.draw_depth_map ? 1 : 0},
-            {"_draw_anaglyph", r.draw_anaglyph ? 1 : 0},                     {"_draw_side_by_side", r.draw_side_by_side ? 1 : 0}};
+            {"_use_180_camera", r.cam.use_180_camera ? 1 : 0},               {"_draw_depth_map", r.opt.draw_depth_map ? 1 : 0},
+            {"_draw_anaglyph", r.opt.draw_anaglyph ? 1 : 0},                 {"_draw_side_by_side", r.opt.draw_side_by_side ? 1 : 0}};
 }
 
-static void refresh_generated(ptl_scene* s, unsigned flags, const std::set<std::string>* keep_dynamic = nullptr, const std::map<std::string, int>* switches = nullptr,
-                              const std::set<std::string>* keep_unmasked = nullptr, bool full_chains = false, bool no_affine = false) {
+// Generates the scene's source for `flags` into s->last; a renderer's build also passes what its stage has learnt and its mode switches.
+static void refresh_generated(ptl_scene* s, unsigned flags, const StageMemory* stage = nullptr, const std::map<std::string, int>* switches = nullptr) {
     KernelOptions opts = options_from_flags(flags);
-    opts.full_chains = full_chains;
-    if (no_affine) opts.affine_rays = false;
     opts.mask_cache = &s->mask_cache;
-    if (keep_dynamic) opts.keep_dynamic = *keep_dynamic;
-    if (keep_unmasked) opts.keep_unmasked = *keep_unmasked;
-    if (switches && (flags & (13u | (1u << 20))) != 0) opts.baked_options = *switches;
+    if (stage) {
+        opts.full_chains = stage->full_chains;
+        if (stage->no_affine) opts.affine_rays = false;
+        opts.keep_dynamic = stage->keep_dynamic;
+        opts.keep_unmasked = stage->keep_unmasked;
+    }
+    if (switches && specialised(flags)) opts.baked_options = *switches;
     CodegenFlags cg;
-    cg.defer_loop_updates = (flags & 128u) == 0;  // PTL_FLAG_NO_DEFERRED_UPDATES: the snippets exactly as written (A/B measurements, tests)
+    cg.defer_loop_updates = (flags & PTL_FLAG_NO_DEFERRED_UPDATES) == 0;  // the snippets exactly as written (A/B measurements, tests)
     s->last = generate_kernel_source(*s->scene, cg, opts);
     s->desc_names.clear();
     s->descs.clear();
@@ -694,12 +720,6 @@ int update_videos(ptl_renderer* r) {
 
 }  // namespace
 
-static constexpr unsigned kAsyncRejit = 1u << 17;  // PTL_FLAG_ASYNC_REJIT
-// PTL_FLAG_SPECIALIZE_PATTERNS (bit 20): no VALUE of the scene is compiled in, only what survives while values move -- the zero patterns of
-// the matrices and the renderer's mode switches.  kSpecialised = the builds that compile in something a later state can invalidate.
-static constexpr unsigned kPatterns = 1u << 20;
-static constexpr unsigned kSpecialised = 13u | kPatterns;
-
 // reload_textures (main.rs:1066-1083) into a freshly built kernel
 static int bind_textures(ptl_renderer* r, ptl_kernel* k) {
     if (r->device < 0) return PTL_OK;
@@ -707,16 +727,15 @@ static int bind_textures(ptl_renderer* r, ptl_kernel* k) {
         std::string path = r->asset_root.empty() ? t.path : r->asset_root + "/" + t.path;
         uint8_t* px = nullptr;
         int w = 0, h = 0;
-        if (ptl_png_read(path.c_str(), &px, &w, &h) != PTL_OK) continue;  // like the reference: the sampler stays unbound (see build_kernel)
+        // like the reference (data.texture_errors, src/main.rs:1082-1084): keep going, the sampler stays unbound and reads as (0, 0, 0, 1);
+        // the message remains available through ptl_last_error()
+        if (ptl_png_read(path.c_str(), &px, &w, &h) != PTL_OK) continue;
         int trc = ptl_kernel_set_texture(k, (t.name + "_tex").c_str(), px, w, h);
         std::free(px);
         if (trc < 0) return trc;
     }
     return PTL_OK;
 }
-
-// the kernel the draws use from now on: a different one starts from a blank uniform block and blank samplers
-static int activate_kernel(ptl_renderer* r, ptl_kernel* k);
 
 // The renderer's kernels are built in two halves (kernel.cpp `ptl_kernel::split`): the render module now, the camera-teleport module when a
 // query first asks for it -- a fifth of every build that a still camera never needs.  PTL_ONE_MODULE=1: one module with every entry (A/B).
@@ -729,7 +748,7 @@ static bool split_builds() {
 // __launch_bounds__(256, waves)) and the split.
 static std::vector<std::string> build_defines(const GeneratedKernel&, unsigned flags) {
     std::vector<std::string> d;
-    unsigned waves = (flags >> 8) & 0xFu;
+    unsigned waves = (flags >> PTL_FLAG_WAVES_SHIFT) & 0xFu;
     if (waves) d.push_back("PTL_WAVES_PER_EU=" + std::to_string(waves));
     if (split_builds()) d.push_back("PTL_RENDER_MODULE");
     return d;
@@ -827,74 +846,143 @@ static void drop_staged_slices(ptl_renderer* r) {  // forget what was staged (af
     r->parked_kernels.clear();
 }
 
-static int build_kernel(ptl_renderer* r, char* log, size_t log_cap) {
-    ptl_scene* s = r->owner;
-    if (!(r->kernel_stage == r->scene->current_stage)) r->keep_dynamic.clear();  // another stage / clip: judge afresh what is constant
-    if (!(r->kernel_stage == r->scene->current_stage)) r->keep_unmasked.clear();
-    if (!(r->kernel_stage == r->scene->current_stage)) r->full_chains = false;
-    if (!(r->kernel_stage == r->scene->current_stage)) {
-        r->no_affine = !camera_is_affine(*r) || r->affine_violations_seen > 0;
-        r->affine_returns = 0;
-    } else if (r->no_affine && r->affine_violations_seen == 0 && r->affine_returns < 1 && camera_is_affine(*r) && !r->no_affine_just_set) {
+// Zero patterns compiled into the current kernel (r->masked) against the values a draw is about to upload: a matrix with a non-zero where
+// the pattern says zero is demoted (keep_unmasked) and reported.
+static bool zero_patterns_broken(ptl_renderer* r, const std::vector<UniformUpload>& values) {
+    StageMemory& m = r->stage;
+    bool broken = false;
+    // a kernel with shortened products is exact for finite vectors: a matrix that got infinite elements, or NaN beside numbers, since the kernel was generated
+    // (the generator checks the values it sees, codegen.cpp `full_chains`) asks for the full chains from here on
+    if (r->shortened && !m.full_chains)
+        for (const UniformUpload& v : values)
+            if (v.type == UniformType::Mat4 && matrix_breaks_short_chains(v.f)) m.full_chains = broken = true;
+    // ... and a kernel with affine rays is exact while every scene matrix maps w = 1 to 1 and w = 0 to 0 (or is NaN throughout: a switched-off object)
+    if (r->affine_rays && !m.no_affine)
+        for (const UniformUpload& v : values) {
+            if (v.type != UniformType::Mat4 || matrix_is_affine(v.f)) continue;
+            bool all_nan = true;
+            for (int k = 0; k < 16; ++k) all_nan = all_nan && std::isnan(v.f[k]);
+            if (!all_nan) m.no_affine = m.no_affine_just_set = broken = true;
+        }
+    for (auto& [name, mask] : r->masked)
+        for (const UniformUpload& v : values) {
+            if (v.name != name || v.type != UniformType::Mat4) continue;
+            if (!pattern_holds(mask, v.f)) {  // a non-zero where the kernel skips a term, or a +-1 the kernel has as a literal and the matrix no longer holds
+                m.keep_unmasked.insert(name);
+                broken = true;
+            }
+            break;
+        }
+    // one broken pattern says the probes did not see this clip's motion: every mask goes, so that a clip costs at most ONE extra rebuild
+    if (!m.keep_unmasked.empty())
+        for (auto& mk : r->masked) m.keep_unmasked.insert(mk.first);
+    return broken;
+}
+
+// Clip-constant values compiled into the current kernel (r->baked) against the values a draw is about to upload: one that moved after all is
+// demoted to a run-time uniform (keep_dynamic).
+static bool baked_values_moved(ptl_renderer* r, const std::vector<UniformUpload>& values) {
+    bool moved = false;
+    size_t at = 0;
+    for (const UniformUpload& b : r->baked) {
+        while (at < values.size() && values[at].name != b.name) ++at;  // same order as at generation time
+        if (at == values.size()) return true;
+        if (!values[at].same_value(b)) {
+            r->stage.keep_dynamic.insert(b.name);
+            moved = true;
+        }
+    }
+    return moved;
+}
+
+enum class Rebuild { none, quiet, counted };  // (quiet: a rebuild that ptl_renderer_rejit_count does not count)
+
+// The one answer to "does the current kernel still fit the renderer's state, and if not, what replaces it?", for the draws (with and without
+// PTL_FLAG_ASYNC_REJIT), ptl_renderer_kernel and the synchronous rebuilds (rebuild_now: `forced`, the triggers are not looked at).  The scene's
+// values are examined only when the caller passes them (`values`: what a draw is about to upload).  When a rebuild is due, the specialised
+// source of the current state is generated and r->want holds its build; the caller compiles it (build_kernel, or the worker thread).
+static Rebuild decide_rebuild(ptl_renderer* r, const std::vector<UniformUpload>* values, Rebuild forced = Rebuild::none) {
+    StageMemory& m = r->stage;
+    Rebuild why = forced;
+    if (why == Rebuild::none) {
+        // the camera went through something that is not an affine map: the kernel's w = 1 / w = 0 no longer holds for primary rays
+        const bool left_affine_maps = r->affine_rays && !m.no_affine && !camera_is_affine(*r);
+        if (left_affine_maps) m.no_affine = m.no_affine_just_set = true;
+        if (left_affine_maps || (specialised(r->flags) && mode_switches(*r) != r->kernel_switches)) {
+            why = Rebuild::counted;  // (a camera model / output mode was switched: the kernel has the old one compiled in and the new one compiled out)
+        } else if (values && bakes_values(r->flags) && r->kernel_scene_version != r->scene->version) {
+            why = Rebuild::quiet;  // values are baked in and the scene changed (cached by source hash)
+        } else if (values && clip_constant(r->flags)) {
+            // the kernel stays valid as long as every compiled-in value and zero pattern still holds; what moved after all is demoted
+            const bool stage_changed = !(r->kernel_stage == r->scene->current_stage);
+            const bool moved = baked_values_moved(r, *values);
+            const bool broken = zero_patterns_broken(r, *values);  // an animated matrix left the zero pattern its products were shortened for
+            if (stage_changed || moved || broken) why = Rebuild::counted;
+        }
+    }
+    if (why == Rebuild::none) return why;
+    const bool camera_affine = camera_is_affine(*r);
+    if (!(r->kernel_stage == r->scene->current_stage)) {  // another stage / clip: judge afresh what is constant
+        m = StageMemory{};
+        m.no_affine = !camera_affine || r->affine_violations_seen > 0;
+    } else if (m.no_affine && r->affine_violations_seen == 0 && m.affine_returns < 1 && camera_affine && !m.no_affine_just_set) {
         // one transient non-affine camera or matrix state cost the rest of the stage ~16 % of kernel time.  A rebuild that happens for another
         // reason may return to affine rays ONCE per stage when the camera is affine again (the generator re-checks the scene's matrices itself); a second
-        // break keeps them off, so a state that flickers cannot rebuild per frame.  A violation the checking build counted stays off for good.
-        r->no_affine = false;
-        ++r->affine_returns;
+        // break keeps them off, so a state that flickers cannot rebuild per frame.  A violation the checking build counted keeps them off for good.
+        m.no_affine = false;
+        ++m.affine_returns;
     }
-    r->no_affine_just_set = false;
+    m.no_affine = m.no_affine || !camera_affine;  // (no build assumes w = 1 / 0 of a camera that does not keep them)
+    m.no_affine_just_set = false;
     r->kernel_switches = mode_switches(*r);
-    refresh_generated(s, r->flags, &r->keep_dynamic, &r->kernel_switches, &r->keep_unmasked, r->full_chains, r->no_affine);
+    ptl_scene* s = r->owner;
+    refresh_generated(s, r->flags, &m, &r->kernel_switches);
     r->baked = s->last.baked;
     r->masked = s->last.masked;
     r->affine_rays = s->last.affine_rays;
     r->shortened = !s->last.full_chains && (s->last.masked.size() > 0 || std::find(s->last.defines.begin(), s->last.defines.end(), "PTL_DROP_ZERO_TERMS") != s->last.defines.end());
     r->kernel_stage = r->scene->current_stage;
-    if (r->kernel && s->last.source == r->kernel_source) {  // nothing baked in changed
-        r->kernel_scene_version = r->scene->version;
-        return PTL_OK;
-    }
-    const std::vector<std::string> extra = build_defines(s->last, r->flags);  // (not into s->last.defines: ptl_scene_generated_defines describes the source, not this build)
-    std::vector<const char*> defines;
-    for (auto& d : s->last.defines) defines.push_back(d.c_str());
-    for (auto& d : extra) defines.push_back(d.c_str());
-    ptl_kernel* k = nullptr;
-    int rc = ptl_kernel_compile(r->device, s->last.source.c_str(), s->descs.data(), (int)s->descs.size(), s->last.uniform_block_size, defines.data(),
-                                (int)defines.size(), &k, log, log_cap);
-    if (rc != PTL_OK) return rc;
-    if (r->device >= 0) {  // reload_textures (main.rs:1066-1083)
-        for (const Texture& t : r->scene->textures) {
-            std::string path = r->asset_root.empty() ? t.path : r->asset_root + "/" + t.path;
-            uint8_t* px = nullptr;
-            int w = 0, h = 0;
-            if (ptl_png_read(path.c_str(), &px, &w, &h) != PTL_OK) {
-                // like the reference (data.texture_errors, src/main.rs:1082-1084): keep going, the sampler stays
-                // unbound and reads as (0, 0, 0, 1); the message remains available through ptl_last_error()
-                continue;
-            }
-            int trc = ptl_kernel_set_texture(k, (t.name + "_tex").c_str(), px, w, h);
-            std::free(px);
-            if (trc < 0) {
-                ptl_kernel_destroy(k);
-                return trc;
-            }
-        }
-    }
-    if (r->lanes_of == r->kernel) drop_lane_clones(r);
-    wait_for_lanes(r);
-    retire_kernel(r, r->kernel);
+    r->want = snapshot_build(s, r->flags);
+    return why;
+}
+
+// The kernel the draws use from now on: a different one starts from a blank uniform block and blank samplers.
+static int activate_kernel(ptl_renderer* r, ptl_kernel* k) {
+    if (r->kernel == k) return PTL_OK;
     r->kernel = k;
-    r->kernel_source = s->last.source;
-    r->kernel_scene_version = r->scene->version;
-    r->uploaded_scene = 0;  // a fresh uniform block: upload everything again
+    r->uploaded_scene = 0;  // upload everything again ...
     r->uploaded_options = 0;
-    for (auto& v : r->videos) v.bound = -1;  // ... and fresh samplers: bind the current video frames again
+    r->uploaded_w = r->uploaded_h = -1;
+    for (auto& v : r->videos) v.bound = -1;  // ... and bind the current video frames again
     return update_videos(r);
 }
 
-// Background re-JIT bookkeeping around a synchronous build_kernel() (renderer creation; a switch of the specialisation bits):
-// `kernel` aliases `spec_kernel` or `dyn_kernel` in that mode, so the pair is dropped as a whole before the rebuild (the worker joined
-// first) and the freshly built specialised kernel seeds it again afterwards.
+// The only place where a newly built kernel `k` replaces one of the renderer's: `old` -- the active kernel, or with PTL_FLAG_ASYNC_REJIT the
+// specialised one that an adopted build supersedes -- loses its lane clones and is retired (parked while a staged slice names it).
+static int install_kernel(ptl_renderer* r, ptl_kernel* k, ptl_kernel* old) {
+    if (r->lanes_of == old) drop_lane_clones(r);
+    wait_for_lanes(r);
+    retire_kernel(r, old);
+    return activate_kernel(r, k);
+}
+
+// compile + load textures, the JIT step of SceneRenderer::new (main.rs:946-1010,1066-1083): r->want, now, on the calling thread
+static int build_kernel(ptl_renderer* r, char* log, size_t log_cap) {
+    if (r->kernel && r->want.source == r->kernel_source) {  // nothing compiled in changed
+        r->kernel_scene_version = r->scene->version;
+        return PTL_OK;
+    }
+    ptl_kernel* k = nullptr;
+    int rc = compile_build(r->want, r->device, nullptr, &k, log, log_cap);
+    if (rc == PTL_OK && (rc = bind_textures(r, k)) < 0) ptl_kernel_destroy(k);
+    if (rc != PTL_OK) return rc;
+    r->kernel_source = r->want.source;
+    r->kernel_scene_version = r->scene->version;
+    return install_kernel(r, k, r->kernel);
+}
+
+// With PTL_FLAG_ASYNC_REJIT `kernel` aliases `spec_kernel` or `dyn_kernel`: before a synchronous rebuild the pair is dropped as a whole (the
+// worker joined first), and the freshly built specialised kernel seeds it again afterwards.
 static void drop_async_kernels(ptl_renderer* r) {
     if (r->job) {
         if (r->job->worker.joinable()) r->job->worker.join();
@@ -913,11 +1001,27 @@ static void drop_async_kernels(ptl_renderer* r) {
     r->want = ptl_renderer::Build{};
 }
 static void seed_async_kernels(ptl_renderer* r) {
-    if ((r->flags & kAsyncRejit) != 0 && (r->flags & kSpecialised) != 0 && r->device >= 0) {  // the first kernel is the specialised one of this state
+    if (async_rejit(*r)) {  // the first kernel is the specialised one of this state
         r->spec_kernel = r->kernel;
         r->spec_source = r->kernel_source;
-        r->want = snapshot_build(r->owner, r->flags);
     }
+}
+
+// A rebuild that is due, compiled on the calling thread: the draws of a renderer without PTL_FLAG_ASYNC_REJIT, ptl_renderer_kernel, rebuild_now.
+static int update_kernel(ptl_renderer* r, const std::vector<UniformUpload>* values, Rebuild forced = Rebuild::none, char* log = nullptr, size_t log_cap = 0) {
+    const Rebuild why = decide_rebuild(r, values, forced);
+    if (why == Rebuild::none) return PTL_OK;
+    int rc = build_kernel(r, log, log_cap);
+    if (rc == PTL_OK && why == Rebuild::counted) ++r->rejit_count;
+    return rc;
+}
+
+// A rebuild on the calling thread also under PTL_FLAG_ASYNC_REJIT: renderer creation, a switch of the specialisation bits, the check-affine belt.
+static int rebuild_now(ptl_renderer* r, Rebuild why, char* log, size_t log_cap) {
+    drop_async_kernels(r);
+    if (int rc = update_kernel(r, nullptr, why, log, log_cap); rc != PTL_OK) return rc;
+    seed_async_kernels(r);
+    return PTL_OK;
 }
 
 static int set_plain_option(ptl_renderer* r, const std::string& n, double v);
@@ -944,16 +1048,15 @@ extern "C" int ptl_renderer_create_with_options(ptl_scene* s, int device, const 
                 return (int)PTL_ERR_INVALID;
             }
         }
-        int rc = build_kernel(r.get(), log, log_cap);
+        int rc = rebuild_now(r.get(), Rebuild::quiet, log, log_cap);
         if (rc != PTL_OK) return rc;
-        seed_async_kernels(r.get());
         // cam.set_cam(scene.cam); offset_after_material from the scene (main.rs:1057-1059)
         const CamSettings& c = s->scene->cam;
         r->cam.look_at = c.look_at;
         r->cam.alpha = c.alpha;
         r->cam.beta = c.beta;
         r->cam.r = c.r;
-        r->offset_after_material = c.offset_after_material;
+        r->opt.offset_after_material = c.offset_after_material;
         r->cam.prev_cam_pos = cam_pos(r->cam);  // main.rs:1058
         r->original_cam = calculated_of(r->cam);  // render_frame inserts "OriginalCam" up front (main.rs:2893-2896)
         *out = r.release();
@@ -972,32 +1075,32 @@ static int set_plain_option(ptl_renderer* r, const std::string& n, double v) {
         r->check_affine_on_new_source = b;
         return PTL_OK;
     }
-    if (n == "render_depth") r->render_depth = (int)v;
-    else if (n == "aa_count") r->aa_count = (int)v;
-    else if (n == "aa_start") r->aa_start = (int)v;
+    if (n == "render_depth") r->opt.render_depth = (int)v;
+    else if (n == "aa_count") r->opt.aa_count = (int)v;
+    else if (n == "aa_start") r->opt.aa_start = (int)v;
     else if (n == "view_angle") r->cam.view_angle = v;
     else if (n == "use_panini_projection") r->cam.use_panini_projection = b;
     else if (n == "panini_param") r->cam.panini_param = v;
     else if (n == "use_360_camera") r->cam.use_360_camera = b;
     else if (n == "use_180_camera") r->cam.use_180_camera = b;
-    else if (n == "darken_by_distance") r->darken_by_distance = b;
-    else if (n == "gray_t_start") r->gray_t_start = v;
-    else if (n == "gray_t_size") r->gray_t_size = v;
-    else if (n == "draw_depth_map") r->draw_depth_map = b;
-    else if (n == "depth_map_min") r->depth_map_min = v;
-    else if (n == "depth_map_max") r->depth_map_max = v;
-    else if (n == "angle_color_disable") r->angle_color_disable = b;
-    else if (n == "grid_disable") r->grid_disable = b;
-    else if (n == "black_border_disable") r->black_border_disable = b;
-    else if (n == "offset_after_material") r->offset_after_material = v;
-    else if (n == "draw_side_by_side") r->draw_side_by_side = b;
+    else if (n == "darken_by_distance") r->opt.darken_by_distance = b;
+    else if (n == "gray_t_start") r->opt.gray_t_start = v;
+    else if (n == "gray_t_size") r->opt.gray_t_size = v;
+    else if (n == "draw_depth_map") r->opt.draw_depth_map = b;
+    else if (n == "depth_map_min") r->opt.depth_map_min = v;
+    else if (n == "depth_map_max") r->opt.depth_map_max = v;
+    else if (n == "angle_color_disable") r->opt.angle_color_disable = b;
+    else if (n == "grid_disable") r->opt.grid_disable = b;
+    else if (n == "black_border_disable") r->opt.black_border_disable = b;
+    else if (n == "offset_after_material") r->opt.offset_after_material = v;
+    else if (n == "draw_side_by_side") r->opt.draw_side_by_side = b;
     else if (n == "in_subspace") r->cam.in_subspace = b;
-    else if (n == "draw_anaglyph") r->draw_anaglyph = b;
-    else if (n == "anaglyph_mode") r->anaglyph_mode = b;
-    else if (n == "anaglyph_p") r->anaglyph_p = v;
-    else if (n == "anaglyph_q") r->anaglyph_q = v;
-    else if (n == "eye_distance") r->eye_distance = v;
-    else if (n == "swap_eyes") r->swap_eyes = b;
+    else if (n == "draw_anaglyph") r->opt.draw_anaglyph = b;
+    else if (n == "anaglyph_mode") r->opt.anaglyph_mode = b;
+    else if (n == "anaglyph_p") r->opt.anaglyph_p = v;
+    else if (n == "anaglyph_q") r->opt.anaglyph_q = v;
+    else if (n == "eye_distance") r->opt.eye_distance = v;
+    else if (n == "swap_eyes") r->opt.swap_eyes = b;
     else if (n == "allow_teleport") r->cam.allow_teleport = b;    // RotateAroundCam toggles, src/main.rs:136-137
     else if (n == "stop_at_objects") r->cam.stop_at_objects = b;
     else if (n == "concurrent_draws") {  // 1 = off (the default); K <= 8 kernel instances on K internal streams (ptl_renderer::Lane)
@@ -1027,18 +1130,14 @@ extern "C" int ptl_renderer_set_option(ptl_renderer* r, const char* name, double
     if (!r || !name) return PTL_ERR_INVALID;
     std::string n = name;
     if (n == "specialize_static") {  // switch clip-constant specialisation (flags bit3) on or off for what follows
-        unsigned want = v > 0.5 ? (r->flags | 8u) : (r->flags & ~8u);
+        unsigned want = v > 0.5 ? (r->flags | PTL_FLAG_SPECIALIZE_STATIC) : (r->flags & ~PTL_FLAG_SPECIALIZE_STATIC);
         if (want == r->flags) return PTL_OK;
         return guarded([&] {
-            // With PTL_FLAG_ASYNC_REJIT `kernel` is one of spec_kernel / dyn_kernel and a worker may be compiling for the old flags: the
-            // pair is dropped as a whole (build_kernel would free only the alias), rebuilt synchronously like at creation, and re-seeded.
-            const bool async = (r->flags & kAsyncRejit) != 0 && r->device >= 0;
-            if (async) drop_async_kernels(r);
+            // (with PTL_FLAG_ASYNC_REJIT a worker may be compiling for the old flags: rebuilt synchronously like at creation)
             r->flags = want;
-            r->keep_dynamic.clear();
-            int rc = build_kernel(r, nullptr, 0);
+            r->stage.keep_dynamic.clear();
+            int rc = rebuild_now(r, Rebuild::quiet, nullptr, 0);
             if (rc != PTL_OK) return rc;
-            if (async) seed_async_kernels(r);
             ++r->options_version;
             return (int)PTL_OK;
         });
@@ -1114,85 +1213,15 @@ extern "C" int ptl_renderer_uniform_value(ptl_renderer* r, int width, int height
     });
 }
 
-// Zero patterns compiled into the current kernel (r->masked) against the values a draw is about to upload: a matrix with a non-zero where
-// the pattern says zero is demoted (keep_unmasked) and reported.
-static bool zero_patterns_broken(ptl_renderer* r, const std::vector<UniformUpload>& values) {
-    bool broken = false;
-    // a kernel with shortened products is exact for finite vectors: a matrix that got infinite elements, or NaN beside numbers, since the kernel was generated
-    // (the generator checks the values it sees, codegen.cpp `full_chains`) asks for the full chains from here on
-    if (r->shortened && !r->full_chains)
-        for (const UniformUpload& v : values)
-            if (v.type == UniformType::Mat4 && matrix_breaks_short_chains(v.f)) r->full_chains = broken = true;
-    // ... and a kernel with affine rays is exact while every scene matrix maps w = 1 to 1 and w = 0 to 0 (or is NaN throughout: a switched-off object)
-    if (r->affine_rays && !r->no_affine)
-        for (const UniformUpload& v : values) {
-            if (v.type != UniformType::Mat4 || matrix_is_affine(v.f)) continue;
-            bool all_nan = true;
-            for (int k = 0; k < 16; ++k) all_nan = all_nan && std::isnan(v.f[k]);
-            if (!all_nan) r->no_affine = r->no_affine_just_set = broken = true;
-        }
-    for (auto& [name, mask] : r->masked)
-        for (const UniformUpload& v : values) {
-            if (v.name != name || v.type != UniformType::Mat4) continue;
-            if (!pattern_holds(mask, v.f)) {  // a non-zero where the kernel skips a term, or a +-1 the kernel has as a literal and the matrix no longer holds
-                r->keep_unmasked.insert(name);
-                broken = true;
-            }
-            break;
-        }
-    // one broken pattern says the probes did not see this clip's motion: every mask goes, so that a clip costs at most ONE extra rebuild
-    if (!r->keep_unmasked.empty())
-        for (auto& m : r->masked) r->keep_unmasked.insert(m.first);
-    return broken;
-}
-
-static int activate_kernel(ptl_renderer* r, ptl_kernel* k) {
-    if (r->kernel == k) return PTL_OK;
-    r->kernel = k;
-    r->uploaded_scene = 0;
-    r->uploaded_options = 0;
-    r->uploaded_w = r->uploaded_h = -1;
-    for (auto& v : r->videos) v.bound = -1;
-    return update_videos(r);
-}
-
-// PTL_FLAG_ASYNC_REJIT: pick the kernel for this draw without ever waiting for a compile of the specialised source (see ptl_renderer::Job).
-static int async_select_kernel(ptl_renderer* r) {
+// PTL_FLAG_ASYNC_REJIT: pick the kernel for this draw without ever waiting for a compile of the specialised source (see ptl_renderer::Job):
+// the wanted build is compiled by a worker thread, and the draws use `dyn_kernel` until it is done.
+static int async_select_kernel(ptl_renderer* r, const std::vector<UniformUpload>* values) {
     ptl_scene* s = r->owner;
-    const bool changed = r->kernel_scene_version != r->scene->version || !(r->kernel_stage == r->scene->current_stage) || mode_switches(*r) != r->kernel_switches ||
-                         (r->affine_rays && !r->no_affine && !camera_is_affine(*r));  // (a camera that stopped being affine: the affine-rays kernel is no longer valid)
+    const bool changed = decide_rebuild(r, values) != Rebuild::none;
+    if (changed) r->kernel_scene_version = r->scene->version;
     if (!changed && !r->job && r->kernel == r->spec_kernel) return PTL_OK;
-    if (changed) {
-        if (!(r->kernel_stage == r->scene->current_stage)) {
-            r->keep_dynamic.clear();
-            r->keep_unmasked.clear();
-            r->full_chains = false;
-            r->no_affine = false;
-        }
-        if (!camera_is_affine(*r)) r->no_affine = true;
-        if ((r->flags & (8u | kPatterns)) != 0 && (r->flags & 5u) == 0) {  // clip-constant specialisation: a compiled-in value that moved becomes a run-time uniform
-            std::vector<UniformUpload> values = evaluate_scene_uniforms(*r->scene, nullptr);
-            size_t at = 0;
-            for (const UniformUpload& b : r->want.baked) {
-                while (at < values.size() && values[at].name != b.name) ++at;
-                if (at == values.size()) break;
-                if (!values[at].same_value(b)) r->keep_dynamic.insert(b.name);
-            }
-            zero_patterns_broken(r, values);
-        }
-        r->kernel_switches = mode_switches(*r);
-        refresh_generated(s, r->flags, &r->keep_dynamic, &r->kernel_switches, &r->keep_unmasked, r->full_chains, r->no_affine);  // the specialised source of the CURRENT state (generation is milliseconds)
-        r->masked = s->last.masked;
-        r->affine_rays = s->last.affine_rays;
-        r->shortened = !s->last.full_chains && (s->last.masked.size() > 0 || std::find(s->last.defines.begin(), s->last.defines.end(), "PTL_DROP_ZERO_TERMS") != s->last.defines.end());
-        r->want = snapshot_build(s, r->flags);
-        r->kernel_scene_version = r->scene->version;
-        r->kernel_stage = r->scene->current_stage;
-    }
-    if (r->spec_kernel && r->spec_source == r->want.source) {  // (also: the state moved back to what the specialised kernel was built for)
-        r->baked = r->want.baked;
+    if (r->spec_kernel && r->spec_source == r->want.source)  // (also: the state moved back to what the specialised kernel was built for)
         return activate_kernel(r, r->spec_kernel);
-    }
     if (r->job && r->job->state.load() != 1) {  // the worker has finished
         std::shared_ptr<ptl_renderer::Job> job = r->job;
         if (job->worker.joinable()) job->worker.join();
@@ -1204,14 +1233,9 @@ static int async_select_kernel(ptl_renderer* r) {
             if (rc == PTL_OK) {
                 ptl_kernel* old = r->spec_kernel;
                 r->spec_kernel = k;
-                r->spec_source = job->build.source;
-                r->kernel_source = r->spec_source;
-                r->baked = job->build.baked;
+                r->spec_source = r->kernel_source = job->build.source;
                 ++r->rejit_count;
-                rc = activate_kernel(r, k);
-                if (r->lanes_of == old) drop_lane_clones(r);
-                retire_kernel(r, old);  // (never the active one: `k` has just been activated; parked while a staged slice names it)
-                return rc;
+                return install_kernel(r, k, old);
             }
             r->failed_source = job->build.source;
         } else if (job->state.load() == 3) {
@@ -1237,7 +1261,7 @@ static int async_select_kernel(ptl_renderer* r) {
         r->job = job;
     }
     if (!r->dyn_kernel) {  // first need: built here, once (a cached code object makes it a module load)
-        refresh_generated(s, r->flags & ~kSpecialised);
+        refresh_generated(s, r->flags & ~kSpecialisation);
         ptl_renderer::Build dyn = snapshot_build(s, r->flags);
         ptl_kernel* k = nullptr;
         int rc = compile_build(dyn, r->device, nullptr, &k, nullptr, 0);
@@ -1250,61 +1274,20 @@ static int async_select_kernel(ptl_renderer* r) {
 
 static int prepare_draw(ptl_renderer* r, const ptl_frame* frame) {
     send_camera_matrix(r);
-    const bool async = (r->flags & kAsyncRejit) != 0 && (r->flags & kSpecialised) != 0 && r->device >= 0;
-    if (async) {
-        int rc = async_select_kernel(r);
-        if (rc != PTL_OK) return rc;
-    }
-    if (!async && (r->flags & kSpecialised) != 0 && mode_switches(*r) != r->kernel_switches) {
-        // a camera model / output mode was switched: the specialised kernel has the old one compiled in (and the new one compiled out)
-        int rc = build_kernel(r, nullptr, 0);
-        if (rc != PTL_OK) return rc;
-        ++r->rejit_count;
-    }
-    if (!async && r->affine_rays && !r->no_affine && !camera_is_affine(*r)) {
-        // the camera went through something that is not an affine map: the kernel's w = 1 / w = 0 no longer holds for primary rays
-        r->no_affine = r->no_affine_just_set = true;
-        int rc = build_kernel(r, nullptr, 0);
-        if (rc != PTL_OK) return rc;
-        ++r->rejit_count;
-    }
-    if (!async && (r->flags & 5u) != 0 && r->kernel_scene_version != r->scene->version) {
-        // values are baked into a specialised kernel: the scene changed, so JIT again (cached by source hash)
-        int rc = build_kernel(r, nullptr, 0);
-        if (rc != PTL_OK) return rc;
-    }
-    if (r->uploaded_scene != r->scene->version) {
-        std::vector<std::string> errors;
-        std::vector<UniformUpload> values = evaluate_scene_uniforms(*r->scene, &errors);  // scene.set_uniforms
-        if (!async && (r->flags & (8u | kPatterns)) != 0 && (r->flags & 5u) == 0) {
-            // clip-constant specialisation: the kernel stays valid as long as every compiled-in value still holds; a value
-            // that moved after all is demoted to a run-time uniform and the kernel is built again (cached by source hash)
-            bool stale = !(r->kernel_stage == r->scene->current_stage);
-            size_t at = 0;
-            for (const UniformUpload& b : r->baked) {
-                while (at < values.size() && values[at].name != b.name) ++at;  // same order as at generation time
-                if (at == values.size()) {
-                    stale = true;
-                    break;
-                }
-                if (!values[at].same_value(b)) {
-                    r->keep_dynamic.insert(b.name);
-                    stale = true;
-                }
-            }
-            if (zero_patterns_broken(r, values)) stale = true;  // an animated matrix left the zero pattern its products were shortened for
-            if (stale) {
-                int rc = build_kernel(r, nullptr, 0);
-                if (rc != PTL_OK) return rc;
-                ++r->rejit_count;
-            }
-        }
-        int rc = upload(r->kernel, values);
-        if (rc < 0) return rc;
+    // the scene's values (scene.set_uniforms): evaluated when a draw has to upload them anyway -- a draw of an unchanged state evaluates nothing
+    std::vector<std::string> errors;
+    std::vector<UniformUpload> values;
+    const bool scene_moved = r->uploaded_scene != r->scene->version;
+    if (scene_moved) values = evaluate_scene_uniforms(*r->scene, &errors);
+    int rc = async_rejit(*r) ? async_select_kernel(r, scene_moved ? &values : nullptr) : update_kernel(r, scene_moved ? &values : nullptr);
+    if (rc != PTL_OK) return rc;
+    if (r->uploaded_scene != r->scene->version) {  // (also after a rebuild: a fresh uniform block)
+        if (!scene_moved) values = evaluate_scene_uniforms(*r->scene, &errors);
+        if (rc = upload(r->kernel, values); rc < 0) return rc;
         r->uploaded_scene = r->scene->version;
     }
     if (r->uploaded_options != r->options_version || r->uploaded_w != frame->width || r->uploaded_h != frame->height) {
-        int rc = upload(r->kernel, builtin_uniforms(*r, frame->width, frame->height));  // self.set_uniforms(w, h)
+        rc = upload(r->kernel, builtin_uniforms(*r, frame->width, frame->height));  // self.set_uniforms(w, h)
         if (rc < 0) return rc;
         r->uploaded_options = r->options_version;
         r->uploaded_w = frame->width;
@@ -1426,33 +1409,14 @@ extern "C" int ptl_renderer_join(ptl_renderer* r, void* stream) {
 // other values for this very state -- the renderer then switches affine rays off for its stage and rebuilds (one re-JIT, the frames stay right).
 static int check_affine_now(ptl_renderer* r, int width, int height, unsigned long long* violations) {
     if (r->device < 0) return PTL_ERR_NO_DEVICE;
-    const unsigned flags = (r->flags & ~(kAsyncRejit | (1u << 22) | (1u << 23))) | (1u << 25) | 2u | 262144u;  // not async, no slices entry; checking + counting, quick JIT
+    const unsigned flags = (r->flags & ~(PTL_FLAG_ASYNC_REJIT | PTL_FLAG_SLICES | PTL_FLAG_NO_AFFINE_RAYS)) | PTL_FLAG_CHECK_AFFINE | PTL_FLAG_COUNT_SEGMENTS |
+                           PTL_FLAG_QUICK_JIT;  // not async, no slices entry; checking + counting, quick JIT
     std::vector<char> log(1 << 16);
     ptl_renderer* sib = nullptr;
     int rc = ptl_renderer_create(r->owner, r->device, r->asset_root.c_str(), flags, &sib, log.data(), log.size());
     if (rc != PTL_OK) return rc;
     sib->cam = r->cam;
-    sib->offset_after_material = r->offset_after_material;
-    sib->gray_t_start = r->gray_t_start;
-    sib->gray_t_size = r->gray_t_size;
-    sib->render_depth = r->render_depth;
-    sib->aa_count = r->aa_count;
-    sib->aa_start = r->aa_start;
-    sib->draw_side_by_side = r->draw_side_by_side;
-    sib->draw_depth_map = r->draw_depth_map;
-    sib->angle_color_disable = r->angle_color_disable;
-    sib->grid_disable = r->grid_disable;
-    sib->black_border_disable = r->black_border_disable;
-    sib->darken_by_distance = r->darken_by_distance;
-    sib->depth_map_min = r->depth_map_min;
-    sib->depth_map_max = r->depth_map_max;
-    sib->anaglyph_p = r->anaglyph_p;
-    sib->anaglyph_q = r->anaglyph_q;
-    sib->draw_anaglyph = r->draw_anaglyph;
-    sib->anaglyph_mode = r->anaglyph_mode;
-    sib->eye_distance = r->eye_distance;
-    sib->swap_eyes = r->swap_eyes;
-    sib->check_affine_on_new_source = false;
+    sib->opt = r->opt;
     ++sib->options_version;
     ptl_frame f{};
     f.width = width;
@@ -1465,15 +1429,11 @@ static int check_affine_now(ptl_renderer* r, int width, int height, unsigned lon
     ptl_renderer_destroy(sib);
     if (rc != PTL_OK) return rc;
     if (violations) *violations = count;
-    r->affine_violations_seen = count;
+    r->affine_violations_seen = std::max<unsigned long long>(r->affine_violations_seen, count);  // (a later clean check -- another view -- clears nothing)
     r->checked_source = r->kernel_source;
-    if (count > 0 && r->affine_rays && !r->no_affine) {
-        r->no_affine = r->no_affine_just_set = true;
-        drop_async_kernels(r);
-        rc = build_kernel(r, nullptr, 0);
-        if (rc != PTL_OK) return rc;
-        seed_async_kernels(r);
-        ++r->rejit_count;
+    if (count > 0 && r->affine_rays && !r->stage.no_affine) {
+        r->stage.no_affine = r->stage.no_affine_just_set = true;
+        if (rc = rebuild_now(r, Rebuild::counted, nullptr, 0); rc != PTL_OK) return rc;
         r->checked_source = r->kernel_source;
         set_last_error("check_affine: " + std::to_string(count) + " ray halves met a product with a w that is not 1 / 0: affine rays switched off for this stage");
     }
@@ -1493,7 +1453,7 @@ extern "C" int ptl_renderer_check_affine(ptl_renderer* r, int width, int height,
 }
 // (before a draw: option "check_affine" / PTL_CHECK_AFFINE=1 -- once per new source that has affine rays)
 static int check_affine_if_asked(ptl_renderer* r, const ptl_frame* frame) {
-    if (!r->check_affine_on_new_source || !r->affine_rays || r->no_affine || r->device < 0 || r->checked_source == r->kernel_source) return PTL_OK;
+    if (!r->check_affine_on_new_source || !r->affine_rays || r->stage.no_affine || r->device < 0 || r->checked_source == r->kernel_source) return PTL_OK;
     int rc = check_affine_now(r, 64, 36, nullptr);
     if (rc != PTL_OK) return rc;
     return prepare_draw(r, frame);  // (the rebuilt kernel, if any, wants its uniforms)
@@ -1635,8 +1595,8 @@ int teleport_camera(ptl_renderer* r, const Camera& prev_cam, int* teleported, in
 // the segment camera -> eye crosses a portal, the eye gets its own teleported matrix (and subspace flag).
 int teleport_eye_matrices(ptl_renderer* r) {
     Camera& cam = r->cam;
-    if (!((r->draw_anaglyph || r->draw_side_by_side) && cam.allow_teleport)) return PTL_OK;
-    double eye_distance = r->swap_eyes ? -r->eye_distance : r->eye_distance;
+    if (!((r->opt.draw_anaglyph || r->opt.draw_side_by_side) && cam.allow_teleport)) return PTL_OK;
+    double eye_distance = r->opt.swap_eyes ? -r->opt.eye_distance : r->opt.eye_distance;
     auto one_eye = [&](double x, DMat4* out_m, bool* out_sub) -> int {
         DVec3 start_pos = cam_pos(cam);
         DMat4 m = cam.matrix();
@@ -1779,17 +1739,9 @@ extern "C" int ptl_renderer_camera_state(ptl_renderer* r, double teleport16[16],
 
 extern "C" ptl_kernel* ptl_renderer_kernel(ptl_renderer* r) {
     if (!r) return nullptr;
-    // the kernel the next draw would use: a specialised build follows the mode switches (also on a handle without a device, which never draws)
-    const bool camera_left_the_affine_maps = r->affine_rays && !r->no_affine && !camera_is_affine(*r);
-    if (camera_left_the_affine_maps && !((r->flags & kAsyncRejit) != 0 && r->device >= 0)) r->no_affine = r->no_affine_just_set = true;
-    if ((r->flags & kSpecialised) != 0 && !((r->flags & kAsyncRejit) != 0 && r->device >= 0) && (mode_switches(*r) != r->kernel_switches || camera_left_the_affine_maps)) {
-        int rc = guarded([&] {
-            int rc2 = build_kernel(r, nullptr, 0);
-            if (rc2 == PTL_OK) ++r->rejit_count;
-            return rc2;
-        });
-        if (rc != PTL_OK) return nullptr;  // ptl_last_error() says why; the old kernel has other switches compiled in
-    }
+    // the kernel the next draw would use: a specialised build follows the mode switches and the camera (also on a handle without a device, which
+    // never draws); the scene's values are the draw's to examine
+    if (!async_rejit(*r) && guarded([&] { return update_kernel(r, nullptr); }) != PTL_OK) return nullptr;  // ptl_last_error() says why
     return r->kernel;
 }
 extern "C" int ptl_renderer_kernel_source(ptl_renderer* r, char** source) {

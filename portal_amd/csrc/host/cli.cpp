@@ -178,11 +178,11 @@ constexpr unsigned kRenderFlags = 0u;
 // `render` (clips): the kernel a clip runs on when it gets no clip-constant build of its own still has the zero patterns of the scene's
 // matrices and the mode switches compiled in (PTL_FLAG_SPECIALIZE_PATTERNS, bit 20: no value baked, so nothing moves under it but a
 // pattern -- one rebuild per stage at most): 0.58 against 0.83 ms on the headline frame (profiles/r04/ab_bounded_snippets.jsonl `patterns`)
-constexpr unsigned kClipFlags = kRenderFlags | (1u << 20);
+constexpr unsigned kClipFlags = kRenderFlags | PTL_FLAG_SPECIALIZE_PATTERNS;
 // ... and, for a clip with motion blur, the slices entry (bit 22): the blur sub-frames of an output frame differ in their uniforms only and are
 // traced by ONE launch (grid.z = sub-frame, a uniform block per slice), so the ramp and tail of a small frame overlap with its neighbours' instead
 // of adding up: 1080p monoportal 0.0526 -> 0.0415 ms per sub-frame, 720p 0.0319 -> 0.0213, 4K aa 4 0.885 -> 0.861 (profiles/r04/concurrent_draws.jsonl)
-constexpr unsigned kSlicesFlag = 1u << 22;
+constexpr unsigned kSlicesFlag = PTL_FLAG_SLICES;
 inline bool batch_subframes(int blur, int batch_option) { return batch_option != 0 && blur >= 2 && blur <= 16; }
 // frames of a clip are intermediates (ffmpeg reads them, then anim/ is removed): fast deflate, 2.3x the encode rate of level 6
 constexpr int kFrameDeflateLevel = 3;
@@ -266,17 +266,19 @@ int setup_renderer(const Options& o, ptl_scene* scene, ptl_renderer* r, bool sce
     return 0;
 }
 
+// --fast: tolerance mode; --exact-cr: numerics contract 1
+unsigned numerics_flags(const Options& o) { return (o.fast ? PTL_FLAG_FAST_MATH : 0u) | (o.exact_cr ? PTL_FLAG_EXACT_CR : 0u); }
+
 unsigned frame_flags(const Options& o) {
     unsigned f = kRenderFlags;
     // One frame of one scene state: baking the state in is the cheaper build (0.74 s against 1.08 s of hiprtc for the headline scene:
     // the folded source is smaller) AND the faster kernel (0.53 against 1.31 ms), so it is the default; --specialize 0 keeps every
     // scene uniform a run-time value (profiles/r02/render_frame_e2e.log).
-    if (o.specialize != 0) f |= 1u | 4u;
-    if (o.fast) f |= 64u;                // --fast: tolerance mode (PTL_FLAG_FAST_MATH)
-    if (o.exact_cr) f |= 16384u;         // --exact-cr: numerics contract 1 (PTL_FLAG_EXACT_CR)
+    if (o.specialize != 0) f |= PTL_FLAG_SPECIALIZE_INTS | PTL_FLAG_SPECIALIZE_ALL;
+    f |= numerics_flags(o);
     // ONE frame: the wall time is the JIT's, not the kernel's (profiles/r03/render_frame_e2e.log: 2.4 s of -O3 hiprtc for a 0.33 ms kernel, 1.2 s
     // of -O1 for a 0.36 ms one) -- unless the caller wants the shipped optimisation level (--opt3), e.g. to fill the cache for a bench
-    if (!o.opt3) f |= 262144u;           // PTL_FLAG_QUICK_JIT
+    if (!o.opt3) f |= PTL_FLAG_QUICK_JIT;
     return f;
 }
 
@@ -488,7 +490,7 @@ int precompile(const Options& o) {
     if (!o.stage.empty() && ptl_scene_init_stage(scene, o.stage.c_str(), stage_cam, sizeof stage_cam) != PTL_OK) return fail("stage");
     std::vector<char> log(1 << 16);
     std::vector<unsigned> variants = {frame_flags(o)};
-    if (o.specialize != 0) variants.push_back(kClipFlags | (batch_subframes(o.blur, o.batch) ? kSlicesFlag : 0u) | (o.fast ? 64u : 0u) | (o.exact_cr ? 16384u : 0u) | (o.opt3 ? 0u : 262144u));  // + the dynamic-uniform kernel `render` starts clips with
+    if (o.specialize != 0) variants.push_back(kClipFlags | (batch_subframes(o.blur, o.batch) ? kSlicesFlag : 0u) | numerics_flags(o) | (o.opt3 ? 0u : PTL_FLAG_QUICK_JIT));  // + the dynamic-uniform kernel `render` starts clips with
     for (unsigned flags : variants) {
         auto t1 = std::chrono::steady_clock::now();
         ptl_renderer* r = nullptr;
@@ -720,7 +722,7 @@ void prefetch_clip_kernel(std::string path, std::vector<std::string> history, st
     const char* names[] = {"draw_side_by_side"};
     const double values[] = {stereo ? 1.0 : 0.0};
     ptl_renderer* r = nullptr;
-    if (ptl_renderer_create_with_options(scene, -1, asset_root.c_str(), kClipFlags | 8u | extra_flags, names, values, 1, &r, nullptr, 0) == PTL_OK) {
+    if (ptl_renderer_create_with_options(scene, -1, asset_root.c_str(), kClipFlags | PTL_FLAG_SPECIALIZE_STATIC | extra_flags, names, values, 1, &r, nullptr, 0) == PTL_OK) {
         ptl_renderer_prebuild_teleport(r);  // the camera of a clip moves: its teleport queries need the other half of the build as well
         ptl_renderer_destroy(r);
     }
@@ -797,7 +799,8 @@ int render(const Options& o) {
             if (ptl_scene_init_animation(scene, todo[0].first.c_str()) != PTL_OK) return fail("init_animation");
             apply_clip_overrides(scene, nullptr, todo[0].first, nullptr);
         }
-        unsigned start_flags = kClipFlags | (batch_subframes(o.blur, o.batch) ? kSlicesFlag : 0u) | (o.fast ? 64u : 0u) | (o.exact_cr ? 16384u : 0u) | (o.opt3 ? 0u : 262144u) | (start_baked ? 8u : 0u);
+        unsigned start_flags = kClipFlags | (batch_subframes(o.blur, o.batch) ? kSlicesFlag : 0u) | numerics_flags(o) | (o.opt3 ? 0u : PTL_FLAG_QUICK_JIT) |
+                               (start_baked ? PTL_FLAG_SPECIALIZE_STATIC : 0u);
         const char* create_names[] = {"aa_count", "render_depth", "draw_side_by_side"};  // before the first build: a baked kernel has its mode switches compiled in
         const double create_values[] = {(double)o.aa, (double)o.depth, o.stereo ? 1.0 : 0.0};
         if (ptl_renderer_create_with_options(scene, o.device, o.asset_root.c_str(), start_flags, create_names, create_values, 3, &r, log.data(), log.size()) !=
@@ -828,7 +831,7 @@ int render(const Options& o) {
             int n_workers = (int)std::min<size_t>({(size_t)6, todo.size() - 1, (size_t)std::max(1u, std::thread::hardware_concurrency() / 4)});
             pf.next = 1;  // the first clip is compiled by the main thread right away
             for (int wk = 0; wk < n_workers; ++wk)
-                pf.workers.emplace_back([&pf, &todo, &specialise, path, asset_root = o.asset_root, extra_flags = (o.fast ? 64u : 0u) | (o.exact_cr ? 16384u : 0u) | (batch_subframes(o.blur, o.batch) ? kSlicesFlag : 0u), stereo = o.stereo] {
+                pf.workers.emplace_back([&pf, &todo, &specialise, path, asset_root = o.asset_root, extra_flags = numerics_flags(o) | (batch_subframes(o.blur, o.batch) ? kSlicesFlag : 0u), stereo = o.stereo] {
                     for (;;) {
                         size_t k;
                         {
@@ -912,7 +915,7 @@ int check(const Options& o) {
         r = nullptr;
         // with a GPU: the build `render-frame` draws with (everything baked), and -- where it has affine rays -- the checking build of the same state
         // at 64 x 36: does any ray reach a product with a w the kernel assumes otherwise? (ptl_renderer_check_affine)
-        if (ptl_device_count() > 0 && ptl_renderer_create(scene, o.device, o.asset_root.c_str(), 5u | 262144u, &r, log.data(), log.size()) == PTL_OK) {
+        if (ptl_device_count() > 0 && ptl_renderer_create(scene, o.device, o.asset_root.c_str(), PTL_FLAG_SPECIALIZE_INTS | PTL_FLAG_SPECIALIZE_ALL | PTL_FLAG_QUICK_JIT, &r, log.data(), log.size()) == PTL_OK) {
             if (ptl_renderer_affine_rays(r) == 1) {
                 unsigned long long bad = 0;
                 if (ptl_renderer_check_affine(r, 64, 36, &bad) == PTL_OK)

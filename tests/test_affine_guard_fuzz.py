@@ -307,3 +307,92 @@ def test_a_renderer_that_checks_finds_the_hole_and_switches_affine_rays_off(gpu,
         clean = pa.SceneRenderer(pa.Scene.from_file(pa.scene_path(name)), device=0, flags=spec | pa.FLAG_QUICK_JIT)
         clean.set_option("render_depth", 12)
         assert clean.affine_rays() and clean.check_affine(128, 72) == 0 and clean.affine_rays() and clean.rejit_count() == 0
+
+
+def _settled_frame(r, w, h):
+    """FLAG_ASYNC_REJIT: draw until the background build of the current state has been adopted; the last frame."""
+    import time
+
+    got = r.draw(w, h, rgba32f=True)["rgba32f"]
+    deadline = time.time() + 120
+    while r.rejit_pending() and time.time() < deadline:
+        time.sleep(0.05)
+        got = r.draw(w, h, rgba32f=True)["rgba32f"]
+    assert not r.rejit_pending()
+    return got
+
+
+@pytest.mark.gpu
+def test_the_belts_verdict_outlives_a_stage_change_with_background_rejit(gpu, monkeypatch):
+    """a violation the check-affine belt counted keeps affine rays off for good.  A renderer with FLAG_ASYNC_REJIT decides its stage
+    changes by the same rule as a synchronous one; it used to switch affine rays on again at the next stage and draw the hole."""
+    pa = gpu
+    spec = pa.FLAG_SPECIALIZE_INTS | pa.FLAG_SPECIALIZE_ALL
+    w, h = 96, 64
+    text = bend_scene("r.o[3] = 2.0;", LIBRARY_CLEAN).replace("animation_stages: ([]),", 'animation_stages: ([(name: "later", data: (uniforms: {}, matrices: {}))]),')
+    plain = pa.Scene.from_text(text)
+    general = pa.SceneRenderer(plain, device=0, flags=spec | pa.FLAG_NO_AFFINE_RAYS | pa.FLAG_QUICK_JIT)
+    monkeypatch.setenv("PTL_AFFINE_RAYS_SKIP_SCAN", "1")
+    scene = pa.Scene.from_text(text)
+    r = pa.SceneRenderer(scene, device=0, flags=spec | pa.FLAG_ASYNC_REJIT | pa.FLAG_QUICK_JIT)
+    for x in (r, general):
+        x.set_option("render_depth", 6)
+    assert r.affine_rays() and r.check_affine() > 0 and not r.affine_rays()
+    for s in (scene, plain):
+        assert s.init_stage("later") == ""
+    got = _settled_frame(r, w, h)
+    assert not r.affine_rays()
+    assert np.array_equal(got.view(np.uint32), general.draw(w, h, rgba32f=True)["rgba32f"].view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_a_clean_check_does_not_clear_a_counted_violation(gpu, monkeypatch):
+    """a later check that counts nothing -- another view, one without the hole -- does not undo an earlier count; the rebuild for another
+    reason that may return to affine rays once per stage does not return to them for snippets already shown to break the assumption."""
+    pa = gpu
+    spec = pa.FLAG_SPECIALIZE_INTS | pa.FLAG_SPECIALIZE_ALL
+    w, h = 96, 64
+    text = bend_scene("r.o[3] = 2.0;", LIBRARY_CLEAN)
+    general = pa.SceneRenderer(pa.Scene.from_text(text), device=0, flags=spec | pa.FLAG_NO_AFFINE_RAYS | pa.FLAG_QUICK_JIT)
+    monkeypatch.setenv("PTL_AFFINE_RAYS_SKIP_SCAN", "1")
+    r = pa.SceneRenderer(pa.Scene.from_text(text), device=0, flags=spec | pa.FLAG_QUICK_JIT)
+    for x in (r, general):
+        x.set_option("render_depth", 6)
+    assert r.check_affine() > 0 and not r.affine_rays() and r.rejit_count() == 1
+    cam = pa.Scene.from_text(text).cam()
+    for x in (r, general):
+        x.set_camera((0.0, 0.0, -50.0), cam["alpha"], cam["beta"], cam["r"])   # looking away from the pane and the portals
+    assert r.check_affine() == 0 and not r.affine_rays()
+    for x in (r, general):
+        x.set_option("use_360_camera", 1)
+    assert not r.affine_rays() and r.rejit_count() == 2
+    assert np.array_equal(r.draw(w, h, rgba32f=True)["rgba32f"].view(np.uint32), general.draw(w, h, rgba32f=True)["rgba32f"].view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_a_renderer_with_background_rejit_returns_to_affine_rays_once_per_stage(gpu):
+    """ADVICE r5's rule -- after a camera that left the affine maps, a rebuild for another reason may return to affine rays once per stage -- holds
+    with FLAG_ASYNC_REJIT as well (tests/test_host_logic.py::test_one_return_to_affine_rays_per_stage has the synchronous renderer).  The
+    kernels differ; every frame is the un-specialised kernel's bit for bit."""
+    pa = gpu
+    text = open(pa.scene_path("basics")).read()
+    cam_text = text.replace("matrix: (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0),", "matrix: (1.0, 0.0, 0.0, 0.125, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0),", 1)
+    assert cam_text != text
+    r = pa.SceneRenderer(pa.Scene.from_text(cam_text), device=0, flags=pa.FLAG_SPECIALIZE_PATTERNS | pa.FLAG_ASYNC_REJIT | pa.FLAG_QUICK_JIT)
+    ref = pa.SceneRenderer(pa.Scene.from_text(cam_text), device=0, flags=0)
+    w, h = 96, 54
+
+    def step(action, value):
+        for x in (r, ref):
+            getattr(x, action)(*value)
+        got = _settled_frame(r, w, h)
+        assert np.array_equal(got.view(np.uint32), ref.draw(w, h, rgba32f=True)["rgba32f"].view(np.uint32)), (action, value)
+        return r.affine_rays()
+
+    assert step("set_option", ("render_depth", 8))
+    assert not step("use_camera", ("doorway",))
+    assert not step("use_camera", ("red",))                       # no rebuild of its own
+    assert step("set_option", ("use_360_camera", 1))              # a rebuild for another reason returns to affine rays ...
+    assert not step("use_camera", ("doorway",))
+    assert not step("use_camera", ("red",))
+    assert not step("set_option", ("use_360_camera", 0))          # ... once per stage

@@ -30,6 +30,17 @@ def test_library_exports_every_declared_symbol(pa):
     assert not missing, f"declared in include/portal_amd.h but not exported: {missing}"
 
 
+def test_the_headers_flag_bits_are_the_packages(pa):
+    """include/portal_amd.h names the flag bits the C++ tests (PTL_FLAG_*); portal_amd has the same names (FLAG_*), bit for bit."""
+    header = open(os.path.join(ROOT, "include", "portal_amd.h")).read()
+    bits = {m[0]: int(m[1]) << int(m[2]) for m in re.findall(r"#define PTL_FLAG_(\w+) \((\d+)u << (\d+)\)", header)}
+    assert set(re.findall(r"#define PTL_FLAG_(\w+)", header)) == set(bits) | {"WAVES_SHIFT"}
+    assert bits == {name[len("FLAG_"):]: value for name, value in vars(pa).items() if name.startswith("FLAG_")}
+    assert len(set(bits.values())) == len(bits) and all(v & 0xF00 == 0 for v in bits.values())   # one bit each, none among the occupancy hint's
+    shift = int(re.search(r"#define PTL_FLAG_WAVES_SHIFT (\d+)", header).group(1))
+    assert all(pa.flag_waves(n) == n << shift for n in range(16))
+
+
 def test_version_and_no_gpu_paths_fail_loudly(pa):
     assert "portal_amd" in pa.version()
     scene = pa.Scene.from_file(pa.scene_path("basics"))
