@@ -533,6 +533,7 @@ static KernelOptions options_from_flags(unsigned flags) {
     const bool first_trip_forms = on(PTL_FLAG_KEEP_TRANSFORM_DODGES) || specialised(flags);
     o.first_trip_planes = first_trip_forms && !on(PTL_FLAG_NO_FIRST_TRIP_PLANES);  // one scene_intersect for every trip
     if (const char* ab = std::getenv("PTL_AB_FIRST_TRIP_PLANES"); ab && (ab[0] == '0' || ab[0] == '1')) o.first_trip_planes = ab[0] == '1' && !on(PTL_FLAG_NO_FIRST_TRIP_PLANES);  // (A/B hook)
+    if (const char* skip = std::getenv("PTL_AFFINE_RAYS_SKIP_SCAN")) o.skip_affine_scan = skip[0] == '1';  // (test hook: KernelOptions::skip_affine_scan)
     // PTL_FLAG_NO_UNROLL: keep snippet loops with baked bounds as loops (A/B measurements).  The quick build keeps them too: unrolling
     // is half of its hiprtc time for the headline scene (3.4 -> 1.8 s on this container's cores) and buys 0.05 ms of kernel
     o.unroll_baked_loops = !on(PTL_FLAG_NO_UNROLL) && !o.quick_jit;
@@ -858,12 +859,8 @@ static bool zero_patterns_broken(ptl_renderer* r, const std::vector<UniformUploa
             if (v.type == UniformType::Mat4 && matrix_breaks_short_chains(v.f)) m.full_chains = broken = true;
     // ... and a kernel with affine rays is exact while every scene matrix maps w = 1 to 1 and w = 0 to 0 (or is NaN throughout: a switched-off object)
     if (r->affine_rays && !m.no_affine)
-        for (const UniformUpload& v : values) {
-            if (v.type != UniformType::Mat4 || matrix_is_affine(v.f)) continue;
-            bool all_nan = true;
-            for (int k = 0; k < 16; ++k) all_nan = all_nan && std::isnan(v.f[k]);
-            if (!all_nan) m.no_affine = m.no_affine_just_set = broken = true;
-        }
+        for (const UniformUpload& v : values)
+            if (v.type == UniformType::Mat4 && !matrix_keeps_rays_affine(v.f)) m.no_affine = m.no_affine_just_set = broken = true;
     for (auto& [name, mask] : r->masked)
         for (const UniformUpload& v : values) {
             if (v.name != name || v.type != UniformType::Mat4) continue;
@@ -940,7 +937,7 @@ static Rebuild decide_rebuild(ptl_renderer* r, const std::vector<UniformUpload>*
     r->baked = s->last.baked;
     r->masked = s->last.masked;
     r->affine_rays = s->last.affine_rays;
-    r->shortened = !s->last.full_chains && (s->last.masked.size() > 0 || std::find(s->last.defines.begin(), s->last.defines.end(), "PTL_DROP_ZERO_TERMS") != s->last.defines.end());
+    r->shortened = s->last.shortened;
     r->kernel_stage = r->scene->current_stage;
     r->want = snapshot_build(s, r->flags);
     return why;

@@ -13,6 +13,7 @@
 #include <regex>
 #include <set>
 #include <sstream>
+#include <tuple>
 
 namespace ptl {
 
@@ -321,87 +322,9 @@ std::vector<UniformUpload> evaluate_scene_uniforms(const Scene& scene, std::vect
 }
 
 // ------------------------------------------------------------------------------------------
-// slot generators (scene.rs:693-1063)
+// what the generator reads out of a GLSL text
 // ------------------------------------------------------------------------------------------
 namespace {
-
-// Scene snippets on their way into the kernel: tag filter, (optionally) uniform-only work moved to the prologue kernel
-// (glsl_hoist.h; prepared for all snippets at once by `prepare`, because the members it creates belong into the uniform block
-// that is emitted before any snippet), GLSL -> C++.
-struct SnippetTranslator {
-    const CodegenFlags& flags;
-    std::map<const std::string*, std::string> hoisted;  // source text of a snippet (by address) -> filtered + hoisted GLSL
-    std::map<const std::string*, std::string> hoisted_first;  // ... and its first-trip variant (intersection materials, KernelOptions::first_trip)
-    std::vector<HoistedMember> members;
-    std::string prologue;  // GLSL
-    int next_member = 0;
-    // Int uniforms baked into this build, with their values: a counting loop `for (int k = 0; k < NAME_u; k++)` of a snippet whose bound
-    // is one of them (and small) is unrolled.  The same operations in the same order -- identical frames -- but every iteration
-    // then has its own constants: the loop counter (`size` of scenes/portal_in_portal.ron:1144 drives an inner loop and a material
-    // index) and, with the matrices baked too, whatever the iteration does to loop-carried uniform values.  Measured on the headline
-    // (profiles/r03/stub_profile.jsonl `pip_unrolled`, variants5_unroll.jsonl): 0.409 -> 0.350 ms, same frame hash.
-    std::map<std::string, int> unroll_bounds;
-    static constexpr int kUnrollLimit = 16;
-    // intersection-material snippets that take the caller's distance bound (KernelOptions::bound_snippets): their filtered GLSL with the
-    // bounded conditions, by the address of the scene's text
-    std::map<const std::string*, std::string> bounded_src;
-    std::string filtered(const std::string& code) const {
-        auto it = bounded_src.find(&code);
-        return it != bounded_src.end() ? it->second : filter_tagged_lines(code, flags);
-    }
-
-    std::string unrolled(std::string cxx) const {
-        if (unroll_bounds.empty()) return cxx;
-        static const std::regex loop(R"(for \(int (\w+) = 0; (\w+) < (\w+); (\w+)\+\+\) \{)");
-        std::string out;
-        auto begin = std::sregex_iterator(cxx.begin(), cxx.end(), loop);
-        size_t last = 0;
-        for (auto it = begin; it != std::sregex_iterator(); ++it) {
-            const std::smatch& m = *it;
-            out.append(cxx, last, (size_t)m.position() - last);
-            last = (size_t)m.position();
-            auto b = unroll_bounds.find(m[3].str());
-            if (m[1] == m[2] && m[1] == m[4] && b != unroll_bounds.end() && b->second >= 2 && b->second <= kUnrollLimit) out += "_Pragma(\"unroll\") ";
-        }
-        out.append(cxx, last, std::string::npos);
-        return out;
-    }
-
-    void prepare(const std::string& code, const HoistParams& base, bool body_only, std::vector<std::string> params) {
-        HoistParams hp = base;
-        hp.body_only = body_only;
-        hp.body_params = std::move(params);
-        HoistResult r = hoist_uniform_work(filtered(code), hp, next_member);
-        if (r.members.empty()) return;
-        hoisted[&code] = r.glsl;
-        members.insert(members.end(), r.members.begin(), r.members.end());
-        prologue += r.prologue;
-    }
-    // the first-trip variant of an intersection-material snippet: parameter `r` starts at the camera
-    void prepare_first(const std::string& code, const HoistParams& base) {
-        HoistParams hp = base;
-        hp.body_only = true;
-        hp.body_params = {"r", "ptl_far"};
-        hp.origin_uniform_rays = {"r"};
-        hp.origin_expr = "PTL_DV_OUT.ptl_dv_origin";
-        HoistResult r = hoist_uniform_work(filtered(code), hp, next_member);
-        if (r.members.empty()) return;
-        hoisted_first[&code] = r.glsl;
-        members.insert(members.end(), r.members.begin(), r.members.end());
-        prologue += r.prologue;
-    }
-    bool has_first(const std::string& code) const { return hoisted_first.count(&code) != 0; }
-    std::string first(const std::string& code) const { return unrolled(translate_glsl(hoisted_first.at(&code), flags.defer_loop_updates)); }
-    std::string operator()(const std::string& code) const {
-        auto it = hoisted.find(&code);
-        return unrolled(translate_glsl(it != hoisted.end() ? it->second : filtered(code), flags.defer_loop_updates));
-    }
-    // a file-scope library text: its function definitions become PTL_FN (force-inlined) like the rest of the kernel
-    std::string library(const std::string& code) const {
-        auto it = hoisted.find(&code);
-        return unrolled(translate_glsl(it != hoisted.end() ? it->second : filtered(code), flags.defer_loop_updates, true));
-    }
-};
 
 // names of the functions a GLSL text defines (`type name(...) {` at brace depth 0)
 void defined_functions(const std::string& glsl, std::set<std::string>& names) {
@@ -452,11 +375,6 @@ void functions_with_out_params(const std::string& glsl, std::set<std::string>& n
         pos = after;
     }
 }
-
-struct PortalMaterialNames {
-    int pos;
-    std::string a, b;
-};
 
 }  // namespace
 
@@ -652,6 +570,10 @@ bool matrix_breaks_short_chains(const float m[16]) {
 }
 
 bool matrix_is_affine(const float m[16]) { return m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f; }
+
+bool matrix_keeps_rays_affine(const float m[16]) {
+    return matrix_is_affine(m) || std::all_of(m, m + 16, [](float e) { return std::isnan(e); });
+}
 
 namespace {
 // the significant tokens of a snippet (no spaces, no comments, no preprocessor lines)
@@ -908,713 +830,857 @@ bool snippets_keep_rays_affine(const std::vector<std::string>& codes, std::strin
     return true;
 }
 
-GeneratedKernel generate_kernel_source(const Scene& scene, const CodegenFlags& flags_in, const KernelOptions& opts) {
-    CodegenFlags flags = flags_in;  // (a copy: a kernel with affine rays drops the deferred loop updates, below)
-    GeneratedKernel gk;
-    std::map<std::string, StringStorage> storages;
-    SnippetTranslator snippet{flags, {}, {}, {}, {}, 0, {}, {}};
+// ------------------------------------------------------------------------------------------
+// the plan of one build: every decision, no text
+// ------------------------------------------------------------------------------------------
+namespace {
 
-    // --- uniform block --------------------------------------------------------------------
-    {
-        std::vector<UniformDesc> list;
-        for (auto& tex : scene_texture_list(scene)) list.push_back({tex, UniformType::Sampler, 0});
-        for (auto& u : scene_uniform_list(scene)) list.push_back(u);
-        size_t off = 0;
-        for (auto& u : list) {
-            u.offset = off;
-            off += uniform_type_size(u.type);
-        }
-        bool has_sampler = !list.empty() && list[0].type == UniformType::Sampler;  // pointer member -> 8-byte struct alignment
-        gk.uniform_block_size = has_sampler ? ((off + 7) & ~(size_t)7) : off;
-        gk.uniforms = list;
+// One GLSL text of the scene on its way into the kernel: tag filter, (optionally) the caller's distance bound, (optionally) uniform-only work
+// moved to the prologue kernel (glsl_hoist.h; planned for all snippets at once, because the members it creates belong into the uniform block
+// that is emitted before any snippet), GLSL -> C++ (translate_snippet).
+struct SceneSnippet {
+    enum Kind { Library, MaterialBody, FlatObject, ComplexObject, IntersectionMaterial };
+    Kind kind;
+    const std::string* code;    // the scene's text as written; its address names the snippet
+    bool portal;                // (objects) the generated function has the extra parameter `first`
+    std::string filtered;       // the text behind the tag filter
+    std::string bounded;        // ... with the caller's distance bound in its `nearer` conditions ("": as written; KernelOptions::bound_snippets)
+    std::string hoisted;        // ... with its uniform-only work replaced by reads of block members ("": nothing hoisted)
+    std::string hoisted_first;  // the first-trip variant of an intersection material: parameter `r` starts at the camera ("": none; KernelOptions::first_trip)
+    const std::string& source() const { return bounded.empty() ? filtered : bounded; }
+    const std::string& glsl() const { return hoisted.empty() ? source() : hoisted; }
+};
 
-        StringStorage s;
-        // JIT-time specialisation: current values baked in as literals (same arithmetic, the
-        // compiler folds branches on mode switches / ray-independent subexpressions)
-        std::map<std::string, std::string> baked;
-        if (opts.specialize_ints || opts.specialize_all || opts.specialize_static || opts.specialize_static_ints) {
-            auto hexf = [](float v) -> std::string {
-                if (std::isnan(v)) return "__builtin_nanf(\"\")";
-                if (std::isinf(v)) return v > 0 ? "__builtin_inff()" : "(-__builtin_inff())";
-                char buf[48];
-                std::snprintf(buf, sizeof buf, "%af", (double)v);
-                return buf;
-            };
-            for (auto& up : evaluate_scene_uniforms(scene, nullptr)) {
-                if (up.name == "teleport_light_u") continue;  // forced to 1 by the camera-teleport query (src/main.rs:1367)
-                if (opts.keep_dynamic.count(up.name)) continue;
-                if (opts.specialize_static && up.animated) continue;  // changes every frame: stays a run-time uniform
-                const bool switches_only = opts.specialize_static_ints && !(opts.specialize_ints || opts.specialize_all || opts.specialize_static);
-                if (switches_only && (up.animated || up.type != UniformType::Int1)) continue;  // the patterns build: only the Bool / Int uniforms that hold still
-                bool all = opts.specialize_all || opts.specialize_static;
-                if (up.type == UniformType::Int1) {
-                    baked[up.name] = std::to_string(up.i);
-                    if (opts.unroll_baked_loops) snippet.unroll_bounds[up.name] = up.i;
-                } else if (all && up.type == UniformType::Float1) {
-                    baked[up.name] = hexf(up.f[0]);
-                } else if (all && up.type == UniformType::Mat4) {
-                    std::string m = "mat4(";
-                    for (int k = 0; k < 16; ++k) m += (k ? ", " : "") + hexf(up.f[k]);
-                    baked[up.name] = m + ")";
-                } else {
-                    continue;
-                }
-                gk.baked.push_back(up);
-            }
-        }
-        // Shortened products are exact for finite vectors (device/ptl_glsl.h, "the deviation, stated"): a skipped `0 * x` would have been NaN
-        // for an infinite or NaN x.  Where such vectors come from is known at generation time -- a matrix with non-finite elements (the
-        // inverse of a zero scale, 1/0 in a formula) -- so it is decided here, for the whole kernel:
-        //   * a matrix that is NaN in EVERY element (glam's inverse of a matrix scaled to zero on all axes: how the reference's scenes switch
-        //     an object off, scenes/portal_in_portal.ron `c0`) turns every vector into all-NaN, and NaN times a retained non-zero element is
-        //     NaN in the short chain as in the full one: allowed;
-        //   * any other non-finite matrix (infinities, or NaN beside numbers) produces +-inf components, for which the two chains do differ
-        //     (inf * 1 against inf * 1 + 0 * inf = NaN): the kernel keeps every full chain (GeneratedKernel::full_chains).
-        gk.full_chains = opts.full_chains;
-        if (!gk.full_chains && (opts.mask_zero_elements || opts.specialize_all || opts.specialize_static))
-            for (auto& up : evaluate_scene_uniforms(scene, nullptr))
-                if (up.type == UniformType::Mat4 && matrix_breaks_short_chains(up.f)) gk.full_chains = true;
-        if (opts.mask_zero_elements && !opts.exact_cr && !opts.fast_math && !gk.full_chains) {
-            auto pattern_of = [](const UniformUpload& up) { return matrix_pattern(up.f); };
-            std::vector<std::pair<std::string, MatrixPattern>> found;
-            bool any_animated = false;
-            const std::vector<UniformUpload> current = evaluate_scene_uniforms(scene, nullptr);
-            // the state the patterns depend on: stage / clip, every value that is not animated (the probes move the animated ones themselves)
-            std::string key;
-            if (opts.mask_cache) {
-                auto put = [&key](const void* p, size_t n) { key.append(static_cast<const char*>(p), n); };
-                const int stage[3] = {(int)scene.current_stage.kind, scene.current_stage.index, scene.run_animations ? 1 : 0};
-                put(stage, sizeof stage);
-                for (auto& up : current) {
-                    key += up.name;
-                    key += up.animated ? '~' : '=';
-                    if (!up.animated) {
-                        put(up.f, sizeof up.f);
-                        put(&up.i, sizeof up.i);
-                    }
-                    key += baked.count(up.name) ? 'b' : (opts.keep_unmasked.count(up.name) ? 'k' : 'r');
-                }
-            }
-            // (a hit must still cover what the animated matrices hold NOW: their values are not part of the key, and a build with baked Bool /
-            // Int uniforms has nothing but this generation between a moved value and the draw)
-            bool hit = opts.mask_cache && !key.empty() && key == opts.mask_cache->key;
-            if (hit)
-                for (auto& up : current) {
-                    if (up.type != UniformType::Mat4 || !up.animated || baked.count(up.name) || opts.keep_unmasked.count(up.name)) continue;
-                    MatrixPattern mask = 0xffffu;
-                    for (auto& m : opts.mask_cache->masked)
-                        if (m.first == up.name) mask = m.second;
-                    if (!pattern_holds(mask, up.f)) hit = false;
-                }
-            if (hit) {
-                ++opts.mask_cache->hits;
-                gk.masked = opts.mask_cache->masked;
-            } else {
-                for (auto& up : current) {
-                    if (up.type != UniformType::Mat4 || baked.count(up.name) || opts.keep_unmasked.count(up.name)) continue;
-                    found.emplace_back(up.name, pattern_of(up));
-                    any_animated = any_animated || up.animated;
-                }
-                // A matrix that reads the formulas' `time` is identity-like exactly when a clip starts -- the moment a clip-constant kernel is
-                // generated.  Its pattern is therefore taken over the whole clip: the union over probes of `time` in [0, 1] (a copy of the scene;
-                // the pattern of an animation changes at its end points or nowhere, a probe that misses something costs one rebuild, not a pixel).
-                if (any_animated) {
-                    auto take = [&](const Scene& probe) {
-                        for (auto& up : evaluate_scene_uniforms(probe, nullptr))
-                            if (up.type == UniformType::Mat4 && up.animated)
-                                for (auto& f : found)
-                                    if (f.first == up.name) f.second = combine_patterns(f.second, pattern_of(up));
-                    };
-                    Scene probe = scene;
-                    const bool in_clip = !scene.run_animations && scene.current_stage.kind == StageRef::RealAnimation && scene.current_stage.index >= 0 &&
-                                         scene.current_stage.index < (int)scene.animations.size() && scene.animations[scene.current_stage.index].duration > 0.0;
-                    if (in_clip) {
-                        // inside a clip: the video pipeline's own step (Scene::update) at 33 moments of the clip.  On the reference's corpus (471 clips,
-                        // patterns taken on a 240-point grid) 7 probes miss something in 16 clips, 16 in 10, 32 in none: elements like cos(pi/2)
-                        // flicker between 0 and 1e-17, and every miss is a rebuild in the middle of a clip
-                        const double duration = scene.animations[scene.current_stage.index].duration;
-                        try {
-                            for (int k = 0; k <= 32; ++k) {
-                                probe.update(duration * (k < 32 ? k / 32.0 : 0.999999));
-                                take(probe);
-                            }
-                        } catch (const std::exception&) {  // a clip whose cameras cannot be evaluated fails where it is played, not here: no pattern for what moves
-                            for (auto& up : evaluate_scene_uniforms(scene, nullptr))
-                                if (up.type == UniformType::Mat4 && up.animated)
-                                    for (auto& f : found)
-                                        if (f.first == up.name) f.second = 0xffffu;
-                        }
-                    } else {
-                        for (double t : {0.0, 0.0625, 0.271, 0.5, 0.729, 0.9375, 1.0}) {
-                            probe.time = t;
-                            take(probe);
-                        }
-                    }
-                    // The other per-frame input is the camera (Matrix::Camera): one probe gives it a matrix without a single zero, so that
-                    // nothing that follows the camera is ever masked (a renderer is even created before its camera is known).
-                    probe = scene;
-                    probe.camera_matrix = DMat4::from_cols(DVec4(0.36, 0.48, -0.8, 0.013), DVec4(-0.8, 0.6, 0.017, 0.011), DVec4(0.48, 0.64, 0.6, 0.019), DVec4(0.37, -1.21, 2.53, 1.0));
-                    take(probe);
-                }
-                for (auto& f : found)
-                    if (f.second != 0xffffu) gk.masked.push_back(f);
-                if (opts.mask_cache) {
-                    ++opts.mask_cache->misses;
-                    opts.mask_cache->key = key;
-                    opts.mask_cache->masked = gk.masked;
-                }
-            }
-        }
-        // --- affine rays (KernelOptions::affine_rays): every matrix of the scene maps w = 1 to 1 and w = 0 to 0 (bottom row 0 0 0 1) -- or is NaN in
-        // every element (a switched-off object: its products are NaN whatever the w) -- and no scene snippet writes a ray's w.  Only in builds
-        // that may shorten products at all (the same deviation for non-finite rays, the same guard), i.e. never in the un-specialised build.
-        // (the tolerance mode gets them too: it is not bit-exact anyway, and without them it was SLOWER than the exact kernel -- 0.217 against 0.191 ms)
-        if (opts.affine_rays && !opts.check_affine && !opts.exact_cr && !gk.full_chains && (opts.mask_zero_elements || opts.specialize_all || opts.specialize_static)) {
-            bool affine = true;
-            // (a matrix that stays a run-time value: what holds now is checked again by the renderer before every upload that could change it
-            // -- capi.cpp `zero_patterns_broken` for the builds that keep their kernel across scene states; the others come back here)
-            for (auto& up : evaluate_scene_uniforms(scene, nullptr)) {
-                if (up.type != UniformType::Mat4) continue;
-                bool all_nan = true;
-                for (int k = 0; k < 16; ++k) all_nan = all_nan && std::isnan(up.f[k]);
-                affine = affine && (all_nan || matrix_is_affine(up.f));
-            }
-            if (affine) {
-                std::vector<std::string> codes;
-                for (const NamedCode& lib : scene.library) codes.push_back(filter_tagged_lines(lib.code, flags));
-                for (const Material& m : scene.materials)
-                    if (m.kind == Material::Complex) codes.push_back(filter_tagged_lines(m.code, flags));
-                for (const Object& o : scene.objects)
-                    if (o.kind == Object::Flat || o.kind == Object::Complex) codes.push_back(filter_tagged_lines(o.code, flags));
-                for (const NamedCode& im : scene.intersection_materials) codes.push_back(filter_tagged_lines(im.code, flags));
-                // (PTL_AFFINE_RAYS_SKIP_SCAN=1: a TEST hook -- tests/test_affine_guard_fuzz.py shows what a snippet the scan refuses would draw with the assumption)
-                const char* skip = std::getenv("PTL_AFFINE_RAYS_SKIP_SCAN");
-                affine = (skip && skip[0] == '1') || snippets_keep_rays_affine(codes, &gk.affine_rays_refused_because);
-            }
-            gk.affine_rays = affine;
-        }
-        // Deferred loop updates (glsl_translate.h) and the first-trip copies of the intersection-material snippets (ptl_trace.tpl PTL_FIRST_TRIP)
-        // both exist to dodge `transform(uniform matrix, ray)` -- 32 FMAs in the un-specialised kernel.  In a kernel with affine rays the matrices
-        // are literals or carry their patterns, a transform of the reference's portal matrices is a handful of additions, and the bookkeeping
-        // around it (pending counters and their flush loops; a second copy of every snippet and a wave-level choice between the two) costs more
-        // than it saves: measured on the headline, same frames, baked 0.2305 -> 0.2046 ms, Int-baked 0.272 -> 0.239, patterns 0.274 -> 0.239
-        // (profiles/r05/ab_flags2.jsonl; the un-specialised kernel: 0.70 -> 0.89 without the deferral, so it keeps both).
-        const bool cheap_transforms = gk.affine_rays && !opts.keep_transform_dodges;
-        if (cheap_transforms) flags.defer_loop_updates = false;
-        const bool first_trip_snippets = opts.first_trip && !cheap_transforms;
-        // (KernelOptions::baked_options is only filled in for builds that may compile the switches in: any specialisation, patterns-only included)
-        for (auto& [name, value] : opts.baked_options)
-                for (auto& u : list)
-                    if (u.name == name && u.type == UniformType::Int1) baked[name] = std::to_string(value);
-        // first-trip plane tests (KernelOptions::first_trip_planes): only where some Flat object's matrix is a run-time value
-        auto first_trip_planes_wanted = [&]() {
-            if (!(opts.derived_uniforms && opts.first_trip_planes)) return false;
-            for (const Object& o : scene.objects) {
-                if (o.kind != Object::Flat) continue;
-                if (!baked.count(inverse_name(matrix_name(scene, o.m0, o)))) return true;
-                if (o.portal && !baked.count(inverse_name(matrix_name(scene, o.m1, o)))) return true;
-            }
-            return false;
-        };
-        // --- derived uniforms: one entry per plane test of a Flat object whose matrix is a run-time uniform -------------
-        if (opts.derived_uniforms) {
-            for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
-                const Object& o = scene.objects[pos];
-                if (o.kind != Object::Flat) continue;
-                auto add = [&](int midx, int side, const std::string& normal_expr, const std::string& arg_expr) {
-                    const std::string& m = matrix_name(scene, midx, o);
-                    if (baked.count(normal_name(m))) return;  // literal matrix: the compiler folds all of this
-                    DerivedPlane d;
-                    d.object = (int)pos;
-                    d.side = side;
-                    d.member = "ptl_dv_" + std::to_string(pos) + "_" + std::to_string(side);
-                    d.normal_expr = normal_expr + normal_name(m) + ")";
-                    d.arg_expr = arg_expr + normal_name(m) + ")";
-                    gk.derived.push_back(d);
-                };
-                if (!o.portal) {
-                    add(o.m0, 0, "-get_normal(", "get_normal(");
-                } else {
-                    add(o.m0, 0, "-get_normal(", "-get_normal(");
-                    add(o.m1, 1, "get_normal(", "get_normal(");
-                }
-            }
-        }
-        {  // out / inout arguments are lowered to references: refuse the scenes for which that is not GLSL's copy in / copy out
-            std::vector<std::string> file_scope, bodies;
-            for (const NamedCode& lib : scene.library) file_scope.push_back(filter_tagged_lines(lib.code, flags));
-            for (const Material& m : scene.materials)
-                if (m.kind == Material::Complex) bodies.push_back(filter_tagged_lines(m.code, flags));
-            for (const Object& o : scene.objects)
-                if (o.kind == Object::Flat || o.kind == Object::Complex) bodies.push_back(filter_tagged_lines(o.code, flags));
-            for (const NamedCode& im : scene.intersection_materials) bodies.push_back(filter_tagged_lines(im.code, flags));
-            check_out_argument_aliasing(file_scope, bodies);
-        }
-        // --- the caller's distance bound inside the intersection-material snippets (KernelOptions::bound_snippets) ----------------
-        if (opts.bound_snippets && !scene.intersection_materials.empty()) {
-            // process_portal_intersection never resets SceneIntersection::in_subspace (library.glsl:571-589): with subspace portals a skipped
-            // candidate could leave that flag behind, so a scene whose GLSL names them keeps its snippets as written
-            bool subspace = false;
-            auto names_subspace = [&](const std::string& code) {
-                for (const Token& t : tokenize_glsl(code))
-                    if (t.kind == Token::Ident && (t.text == "TELEPORT_SUBSPACE" || t.text == "in_subspace")) subspace = true;
-            };
-            std::set<std::string> with_out;
-            for (const NamedCode& lib : scene.library) names_subspace(lib.code), functions_with_out_params(lib.code, with_out);
-            for (const Material& m : scene.materials)
-                if (m.kind == Material::Complex) names_subspace(m.code);
-            for (const Object& o : scene.objects)
-                if (o.kind == Object::Flat || o.kind == Object::Complex) names_subspace(o.code);
-            for (const NamedCode& im : scene.intersection_materials) names_subspace(im.code);
-            if (!subspace)
-                for (const NamedCode& im : scene.intersection_materials) {
-                    int n = 0;
-                    std::string bounded = bound_nearer_blocks(filter_tagged_lines(im.code, flags), with_out, &n);
-                    if (n > 0) {
-                        snippet.bounded_src[&im.code] = bounded;
-                        gk.bounded_snippet_blocks += n;
-                    }
-                }
-        }
-        // --- uniform-only work of the scene snippets: members behind the derived planes, filled by the same prologue kernel -----
-        if (opts.derived_uniforms && opts.hoist_uniform_work) {
-            HoistParams hp;
-            for (auto& u : list) {
-                if (u.type == UniformType::Sampler) continue;
-                if (baked.count(u.name)) hp.constants[u.name] = cxx_type(u.type);
-                else hp.uniforms[u.name] = cxx_type(u.type);
-            }
-            for (const NamedCode& lib : scene.library) functions_with_out_params(lib.code, hp.functions_with_out_params);
-            for (const NamedCode& lib : scene.library) defined_functions(lib.code, hp.scene_functions);
-            for (const NamedCode& lib : scene.library) snippet.prepare(lib.code, hp, false, {});
-            for (const Material& m : scene.materials)
-                if (m.kind == Material::Complex) snippet.prepare(m.code, hp, true, {"hit", "r", "i"});
-            for (const Object& o : scene.objects) {
-                if (o.kind == Object::Flat) snippet.prepare(o.code, hp, true, o.portal ? std::vector<std::string>{"pos", "x", "y", "back", "first"} : std::vector<std::string>{"pos", "x", "y", "back"});
-                else if (o.kind == Object::Complex) snippet.prepare(o.code, hp, true, o.portal ? std::vector<std::string>{"r", "first"} : std::vector<std::string>{"r"});
-            }
-            for (const NamedCode& im : scene.intersection_materials) snippet.prepare(im.code, hp, true, {"r", "ptl_far"});
-            if (first_trip_snippets)
-                for (const NamedCode& im : scene.intersection_materials) snippet.prepare_first(im.code, hp);
-        }
-        // (in the TEXT as well as among the defines: a renderer tells "nothing compiled in changed" by comparing sources, and a kernel with and
-        // one without affine rays differ in nothing else)
-        if (gk.affine_rays) s.add_string("#define PTL_AFFINE_RAYS 1\n");
-        if (opts.check_affine) s.add_string("#define PTL_CHECK_AFFINE 1\n");  // (implies PTL_COUNT_SEGMENTS: the counter counts rays whose w is not 1 / 0)
-        if (opts.derived_uniforms) s.add_string("#define PTL_DERIVED_BUILTINS 1\n");
-        {
-            if (first_trip_planes_wanted())
-                s.add_string("#define PTL_FIRST_TRIP_PLANES 1\n#ifndef PTL_FIRST_TRIP\n#define PTL_FIRST_TRIP 1\n#endif\n");
-            bool any_first_snippet = false;
-            for (const NamedCode& im : scene.intersection_materials) any_first_snippet = any_first_snippet || snippet.has_first(im.code);
-            if (any_first_snippet) s.add_string("#define PTL_FIRST_TRIP_SNIPPETS 1\n#ifndef PTL_FIRST_TRIP\n#define PTL_FIRST_TRIP 1\n#endif\n");
-        }
-        s.add_string("struct ptl_uniform_block {\n");
-        for (auto& u : list) s.add_string(std::string("    ") + cxx_type(u.type) + " " + u.name + ";\n");
-        // written by ptl_derive_kernel (never by the host: uploads stop at uniform_block_size)
-        if (opts.derived_uniforms)  // the per-pixel work that depends on the frame's builtins alone (ptl_trace.tpl derive())
-            s.add_string("    vec4 ptl_dv_origin;\n    vec4 ptl_dv_origin_left;\n    vec4 ptl_dv_origin_right;\n    vec2 ptl_dv_half_resolution;\n"
-                         "    float ptl_dv_tan_half_view;\n    float ptl_dv_pixel_size;\n");
-        for (auto& d : gk.derived) s.add_string("    vec3 " + d.member + "_nrm;\n    int " + d.member + "_col;\n");
-        // first-trip plane tests: `plane_inv * camera origin` per generated plane test (KernelOptions::first_trip_planes)
-        // (not with every scene uniform baked in: with the zero terms of the literal matrices skipped the origin half of a plane test
-        // is a couple of FMAs, and the second copy of scene_intersect measured no gain there -- profiles/r03/variants7_first_trip_planes.jsonl)
-        const bool first_planes = first_trip_planes_wanted();
-        if (first_planes)
-            for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
-                const Object& o = scene.objects[pos];
-                if (o.kind != Object::Flat) continue;
-                s.add_string("    vec4 ptl_dvo_" + std::to_string(pos) + "_0;\n");
-                if (o.portal) s.add_string("    vec4 ptl_dvo_" + std::to_string(pos) + "_1;\n");
-                gk.first_trip_plane_tests += o.portal ? 2 : 1;
-            }
-        for (auto& m : snippet.members) s.add_string("    " + m.type + " " + m.name + (m.length ? "[" + std::to_string(m.length) + "]" : "") + ";\n");
-        s.add_string("};\n");
-        s.add_string("#if PTL_DEVICE_BUILD\n__constant__ ptl_uniform_block ptl_u;\n#else\nptl_uniform_block ptl_u;\n#endif\n");
-        // where the kernel reads uniforms from: the __constant__ block through the scalar cache
-        // (default), or a per-workgroup LDS copy (-DPTL_UNIFORMS_IN_LDS, staged in ptl_entry.h)
-        s.add_string("#if PTL_DEVICE_BUILD && defined(PTL_UNIFORMS_IN_LDS)\n__shared__ ptl_uniform_block ptl_lds_u;\n#define PTL_U ptl_lds_u\n"
-                     "#elif PTL_DEVICE_BUILD && defined(PTL_UNIFORM_RELOAD)\n"
-                     "// every access goes through a pointer the optimiser cannot see through: scalar loads stay where they are\n"
-                     "// used instead of being hoisted out of the bounce loop and spilled (SGPR -> VGPR lanes)\n"
-                     "PTL_FN const ptl_uniform_block& ptl_ublock() { const ptl_uniform_block* p = &ptl_u; asm volatile(\"\" : \"+s\"(p)); return *p; }\n"
-                     "#define PTL_U (ptl_ublock())\n"
-                     "#else\n#define PTL_U ptl_u\n#endif\n");
-        for (auto& u : list)
-            s.add_string("static_assert(__builtin_offsetof(ptl_uniform_block, " + u.name + ") == " + std::to_string(u.offset) + ", \"uniform layout\");\n");
-        for (auto& u : list) {
-            auto it = baked.find(u.name);
-            if (it != baked.end()) s.add_string("#define " + u.name + " (" + it->second + ")\n");
-            else s.add_string("#define " + u.name + " (PTL_U." + u.name + ")\n");
-        }
-        for (auto& [name, mask] : gk.masked) {
-            char hex[96];
-            const unsigned ones = (unsigned)((mask >> 16) & 0xffffu), negs = (unsigned)((mask >> 32) & 0xffffu);
-            if (ones | negs) std::snprintf(hex, sizeof hex, "0x%04xu | PTL_UNIT_BITS(0x%04x, 0x%04x)", (unsigned)(mask & 0xffffu), ones, negs);
-            else std::snprintf(hex, sizeof hex, "0x%04xu", (unsigned)(mask & 0xffffu));
-            s.add_string("#define PTL_MASK_" + name + " " + hex + "\n");
-        }
-        storages["uniforms"] = std::move(s);
+// Every snippet of the scene, in the order the affine scan reports and the hoister numbers its members by: library, Complex materials,
+// Flat / Complex objects, intersection materials.
+std::vector<SceneSnippet> scene_snippets(const Scene& scene, const CodegenFlags& flags) {
+    std::vector<SceneSnippet> out;
+    auto add = [&](SceneSnippet::Kind kind, const std::string& code, bool portal) { out.push_back({kind, &code, portal, filter_tagged_lines(code, flags), {}, {}, {}}); };
+    for (const NamedCode& lib : scene.library) add(SceneSnippet::Library, lib.code, false);
+    for (const Material& m : scene.materials)
+        if (m.kind == Material::Complex) add(SceneSnippet::MaterialBody, m.code, false);
+    for (const Object& o : scene.objects)
+        if (o.kind == Object::Flat || o.kind == Object::Complex) add(o.kind == Object::Flat ? SceneSnippet::FlatObject : SceneSnippet::ComplexObject, o.code, o.portal);
+    for (const NamedCode& im : scene.intersection_materials) add(SceneSnippet::IntersectionMaterial, im.code, false);
+    return out;
+}
+
+struct BuildPlan {
+    std::vector<UniformDesc> uniforms;  // the block's layout: samplers first, then Scene::uniforms() order, with offsets
+    size_t uniform_block_size = 0;
+    std::map<std::string, std::string> baked;  // uniforms compiled in: name -> literal
+    std::vector<UniformUpload> baked_values;   // ... the scene's among them, with the values (GeneratedKernel::baked)
+    // Int uniforms baked into this build, with their values: a counting loop `for (int k = 0; k < NAME_u; k++)` of a snippet whose bound
+    // is one of them (and small) is unrolled.  The same operations in the same order -- identical frames -- but every iteration
+    // then has its own constants: the loop counter (`size` of scenes/portal_in_portal.ron:1144 drives an inner loop and a material
+    // index) and, with the matrices baked too, whatever the iteration does to loop-carried uniform values.  Measured on the headline
+    // (profiles/r03/stub_profile.jsonl `pip_unrolled`, variants5_unroll.jsonl): 0.409 -> 0.350 ms, same frame hash.
+    std::map<std::string, int> unroll_bounds;
+    bool full_chains = false;  // no matrix product is shortened (GeneratedKernel::full_chains)
+    std::vector<std::pair<std::string, MatrixPattern>> masked;
+    bool affine_rays = false;
+    std::string affine_rays_refused_because;
+    bool cheap_transforms = false;     // affine rays: a transform is a few additions, and the two dodges of it are dropped (plan_build):
+    bool defer_loop_updates = true;    // ... translate_glsl's deferred loop-carried ray transforms
+    bool first_trip_snippets = false;  // ... first-trip copies of the intersection-material snippets
+    std::vector<DerivedPlane> derived;
+    int first_trip_plane_tests = 0;  // > 0: the generated plane tests get their first-trip form (ptl_dvo_<object>_<side> members), this many
+    std::vector<SceneSnippet> snippets;
+    int bounded_snippet_blocks = 0;
+    std::vector<HoistedMember> hoisted_members;  // block members that hold uniform-only work of the snippets ...
+    std::string hoisted_prologue;                // ... and the GLSL that fills them
+
+    const SceneSnippet& snippet(const std::string& code) const {
+        for (const SceneSnippet& s : snippets)
+            if (s.code == &code) return s;
+        throw std::logic_error("BuildPlan: a scene text that is no snippet");
     }
-
-    // --- materials (scene.rs:720-845) -----------------------------------------------------
-    {
-        StringStorage processing, defines;
-        int counter = 0;
-        // Round 6 -- table-driven Simple materials (KernelOptions::material_table).  The reference prints one `else if (i.material == X_M) return
-        // material_simple2(hit, r, <nine literals>)` per material (scene.rs:736-760): 30 of the headline's 34, each an inlined copy of the same body
-        // behind its own compare-and-branch, and a wave that straddles two materials runs two copies.  Here the nine literals of every Simple material
-        // (and of the three DEBUG_* system materials) sit in a table indexed by the material id -- staged in LDS per workgroup by the kernel entries,
-        // read back per lane with two ds_read_b128 -- and ONE call of material_simple2 serves all of them.  Same function, same argument values, same
-        // operation order: no bit moves (a literal `1.0f - 0.5f` folded by the compiler is the value the instruction computes).
-        struct TableEntry { float color[3], normal_coef, grid_scale, grid_coef; unsigned flags; };  // flags: 1 grid, 2 grid2, 4 grid3, 8 present
-        std::map<int, TableEntry> table;
-        if (opts.material_table != 0) {
-            const float hi = 0.9f, lo = 0.2f;  // src/library.glsl:387-398 via ptl_trace.tpl: color(0.9, 0.2, 0.2) = the squares, one binary32 multiplication each
-            const float hh = hi * hi, ll = lo * lo;
-            table[3] = TableEntry{{hh, ll, ll}, 0.5f, 1.0f, 0.0f, 8u};  // DEBUG_RED / GREEN / BLUE
-            table[4] = TableEntry{{ll, hh, ll}, 0.5f, 1.0f, 0.0f, 8u};
-            table[5] = TableEntry{{ll, ll, hh}, 0.5f, 1.0f, 0.0f, 8u};
-        }
-        for (const Material& m : scene.materials) {
-            std::string name_m = m.name + "_M";
-            defines.add_string("#define " + name_m + " (USER_MATERIAL_OFFSET + " + std::to_string(counter++) + ")\n");
-            if (opts.material_table != 0 && m.kind == Material::Simple) {
-                table[10 + counter - 1] = TableEntry{{(float)m.color[0], (float)m.color[1], (float)m.color[2]}, (float)m.normal_coef, (float)m.grid_scale, (float)m.grid_coef,
-                                                     8u | (m.grid ? 1u : 0u) | (m.grid2 ? 2u : 0u) | (m.grid3 ? 4u : 0u)};
-                continue;
-            }
-            processing.add_string("} else if (i.material == " + name_m + ") {\n");
-            switch (m.kind) {
-                case Material::Simple:
-                    processing.add_string("return material_simple2(hit, r, vec3(" + f32_literal(m.color[0]) + ", " + f32_literal(m.color[1]) + ", " +
-                                          f32_literal(m.color[2]) + "), " + f32_literal(m.normal_coef) + ", " + bool_lit(m.grid) + ", " +
-                                          f32_literal(m.grid_scale) + ", " + f32_literal(m.grid_coef) + ", " + bool_lit(m.grid2) + ", " + bool_lit(m.grid3) + ");\n");
-                    break;
-                case Material::Reflect:
-                    processing.add_string("return material_reflect(hit, r, vec3(" + f32_literal(m.color[0]) + ", " + f32_literal(m.color[1]) + ", " +
-                                          f32_literal(m.color[2]) + "));\n");
-                    break;
-                case Material::Refract:
-                    processing.add_string("return material_refract(hit, r, vec3(" + f32_literal(m.color[0]) + ", " + f32_literal(m.color[1]) + ", " +
-                                          f32_literal(m.color[2]) + "), " + f32_literal(m.refractive_index) + ");\n");
-                    break;
-                case Material::Complex:
-                    processing.add_identifier_string({"material", m.name}, snippet(m.code));
-                    processing.add_string("\n");
-                    break;
-            }
-        }
-        for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
-            const Object& o = scene.objects[pos];
-            if (o.kind == Object::DebugMatrix || !o.portal) continue;
-            if (o.m0 < 0 || o.m1 < 0) continue;
-            const std::string& a = matrix_name(scene, o.m0, o);
-            const std::string& b = matrix_name(scene, o.m1, o);
-            std::string m1 = "teleport_" + std::to_string(pos) + "_1_M", m2 = "teleport_" + std::to_string(pos) + "_2_M";
-            defines.add_string("#define " + m1 + " (USER_MATERIAL_OFFSET + " + std::to_string(counter++) + ")\n");
-            defines.add_string("#define " + m2 + " (USER_MATERIAL_OFFSET + " + std::to_string(counter++) + ")\n");
-            // material_teleport(hit, r, M) (library.glsl:366-379) spelled as its body: behind the function parameter the product with M is out of
-            // reach of the zero / unit patterns (apply_zero_masks rewrites `transform(<uniform>, ..)` by name) -- the same two calls, same values
-            processing.add_string("} else if (i.material == " + m1 + ") {\n");
-            processing.add_string("return material_teleport_transformed(transform(" + teleport_name(a, b) + ", r), hit.n);");
-            processing.add_string("} else if (i.material == " + m2 + ") {\n");
-            processing.add_string("return material_teleport_transformed(transform(" + teleport_name(b, a) + ", r), hit.n);");
-        }
-        if (opts.material_table != 0) {
-            const int entries = table.rbegin()->first + 1;
-            auto bits = [](float v) {
-                unsigned u;
-                std::memcpy(&u, &v, 4);
-                char buf[16];
-                std::snprintf(buf, sizeof buf, "0x%08xu", u);
-                return std::string(buf);
-            };
-            std::string init, masks;
-            for (int id = 0; id < entries; ++id) {
-                auto it = table.find(id);
-                const TableEntry e = it == table.end() ? TableEntry{{0, 0, 0}, 0, 0, 0, 0u} : it->second;
-                init += "    " + bits(e.color[0]) + ", " + bits(e.color[1]) + ", " + bits(e.color[2]) + ", " + bits(e.normal_coef) + ", " + bits(e.grid_scale) + ", " +
-                        bits(e.grid_coef) + ", " + std::to_string(e.flags) + "u, 0u,\n";
-            }
-            for (int w = 0; w * 64 < entries; ++w) {
-                unsigned long long mask = 0;
-                for (int b = 0; b < 64; ++b)
-                    if (table.count(w * 64 + b)) mask |= 1ull << b;
-                char buf[48];
-                std::snprintf(buf, sizeof buf, "0x%016llxull", mask);
-                masks += std::string(w ? ", " : "") + buf;
-            }
-            defines.add_string("#define PTL_MATERIAL_TABLE " + std::to_string(opts.material_table) + "\n#define PTL_MATERIAL_TABLE_WORDS " + std::to_string(entries * 8) + "\n"
-                               "// per material id: colour x y z, normal_coef | grid_scale, grid_coef, flags (1 grid, 2 grid2, 4 grid3, 8 = a Simple material), 0 -- binary32 bit patterns\n"
-                               "#if PTL_DEVICE_BUILD && PTL_MATERIAL_TABLE == 1\n__constant__ const unsigned int ptl_material_table_init[PTL_MATERIAL_TABLE_WORDS] = {\n" + init + "};\n"
-                               "__shared__ __attribute__((aligned(16))) unsigned int ptl_material_table[PTL_MATERIAL_TABLE_WORDS];  // filled by the kernel entries (ptl_entry.h)\n"
-                               "#elif PTL_DEVICE_BUILD\n__constant__ const unsigned int ptl_material_table[PTL_MATERIAL_TABLE_WORDS] __attribute__((aligned(32))) = {\n" + init + "};\n"
-                               "#else\nstatic const unsigned int ptl_material_table[PTL_MATERIAL_TABLE_WORDS] __attribute__((aligned(16))) = {\n" + init + "};\n#endif\n"
-                               "PTL_FN bool ptl_material_in_table(int id) {\n"
-                               "    const unsigned long long masks[] = {" + masks + "};\n"
-                               "    return (unsigned)id < " + std::to_string(entries) + "u && ((masks[(unsigned)id >> 6] >> ((unsigned)id & 63u)) & 1ull) != 0;\n}\n");
-        }
-        storages["material_processing"] = std::move(processing);
-        storages["materials_defines"] = std::move(defines);
+    bool any_first_snippet() const {
+        return std::any_of(snippets.begin(), snippets.end(), [](const SceneSnippet& s) { return !s.hoisted_first.empty(); });
     }
+};
 
-    // --- is_inside_N / intersect_N (scene.rs:847-883) --------------------------------------
-    {
-        StringStorage s;
-        for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
-            const Object& o = scene.objects[pos];
-            std::string p = std::to_string(pos);
-            if (o.kind == Object::Flat) {
-                if (o.portal) s.add_string("PTL_FN int is_inside_" + p + "(vec4 pos, float x, float y, bool back, bool first) {\n");
-                else s.add_string("PTL_FN int is_inside_" + p + "(vec4 pos, float x, float y, bool back) {\n");
-                s.add_identifier_string({"object", o.name}, snippet(o.code));
-                s.add_string("\n}\n");
-            } else if (o.kind == Object::Complex) {
-                if (o.portal) s.add_string("PTL_FN SceneIntersection intersect_" + p + "(Ray r, bool first) {\n");
-                else s.add_string("PTL_FN SceneIntersection intersect_" + p + "(Ray r) {\n");
-                s.add_identifier_string({"object", o.name}, snippet(o.code));
-                s.add_string("\n}\n");
-            }
-        }
-        storages["intersection_functions"] = std::move(s);
+// "this build may shorten matrix products at all" (masks, or literal matrices whose zero terms are dropped) ...
+bool may_shorten_products(const KernelOptions& opts) { return opts.mask_zero_elements || opts.specialize_all || opts.specialize_static; }
+// ... and "what it shortens stays exact": contract 2, no tolerance mode, every matrix finite
+bool short_chains_exact(const KernelOptions& opts, bool full_chains) { return !opts.exact_cr && !opts.fast_math && !full_chains; }
+
+void plan_uniform_layout(const Scene& scene, BuildPlan& plan) {
+    std::vector<UniformDesc>& list = plan.uniforms;
+    for (auto& tex : scene_texture_list(scene)) list.push_back({tex, UniformType::Sampler, 0});
+    for (auto& u : scene_uniform_list(scene)) list.push_back(u);
+    size_t off = 0;
+    for (auto& u : list) {
+        u.offset = off;
+        off += uniform_type_size(u.type);
     }
+    bool has_sampler = !list.empty() && list[0].type == UniformType::Sampler;  // pointer member -> 8-byte struct alignment
+    plan.uniform_block_size = has_sampler ? ((off + 7) & ~(size_t)7) : off;
+}
 
-    // --- per-object intersection statements (scene.rs:885-1009) ----------------------------
-    // Emitted once in the general form and, with KernelOptions::first_trip_planes, once more for the trip on which every ray of the wave
-    // still starts at the camera: there `plane_inv * r.o` of a Flat object is the prologue's `ptl_dvo_<object>_<side>` (derive() below
-    // evaluates the very product on the very origin), and the plane test / the cull take it instead of transforming the origin per lane.
-    auto emit_intersections = [&](bool first_form) {
-        StringStorage s;
-        for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
-            const Object& o = scene.objects[pos];
-            std::string p = std::to_string(pos);
-            auto open_guard = [&] {
-                if (o.in_subspace == Subspace::Normal) s.add_string("if (r.in_subspace == false) {");
-                else if (o.in_subspace == Subspace::Subspace) s.add_string("if (r.in_subspace == true) {");
-            };
-            auto close_guard = [&] {
-                if (o.in_subspace != Subspace::Both) s.add_string("}");
-            };
-            auto transformed = [&](const std::string& inv) {
-                s.add_string("transformed_ray = transform(" + inv + ", r);\nlen = length(transformed_ray.d);\ntransformed_ray = normalize_ray(transformed_ray);");
-            };
-            if (o.kind == Object::DebugMatrix) {
-                const std::string& m = matrix_name(scene, o.m0, o);
-                transformed(inverse_name(m));
-                s.add_string("ihit = debug_intersect(transformed_ray);\nihit.hit.t = ptl_div(ihit.hit.t, len);\n");
-                // quirk kept from the reference: the normal uses adjugate of the *inverse* matrix here
-                s.add_string("if (nearer(i, ihit)) { i = ihit; i.hit.n = normalize(adjugate(" + inverse_name(m) + ") * i.hit.n); }\n\n");
-            } else if (o.kind == Object::Flat) {
-                open_guard();
-                auto derived_of = [&](int side) -> const DerivedPlane* {
-                    for (auto& d : gk.derived)
-                        if (d.object == (int)pos && d.side == side) return &d;
-                    return nullptr;
-                };
-                // with a derived entry: the unit normal and both is_collinear verdicts come from the prologue kernel
-                // (ptl_tracer::derive below evaluates exactly the expressions of the plain form)
-                // first form: the transformed origin of this test, and the `_o` variants of the cull and the plane test that take it
-                auto origin_of = [&](int side) { return "PTL_U.ptl_dvo_" + p + "_" + std::to_string(side); };
-                auto cull_call = [&](const std::string& inv, int side) {
-                    return first_form ? "ptl_plane_cull_o(r, " + inv + ", " + origin_of(side) + ", PTL_BEST_T(i))" : "ptl_plane_cull(r, " + inv + ", PTL_BEST_T(i))";
-                };
-                auto derived_test = [&](const DerivedPlane& d, const std::string& inv, const std::string& process_open, const std::string& extra_args,
-                                        const std::string& process_close) {
-                    s.add_string("if (!" + cull_call(inv, d.side) + ") {\n");
-                    if (first_form) s.add_string("hit = plane_intersect_derived_o(r, " + inv + ", PTL_U." + d.member + "_nrm, flipped, " + origin_of(d.side) + ");\n");
-                    else
-                    s.add_string("hit = plane_intersect_derived(r, " + inv + ", PTL_U." + d.member + "_nrm, flipped);\n");
-                    s.add_string("if (nearer(i, hit)) { i = " + process_open + "is_inside_" + p + "(r.o + r.d * hit.t, hit.u, hit.v, ((PTL_U." + d.member +
-                                 "_col >> (flipped ? 1 : 0)) & 1) != 0" + extra_args + ")" + process_close + "; }\n}\n\n");
-                };
-                if (!o.portal) {
-                    const std::string& m = matrix_name(scene, o.m0, o);
-                    if (const DerivedPlane* d = derived_of(0)) {
-                        derived_test(*d, inverse_name(m), "process_plane_intersection(i, hit, ", "", ")");
-                    } else {
-                        s.add_string("if (!" + cull_call(inverse_name(m), 0) + ") {\n");
-                        s.add_string("normal = -get_normal(" + normal_name(m) + ");\n");
-                        if (first_form) s.add_string("hit = plane_intersect_o(r, " + inverse_name(m) + ", get_normal(" + normal_name(m) + "), " + origin_of(0) + ");\n");
-                        else
-                        s.add_string("hit = plane_intersect(r, " + inverse_name(m) + ", get_normal(" + normal_name(m) + "));\n");
-                        s.add_string("if (nearer(i, hit)) { i = process_plane_intersection(i, hit, is_inside_" + p +
-                                     "(r.o + r.d * hit.t, hit.u, hit.v, is_collinear(hit.n, normal))); }\n}\n\n");
-                    }
-                } else {
-                    auto side = [&](const std::string& m, bool first, const std::string& material) {
-                        if (const DerivedPlane* d = derived_of(first ? 0 : 1)) {
-                            derived_test(*d, inverse_name(m), "process_portal_intersection(i, hit, ", std::string(", ") + bool_lit(first), ", " + material + ")");
-                            return;
-                        }
-                        s.add_string("if (!" + cull_call(inverse_name(m), first ? 0 : 1) + ") {\n");
-                        s.add_string(std::string("normal = ") + (first ? "-" : "") + "get_normal(" + normal_name(m) + ");\n");
-                        if (first_form) s.add_string("hit = plane_intersect_o(r, " + inverse_name(m) + ", normal, " + origin_of(first ? 0 : 1) + ");\n");
-                        else
-                        s.add_string("hit = plane_intersect(r, " + inverse_name(m) + ", normal);\n");
-                        s.add_string("if (nearer(i, hit)) { i = process_portal_intersection(i, hit, is_inside_" + p +
-                                     "(r.o + r.d * hit.t, hit.u, hit.v, is_collinear(hit.n, normal), " + bool_lit(first) + "), " + material + "); }\n}\n\n");
-                    };
-                    const std::string& a = matrix_name(scene, o.m0, o);
-                    const std::string& b = matrix_name(scene, o.m1, o);
-                    side(a, true, "teleport_" + p + "_1_M");
-                    side(b, false, "teleport_" + p + "_2_M");
-                }
-                close_guard();
-            } else {  // Complex
-                open_guard();
-                if (!o.portal) {
-                    const std::string& m = matrix_name(scene, o.m0, o);
-                    transformed(inverse_name(m));
-                    s.add_string("ihit = intersect_" + p + "(transformed_ray);\nihit.hit.t = ptl_div(ihit.hit.t, len);\n");
-                    s.add_string("if (nearer(i, ihit)) { i = ihit; i.hit.n = normalize(adjugate(" + normal_name(m) + ") * i.hit.n); }\n\n");
-                } else {
-                    auto side = [&](const std::string& m, bool first, const std::string& material) {
-                        transformed(inverse_name(m));
-                        s.add_string("ihit = intersect_" + p + "(transformed_ray, " + bool_lit(first) + ");\nihit.hit.t = ptl_div(ihit.hit.t, len);\n");
-                        s.add_string("if (nearer(i, ihit) && ihit.material != NOT_INSIDE) { if (ihit.material == TELEPORT) { ihit.material = " + material +
-                                     "; } if (ihit.material == TELEPORT_SUBSPACE) { ihit.material = " + material +
-                                     "; ihit.in_subspace = true; } i = ihit; i.hit.n = normalize(adjugate(" + normal_name(m) + ") * i.hit.n); }\n\n");
-                    };
-                    const std::string& a = matrix_name(scene, o.m0, o);
-                    const std::string& b = matrix_name(scene, o.m1, o);
-                    side(a, true, "teleport_" + p + "_1_M");
-                    side(b, false, "teleport_" + p + "_2_M");
-                }
-                close_guard();
-            }
-            s.add_string("\n");
-        }
-        return s;
+// JIT-time specialisation: current values baked in as literals (same arithmetic, the
+// compiler folds branches on mode switches / ray-independent subexpressions)
+void plan_baked_values(const std::vector<UniformUpload>& values, const KernelOptions& opts, BuildPlan& plan) {
+    if (!(opts.specialize_ints || opts.specialize_all || opts.specialize_static || opts.specialize_static_ints)) return;
+    auto hexf = [](float v) -> std::string {
+        if (std::isnan(v)) return "__builtin_nanf(\"\")";
+        if (std::isinf(v)) return v > 0 ? "__builtin_inff()" : "(-__builtin_inff())";
+        char buf[48];
+        std::snprintf(buf, sizeof buf, "%af", (double)v);
+        return buf;
     };
-    storages["intersections"] = emit_intersections(false);
-    storages["intersections_first"] = gk.first_trip_plane_tests > 0 ? emit_intersections(true) : StringStorage();
-
-    // --- prologue: the ray-independent part of every derived plane test, once per uniform upload ----------
-    {
-        StringStorage s;
-        if (gk.first_trip_plane_tests > 0) {
-            s.add_string("    // first-trip plane tests: plane_inv * (origin of every primary ray), the product transform() would evaluate per lane\n");
-            for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
-                const Object& o = scene.objects[pos];
-                if (o.kind != Object::Flat) continue;
-                s.add_string("    out->ptl_dvo_" + std::to_string(pos) + "_0 = " + inverse_name(matrix_name(scene, o.m0, o)) + " * out->ptl_dv_origin;\n");
-                if (o.portal) s.add_string("    out->ptl_dvo_" + std::to_string(pos) + "_1 = " + inverse_name(matrix_name(scene, o.m1, o)) + " * out->ptl_dv_origin;\n");
-            }
-        }
-        for (auto& d : gk.derived) {
-            s.add_string("    {\n        vec3 normal = " + d.normal_expr + ";\n        vec3 unit = normalize(" + d.arg_expr + ");\n");
-            s.add_string("        out->" + d.member + "_nrm = unit;\n");
-            s.add_string("        out->" + d.member + "_col = (is_collinear(unit, normal) ? 1 : 0) | (is_collinear(unit * -1.0f, normal) ? 2 : 0);\n    }\n");
-        }
-        if (!snippet.prologue.empty()) {
-            s.add_string("    // uniform-only work of the scene snippets (host/glsl_hoist.h)\n");
-            s.add_string(translate_glsl(snippet.prologue, false));
-        }
-        gk.hoisted_members = (int)snippet.members.size();
-        storages["derive"] = std::move(s);
-    }
-
-    // --- intersection materials (scene.rs:1011-1035) --------------------------------------
-    {
-        StringStorage fns, calls, calls_first;
-        bool any_first = false;
-        for (size_t pos = 0; pos < scene.intersection_materials.size(); ++pos) any_first = any_first || snippet.has_first(scene.intersection_materials[pos].code);
-        for (size_t pos = 0; pos < scene.intersection_materials.size(); ++pos) {
-            const NamedCode& im = scene.intersection_materials[pos];
-            fns.add_string("PTL_FN SceneIntersectionWithMaterial intersect_material_" + std::to_string(pos) + "(Ray r, float ptl_far) {\n(void)ptl_far; ");
-            fns.add_identifier_string({"intersection_material", im.name}, snippet(im.code));
-            fns.add_string("\n}\n");
-            calls.add_string("hit = intersect_material_" + std::to_string(pos) + "(r, ptl_far);\n");
-            calls.add_string("if (nearer(result.scene.hit, hit.scene.hit)) { result = hit; }\n\n");
-            if (!any_first) continue;
-            const bool own = snippet.has_first(im.code);  // (a snippet without ray chains: its general form serves the first trip too)
-            if (own) {
-                fns.add_string("PTL_FN SceneIntersectionWithMaterial intersect_material_" + std::to_string(pos) + "_first(Ray r, float ptl_far) {\n(void)ptl_far; ");
-                fns.add_string(snippet.first(im.code));
-                fns.add_string("\n}\n");
-            }
-            calls_first.add_string("hit = intersect_material_" + std::to_string(pos) + (own ? "_first" : "") + "(r, ptl_far);\n");
-            calls_first.add_string("if (nearer(result.scene.hit, hit.scene.hit)) { result = hit; }\n\n");
-        }
-        gk.first_trip_variants = any_first;
-        // A loop in an intersection-material snippet (portal_in_portal's ten nested copies) puts the deepest call chain of the kernel inside a
-        // loop nest; unrolled -- its bound a baked Int (`unrolled()` above) -- it multiplies the body that LLVM's bottom-up inliner pipeline
-        // re-simplifies at every call level: the kernels whose hiprtc time that pipeline dominates (kernel.cpp compile_options;
-        // tools/jit_inliner_survey.py).  The JIT switches to the module inliner for them.  Only for them: it needs ~10 more VGPRs, which the
-        // baked builds have (115 -> 125 of 128) and the others do not (patterns build with the slices entry: 120 -> 139, a wave per SIMD lost).
-        for (const NamedCode& im : scene.intersection_materials) {
-            bool loops = false;
-            for (const Token& t : tokenize_glsl(filter_tagged_lines(im.code, flags)))
-                if (t.kind == Token::Ident && (t.text == "for" || t.text == "while")) loops = true;
-            if (loops && snippet(im.code).find("_Pragma(\"unroll\")") != std::string::npos) gk.looped_snippets = true;
-        }
-        storages["intersection_material_functions"] = std::move(fns);
-        storages["intersection_material_processing"] = std::move(calls);
-        storages["intersection_material_processing_first"] = std::move(calls_first);
-    }
-
-    // --- library (scene.rs:1037-1044) -----------------------------------------------------
-    {
-        StringStorage s;
-        for (const NamedCode& lib : scene.library) {
-            // scene functions are plain GLSL functions: the translation puts PTL_FN in front of every definition
-            s.add_identifier_string({"library", lib.name}, snippet.library(lib.code));
-        }
-        storages["library"] = std::move(s);
-    }
-
-    // --- prelude + skybox -----------------------------------------------------------------
-    {
-        StringStorage s;
-        s.add_string(device_source_glsl());
-        s.add_string("\n");
-        storages["predefined_library"] = std::move(s);
-    }
-    {
-        StringStorage s;
-        if (scene.skybox) {
-            s.add_string("vec4 rd2 = ptl_mul_runtime(_camera_mul_inv, r.d);");
-            s.add_string("float u = atan(rd2.z, rd2.x);");
-            s.add_string("float v = atan(sqrt(rd2.x * rd2.x + rd2.z * rd2.z), rd2.y);");
-            s.add_string("vec3 not_found_color = sqrvec(texture(" + *scene.skybox + "_tex, vec2(ptl_div(ptl_div(u, PI) + 1.0f, 2.0f), ptl_div(v, PI))).sw<0,1,2>());");
+    for (auto& up : values) {
+        if (up.name == "teleport_light_u") continue;  // forced to 1 by the camera-teleport query (src/main.rs:1367)
+        if (opts.keep_dynamic.count(up.name)) continue;
+        if (opts.specialize_static && up.animated) continue;  // changes every frame: stays a run-time uniform
+        const bool switches_only = opts.specialize_static_ints && !(opts.specialize_ints || opts.specialize_all || opts.specialize_static);
+        if (switches_only && (up.animated || up.type != UniformType::Int1)) continue;  // the patterns build: only the Bool / Int uniforms that hold still
+        bool all = opts.specialize_all || opts.specialize_static;
+        if (up.type == UniformType::Int1) {
+            plan.baked[up.name] = std::to_string(up.i);
+            if (opts.unroll_baked_loops) plan.unroll_bounds[up.name] = up.i;
+        } else if (all && up.type == UniformType::Float1) {
+            plan.baked[up.name] = hexf(up.f[0]);
+        } else if (all && up.type == UniformType::Mat4) {
+            std::string m = "mat4(";
+            for (int k = 0; k < 16; ++k) m += (k ? ", " : "") + hexf(up.f[k]);
+            plan.baked[up.name] = m + ")";
         } else {
-            s.add_string("vec3 not_found_color = color(0.6f, 0.6f, 0.6f);");
+            continue;
         }
-        storages["skybox_processing"] = std::move(s);
+        plan.baked_values.push_back(up);
     }
+}
 
+// Shortened products are exact for finite vectors (device/ptl_glsl.h, "the deviation, stated"): a skipped `0 * x` would have been NaN
+// for an infinite or NaN x.  Where such vectors come from is known at generation time -- a matrix with non-finite elements (the
+// inverse of a zero scale, 1/0 in a formula) -- so it is decided here, for the whole kernel:
+//   * a matrix that is NaN in EVERY element (glam's inverse of a matrix scaled to zero on all axes: how the reference's scenes switch
+//     an object off, scenes/portal_in_portal.ron `c0`) turns every vector into all-NaN, and NaN times a retained non-zero element is
+//     NaN in the short chain as in the full one: allowed;
+//   * any other non-finite matrix (infinities, or NaN beside numbers) produces +-inf components, for which the two chains do differ
+//     (inf * 1 against inf * 1 + 0 * inf = NaN): the kernel keeps every full chain (GeneratedKernel::full_chains).
+bool plan_full_chains(const std::vector<UniformUpload>& values, const KernelOptions& opts) {
+    if (opts.full_chains || !may_shorten_products(opts)) return opts.full_chains;
+    for (auto& up : values)
+        if (up.type == UniformType::Mat4 && matrix_breaks_short_chains(up.f)) return true;
+    return false;
+}
+
+// the state the zero patterns depend on: stage / clip, every value that is not animated (the probes move the animated ones themselves)
+std::string zero_mask_cache_key(const Scene& scene, const std::vector<UniformUpload>& values, const std::map<std::string, std::string>& baked, const KernelOptions& opts) {
+    std::string key;
+    auto put = [&key](const void* p, size_t n) { key.append(static_cast<const char*>(p), n); };
+    const int stage[3] = {(int)scene.current_stage.kind, scene.current_stage.index, scene.run_animations ? 1 : 0};
+    put(stage, sizeof stage);
+    for (auto& up : values) {
+        key += up.name;
+        key += up.animated ? '~' : '=';
+        if (!up.animated) {
+            put(up.f, sizeof up.f);
+            put(&up.i, sizeof up.i);
+        }
+        key += baked.count(up.name) ? 'b' : (opts.keep_unmasked.count(up.name) ? 'k' : 'r');
+    }
+    return key;
+}
+
+// The patterns in `found` of the matrices that move, taken over the whole clip.  A matrix that reads the formulas' `time` is identity-like
+// exactly when a clip starts -- the moment a clip-constant kernel is generated: the union over probes of `time` in [0, 1] (a copy of the scene;
+// the pattern of an animation changes at its end points or nowhere, a probe that misses something costs one rebuild, not a pixel).
+void probe_animated_patterns(const Scene& scene, const std::vector<UniformUpload>& values, std::vector<std::pair<std::string, MatrixPattern>>& found) {
+    auto take = [&](const Scene& probe) {
+        for (auto& up : evaluate_scene_uniforms(probe, nullptr))
+            if (up.type == UniformType::Mat4 && up.animated)
+                for (auto& f : found)
+                    if (f.first == up.name) f.second = combine_patterns(f.second, matrix_pattern(up.f));
+    };
+    Scene probe = scene;
+    const bool in_clip = !scene.run_animations && scene.current_stage.kind == StageRef::RealAnimation && scene.current_stage.index >= 0 &&
+                         scene.current_stage.index < (int)scene.animations.size() && scene.animations[scene.current_stage.index].duration > 0.0;
+    if (in_clip) {
+        // inside a clip: the video pipeline's own step (Scene::update) at 33 moments of the clip.  On the reference's corpus (471 clips,
+        // patterns taken on a 240-point grid) 7 probes miss something in 16 clips, 16 in 10, 32 in none: elements like cos(pi/2)
+        // flicker between 0 and 1e-17, and every miss is a rebuild in the middle of a clip
+        const double duration = scene.animations[scene.current_stage.index].duration;
+        try {
+            for (int k = 0; k <= 32; ++k) {
+                probe.update(duration * (k < 32 ? k / 32.0 : 0.999999));
+                take(probe);
+            }
+        } catch (const std::exception&) {  // a clip whose cameras cannot be evaluated fails where it is played, not here: no pattern for what moves
+            for (auto& up : values)
+                if (up.type == UniformType::Mat4 && up.animated)
+                    for (auto& f : found)
+                        if (f.first == up.name) f.second = 0xffffu;
+        }
+    } else {
+        for (double t : {0.0, 0.0625, 0.271, 0.5, 0.729, 0.9375, 1.0}) {
+            probe.time = t;
+            take(probe);
+        }
+    }
+    // The other per-frame input is the camera (Matrix::Camera): one probe gives it a matrix without a single zero, so that
+    // nothing that follows the camera is ever masked (a renderer is even created before its camera is known).
+    probe = scene;
+    probe.camera_matrix = DMat4::from_cols(DVec4(0.36, 0.48, -0.8, 0.013), DVec4(-0.8, 0.6, 0.017, 0.011), DVec4(0.48, 0.64, 0.6, 0.019), DVec4(0.37, -1.21, 2.53, 1.0));
+    take(probe);
+}
+
+// KernelOptions::mask_zero_elements: the zero / unit pattern of every matrix that stays a run-time value, from the cache while the state it
+// was probed in still holds.
+std::vector<std::pair<std::string, MatrixPattern>> plan_zero_patterns(const Scene& scene, const std::vector<UniformUpload>& values, const std::map<std::string, std::string>& baked,
+                                                                      bool full_chains, const KernelOptions& opts) {
+    if (!opts.mask_zero_elements || !short_chains_exact(opts, full_chains)) return {};
+    auto run_time = [&](const UniformUpload& up) { return up.type == UniformType::Mat4 && !baked.count(up.name) && !opts.keep_unmasked.count(up.name); };
+    const std::string key = opts.mask_cache ? zero_mask_cache_key(scene, values, baked, opts) : std::string();
+    // (a hit must still cover what the animated matrices hold NOW: their values are not part of the key, and a build with baked Bool /
+    // Int uniforms has nothing but this generation between a moved value and the draw)
+    bool hit = opts.mask_cache && !key.empty() && key == opts.mask_cache->key;
+    if (hit)
+        for (auto& up : values) {
+            if (!run_time(up) || !up.animated) continue;
+            MatrixPattern mask = 0xffffu;
+            for (auto& m : opts.mask_cache->masked)
+                if (m.first == up.name) mask = m.second;
+            if (!pattern_holds(mask, up.f)) hit = false;
+        }
+    if (hit) {
+        ++opts.mask_cache->hits;
+        return opts.mask_cache->masked;
+    }
+    std::vector<std::pair<std::string, MatrixPattern>> found, masked;
+    bool any_animated = false;
+    for (auto& up : values) {
+        if (!run_time(up)) continue;
+        found.emplace_back(up.name, matrix_pattern(up.f));
+        any_animated = any_animated || up.animated;
+    }
+    if (any_animated) probe_animated_patterns(scene, values, found);
+    for (auto& f : found)
+        if (f.second != 0xffffu) masked.push_back(f);
+    if (opts.mask_cache) {
+        ++opts.mask_cache->misses;
+        opts.mask_cache->key = key;
+        opts.mask_cache->masked = masked;
+    }
+    return masked;
+}
+
+// Affine rays (KernelOptions::affine_rays): every matrix of the scene maps w = 1 to 1 and w = 0 to 0 (bottom row 0 0 0 1) -- or is NaN in
+// every element (a switched-off object: its products are NaN whatever the w) -- and no scene snippet writes a ray's w.  Only in builds
+// that may shorten products at all (the same deviation for non-finite rays, the same guard), i.e. never in the un-specialised build.
+// (the tolerance mode gets them too: it is not bit-exact anyway, and without them it was SLOWER than the exact kernel -- 0.217 against 0.191 ms)
+bool plan_affine_rays(const std::vector<UniformUpload>& values, const std::vector<SceneSnippet>& snippets, bool full_chains, const KernelOptions& opts, std::string* refused_because) {
+    if (!opts.affine_rays || opts.check_affine || opts.exact_cr || full_chains || !may_shorten_products(opts)) return false;
+    // (a matrix that stays a run-time value: what holds now is checked again by the renderer before every upload that could change it
+    // -- capi.cpp `zero_patterns_broken` for the builds that keep their kernel across scene states; the others come back here)
+    for (auto& up : values)
+        if (up.type == UniformType::Mat4 && !matrix_keeps_rays_affine(up.f)) return false;
+    if (opts.skip_affine_scan) return true;
+    std::vector<std::string> codes;
+    for (const SceneSnippet& s : snippets) codes.push_back(s.filtered);
+    return snippets_keep_rays_affine(codes, refused_because);
+}
+
+// first-trip plane tests (KernelOptions::first_trip_planes): `plane_inv * camera origin` per generated plane test, only where some Flat
+// object's matrix is a run-time value
+// (not with every scene uniform baked in: with the zero terms of the literal matrices skipped the origin half of a plane test
+// is a couple of FMAs, and the second copy of scene_intersect measured no gain there -- profiles/r03/variants7_first_trip_planes.jsonl)
+int plan_first_trip_planes(const Scene& scene, const std::map<std::string, std::string>& baked, const KernelOptions& opts) {
+    if (!(opts.derived_uniforms && opts.first_trip_planes)) return 0;
+    bool wanted = false;
+    int tests = 0;
+    for (const Object& o : scene.objects) {
+        if (o.kind != Object::Flat) continue;
+        wanted = wanted || !baked.count(inverse_name(matrix_name(scene, o.m0, o))) || (o.portal && !baked.count(inverse_name(matrix_name(scene, o.m1, o))));
+        tests += o.portal ? 2 : 1;
+    }
+    return wanted ? tests : 0;
+}
+
+// derived uniforms: one entry per plane test of a Flat object whose matrix is a run-time uniform
+std::vector<DerivedPlane> plan_derived_planes(const Scene& scene, const std::map<std::string, std::string>& baked, const KernelOptions& opts) {
+    std::vector<DerivedPlane> derived;
+    if (!opts.derived_uniforms) return derived;
+    for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
+        const Object& o = scene.objects[pos];
+        if (o.kind != Object::Flat) continue;
+        auto add = [&](int midx, int side, const std::string& normal_expr, const std::string& arg_expr) {
+            const std::string& m = matrix_name(scene, midx, o);
+            if (baked.count(normal_name(m))) return;  // literal matrix: the compiler folds all of this
+            DerivedPlane d;
+            d.object = (int)pos;
+            d.side = side;
+            d.member = "ptl_dv_" + std::to_string(pos) + "_" + std::to_string(side);
+            d.normal_expr = normal_expr + normal_name(m) + ")";
+            d.arg_expr = arg_expr + normal_name(m) + ")";
+            derived.push_back(d);
+        };
+        if (!o.portal) {
+            add(o.m0, 0, "-get_normal(", "get_normal(");
+        } else {
+            add(o.m0, 0, "-get_normal(", "-get_normal(");
+            add(o.m1, 1, "get_normal(", "get_normal(");
+        }
+    }
+    return derived;
+}
+
+// out / inout arguments are lowered to references: refuse the scenes for which that is not GLSL's copy in / copy out
+void check_snippet_out_arguments(const std::vector<SceneSnippet>& snippets) {
+    std::vector<std::string> file_scope, bodies;
+    for (const SceneSnippet& s : snippets) (s.kind == SceneSnippet::Library ? file_scope : bodies).push_back(s.filtered);
+    check_out_argument_aliasing(file_scope, bodies);
+}
+
+// the caller's distance bound inside the intersection-material snippets (KernelOptions::bound_snippets)
+void plan_bounded_snippets(BuildPlan& plan, const KernelOptions& opts) {
+    if (!opts.bound_snippets) return;
+    // process_portal_intersection never resets SceneIntersection::in_subspace (library.glsl:571-589): with subspace portals a skipped
+    // candidate could leave that flag behind, so a scene whose GLSL names them keeps its snippets as written
+    std::set<std::string> with_out;
+    for (const SceneSnippet& s : plan.snippets) {
+        if (s.kind == SceneSnippet::Library) functions_with_out_params(*s.code, with_out);
+        for (const Token& t : tokenize_glsl(*s.code))
+            if (t.kind == Token::Ident && (t.text == "TELEPORT_SUBSPACE" || t.text == "in_subspace")) return;
+    }
+    for (SceneSnippet& s : plan.snippets) {
+        if (s.kind != SceneSnippet::IntersectionMaterial) continue;
+        int n = 0;
+        std::string bounded = bound_nearer_blocks(s.filtered, with_out, &n);
+        if (n > 0) {
+            s.bounded = bounded;
+            plan.bounded_snippet_blocks += n;
+        }
+    }
+}
+
+// uniform-only work of the scene snippets: members behind the derived planes, filled by the same prologue kernel
+void plan_hoisted_work(BuildPlan& plan, const KernelOptions& opts) {
+    if (!(opts.derived_uniforms && opts.hoist_uniform_work)) return;
+    HoistParams base;
+    for (auto& u : plan.uniforms) {
+        if (u.type == UniformType::Sampler) continue;
+        if (plan.baked.count(u.name)) base.constants[u.name] = cxx_type(u.type);
+        else base.uniforms[u.name] = cxx_type(u.type);
+    }
+    for (const SceneSnippet& s : plan.snippets)
+        if (s.kind == SceneSnippet::Library) {
+            functions_with_out_params(*s.code, base.functions_with_out_params);
+            defined_functions(*s.code, base.scene_functions);
+        }
+    int next_member = 0;
+    auto hoist = [&](const SceneSnippet& s, const HoistParams& hp, std::string& into) {
+        HoistResult r = hoist_uniform_work(s.source(), hp, next_member);
+        if (r.members.empty()) return;
+        into = r.glsl;
+        plan.hoisted_members.insert(plan.hoisted_members.end(), r.members.begin(), r.members.end());
+        plan.hoisted_prologue += r.prologue;
+    };
+    for (SceneSnippet& s : plan.snippets) {
+        HoistParams hp = base;
+        hp.body_only = s.kind != SceneSnippet::Library;
+        switch (s.kind) {
+            case SceneSnippet::Library: break;
+            case SceneSnippet::MaterialBody: hp.body_params = {"hit", "r", "i"}; break;
+            case SceneSnippet::FlatObject: hp.body_params = {"pos", "x", "y", "back"}; break;
+            case SceneSnippet::ComplexObject: hp.body_params = {"r"}; break;
+            case SceneSnippet::IntersectionMaterial: hp.body_params = {"r", "ptl_far"}; break;
+        }
+        if (s.portal) hp.body_params.push_back("first");
+        hoist(s, hp, s.hoisted);
+    }
+    if (!plan.first_trip_snippets) return;
+    for (SceneSnippet& s : plan.snippets) {  // the first-trip variant of an intersection-material snippet: parameter `r` starts at the camera
+        if (s.kind != SceneSnippet::IntersectionMaterial) continue;
+        HoistParams hp = base;
+        hp.body_only = true;
+        hp.body_params = {"r", "ptl_far"};
+        hp.origin_uniform_rays = {"r"};
+        hp.origin_expr = "PTL_DV_OUT.ptl_dv_origin";
+        hoist(s, hp, s.hoisted_first);
+    }
+}
+
+// The decisions of one build, in the order in which they depend on each other.
+BuildPlan plan_build(const Scene& scene, const CodegenFlags& flags, const KernelOptions& opts, const std::vector<UniformUpload>& values) {
+    BuildPlan plan;
+    plan_uniform_layout(scene, plan);
+    plan_baked_values(values, opts, plan);
+    plan.full_chains = plan_full_chains(values, opts);
+    plan.masked = plan_zero_patterns(scene, values, plan.baked, plan.full_chains, opts);
+    plan.snippets = scene_snippets(scene, flags);
+    plan.affine_rays = plan_affine_rays(values, plan.snippets, plan.full_chains, opts, &plan.affine_rays_refused_because);
+    // Deferred loop updates (glsl_translate.h) and the first-trip copies of the intersection-material snippets (ptl_trace.tpl PTL_FIRST_TRIP)
+    // both exist to dodge `transform(uniform matrix, ray)` -- 32 FMAs in the un-specialised kernel.  In a kernel with affine rays the matrices
+    // are literals or carry their patterns, a transform of the reference's portal matrices is a handful of additions, and the bookkeeping
+    // around it (pending counters and their flush loops; a second copy of every snippet and a wave-level choice between the two) costs more
+    // than it saves: measured on the headline, same frames, baked 0.2305 -> 0.2046 ms, Int-baked 0.272 -> 0.239, patterns 0.274 -> 0.239
+    // (profiles/r05/ab_flags2.jsonl; the un-specialised kernel: 0.70 -> 0.89 without the deferral, so it keeps both).
+    plan.cheap_transforms = plan.affine_rays && !opts.keep_transform_dodges;
+    plan.defer_loop_updates = flags.defer_loop_updates && !plan.cheap_transforms;
+    plan.first_trip_snippets = opts.first_trip && !plan.cheap_transforms;
+    // (KernelOptions::baked_options is only filled in for builds that may compile the switches in: any specialisation, patterns-only included)
+    for (auto& [name, value] : opts.baked_options)
+        for (auto& u : plan.uniforms)
+            if (u.name == name && u.type == UniformType::Int1) plan.baked[name] = std::to_string(value);
+    plan.first_trip_plane_tests = plan_first_trip_planes(scene, plan.baked, opts);
+    plan.derived = plan_derived_planes(scene, plan.baked, opts);
+    check_snippet_out_arguments(plan.snippets);
+    plan_bounded_snippets(plan, opts);
+    plan_hoisted_work(plan, opts);
+    return plan;
+}
+
+// ------------------------------------------------------------------------------------------
+// slot generators (scene.rs:693-1063): one per slot of the kernel template, text only
+// ------------------------------------------------------------------------------------------
+
+// GLSL -> C++ as this build wants it.  `file_scope`: a library text, whose function definitions become PTL_FN (force-inlined) like the rest of the kernel.
+std::string translate_snippet(const BuildPlan& plan, const std::string& glsl, bool file_scope = false) {
+    std::string cxx = translate_glsl(glsl, plan.defer_loop_updates, file_scope);
+    if (plan.unroll_bounds.empty()) return cxx;
+    constexpr int kUnrollLimit = 16;
+    static const std::regex loop(R"(for \(int (\w+) = 0; (\w+) < (\w+); (\w+)\+\+\) \{)");
+    std::string out;
+    auto begin = std::sregex_iterator(cxx.begin(), cxx.end(), loop);
+    size_t last = 0;
+    for (auto it = begin; it != std::sregex_iterator(); ++it) {
+        const std::smatch& m = *it;
+        out.append(cxx, last, (size_t)m.position() - last);
+        last = (size_t)m.position();
+        auto b = plan.unroll_bounds.find(m[3].str());
+        if (m[1] == m[2] && m[1] == m[4] && b != plan.unroll_bounds.end() && b->second >= 2 && b->second <= kUnrollLimit) out += "_Pragma(\"unroll\") ";
+    }
+    out.append(cxx, last, std::string::npos);
+    return out;
+}
+std::string translate_snippet(const BuildPlan& plan, const SceneSnippet& s) { return translate_snippet(plan, s.glsl(), s.kind == SceneSnippet::Library); }
+
+StringStorage emit_uniforms(const Scene& scene, const BuildPlan& plan, const KernelOptions& opts) {
+    StringStorage s;
+    // (in the TEXT as well as among the defines: a renderer tells "nothing compiled in changed" by comparing sources, and a kernel with and
+    // one without affine rays differ in nothing else)
+    if (plan.affine_rays) s.add_string("#define PTL_AFFINE_RAYS 1\n");
+    if (opts.check_affine) s.add_string("#define PTL_CHECK_AFFINE 1\n");  // (implies PTL_COUNT_SEGMENTS: the counter counts rays whose w is not 1 / 0)
+    if (opts.derived_uniforms) s.add_string("#define PTL_DERIVED_BUILTINS 1\n");
+    if (plan.first_trip_plane_tests > 0) s.add_string("#define PTL_FIRST_TRIP_PLANES 1\n#ifndef PTL_FIRST_TRIP\n#define PTL_FIRST_TRIP 1\n#endif\n");
+    if (plan.any_first_snippet()) s.add_string("#define PTL_FIRST_TRIP_SNIPPETS 1\n#ifndef PTL_FIRST_TRIP\n#define PTL_FIRST_TRIP 1\n#endif\n");
+    s.add_string("struct ptl_uniform_block {\n");
+    for (auto& u : plan.uniforms) s.add_string(std::string("    ") + cxx_type(u.type) + " " + u.name + ";\n");
+    // written by ptl_derive_kernel (never by the host: uploads stop at uniform_block_size)
+    if (opts.derived_uniforms)  // the per-pixel work that depends on the frame's builtins alone (ptl_trace.tpl derive())
+        s.add_string("    vec4 ptl_dv_origin;\n    vec4 ptl_dv_origin_left;\n    vec4 ptl_dv_origin_right;\n    vec2 ptl_dv_half_resolution;\n"
+                     "    float ptl_dv_tan_half_view;\n    float ptl_dv_pixel_size;\n");
+    for (auto& d : plan.derived) s.add_string("    vec3 " + d.member + "_nrm;\n    int " + d.member + "_col;\n");
+    if (plan.first_trip_plane_tests > 0)
+        for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
+            const Object& o = scene.objects[pos];
+            if (o.kind != Object::Flat) continue;
+            s.add_string("    vec4 ptl_dvo_" + std::to_string(pos) + "_0;\n");
+            if (o.portal) s.add_string("    vec4 ptl_dvo_" + std::to_string(pos) + "_1;\n");
+        }
+    for (auto& m : plan.hoisted_members) s.add_string("    " + m.type + " " + m.name + (m.length ? "[" + std::to_string(m.length) + "]" : "") + ";\n");
+    s.add_string("};\n");
+    s.add_string("#if PTL_DEVICE_BUILD\n__constant__ ptl_uniform_block ptl_u;\n#else\nptl_uniform_block ptl_u;\n#endif\n");
+    // where the kernel reads uniforms from: the __constant__ block through the scalar cache
+    // (default), or a per-workgroup LDS copy (-DPTL_UNIFORMS_IN_LDS, staged in ptl_entry.h)
+    s.add_string("#if PTL_DEVICE_BUILD && defined(PTL_UNIFORMS_IN_LDS)\n__shared__ ptl_uniform_block ptl_lds_u;\n#define PTL_U ptl_lds_u\n"
+                 "#elif PTL_DEVICE_BUILD && defined(PTL_UNIFORM_RELOAD)\n"
+                 "// every access goes through a pointer the optimiser cannot see through: scalar loads stay where they are\n"
+                 "// used instead of being hoisted out of the bounce loop and spilled (SGPR -> VGPR lanes)\n"
+                 "PTL_FN const ptl_uniform_block& ptl_ublock() { const ptl_uniform_block* p = &ptl_u; asm volatile(\"\" : \"+s\"(p)); return *p; }\n"
+                 "#define PTL_U (ptl_ublock())\n"
+                 "#else\n#define PTL_U ptl_u\n#endif\n");
+    for (auto& u : plan.uniforms)
+        s.add_string("static_assert(__builtin_offsetof(ptl_uniform_block, " + u.name + ") == " + std::to_string(u.offset) + ", \"uniform layout\");\n");
+    for (auto& u : plan.uniforms) {
+        auto it = plan.baked.find(u.name);
+        if (it != plan.baked.end()) s.add_string("#define " + u.name + " (" + it->second + ")\n");
+        else s.add_string("#define " + u.name + " (PTL_U." + u.name + ")\n");
+    }
+    for (auto& [name, mask] : plan.masked) {
+        char hex[96];
+        const unsigned ones = (unsigned)((mask >> 16) & 0xffffu), negs = (unsigned)((mask >> 32) & 0xffffu);
+        if (ones | negs) std::snprintf(hex, sizeof hex, "0x%04xu | PTL_UNIT_BITS(0x%04x, 0x%04x)", (unsigned)(mask & 0xffffu), ones, negs);
+        else std::snprintf(hex, sizeof hex, "0x%04xu", (unsigned)(mask & 0xffffu));
+        s.add_string("#define PTL_MASK_" + name + " " + hex + "\n");
+    }
+    return s;
+}
+
+// Round 6 -- table-driven Simple materials (KernelOptions::material_table).  The reference prints one `else if (i.material == X_M) return
+// material_simple2(hit, r, <nine literals>)` per material (scene.rs:736-760): 30 of the headline's 34, each an inlined copy of the same body
+// behind its own compare-and-branch, and a wave that straddles two materials runs two copies.  Here the nine literals of every Simple material
+// (and of the three DEBUG_* system materials) sit in a table indexed by the material id -- staged in LDS per workgroup by the kernel entries,
+// read back per lane with two ds_read_b128 -- and ONE call of material_simple2 serves all of them.  Same function, same argument values, same
+// operation order: no bit moves (a literal `1.0f - 0.5f` folded by the compiler is the value the instruction computes).
+struct MaterialTableEntry { float color[3], normal_coef, grid_scale, grid_coef; unsigned flags; };  // flags: 1 grid, 2 grid2, 4 grid3, 8 present
+
+std::string material_table_text(const std::map<int, MaterialTableEntry>& table, int mode) {
+    const int entries = table.rbegin()->first + 1;
+    auto bits = [](float v) {
+        unsigned u;
+        std::memcpy(&u, &v, 4);
+        char buf[16];
+        std::snprintf(buf, sizeof buf, "0x%08xu", u);
+        return std::string(buf);
+    };
+    std::string init, masks;
+    for (int id = 0; id < entries; ++id) {
+        auto it = table.find(id);
+        const MaterialTableEntry e = it == table.end() ? MaterialTableEntry{{0, 0, 0}, 0, 0, 0, 0u} : it->second;
+        init += "    " + bits(e.color[0]) + ", " + bits(e.color[1]) + ", " + bits(e.color[2]) + ", " + bits(e.normal_coef) + ", " + bits(e.grid_scale) + ", " +
+                bits(e.grid_coef) + ", " + std::to_string(e.flags) + "u, 0u,\n";
+    }
+    for (int w = 0; w * 64 < entries; ++w) {
+        unsigned long long mask = 0;
+        for (int b = 0; b < 64; ++b)
+            if (table.count(w * 64 + b)) mask |= 1ull << b;
+        char buf[48];
+        std::snprintf(buf, sizeof buf, "0x%016llxull", mask);
+        masks += std::string(w ? ", " : "") + buf;
+    }
+    return "#define PTL_MATERIAL_TABLE " + std::to_string(mode) + "\n#define PTL_MATERIAL_TABLE_WORDS " + std::to_string(entries * 8) + "\n"
+           "// per material id: colour x y z, normal_coef | grid_scale, grid_coef, flags (1 grid, 2 grid2, 4 grid3, 8 = a Simple material), 0 -- binary32 bit patterns\n"
+           "#if PTL_DEVICE_BUILD && PTL_MATERIAL_TABLE == 1\n__constant__ const unsigned int ptl_material_table_init[PTL_MATERIAL_TABLE_WORDS] = {\n" + init + "};\n"
+           "__shared__ __attribute__((aligned(16))) unsigned int ptl_material_table[PTL_MATERIAL_TABLE_WORDS];  // filled by the kernel entries (ptl_entry.h)\n"
+           "#elif PTL_DEVICE_BUILD\n__constant__ const unsigned int ptl_material_table[PTL_MATERIAL_TABLE_WORDS] __attribute__((aligned(32))) = {\n" + init + "};\n"
+           "#else\nstatic const unsigned int ptl_material_table[PTL_MATERIAL_TABLE_WORDS] __attribute__((aligned(16))) = {\n" + init + "};\n#endif\n"
+           "PTL_FN bool ptl_material_in_table(int id) {\n"
+           "    const unsigned long long masks[] = {" + masks + "};\n"
+           "    return (unsigned)id < " + std::to_string(entries) + "u && ((masks[(unsigned)id >> 6] >> ((unsigned)id & 63u)) & 1ull) != 0;\n}\n";
+}
+
+// materials (scene.rs:720-845): the slots `material_processing` and `materials_defines`, which share the numbering of the materials
+std::pair<StringStorage, StringStorage> emit_materials(const Scene& scene, const BuildPlan& plan, const KernelOptions& opts) {
+    StringStorage processing, defines;
+    int counter = 0;
+    std::map<int, MaterialTableEntry> table;
+    if (opts.material_table != 0) {
+        const float hi = 0.9f, lo = 0.2f;  // src/library.glsl:387-398 via ptl_trace.tpl: color(0.9, 0.2, 0.2) = the squares, one binary32 multiplication each
+        const float hh = hi * hi, ll = lo * lo;
+        table[3] = MaterialTableEntry{{hh, ll, ll}, 0.5f, 1.0f, 0.0f, 8u};  // DEBUG_RED / GREEN / BLUE
+        table[4] = MaterialTableEntry{{ll, hh, ll}, 0.5f, 1.0f, 0.0f, 8u};
+        table[5] = MaterialTableEntry{{ll, ll, hh}, 0.5f, 1.0f, 0.0f, 8u};
+    }
+    for (const Material& m : scene.materials) {
+        std::string name_m = m.name + "_M";
+        defines.add_string("#define " + name_m + " (USER_MATERIAL_OFFSET + " + std::to_string(counter++) + ")\n");
+        if (opts.material_table != 0 && m.kind == Material::Simple) {
+            table[10 + counter - 1] = MaterialTableEntry{{(float)m.color[0], (float)m.color[1], (float)m.color[2]}, (float)m.normal_coef, (float)m.grid_scale, (float)m.grid_coef,
+                                                         8u | (m.grid ? 1u : 0u) | (m.grid2 ? 2u : 0u) | (m.grid3 ? 4u : 0u)};
+            continue;
+        }
+        processing.add_string("} else if (i.material == " + name_m + ") {\n");
+        switch (m.kind) {
+            case Material::Simple:
+                processing.add_string("return material_simple2(hit, r, vec3(" + f32_literal(m.color[0]) + ", " + f32_literal(m.color[1]) + ", " +
+                                      f32_literal(m.color[2]) + "), " + f32_literal(m.normal_coef) + ", " + bool_lit(m.grid) + ", " +
+                                      f32_literal(m.grid_scale) + ", " + f32_literal(m.grid_coef) + ", " + bool_lit(m.grid2) + ", " + bool_lit(m.grid3) + ");\n");
+                break;
+            case Material::Reflect:
+                processing.add_string("return material_reflect(hit, r, vec3(" + f32_literal(m.color[0]) + ", " + f32_literal(m.color[1]) + ", " +
+                                      f32_literal(m.color[2]) + "));\n");
+                break;
+            case Material::Refract:
+                processing.add_string("return material_refract(hit, r, vec3(" + f32_literal(m.color[0]) + ", " + f32_literal(m.color[1]) + ", " +
+                                      f32_literal(m.color[2]) + "), " + f32_literal(m.refractive_index) + ");\n");
+                break;
+            case Material::Complex:
+                processing.add_identifier_string({"material", m.name}, translate_snippet(plan, plan.snippet(m.code)));
+                processing.add_string("\n");
+                break;
+        }
+    }
+    for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
+        const Object& o = scene.objects[pos];
+        if (o.kind == Object::DebugMatrix || !o.portal) continue;
+        if (o.m0 < 0 || o.m1 < 0) continue;
+        const std::string& a = matrix_name(scene, o.m0, o);
+        const std::string& b = matrix_name(scene, o.m1, o);
+        std::string m1 = "teleport_" + std::to_string(pos) + "_1_M", m2 = "teleport_" + std::to_string(pos) + "_2_M";
+        defines.add_string("#define " + m1 + " (USER_MATERIAL_OFFSET + " + std::to_string(counter++) + ")\n");
+        defines.add_string("#define " + m2 + " (USER_MATERIAL_OFFSET + " + std::to_string(counter++) + ")\n");
+        // material_teleport(hit, r, M) (library.glsl:366-379) spelled as its body: behind the function parameter the product with M is out of
+        // reach of the zero / unit patterns (apply_zero_masks rewrites `transform(<uniform>, ..)` by name) -- the same two calls, same values
+        processing.add_string("} else if (i.material == " + m1 + ") {\n");
+        processing.add_string("return material_teleport_transformed(transform(" + teleport_name(a, b) + ", r), hit.n);");
+        processing.add_string("} else if (i.material == " + m2 + ") {\n");
+        processing.add_string("return material_teleport_transformed(transform(" + teleport_name(b, a) + ", r), hit.n);");
+    }
+    if (opts.material_table != 0) defines.add_string(material_table_text(table, opts.material_table));
     // The prelude needs the uniform accessors, so the library header goes after the uniform
     // block: splice it at the head of the `materials_defines` slot (order in the reference:
     // predefined library -> uniforms -> textures -> material defines -> library -> ...).
-    {
-        StringStorage s;
-        s.add_string("}  // namespace glsl\n");
-        s.add_string(device_source_library());
-        s.add_string("\nnamespace glsl {\n");
-        s.add_string_storage(std::move(storages["materials_defines"]));
-        storages["materials_defines"] = std::move(s);
-    }
+    StringStorage spliced;
+    spliced.add_string("}  // namespace glsl\n");
+    spliced.add_string(device_source_library());
+    spliced.add_string("\nnamespace glsl {\n");
+    spliced.add_string_storage(std::move(defines));
+    return {std::move(processing), std::move(spliced)};
+}
 
-    StringStorage body = apply_template(device_source_trace_template(), std::move(storages));
-    body.add_string("\n");
-    body.add_string(device_source_entry());
-    gk.source = std::move(body.storage);
-    gk.line_numbers = std::move(body.line_numbers);
-    apply_zero_masks(gk.source, gk.masked);
-    if (opts.slices_entry) apply_slices_entry(gk.source);
+// is_inside_N / intersect_N (scene.rs:847-883)
+StringStorage emit_intersection_functions(const Scene& scene, const BuildPlan& plan, const KernelOptions&) {
+    StringStorage s;
+    for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
+        const Object& o = scene.objects[pos];
+        std::string p = std::to_string(pos);
+        if (o.kind == Object::Flat) {
+            if (o.portal) s.add_string("PTL_FN int is_inside_" + p + "(vec4 pos, float x, float y, bool back, bool first) {\n");
+            else s.add_string("PTL_FN int is_inside_" + p + "(vec4 pos, float x, float y, bool back) {\n");
+        } else if (o.kind == Object::Complex) {
+            if (o.portal) s.add_string("PTL_FN SceneIntersection intersect_" + p + "(Ray r, bool first) {\n");
+            else s.add_string("PTL_FN SceneIntersection intersect_" + p + "(Ray r) {\n");
+        } else {
+            continue;
+        }
+        s.add_identifier_string({"object", o.name}, translate_snippet(plan, plan.snippet(o.code)));
+        s.add_string("\n}\n");
+    }
+    return s;
+}
+
+// One generated plane test of Flat object `p`: side 0 is the object's (first) matrix `m`, side 1 a portal's second; `material` names the
+// teleport material of a portal's side ("": a plain plane).  With a derived entry `d` the unit normal and both is_collinear verdicts come
+// from the prologue kernel (emit_derive evaluates exactly the expressions of the plain form).  The first form takes the transformed origin
+// of this test from the prologue too, through the `_o` variants of the cull and the plane test.
+void emit_plane_test(StringStorage& s, const std::string& p, const std::string& m, int side, const std::string& material, const DerivedPlane* d, bool first_form) {
+    const bool portal = !material.empty();
+    const std::string inv = inverse_name(m), o = first_form ? "_o" : "";
+    const std::string origin = first_form ? ", PTL_U.ptl_dvo_" + p + "_" + std::to_string(side) : "";
+    s.add_string("if (!ptl_plane_cull" + o + "(r, " + inv + origin + ", PTL_BEST_T(i))) {\n");
+    std::string back;  // is_inside's `back`: the plane is seen from behind
+    if (d) {
+        s.add_string("hit = plane_intersect_derived" + o + "(r, " + inv + ", PTL_U." + d->member + "_nrm, flipped" + origin + ");\n");
+        back = "((PTL_U." + d->member + "_col >> (flipped ? 1 : 0)) & 1) != 0";
+    } else {
+        s.add_string(std::string("normal = ") + (side == 0 ? "-" : "") + "get_normal(" + normal_name(m) + ");\n");
+        s.add_string("hit = plane_intersect" + o + "(r, " + inv + ", " + (portal ? "normal" : "get_normal(" + normal_name(m) + ")") + origin + ");\n");
+        back = "is_collinear(hit.n, normal)";
+    }
+    s.add_string(std::string("if (nearer(i, hit)) { i = ") + (portal ? "process_portal_intersection" : "process_plane_intersection") + "(i, hit, is_inside_" + p +
+                 "(r.o + r.d * hit.t, hit.u, hit.v, " + back + (portal ? std::string(", ") + bool_lit(side == 0) : "") + ")" + (portal ? ", " + material : "") + "); }\n}\n\n");
+}
+
+// Per-object intersection statements (scene.rs:885-1009).  Emitted once in the general form and, with KernelOptions::first_trip_planes, once
+// more for the trip on which every ray of the wave still starts at the camera: there `plane_inv * r.o` of a Flat object is the prologue's
+// `ptl_dvo_<object>_<side>` (emit_derive evaluates the very product on the very origin), and the plane test / the cull take it instead of
+// transforming the origin per lane.
+StringStorage emit_intersections(const Scene& scene, const BuildPlan& plan, const KernelOptions&, bool first_form) {
+    StringStorage s;
+    for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
+        const Object& o = scene.objects[pos];
+        std::string p = std::to_string(pos);
+        auto transformed = [&](const std::string& inv) {
+            s.add_string("transformed_ray = transform(" + inv + ", r);\nlen = length(transformed_ray.d);\ntransformed_ray = normalize_ray(transformed_ray);");
+        };
+        if (o.kind != Object::DebugMatrix) {
+            if (o.in_subspace == Subspace::Normal) s.add_string("if (r.in_subspace == false) {");
+            else if (o.in_subspace == Subspace::Subspace) s.add_string("if (r.in_subspace == true) {");
+        }
+        if (o.kind == Object::DebugMatrix) {
+            const std::string& m = matrix_name(scene, o.m0, o);
+            transformed(inverse_name(m));
+            s.add_string("ihit = debug_intersect(transformed_ray);\nihit.hit.t = ptl_div(ihit.hit.t, len);\n");
+            // quirk kept from the reference: the normal uses adjugate of the *inverse* matrix here
+            s.add_string("if (nearer(i, ihit)) { i = ihit; i.hit.n = normalize(adjugate(" + inverse_name(m) + ") * i.hit.n); }\n\n");
+        } else if (o.kind == Object::Flat) {
+            auto test = [&](int side, const std::string& material) {
+                const DerivedPlane* derived = nullptr;
+                for (auto& d : plan.derived)
+                    if (d.object == (int)pos && d.side == side && !derived) derived = &d;
+                emit_plane_test(s, p, matrix_name(scene, side == 0 ? o.m0 : o.m1, o), side, material, derived, first_form);
+            };
+            if (!o.portal) {
+                test(0, "");
+            } else {
+                test(0, "teleport_" + p + "_1_M");
+                test(1, "teleport_" + p + "_2_M");
+            }
+        } else if (!o.portal) {  // Complex
+            const std::string& m = matrix_name(scene, o.m0, o);
+            transformed(inverse_name(m));
+            s.add_string("ihit = intersect_" + p + "(transformed_ray);\nihit.hit.t = ptl_div(ihit.hit.t, len);\n");
+            s.add_string("if (nearer(i, ihit)) { i = ihit; i.hit.n = normalize(adjugate(" + normal_name(m) + ") * i.hit.n); }\n\n");
+        } else {
+            auto side = [&](const std::string& m, bool first, const std::string& material) {
+                transformed(inverse_name(m));
+                s.add_string("ihit = intersect_" + p + "(transformed_ray, " + bool_lit(first) + ");\nihit.hit.t = ptl_div(ihit.hit.t, len);\n");
+                s.add_string("if (nearer(i, ihit) && ihit.material != NOT_INSIDE) { if (ihit.material == TELEPORT) { ihit.material = " + material +
+                             "; } if (ihit.material == TELEPORT_SUBSPACE) { ihit.material = " + material +
+                             "; ihit.in_subspace = true; } i = ihit; i.hit.n = normalize(adjugate(" + normal_name(m) + ") * i.hit.n); }\n\n");
+            };
+            side(matrix_name(scene, o.m0, o), true, "teleport_" + p + "_1_M");
+            side(matrix_name(scene, o.m1, o), false, "teleport_" + p + "_2_M");
+        }
+        if (o.kind != Object::DebugMatrix && o.in_subspace != Subspace::Both) s.add_string("}");
+        s.add_string("\n");
+    }
+    return s;
+}
+
+// prologue: the ray-independent part of every derived plane test, once per uniform upload
+StringStorage emit_derive(const Scene& scene, const BuildPlan& plan, const KernelOptions&) {
+    StringStorage s;
+    if (plan.first_trip_plane_tests > 0) {
+        s.add_string("    // first-trip plane tests: plane_inv * (origin of every primary ray), the product transform() would evaluate per lane\n");
+        for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
+            const Object& o = scene.objects[pos];
+            if (o.kind != Object::Flat) continue;
+            s.add_string("    out->ptl_dvo_" + std::to_string(pos) + "_0 = " + inverse_name(matrix_name(scene, o.m0, o)) + " * out->ptl_dv_origin;\n");
+            if (o.portal) s.add_string("    out->ptl_dvo_" + std::to_string(pos) + "_1 = " + inverse_name(matrix_name(scene, o.m1, o)) + " * out->ptl_dv_origin;\n");
+        }
+    }
+    for (auto& d : plan.derived) {
+        s.add_string("    {\n        vec3 normal = " + d.normal_expr + ";\n        vec3 unit = normalize(" + d.arg_expr + ");\n");
+        s.add_string("        out->" + d.member + "_nrm = unit;\n");
+        s.add_string("        out->" + d.member + "_col = (is_collinear(unit, normal) ? 1 : 0) | (is_collinear(unit * -1.0f, normal) ? 2 : 0);\n    }\n");
+    }
+    if (!plan.hoisted_prologue.empty()) {
+        s.add_string("    // uniform-only work of the scene snippets (host/glsl_hoist.h)\n");
+        s.add_string(translate_glsl(plan.hoisted_prologue, false));
+    }
+    return s;
+}
+
+// intersection materials (scene.rs:1011-1035): the functions, with the first-trip copies of those that have one ...
+StringStorage emit_intersection_material_functions(const Scene& scene, const BuildPlan& plan, const KernelOptions&) {
+    StringStorage fns;
+    for (size_t pos = 0; pos < scene.intersection_materials.size(); ++pos) {
+        const NamedCode& im = scene.intersection_materials[pos];
+        const SceneSnippet& snippet = plan.snippet(im.code);
+        fns.add_string("PTL_FN SceneIntersectionWithMaterial intersect_material_" + std::to_string(pos) + "(Ray r, float ptl_far) {\n(void)ptl_far; ");
+        fns.add_identifier_string({"intersection_material", im.name}, translate_snippet(plan, snippet));
+        fns.add_string("\n}\n");
+        if (snippet.hoisted_first.empty()) continue;
+        fns.add_string("PTL_FN SceneIntersectionWithMaterial intersect_material_" + std::to_string(pos) + "_first(Ray r, float ptl_far) {\n(void)ptl_far; ");
+        fns.add_string(translate_snippet(plan, snippet.hoisted_first));
+        fns.add_string("\n}\n");
+    }
+    return fns;
+}
+// ... and their calls; in the first form only when some snippet has a first-trip copy
+// (a snippet without ray chains has none: its general form serves the first trip too)
+StringStorage emit_intersection_material_processing(const Scene& scene, const BuildPlan& plan, const KernelOptions&, bool first_form) {
+    StringStorage calls;
+    if (first_form && !plan.any_first_snippet()) return calls;
+    for (size_t pos = 0; pos < scene.intersection_materials.size(); ++pos) {
+        const bool own = first_form && !plan.snippet(scene.intersection_materials[pos].code).hoisted_first.empty();
+        calls.add_string("hit = intersect_material_" + std::to_string(pos) + (own ? "_first" : "") + "(r, ptl_far);\n");
+        calls.add_string("if (nearer(result.scene.hit, hit.scene.hit)) { result = hit; }\n\n");
+    }
+    return calls;
+}
+
+// library (scene.rs:1037-1044)
+StringStorage emit_library(const Scene& scene, const BuildPlan& plan, const KernelOptions&) {
+    StringStorage s;
+    // scene functions are plain GLSL functions: the translation puts PTL_FN in front of every definition
+    for (const NamedCode& lib : scene.library) s.add_identifier_string({"library", lib.name}, translate_snippet(plan, plan.snippet(lib.code)));
+    return s;
+}
+
+StringStorage emit_predefined_library(const Scene&, const BuildPlan&, const KernelOptions&) {
+    StringStorage s;
+    s.add_string(device_source_glsl());
+    s.add_string("\n");
+    return s;
+}
+
+StringStorage emit_skybox_processing(const Scene& scene, const BuildPlan&, const KernelOptions&) {
+    StringStorage s;
+    if (scene.skybox) {
+        s.add_string("vec4 rd2 = ptl_mul_runtime(_camera_mul_inv, r.d);");
+        s.add_string("float u = atan(rd2.z, rd2.x);");
+        s.add_string("float v = atan(sqrt(rd2.x * rd2.x + rd2.z * rd2.z), rd2.y);");
+        s.add_string("vec3 not_found_color = sqrvec(texture(" + *scene.skybox + "_tex, vec2(ptl_div(ptl_div(u, PI) + 1.0f, 2.0f), ptl_div(v, PI))).sw<0,1,2>());");
+    } else {
+        s.add_string("vec3 not_found_color = color(0.6f, 0.6f, 0.6f);");
+    }
+    return s;
+}
+
+// A loop in an intersection-material snippet (portal_in_portal's ten nested copies) puts the deepest call chain of the kernel inside a
+// loop nest; unrolled -- its bound a baked Int (translate_snippet) -- it multiplies the body that LLVM's bottom-up inliner pipeline
+// re-simplifies at every call level: the kernels whose hiprtc time that pipeline dominates (kernel.cpp compile_options;
+// tools/jit_inliner_survey.py).  The JIT switches to the module inliner for them.  Only for them: it needs ~10 more VGPRs, which the
+// baked builds have (115 -> 125 of 128) and the others do not (patterns build with the slices entry: 120 -> 139, a wave per SIMD lost).
+bool has_unrolled_snippet_loop(const BuildPlan& plan) {
+    for (const SceneSnippet& s : plan.snippets) {
+        if (s.kind != SceneSnippet::IntersectionMaterial) continue;
+        bool loops = false;
+        for (const Token& t : tokenize_glsl(s.filtered))
+            if (t.kind == Token::Ident && (t.text == "for" || t.text == "while")) loops = true;
+        if (loops && translate_snippet(plan, s).find("_Pragma(\"unroll\")") != std::string::npos) return true;
+    }
+    return false;
+}
+
+// what the plan says about the kernel, for the renderer ...
+GeneratedKernel describe_kernel(const BuildPlan& plan, const KernelOptions& opts) {
+    GeneratedKernel gk;
+    gk.uniforms = plan.uniforms;
+    gk.uniform_block_size = plan.uniform_block_size;
+    gk.baked = plan.baked_values;
+    gk.first_trip_plane_tests = plan.first_trip_plane_tests;
+    gk.first_trip_variants = plan.any_first_snippet();
+    gk.looped_snippets = has_unrolled_snippet_loop(plan);
+    gk.hoisted_members = (int)plan.hoisted_members.size();
+    gk.derived = plan.derived;
+    gk.masked = plan.masked;
+    gk.bounded_snippet_blocks = plan.bounded_snippet_blocks;
+    gk.full_chains = plan.full_chains;
+    gk.affine_rays_refused_because = plan.affine_rays_refused_because;
+    gk.affine_rays = plan.affine_rays;
+    // matrices baked into the source: a matrix product skips the terms whose matrix element is zero (device/ptl_glsl.h `ptl_mterm`)
+    const bool drop_zero_terms = (opts.specialize_all || opts.specialize_static) && short_chains_exact(opts, plan.full_chains);
+    gk.shortened = drop_zero_terms || !plan.masked.empty();
+    // ... and for the compiler
     if (opts.count_segments || opts.check_affine) gk.defines.push_back("PTL_COUNT_SEGMENTS");
     if (opts.check_affine) gk.defines.push_back("PTL_CHECK_AFFINE");
     if (opts.anaglyph) gk.defines.push_back("PTL_ANAGLYPH");
     if (opts.fast_math) gk.defines.push_back("PTL_FAST_MATH");
     if (opts.exact_cr) gk.defines.push_back("PTL_CONTRACT_V1");
     if (opts.quick_jit) gk.defines.push_back("PTL_QUICK_JIT");
-    // matrices baked into the source: a matrix product skips the terms whose matrix element is zero (device/ptl_glsl.h `ptl_mterm`)
-    if ((opts.specialize_all || opts.specialize_static) && !opts.exact_cr && !opts.fast_math && !gk.full_chains) gk.defines.push_back("PTL_DROP_ZERO_TERMS");
+    if (drop_zero_terms) gk.defines.push_back("PTL_DROP_ZERO_TERMS");
     if (gk.affine_rays) gk.defines.push_back("PTL_AFFINE_RAYS");
     if (gk.first_trip_variants) gk.defines.push_back("PTL_FIRST_TRIP");
     if (gk.looped_snippets) gk.defines.push_back("PTL_JIT_MODULE_INLINER");
     if (gk.bounded_snippet_blocks > 0) gk.defines.push_back("PTL_BOUNDED_SNIPPETS");
+    return gk;
+}
+
+}  // namespace
+
+GeneratedKernel generate_kernel_source(const Scene& scene, const CodegenFlags& flags, const KernelOptions& opts) {
+    const std::vector<UniformUpload> values = evaluate_scene_uniforms(scene, nullptr);
+    const BuildPlan plan = plan_build(scene, flags, opts, values);
+
+    std::map<std::string, StringStorage> slots;
+    slots["uniforms"] = emit_uniforms(scene, plan, opts);
+    std::tie(slots["material_processing"], slots["materials_defines"]) = emit_materials(scene, plan, opts);
+    slots["intersection_functions"] = emit_intersection_functions(scene, plan, opts);
+    slots["intersections"] = emit_intersections(scene, plan, opts, false);
+    slots["intersections_first"] = plan.first_trip_plane_tests > 0 ? emit_intersections(scene, plan, opts, true) : StringStorage();
+    slots["derive"] = emit_derive(scene, plan, opts);
+    slots["intersection_material_functions"] = emit_intersection_material_functions(scene, plan, opts);
+    slots["intersection_material_processing"] = emit_intersection_material_processing(scene, plan, opts, false);
+    slots["intersection_material_processing_first"] = emit_intersection_material_processing(scene, plan, opts, true);
+    slots["library"] = emit_library(scene, plan, opts);
+    slots["predefined_library"] = emit_predefined_library(scene, plan, opts);
+    slots["skybox_processing"] = emit_skybox_processing(scene, plan, opts);
+
+    StringStorage body = apply_template(device_source_trace_template(), std::move(slots));
+    body.add_string("\n");
+    body.add_string(device_source_entry());
+    GeneratedKernel gk = describe_kernel(plan, opts);
+    gk.source = std::move(body.storage);
+    gk.line_numbers = std::move(body.line_numbers);
+    apply_zero_masks(gk.source, gk.masked);
+    if (opts.slices_entry) apply_slices_entry(gk.source);
     return gk;
 }
 

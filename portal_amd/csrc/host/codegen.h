@@ -134,7 +134,7 @@ struct KernelOptions {
     // first-trip variants of the intersection-material snippets (ptl_trace.tpl PTL_FIRST_TRIP): the origin half of their ray arithmetic
     // comes from the prologue while the ray still starts at the camera.  Needs derived_uniforms and hoist_uniform_work.
     bool first_trip = true;
-    // snippet loops whose bound is a baked Int uniform (<= 16) are unrolled (codegen.cpp SnippetTranslator::unrolled): identical frames
+    // snippet loops whose bound is a baked Int uniform (<= 16) are unrolled (codegen.cpp translate_snippet): identical frames
     bool unroll_baked_loops = true;
     bool exact_cr = false;   // PTL_CONTRACT_V1: the rounds-1-2 numerics contract (IEEE correctly rounded / and sqrt for every input) instead of contract 2 (device/ptl_glsl.h)
     // first-trip form of the GENERATED plane tests (scene.rs:912-948): a second copy of scene_intersect for the trip on which every ray of the
@@ -163,6 +163,9 @@ struct KernelOptions {
     // the matrix-times-ray products, the bounce loop -- count the ray halves that arrive with another w than 1 / 0 into the `segments` counter
     // (device/ptl_glsl.h PTL_CHECK_AFFINE).  Its frame is right either way; a non-zero count says an affine-rays kernel's would not be.
     bool check_affine = false;
+    // A TEST hook (PTL_AFFINE_RAYS_SKIP_SCAN=1, read by capi.cpp `options_from_flags`): the snippets are not scanned, the matrices alone decide --
+    // tests/test_affine_guard_fuzz.py shows what a snippet the scan refuses would draw with the assumption.
+    bool skip_affine_scan = false;
     // Round 6: the Simple materials' literals in a per-workgroup LDS table, one material_simple2 call for all of them (codegen.cpp, materials).
     // Identical frames; PTL_FLAG_NO_MATERIAL_TABLE (bit 26) keeps the reference's chain of one inlined call per material (A/B measurements, tests).
     // MEASURED (profiles/r06/ab_material_table.jsonl): the LDS table is SLOWER than the reference's chain -- headline 0.1925 against 0.1873 ms, C2 0.0378
@@ -201,6 +204,7 @@ struct GeneratedKernel {
     std::vector<std::pair<std::string, MatrixPattern>> masked;  // run-time matrices whose pattern is compiled in (MatrixPattern)
     int bounded_snippet_blocks = 0;     // `nearer` blocks of intersection-material snippets that take the caller's distance bound (define PTL_BOUNDED_SNIPPETS)
     bool full_chains = false;           // a matrix of the scene is not finite (or KernelOptions::full_chains): no product was shortened
+    bool shortened = false;             // some product skips zero terms (define PTL_DROP_ZERO_TERMS and / or masks): exact for finite vectors only
     std::string affine_rays_refused_because;  // what `snippets_keep_rays_affine` said when it switched the assumption off ("" otherwise)
     bool affine_rays = false;           // generated with PTL_AFFINE_RAYS: valid while the camera matrices have the bottom row 0 0 0 1
 };
@@ -216,6 +220,9 @@ GeneratedKernel generate_kernel_source(const Scene& scene, const CodegenFlags& f
 bool matrix_breaks_short_chains(const float m[16]);
 // Bottom row exactly 0 0 0 1 (column-major elements 3, 7, 11, 15): an affine map -- it keeps the w of a point at 1 and of a direction at 0.
 bool matrix_is_affine(const float m[16]);
+// ... or NaN in every element (a switched-off object: its products are NaN whatever the w): what a kernel with affine rays asks of every
+// scene matrix, at generation time and before every upload (capi.cpp `zero_patterns_broken`).
+bool matrix_keeps_rays_affine(const float m[16]);
 inline bool pattern_is_affine(MatrixPattern p) { return (p & ((1ull << 3) | (1ull << 7) | (1ull << 11))) == 0 && ((p >> (16 + 15)) & 1ull) != 0; }
 // Do the scene's GLSL snippets keep rays affine?  True unless one of them builds a Ray from parts that are not spelled `vec4(.., 1.)` /
 // `vec4(.., 0.)`, assigns a ray's `.o` / `.d` in another than a whitelisted form, calls transform() with a matrix that is not a scene uniform
