@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "glsl_translate.h"
+#include "internal.h"
 #include "scene.h"
 
 namespace ptl {
@@ -220,9 +221,7 @@ GeneratedKernel generate_kernel_source(const Scene& scene, const CodegenFlags& f
 bool matrix_breaks_short_chains(const float m[16]);
 // Bottom row exactly 0 0 0 1 (column-major elements 3, 7, 11, 15): an affine map -- it keeps the w of a point at 1 and of a direction at 0.
 bool matrix_is_affine(const float m[16]);
-// ... or NaN in every element (a switched-off object: its products are NaN whatever the w): what a kernel with affine rays asks of every
-// scene matrix, at generation time and before every upload (capi.cpp `zero_patterns_broken`).
-bool matrix_keeps_rays_affine(const float m[16]);
+// (matrix_keeps_rays_affine -- that, or NaN in every element -- is declared in internal.h: layer 1 asks it too)
 inline bool pattern_is_affine(MatrixPattern p) { return (p & ((1ull << 3) | (1ull << 7) | (1ull << 11))) == 0 && ((p >> (16 + 15)) & 1ull) != 0; }
 // Do the scene's GLSL snippets keep rays affine?  True unless one of them builds a Ray from parts that are not spelled `vec4(.., 1.)` /
 // `vec4(.., 0.)`, assigns a ray's `.o` / `.d` in another than a whitelisted form, calls transform() with a matrix that is not a scene uniform

@@ -13,18 +13,89 @@
 #include <memory>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../../include/portal_amd.h"
 #include "hip_api.h"
 #include "internal.h"
 
-namespace ptl {
+using namespace ptl;
 
+static constexpr int kMaxSlices = 16;
+
+static size_t type_size(ptl_type t) {
+    switch (t) {
+        case PTL_MAT4: return 64;
+        case PTL_F32: case PTL_I32: return 4;
+        case PTL_VEC2: return 8;
+        case PTL_VEC3: return 12;
+        case PTL_SAMPLER: return 16;
+    }
+    return 0;
+}
+
+struct ptl_kernel {
+    int device = -1;
+    std::vector<char> code;
+    hip::hipModule_t module = nullptr;
+    hip::hipFunction_t fn = nullptr;
+    hip::hipFunction_t teleport_fn = nullptr;  // optional: ptl_teleport_kernel
+    hip::hipFunction_t derive_fn = nullptr;    // optional: ptl_derive_kernel, the uniform prologue (runs after every upload)
+    void* dev_block = nullptr;  // address of __constant__ ptl_u
+    size_t dev_block_size = 0;
+    std::vector<unsigned char> shadow;  // host copy of the uniform block
+    bool dirty = true;
+    struct Slot {
+        ptl_type type;
+        size_t offset;
+    };
+    std::map<std::string, Slot> slots;
+    std::map<std::string, void*> textures;  // sampler -> device texel buffer
+    // Staged slices carry sampler records: a texel buffer that a staged slice may still name is not freed by a re-bind of its sampler (a video
+    // texture that steps to its next frame between two sub-frames of one launch) but retired, and freed behind the next launch.
+    std::vector<void*> retired_textures;
+    bool staged_since_launch = false;  // ptl_kernel_stage_slice* since the last launch: its sampler records are live
+    int texture_holds = 0;             // ptl_kernel_hold_textures: a caller keeps snapshots of the block that name texel buffers
+    hip::hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hip::hipEvent_t ev_done = nullptr;  // recorded behind every render launch: what destroy / a teleport query wait for.  Owned here, so it
+                                        // stays valid when the caller has already destroyed the stream it launched on (a torch stream, a
+                                        // user stream freed before the renderer: Python __del__ order is unspecified).
+    // A module generated with the slices entry (codegen.cpp `apply_slices_entry`): its render entry `ptl_render_slices_kernel` reads the uniform
+    // block of slice blockIdx.z from a device buffer of blocks, so one launch can trace several frames with different uniforms.  The module's
+    // own global block stays what the camera-teleport query uses.
+    bool sliced = false;
+    bool affine_rays = false;  // compiled with PTL_AFFINE_RAYS: its products assume o.w = 1 / d.w = 0, which a matrix with another bottom row than 0 0 0 1 breaks
+    hip::hipFunction_t derive_slices_fn = nullptr;
+    void* dev_slices = nullptr;           // kMaxSlices blocks of dev_block_size bytes
+    std::vector<unsigned char> staged;    // host side of it: slice j at j * dev_block_size (ptl_kernel_stage_slice)
+    bool slice0_dirty = true;             // slice 0 of the buffer no longer holds `shadow` (a single draw uses slice 0)
+    // A module compiled with -DPTL_RENDER_MODULE has no camera-teleport entry (ptl_entry.h): that entry is a second copy of the whole tracer
+    // and a fifth of every build, and only a camera that moves asks for it.  Such a kernel keeps what its build was made from and compiles
+    // the other half -- the same source with -DPTL_TELEPORT_MODULE: the teleport entry and the prologue, no render entry -- at the first query
+    // (ptl_kernel_teleport_ray / ptl_kernel_prebuild_teleport).  The companion has a uniform block of its own; a query copies this kernel's.
+    bool split = false;
+    std::string source;
+    std::vector<std::string> defines;
+    ptl_kernel* companion = nullptr;
+    unsigned block_waves = 4;       // PTL_BLOCK_WAVES (experiments with narrower workgroups), read once at compile time
+    void* last_stream = nullptr;    // the stream of the most recent render launch ...
+    bool launched = false;          // ... which may still be reading the uniform block
+};
+
+namespace ptl {
 thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
+}  // namespace ptl
 
 namespace {
+
+using Options = std::vector<std::string>;
+
+struct Destroy {
+    void operator()(ptl_kernel* p) const { ptl_kernel_destroy(p); }  // error paths: unload the module, free events and textures
+};
+using KernelPtr = std::unique_ptr<ptl_kernel, Destroy>;
 
 bool hip_ok(const hip::Runtime* rt, int err, const char* what) {
     if (err == 0) return true;
@@ -39,18 +110,6 @@ unsigned long long fnv1a(const std::string& s, unsigned long long h = 1469598103
         h *= 1099511628211ull;
     }
     return h;
-}
-
-std::string cache_dir() {
-    const char* env = std::getenv("PTL_CACHE_DIR");
-    if (env && !*env) return "";  // PTL_CACHE_DIR="" disables the cache
-    return env ? env : "";
-}
-
-bool quick_build(const std::vector<std::string>& opts) {
-    for (auto& o : opts)
-        if (o == "-O1") return true;
-    return false;
 }
 
 std::string opt_level(bool quick) {
@@ -104,35 +163,59 @@ int code_object_note_max(const std::vector<char>& code, const char* key, const c
     return best;
 }
 
-std::vector<std::string> compile_options(const char* const* defines, int n_defines) {
+// ---- the compile pipeline: request -> traits -> options -> cache / hiprtc + occupancy ladder -> module -------------------------------
+struct CompileRequest {  // the arguments of ptl_kernel_compile
+    int device;
+    const char* source;
+    const ptl_uniform_desc* uniforms; int n_uniforms;
+    size_t block_size;
+    const char* const* defines; int n_defines;
+    char* log; size_t log_cap;
+};
+
+bool has_define(const CompileRequest& rq, const char* name) {
+    for (int k = 0; k < rq.n_defines; ++k)
+        if (std::strcmp(rq.defines[k], name) == 0) return true;
+    return false;
+}
+
+struct BuildTraits {  // what the generator's defines say about the build (codegen.cpp sets them; a layer-1 caller may)
+    bool affine_rays;            // PTL_AFFINE_RAYS: see ptl_kernel::affine_rays
+    bool split, teleport_only;   // PTL_RENDER_MODULE / PTL_TELEPORT_MODULE, the two halves of a split build: see ptl_kernel::split
+    bool fast;                   // PTL_FAST_MATH, the tolerance mode (device/ptl_glsl.h): contraction and approximate / and sqrt allowed
+    bool quick, module_inliner;  // PTL_QUICK_JIT, PTL_JIT_MODULE_INLINER: see opt_level, compile_options
+};
+
+BuildTraits read_traits(const CompileRequest& rq) {
+    return {has_define(rq, "PTL_AFFINE_RAYS"), has_define(rq, "PTL_RENDER_MODULE"), has_define(rq, "PTL_TELEPORT_MODULE"),
+            has_define(rq, "PTL_FAST_MATH"), has_define(rq, "PTL_QUICK_JIT"), has_define(rq, "PTL_JIT_MODULE_INLINER")};
+}
+
+Options compile_options(const CompileRequest& rq, const BuildTraits& t) {
     const char* arch = std::getenv("PTL_OFFLOAD_ARCH");
-    bool fast = false;  // the tolerance mode (device/ptl_glsl.h, PTL_FAST_MATH): contraction and approximate / and sqrt allowed
-    bool quick = false;
-    for (int k = 0; k < n_defines; ++k) fast = fast || std::string(defines[k]) == "PTL_FAST_MATH";
-    for (int k = 0; k < n_defines; ++k) quick = quick || std::string(defines[k]) == "PTL_QUICK_JIT";
-    std::vector<std::string> o = {std::string("--offload-arch=") + (arch ? arch : "gfx950"),
-                                  // -O3 WITHOUT the SLP vectoriser, measured on the round-3 kernels (profiles/r03/variants9_opt_level.jsonl, same
-                                  // frame hashes): against -O1 the baked kernels are 10-23 % faster (portal_in_portal 4K 0.364 -> 0.327 ms,
-                                  // triple_portal 0.333 -> 0.300, monoportal 1080p 0.069 -> 0.055, plus_ultra 0.99 -> 0.76), the Int-baked and
-                                  // un-specialised ones 2-30 % (plus_ultra un-specialised 4.5 -> 2.0 ms) with ONE exception, the un-specialised
-                                  // portal_in_portal (0.78 -> 0.88: PTL_JIT_OPT=-O1 restores it; bench.py reports the better of the two).
-                                  // Rounds 1-2 shipped -O1: what lost then was the SLP vectoriser (v_pk_* pairs, long live ranges, spills --
-                                  // still true: plain -O3 is 0.362 / 0.361 / 1.27 on the first three), not the rest of -O2/-O3.
-                                  opt_level(quick),
-                                  "-fno-slp-vectorize",
-                                  "-std=c++20",
-                                  fast ? "-ffp-contract=fast" : "-ffp-contract=off",  // exact mode: FMAs only where device/ptl_glsl.h spells them
-                                  fast ? "-fno-hip-fp32-correctly-rounded-divide-sqrt" : "-fhip-fp32-correctly-rounded-divide-sqrt",
-                                  "-fno-gpu-approx-transcendentals" /* no-op on older clang, harmless */
-                                  // LLVM's default ("greedy") VGPR allocator MISCOMPILES divergent control flow now and then on this
-                                  // toolchain (ROCm 7.2): a value that is live across an exec-masked inner block gets its registers
-                                  // handed to temporaries of that block, so the lanes that skip the block's redefinition read garbage.
-                                  // Found by the GLSL fuzzer on gfx950 (tests/test_gpu_parity.py::test_greedy_regalloc_miscompile_stays_fixed:
-                                  // seed 105219, three pixels, reproduced down to a 3-branch kernel; host build and oracle agree with each
-                                  // other, every -O level, scheduler and machine-pass switch keeps the fault, `-vgpr-regalloc=basic` and
-                                  // `=fast` remove it).  The basic allocator does no live-range splitting; it costs 0-3 % of kernel time
-                                  // (profiles/r01/variants15_regalloc.jsonl), same frames.  PTL_VGPR_REGALLOC=default leaves the choice to the toolchain again.
-                                  };
+    Options o = {std::string("--offload-arch=") + (arch ? arch : "gfx950"),
+                 // -O3 WITHOUT the SLP vectoriser, measured on the round-3 kernels (profiles/r03/variants9_opt_level.jsonl, same
+                 // frame hashes): against -O1 the baked kernels are 10-23 % faster (portal_in_portal 4K 0.364 -> 0.327 ms,
+                 // triple_portal 0.333 -> 0.300, monoportal 1080p 0.069 -> 0.055, plus_ultra 0.99 -> 0.76), the Int-baked and
+                 // un-specialised ones 2-30 % (plus_ultra un-specialised 4.5 -> 2.0 ms) with ONE exception, the un-specialised
+                 // portal_in_portal (0.78 -> 0.88: PTL_JIT_OPT=-O1 restores it; bench.py reports the better of the two).
+                 // Rounds 1-2 shipped -O1: what lost then was the SLP vectoriser (v_pk_* pairs, long live ranges, spills --
+                 // still true: plain -O3 is 0.362 / 0.361 / 1.27 on the first three), not the rest of -O2/-O3.
+                 opt_level(t.quick),
+                 "-fno-slp-vectorize",
+                 "-std=c++20",
+                 t.fast ? "-ffp-contract=fast" : "-ffp-contract=off",  // exact mode: FMAs only where device/ptl_glsl.h spells them
+                 t.fast ? "-fno-hip-fp32-correctly-rounded-divide-sqrt" : "-fhip-fp32-correctly-rounded-divide-sqrt",
+                 "-fno-gpu-approx-transcendentals" /* no-op on older clang, harmless */
+                 // LLVM's default ("greedy") VGPR allocator MISCOMPILES divergent control flow now and then on this
+                 // toolchain (ROCm 7.2): a value that is live across an exec-masked inner block gets its registers
+                 // handed to temporaries of that block, so the lanes that skip the block's redefinition read garbage.
+                 // Found by the GLSL fuzzer on gfx950 (tests/test_gpu_parity.py::test_greedy_regalloc_miscompile_stays_fixed:
+                 // seed 105219, three pixels, reproduced down to a 3-branch kernel; host build and oracle agree with each
+                 // other, every -O level, scheduler and machine-pass switch keeps the fault, `-vgpr-regalloc=basic` and
+                 // `=fast` remove it).  The basic allocator does no live-range splitting; it costs 0-3 % of kernel time
+                 // (profiles/r01/variants15_regalloc.jsonl), same frames.  PTL_VGPR_REGALLOC=default leaves the choice to the toolchain again.
+                 };
     {
         const char* ra = std::getenv("PTL_VGPR_REGALLOC");  // "default": say nothing, i.e. the toolchain's own choice (the faulty one)
         if (!ra || std::string(ra) != "default") {
@@ -152,14 +235,12 @@ std::vector<std::string> compile_options(const char* const* defines, int n_defin
         // those keep the toolchain's default.  Same source, same arithmetic, other instruction schedule: bit-identical frames.
         // PTL_MODULE_INLINER=0 / 1 forces the choice.
         const char* mi = std::getenv("PTL_MODULE_INLINER");
-        bool wanted = false;
-        for (int k = 0; k < n_defines; ++k) wanted = wanted || std::string(defines[k]) == "PTL_JIT_MODULE_INLINER";
-        if (mi ? (mi[0] != '0') : wanted) {
+        if (mi ? (mi[0] != '0') : t.module_inliner) {
             o.push_back("-mllvm");
             o.push_back("-enable-module-inliner");
         }
     }
-    if (fast && !std::getenv("PTL_FAST_KEEP_ZEROS")) {
+    if (t.fast && !std::getenv("PTL_FAST_KEEP_ZEROS")) {
         // Tolerance mode only: a product with a literal zero is zero.  With the scene state baked in, the portal matrices of most scenes are
         // translations and axis rotations -- 41 % of the multiplications in the headline snippet's loop have a literal +-0 operand, and
         // IEEE keeps every one of them alive (0 * x is -0, or NaN for an infinite x).  What this gives up beyond the rest of the mode:
@@ -177,62 +258,262 @@ std::vector<std::string> compile_options(const char* const* defines, int n_defin
             pos = sp + 1;
         }
     }
-    for (int k = 0; k < n_defines; ++k) o.push_back(std::string("-D") + defines[k]);
+    for (int k = 0; k < rq.n_defines; ++k) o.push_back(std::string("-D") + rq.defines[k]);
     return o;
 }
 
-}  // namespace
-}  // namespace ptl
+// The code-object cache: same source + options -> same gfx950 binary.  "" when there is no cache directory.
+std::string cache_path(const char* source, const Options& opts) {
+    const char* cdir = std::getenv("PTL_CACHE_DIR");
+    if (!cdir || !*cdir) return "";
+    unsigned long long h = fnv1a(source);
+    for (auto& o : opts) h = fnv1a(o, h);
+    h = fnv1a("jit policy 6: occupancy retries end with an -O1 attempt", h);  // (what occupancy_ladder does to options on its own is part of the key)
+    // ... produced by THIS toolchain: the cache travels between machines (build container -> GPU box), and the options above exist to
+    // dodge a fault of one particular compiler.  hiprtc's version and the path it was loaded from go into the key.
+    std::string err;
+    if (const hip::Rtc* rc = hip::rtc(&err)) h = fnv1a("hiprtc " + rc->real_path, h);  // ".../libhiprtc.so.7.2.70200"
+    char name[64];
+    std::snprintf(name, sizeof name, "/ptl_%016llx.hsaco", h);
+    return std::string(cdir) + name;
+}
 
-using namespace ptl;
-
-struct ptl_kernel {
-    int device = -1;
+std::vector<char> cache_load(const std::string& path) {
     std::vector<char> code;
-    hip::hipModule_t module = nullptr;
-    hip::hipFunction_t fn = nullptr;
-    hip::hipFunction_t teleport_fn = nullptr;  // optional: ptl_teleport_kernel
-    hip::hipFunction_t derive_fn = nullptr;    // optional: ptl_derive_kernel, the uniform prologue (runs after every upload)
-    void* dev_block = nullptr;  // address of __constant__ ptl_u
-    size_t dev_block_size = 0;
-    std::vector<unsigned char> shadow;  // host copy of the uniform block
-    bool dirty = true;
-    struct Slot {
-        ptl_type type;
-        size_t offset;
-    };
-    std::map<std::string, Slot> slots;
-    std::map<std::string, void*> textures;  // sampler -> device texel buffer
-    // Staged slices carry sampler records: a texel buffer that a staged slice may still name is not freed by a re-bind of its sampler (a video
-    // texture that steps to its next frame between two sub-frames of one launch) but retired, and freed behind the next launch.
-    std::vector<void*> retired_textures;
-    bool staged_since_launch = false;  // ptl_kernel_stage_slice* since the last launch: its sampler records are live
-    int texture_holds = 0;             // ptl_kernel_hold_textures: a caller keeps snapshots of the block that name texel buffers
-    hip::hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hip::hipEvent_t ev_done = nullptr;  // recorded behind every render launch: what destroy / a teleport query wait for.  Owned here, so it
-                                        // stays valid when the caller has already destroyed the stream it launched on (a torch stream, a
-                                        // user stream freed before the renderer: Python __del__ order is unspecified).
-    // A module generated with the slices entry (codegen.cpp `apply_slices_entry`): its render entry `ptl_render_slices_kernel` reads the uniform
-    // block of slice blockIdx.z from a device buffer of blocks, so one launch can trace several frames with different uniforms.  The module's
-    // own global block stays what the camera-teleport query uses.
-    bool sliced = false;
-    bool affine_rays = false;  // compiled with PTL_AFFINE_RAYS: its products assume o.w = 1 / d.w = 0, which a matrix with another bottom row than 0 0 0 1 breaks
-    hip::hipFunction_t derive_slices_fn = nullptr;
-    void* dev_slices = nullptr;           // kMaxSlices blocks of dev_block_size bytes
-    std::vector<unsigned char> staged;    // host side of it: slice j at j * dev_block_size (ptl_kernel_stage_slice)
-    bool slice0_dirty = true;             // slice 0 of the buffer no longer holds `shadow` (a single draw uses slice 0)
-    // A module compiled with -DPTL_RENDER_MODULE has no camera-teleport entry (ptl_entry.h): that entry is a second copy of the whole tracer
-    // and a fifth of every build, and only a camera that moves asks for it.  Such a kernel keeps what its build was made from and compiles
-    // the other half -- the same source with -DPTL_TELEPORT_MODULE: the teleport entry and the prologue, no render entry -- at the first query
-    // (ptl_kernel_teleport_ray / ptl_kernel_prebuild_teleport).  The companion has a uniform block of its own; a query copies this kernel's.
-    bool split = false;
-    std::string source;
-    std::vector<std::string> defines;
-    ptl_kernel* companion = nullptr;
-    unsigned block_waves = 4;       // PTL_BLOCK_WAVES (experiments with narrower workgroups), read once at compile time
-    void* last_stream = nullptr;    // the stream of the most recent render launch ...
-    bool launched = false;          // ... which may still be reading the uniform block
+    std::ifstream f(path, std::ios::binary);
+    if (f) code.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+    if (code.size() < 64 || std::memcmp(code.data(), "\x7f" "ELF", 4) != 0) code.clear();  // truncated or foreign file: compile again
+    return code;
+}
+
+void cache_store(const std::string& path, const std::vector<char>& code) {
+    ::mkdir(path.substr(0, path.rfind('/')).c_str(), 0755);
+    // one temp file per COMPILE, not per process: background re-JIT workers and the ranks of a frame group compile the same source on
+    // several threads of one process, and a shared temp path would let one of them rename a file another is still writing
+    static std::atomic<unsigned long> compile_serial{0};
+    const std::string tmp = path + ".tmp" + std::to_string((long)getpid()) + "." + std::to_string(compile_serial.fetch_add(1));
+    std::ofstream f(tmp, std::ios::binary);
+    f.write(code.data(), (std::streamsize)code.size());
+    f.close();
+    if (f) std::rename(tmp.c_str(), path.c_str());
+}
+
+// One hiprtc run.  `report`: errors go to ptl_last_error and the compiler's log to the caller's buffer.
+int run_hiprtc(const hip::Rtc* rc, const CompileRequest& rq, const Options& options, std::vector<char>& code, bool report) {
+    hip::hiprtcProgram prog = nullptr;
+    int r = rc->hiprtcCreateProgram(&prog, rq.source, "portal_scene.hip", 0, nullptr, nullptr);
+    if (r != 0) {
+        if (report) set_last_error(std::string("hiprtcCreateProgram: ") + rc->hiprtcGetErrorString(r));
+        return PTL_ERR_COMPILE;
+    }
+    std::vector<const char*> copts;
+    for (auto& o : options) copts.push_back(o.c_str());
+    r = rc->hiprtcCompileProgram(prog, (int)copts.size(), copts.data());
+    size_t log_size = 0;
+    rc->hiprtcGetProgramLogSize(prog, &log_size);
+    if (log_size > 1 && report) {
+        std::vector<char> buf(log_size + 1, 0);
+        rc->hiprtcGetProgramLog(prog, buf.data());
+        if (rq.log && rq.log_cap) {
+            std::strncpy(rq.log, buf.data(), rq.log_cap - 1);
+            rq.log[rq.log_cap - 1] = '\0';
+        }
+        if (r != 0) set_last_error(std::string("hiprtc: ") + buf.data());
+    }
+    if (r != 0) {
+        if (log_size <= 1 && report) set_last_error(std::string("hiprtcCompileProgram: ") + rc->hiprtcGetErrorString(r));
+        rc->hiprtcDestroyProgram(&prog);
+        return PTL_ERR_COMPILE;
+    }
+    size_t code_size = 0;
+    rc->hiprtcGetCodeSize(prog, &code_size);
+    code.resize(code_size);
+    rc->hiprtcGetCode(prog, code.data());
+    rc->hiprtcDestroyProgram(&prog);
+    return PTL_OK;
+}
+
+// ---- the occupancy ladder ------------------------------------------------------------------------------------------------------------
+// 128 VGPRs is where the fourth wave per SIMD goes.  A kernel that lands a few registers above it without having been told an occupancy
+// is compiled again, rung by rung, until a build fits four waves (same source, same arithmetic, same frames): one to three more hiprtc
+// runs for the rare kernel in that band, once -- the code object is cached under the key of the options the caller asked for.
+// A rung gives the options of its attempt, or none where it does not apply.
+
+// No PTL_WAVES_PER_EU: the module inliner's builds of portal_in_portal with the Panini switch and the slices entry, 130 VGPRs, 0.262 ->
+// 0.314 ms per frame.  Once more with __launch_bounds__(256, 4), kept if the allocator got there without spilling.
+Options under_the_cap(Options o) { return o.push_back("-DPTL_WAVES_PER_EU=4"), o; }
+
+// ... and if the cap only produces spills while the build came from the module inliner -- whose schedule needs ~10 registers more than the
+// bottom-up pipeline's (portal_in_portal_plus_ultra with its Ints baked: 139 against 128) -- the toolchain's own pipeline gets a try under
+// the same cap.
+Options bottom_up_under_the_cap(Options o) {
+    const size_t before = o.size();
+    for (size_t i = 0; i + 1 < o.size();)
+        if (o[i] == "-mllvm" && o[i + 1] == "-enable-module-inliner") o.erase(o.begin() + i, o.begin() + i + 2);
+        else ++i;
+    return o.size() < before ? under_the_cap(o) : Options{};
+}
+
+// Round 6: ... and when no cap gets there without spilling, the -O1 pipeline gets a try without one.  What pushes a kernel into this band
+// is -O3's appetite (hoisting and unrolling across the scene's loops): the un-specialised headline kernel is 139 VGPRs and three waves
+// per SIMD at -O3, 128 + 8 bytes of scratch under the cap, and 117 VGPRs without a spill at -O1 -- 0.825 / 0.705 / 0.703 ms
+// (profiles/r06/unspec_anatomy.jsonl): "-O1 beats -O3 on this kernel" (VERDICT r5 #5b) is an occupancy effect, and this is the rule that
+// follows from it.  Not for a quick build, which is at -O1 already.
+Options at_o1_without_a_cap(Options o) {
+    bool lowered = false;
+    for (auto& s : o) {
+        if (s == "-O1") return {};
+        if (s == "-O3") s = "-O1", lowered = true;
+    }
+    return lowered ? o : Options{};
+}
+
+struct Rung {
+    Options (*attempt)(Options);
+    bool check_vgprs;  // a rung that changes the pipeline has to land at 128 registers; the plain cap's build does if it does not spill
 };
+const Rung kLadder[] = {{under_the_cap, false}, {bottom_up_under_the_cap, true}, {at_o1_without_a_cap, true}};
+
+int render_note(const std::vector<char>& code, const char* key) { return code_object_note_max(code, key, "ptl_render"); }  // the render entries only
+
+// Does `candidate` fit four waves per SIMD no worse than the first build: no spills, no more scratch.
+bool fits_four_waves(const std::vector<char>& candidate, const std::vector<char>& first, bool check_vgprs) {
+    return (!check_vgprs || render_note(candidate, ".vgpr_count") <= 128) && render_note(candidate, ".vgpr_spill_count") == 0 &&
+           render_note(candidate, ".private_segment_fixed_size") <= render_note(first, ".private_segment_fixed_size");
+}
+
+// `code`: the first build, made with `opts`; replaced by the first rung's build that fits.  Only the first build reports errors.
+void occupancy_ladder(const hip::Rtc* rc, const CompileRequest& rq, const Options& opts, bool teleport_only, std::vector<char>& code) {
+    bool hinted = false;
+    for (auto& o : opts) hinted = hinted || o.find("PTL_WAVES_PER_EU") != std::string::npos;  // (a define of the caller's, or PTL_HIPRTC_FLAGS of an experiment)
+    const int vgprs = render_note(code, ".vgpr_count");
+    if (hinted || teleport_only || vgprs <= 128 || vgprs > 168 || std::getenv("PTL_NO_OCCUPANCY_RETRY")) return;
+    for (const Rung& rung : kLadder) {
+        const Options o = rung.attempt(opts);
+        std::vector<char> candidate;
+        if (!o.empty() && run_hiprtc(rc, rq, o, candidate, false) == PTL_OK && fits_four_waves(candidate, code, rung.check_vgprs)) {
+            code.swap(candidate);
+            return;
+        }
+    }
+}
+
+// The request's code object: the cache's when `read_cache`, else hiprtc's, which goes into the cache.  `read_from`: the cache file the object
+// came from, "" otherwise.
+int obtain_code(const CompileRequest& rq, const BuildTraits& traits, bool read_cache, std::vector<char>& code, std::string& read_from) {
+    read_from.clear();
+    const Options opts = compile_options(rq, traits);
+    const std::string path = cache_path(rq.source, opts);
+    code.clear();
+    if (read_cache && !path.empty()) code = cache_load(path);
+    if (!code.empty()) {
+        read_from = path;
+        return PTL_OK;
+    }
+    std::string err;
+    const hip::Rtc* rc = hip::rtc(&err);
+    if (!rc) {
+        set_last_error(err);
+        return PTL_ERR_COMPILE;
+    }
+    if (int r = run_hiprtc(rc, rq, opts, code, true); r != PTL_OK) return r;
+    occupancy_ladder(rc, rq, opts, traits.teleport_only, code);
+    if (!path.empty()) cache_store(path, code);
+    return PTL_OK;
+}
+
+// Loads k->code on the current device and binds what the host side uses of it: entries, uniform block, events.  `Discover`: the plain render
+// entry, else the slices entry (codegen.cpp `apply_slices_entry`).  A code object the runtime refuses leaves k->module null.
+enum class RenderEntry { None, Plain, Sliced, Discover };
+int bind_module(ptl_kernel* k, const hip::Runtime* rt, RenderEntry entry, size_t declared_block_size) {
+    if (!hip_ok(rt, rt->hipModuleLoadData(&k->module, k->code.data()), "hipModuleLoadData")) return k->module = nullptr, PTL_ERR_HIP;
+    if (entry == RenderEntry::Plain || entry == RenderEntry::Discover) {
+        const int e = rt->hipModuleGetFunction(&k->fn, k->module, "ptl_render_kernel");
+        if (e != 0 && entry == RenderEntry::Discover) {
+            rt->hipGetLastError();
+            entry = RenderEntry::Sliced;
+        } else if (!hip_ok(rt, e, "hipModuleGetFunction(ptl_render_kernel)"))
+            return PTL_ERR_HIP;
+    }
+    if (entry == RenderEntry::Sliced) {
+        if (!hip_ok(rt, rt->hipModuleGetFunction(&k->fn, k->module, "ptl_render_slices_kernel"), "hipModuleGetFunction(ptl_render_kernel / ptl_render_slices_kernel)"))
+            return PTL_ERR_HIP;
+        if (!hip_ok(rt, rt->hipModuleGetFunction(&k->derive_slices_fn, k->module, "ptl_derive_slices_kernel"), "hipModuleGetFunction(ptl_derive_slices_kernel)"))
+            return PTL_ERR_HIP;
+        k->sliced = true;
+    }
+    for (auto [fn, name] : {std::pair{&k->teleport_fn, "ptl_teleport_kernel"}, std::pair{&k->derive_fn, "ptl_derive_kernel"}})
+        if (rt->hipModuleGetFunction(fn, k->module, name) != 0) {
+            *fn = nullptr;          // hand-written layer-1 kernels need not have the other entry points
+            rt->hipGetLastError();  // ... and the expected hipErrorNotFound must not stay behind as the thread's sticky
+                                    // error: the next HIP user in the process (PyTorch) would report it as its own
+        }
+    if (!hip_ok(rt, rt->hipModuleGetGlobal(&k->dev_block, &k->dev_block_size, k->module, "_ZN4glsl5ptl_uE"), "hipModuleGetGlobal(ptl_u)"))
+        return PTL_ERR_HIP;
+    if (k->dev_block_size < declared_block_size) {
+        set_last_error("uniform block in the code object is smaller than the declared layout");
+        return PTL_ERR_INVALID;
+    }
+    rt->hipEventCreate(&k->ev0);
+    rt->hipEventCreate(&k->ev1);
+    rt->hipEventCreateWithFlags(&k->ev_done, hip::kEventDisableTiming);
+    if (const char* e = std::getenv("PTL_BLOCK_WAVES")) k->block_waves = (e[0] == '1' || e[0] == '2') ? (unsigned)(e[0] - '0') : 4u;
+    return PTL_OK;
+}
+
+// What both public compile entries do.  `prebuilt`: this code object instead of cache / hiprtc.  `read_cache`: may a cached one be used.
+int compile_kernel(const CompileRequest& rq, const std::vector<char>* prebuilt, bool read_cache, ptl_kernel** out) {
+    if (rq.log && rq.log_cap) rq.log[0] = '\0';
+    if (!rq.source || !out) return PTL_ERR_INVALID;
+    *out = nullptr;
+    KernelPtr k(new ptl_kernel());
+    k->device = rq.device;
+    for (int i = 0; i < rq.n_uniforms; ++i) {
+        const ptl_uniform_desc& u = rq.uniforms[i];
+        k->slots[u.name] = {u.type, u.offset};
+        if (u.offset + type_size(u.type) > rq.block_size) {
+            set_last_error(std::string("uniform `") + u.name + "` lies outside the block");
+            return PTL_ERR_INVALID;
+        }
+    }
+    k->shadow.assign(rq.block_size, 0);
+    const BuildTraits traits = read_traits(rq);
+    k->affine_rays = traits.affine_rays;
+    k->split = traits.split;
+    if (k->split) {
+        k->source = rq.source;
+        k->defines.assign(rq.defines, rq.defines + rq.n_defines);
+    }
+    std::string read_from;
+    if (prebuilt) k->code = *prebuilt;  // compiled elsewhere from this very source: nothing to look up, nothing to build or store
+    else if (int rc = obtain_code(rq, traits, read_cache, k->code, read_from); rc != PTL_OK) return rc;
+    if (rq.device < 0) {  // compile-only handle
+        *out = k.release();
+        return PTL_OK;
+    }
+    std::string err;
+    const hip::Runtime* rt = hip::runtime(&err);
+    if (!rt) {
+        set_last_error(err);
+        return PTL_ERR_NO_DEVICE;
+    }
+    if (!hip_ok(rt, rt->hipSetDevice(rq.device), "hipSetDevice")) return PTL_ERR_HIP;
+    const RenderEntry entry = traits.teleport_only ? RenderEntry::None : RenderEntry::Discover;  // (the teleport half of a split build: no render entry by construction)
+    int rc = bind_module(k.get(), rt, entry, rq.block_size);
+    if (rc != PTL_OK && !k->module && !read_from.empty()) {
+        // a cached code object this runtime refuses (other GPU, damaged file): drop it and build from source ONCE.  The retry does
+        // not read the cache again -- the file may be undeletable (a read-only or shared cache directory travels from the build
+        // container to the GPU box), and re-reading it would refuse without end.
+        std::remove(read_from.c_str());
+        if (int rc2 = obtain_code(rq, traits, false, k->code, read_from); rc2 != PTL_OK) return rc2;
+        rc = bind_module(k.get(), rt, entry, rq.block_size);
+    }
+    if (rc != PTL_OK) return rc;
+    *out = k.release();
+    return PTL_OK;
+}
+
+}  // namespace
 
 extern "C" const char* ptl_last_error(void) { return g_last_error.c_str(); }
 
@@ -258,21 +539,11 @@ extern "C" int ptl_device_count(void) {
     return n;
 }
 
-static constexpr int kMaxSlices = 16;
-
-static size_t type_size(ptl_type t) {
-    switch (t) {
-        case PTL_MAT4: return 64;
-        case PTL_F32: case PTL_I32: return 4;
-        case PTL_VEC2: return 8;
-        case PTL_VEC3: return 12;
-        case PTL_SAMPLER: return 16;
-    }
-    return 0;
+extern "C" int ptl_kernel_compile(int device, const char* hip_source, const ptl_uniform_desc* uniforms, int n_uniforms,
+                                  size_t uniform_block_size, const char* const* defines, int n_defines, ptl_kernel** out, char* log,
+                                  size_t log_cap) {
+    return compile_kernel({device, hip_source, uniforms, n_uniforms, uniform_block_size, defines, n_defines, log, log_cap}, nullptr, true, out);
 }
-
-static thread_local bool tl_skip_cache_read = false;  // set for the one retry after the runtime refused a cached code object
-static thread_local const std::vector<char>* tl_prebuilt_code = nullptr;  // ptl_kernel_compile_prebuilt: this code object instead of cache / hiprtc
 
 // Layer-1 internal (capi.cpp's background re-JIT): load a code object that another thread compiled from exactly `hip_source` with
 // exactly these defines (a compile-only handle, device = -1) instead of compiling again.
@@ -281,232 +552,7 @@ extern "C" int ptl_kernel_compile_prebuilt(int device, const char* hip_source, c
                                            size_t log_cap) {
     if (!code || code_size < 64) return PTL_ERR_INVALID;
     const std::vector<char> copy(static_cast<const char*>(code), static_cast<const char*>(code) + code_size);
-    tl_prebuilt_code = &copy;
-    const int rc = ptl_kernel_compile(device, hip_source, uniforms, n_uniforms, uniform_block_size, defines, n_defines, out, log, log_cap);
-    tl_prebuilt_code = nullptr;
-    return rc;
-}
-
-extern "C" int ptl_kernel_compile(int device, const char* hip_source, const ptl_uniform_desc* uniforms, int n_uniforms,
-                                  size_t uniform_block_size, const char* const* defines, int n_defines, ptl_kernel** out, char* log,
-                                  size_t log_cap) {
-    if (log && log_cap) log[0] = '\0';
-    if (!hip_source || !out) return PTL_ERR_INVALID;
-    *out = nullptr;
-    struct Destroy {
-        void operator()(ptl_kernel* p) const { ptl_kernel_destroy(p); }  // error paths below: unload the module, free events and textures
-    };
-    std::unique_ptr<ptl_kernel, Destroy> k(new ptl_kernel());
-    k->device = device;
-    for (int i = 0; i < n_uniforms; ++i) {
-        k->slots[uniforms[i].name] = {uniforms[i].type, uniforms[i].offset};
-        if (uniforms[i].offset + type_size(uniforms[i].type) > uniform_block_size) {
-            set_last_error(std::string("uniform `") + uniforms[i].name + "` lies outside the block");
-            return PTL_ERR_INVALID;
-        }
-    }
-    k->shadow.assign(uniform_block_size, 0);
-
-    bool teleport_only = false;
-    for (int i = 0; i < n_defines; ++i) {
-        if (std::string(defines[i]) == "PTL_AFFINE_RAYS") k->affine_rays = true;
-        if (std::string(defines[i]) == "PTL_RENDER_MODULE") k->split = true;
-        if (std::string(defines[i]) == "PTL_TELEPORT_MODULE") teleport_only = true;
-    }
-    if (k->split) {
-        k->source = hip_source;
-        for (int i = 0; i < n_defines; ++i) k->defines.push_back(defines[i]);
-    }
-    std::vector<std::string> opts = compile_options(defines, n_defines);
-    // ---- code-object cache: same source + options -> same gfx950 binary -----------------------
-    std::string cdir = cache_dir();
-    std::string cache_path;
-    if (!cdir.empty()) {
-        unsigned long long h = fnv1a(hip_source);
-        for (auto& o : opts) h = fnv1a(o, h);
-        h = fnv1a("jit policy 6: occupancy retries end with an -O1 attempt", h);  // (what this function does to options on its own is part of the key)
-        // ... produced by THIS toolchain: the cache travels between machines (build container -> GPU box), and the options above exist to
-        // dodge a fault of one particular compiler.  hiprtc's version and the path it was loaded from go into the key.
-        std::string err;
-        if (const hip::Rtc* rc = hip::rtc(&err)) {
-            h = fnv1a("hiprtc " + rc->real_path, h);  // ".../libhiprtc.so.7.2.70200"
-        }
-        char name[64];
-        std::snprintf(name, sizeof name, "/ptl_%016llx.hsaco", h);
-        cache_path = cdir + name;
-        std::ifstream f(cache_path, std::ios::binary);
-        if (f && !tl_skip_cache_read) k->code.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-        if (k->code.size() < 64 || std::memcmp(k->code.data(), "\x7f" "ELF", 4) != 0) k->code.clear();  // truncated or foreign file: compile again
-    }
-    bool from_cache = !k->code.empty();
-    if (tl_prebuilt_code) {  // compiled elsewhere from this very source: nothing to look up, nothing to build
-        k->code = *tl_prebuilt_code;
-        from_cache = false;
-    }
-    if (k->code.empty()) {
-        std::string err;
-        const hip::Rtc* rc = hip::rtc(&err);
-        if (!rc) {
-            set_last_error(err);
-            return PTL_ERR_COMPILE;
-        }
-        auto run_hiprtc = [&](const std::vector<std::string>& options, std::vector<char>& code, bool report) -> int {
-            hip::hiprtcProgram prog = nullptr;
-            int r = rc->hiprtcCreateProgram(&prog, hip_source, "portal_scene.hip", 0, nullptr, nullptr);
-            if (r != 0) {
-                if (report) set_last_error(std::string("hiprtcCreateProgram: ") + rc->hiprtcGetErrorString(r));
-                return PTL_ERR_COMPILE;
-            }
-            std::vector<const char*> copts;
-            for (auto& o : options) copts.push_back(o.c_str());
-            r = rc->hiprtcCompileProgram(prog, (int)copts.size(), copts.data());
-            size_t log_size = 0;
-            rc->hiprtcGetProgramLogSize(prog, &log_size);
-            if (log_size > 1 && report) {
-                std::vector<char> buf(log_size + 1, 0);
-                rc->hiprtcGetProgramLog(prog, buf.data());
-                if (log && log_cap) {
-                    std::strncpy(log, buf.data(), log_cap - 1);
-                    log[log_cap - 1] = '\0';
-                }
-                if (r != 0) set_last_error(std::string("hiprtc: ") + buf.data());
-            }
-            if (r != 0) {
-                if (log_size <= 1 && report) set_last_error(std::string("hiprtcCompileProgram: ") + rc->hiprtcGetErrorString(r));
-                rc->hiprtcDestroyProgram(&prog);
-                return PTL_ERR_COMPILE;
-            }
-            size_t code_size = 0;
-            rc->hiprtcGetCodeSize(prog, &code_size);
-            code.resize(code_size);
-            rc->hiprtcGetCode(prog, code.data());
-            rc->hiprtcDestroyProgram(&prog);
-            return PTL_OK;
-        };
-        if (int rc1 = run_hiprtc(opts, k->code, true); rc1 != PTL_OK) return rc1;
-        // 128 VGPRs is where the fourth wave per SIMD goes.  A kernel that lands a few registers above it without having been told an
-        // occupancy (no PTL_WAVES_PER_EU: the module inliner's builds of portal_in_portal with the Panini switch and the slices entry, 130
-        // VGPRs, 0.262 -> 0.314 ms per frame) is compiled once more with __launch_bounds__(256, 4); that build is kept if the allocator got
-        // there without spilling (the same source under a register cap: same arithmetic, same frames).  One more hiprtc run, for the rare
-        // kernel in that band, stored under the key of the options the caller asked for.
-        bool hinted = false;
-        for (auto& o : opts) hinted = hinted || o.find("PTL_WAVES_PER_EU") != std::string::npos;  // (a define of the caller's, or PTL_HIPRTC_FLAGS of an experiment)
-        const int vgprs = code_object_note_max(k->code, ".vgpr_count", "ptl_render");  // the render entries only
-        if (!hinted && !teleport_only && vgprs > 128 && vgprs <= 168 && !std::getenv("PTL_NO_OCCUPANCY_RETRY")) {
-            std::vector<std::string> capped = opts;
-            capped.push_back("-DPTL_WAVES_PER_EU=4");
-            std::vector<char> second;
-            bool settled = false;
-            if (run_hiprtc(capped, second, false) == PTL_OK && code_object_note_max(second, ".vgpr_spill_count", "ptl_render") == 0 &&
-                code_object_note_max(second, ".private_segment_fixed_size", "ptl_render") <= code_object_note_max(k->code, ".private_segment_fixed_size", "ptl_render")) {
-                k->code.swap(second);
-                settled = true;
-            }
-            // ... and if the cap only produces spills while this build came from the module inliner -- whose schedule needs ~10 registers
-            // more than the bottom-up pipeline's (portal_in_portal_plus_ultra with its Ints baked: 139 against 128) -- the toolchain's own
-            // pipeline gets a try under the same cap: kept when it fits four waves without spilling.  Three hiprtc runs for such a kernel, once (the code
-            // object is cached under the key of the options the caller asked for).
-            if (!settled) {
-                std::vector<std::string> bottom_up;
-                for (size_t i = 0; i < opts.size(); ++i) {
-                    if (opts[i] == "-mllvm" && i + 1 < opts.size() && opts[i + 1] == "-enable-module-inliner") {
-                        ++i;
-                        continue;
-                    }
-                    bottom_up.push_back(opts[i]);
-                }
-                bottom_up.push_back("-DPTL_WAVES_PER_EU=4");
-                std::vector<char> third;
-                if (bottom_up.size() < opts.size() && run_hiprtc(bottom_up, third, false) == PTL_OK && code_object_note_max(third, ".vgpr_count", "ptl_render") <= 128 &&
-                    code_object_note_max(third, ".vgpr_spill_count", "ptl_render") == 0 &&
-                    code_object_note_max(third, ".private_segment_fixed_size", "ptl_render") <= code_object_note_max(k->code, ".private_segment_fixed_size", "ptl_render"))
-                    k->code.swap(third), settled = true;
-            }
-            // Round 6: ... and when no cap gets there without spilling, the -O1 pipeline gets a try without one.  What pushes a kernel into this band
-            // is -O3's appetite (hoisting and unrolling across the scene's loops): the un-specialised headline kernel is 139 VGPRs and three waves
-            // per SIMD at -O3, 128 + 8 bytes of scratch under the cap, and 117 VGPRs without a spill at -O1 -- 0.825 / 0.705 / 0.703 ms
-            // (profiles/r06/unspec_anatomy.jsonl): "-O1 beats -O3 on this kernel" (VERDICT r5 #5b) is an occupancy effect, and this is the rule that
-            // follows from it.  Kept when it fits four waves with no spill; same source, same contract, same frames.
-            if (!settled && !quick_build(opts)) {
-                std::vector<std::string> o1 = opts;
-                for (auto& o : o1)
-                    if (o == "-O3") o = "-O1";
-                std::vector<char> fourth;
-                if (o1 != opts && run_hiprtc(o1, fourth, false) == PTL_OK && code_object_note_max(fourth, ".vgpr_count", "ptl_render") <= 128 &&
-                    code_object_note_max(fourth, ".vgpr_spill_count", "ptl_render") == 0 &&
-                    code_object_note_max(fourth, ".private_segment_fixed_size", "ptl_render") <= code_object_note_max(k->code, ".private_segment_fixed_size", "ptl_render"))
-                    k->code.swap(fourth);
-            }
-        }
-        if (!cache_path.empty()) {
-            ::mkdir(cdir.c_str(), 0755);
-            // one temp file per COMPILE, not per process: background re-JIT workers and the ranks of a frame group compile the same source on
-            // several threads of one process, and a shared temp path would let one of them rename a file another is still writing
-            static std::atomic<unsigned long> compile_serial{0};
-            std::string tmp = cache_path + ".tmp" + std::to_string((long)getpid()) + "." + std::to_string(compile_serial.fetch_add(1));
-            std::ofstream f(tmp, std::ios::binary);
-            f.write(k->code.data(), (std::streamsize)k->code.size());
-            f.close();
-            if (f) std::rename(tmp.c_str(), cache_path.c_str());
-        }
-    }
-    if (device < 0) {  // compile-only handle
-        *out = k.release();
-        return PTL_OK;
-    }
-
-    std::string err;
-    const hip::Runtime* rt = hip::runtime(&err);
-    if (!rt) {
-        set_last_error(err);
-        return PTL_ERR_NO_DEVICE;
-    }
-    if (!hip_ok(rt, rt->hipSetDevice(device), "hipSetDevice")) return PTL_ERR_HIP;
-    if (!hip_ok(rt, rt->hipModuleLoadData(&k->module, k->code.data()), "hipModuleLoadData")) {
-        if (from_cache && !cache_path.empty()) {
-            // a cached code object this runtime refuses (other GPU, damaged file): drop it and build from source ONCE.  The retry does
-            // not read the cache again -- the file may be undeletable (a read-only or shared cache directory travels from the build
-            // container to the GPU box), and re-reading it would recurse without end.
-            std::remove(cache_path.c_str());
-            tl_skip_cache_read = true;
-            const int rc2 = ptl_kernel_compile(device, hip_source, uniforms, n_uniforms, uniform_block_size, defines, n_defines, out, log, log_cap);
-            tl_skip_cache_read = false;
-            return rc2;
-        }
-        return PTL_ERR_HIP;
-    }
-    if (teleport_only) {
-        k->fn = nullptr;  // the teleport half of a split build: no render entry by construction
-    } else if (rt->hipModuleGetFunction(&k->fn, k->module, "ptl_render_kernel") != 0) {
-        rt->hipGetLastError();
-        // a module with the slices entry instead (codegen.cpp `apply_slices_entry`)
-        if (!hip_ok(rt, rt->hipModuleGetFunction(&k->fn, k->module, "ptl_render_slices_kernel"), "hipModuleGetFunction(ptl_render_kernel / ptl_render_slices_kernel)"))
-            return PTL_ERR_HIP;
-        if (!hip_ok(rt, rt->hipModuleGetFunction(&k->derive_slices_fn, k->module, "ptl_derive_slices_kernel"), "hipModuleGetFunction(ptl_derive_slices_kernel)"))
-            return PTL_ERR_HIP;
-        k->sliced = true;
-    }
-    if (rt->hipModuleGetFunction(&k->teleport_fn, k->module, "ptl_teleport_kernel") != 0) {
-        k->teleport_fn = nullptr;   // hand-written layer-1 kernels need not have the second entry point
-        rt->hipGetLastError();      // ... and the expected hipErrorNotFound must not stay behind as the thread's sticky
-                                    // error: the next HIP user in the process (PyTorch) would report it as its own
-    }
-    if (rt->hipModuleGetFunction(&k->derive_fn, k->module, "ptl_derive_kernel") != 0) {
-        k->derive_fn = nullptr;
-        rt->hipGetLastError();
-    }
-    if (!hip_ok(rt, rt->hipModuleGetGlobal(&k->dev_block, &k->dev_block_size, k->module, "_ZN4glsl5ptl_uE"), "hipModuleGetGlobal(ptl_u)"))
-        return PTL_ERR_HIP;
-    if (k->dev_block_size < uniform_block_size) {
-        set_last_error("uniform block in the code object is smaller than the declared layout");
-        return PTL_ERR_INVALID;
-    }
-    rt->hipEventCreate(&k->ev0);
-    rt->hipEventCreate(&k->ev1);
-    rt->hipEventCreateWithFlags(&k->ev_done, hip::kEventDisableTiming);
-    if (const char* e = std::getenv("PTL_BLOCK_WAVES")) k->block_waves = (e[0] == '1' || e[0] == '2') ? (unsigned)(e[0] - '0') : 4u;
-    *out = k.release();
-    return PTL_OK;
+    return compile_kernel({device, hip_source, uniforms, n_uniforms, uniform_block_size, defines, n_defines, log, log_cap}, &copy, false, out);
 }
 
 // A second instance of a compiled kernel on the same device: the same code object loaded once more, hence a uniform block (and a
@@ -518,7 +564,7 @@ extern "C" int ptl_kernel_clone(ptl_kernel* src, ptl_kernel** out) {
     if (src->device < 0 || !src->fn) return PTL_ERR_NO_DEVICE;
     const hip::Runtime* rt = hip::runtime(nullptr);
     if (!rt) return PTL_ERR_NO_DEVICE;
-    auto k = std::make_unique<ptl_kernel>();
+    KernelPtr k(new ptl_kernel());
     k->device = src->device;
     k->code = src->code;
     k->slots = src->slots;
@@ -527,32 +573,9 @@ extern "C" int ptl_kernel_clone(ptl_kernel* src, ptl_kernel** out) {
     k->split = src->split;
     k->source = src->source;
     k->defines = src->defines;
+    // (affine_rays is NOT inherited: a clone accepts matrices through ptl_kernel_set_uniform that its original refuses)
     if (!hip_ok(rt, rt->hipSetDevice(k->device), "hipSetDevice")) return PTL_ERR_HIP;
-    if (!hip_ok(rt, rt->hipModuleLoadData(&k->module, k->code.data()), "hipModuleLoadData(clone)")) return PTL_ERR_HIP;
-    auto fail = [&](int rc) {
-        rt->hipModuleUnload(k->module);
-        k->module = nullptr;
-        return rc;
-    };
-    if (rt->hipModuleGetFunction(&k->fn, k->module, src->sliced ? "ptl_render_slices_kernel" : "ptl_render_kernel") != 0 ||
-        (src->sliced && rt->hipModuleGetFunction(&k->derive_slices_fn, k->module, "ptl_derive_slices_kernel") != 0)) {
-        hip_ok(rt, 1, "hipModuleGetFunction(clone)");
-        return fail(PTL_ERR_HIP);
-    }
-    k->sliced = src->sliced;
-    if (rt->hipModuleGetFunction(&k->teleport_fn, k->module, "ptl_teleport_kernel") != 0) {
-        k->teleport_fn = nullptr;
-        rt->hipGetLastError();
-    }
-    if (rt->hipModuleGetFunction(&k->derive_fn, k->module, "ptl_derive_kernel") != 0) {
-        k->derive_fn = nullptr;
-        rt->hipGetLastError();
-    }
-    if (!hip_ok(rt, rt->hipModuleGetGlobal(&k->dev_block, &k->dev_block_size, k->module, "_ZN4glsl5ptl_uE"), "hipModuleGetGlobal(ptl_u)")) return fail(PTL_ERR_HIP);
-    rt->hipEventCreate(&k->ev0);
-    rt->hipEventCreate(&k->ev1);
-    rt->hipEventCreateWithFlags(&k->ev_done, hip::kEventDisableTiming);
-    k->dirty = true;
+    if (int rc = bind_module(k.get(), rt, src->sliced ? RenderEntry::Sliced : RenderEntry::Plain, k->shadow.size()); rc != PTL_OK) return rc;
     *out = k.release();
     return PTL_OK;
 }
@@ -611,15 +634,10 @@ extern "C" int ptl_kernel_set_uniform(ptl_kernel* k, const char* name, ptl_type 
         // (capi.cpp `camera_is_affine`, `zero_patterns_broken`); a direct caller gets the refusal instead of silently wrong frames.
         const std::string nm = name;
         auto tail = [&](const char* e) { const size_t m = std::strlen(e); return nm.size() >= m && nm.compare(nm.size() - m, m, e) == 0; };
-        if (nm == "_camera" || tail("_mat") || tail("_mat_inv") || tail("_mat_teleport")) {
-            const float* f = static_cast<const float*>(value);
-            bool all_nan = true;
-            for (int e = 0; e < 16; ++e) all_nan = all_nan && f[e] != f[e];
-            if (!all_nan && !(f[3] == 0.0f && f[7] == 0.0f && f[11] == 0.0f && f[15] == 1.0f)) {
-                set_last_error("ptl_kernel_set_uniform: `" + nm + "` is not an affine matrix (bottom row 0 0 0 1) but this kernel was generated with PTL_AFFINE_RAYS; "
-                               "regenerate with flag bit23 (NO AFFINE RAYS)");
-                return PTL_ERR_INVALID;
-            }
+        if ((nm == "_camera" || tail("_mat") || tail("_mat_inv") || tail("_mat_teleport")) && !matrix_keeps_rays_affine(static_cast<const float*>(value))) {
+            set_last_error("ptl_kernel_set_uniform: `" + nm + "` is not an affine matrix (bottom row 0 0 0 1) but this kernel was generated with PTL_AFFINE_RAYS; "
+                           "regenerate with flag bit23 (NO AFFINE RAYS)");
+            return PTL_ERR_INVALID;
         }
     }
     if (std::memcmp(k->shadow.data() + it->second.offset, value, n) != 0) {
@@ -735,8 +753,12 @@ static int upload_slices(ptl_kernel* k, const hip::Runtime* rt, void* stream, in
     return PTL_OK;
 }
 
-static int launch_slices(ptl_kernel* k, const hip::Runtime* rt, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
-                         void* segments, void* stream, float* elapsed_ms) {
+static const char* const kSlicesLaunch = "hipModuleLaunchKernel(ptl_render_slices_kernel)";
+
+// The one render launch.  A module with the slices entry traces slices 0 .. n-1 of its buffer of blocks, slice z into out_rgba8 + z * slice_pixels
+// pixels; the plain entry (n = 1) reads the module's own block.  `label`: what a refused launch is reported as.
+static int launch_render(ptl_kernel* k, const hip::Runtime* rt, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
+                         void* segments, void* stream, float* elapsed_ms, const char* label) {
     int nby = shard_blocks(frame);
     if (nby == 0) {
         if (elapsed_ms) *elapsed_ms = 0.0f;
@@ -745,12 +767,13 @@ static int launch_slices(ptl_kernel* k, const hip::Runtime* rt, const ptl_frame*
     int width = frame->width, height = frame->height, phase = frame->rb_phase, stride = frame->rb_stride;
     int in_place = frame->in_place ? 1 : 0;
     void* blocks = k->dev_slices;
-    void* args[] = {&blocks, &slice_pixels, &out_rgba8, &out_rgba32f, &width, &height, &phase, &stride, &segments, &in_place};
+    void* args[] = {&blocks, &slice_pixels, &out_rgba8, &out_rgba32f, &width, &height, &phase, &stride, &segments, &in_place};  // the plain entry takes the last eight
+    // 256 threads = four 8x8 tiles side by side.  PTL_BLOCK_WAVES=1|2 (experiment, tools/variants.py) launches narrower workgroups.
     const unsigned waves = k->block_waves;
     unsigned gx = (unsigned)((width + 8 * waves - 1) / (8 * waves)), gy = (unsigned)nby;
     if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
-    if (!hip_ok(rt, rt->hipModuleLaunchKernel(k->fn, gx, gy, (unsigned)n, 64 * waves, 1, 1, 0, stream, args, nullptr), "hipModuleLaunchKernel(ptl_render_slices_kernel)")) return PTL_ERR_HIP;
-    k->staged_since_launch = false;  // what was staged is launched: retired texel buffers go with the next re-bind (hipFree waits for this launch)
+    if (!hip_ok(rt, rt->hipModuleLaunchKernel(k->fn, gx, gy, (unsigned)n, 64 * waves, 1, 1, 0, stream, k->sliced ? args : args + 2, nullptr), label)) return PTL_ERR_HIP;
+    if (k->sliced) k->staged_since_launch = false;  // what was staged is launched: retired texel buffers go with the next re-bind (hipFree waits for this launch)
     k->last_stream = stream;
     k->launched = true;
     if (k->ev_done) rt->hipEventRecord(k->ev_done, stream);
@@ -823,7 +846,7 @@ extern "C" int ptl_kernel_render_slices(ptl_kernel* k, const ptl_frame* frame, i
     const hip::Runtime* rt = hip::runtime(nullptr);
     if (!hip_ok(rt, rt->hipSetDevice(k->device), "hipSetDevice")) return PTL_ERR_HIP;
     if (int rc = upload_slices(k, rt, stream, n, false); rc != PTL_OK) return rc;
-    return launch_slices(k, rt, frame, n, out_rgba8, out_rgba32f, slice_pixels, nullptr, stream, elapsed_ms);
+    return launch_render(k, rt, frame, n, out_rgba8, out_rgba32f, slice_pixels, nullptr, stream, elapsed_ms, kSlicesLaunch);
 }
 
 extern "C" int ptl_kernel_render(ptl_kernel* k, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* segments,
@@ -832,33 +855,9 @@ extern "C" int ptl_kernel_render(ptl_kernel* k, const ptl_frame* frame, void* ou
     if (k->device < 0 || !k->fn) return PTL_ERR_NO_DEVICE;
     const hip::Runtime* rt = hip::runtime(nullptr);
     if (!hip_ok(rt, rt->hipSetDevice(k->device), "hipSetDevice")) return PTL_ERR_HIP;
-    if (k->sliced) {  // a single draw of a module with the slices entry: slice 0 of its buffer, one slice
-        if (int rc = upload_slices(k, rt, stream, 1, true); rc != PTL_OK) return rc;
-        return launch_slices(k, rt, frame, 1, out_rgba8, out_rgba32f, 0, segments, stream, elapsed_ms);
-    }
-    if (int rc = upload_uniforms(k, rt, stream); rc != PTL_OK) return rc;
-    int nby = shard_blocks(frame);
-    if (nby == 0) {
-        if (elapsed_ms) *elapsed_ms = 0.0f;
-        return PTL_OK;
-    }
-    int width = frame->width, height = frame->height, phase = frame->rb_phase, stride = frame->rb_stride;
-    int in_place = frame->in_place ? 1 : 0;
-    void* args[] = {&out_rgba8, &out_rgba32f, &width, &height, &phase, &stride, &segments, &in_place};
-    // 256 threads = four 8x8 tiles side by side.  PTL_BLOCK_WAVES=1|2 (experiment, tools/variants.py) launches narrower workgroups.
-    const unsigned waves = k->block_waves;
-    unsigned gx = (unsigned)((width + 8 * waves - 1) / (8 * waves)), gy = (unsigned)nby;
-    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
-    if (!hip_ok(rt, rt->hipModuleLaunchKernel(k->fn, gx, gy, 1, 64 * waves, 1, 1, 0, stream, args, nullptr), "hipModuleLaunchKernel")) return PTL_ERR_HIP;
-    k->last_stream = stream;
-    k->launched = true;
-    if (k->ev_done) rt->hipEventRecord(k->ev_done, stream);
-    if (elapsed_ms) {
-        rt->hipEventRecord(k->ev1, stream);
-        if (!hip_ok(rt, rt->hipEventSynchronize(k->ev1), "hipEventSynchronize")) return PTL_ERR_HIP;
-        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
-    }
-    return PTL_OK;
+    // (a single draw of a module with the slices entry: slice 0 of its buffer, one slice)
+    if (int rc = k->sliced ? upload_slices(k, rt, stream, 1, true) : upload_uniforms(k, rt, stream); rc != PTL_OK) return rc;
+    return launch_render(k, rt, frame, 1, out_rgba8, out_rgba32f, 0, segments, stream, elapsed_ms, k->sliced ? kSlicesLaunch : "hipModuleLaunchKernel");
 }
 
 extern "C" int ptl_kernel_render_to_host(ptl_kernel* k, const ptl_frame* frame, uint8_t* host_rgba8, float* host_rgba32f,
