@@ -513,6 +513,27 @@ int ptl_deinterleave_rows(const uint8_t* shard_rgba8, const ptl_frame* frame, ui
 int ptl_average_images(int device, const void* const* frames_rgba8, int n_frames, void* out_rgba8, int width, int height, void* stream,
                        float* elapsed_ms);
 
+/* The same averaging fused with the conversion to what a video encoder consumes: N RGBA8 sub-frames -> one planar Y'CbCr 4:2:0
+ * 10-bit frame (BT.709 matrix on the gamma-encoded values, full range), the payload of one Y4M frame.  The averaged RGBA8 frame is
+ * never written: the kernel reads 4*N bytes and writes 3 bytes per pixel.
+ * Contract: let A(x, y) = (R, G, B) be the RGBA8 frame ptl_average_images would have written for n_frames >= 2; for n_frames == 1
+ * (a plain RGBA8 -> YUV conversion) the input's own RGB.  Alpha is ignored.  All arithmetic is 32-bit integer:
+ *   Y  = (55896 R + 188037 G + 18982 B + 32768) >> 16                                        per pixel
+ *   S_c = sum over dy = 0, 1 of A_c(2i-1, 2j+dy) + 2 A_c(2i, 2j+dy) + A_c(2i+1, 2j+dy)        coordinates clamped to the frame
+ *   Cb = min(1023, (-30123 S_R - 101335 S_G + 131458 S_B + (512 << 19) + (1 << 18)) >> 19)
+ *   Cr = min(1023, (131458 S_R - 119404 S_G -  12054 S_B + (512 << 19) + (1 << 18)) >> 19)
+ * i.e. H.273 Y = round(1023 E'y), C = round(1023 E'pb) + 512 with coefficients round(K * 1023 / 255 * 2^16), chroma sited like
+ * MPEG-2 ("left": co-sited with luma column 2i, weights 1-2-1; the mean of rows 2j and 2j+1).
+ * Layout of out_yuv (DEVICE pointer, 16-byte aligned, ptl_yuv420p10_frame_bytes(w, h) = 2 (W H + 2 cw ch) bytes): the Y plane, W*H
+ * little-endian uint16, row 0 on top; then Cb and Cr, cw*ch each, cw = (W+1)/2, ch = (H+1)/2.  Any width, height >= 1 (W*H <= 2^29).
+ * Validation, stream and timing are those of ptl_average_images.  There is no host-side conversion. */
+int ptl_average_to_yuv420p10(int device, const void* const* frames_rgba8, int n_frames, void* out_yuv, int width, int height, void* stream,
+                             float* elapsed_ms);
+size_t ptl_yuv420p10_frame_bytes(int width, int height);
+/* The Y4M stream such frames travel in: "YUV4MPEG2 W<w> H<h> F<fps>:1 Ip A1:1 C420p10 XYSCSS=420P10 XCOLORRANGE=FULL\n" once, then
+ * "FRAME\n" + payload per frame.  Writes the header (NUL-terminated) into buf and returns its length; PTL_ERR_INVALID when it does not fit. */
+int ptl_y4m_header(int width, int height, int fps, char* buf, size_t cap);
+
 /* Device frame buffers for callers that keep frames on the GPU between kernels (sub-frames -> ptl_average_images ->
  * one download); the reference's counterpart is the macroquad render target + Texture2D::get_texture_data()
  * (src/main.rs:1041-1042,1803-1816).  ptl_device_download waits for `stream` first (it is a stream-ordered copy). */

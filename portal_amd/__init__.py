@@ -180,6 +180,9 @@ def _load() -> C.CDLL:
         "ptl_renderer_destroy": (None, [vp]),
         "ptl_deinterleave_rows": (ci, [vp, P(Frame), vp]),
         "ptl_average_images": (ci, [ci, P(vp), ci, vp, ci, ci, vp, P(C.c_float)]),
+        "ptl_average_to_yuv420p10": (ci, [ci, P(vp), ci, vp, ci, ci, vp, P(C.c_float)]),
+        "ptl_yuv420p10_frame_bytes": (cs, [ci, ci]),
+        "ptl_y4m_header": (ci, [ci, ci, ci, cp, cs]),
         "ptl_device_alloc": (ci, [ci, cs, P(vp)]),
         "ptl_device_free": (ci, [vp]),
         "ptl_device_download": (ci, [vp, vp, cs, vp]),
@@ -763,6 +766,28 @@ def average_images_device(frame_ptrs, out_ptr: int, width: int, height: int, dev
     _check(lib().ptl_average_images(device, arr, len(frame_ptrs), C.c_void_p(out_ptr), width, height, C.c_void_p(stream or None), C.byref(ms) if timed else None),
            "average_images")
     return ms.value if timed else None
+
+
+def average_to_yuv420p10_device(frame_ptrs, out_ptr: int, width: int, height: int, device: int = 0, stream: int = 0, timed: bool = False):
+    """ptl_average_to_yuv420p10 on DEVICE buffers given as integer addresses: the sub-frames averaged like `average_images_device` and
+    converted to one planar Y'CbCr 4:2:0 10-bit frame (`yuv420p10_frame_bytes` bytes at out_ptr) by the same kernel."""
+    arr = (C.c_void_p * len(frame_ptrs))(*frame_ptrs)
+    ms = C.c_float()
+    _check(lib().ptl_average_to_yuv420p10(device, arr, len(frame_ptrs), C.c_void_p(out_ptr), width, height, C.c_void_p(stream or None), C.byref(ms) if timed else None),
+           "average_to_yuv420p10")
+    return ms.value if timed else None
+
+
+def yuv420p10_frame_bytes(width: int, height: int) -> int:
+    """Bytes of one frame as `average_to_yuv420p10_device` writes it = the payload of one Y4M frame."""
+    return int(lib().ptl_yuv420p10_frame_bytes(width, height))
+
+
+def y4m_header(width: int, height: int, fps: int) -> bytes:
+    """The header line of the Y4M stream those frames travel in (each frame: b"FRAME\\n" + payload)."""
+    buf = C.create_string_buffer(128)
+    n = _check(lib().ptl_y4m_header(width, height, fps, buf, len(buf)), "y4m_header")
+    return buf.raw[:n]
 
 
 def device_alloc(nbytes: int, device: int = 0) -> int:

@@ -6,13 +6,20 @@
 // Video pipeline (render): for every frame i of a clip, `motion_blur_frames` sub-frames are traced straight into
 // device buffers (aa_start = j, time = i/count + j/blur/count*exposure), averaged on the GPU (ptl_average_images),
 // downloaded once, and PNG-encoded on a pool of host threads while the GPU already traces the next frame.
+// With --frames y4m the averaging kernel is the fused one (ptl_average_to_yuv420p10): what is downloaded is the planar 4:2:0 10-bit
+// frame the encoder consumes, and one writer thread streams the frames in order into ffmpeg's stdin (or a .y4m file) while the
+// clip is still rendering: no PNG files, no anim/ directory, no zscale pass.
 #include <dirent.h>
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <signal.h>
+
 #include <algorithm>
+#include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -20,6 +27,7 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -42,6 +50,9 @@ void usage() {
                  "                  [--specialize 0|1]   bake what is constant within a clip into the kernel (default: when it pays)\n"
                  "                  [--fast]             tolerance mode for the whole clip (hardware rcp / sqrt, FMA contraction)\n"
                  "                  [--timing]           wait for every kernel and report GPU time (no host/GPU overlap)\n"
+                 "                  [--frames png|y4m]   png (default): anim/frame_%%d.png, then ffmpeg.  y4m: YUV 4:2:0 10-bit frames from the GPU, streamed in order\n"
+                 "                                       into ffmpeg's stdin while the clip renders (or to video/<scene>/<clip>.y4m without ffmpeg, with --max-frames).\n"
+                 "                                       Not with --shard K/N, N > 1 (a stream needs every frame, in order); a clip is not resumed, it starts at frame 0\n"
                  "       portal-amd emit-source <scene.ron> [--stage NAME]     print the generated HIP kernel source\n"
                  "       portal-amd check <scene.ron> [--stage NAME]           compile for gfx950 (no GPU needed); errors by scene element\n"
                  "       portal-amd write <scene.ron> [--stage NAME] [--set UNIFORM=VALUE ...] --output out.ron     the reference's RON writer\n"
@@ -190,6 +201,7 @@ constexpr int kFrameDeflateLevel = 3;
 struct Options {
     std::string scene, clips, output = "frame.png", asset_root = ".", stage, animation, camera, scenes_dir = "scenes", out_dir = ".", starts_with;
     bool have_camera = false, stereo = false, skip_existing = true;
+    bool y4m = false;     // render --frames y4m: frames leave as one Y4M stream instead of PNG files
     int batch = -1;       // render --batch-subframes 0|1: one launch for a frame's blur sub-frames (default: on where 2 <= blur <= 16)
     int concurrent = -1;  // render --concurrent-draws K: kernel instances in flight for a frame's blur sub-frames (default 1: measured, no gain)
     std::vector<std::pair<std::string, double>> sets;  // --set name=value
@@ -509,6 +521,85 @@ int precompile(const Options& o) {
     return 0;
 }
 
+// One clip as a Y4M stream (--frames y4m): a file, or the stdin of an encoder started as a fresh child process.  Written by ONE thread
+// in frame order; the first error sticks, later writes do nothing, and the clip loop looks at failed() before every frame -- a dead
+// encoder ends the clip instead of blocking it (SIGPIPE is ignored in this mode: the write returns EPIPE).
+class Y4mStream {
+public:
+    ~Y4mStream() { close(); }
+    bool open_file(const std::string& path) {
+        fd_ = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+        if (fd_ < 0) fail("cannot write `" + path + "`: " + std::strerror(errno));
+        return fd_ >= 0;
+    }
+    bool open_program(const std::vector<std::string>& argv) {  // like run_program, with our pipe as its stdin
+        int ends[2];
+        if (::pipe2(ends, O_CLOEXEC) != 0) return fail("pipe: " + std::string(std::strerror(errno))), false;
+        std::vector<char*> args;  // (built before the fork: the child only redirects and executes)
+        for (const std::string& a : argv) args.push_back(const_cast<char*>(a.c_str()));
+        args.push_back(nullptr);
+        started_ = std::chrono::steady_clock::now();
+        child_ = fork();
+        if (child_ < 0) {
+            ::close(ends[0]);
+            ::close(ends[1]);
+            return fail("fork: " + std::string(std::strerror(errno))), false;
+        }
+        if (child_ == 0) {
+            dup2(ends[0], 0);  // (the copy is not close-on-exec; the write end is, so the child sees the end of the stream)
+            int null_fd = ::open("/dev/null", O_WRONLY);
+            if (null_fd >= 0) {
+                dup2(null_fd, 1);
+                dup2(null_fd, 2);
+            }
+            execvp(args[0], args.data());
+            _exit(127);
+        }
+        ::close(ends[0]);
+        fd_ = ends[1];
+        return true;
+    }
+    void write(const void* data, size_t n) {
+        const char* p = static_cast<const char*>(data);
+        while (n > 0 && !failed()) {
+            ssize_t done = ::write(fd_, p, n);
+            if (done < 0 && errno == EINTR) continue;
+            if (done < 0) return fail(std::string(child_ > 0 ? "the encoder stopped reading the stream: " : "cannot write the stream: ") + std::strerror(errno));
+            p += done;
+            n -= (size_t)done;
+        }
+    }
+    void fail(const std::string& what) {
+        if (failed()) return;
+        error_ = what;
+        failed_.store(true, std::memory_order_release);
+    }
+    bool failed() const { return failed_.load(std::memory_order_acquire); }
+    const std::string& error() const { return error_; }  // valid once failed()
+    bool to_program() const { return child_ > 0; }
+    double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - started_).count(); }
+    // end of stream; for a child its exit status (-1: it did not exit by itself), for a file 0
+    int close() {
+        if (fd_ >= 0 && ::close(fd_) != 0) fail(std::string("cannot write the stream: ") + std::strerror(errno));
+        fd_ = -1;
+        if (child_ <= 0) return 0;
+        int status = 0;
+        pid_t got = waitpid(child_, &status, 0);
+        child_ = -1;
+        return got > 0 && WIFEXITED(status) ? WEXITSTATUS(status) : -1;
+    }
+
+private:
+    int fd_ = -1;
+    pid_t child_ = -1;
+    std::atomic<bool> failed_{false};
+    std::string error_;
+    std::chrono::steady_clock::time_point started_ = std::chrono::steady_clock::now();
+};
+
+int run_program(const std::vector<std::string>& argv, bool quiet);
+std::vector<std::string> encoder_arguments(const std::string& video);
+
 // What the clip loop keeps in flight: the download of frame i runs on its own stream into page-locked memory while frame i+1
 // is being traced; `kRing` result buffers so a frame is not overwritten before its copy has left.
 struct FramePipeline {
@@ -539,7 +630,8 @@ struct FramePipeline {
 
 // render_animation (src/main.rs:1758-1873)
 int render_clip(const Options& o, ptl_scene* scene, ptl_renderer* r, const std::string& scene_name, const std::string& clip, double duration, int fps,
-                int width, int height, std::vector<void*>& subframes, FramePipeline& pipe, EncoderPool& pool, PinnedFrames& pinned) {
+                int width, int height, std::vector<void*>& subframes, FramePipeline& pipe, EncoderPool& pool, PinnedFrames& pinned, Y4mStream* y4m,
+                EncoderPool* y4m_writer) {
     auto started = std::chrono::steady_clock::now();
     int rejits_before = ptl_renderer_rejit_count(r);
     std::string video_base = o.out_dir + "/video/" + scene_name + "/" + clip;
@@ -549,17 +641,41 @@ int render_clip(const Options& o, ptl_scene* scene, ptl_renderer* r, const std::
     }
     make_dirs(dir_of(video_base));
     std::string anim_dir = o.out_dir + "/anim";
-    make_dirs(anim_dir);
+    if (!y4m) make_dirs(anim_dir);
     int count = std::max(1, (int)((float)duration * (float)fps));  // ((duration_seconds * fps as f32) as usize).max(1)
     const double exposure = 0.5;
     size_t frame_bytes = (size_t)width * height * 4;
+    const size_t yuv_bytes = y4m ? ptl_yuv420p10_frame_bytes(width, height) : 0;
+    if (y4m) {
+        // Where the stream goes: into an encoder when there is one and the clip is whole, else into a file an encoder can read later.
+        // The encoder is told nothing about scaling or pixel formats: the stream is what it encodes, the -color_* tags say what it is.
+        char header[128];
+        int header_len = ptl_y4m_header(width, height, fps, header, sizeof header);
+        if (header_len < 0) return fail("y4m header");
+        std::vector<std::string> encode = {"ffmpeg", "-f", "yuv4mpegpipe", "-i", "-"};
+        for (const std::string& a : encoder_arguments(video_base + ".mov")) encode.push_back(a);
+        if (o.max_frames < 0 && o.shards == 1 && run_program({"ffmpeg", "-version"}, true) == 0) {
+            std::printf("Start ffmpeg to encode the frames as they arrive\n");
+            y4m->open_program(encode);
+        } else {
+            std::string command;
+            for (const std::string& a : encode) command += (command.empty() ? "" : " ") + (a == "-" ? clip + ".y4m" : a);
+            std::printf("Frames go to `%s.y4m` (%s)\n", video_base.c_str(), command.c_str());
+            y4m->open_file(video_base + ".y4m");
+        }
+        y4m->write(header, (size_t)header_len);
+    }
     double gpu_ms = 0.0;
     long traced = 0, drawn_frames = 0;
     ptl_frame frame{width, height, 0, 1, 0};
     int last = o.max_frames >= 0 ? std::min(count, o.max_frames) : count;
     for (int i = 0; i < last; ++i) {
         std::string name = anim_dir + "/frame_" + std::to_string(i) + ".png";
-        if (i % o.shards != o.shard || exists(name)) {
+        if (y4m && y4m->failed()) {
+            std::fprintf(stderr, "\n%s\n", y4m->error().c_str());
+            return 1;
+        }
+        if (i % o.shards != o.shard || (!y4m && exists(name))) {  // (a stream is not resumed: it holds every frame, from frame 0)
             // Not ours (shard K of N takes every N-th frame) or already on disk.  The camera is stateful -- where it is relative
             // to the portals depends on the path it took (teleport_camera) -- so the host step still runs for every sub-frame:
             // a shard, or a resumed run, then sees exactly the cameras of an uninterrupted run.  (The reference skips the
@@ -577,7 +693,7 @@ int render_clip(const Options& o, ptl_scene* scene, ptl_renderer* r, const std::
             double t = ((double)i / count) + (double)j / o.blur / count * exposure;
             ptl_renderer_set_option(r, "aa_start", j);
             if (ptl_renderer_update(r, t * (double)(float)duration, nullptr, nullptr) != PTL_OK) return fail("update");
-            void* target = o.blur > 1 ? subframes[j] : pipe.results[slot];  // one image: average_images hands it back untouched
+            void* target = o.blur > 1 || y4m ? subframes[j] : pipe.results[slot];  // one image: average_images hands it back untouched (y4m: converted with n = 1)
             float ms = 0.0f;
             if (batched) {
                 // everything a draw does short of launching; the launch follows behind the last sub-frame, once for all of them
@@ -596,9 +712,17 @@ int render_clip(const Options& o, ptl_scene* scene, ptl_renderer* r, const std::
                 if (ptl_renderer_join(r, nullptr) != PTL_OK) return fail("join");  // (the download below is on the default stream)
                 for (int which = 0; which < 2; ++which) {
                     if (!(which == 0 ? first : final_one)) continue;
+                    std::string still_name = video_base + (which == 0 ? ".start.png" : ".end.png");
+                    if (y4m) {  // the pinned buffers hold 4:2:0 frames here, smaller than an RGBA8 one: the two stills of a clip take pageable memory
+                        auto rgba = std::make_shared<std::vector<uint8_t>>(frame_bytes);
+                        if (ptl_device_download(rgba->data(), (batched && which == 0) ? subframes[0] : target, frame_bytes, nullptr) != PTL_OK) return fail("download");
+                        pool.submit([rgba, still_name, width, height] {
+                            if (ptl_png_write(still_name.c_str(), rgba->data(), width, height) != PTL_OK) std::fprintf(stderr, "\n%s\n", ptl_last_error());
+                        });
+                        continue;
+                    }
                     uint8_t* still = pinned.take();
                     if (ptl_device_download(still, (batched && which == 0) ? subframes[0] : target, frame_bytes, nullptr) != PTL_OK) return fail("download");
-                    std::string still_name = video_base + (which == 0 ? ".start.png" : ".end.png");
                     pool.submit([still, still_name, width, height, &pinned] {
                         if (ptl_png_write(still_name.c_str(), still, width, height) != PTL_OK) std::fprintf(stderr, "\n%s\n", ptl_last_error());
                         pinned.give(still);
@@ -607,7 +731,12 @@ int render_clip(const Options& o, ptl_scene* scene, ptl_renderer* r, const std::
             }
         }
         if (ptl_renderer_join(r, nullptr) != PTL_OK) return fail("join");  // the default stream goes on behind every sub-frame of this frame
-        if (o.blur > 1) {
+        if (y4m) {
+            float ms = 0.0f;
+            if (ptl_average_to_yuv420p10(o.device, subframes.data(), o.blur, pipe.results[slot], width, height, nullptr, o.timing ? &ms : nullptr) != PTL_OK)
+                return fail("average_to_yuv420p10");
+            gpu_ms += ms;
+        } else if (o.blur > 1) {
             float ms = 0.0f;
             if (ptl_average_images(o.device, subframes.data(), o.blur, pipe.results[slot], width, height, nullptr, o.timing ? &ms : nullptr) != PTL_OK)
                 return fail("average_images");
@@ -617,12 +746,20 @@ int render_clip(const Options& o, ptl_scene* scene, ptl_renderer* r, const std::
         uint8_t* pixels = pinned.take();  // blocks while every buffer is still being encoded
         void* arrived = nullptr;
         if (ptl_event_record(pipe.produced, nullptr) != PTL_OK || ptl_stream_wait_event(pipe.copy_stream, pipe.produced) != PTL_OK ||
-            ptl_device_download_async(pixels, pipe.results[slot], frame_bytes, pipe.copy_stream) != PTL_OK ||
+            ptl_device_download_async(pixels, pipe.results[slot], y4m ? yuv_bytes : frame_bytes, pipe.copy_stream) != PTL_OK ||
             ptl_event_record(pipe.copied[slot], pipe.copy_stream) != PTL_OK || ptl_event_create(pipe.device, &arrived) != PTL_OK ||
             ptl_event_record(arrived, pipe.copy_stream) != PTL_OK)
             return fail("download");
         pipe.copy_pending[slot] = true;
-        pool.submit([pixels, name, width, height, arrived, &pinned] {
+        if (y4m)  // frames of a stream arrive in order: one writer thread, jobs in submission order
+            y4m_writer->submit([pixels, arrived, yuv_bytes, y4m, &pinned] {
+                if (ptl_event_synchronize(arrived) != PTL_OK) y4m->fail(ptl_last_error());
+                y4m->write("FRAME\n", 6);
+                y4m->write(pixels, yuv_bytes);
+                ptl_event_destroy(arrived);
+                pinned.give(pixels);
+            });
+        else pool.submit([pixels, name, width, height, arrived, &pinned] {
             if (ptl_event_synchronize(arrived) != PTL_OK || ptl_png_write_level(name.c_str(), pixels, width, height, kFrameDeflateLevel) != PTL_OK)
                 std::fprintf(stderr, "\n%s\n", ptl_last_error());
             ptl_event_destroy(arrived);
@@ -677,6 +814,13 @@ void remove_tree(const std::string& path) {  // rm -rf of a directory we created
     ::rmdir(path.c_str());
 }
 
+// the reference's encoder settings (src/main.rs:1843-1857), from -c:v onwards: what follows the input, whichever form the input has
+std::vector<std::string> encoder_arguments(const std::string& video) {
+    return {"-c:v", "libx265", "-pix_fmt", "yuv420p10le", "-crf", "15", "-preset", "slow", "-x265-params",
+            "colorprim=bt709:transfer=iec61966-2-1:colormatrix=bt709:range=full", "-colorspace", "bt709", "-color_primaries", "bt709", "-color_trc",
+            "iec61966-2-1", "-color_range", "pc", "-movflags", "+write_colr+faststart", "-tag:v", "hvc1", "-y", video};
+}
+
 // the reference's ffmpeg hand-off (src/main.rs:1829-1869), same arguments; frames are kept when there is no ffmpeg
 int encode_video(const Options& o, const std::string& scene_name, const std::string& clip, int fps) {
     std::string anim = o.out_dir + "/anim", video = o.out_dir + "/video/" + scene_name + "/" + clip + ".mov";
@@ -691,14 +835,12 @@ int encode_video(const Options& o, const std::string& scene_name, const std::str
     }
     std::printf("Start ffmpeg to render video\n");
     auto started = std::chrono::steady_clock::now();
-    int status = run_program(
-        {"ffmpeg", "-framerate", std::to_string(fps), "-i", anim + "/frame_%d.png", "-vf",
-         "zscale=primariesin=bt709:transferin=iec61966-2-1:matrixin=bt709:rangein=full:primaries=bt709:transfer=iec61966-2-1:matrix=bt709:range=full,"
-         "format=yuv420p10le",
-         "-c:v", "libx265", "-pix_fmt", "yuv420p10le", "-crf", "15", "-preset", "slow", "-x265-params",
-         "colorprim=bt709:transfer=iec61966-2-1:colormatrix=bt709:range=full", "-colorspace", "bt709", "-color_primaries", "bt709", "-color_trc",
-         "iec61966-2-1", "-color_range", "pc", "-movflags", "+write_colr+faststart", "-tag:v", "hvc1", "-y", video},
-        true);
+    std::vector<std::string> command = {
+        "ffmpeg", "-framerate", std::to_string(fps), "-i", anim + "/frame_%d.png", "-vf",
+        "zscale=primariesin=bt709:transferin=iec61966-2-1:matrixin=bt709:rangein=full:primaries=bt709:transfer=iec61966-2-1:matrix=bt709:range=full,"
+        "format=yuv420p10le"};
+    for (const std::string& a : encoder_arguments(video)) command.push_back(a);
+    int status = run_program(command, true);
     std::printf("ffmpeg status: %d\nffmpeg time: %.2f s\n", status, std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count());
     remove_tree(anim);  // like the reference, whatever ffmpeg said (src/main.rs:1860)
     return 0;
@@ -730,6 +872,7 @@ void prefetch_clip_kernel(std::string path, std::vector<std::string> history, st
 }
 
 int render(const Options& o) {
+    if (o.y4m) ::signal(SIGPIPE, SIG_IGN);  // an encoder that dies is a failed write (EPIPE), reported by the clip
     int width = o.stereo ? o.width * 2 : o.width;  // src/main.rs:2822-2829
     auto total_start = std::chrono::steady_clock::now();
     for (const std::string& scene_arg : split_list(o.scene)) {
@@ -824,8 +967,10 @@ int render(const Options& o) {
         void* subframe_block = nullptr;
         if (ptl_device_alloc(o.device, bytes * subframes.size(), &subframe_block) != PTL_OK) return fail("alloc");
         for (size_t j = 0; j < subframes.size(); ++j) subframes[j] = static_cast<char*>(subframe_block) + j * bytes;
+        // what leaves the card per output frame: an RGBA8 frame, or (--frames y4m) the smaller planar 4:2:0 10-bit one
+        const size_t result_bytes = o.y4m ? ptl_yuv420p10_frame_bytes(width, o.height) : bytes;
         FramePipeline pipe;
-        if (!pipe.create(o.device, bytes)) return fail("pipeline");
+        if (!pipe.create(o.device, result_bytes)) return fail("pipeline");
 
         if (o.specialize != 0 && todo.size() > 1) {
             int n_workers = (int)std::min<size_t>({(size_t)6, todo.size() - 1, (size_t)std::max(1u, std::thread::hardware_concurrency() / 4)});
@@ -869,16 +1014,31 @@ int render(const Options& o) {
             {
                 auto clip_start = std::chrono::steady_clock::now();
                 // frames in flight between download and encode: one per encoder thread, but no more than ~2 GB of page-locked memory
-                int in_flight = (int)std::max<size_t>(4, std::min<size_t>((size_t)threads + 2, ((size_t)2 << 30) / bytes));
-                PinnedFrames pinned(bytes, in_flight);
+                int in_flight = (int)std::max<size_t>(4, std::min<size_t>((size_t)threads + 2, ((size_t)2 << 30) / result_bytes));
+                PinnedFrames pinned(result_bytes, in_flight);
                 if (!pinned.ok()) return fail("pinned host memory");
                 EncoderPool pool(threads, (size_t)threads * 2);
-                int rc = render_clip(o, scene, r, scene_name, clip, todo[k].second, fps, width, o.height, subframes, pipe, pool, pinned);
+                Y4mStream y4m;
+                EncoderPool y4m_writer(o.y4m ? 1 : 0, (size_t)in_flight);
+                int rc = render_clip(o, scene, r, scene_name, clip, todo[k].second, fps, width, o.height, subframes, pipe, pool, pinned, o.y4m ? &y4m : nullptr,
+                                     &y4m_writer);
+                y4m_writer.finish();  // the stream has every frame that was submitted
                 pool.finish();  // joins the encoders: every frame file is on disk (and every pinned buffer is back)
+                const bool to_program = y4m.to_program();
+                const int status = y4m.close();  // end of stream: an encoder finishes the video now
+                if (to_program) std::printf("ffmpeg status: %d\nffmpeg time: %.2f s\n", status, y4m.seconds());
+                if (rc == 0 && y4m.failed()) {
+                    std::fprintf(stderr, "%s\n", y4m.error().c_str());
+                    rc = 1;
+                }
+                if (rc == 0 && status != 0) {
+                    std::fprintf(stderr, "the encoder of clip `%s` failed (status %d)\n", clip.c_str(), status);
+                    rc = 1;
+                }
                 if (rc != 0) return rc;
                 std::printf("Clip `%s` on disk after %.2f s\n", clip.c_str(), std::chrono::duration<double>(std::chrono::steady_clock::now() - clip_start).count());
             }
-            if (o.shards == 1 && o.max_frames < 0) encode_video(o, scene_name, clip, fps);
+            if (!o.y4m && o.shards == 1 && o.max_frames < 0) encode_video(o, scene_name, clip, fps);
         }
         ptl_device_free(subframe_block);
         ptl_renderer_destroy(r);
@@ -1058,6 +1218,14 @@ int main(int argc, char** argv) {
         else if (a == "--max-frames") o.max_frames = std::atoi(next());
         else if (a == "--specialize") o.specialize = std::atoi(next());
         else if (a == "--timing") o.timing = true;
+        else if (a == "--frames") {
+            std::string form = next();
+            if (form != "png" && form != "y4m") {
+                std::fprintf(stderr, "--frames png|y4m\n");
+                return 2;
+            }
+            o.y4m = form == "y4m";
+        }
         else if (a == "--gpus") o.gpus = std::atoi(next());
         else if (a == "--devices") o.devices = next();
         else if (a == "--transport") o.transport = next();
@@ -1094,6 +1262,10 @@ int main(int argc, char** argv) {
     }
     if (o.blur < 1 || o.blur > 256) {
         std::fprintf(stderr, "--motion-blur-frames must be 1..256\n");
+        return 2;
+    }
+    if (o.y4m && o.shards > 1) {
+        std::fprintf(stderr, "--frames y4m cannot be combined with --shard K/N, N > 1: a stream needs every frame, in order\n");
         return 2;
     }
     if (cmd == "render") return render(o);

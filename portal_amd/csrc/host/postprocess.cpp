@@ -78,18 +78,29 @@ int load_kernel(int device, const char* file, const char* entry, LoadedKernel** 
     return PTL_OK;
 }
 
-}  // namespace
+// What ptl_average_images and ptl_average_to_yuv420p10 share: a kernel over N sub-frames with two entries (up to 64 pointers in the
+// kernel arguments, beyond in a device table), launched as `lanes` lanes in workgroups of 256 (grid-stride beyond the cap) on `stream`.
+// The kernel's arguments are (frames, n, tail...).
+struct SubframeKernel {
+    const char* file;
+    const char* entry_list;
+    const char* entry_table;
+    const char* what;
+};
 
-extern "C" int ptl_average_images(int device, const void* const* frames_rgba8, int n_frames, void* out_rgba8, int width, int height,
-                                  void* stream, float* elapsed_ms) {
-    if (!frames_rgba8 || !out_rgba8 || n_frames < 1 || n_frames > kMaxSubframesTable || width <= 0 || height <= 0) return PTL_ERR_INVALID;
+int check_subframes(const void* const* frames_rgba8, int n_frames, const void* out, int width, int height) {
+    if (!frames_rgba8 || !out || n_frames < 1 || n_frames > kMaxSubframesTable || width <= 0 || height <= 0) return PTL_ERR_INVALID;
     for (int k = 0; k < n_frames; ++k)
         if (!frames_rgba8[k] || (reinterpret_cast<uintptr_t>(frames_rgba8[k]) & 15u)) return PTL_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(out_rgba8) & 15u) return PTL_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(out) & 15u) return PTL_ERR_INVALID;
+    return PTL_OK;
+}
+
+int launch_over_subframes(int device, const SubframeKernel& kernel, const void* const* frames_rgba8, int n_frames, std::vector<void*> tail, long lanes,
+                          void* stream, float* elapsed_ms) {
     LoadedKernel* k = nullptr;
-    const char* variant = std::getenv("PTL_AVERAGE_IMAGES_HSACO");  // tuning only: another build of the same kernel (tools/average_variants.py)
     const bool table = n_frames > kMaxSubframes;
-    int rc = load_kernel(device, variant && *variant ? variant : "average_images.hsaco", table ? "ptl_average_images_table_kernel" : "ptl_average_images_kernel", &k);
+    int rc = load_kernel(device, kernel.file, table ? kernel.entry_table : kernel.entry_list, &k);
     if (rc != PTL_OK) return rc;
     const hip::Runtime* rt = hip::runtime(nullptr);
     rt->hipSetDevice(device);
@@ -97,29 +108,27 @@ extern "C" int ptl_average_images(int device, const void* const* frames_rgba8, i
         const void* frame[kMaxSubframes];
     } list{};
     for (int i = 0; i < n_frames && !table; ++i) list.frame[i] = frames_rgba8[i];
-    long n_px = (long)width * height, n_vec = n_px / 4;
     int n = n_frames;
     void* dev_table = nullptr;
     if (table) {  // rare (the reference's clips use <= 16): a pointer table per call, freed once the launch has gone through the stream
         if (rt->hipMalloc(&dev_table, sizeof(void*) * (size_t)n_frames) != 0 ||
             rt->hipMemcpyAsync(dev_table, frames_rgba8, sizeof(void*) * (size_t)n_frames, hip::kMemcpyHostToDevice, stream) != 0) {
             if (dev_table) rt->hipFree(dev_table);
-            set_last_error("average_images: cannot stage the sub-frame pointer table");
+            set_last_error(std::string(kernel.what) + ": cannot stage the sub-frame pointer table");
             return PTL_ERR_HIP;
         }
     }
-    void* args_list[] = {&list, &n, &out_rgba8, &n_px};
-    void* args_table[] = {&dev_table, &n, &out_rgba8, &n_px};
-    void** args = table ? args_table : args_list;
-    long blocks = std::max(1L, (n_vec + 255) / 256);
+    std::vector<void*> args = {table ? static_cast<void*>(&dev_table) : static_cast<void*>(&list), &n};
+    args.insert(args.end(), tail.begin(), tail.end());
+    long blocks = std::max(1L, (lanes + 255) / 256);
     long cap = 256 * 16;  // grid-stride beyond 16 workgroups per CU
     if (const char* c = std::getenv("PTL_AVERAGE_IMAGES_GRID_CAP")) cap = std::atol(c) > 0 ? std::atol(c) : cap;
     if (blocks > cap) blocks = cap;
     if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
-    int err = rt->hipModuleLaunchKernel(k->fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream, args, nullptr);
+    int err = rt->hipModuleLaunchKernel(k->fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream, args.data(), nullptr);
     if (err != 0) {
         if (dev_table) rt->hipFree(dev_table);
-        set_last_error(std::string("hipModuleLaunchKernel(average_images): ") + rt->hipGetErrorString(err));
+        set_last_error(std::string("hipModuleLaunchKernel(") + kernel.what + "): " + rt->hipGetErrorString(err));
         return PTL_ERR_HIP;
     }
     if (elapsed_ms) {
@@ -132,6 +141,41 @@ extern "C" int ptl_average_images(int device, const void* const* frames_rgba8, i
         rt->hipFree(dev_table);
     }
     return PTL_OK;
+}
+
+}  // namespace
+
+extern "C" int ptl_average_images(int device, const void* const* frames_rgba8, int n_frames, void* out_rgba8, int width, int height,
+                                  void* stream, float* elapsed_ms) {
+    if (int rc = check_subframes(frames_rgba8, n_frames, out_rgba8, width, height)) return rc;
+    const char* variant = std::getenv("PTL_AVERAGE_IMAGES_HSACO");  // tuning only: another build of the same kernel (tools/average_variants.py)
+    const SubframeKernel kernel{variant && *variant ? variant : "average_images.hsaco", "ptl_average_images_kernel", "ptl_average_images_table_kernel", "average_images"};
+    long n_px = (long)width * height;
+    return launch_over_subframes(device, kernel, frames_rgba8, n_frames, {&out_rgba8, &n_px}, n_px / 4, stream, elapsed_ms);  // a lane per 16-byte vector
+}
+
+// ptl_average_to_yuv420p10: the same averaging fused with the conversion to planar Y'CbCr 4:2:0 10 bit (portal_amd/csrc/kernels/yuv420p10.hip,
+// the contract is in include/portal_amd.h).  A lane owns an 8x2 block where the frame allows it (W % 16 == 0, H even), else one chroma sample.
+extern "C" size_t ptl_yuv420p10_frame_bytes(int width, int height) {
+    if (width <= 0 || height <= 0) return 0;
+    const size_t cw = ((size_t)width + 1) / 2, ch = ((size_t)height + 1) / 2;
+    return 2 * ((size_t)width * (size_t)height + 2 * cw * ch);
+}
+
+extern "C" int ptl_average_to_yuv420p10(int device, const void* const* frames_rgba8, int n_frames, void* out_yuv, int width, int height, void* stream,
+                                        float* elapsed_ms) {
+    if (int rc = check_subframes(frames_rgba8, n_frames, out_yuv, width, height)) return rc;
+    if ((long)width * height > (1L << 29)) return PTL_ERR_INVALID;  // the kernel addresses a sub-frame with 32-bit byte offsets
+    const SubframeKernel kernel{"yuv420p10.hsaco", "ptl_average_to_yuv420p10_kernel", "ptl_average_to_yuv420p10_table_kernel", "average_to_yuv420p10"};
+    const bool blocks_8x2 = width % 16 == 0 && height % 2 == 0;  // the kernel takes the same decision
+    long lanes = blocks_8x2 ? (long)(width / 8) * (height / 2) : (long)((width + 1) / 2) * ((height + 1) / 2);
+    return launch_over_subframes(device, kernel, frames_rgba8, n_frames, {&out_yuv, &width, &height}, lanes, stream, elapsed_ms);
+}
+
+extern "C" int ptl_y4m_header(int width, int height, int fps, char* buf, size_t cap) {
+    if (width <= 0 || height <= 0 || fps <= 0 || !buf) return PTL_ERR_INVALID;
+    int len = std::snprintf(buf, cap, "YUV4MPEG2 W%d H%d F%d:1 Ip A1:1 C420p10 XYSCSS=420P10 XCOLORRANGE=FULL\n", width, height, fps);
+    return len > 0 && (size_t)len < cap ? len : PTL_ERR_INVALID;  // (the terminating NUL has to fit as well)
 }
 
 // Device frame buffers for callers that keep frames on the GPU between kernels (the video pipeline: sub-frames ->

@@ -1,0 +1,378 @@
+"""`render --frames y4m`: the fused average-and-convert kernel (portal_amd/csrc/kernels/yuv420p10.hip), its C ABI and the Y4M stream
+of the CLI, against tests/yuv_reference.py (a numpy restatement of the contract in DESIGN.md 2.3).  Every comparison is byte equality."""
+import os
+import re
+import stat
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import yuv_reference as yr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+SIZES = [(1, 1), (2, 2), (3, 1), (5, 7), (13, 11), (16, 2), (64, 36), (1023, 3), (1920, 1080), (3840, 2160)]
+
+
+# ---------------------------------------------------------------------------------------------
+# CPU
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("w,h,fps", [(64, 36, 2), (3840, 2160, 60), (7680, 2160, 600), (1, 1, 1), (1023, 3, 24)])
+def test_y4m_header_text(pa, w, h, fps):
+    import ctypes as C
+
+    want = f"YUV4MPEG2 W{w} H{h} F{fps}:1 Ip A1:1 C420p10 XYSCSS=420P10 XCOLORRANGE=FULL\n".encode()
+    assert pa.y4m_header(w, h, fps) == want == yr.y4m_header(w, h, fps)
+    buf = C.create_string_buffer(len(want) + 1)  # the text and its NUL fit exactly
+    assert pa.lib().ptl_y4m_header(w, h, fps, buf, len(buf)) == len(want) and buf.value == want
+    for cap in (0, 1, 16, len(want)):
+        short = C.create_string_buffer(max(cap, 1))
+        assert pa.lib().ptl_y4m_header(w, h, fps, short, cap) == -1  # PTL_ERR_INVALID
+    assert pa.lib().ptl_y4m_header(w, h, 0, buf, len(buf)) == -1 and pa.lib().ptl_y4m_header(0, h, fps, buf, len(buf)) == -1
+
+
+def test_frame_bytes_is_the_formula(pa):
+    for w, h in SIZES + [(7680, 4320), (7, 7), (1, 2), (2, 1)]:
+        cw, ch = (w + 1) // 2, (h + 1) // 2
+        assert pa.yuv420p10_frame_bytes(w, h) == 2 * (w * h + 2 * cw * ch) == yr.frame_bytes(w, h), (w, h)
+        if w * h < 1 << 16:
+            assert len(yr.yuv_reference(np.zeros((h, w, 4), np.uint8))) == yr.frame_bytes(w, h)
+    assert pa.yuv420p10_frame_bytes(3840, 2160) == 3 * 3840 * 2160  # 3 bytes per pixel where both sizes are even
+    assert pa.yuv420p10_frame_bytes(0, 4) == 0 and pa.yuv420p10_frame_bytes(4, -1) == 0
+
+
+def test_entry_points_refuse_what_average_images_refuses(pa):
+    """Validation comes before any GPU call: no frames, bad counts, bad sizes, unaligned pointers -> PTL_ERR_INVALID."""
+    import ctypes as C
+
+    L = pa.lib()
+    ptrs = (C.c_void_p * 2)(4096, 8192)
+    out = C.c_void_p(1 << 20)
+    assert L.ptl_average_to_yuv420p10(0, None, 2, out, 4, 4, None, None) == -1
+    assert L.ptl_average_to_yuv420p10(0, ptrs, 2, None, 4, 4, None, None) == -1
+    assert L.ptl_average_to_yuv420p10(0, ptrs, 0, out, 4, 4, None, None) == -1
+    assert L.ptl_average_to_yuv420p10(0, ptrs, 2, out, 0, 4, None, None) == -1
+    assert L.ptl_average_to_yuv420p10(0, ptrs, 2, out, 4, -2, None, None) == -1
+    assert L.ptl_average_to_yuv420p10(0, ptrs, 2, C.c_void_p((1 << 20) + 8), 4, 4, None, None) == -1
+    assert L.ptl_average_to_yuv420p10(0, (C.c_void_p * 2)(4096, 8196), 2, out, 4, 4, None, None) == -1
+    many = (C.c_void_p * 257)(*([4096] * 257))
+    assert L.ptl_average_to_yuv420p10(0, many, 257, out, 4, 4, None, None) == -1
+    assert L.ptl_average_to_yuv420p10(0, ptrs, 2, out, 1 << 15, (1 << 14) + 1, None, None) == -1  # beyond 2^29 pixels
+
+
+def test_make_kernels_builds_the_code_object_without_scratch(pa, tmp_path):
+    """`make kernels` leaves portal_amd/kernels/yuv420p10.hsaco; both entries compile for gfx950 with 0 bytes of scratch and no LDS,
+    and average_images.hip still gets its device functions from the header the two kernels share."""
+    subprocess.run(["make", "kernels"], cwd=ROOT, check=True, capture_output=True)
+    assert os.path.getsize(os.path.join(ROOT, "portal_amd", "kernels", "yuv420p10.hsaco")) > 1000
+    src = os.path.join(ROOT, "portal_amd", "csrc", "kernels", "yuv420p10.hip")
+    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-vgpr-regalloc=basic", "--genco", "--no-gpu-bundle-output",
+                          "-Rpass-analysis=kernel-resource-usage", src, "-o", str(tmp_path / "yuv420p10.hsaco")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr
+    usage = {}
+    name = None
+    for line in out.stderr.splitlines():
+        m = re.search(r"Function Name: (\w+)", line)
+        if m:
+            name = m.group(1)
+        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|VGPRs): (\d+)", line)
+        if m and name:
+            usage.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    print(usage)
+    assert set(usage) == {"ptl_average_to_yuv420p10_kernel", "ptl_average_to_yuv420p10_table_kernel"}
+    for entry, u in usage.items():
+        assert u["ScratchSize [bytes/lane]"] == 0 and u["LDS Size [bytes/block]"] == 0, (entry, u)
+        assert u["VGPRs"] <= 128, (entry, u)  # four waves per SIMD
+    for kernel in ("average_images.hip", "yuv420p10.hip"):
+        assert '#include "average_common.h"' in open(os.path.join(ROOT, "portal_amd", "csrc", "kernels", kernel)).read()
+
+
+@pytest.mark.parametrize("extra,reason", [(["--frames", "y4m", "--shard", "0/2"], "a stream needs every frame, in order"),
+                                          (["--shard", "1/3", "--frames", "y4m"], "a stream needs every frame, in order"),
+                                          (["--frames", "bogus"], "--frames png|y4m")])
+def test_render_refuses_what_a_stream_cannot_do(pa, tmp_path, extra, reason):
+    """Refused while the arguments are parsed: exit status 2, one line of reason, nothing rendered (this machine has no GPU to ask)."""
+    exe = os.path.join(os.path.dirname(pa.__file__), "portal-amd")
+    clip = pa.Scene.from_file(pa.scene_path("basics")).animations()[0][0]
+    out = subprocess.run([exe, "render", pa.scene_path("basics"), clip, "--out-dir", str(tmp_path)] + extra, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2, out.stderr + out.stdout
+    assert reason in out.stderr and len(out.stderr.strip().splitlines()) == 1
+    assert not os.listdir(tmp_path)
+
+
+def test_reference_helper_against_the_real_valued_definition():
+    """Pins the fixture, not the product: on flat colours (all 256 greys, the eight cube corners, 10^5 seeded colours) the integer
+    contract stays within 0.51 codes of H.273 in real numbers (measured: 0.502), greys are exact and have neutral chroma."""
+    rng = np.random.default_rng(709)
+    greys = np.repeat(np.arange(256)[:, None], 3, axis=1)
+    corners = np.array([[r, g, b] for r in (0, 255) for g in (0, 255) for b in (0, 255)])
+    colours = np.concatenate([greys, corners, rng.integers(0, 256, (100000, 3))]).astype(np.uint8)
+    # colour k fills rows 2k, 2k+1 of a two-pixel-wide frame: each chroma sample then sees one flat colour (its columns clamp to the frame)
+    frame = np.repeat(np.repeat(colours[:, None, :], 2, axis=0), 2, axis=1)
+    y, cb, cr = yr.yuv_planes(frame)
+    assert y.min() >= 0 and y.max() <= 1023 and cb.min() >= 0 and cb.max() <= 1023 and cr.min() >= 0 and cr.max() <= 1023
+    ry, rcb, rcr = yr.real_valued(colours)
+    worst = {}
+    for name, got, real in (("Y", y[::2, 0], ry), ("Y'", y[1::2, 1], ry), ("Cb", cb[:, 0], rcb), ("Cr", cr[:, 0], rcr)):
+        worst[name] = float(np.abs(got - real).max())
+    print(worst)
+    assert max(worst.values()) <= 0.51, worst
+    assert np.array_equal(y[0:512:2, 0], np.round(1023 * np.arange(256) / 255).astype(np.int32))
+    assert (cb[:256] == 512).all() and (cr[:256] == 512).all()
+    # siting: a frame that is black left of column 2 and white from it: sample 1 sits ON column 2 (weights 1-2-1 over columns 1, 2, 3)
+    step = np.zeros((2, 6, 3), np.uint8)
+    step[:, 2:, 2] = 255  # blue only, so Cb moves
+    _, cb, _ = yr.yuv_planes(step)
+    s = np.array([0, 3 * 2 * 255, 4 * 2 * 255])  # S_B of the three samples: columns (0,0,1), (1,2,3), (3,4,5)
+    assert np.array_equal(cb[0], np.minimum(1023, (131458 * s + (512 << 19) + (1 << 18)) >> 19))
+
+
+# ---------------------------------------------------------------------------------------------
+# GPU
+# ---------------------------------------------------------------------------------------------
+GUARD = 0xA5
+
+
+@pytest.fixture(scope="module")
+def gpu(pa):
+    if pa.device_count() < 1:
+        pytest.fail("no HIP device visible: the render path has no CPU fallback")
+    return pa
+
+
+def _convert(pa, frames, w, h, offset=0):
+    """Sub-frames (numpy or cuda tensors) -> payload bytes; the 64 guard bytes behind the frame (and `offset` before it) must survive."""
+    import torch
+
+    dev = [f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)).cuda() for f in frames]
+    nbytes = pa.yuv420p10_frame_bytes(w, h)
+    buf = torch.full((offset + nbytes + 64,), GUARD, dtype=torch.uint8, device="cuda")
+    assert buf.data_ptr() % 256 == 0
+    pa.average_to_yuv420p10_device([d.data_ptr() for d in dev], buf.data_ptr() + offset, w, h, stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    host = buf.cpu().numpy()
+    assert (host[:offset] == GUARD).all() and (host[offset + nbytes:] == GUARD).all(), "written outside the frame"
+    return host[offset: offset + nbytes].tobytes()
+
+
+def _assert_same_payload(got: bytes, want: bytes, w, h, what):
+    if got == want:
+        return
+    assert len(got) == len(want), (what, len(got), len(want))
+    for name, g, r in zip(("Y", "Cb", "Cr"), yr.split_planes(got, w, h), yr.split_planes(want, w, h)):
+        bad = np.argwhere(g != r)
+        if len(bad):
+            y, x = bad[0]
+            pytest.fail(f"{what}: plane {name} differs in {len(bad)} of {g.size} samples, first at x={x} y={y}: got {g[y, x]}, want {r[y, x]}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 7, 16, 64, 65, 256])
+def test_kernel_matches_reference_for_every_subframe_count(gpu, n):
+    """244x135 (general path): the frame == yuv_reference(average_images(sub-frames)); n = 1 converts the input's own RGB; beyond 64
+    sub-frames the pointer-table entry."""
+    from oracle import postprocess as pp
+
+    w, h = 244, 135
+    rng = np.random.default_rng(1000 + n)
+    frames = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(n)]
+    frames[0][:4] = 255
+    frames[-1][-4:] = 0
+    want = yr.yuv_reference(pp.average_images(frames) if n > 1 else frames[0])
+    _assert_same_payload(_convert(gpu, frames, w, h), want, w, h, f"n={n}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 7, 16, 64, 65, 256])
+def test_block_path_matches_reference_for_every_subframe_count(gpu, n):
+    """The same at 256x134 (W % 16 == 0, H even: a lane owns an 8x2 block; 32 blocks per row, so waves span two row pairs)."""
+    from oracle import postprocess as pp
+
+    w, h = 256, 134
+    rng = np.random.default_rng(2000 + n)
+    frames = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(n)]
+    want = yr.yuv_reference(pp.average_images(frames) if n > 1 else frames[0])
+    _assert_same_payload(_convert(gpu, frames, w, h), want, w, h, f"n={n}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", SIZES)
+def test_kernel_matches_reference_at_any_frame_size(gpu, w, h):
+    """Odd sizes, one-pixel frames, video sizes, three sub-frames: byte-exact, and nothing written behind frame_bytes."""
+    from oracle import postprocess as pp
+
+    rng = np.random.default_rng(w * 100 + h)
+    frames = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(3)]
+    _assert_same_payload(_convert(gpu, frames, w, h), yr.yuv_reference(pp.average_images(frames)), w, h, f"{w}x{h}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", [(13, 11), (5, 7), (1, 1)])
+def test_chroma_planes_need_no_alignment(gpu, w, h):
+    """The frame starts 16-byte aligned (as the entry point demands) but W*H is odd: Cb starts at byte 2*W*H, 2-byte aligned only."""
+    from oracle import postprocess as pp
+
+    assert (w * h) % 2 == 1
+    rng = np.random.default_rng(77 + w)
+    frames = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(3)]
+    _assert_same_payload(_convert(gpu, frames, w, h, offset=16), yr.yuv_reference(pp.average_images(frames)), w, h, f"{w}x{h} at +16")
+
+
+@pytest.mark.gpu
+def test_every_colour_once(gpu):
+    """4096x4096 holding all 2^24 RGB triples (alpha 0: ignored), n = 1: all three planes equal the reference."""
+    w = h = 4096
+    frame = np.arange(1 << 24, dtype="<u4").view(np.uint8).reshape(h, w, 4)
+    assert frame[0, 1].tolist() == [1, 0, 0, 0] and frame[-1, -1].tolist() == [255, 255, 255, 0]
+    got = _convert(gpu, [frame], w, h)
+    _assert_same_payload(got, yr.yuv_reference(frame), w, h, "every colour")
+    y, cb, cr = yr.split_planes(got, w, h)
+    assert y.min() == 0 and y.max() == 1023 and cb.max() <= 1023 and cr.max() <= 1023
+
+
+@pytest.mark.gpu
+def test_full_size_properties(gpu):
+    """4K, 4 sub-frames: permuting the inputs changes no byte; four copies of one frame equal n = 1 of that frame, which equals the reference."""
+    import torch
+
+    w, h = 3840, 2160
+    g = torch.Generator(device="cuda").manual_seed(5)
+    frames = [torch.randint(0, 256, (h, w, 4), dtype=torch.uint8, device="cuda", generator=g) for _ in range(4)]
+    forward = _convert(gpu, frames, w, h)
+    assert forward == _convert(gpu, list(reversed(frames)), w, h)
+    one = _convert(gpu, [frames[0]], w, h)
+    assert one == _convert(gpu, [frames[0]] * 4, w, h)
+    _assert_same_payload(one, yr.yuv_reference(frames[0].cpu().numpy()), w, h, "4K n=1")
+    assert forward != one
+
+
+@pytest.mark.gpu
+def test_elapsed_ms_and_a_stream_of_the_callers(gpu):
+    """Like ptl_average_images: launched on the stream it is given (here a non-default torch stream, with the inputs produced on it),
+    and with elapsed_ms the launch is bracketed by events and waited for."""
+    import torch
+    from oracle import postprocess as pp
+
+    pa = gpu
+    w, h = 640, 360
+    nbytes = pa.yuv420p10_frame_bytes(w, h)
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        g = torch.Generator(device="cuda").manual_seed(11)
+        frames = [torch.randint(0, 256, (h, w, 4), dtype=torch.uint8, device="cuda", generator=g) for _ in range(4)]
+        out = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        ms = pa.average_to_yuv420p10_device([f.data_ptr() for f in frames], out.data_ptr(), w, h, stream=side.cuda_stream, timed=True)
+        assert ms is not None and 0.0 < ms < 1000.0
+        got = out.cpu().numpy().tobytes()  # the timed call has waited; the copy is ordered behind it on the same stream anyway
+        out.zero_()
+        assert pa.average_to_yuv420p10_device([f.data_ptr() for f in frames], out.data_ptr(), w, h, stream=side.cuda_stream) is None
+        side.synchronize()
+        assert out.cpu().numpy().tobytes() == got
+    want = yr.yuv_reference(pp.average_images([f.cpu().numpy() for f in frames]))
+    _assert_same_payload(got, want, w, h, "side stream")
+
+
+# ---- the CLI ---------------------------------------------------------------------------------
+W, H, FPS = 64, 36, 2
+
+
+def _path_without_ffmpeg():
+    return os.pathsep.join(d for d in os.environ.get("PATH", "").split(os.pathsep) if d and not os.path.exists(os.path.join(d, "ffmpeg")))
+
+
+def _render(pa, out_dir, blur, path, timeout=600):
+    exe = os.path.join(os.path.dirname(pa.__file__), "portal-amd")
+    scene = pa.scene_path("basics")
+    clip = pa.Scene.from_file(scene).animations()[0][0]
+    env = dict(os.environ, PATH=path)
+    return subprocess.run([exe, "render", scene, clip, "--width", str(W), "--height", str(H), "--fps", str(FPS), "--motion-blur-frames", str(blur), "--aa-count", "2",
+                           "--render-depth", "12", "--frames", "y4m", "--out-dir", str(out_dir), "--asset-root", os.path.dirname(os.path.dirname(scene))],
+                          capture_output=True, text=True, timeout=timeout, env=env)
+
+
+def _expected_stream(pa, blur):
+    """The clip drawn through the Python mirror, as test_render_cli_writes_the_frames_the_library_draws does: (stream bytes, first and last sub-frame, count)."""
+    from oracle import postprocess as pp
+
+    clip, duration = pa.Scene.from_file(pa.scene_path("basics")).animations()[0]
+    count = max(1, int(np.float32(duration) * np.float32(FPS)))
+    scene = pa.Scene.from_file(pa.scene_path("basics"))
+    r = pa.SceneRenderer(scene, device=0)
+    r.set_option("aa_count", 2)
+    r.set_option("render_depth", 12)
+    scene.init_animation(clip)
+    r.update(0.0)
+    stream, first, last = yr.y4m_header(W, H, FPS), None, None
+    for i in range(count):
+        subs = []
+        for j in range(blur):
+            r.set_option("aa_start", j)
+            r.update((i / count + j / blur / count * 0.5) * float(np.float32(duration)))
+            subs.append(r.draw(W, H)["rgba8"])
+        first = subs[0] if first is None else first
+        last = subs[-1]
+        stream += b"FRAME\n" + yr.yuv_reference(pp.average_images(subs))
+    return stream, first, last, count, clip
+
+
+def _check_stream(got: bytes, want: bytes, count):
+    header = yr.y4m_header(W, H, FPS)
+    size = 6 + yr.frame_bytes(W, H)
+    assert got[: len(header)] == header
+    assert len(got) == len(header) + count * size, "not exactly `count` frames"
+    for i in range(count):
+        a = len(header) + i * size
+        assert got[a: a + 6] == b"FRAME\n", i
+        _assert_same_payload(got[a + 6: a + size], want[a + 6: a + size], W, H, f"frame {i}")
+    assert got == want
+
+
+def _write_stub(directory, body):
+    os.makedirs(directory, exist_ok=True)
+    stub = os.path.join(directory, "ffmpeg")
+    with open(stub, "w") as f:
+        f.write("#!/bin/sh\n" + body)
+    os.chmod(stub, os.stat(stub).st_mode | stat.S_IXUSR | stat.S_IXGRP | stat.S_IXOTH)
+    return stub
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("blur", [3, 1])
+def test_render_cli_streams_the_frames_the_library_draws(gpu, tmp_path, blur):
+    """`portal-amd render --frames y4m` end to end, with motion blur (a, b) and with --motion-blur-frames 1 (c): without an ffmpeg the
+    stream is <clip>.y4m; with one it goes through the encoder's stdin -- here a stub that copies stdin to its last argument, so the
+    .mov holds the stream byte for byte.  Header, frame count, every payload, the PNG stills; no anim/ directory."""
+    pa = gpu
+    want, first, last, count, clip = _expected_stream(pa, blur)
+    video = tmp_path / "file" / "video" / "basics"
+    out = _render(pa, tmp_path / "file", blur, _path_without_ffmpeg())
+    assert out.returncode == 0, out.stderr + out.stdout
+    _check_stream((video / f"{clip}.y4m").read_bytes(), want, count)
+    assert "ffmpeg -f yuv4mpegpipe -i" in out.stdout  # the message names the command that would encode the file
+    assert np.array_equal(pa.png_read(str(video / f"{clip}.start.png")), first)
+    assert np.array_equal(pa.png_read(str(video / f"{clip}.end.png")), last)
+    assert not (tmp_path / "file" / "anim").exists() and not (video / f"{clip}.frames").exists() and not (video / f"{clip}.mov").exists()
+
+    args_file = tmp_path / "stub_args.txt"
+    _write_stub(tmp_path / "bin", f'if [ "$1" = "-version" ]; then exit 0; fi\nprintf \'%s\\n\' "$@" > "{args_file}"\nfor last; do :; done\nexec cat > "$last"\n')
+    out = _render(pa, tmp_path / "pipe", blur, str(tmp_path / "bin") + os.pathsep + os.environ.get("PATH", ""))
+    assert out.returncode == 0, out.stderr + out.stdout
+    video = tmp_path / "pipe" / "video" / "basics"
+    _check_stream((video / f"{clip}.mov").read_bytes(), want, count)
+    args = args_file.read_text().splitlines()
+    assert args[:4] == ["-f", "yuv4mpegpipe", "-i", "-"] and args[4:6] == ["-c:v", "libx265"] and args[-1] == str(video / f"{clip}.mov")
+    assert not any("zscale" in a or a in ("-framerate", "-vf") or "frame_%d" in a for a in args)
+    assert "ffmpeg status: 0" in out.stdout
+    assert np.array_equal(pa.png_read(str(video / f"{clip}.start.png")), first)
+    assert np.array_equal(pa.png_read(str(video / f"{clip}.end.png")), last)
+    assert not (tmp_path / "pipe" / "anim").exists() and not (video / f"{clip}.y4m").exists()
+
+
+@pytest.mark.gpu
+def test_render_cli_fails_when_the_encoder_dies(gpu, tmp_path):
+    """(d) An encoder that exits at once: the CLI reports it and returns non-zero, within the timeout, instead of blocking on the pipe."""
+    _write_stub(tmp_path / "bin", 'if [ "$1" = "-version" ]; then exit 0; fi\nexit 1\n')
+    out = _render(gpu, tmp_path / "dead", 3, str(tmp_path / "bin") + os.pathsep + os.environ.get("PATH", ""), timeout=300)
+    assert out.returncode not in (0, 2), out.stderr + out.stdout
+    assert "encoder" in out.stderr
