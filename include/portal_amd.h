@@ -257,6 +257,7 @@ int ptl_scene_texture(ptl_scene* s, int index, char* name, size_t name_cap, char
 #define PTL_FLAG_CHECK_AFFINE (1u << 25)
 #define PTL_FLAG_MATERIAL_TABLE_LDS (1u << 26)
 #define PTL_FLAG_MATERIAL_TABLE_SCALAR (1u << 27)
+#define PTL_FLAG_REFINE (1u << 28)
 
 /* Scene::generate_shader_code: returns a malloc'ed NUL-terminated HIP C++ source (free with
  * ptl_free).  flags: bit0 = bake Bool/Int scene uniforms as literals, bit1 = count segments,
@@ -346,6 +347,8 @@ int ptl_scene_texture(ptl_scene* s, int index, char* name, size_t name_cap, char
  * they dodge `transform(uniform matrix, ray)`, which is a handful of additions there and cheaper than the bookkeeping around it (headline baked
  * 0.2305 -> 0.2046 ms, Int-baked 0.272 -> 0.239, patterns 0.274 -> 0.239; identical frames); this bit keeps them.  Kernels without affine rays (the
  * un-specialised one above all: 0.70 against 0.89 ms) keep the deferral anyway,
+ * bit28 = REFINE: the module gets a second render entry, `ptl_render_refine_kernel`, which shades a device-side list of pixels instead of a
+ * rectangle (ptl_kernel_render_refine, ptl_renderer_draw_adaptive below).  A source generated without it is byte for byte what it was.  Not with bit22,
  * bit15 = NO unrolling of baked loops: by default (with bit0) a counting loop of a scene snippet whose bound is a baked Int uniform
  * (<= 16 iterations) is unrolled -- the same operations in the same order, identical frames; every iteration then has its own
  * constants (scenes/portal_in_portal.ron's `size` drives an inner loop and a material index).
@@ -390,7 +393,7 @@ int ptl_renderer_create_with_options(ptl_scene* s, int device, const char* asset
  * "aa_start", "view_angle", "use_panini_projection", "panini_param", "use_360_camera",
  * "use_180_camera", "darken_by_distance", "gray_t_start", "gray_t_size", "draw_depth_map",
  * "depth_map_min", "depth_map_max", "angle_color_disable", "grid_disable",
- * "black_border_disable", "offset_after_material", "draw_side_by_side". */
+ * "black_border_disable", "offset_after_material", "draw_side_by_side"; "adaptive_aa_threshold" (ptl_renderer_draw_adaptive). */
 /* The translation unit the renderer's current kernel was compiled from (malloc'ed, free with ptl_free): ptl_scene_generate_source's text
  * with the renderer's own mode switches compiled in where it is a specialised build -- what tools/isa_hist.py attributes instructions to. */
 int ptl_renderer_kernel_source(ptl_renderer* r, char** source);
@@ -530,6 +533,48 @@ int ptl_average_images(int device, const void* const* frames_rgba8, int n_frames
 int ptl_average_to_yuv420p10(int device, const void* const* frames_rgba8, int n_frames, void* out_yuv, int width, int height, void* stream,
                              float* elapsed_ms);
 size_t ptl_yuv420p10_frame_bytes(int width, int height);
+/* ---- adaptive anti-aliasing: supersample only the pixels that sit on an edge (opt-in, approximate by design) ------------------------
+ * Every anti-aliasing sample costs a full trace, and most pixels of a frame are flat walls and smooth gradients whose centre sample is
+ * already the final 8-bit colour.  An adaptive draw traces ONE sample per pixel, classifies the frame it got, and traces the full
+ * `aa_count` only where a pixel differs from a neighbour.  Contract, integers only (tests/adaptive_reference.py restates it in numpy):
+ *   P = the RGBA8 frame ptl_renderer_draw writes for the current state with `_aa_count` = 1,
+ *   F = the frame it writes with `_aa_count` = N, the renderer's "aa_count" option (`_aa_start` and everything else unchanged),
+ *   T = an integer in -1 .. 255, the renderer option "adaptive_aa_threshold" (default 4),
+ *   d(x, y)      = max over dx, dy in {-1, 0, 1}, c in {R, G, B} of | P(clamp(x+dx), clamp(y+dy)).c - P(x, y).c |
+ *   refine(x, y) = d(x, y) > T
+ *   out(x, y)    = refine(x, y) ? F(x, y) : P(x, y)
+ * Coordinates clamp to the frame; alpha is ignored; `out` covers the RGBA8 bytes and, where asked for, the RGBA32F bits (byte for byte
+ * those of F and P: a pixel's value does not depend on which lanes share its wave).  T = -1 refines everything (out == F), T = 255
+ * nothing (out == P); with N = 1 the call is a plain draw and the list is empty.  What the method cannot see: a feature thinner than a
+ * pixel that the centre samples of a whole 3x3 neighbourhood miss stays at its one-sample colour (DESIGN.md 2.6 has the measured counts).
+ *
+ * ptl_aa_edges: the classification alone.  frame_rgba8 = W*H RGBA8 pixels, list = room for W*H uint32, count = one uint32 -- all DEVICE
+ * pointers, 4-byte aligned.  Writes the indices y*W + x of the refined pixels as a dense list and their number; the count is reset on
+ * `stream` by the call itself.  The order of the list is free, but entries produced together are spatial neighbours (a 64x32 region per
+ * workgroup, 8x8 tile after 8x8 tile), so 64 consecutive entries still make a compact bundle of rays.  W*H <= 2^31.
+ * ptl_kernel_render_refine: the kernel's second render entry (sources generated with PTL_FLAG_REFINE, bit 28) shades the *count pixels of
+ * `list` with the uniforms set now and stores each into the FULL frame at out_rgba8 / out_rgba32f (either may be NULL).  The count is
+ * read on the device: no host read-back, no synchronisation.  `segments` as in ptl_kernel_render.
+ * Both validate their arguments before any GPU call (PTL_ERR_INVALID): null pointers, sizes <= 0, W*H > 2^31, T outside -1 .. 255, a
+ * sharded or in-place frame (rb_stride != 1, rb_phase != 0, in_place), a kernel without the refine entry.  Stream and timing as in
+ * ptl_average_images / ptl_kernel_render. */
+int ptl_aa_edges(int device, const void* frame_rgba8, int width, int height, int threshold, void* list, void* count, void* stream,
+                 float* elapsed_ms);
+int ptl_kernel_render_refine(ptl_kernel* k, const ptl_frame* frame, const void* list, const void* count, void* out_rgba8, void* out_rgba32f,
+                             void* segments, void* stream, float* elapsed_ms);
+/* ptl_renderer_draw_adaptive: one adaptive draw of a renderer created with PTL_FLAG_REFINE (without it: PTL_ERR_INVALID and a message).
+ * Everything a draw does before its launch runs ONCE; then pass 1 with `_aa_count` 1, the classification of out_rgba8 (required), and
+ * the refine pass with `_aa_count` N go on the caller's stream, behind a join of the lanes.  One kernel serves both passes -- `_aa_count`
+ * is a run-time builtin in every build -- so no rebuild falls between them; a background rebuild (PTL_FLAG_ASYNC_REJIT) is adopted before
+ * or after the draw, never in between.  elapsed_ms: the sum of the three launches' GPU times (the call then waits after each;
+ * ptl_renderer_adaptive_times hands out the three).  Whole frames only; frame groups and slices (PTL_FLAG_SLICES cannot be combined
+ * with PTL_FLAG_REFINE) are out of scope.
+ * ptl_renderer_adaptive_result: the list and the count of the last adaptive draw, DEVICE pointers owned and reused by the renderer,
+ * ordered on that draw's stream and valid until the next adaptive draw or destroy. */
+int ptl_renderer_draw_adaptive(ptl_renderer* r, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* stream, float* elapsed_ms);
+int ptl_renderer_adaptive_result(ptl_renderer* r, void** list, void** count);
+int ptl_renderer_adaptive_times(ptl_renderer* r, float ms3[3]); /* pass 1, classification, refine pass of the last TIMED adaptive draw */
+
 /* The Y4M stream such frames travel in: "YUV4MPEG2 W<w> H<h> F<fps>:1 Ip A1:1 C420p10 XYSCSS=420P10 XCOLORRANGE=FULL\n" once, then
  * "FRAME\n" + payload per frame.  Writes the header (NUL-terminated) into buf and returns its length; PTL_ERR_INVALID when it does not fit. */
 int ptl_y4m_header(int width, int height, int fps, char* buf, size_t cap);
@@ -639,7 +684,8 @@ int ptl_strstore_get_identifier(const ptl_strstore* s, int line, char* kind, siz
                                 int* local_line);
 
 /* The fixed device sources embedded in the library: "glsl" (types + numerics contract),
- * "library" (prelude), "trace" (kernel template), "entry" (launchable entry points).
+ * "library" (prelude), "trace" (kernel template), "entry" (launchable entry points),
+ * "refine_entry" (the list-driven render entry of PTL_FLAG_REFINE builds).
  * Returns NULL for an unknown name.  Lets a caller write its own kernel against the same
  * conventions and hand it to ptl_kernel_compile. */
 const char* ptl_device_source(const char* which);

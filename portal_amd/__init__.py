@@ -64,6 +64,7 @@ FLAG_MATERIAL_TABLE_LDS = 1 << 26  # A/B (measured slower, off by default): the 
 FLAG_MATERIAL_TABLE_SCALAR = 1 << 27  # A/B (measured: no gain): the same table in constant memory, a scalar load per distinct material of the wave (waterfall)
 FLAG_CHECK_AFFINE = 1 << 25  # diagnostics: general products, and `segments` counts the ray halves that meet a product / the bounce loop with a w that is not 1 / 0
 FLAG_NO_AFFINE_RAYS = 8388608  # A/B: matrix-times-ray products never assume o.w = 1 / d.w = 0 (default in specialised builds of affine scenes: they do; identical frames)
+FLAG_REFINE = 1 << 28  # adaptive anti-aliasing: a second render entry that shades a device-side list of pixels (SceneRenderer.draw_adaptive)
 FLAG_SLICES = 4194304  # the render entry reads its uniform block from a buffer of blocks (one per blockIdx.z): stage_slice / draw_slices, one launch for several draws
 FLAG_NO_ZERO_MASKS = 524288  # A/B: run-time matrices keep their full products although their zero pattern is known (KernelOptions::mask_zero_elements)
 FLAG_ASYNC_REJIT = 131072  # a specialised renderer never stalls on a rebuild: it draws with the un-specialised kernel until a worker thread has the new one
@@ -182,6 +183,11 @@ def _load() -> C.CDLL:
         "ptl_average_images": (ci, [ci, P(vp), ci, vp, ci, ci, vp, P(C.c_float)]),
         "ptl_average_to_yuv420p10": (ci, [ci, P(vp), ci, vp, ci, ci, vp, P(C.c_float)]),
         "ptl_yuv420p10_frame_bytes": (cs, [ci, ci]),
+        "ptl_aa_edges": (ci, [ci, vp, ci, ci, ci, vp, vp, vp, P(C.c_float)]),
+        "ptl_kernel_render_refine": (ci, [vp, P(Frame), vp, vp, vp, vp, vp, vp, P(C.c_float)]),
+        "ptl_renderer_draw_adaptive": (ci, [vp, P(Frame), vp, vp, vp, P(C.c_float)]),
+        "ptl_renderer_adaptive_result": (ci, [vp, P(vp), P(vp)]),
+        "ptl_renderer_adaptive_times": (ci, [vp, P(C.c_float)]),
         "ptl_y4m_header": (ci, [ci, ci, ci, cp, cs]),
         "ptl_device_alloc": (ci, [ci, cs, P(vp)]),
         "ptl_device_free": (ci, [vp]),
@@ -635,6 +641,48 @@ class SceneRenderer:
         _check(rc, "draw_texture")
         return {"rgba8": a8, "rgba32f": a32, "segments": seg.value if segments else None, "ms": ms.value}
 
+    def draw_adaptive_device(self, frame: Frame, out_rgba8: int, out_rgba32f: int = 0, stream: int = 0, timed: bool = False):
+        """ptl_renderer_draw_adaptive into DEVICE buffers given as integer addresses (FLAG_REFINE renderers; the threshold is the option
+        ``adaptive_aa_threshold``).  Returns the summed GPU time of the three launches in ms when ``timed`` (waits), else None."""
+        ms = C.c_float()
+        _check(lib().ptl_renderer_draw_adaptive(self._h, C.byref(frame), C.c_void_p(out_rgba8 or None), C.c_void_p(out_rgba32f or None),
+                                                C.c_void_p(stream or None), C.byref(ms) if timed else None), "ptl_renderer_draw_adaptive")
+        return ms.value if timed else None
+
+    def adaptive_result(self):
+        """Device addresses (list, count) of the last adaptive draw: owned by the renderer, valid until the next adaptive draw."""
+        lst, cnt = C.c_void_p(), C.c_void_p()
+        _check(lib().ptl_renderer_adaptive_result(self._h, C.byref(lst), C.byref(cnt)), "ptl_renderer_adaptive_result")
+        return int(lst.value), int(cnt.value)
+
+    def adaptive_times(self):
+        """GPU times in ms of the last TIMED adaptive draw: (pass 1, classification, refine pass)."""
+        ms = (C.c_float * 3)()
+        _check(lib().ptl_renderer_adaptive_times(self._h, ms), "ptl_renderer_adaptive_times")
+        return tuple(float(v) for v in ms)
+
+    def draw_adaptive(self, width: int, height: int, threshold: int = 4, rgba32f: bool = False):
+        """Adaptive anti-aliasing (include/portal_amd.h): one sample per pixel, then the full ``aa_count`` where a pixel differs from a
+        neighbour by more than ``threshold`` codes.  Returns dict(rgba8=HxWx4 u8, rgba32f=HxWx4 f32 or None, count=int,
+        list=the refined pixel indices y*W+x (uint32, in the order the GPU produced them), ms=float, ms_passes=(pass 1, classify, refine))."""
+        self.set_option("adaptive_aa_threshold", threshold)
+        frame = Frame(width, height, 0, 1)
+        n = width * height
+        d8 = device_alloc(n * 4, self.device)
+        d32 = device_alloc(n * 16, self.device) if rgba32f else 0
+        try:
+            ms = self.draw_adaptive_device(frame, d8, d32, timed=True)
+            a8 = device_download(d8, n * 4).reshape(height, width, 4)
+            a32 = device_download(d32, n * 16).view(np.float32).reshape(height, width, 4) if rgba32f else None
+            lst, cnt = self.adaptive_result()
+            count = int(device_download(cnt, 4).view(np.uint32)[0])
+            entries = device_download(lst, count * 4).view(np.uint32) if count else np.empty(0, np.uint32)
+        finally:
+            device_free(d8)
+            if d32:
+                device_free(d32)
+        return {"rgba8": a8, "rgba32f": a32, "count": count, "list": entries, "ms": ms, "ms_passes": self.adaptive_times()}
+
 
 GROUP_PEER_STORES, GROUP_COPY_GATHER, GROUP_RCCL_GATHER = 0, 1, 2
 
@@ -775,6 +823,16 @@ def average_to_yuv420p10_device(frame_ptrs, out_ptr: int, width: int, height: in
     ms = C.c_float()
     _check(lib().ptl_average_to_yuv420p10(device, arr, len(frame_ptrs), C.c_void_p(out_ptr), width, height, C.c_void_p(stream or None), C.byref(ms) if timed else None),
            "average_to_yuv420p10")
+    return ms.value if timed else None
+
+
+def aa_edges_device(frame_ptr: int, width: int, height: int, threshold: int, list_ptr: int, count_ptr: int, device: int = 0, stream: int = 0, timed: bool = False):
+    """ptl_aa_edges on DEVICE buffers given as integer addresses: the pixels of the RGBA8 frame that differ from one of their eight
+    neighbours by more than `threshold` codes in R, G or B -> their indices y*W+x at list_ptr (room for W*H uint32) and their number
+    at count_ptr (one uint32, reset by the call)."""
+    ms = C.c_float()
+    _check(lib().ptl_aa_edges(device, C.c_void_p(frame_ptr or None), width, height, threshold, C.c_void_p(list_ptr or None), C.c_void_p(count_ptr or None),
+                              C.c_void_p(stream or None), C.byref(ms) if timed else None), "aa_edges")
     return ms.value if timed else None
 
 

@@ -217,6 +217,12 @@ struct ptl_renderer {
         long bound = -1;
     };
     std::vector<VideoState> videos;
+    // ptl_renderer_draw_adaptive: the list of refined pixels and their count, in device memory; owned here, reused from draw to draw
+    void* adaptive_list = nullptr;
+    void* adaptive_count = nullptr;
+    size_t adaptive_capacity = 0;  // entries
+    int adaptive_threshold = 4;    // option "adaptive_aa_threshold"
+    float adaptive_ms[3] = {0.0f, 0.0f, 0.0f};  // the last timed adaptive draw: pass 1, classification, refine pass
 };
 
 namespace {
@@ -522,6 +528,7 @@ static KernelOptions options_from_flags(unsigned flags) {
     // state of the scene -- the background re-JIT draws with it meanwhile); PTL_FLAG_NO_ZERO_MASKS (bit 19) for A/B measurements and tests
     o.mask_zero_elements = specialised(flags) && !on(PTL_FLAG_NO_ZERO_MASKS);
     o.slices_entry = on(PTL_FLAG_SLICES);  // the render entry reads its uniform block from a buffer of blocks, one per blockIdx.z
+    o.refine_entry = on(PTL_FLAG_REFINE);  // a second render entry over a device-side list of pixels (ptl_renderer_draw_adaptive)
     o.bound_snippets = on(PTL_FLAG_BOUNDED_SNIPPETS);  // scene_intersect first, its distance bounds the intersection-material snippets (opt-in: measured, no gain)
     // Round 6: the first-trip forms -- a second copy of scene_intersect and of every intersection-material snippet for the trip on which all rays of a
     // wave still start at the camera -- are OPT-IN IN THE UN-SPECIALISED KERNEL (bit 24, PTL_FLAG_KEEP_TRANSFORM_DODGES) and stay the default of the
@@ -1034,6 +1041,10 @@ extern "C" int ptl_renderer_create_with_options(ptl_scene* s, int device, const 
         r->device = device;
         r->flags = flags;
         r->asset_root = asset_root ? asset_root : "";
+        if ((flags & PTL_FLAG_REFINE) && (flags & PTL_FLAG_SLICES)) {
+            set_last_error("ptl_renderer_create: PTL_FLAG_REFINE and PTL_FLAG_SLICES cannot be combined (the refine entry reads the module's own uniform block)");
+            return (int)PTL_ERR_INVALID;
+        }
         if (const char* e = std::getenv("PTL_CHECK_AFFINE"); e && e[0] == '1') r->check_affine_on_new_source = true;
         // options first: a specialised build compiles the mode switches in (mode_switches), so the FIRST build is already the one the
         // caller will draw with (`render --stereoimage`: draw_side_by_side) instead of a build nothing runs on plus a rebuild
@@ -1112,6 +1123,10 @@ static int set_plain_option(ptl_renderer* r, const std::string& n, double v) {
     else if (n == "lane_stagger_us") {  // the first draw of lanes 2 .. K after a join comes this much (x 2 / K) later than the previous lane's (ptl_renderer::lane_stagger_us)
         if (!(v >= 0.0) || v > 1e6) return PTL_ERR_INVALID;
         r->lane_stagger_us = v;
+        return PTL_OK;
+    }
+    else if (n == "adaptive_aa_threshold") {  // T of ptl_renderer_draw_adaptive (-1 .. 255; the draw refuses anything else): no uniform depends on it
+        r->adaptive_threshold = (int)v;
         return PTL_OK;
     }
     else if (n == "lane_fence") {  // 1 (default): a lane's launch waits for what the caller's stream holds; 0: it does not (ptl_renderer::Lane)
@@ -1406,7 +1421,7 @@ extern "C" int ptl_renderer_join(ptl_renderer* r, void* stream) {
 // other values for this very state -- the renderer then switches affine rays off for its stage and rebuilds (one re-JIT, the frames stay right).
 static int check_affine_now(ptl_renderer* r, int width, int height, unsigned long long* violations) {
     if (r->device < 0) return PTL_ERR_NO_DEVICE;
-    const unsigned flags = (r->flags & ~(PTL_FLAG_ASYNC_REJIT | PTL_FLAG_SLICES | PTL_FLAG_NO_AFFINE_RAYS)) | PTL_FLAG_CHECK_AFFINE | PTL_FLAG_COUNT_SEGMENTS |
+    const unsigned flags = (r->flags & ~(PTL_FLAG_ASYNC_REJIT | PTL_FLAG_SLICES | PTL_FLAG_REFINE | PTL_FLAG_NO_AFFINE_RAYS)) | PTL_FLAG_CHECK_AFFINE | PTL_FLAG_COUNT_SEGMENTS |
                            PTL_FLAG_QUICK_JIT;  // not async, no slices entry; checking + counting, quick JIT
     std::vector<char> log(1 << 16);
     ptl_renderer* sib = nullptr;
@@ -1468,6 +1483,71 @@ extern "C" int ptl_renderer_draw(ptl_renderer* r, const ptl_frame* frame, void* 
         if (int jrc = join_lanes(r, stream); jrc != PTL_OK) return jrc;
         return ptl_kernel_render(r->kernel, frame, out_rgba8, out_rgba32f, segments, stream, elapsed_ms);
     });
+}
+// Adaptive anti-aliasing (include/portal_amd.h has the contract): the frame with one sample per pixel, the classification of its RGBA8
+// bytes, and the flagged pixels again with the full `_aa_count` -- three launches on the caller's stream, nothing read back in between.
+// `_aa_count` is a run-time builtin in every build, so ONE kernel serves both passes: prepare_draw runs once, in front of pass 1, and is the
+// only place where a kernel is rebuilt or a background build adopted -- never between the passes.
+extern "C" int ptl_renderer_draw_adaptive(ptl_renderer* r, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* stream, float* elapsed_ms) {
+    if (!r || !frame || !out_rgba8 || frame->width <= 0 || frame->height <= 0) return PTL_ERR_INVALID;
+    if (frame->rb_stride != 1 || frame->rb_phase != 0 || frame->in_place) {
+        set_last_error("ptl_renderer_draw_adaptive: a whole frame only (rb_phase 0, rb_stride 1, not in_place)");
+        return PTL_ERR_INVALID;
+    }
+    if ((long long)frame->width * frame->height > (1LL << 31)) return PTL_ERR_INVALID;
+    if (r->adaptive_threshold < -1 || r->adaptive_threshold > 255) {
+        set_last_error("ptl_renderer_draw_adaptive: option adaptive_aa_threshold is outside -1 .. 255");
+        return PTL_ERR_INVALID;
+    }
+    if (!(r->flags & PTL_FLAG_REFINE)) {
+        set_last_error("ptl_renderer_draw_adaptive: the renderer was created without PTL_FLAG_REFINE: its kernel has no refine entry");
+        return PTL_ERR_INVALID;
+    }
+    if (r->device < 0) return PTL_ERR_NO_DEVICE;
+    return guarded([&] {
+        int rc = prepare_draw(r, frame);
+        if (rc < 0) return rc;
+        if (rc = check_affine_if_asked(r, frame); rc < 0) return rc;
+        if (int jrc = join_lanes(r, stream); jrc != PTL_OK) return jrc;
+        const size_t pixels = (size_t)frame->width * (size_t)frame->height;
+        if (r->adaptive_capacity < pixels) {
+            if (r->adaptive_list) ptl_device_free(r->adaptive_list);
+            r->adaptive_list = nullptr;
+            r->adaptive_capacity = 0;
+            if (rc = ptl_device_alloc(r->device, pixels * 4, &r->adaptive_list); rc != PTL_OK) return rc;
+            r->adaptive_capacity = pixels;
+        }
+        if (!r->adaptive_count)
+            if (rc = ptl_device_alloc(r->device, 16, &r->adaptive_count); rc != PTL_OK) return rc;
+        float ms[3] = {0.0f, 0.0f, 0.0f};
+        const int full = r->opt.aa_count, one = 1;
+        // With N = 1 the call is a plain draw and the list is empty: T = 255 flags nothing, and the refine pass is not launched.
+        const bool plain = full <= 1;
+        if (!plain) ptl_kernel_set_uniform(r->kernel, "_aa_count", PTL_I32, &one);
+        rc = ptl_kernel_render(r->kernel, frame, out_rgba8, out_rgba32f, nullptr, stream, elapsed_ms ? &ms[0] : nullptr);
+        if (!plain) ptl_kernel_set_uniform(r->kernel, "_aa_count", PTL_I32, &full);  // (the host copy is again what prepare_draw left; uploaded in front of the refine pass)
+        if (rc == PTL_OK)
+            rc = ptl_aa_edges(r->device, out_rgba8, frame->width, frame->height, plain ? 255 : r->adaptive_threshold, r->adaptive_list, r->adaptive_count, stream,
+                              elapsed_ms ? &ms[1] : nullptr);
+        if (rc == PTL_OK && !plain)
+            rc = ptl_kernel_render_refine(r->kernel, frame, r->adaptive_list, r->adaptive_count, out_rgba8, out_rgba32f, nullptr, stream, elapsed_ms ? &ms[2] : nullptr);
+        if (elapsed_ms) {
+            *elapsed_ms = ms[0] + ms[1] + ms[2];
+            std::copy(ms, ms + 3, r->adaptive_ms);
+        }
+        return rc;
+    });
+}
+extern "C" int ptl_renderer_adaptive_result(ptl_renderer* r, void** list, void** count) {
+    if (!r || !r->adaptive_list || !r->adaptive_count) return PTL_ERR_INVALID;
+    if (list) *list = r->adaptive_list;
+    if (count) *count = r->adaptive_count;
+    return PTL_OK;
+}
+extern "C" int ptl_renderer_adaptive_times(ptl_renderer* r, float ms3[3]) {
+    if (!r || !ms3) return PTL_ERR_INVALID;
+    std::copy(r->adaptive_ms, r->adaptive_ms + 3, ms3);
+    return PTL_OK;
 }
 extern "C" int ptl_renderer_draw_to_host(ptl_renderer* r, const ptl_frame* frame, uint8_t* host_rgba8, float* host_rgba32f,
                                          uint64_t* host_segments, float* elapsed_ms) {
@@ -1818,6 +1898,8 @@ extern "C" void ptl_renderer_destroy(ptl_renderer* r) {
     for (auto& l : r->lanes)
         if (l.done) ptl_event_destroy(l.done);  // (the lanes' streams belong to the process-wide pool)
     if (r->fence) ptl_event_destroy(r->fence);
+    if (r->adaptive_list) ptl_device_free(r->adaptive_list);  // (hipFree waits for the device: the last adaptive draw has finished)
+    if (r->adaptive_count) ptl_device_free(r->adaptive_count);
     if (r->spec_kernel || r->dyn_kernel) {  // background re-JIT: `kernel` is one of these two
         ptl_kernel_destroy(r->spec_kernel);
         ptl_kernel_destroy(r->dyn_kernel);
@@ -1883,6 +1965,7 @@ extern "C" const char* ptl_device_source(const char* which) {
     if (w == "library") return device_source_library();
     if (w == "trace") return device_source_trace_template();
     if (w == "entry") return device_source_entry();
+    if (w == "refine_entry") return device_source_refine_entry();
     return nullptr;
 }
 

@@ -43,6 +43,7 @@ void usage() {
                  "                  [--width W] [--height H] [--aa-count N] [--render-depth D] [--device I] [--asset-root DIR] [--panini D --fov DEG]\n"
                  "                  [--gpus N | --devices a,b,..] [--transport stores|copy|rccl] [--multi-process]   one frame across the GPUs of a node\n"
                  "                  [--specialize 0] do NOT bake the scene state into the kernel   [--fast] tolerance mode   [--exact-cr] numerics contract 1   [--opt3] JIT at -O3 like the library default (render-frame: -O1)   [--timing] where the wall time went\n"
+                 "                  [--adaptive-aa [T]]  one sample per pixel, --aa-count samples only where a pixel differs from a neighbour by more than T codes (default 4, -1 .. 255); one GPU\n"
                  "       portal-amd precompile <scene.ron> [--stage NAME] [--specialize 0]      fill the code-object cache (no GPU needed)\n"
                  "       portal-amd render <scene[,scene..]> [clip[,clip..]] [--width 3840] [--height 2160] [--fps 60] [--motion-blur-frames 1]\n"
                  "                  [--stereoimage] [--batch-subframes 0|1] [--no-skip-existing] [--filter-starts-with P] [--aa-count 4] [--render-depth 150]\n"
@@ -213,6 +214,8 @@ struct Options {
     int gpus = 1, rank = 0, world = 1;
     std::string devices, transport = "stores", ipc_handle;
     bool multi_process = false, fast = false, exact_cr = false, opt3 = false;
+    bool adaptive = false;   // render-frame --adaptive-aa [T]: one sample per pixel, the full --aa-count only where a pixel differs from a neighbour by more than T codes
+    int adaptive_t = 4;
     std::vector<std::string> argv;  // the command line as given (handed on to shard processes)
 };
 
@@ -291,6 +294,7 @@ unsigned frame_flags(const Options& o) {
     // ONE frame: the wall time is the JIT's, not the kernel's (profiles/r03/render_frame_e2e.log: 2.4 s of -O3 hiprtc for a 0.33 ms kernel, 1.2 s
     // of -O1 for a 0.36 ms one) -- unless the caller wants the shipped optimisation level (--opt3), e.g. to fill the cache for a bench
     if (!o.opt3) f |= PTL_FLAG_QUICK_JIT;
+    if (o.adaptive) f |= PTL_FLAG_REFINE;  // the kernel's second render entry, over the list of flagged pixels
     return f;
 }
 
@@ -473,13 +477,28 @@ int render_frame(const Options& o) {
     if (int rc = setup_renderer(o, scene, r, true)) return rc;
     ptl_frame frame{o.width, o.height, 0, 1, 0};
     float ms = 0.0f;
-    if (ptl_renderer_draw_to_host(r, &frame, img.data(), nullptr, nullptr, &ms) != PTL_OK) return fail("render");
+    unsigned int refined = 0;
+    float pass_ms[3] = {0.0f, 0.0f, 0.0f};
+    if (o.adaptive) {  // one sample per pixel, classification, the flagged pixels again with --aa-count samples: three launches, one download
+        void *dev = nullptr, *list = nullptr, *count = nullptr;
+        ptl_renderer_set_option(r, "adaptive_aa_threshold", o.adaptive_t);
+        if (ptl_device_alloc(devices[0], img.size(), &dev) != PTL_OK) return fail("device frame");
+        if (ptl_renderer_draw_adaptive(r, &frame, dev, nullptr, nullptr, &ms) != PTL_OK) return fail("render");
+        if (ptl_device_download(img.data(), dev, img.size(), nullptr) != PTL_OK) return fail("download");
+        if (ptl_renderer_adaptive_result(r, &list, &count) != PTL_OK || ptl_device_download(&refined, count, sizeof refined, nullptr) != PTL_OK) return fail("refined count");
+        ptl_renderer_adaptive_times(r, pass_ms);
+        ptl_device_free(dev);
+    } else if (ptl_renderer_draw_to_host(r, &frame, img.data(), nullptr, nullptr, &ms) != PTL_OK)
+        return fail("render");
     double t_draw = seconds_since(t0);
     if (!dir_of(o.output).empty()) make_dirs(dir_of(o.output));
     if (ptl_png_write(o.output.c_str(), img.data(), o.width, o.height) != PTL_OK) return fail("png");
     double total = seconds_since(t0);
     std::printf("Rendered `%s` to `%s` (%dx%d, aa %d, depth %d): kernel %.3f ms, %.1f Mray/s; total %.2f s\n", o.scene.c_str(), o.output.c_str(),
                 o.width, o.height, o.aa, o.depth, ms, (double)o.width * o.height * o.aa / (ms * 1e3), total);
+    if (o.adaptive && o.timing)
+        std::printf("adaptive aa: threshold %d, %u of %zu pixels refined (%.2f %%); GPU ms: one-sample pass %.3f, classification %.3f, refine pass %.3f\n", o.adaptive_t,
+                    refined, (size_t)o.width * o.height, 100.0 * refined / ((double)o.width * o.height), pass_ms[0], pass_ms[1], pass_ms[2]);
     if (o.timing)  // where the wall time went: the JIT (or the code-object cache) dominates a single frame
         std::printf("timing: scene load %.3f s, generate + compile/load kernel %.3f s, update + draw + download %.3f s, png %.3f s\n", t_load,
                     t_build - t_load, t_draw - t_build, total - t_draw);
@@ -1230,6 +1249,21 @@ int main(int argc, char** argv) {
         else if (a == "--devices") o.devices = next();
         else if (a == "--transport") o.transport = next();
         else if (a == "--multi-process") o.multi_process = true;
+        else if (a == "--adaptive-aa") {
+            o.adaptive = true;
+            if (i + 1 < argc) {  // the threshold is optional: an integer right behind the switch is it ("-1" included)
+                char* end = nullptr;
+                const long t = std::strtol(argv[i + 1], &end, 10);
+                if (end != argv[i + 1] && *end == '\0') {
+                    ++i;
+                    if (t < -1 || t > 255) {
+                        std::fprintf(stderr, "--adaptive-aa T: the threshold is an integer in -1 .. 255\n");
+                        return 2;
+                    }
+                    o.adaptive_t = (int)t;
+                }
+            }
+        }
         else if (a == "--fast") o.fast = true;
         else if (a == "--exact-cr") o.exact_cr = true;
         else if (a == "--opt3") o.opt3 = true;
@@ -1266,6 +1300,14 @@ int main(int argc, char** argv) {
     }
     if (o.y4m && o.shards > 1) {
         std::fprintf(stderr, "--frames y4m cannot be combined with --shard K/N, N > 1: a stream needs every frame, in order\n");
+        return 2;
+    }
+    if (o.adaptive && cmd != "render-frame") {
+        std::fprintf(stderr, "--adaptive-aa is an option of render-frame: clips trace their sub-frames through the slices entry, which has no refine pass\n");
+        return 2;
+    }
+    if (o.adaptive && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.shards > 1)) {
+        std::fprintf(stderr, "--adaptive-aa draws whole frames on one GPU: it cannot be combined with --gpus N, N > 1, several --devices or --shard\n");
         return 2;
     }
     if (cmd == "render") return render(o);

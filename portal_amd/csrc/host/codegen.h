@@ -154,6 +154,10 @@ struct KernelOptions {
     // frame (src/main.rs:1798 re-draws with `_aa_start` windows one after the other) -- so that their ramps and tails overlap.  Applied to the
     // generated text by substitution (codegen.cpp `apply_slices_entry`): kernels built without it are byte for byte what they were.
     bool slices_entry = false;
+    // Adaptive anti-aliasing (PTL_FLAG_REFINE): the module gets a second render entry, `ptl_render_refine_kernel` (device/ptl_refine_entry.h), which
+    // shades the pixels of a device-side list instead of a rectangle.  Spliced into the generated text like the slices entry (codegen.cpp
+    // `apply_refine_entry`): kernels built without it are byte for byte what they were.  Not together with slices_entry.
+    bool refine_entry = false;
     // Affine rays (round 5): in a kernel whose every scene matrix is KNOWN to have the bottom row 0 0 0 1 (baked, or through its pattern) and
     // whose scene snippets never write a ray's w, every origin has w = 1 and every direction w = 0, and the products of a matrix with a ray
     // say so (device/ptl_glsl.h PTL_AFFINE_RAYS): the translation column costs a direction nothing, the w row folds to a constant.  Exact for
@@ -241,5 +245,6 @@ const char* device_source_glsl();
 const char* device_source_library();
 const char* device_source_trace_template();
 const char* device_source_entry();
+const char* device_source_refine_entry();
 
 }  // namespace ptl

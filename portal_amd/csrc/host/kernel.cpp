@@ -42,6 +42,8 @@ struct ptl_kernel {
     hip::hipFunction_t fn = nullptr;
     hip::hipFunction_t teleport_fn = nullptr;  // optional: ptl_teleport_kernel
     hip::hipFunction_t derive_fn = nullptr;    // optional: ptl_derive_kernel, the uniform prologue (runs after every upload)
+    hip::hipFunction_t refine_fn = nullptr;    // optional: ptl_render_refine_kernel, the list-driven render entry (sources generated with PTL_FLAG_REFINE)
+    bool has_refine = false;                   // the source names that entry (known without a device)
     void* dev_block = nullptr;  // address of __constant__ ptl_u
     size_t dev_block_size = 0;
     std::vector<unsigned char> shadow;  // host copy of the uniform block
@@ -442,7 +444,7 @@ int bind_module(ptl_kernel* k, const hip::Runtime* rt, RenderEntry entry, size_t
             return PTL_ERR_HIP;
         k->sliced = true;
     }
-    for (auto [fn, name] : {std::pair{&k->teleport_fn, "ptl_teleport_kernel"}, std::pair{&k->derive_fn, "ptl_derive_kernel"}})
+    for (auto [fn, name] : {std::pair{&k->teleport_fn, "ptl_teleport_kernel"}, std::pair{&k->derive_fn, "ptl_derive_kernel"}, std::pair{&k->refine_fn, "ptl_render_refine_kernel"}})
         if (rt->hipModuleGetFunction(fn, k->module, name) != 0) {
             *fn = nullptr;          // hand-written layer-1 kernels need not have the other entry points
             rt->hipGetLastError();  // ... and the expected hipErrorNotFound must not stay behind as the thread's sticky
@@ -480,6 +482,7 @@ int compile_kernel(const CompileRequest& rq, const std::vector<char>* prebuilt, 
     const BuildTraits traits = read_traits(rq);
     k->affine_rays = traits.affine_rays;
     k->split = traits.split;
+    k->has_refine = !traits.teleport_only && std::strstr(rq.source, "ptl_render_refine_kernel(") != nullptr;
     if (k->split) {
         k->source = rq.source;
         k->defines.assign(rq.defines, rq.defines + rq.n_defines);
@@ -571,6 +574,7 @@ extern "C" int ptl_kernel_clone(ptl_kernel* src, ptl_kernel** out) {
     k->shadow = src->shadow;
     k->block_waves = src->block_waves;
     k->split = src->split;
+    k->has_refine = src->has_refine;
     k->source = src->source;
     k->defines = src->defines;
     // (affine_rays is NOT inherited: a clone accepts matrices through ptl_kernel_set_uniform that its original refuses)
@@ -858,6 +862,44 @@ extern "C" int ptl_kernel_render(ptl_kernel* k, const ptl_frame* frame, void* ou
     // (a single draw of a module with the slices entry: slice 0 of its buffer, one slice)
     if (int rc = k->sliced ? upload_slices(k, rt, stream, 1, true) : upload_uniforms(k, rt, stream); rc != PTL_OK) return rc;
     return launch_render(k, rt, frame, 1, out_rgba8, out_rgba32f, 0, segments, stream, elapsed_ms, k->sliced ? kSlicesLaunch : "hipModuleLaunchKernel");
+}
+
+// The refine pass of the adaptive anti-aliasing: the module's second render entry (device/ptl_refine_entry.h) shades the `*count` pixels of
+// `list` -- both in device memory, read on the device -- with the uniforms set now, each lane storing its own pixel into the full frame.
+// A grid of fixed size, chosen from the frame size; the workgroups stride over the list.
+extern "C" int ptl_kernel_render_refine(ptl_kernel* k, const ptl_frame* frame, const void* list, const void* count, void* out_rgba8, void* out_rgba32f,
+                                        void* segments, void* stream, float* elapsed_ms) {
+    if (!k || !frame || !list || !count || frame->width <= 0 || frame->height <= 0) return PTL_ERR_INVALID;
+    if (frame->rb_stride != 1 || frame->rb_phase != 0 || frame->in_place) {
+        set_last_error("ptl_kernel_render_refine: the list names pixels of a whole frame (rb_phase 0, rb_stride 1, not in_place)");
+        return PTL_ERR_INVALID;
+    }
+    if ((long long)frame->width * frame->height > (1LL << 31)) return PTL_ERR_INVALID;  // an entry is a 32-bit pixel index
+    if (!k->has_refine) {
+        set_last_error("ptl_kernel_render_refine: the kernel was not generated with the refine entry (PTL_FLAG_REFINE)");
+        return PTL_ERR_INVALID;
+    }
+    if (k->device < 0 || !k->refine_fn) return PTL_ERR_NO_DEVICE;
+    const hip::Runtime* rt = hip::runtime(nullptr);
+    if (!hip_ok(rt, rt->hipSetDevice(k->device), "hipSetDevice")) return PTL_ERR_HIP;
+    if (int rc = upload_uniforms(k, rt, stream); rc != PTL_OK) return rc;
+    int width = frame->width, height = frame->height;
+    void* args[] = {&list, &count, &out_rgba8, &out_rgba32f, &width, &height, &segments};
+    // a chunk of 256 entries per workgroup and trip; 2 048 workgroups (8 per CU) cover a frame's worth of entries in a few trips
+    const long long chunks = ((long long)width * height + 255) / 256;
+    const unsigned grid = (unsigned)std::min<long long>(chunks, 2048);
+    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
+    if (!hip_ok(rt, rt->hipModuleLaunchKernel(k->refine_fn, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr), "hipModuleLaunchKernel(ptl_render_refine_kernel)"))
+        return PTL_ERR_HIP;
+    k->last_stream = stream;
+    k->launched = true;
+    if (k->ev_done) rt->hipEventRecord(k->ev_done, stream);
+    if (elapsed_ms) {
+        rt->hipEventRecord(k->ev1, stream);
+        if (!hip_ok(rt, rt->hipEventSynchronize(k->ev1), "hipEventSynchronize")) return PTL_ERR_HIP;
+        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
+    }
+    return PTL_OK;
 }
 
 extern "C" int ptl_kernel_render_to_host(ptl_kernel* k, const ptl_frame* frame, uint8_t* host_rgba8, float* host_rgba32f,

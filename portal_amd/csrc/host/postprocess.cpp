@@ -172,6 +172,34 @@ extern "C" int ptl_average_to_yuv420p10(int device, const void* const* frames_rg
     return launch_over_subframes(device, kernel, frames_rgba8, n_frames, {&out_yuv, &width, &height}, lanes, stream, elapsed_ms);
 }
 
+// ptl_aa_edges: the classification pass of the adaptive anti-aliasing (portal_amd/csrc/kernels/aa_edges.hip; the contract is in
+// include/portal_amd.h).  The count is reset on `stream` by the call itself; a 256-thread workgroup per 64x32 pixel region.
+extern "C" int ptl_aa_edges(int device, const void* frame_rgba8, int width, int height, int threshold, void* list, void* count, void* stream,
+                            float* elapsed_ms) {
+    if (!frame_rgba8 || !list || !count || width <= 0 || height <= 0 || threshold < -1 || threshold > 255) return PTL_ERR_INVALID;
+    if ((long long)width * height > (1LL << 31)) return PTL_ERR_INVALID;  // an entry is a 32-bit pixel index
+    if ((reinterpret_cast<uintptr_t>(frame_rgba8) | reinterpret_cast<uintptr_t>(list) | reinterpret_cast<uintptr_t>(count)) & 3u) return PTL_ERR_INVALID;
+    LoadedKernel* k = nullptr;
+    if (int rc = load_kernel(device, "aa_edges.hsaco", "ptl_aa_edges_kernel", &k); rc != PTL_OK) return rc;
+    const hip::Runtime* rt = hip::runtime(nullptr);
+    rt->hipSetDevice(device);
+    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
+    int err = rt->hipMemsetAsync(count, 0, 4, stream);
+    void* args[] = {&frame_rgba8, &width, &height, &threshold, &list, &count};
+    if (err == 0) err = rt->hipModuleLaunchKernel(k->fn, (unsigned)((width + 63) / 64), (unsigned)((height + 31) / 32), 1, 256, 1, 1, 0, stream, args, nullptr);
+    if (err != 0) {
+        set_last_error(std::string("hipModuleLaunchKernel(aa_edges): ") + rt->hipGetErrorString(err));
+        rt->hipGetLastError();
+        return PTL_ERR_HIP;
+    }
+    if (elapsed_ms) {
+        rt->hipEventRecord(k->ev1, stream);
+        rt->hipEventSynchronize(k->ev1);
+        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
+    }
+    return PTL_OK;
+}
+
 extern "C" int ptl_y4m_header(int width, int height, int fps, char* buf, size_t cap) {
     if (width <= 0 || height <= 0 || fps <= 0 || !buf) return PTL_ERR_INVALID;
     int len = std::snprintf(buf, cap, "YUV4MPEG2 W%d H%d F%d:1 Ip A1:1 C420p10 XYSCSS=420P10 XCOLORRANGE=FULL\n", width, height, fps);
