@@ -27,8 +27,8 @@ $(OBJDIR)/%.o: $(HOST)/%.cpp $(wildcard $(HOST)/*.h) include/portal_amd.h
 $(LIB): $(OBJS)
 	$(CXX) -shared -o $@ $(OBJS) -ldl -lz -lpthread
 
-$(CLI): $(HOST)/cli.cpp $(LIB) include/portal_amd.h
-	$(CXX) $(CXXFLAGS) $(HOST)/cli.cpp -o $@ -Lportal_amd -lportal_amd -Wl,-rpath,'$$ORIGIN'
+$(CLI): $(HOST)/cli.cpp $(HOST)/cli_video.cpp $(HOST)/cli_common.h $(LIB) include/portal_amd.h
+	$(CXX) $(CXXFLAGS) $(HOST)/cli.cpp $(HOST)/cli_video.cpp -o $@ -Lportal_amd -lportal_amd -Wl,-rpath,'$$ORIGIN'
 
 kernels: $(KERNELS)
 portal_amd/kernels/%.hsaco: portal_amd/csrc/kernels/%.hip portal_amd/csrc/kernels/average_common.h

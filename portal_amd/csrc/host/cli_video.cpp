@@ -1,0 +1,722 @@
+// cli_video.cpp -- `portal-amd render <scenes> [clips]`, the offline counterpart of the reference's `portal render` (src/main.rs:2757-2874 +
+// render_animation src/main.rs:1758-1873).  What is here: the host side of the clip pipeline (EncoderPool, PinnedFrames, FramePipeline), the
+// two forms a clip's frames leave in (FrameOutput: PNG files for ffmpeg, or one Y4M stream), what lives as long as a scene's clips (SceneRun)
+// and as long as one clip (ClipRun), the clip loop (render_clip), the workers that compile the next clips' kernels (Prefetcher) and `render`.
+// Argument parsing and every other command are in cli.cpp; what both share is in cli_common.h.
+//
+// Video pipeline: for every frame i of a clip, `motion_blur_frames` sub-frames are traced straight into device buffers (aa_start = j,
+// time = subframe_time(i, j)), averaged on the GPU (ptl_average_images), downloaded once, and PNG-encoded on a pool of host threads while
+// the GPU already traces the next frame.  With --frames y4m the averaging kernel is the fused one (ptl_average_to_yuv420p10): what is
+// downloaded is the planar 4:2:0 10-bit frame the encoder consumes, and one writer thread streams the frames in order into ffmpeg's stdin
+// (or a .y4m file) while the clip is still rendering: no PNG files, no anim/ directory, no zscale pass.
+#include <dirent.h>
+#include <fcntl.h>
+#include <sys/wait.h>
+#include <unistd.h>
+
+#include <signal.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cerrno>
+#include <condition_variable>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <functional>
+#include <mutex>
+#include <stop_token>
+#include <thread>
+
+#include "cli_common.h"
+
+namespace {
+
+bool exists(const std::string& path) {
+    struct stat st;
+    return ::stat(path.c_str(), &st) == 0;
+}
+
+// The reference compiles its scene list in (src/gui/scenes.rs); here a scene is a path, or a bare name under --scenes-dir.
+std::string scene_file(const std::string& arg, const std::string& scenes_dir) {
+    bool looks_like_a_path = arg.find('/') != std::string::npos || (arg.size() > 4 && arg.compare(arg.size() - 4, 4, ".ron") == 0);
+    if (exists(arg) || looks_like_a_path) return arg;
+    return scenes_dir + "/" + arg + ".ron";
+}
+
+std::string scene_link(const std::string& path) {  // "dir/name.ron" -> "name"
+    size_t slash = path.rfind('/');
+    std::string base = slash == std::string::npos ? path : path.substr(slash + 1);
+    return base.size() > 4 && base.substr(base.size() - 4) == ".ron" ? base.substr(0, base.size() - 4) : base;
+}
+
+// Host threads that PNG-encode finished frames while the GPU traces the next ones.
+class EncoderPool {
+public:
+    EncoderPool(int threads, size_t max_pending) : max_pending_(max_pending) {
+        for (int k = 0; k < threads; ++k) workers_.emplace_back([this] { run(); });
+    }
+    ~EncoderPool() { finish(); }
+    void submit(std::function<void()> job) {
+        std::unique_lock<std::mutex> lock(mu_);
+        space_.wait(lock, [&] { return jobs_.size() < max_pending_; });
+        jobs_.push_back(std::move(job));
+        work_.notify_one();
+    }
+    void finish() {
+        {
+            std::unique_lock<std::mutex> lock(mu_);
+            done_ = true;
+        }
+        work_.notify_all();
+        for (auto& t : workers_)
+            if (t.joinable()) t.join();
+    }
+
+private:
+    void run() {
+        for (;;) {
+            std::function<void()> job;
+            {
+                std::unique_lock<std::mutex> lock(mu_);
+                work_.wait(lock, [&] { return done_ || !jobs_.empty(); });
+                if (jobs_.empty()) return;
+                job = std::move(jobs_.front());
+                jobs_.pop_front();
+                space_.notify_one();
+            }
+            job();
+        }
+    }
+    std::mutex mu_;
+    std::condition_variable work_, space_;
+    std::deque<std::function<void()>> jobs_;
+    std::vector<std::thread> workers_;
+    size_t max_pending_;
+    bool done_ = false;
+};
+
+// Page-locked frame buffers recycled between the download and the encoder threads.
+class PinnedFrames {
+public:
+    PinnedFrames(size_t bytes, int count) {
+        for (int k = 0; k < count; ++k) {
+            void* p = nullptr;
+            if (ptl_host_alloc(bytes, &p) != PTL_OK) break;
+            all_.push_back(p);
+            free_.push_back(p);
+        }
+    }
+    ~PinnedFrames() {
+        for (void* p : all_) ptl_host_free(p);
+    }
+    bool ok() const { return !all_.empty(); }
+    uint8_t* take() {
+        std::unique_lock<std::mutex> lock(mu_);
+        cv_.wait(lock, [&] { return !free_.empty(); });
+        void* p = free_.back();
+        free_.pop_back();
+        return static_cast<uint8_t*>(p);
+    }
+    void give(uint8_t* p) {
+        std::unique_lock<std::mutex> lock(mu_);
+        free_.push_back(p);
+        cv_.notify_one();
+    }
+
+private:
+    std::vector<void*> all_, free_;
+    std::mutex mu_;
+    std::condition_variable cv_;
+};
+
+// frames of a clip are intermediates (ffmpeg reads them, then anim/ is removed): fast deflate, 2.3x the encode rate of level 6
+constexpr int kFrameDeflateLevel = 3;
+
+// Start a program without a shell (arguments are passed as they are: no quoting rules to get wrong), as a fresh child process: `stdin_fd` >= 0
+// becomes its stdin, `quiet` sends what it prints to /dev/null.  Its pid, or -1
+pid_t start_program(const std::vector<std::string>& argv, int stdin_fd, bool quiet) {
+    std::vector<char*> args;  // (built before the fork: the child only redirects and executes)
+    for (const std::string& a : argv) args.push_back(const_cast<char*>(a.c_str()));
+    args.push_back(nullptr);
+    pid_t pid = fork();
+    if (pid != 0) return pid;
+    if (stdin_fd >= 0) dup2(stdin_fd, 0);  // (the copy is not close-on-exec)
+    int null_fd = quiet ? open("/dev/null", O_WRONLY) : -1;
+    if (null_fd >= 0) {
+        dup2(null_fd, 1);
+        dup2(null_fd, 2);
+    }
+    execvp(args[0], args.data());
+    _exit(127);
+}
+int wait_program(pid_t pid) {  // its exit status; -1: it did not exit by itself
+    int status = 0;
+    return waitpid(pid, &status, 0) > 0 && WIFEXITED(status) ? WEXITSTATUS(status) : -1;
+}
+int run_program(const std::vector<std::string>& argv, bool quiet) {  // -1 = could not start
+    pid_t pid = start_program(argv, -1, quiet);
+    return pid < 0 ? -1 : wait_program(pid);
+}
+
+// One clip as a Y4M stream (--frames y4m): a file, or the stdin of an encoder started as a fresh child process.  Written by ONE thread
+// in frame order; the first error sticks, later writes do nothing, and the clip loop looks at failed() before every frame -- a dead
+// encoder ends the clip instead of blocking it (SIGPIPE is ignored in this mode: the write returns EPIPE).
+class Y4mStream {
+public:
+    ~Y4mStream() { close(); }
+    bool open_file(const std::string& path) {
+        fd_ = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+        if (fd_ < 0) fail("cannot write `" + path + "`: " + std::strerror(errno));
+        return fd_ >= 0;
+    }
+    bool open_program(const std::vector<std::string>& argv) {  // our pipe is its stdin
+        int ends[2];
+        if (::pipe2(ends, O_CLOEXEC) != 0) return fail("pipe: " + std::string(std::strerror(errno))), false;
+        started_ = std::chrono::steady_clock::now();
+        child_ = start_program(argv, ends[0], true);  // (the write end is close-on-exec, so the child sees the end of the stream)
+        if (child_ < 0) {
+            ::close(ends[0]);
+            ::close(ends[1]);
+            return fail("fork: " + std::string(std::strerror(errno))), false;
+        }
+        ::close(ends[0]);
+        fd_ = ends[1];
+        return true;
+    }
+    void write(const void* data, size_t n) {
+        const char* p = static_cast<const char*>(data);
+        while (n > 0 && !failed()) {
+            ssize_t done = ::write(fd_, p, n);
+            if (done < 0 && errno == EINTR) continue;
+            if (done < 0) return fail(std::string(child_ > 0 ? "the encoder stopped reading the stream: " : "cannot write the stream: ") + std::strerror(errno));
+            p += done;
+            n -= (size_t)done;
+        }
+    }
+    void fail(const std::string& what) {
+        if (failed()) return;
+        error_ = what;
+        failed_.store(true, std::memory_order_release);
+    }
+    bool failed() const { return failed_.load(std::memory_order_acquire); }
+    const std::string& error() const { return error_; }  // valid once failed()
+    bool to_program() const { return child_ > 0; }
+    double seconds() const { return seconds_since(started_); }
+    // end of stream; for a child its exit status (-1: it did not exit by itself), for a file 0
+    int close() {
+        if (fd_ >= 0 && ::close(fd_) != 0) fail(std::string("cannot write the stream: ") + std::strerror(errno));
+        fd_ = -1;
+        return child_ > 0 ? wait_program(std::exchange(child_, -1)) : 0;
+    }
+
+private:
+    int fd_ = -1;
+    pid_t child_ = -1;
+    std::atomic<bool> failed_{false};
+    std::string error_;
+    std::chrono::steady_clock::time_point started_ = std::chrono::steady_clock::now();
+};
+
+void remove_tree(const std::string& path) {  // rm -rf of a directory we created ourselves (frames only, one level)
+    if (DIR* d = opendir(path.c_str())) {
+        while (dirent* e = readdir(d)) {
+            std::string name = e->d_name;
+            if (name != "." && name != "..") ::unlink((path + "/" + name).c_str());
+        }
+        closedir(d);
+    }
+    ::rmdir(path.c_str());
+}
+
+// the reference's encoder settings (src/main.rs:1843-1857), from -c:v onwards: what follows the input, whichever form the input has
+std::vector<std::string> encoder_arguments(const std::string& video) {
+    return {"-c:v", "libx265", "-pix_fmt", "yuv420p10le", "-crf", "15", "-preset", "slow", "-x265-params",
+            "colorprim=bt709:transfer=iec61966-2-1:colormatrix=bt709:range=full", "-colorspace", "bt709", "-color_primaries", "bt709", "-color_trc",
+            "iec61966-2-1", "-color_range", "pc", "-movflags", "+write_colr+faststart", "-tag:v", "hvc1", "-y", video};
+}
+
+// the reference's ffmpeg hand-off (src/main.rs:1829-1869), same arguments; frames are kept when there is no ffmpeg
+int encode_video(const Options& o, const std::string& scene_name, const std::string& clip, int fps) {
+    std::string anim = o.out_dir + "/anim", video = o.out_dir + "/video/" + scene_name + "/" + clip + ".mov";
+    if (run_program({"ffmpeg", "-version"}, true) != 0) {
+        // no encoder on this machine: park the clip's frames next to where the video would be, so the next clip starts
+        // from an empty anim/ (the reference removes anim/ after ffmpeg; frame_%d.png of another clip would be "existing")
+        std::string frames = o.out_dir + "/video/" + scene_name + "/" + clip + ".frames";
+        remove_tree(frames);
+        if (::rename(anim.c_str(), frames.c_str()) != 0) std::fprintf(stderr, "could not move anim/ to %s\n", frames.c_str());
+        std::printf("ffmpeg not found: frames kept in `%s` (ffmpeg -framerate %d -i frame_%%d.png ... ../%s.mov)\n", frames.c_str(), fps, clip.c_str());
+        return 0;
+    }
+    std::printf("Start ffmpeg to render video\n");
+    auto started = std::chrono::steady_clock::now();
+    std::vector<std::string> command = {
+        "ffmpeg", "-framerate", std::to_string(fps), "-i", anim + "/frame_%d.png", "-vf",
+        "zscale=primariesin=bt709:transferin=iec61966-2-1:matrixin=bt709:rangein=full:primaries=bt709:transfer=iec61966-2-1:matrix=bt709:range=full,"
+        "format=yuv420p10le"};
+    for (const std::string& a : encoder_arguments(video)) command.push_back(a);
+    int status = run_program(command, true);
+    std::printf("ffmpeg status: %d\nffmpeg time: %.2f s\n", status, std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count());
+    remove_tree(anim);  // like the reference, whatever ffmpeg said (src/main.rs:1860)
+    return 0;
+}
+
+// What the clip loop keeps in flight: the download of frame i runs on its own stream into page-locked memory while frame i+1
+// is being traced; `kRing` result buffers so a frame is not overwritten before its copy has left.
+struct FramePipeline {
+    static constexpr int kRing = 3;
+    int device = 0;
+    void* copy_stream = nullptr;
+    void* results[kRing] = {nullptr, nullptr, nullptr};   // device RGBA8 frames ready for download
+    void* copied[kRing] = {nullptr, nullptr, nullptr};    // event: the copy out of results[k] has finished
+    bool copy_pending[kRing] = {false, false, false};
+    void* produced = nullptr;                             // event: results[k] is complete on the tracing stream
+
+    bool create(int dev, size_t bytes) {
+        device = dev;
+        if (ptl_stream_create(dev, &copy_stream) != PTL_OK || ptl_event_create(dev, &produced) != PTL_OK) return false;
+        for (int k = 0; k < kRing; ++k)
+            if (ptl_device_alloc(dev, bytes, &results[k]) != PTL_OK || ptl_event_create(dev, &copied[k]) != PTL_OK) return false;
+        return true;
+    }
+    ~FramePipeline() {
+        if (copy_stream) ptl_stream_destroy(copy_stream);
+        if (produced) ptl_event_destroy(produced);
+        for (int k = 0; k < kRing; ++k) {
+            if (copied[k]) ptl_event_destroy(copied[k]);
+            if (results[k]) ptl_device_free(results[k]);
+        }
+    }
+};
+
+// One clip of the run
+struct Clip {
+    std::string name;
+    double duration;
+    int fps = 0;              // --fps, or the clip's own (kClipOverrides)
+    bool specialise = false;  // it gets a clip-constant kernel: that repays its extra JIT (~1 s) only on a clip with enough work
+};
+
+// What lives as long as a scene's clips.  Released in reverse order: the pipeline, the sub-frame block, the renderer, the scene.
+struct SceneRun {
+    SceneRun(const Options& o, std::string name) : o(o), name(std::move(name)) {}
+    const Options& o;
+    const std::string name;                                   // video/<name>/<clip>
+    const int width = o.stereo ? o.width * 2 : o.width;      // src/main.rs:2822-2829
+    const int height = o.height;
+    const int threads = (int)std::min(64u, std::max(2u, std::thread::hardware_concurrency() * 3 / 4));  // PNG encoders
+    const size_t frame_bytes = (size_t)width * height * 4;   // an RGBA8 frame: a sub-frame, a still
+    size_t result_bytes = 0;                                  // a frame as it leaves the card
+    ScenePtr scene;
+    RendererPtr r;
+    std::unique_ptr<void, HandleFree> subframe_block;  // ONE allocation, sub-frame j at j * bytes: what the one-launch form writes (slice z behind slice z - 1)
+    std::vector<void*> subframes;
+    FramePipeline pipe;
+};
+
+// ---- the two forms a clip's frames leave in ------------------------------------------------------
+// One object per clip.  It alone knows how the clip opens, whether a frame is already there, where a sub-frame is drawn and which kernel
+// makes the result of them, how many bytes leave the card, what the host does with a downloaded frame, and how the clip ends.
+class FrameOutput {
+public:
+    FrameOutput(const SceneRun& run, const Clip& clip)
+        : video_base(run.o.out_dir + "/video/" + run.name + "/" + clip.name), run_(run), o_(run.o), clip_(clip.name), fps_(clip.fps) {}
+    virtual ~FrameOutput() = default;
+    virtual size_t result_bytes() const = 0;  // one frame as it leaves the card
+    virtual int open() = 0;                   // 0, or the exit status
+    virtual int check() { return 0; }         // before every frame: 0 while frames can still leave, else the exit status (reported)
+    virtual bool have(int i) const = 0;       // frame i is already there: it is not drawn again
+    virtual bool draws_result() const = 0;    // a frame of ONE sub-frame that needs no kernel is drawn where the result is expected, make_result() not called
+    virtual int make_result(void* result, float* ms) = 0;  // the kernel that turns the --motion-blur-frames sub-frames into the result
+    // the host's part: `pixels` (page-locked, to give back) hold frame i once `arrived` (an event, to destroy) has happened
+    virtual void submit(int i, uint8_t* pixels, void* arrived, EncoderPool& pool, PinnedFrames& pinned) = 0;
+    // every frame that was submitted is where it goes, and what follows a clip that is whole; `rc`: what the clip loop returned
+    virtual int close(int rc, EncoderPool& pool, std::chrono::steady_clock::time_point clip_start) = 0;
+    const std::string video_base;
+
+protected:
+    void report_on_disk(std::chrono::steady_clock::time_point clip_start) const { std::printf("Clip `%s` on disk after %.2f s\n", clip_.c_str(), seconds_since(clip_start)); }
+    const SceneRun& run_;
+    const Options& o_;
+    const std::string clip_;
+    const int fps_;
+};
+
+// anim/frame_<i>.png, encoded in any order by the pool; then ffmpeg reads them (encode_video)
+class PngOutput : public FrameOutput {
+public:
+    using FrameOutput::FrameOutput;
+    size_t result_bytes() const override { return run_.frame_bytes; }
+    int open() override {
+        make_dirs(anim_dir_);
+        return 0;
+    }
+    bool have(int i) const override { return exists(frame_name(i)); }
+    bool draws_result() const override { return o_.blur == 1; }  // one image: average_images would hand it back untouched
+    int make_result(void* result, float* ms) override {
+        return ptl_average_images(o_.device, run_.subframes.data(), o_.blur, result, run_.width, run_.height, nullptr, ms) == PTL_OK ? 0 : fail("average_images");
+    }
+    void submit(int i, uint8_t* pixels, void* arrived, EncoderPool& pool, PinnedFrames& pinned) override {
+        pool.submit([pixels, name = frame_name(i), width = run_.width, height = run_.height, arrived, &pinned] {
+            if (ptl_event_synchronize(arrived) != PTL_OK || ptl_png_write_level(name.c_str(), pixels, width, height, kFrameDeflateLevel) != PTL_OK)
+                std::fprintf(stderr, "\n%s\n", ptl_last_error());
+            ptl_event_destroy(arrived);
+            pinned.give(pixels);
+        });
+    }
+    int close(int rc, EncoderPool& pool, std::chrono::steady_clock::time_point clip_start) override {
+        pool.finish();  // joins the encoders: every frame file is on disk (and every pinned buffer is back)
+        if (rc != 0) return rc;
+        report_on_disk(clip_start);
+        if (o_.shards == 1 && o_.max_frames < 0) encode_video(o_, run_.name, clip_, fps_);
+        return 0;
+    }
+
+private:
+    std::string frame_name(int i) const { return anim_dir_ + "/frame_" + std::to_string(i) + ".png"; }
+    const std::string anim_dir_ = o_.out_dir + "/anim";
+};
+
+// One Y4M stream, written in frame order by a thread of its own.  (A stream is not resumed: it holds every frame, from frame 0.)
+class Y4mOutput : public FrameOutput {
+public:
+    Y4mOutput(const SceneRun& run, const Clip& clip, size_t max_pending) : FrameOutput(run, clip), writer_(1, max_pending) {}
+    size_t result_bytes() const override { return ptl_yuv420p10_frame_bytes(run_.width, run_.height); }
+    int open() override {
+        ::signal(SIGPIPE, SIG_IGN);  // an encoder that dies is a failed write (EPIPE), reported by the clip
+        // Where the stream goes: into an encoder when there is one and the clip is whole, else into a file an encoder can read later.
+        // The encoder is told nothing about scaling or pixel formats: the stream is what it encodes, the -color_* tags say what it is.
+        char header[128];
+        int header_len = ptl_y4m_header(run_.width, run_.height, fps_, header, sizeof header);
+        if (header_len < 0) return fail("y4m header");
+        std::vector<std::string> encode = {"ffmpeg", "-f", "yuv4mpegpipe", "-i", "-"};
+        for (const std::string& a : encoder_arguments(video_base + ".mov")) encode.push_back(a);
+        if (o_.max_frames < 0 && o_.shards == 1 && run_program({"ffmpeg", "-version"}, true) == 0) {
+            std::printf("Start ffmpeg to encode the frames as they arrive\n");
+            stream_.open_program(encode);
+        } else {
+            std::string command;
+            for (const std::string& a : encode) command += (command.empty() ? "" : " ") + (a == "-" ? clip_ + ".y4m" : a);
+            std::printf("Frames go to `%s.y4m` (%s)\n", video_base.c_str(), command.c_str());
+            stream_.open_file(video_base + ".y4m");
+        }
+        stream_.write(header, (size_t)header_len);
+        return 0;
+    }
+    int check() override {
+        if (stream_.failed()) std::fprintf(stderr, "\n%s\n", stream_.error().c_str());
+        return stream_.failed();
+    }
+    bool have(int) const override { return false; }
+    bool draws_result() const override { return false; }  // (one sub-frame is converted with n = 1)
+    int make_result(void* result, float* ms) override {
+        return ptl_average_to_yuv420p10(o_.device, run_.subframes.data(), o_.blur, result, run_.width, run_.height, nullptr, ms) == PTL_OK ? 0 : fail("average_to_yuv420p10");
+    }
+    void submit(int, uint8_t* pixels, void* arrived, EncoderPool&, PinnedFrames& pinned) override {  // frames of a stream arrive in order: one writer thread, jobs in submission order
+        writer_.submit([this, pixels, arrived, bytes = result_bytes(), &pinned] {
+            if (ptl_event_synchronize(arrived) != PTL_OK) stream_.fail(ptl_last_error());
+            stream_.write("FRAME\n", 6);
+            stream_.write(pixels, bytes);
+            ptl_event_destroy(arrived);
+            pinned.give(pixels);
+        });
+    }
+    int close(int rc, EncoderPool& pool, std::chrono::steady_clock::time_point clip_start) override {
+        writer_.finish();  // the stream has every frame that was submitted
+        pool.finish();     // the stills are on disk
+        const bool to_program = stream_.to_program();
+        const int status = stream_.close();  // end of stream: an encoder finishes the video now
+        if (to_program) std::printf("ffmpeg status: %d\nffmpeg time: %.2f s\n", status, stream_.seconds());
+        if (rc == 0 && stream_.failed()) {
+            std::fprintf(stderr, "%s\n", stream_.error().c_str());
+            rc = 1;
+        }
+        if (rc == 0 && status != 0) {
+            std::fprintf(stderr, "the encoder of clip `%s` failed (status %d)\n", clip_.c_str(), status);
+            rc = 1;
+        }
+        if (rc == 0) report_on_disk(clip_start);
+        return rc;
+    }
+
+private:
+    Y4mStream stream_;
+    EncoderPool writer_;  // (declared behind the stream: it finishes before the stream closes)
+};
+
+std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, size_t max_pending) {  // the ONE place that knows there are two
+    if (run.o.y4m) return std::make_unique<Y4mOutput>(run, clip, max_pending);
+    return std::make_unique<PngOutput>(run, clip);
+}
+
+// What lives as long as a clip.  Released in reverse order: the output (its writer finishes, its stream closes), the pool, the page-locked buffers.
+struct ClipRun {
+    PinnedFrames pinned;
+    EncoderPool pool;
+    std::unique_ptr<FrameOutput> out;
+};
+
+// where in the clip (0 .. 1) sub-frame j of frame i is: the shutter is open for half a frame.  Skipped and drawn frames step the camera
+// through the same times: a shard, or a resumed run, depends on it
+double subframe_time(int i, int j, int count, int blur) {
+    const double exposure = 0.5;
+    return ((double)i / count) + (double)j / blur / count * exposure;
+}
+
+// One of the clip's .start.png / .end.png stills: an RGBA8 sub-frame, through the clip's pool and, where one fits, its page-locked buffers
+// (they hold frames as they leave the card; a 4:2:0 one is smaller than an RGBA8 one: the two stills of such a clip take pageable memory)
+int write_still(const SceneRun& run, ClipRun& c, const void* device_frame, const std::string& name) {
+    uint8_t* pinned = run.frame_bytes <= run.result_bytes ? c.pinned.take() : nullptr;
+    auto pageable = std::make_shared<std::vector<uint8_t>>(pinned ? 0 : run.frame_bytes);
+    uint8_t* still = pinned ? pinned : pageable->data();
+    if (ptl_device_download(still, device_frame, run.frame_bytes, nullptr) != PTL_OK) return fail("download");
+    c.pool.submit([still, pinned, pageable, name, width = run.width, height = run.height, &frames = c.pinned] {
+        if (ptl_png_write(name.c_str(), still, width, height) != PTL_OK) std::fprintf(stderr, "\n%s\n", ptl_last_error());
+        if (pinned) frames.give(pinned);
+    });
+    return 0;
+}
+
+// render_animation (src/main.rs:1758-1873): every frame of the clip traced, made and handed to the output
+int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
+    const Options& o = run.o;
+    ptl_renderer* r = run.r.get();
+    FramePipeline& pipe = run.pipe;
+    FrameOutput& out = *c.out;
+    auto started = std::chrono::steady_clock::now();
+    int rejits_before = ptl_renderer_rejit_count(r);
+    if (o.skip_existing && exists(out.video_base + ".mov")) {
+        std::printf("Skip `%s/%s`, because it's already exists\n", run.name.c_str(), clip.name.c_str());
+        return 0;
+    }
+    make_dirs(dir_of(out.video_base));
+    if (int rc = out.open()) return rc;
+    int count = std::max(1, (int)((float)clip.duration * (float)clip.fps));  // ((duration_seconds * fps as f32) as usize).max(1)
+    double gpu_ms = 0.0;
+    long traced = 0, drawn_frames = 0;
+    ptl_frame frame{run.width, run.height, 0, 1, 0};
+    int last = o.max_frames >= 0 ? std::min(count, o.max_frames) : count;
+    const bool batched = batch_subframes(o), direct = out.draws_result();
+    for (int i = 0; i < last; ++i) {
+        if (int rc = out.check()) return rc;
+        if (i % o.shards != o.shard || out.have(i)) {
+            // Not ours (shard K of N takes every N-th frame) or already on disk.  The camera is stateful -- where it is relative
+            // to the portals depends on the path it took (teleport_camera) -- so the host step still runs for every sub-frame:
+            // a shard, or a resumed run, then sees exactly the cameras of an uninterrupted run.  (The reference skips the
+            // update as well, src/main.rs:1789-1792, and so renders a resumed clip from a different camera history.)
+            for (int j = 0; j < o.blur; ++j)
+                if (ptl_renderer_update(r, subframe_time(i, j, count, o.blur) * (double)(float)clip.duration, nullptr, nullptr) != PTL_OK) return fail("update");
+            continue;
+        }
+        int slot = (int)(drawn_frames++ % FramePipeline::kRing);
+        if (pipe.copy_pending[slot] && ptl_stream_wait_event(nullptr, pipe.copied[slot]) != PTL_OK) return fail("wait");  // GPU-side: slot is free
+        // The sub-frames go one behind the other on one stream.  Several kernel instances in flight (the library's "concurrent_draws") gave identical
+        // frames and NO gain here -- 1080p monoportal 0.0519 ms per sub-frame with one instance, 0.0522 with two, 0.0559 with four; 720p 0.031 -> 0.039;
+        // 4K aa 4 0.884 -> 0.885 / 0.908: the cross-stream event waits cost what the overlapped tails save (profiles/r04/concurrent_draws.jsonl)
+        for (int j = 0; j < o.blur; ++j) {
+            ptl_renderer_set_option(r, "aa_start", j);
+            if (ptl_renderer_update(r, subframe_time(i, j, count, o.blur) * (double)(float)clip.duration, nullptr, nullptr) != PTL_OK) return fail("update");
+            void* target = direct ? pipe.results[slot] : run.subframes[j];
+            float ms = 0.0f;
+            if (batched) {
+                // everything a draw does short of launching; the launch follows behind the last sub-frame, once for all of them
+                if (ptl_renderer_stage_slice(r, &frame, j) != PTL_OK) return fail("stage");
+                if (j == o.blur - 1 && ptl_renderer_draw_slices(r, &frame, o.blur, run.subframes[0], nullptr, (unsigned long long)run.width * run.height, nullptr, o.timing ? &ms : nullptr) != PTL_OK)
+                    return fail("render");
+            } else if (ptl_renderer_draw(r, &frame, target, nullptr, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) {
+                // (without --timing the launch is not waited for: the host evaluates the next sub-frame's uniforms while this one traces)
+                return fail("render");
+            }
+            gpu_ms += ms;
+            ++traced;
+            // the clip's stills: sub-frame 0 of the first frame (read behind the launch, which a batched frame has behind its last sub-frame), the
+            // last of the last.  The download is on the default stream, like the draws
+            if (i == 0 && j == (batched ? o.blur - 1 : 0))
+                if (int rc = write_still(run, c, batched ? run.subframes[0] : target, out.video_base + ".start.png")) return rc;
+            if (i == count - 1 && j == o.blur - 1)
+                if (int rc = write_still(run, c, target, out.video_base + ".end.png")) return rc;
+        }
+        if (!direct) {
+            float ms = 0.0f;
+            if (int rc = out.make_result(pipe.results[slot], o.timing ? &ms : nullptr)) return rc;
+            gpu_ms += ms;
+        }
+        // hand the finished frame to the copy stream and go on tracing; the host job waits for its own event
+        uint8_t* pixels = c.pinned.take();  // blocks while every buffer is still being encoded
+        void* arrived = nullptr;
+        if (ptl_event_record(pipe.produced, nullptr) != PTL_OK || ptl_stream_wait_event(pipe.copy_stream, pipe.produced) != PTL_OK ||
+            ptl_device_download_async(pixels, pipe.results[slot], run.result_bytes, pipe.copy_stream) != PTL_OK ||
+            ptl_event_record(pipe.copied[slot], pipe.copy_stream) != PTL_OK || ptl_event_create(pipe.device, &arrived) != PTL_OK ||
+            ptl_event_record(arrived, pipe.copy_stream) != PTL_OK)
+            return fail("download");
+        pipe.copy_pending[slot] = true;
+        out.submit(i, pixels, arrived, c.pool, c.pinned);
+        std::printf("\r%d/%d done      ", i, count);
+        std::fflush(stdout);
+    }
+    std::printf("\n");
+    char gpu_time[96] = "";
+    if (o.timing) std::snprintf(gpu_time, sizeof gpu_time, ", GPU %.1f ms (%.3f ms each),", gpu_ms, traced ? gpu_ms / traced : 0.0);
+    std::printf("Traced `%s/%s`: %ld sub-frames %dx%d%s submitted after %.2f s, kernel rebuilt %d times\n", run.name.c_str(), clip.name.c_str(), traced, run.width,
+                run.height, gpu_time, seconds_since(started), ptl_renderer_rejit_count(r) - rejits_before);
+    return 0;
+}
+
+// One clip: its buffers, pools and output for as long as it takes, released on every way out
+int render_clip(SceneRun& run, const Clip& clip) {
+    auto clip_start = std::chrono::steady_clock::now();
+    // frames in flight between download and encode: one per encoder thread, but no more than ~2 GB of page-locked memory
+    int in_flight = (int)std::max<size_t>(4, std::min<size_t>((size_t)run.threads + 2, ((size_t)2 << 30) / run.result_bytes));
+    ClipRun c{{run.result_bytes, in_flight}, {run.threads, (size_t)run.threads * 2}, make_output(run, clip, (size_t)in_flight)};
+    if (!c.pinned.ok()) return fail("pinned host memory");
+    return c.out->close(trace_clip(run, c, clip), c.pool, clip_start);
+}
+
+// Warm the code-object cache for the NEXT clip's specialised kernel while the current clip renders: a private copy of the scene
+// is taken through the same history (every clip initialised so far, with its overrides), then compiled for gfx950 without a
+// device.  When the main thread gets to that clip it generates the same source and finds the binary on disk; if the histories
+// ever disagree it just compiles as before.
+void prefetch_clip_kernel(const std::string& path, const std::vector<std::string>& history, const Options& o) {
+    ScenePtr scene = open_scene(path);
+    if (!scene) return;
+    for (const std::string& clip : history) {
+        if (ptl_scene_init_animation(scene.get(), clip.c_str()) != PTL_OK) return;
+        apply_clip_overrides(scene.get(), nullptr, clip, nullptr);
+    }
+    // (the mode switches are compiled into a specialised kernel: the compile-only renderer must have the ones the clip is drawn with)
+    const char* names[] = {"draw_side_by_side"};
+    const double values[] = {o.stereo ? 1.0 : 0.0};
+    ptl_renderer* built = nullptr;
+    if (ptl_renderer_create_with_options(scene.get(), -1, o.asset_root.c_str(), clip_flags(o, true), names, values, 1, &built, nullptr, 0) != PTL_OK) return;
+    RendererPtr r(built);
+    ptl_renderer_prebuild_teleport(r.get());  // the camera of a clip moves: its teleport queries need the other half of the build as well
+}
+
+// Specialised kernels of the clips to come are compiled ahead by a few background threads (in clip order), so a run of
+// many short clips is not a run of JIT waits; the main thread only waits if it reaches a clip before its binary is ready.
+class Prefetcher {
+public:
+    void start(const Options& o, const std::string& path, const std::vector<Clip>& clips) {  // (the first clip is compiled by the main thread right away)
+        done_.assign(clips.size(), 0);
+        if (o.specialize == 0 || clips.size() < 2) return;
+        int n_workers = (int)std::min<size_t>({(size_t)6, clips.size() - 1, (size_t)std::max(1u, std::thread::hardware_concurrency() / 4)});
+        next_ = 1;
+        for (int wk = 0; wk < n_workers; ++wk) workers_.emplace_back([this, &o, path, clips](std::stop_token stop) { work(stop, o, path, clips); });
+    }
+    // Before the main thread builds clip k: waits for its binary if a worker is at it.  true: nobody has started it -- it is the
+    // caller's to compile (the workers leave it alone from now on); false: it is in the cache.
+    bool wait_or_claim(size_t k) {
+        if (workers_.empty() || k < 1) return true;
+        std::unique_lock<std::mutex> lock(mu_);
+        cv_.wait(lock, [&] { return done_[k] || next_ <= k; });
+        if (!done_[k]) next_ = k + 1;
+        return !done_[k];
+    }
+
+private:
+    void work(std::stop_token stop, const Options& o, const std::string& path, const std::vector<Clip>& clips) {
+        for (;;) {
+            size_t k;
+            {
+                std::unique_lock<std::mutex> lock(mu_);
+                if (stop.stop_requested() || next_ >= clips.size()) return;
+                k = next_++;
+            }
+            std::vector<std::string> history;
+            for (size_t c = 0; c <= k; ++c) history.push_back(clips[c].name);
+            if (clips[k].specialise) prefetch_clip_kernel(path, history, o);
+            {
+                std::unique_lock<std::mutex> lock(mu_);
+                done_[k] = 1;
+            }
+            cv_.notify_all();
+        }
+    }
+    std::mutex mu_;
+    std::condition_variable cv_;
+    std::vector<char> done_;
+    size_t next_ = 0;
+    std::vector<std::jthread> workers_;  // (last: they are asked to stop, and joined, before what they use goes)
+};
+
+// which clips: the named ones (render_named_animations) or all, optionally filtered (render_all_animations)
+int clips_to_render(const SceneRun& run, std::vector<Clip>* todo) {  // 0, or the exit status
+    const Options& o = run.o;
+    std::vector<Clip> clips;
+    char name[256];
+    double duration = 0.0;
+    for (int k = 0; ptl_scene_animation(run.scene.get(), k, name, sizeof name, &duration) == PTL_OK; ++k) clips.push_back({name, duration});
+    if (o.clips.empty()) {
+        for (auto& c : clips)
+            if (o.starts_with.empty() || c.name.compare(0, o.starts_with.size(), o.starts_with) == 0) todo->push_back(c);
+    }
+    for (const std::string& want : split_list(o.clips)) {
+        auto it = std::find_if(clips.begin(), clips.end(), [&](auto& c) { return c.name == want; });
+        if (it == clips.end()) return scene_has_no(run.name, "animation", want);
+        todo->push_back(*it);
+    }
+    for (Clip& c : *todo) {
+        c.fps = o.fps;
+        apply_clip_overrides(nullptr, nullptr, c.name, &c.fps);
+        int count = std::max(1, (int)((float)c.duration * (float)c.fps));
+        double samples = (double)run.width * run.height * o.aa * count * o.blur;
+        c.specialise = o.specialize >= 0 ? o.specialize != 0 : samples >= 1e10;
+    }
+    return 0;
+}
+
+int render_scene(const Options& o, const std::string& path) {
+    SceneRun run(o, scene_link(path));
+    std::printf("Rendering scene %s\n", run.name.c_str());
+    run.scene = load_scene(path, run.name);
+    if (!run.scene) return 1;
+    ptl_scene* scene = run.scene.get();
+    std::vector<Clip> todo;
+    if (int rc = clips_to_render(run, &todo)) return rc;
+    // The un-baked kernel (every scene uniform a run-time value) is wanted NOW when a clip starts on it: the quick build.  When the first
+    // clip gets a clip-constant kernel anyway, the renderer is created on that one directly (the scene taken into the clip first, as the
+    // clip loop and prefetch_clip_kernel do) instead of building an un-baked kernel nothing would run on.  profiles/r03/video_*.log
+    bool start_baked = !todo.empty() && todo[0].specialise;
+    if (start_baked) {
+        if (ptl_scene_init_animation(scene, todo[0].name.c_str()) != PTL_OK) return fail("init_animation");
+        apply_clip_overrides(scene, nullptr, todo[0].name, nullptr);
+    }
+    run.r = create_renderer(scene, o.device, o, clip_flags(o, start_baked) | quick_jit_flag(o), "renderer",
+                            {{"aa_count", (double)o.aa}, {"render_depth", (double)o.depth}, {"draw_side_by_side", o.stereo ? 1.0 : 0.0}});
+    if (!run.r) return 1;
+    ptl_renderer* r = run.r.get();
+    ptl_renderer_set_option(r, "aa_count", o.aa);
+    ptl_renderer_set_option(r, "render_depth", o.depth);
+    ptl_renderer_set_option(r, "draw_side_by_side", o.stereo ? 1 : 0);
+    run.result_bytes = make_output(run, Clip{}, 1)->result_bytes();  // (an output that is never opened)
+    void* block = nullptr;
+    run.subframes.assign((size_t)std::max(1, o.blur), nullptr);
+    if (ptl_device_alloc(o.device, run.frame_bytes * run.subframes.size(), &block) != PTL_OK) return fail("alloc");
+    run.subframe_block.reset(block);
+    for (size_t j = 0; j < run.subframes.size(); ++j) run.subframes[j] = static_cast<char*>(block) + j * run.frame_bytes;
+    if (!run.pipe.create(o.device, run.result_bytes)) return fail("pipeline");
+    Prefetcher prefetch;
+    prefetch.start(o, path, todo);
+    for (size_t k = 0; k < todo.size(); ++k) {
+        Clip& clip = todo[k];
+        prefetch.wait_or_claim(k);  // either way the binary is there, or is built, when the renderer asks for it below
+        if (ptl_scene_init_animation(scene, clip.name.c_str()) != PTL_OK) return fail("init_animation");
+        if (ptl_renderer_update(r, 0.0, nullptr, nullptr) != PTL_OK) return fail("update");
+        ptl_renderer_set_option(r, "render_depth", o.depth);
+        apply_clip_overrides(scene, r, clip.name, &clip.fps);
+        if (ptl_renderer_set_option(r, "specialize_static", clip.specialise ? 1 : 0) != PTL_OK) return fail("specialize");
+        std::printf("Rendering animation %s, %zu/%zu\n", clip.name.c_str(), k + 1, todo.size());
+        if (int rc = render_clip(run, clip)) return rc;
+    }
+    return 0;
+}
+
+}  // namespace
+
+int render(const Options& o) {
+    auto total_start = std::chrono::steady_clock::now();
+    for (const std::string& scene_arg : split_list(o.scene))
+        if (int rc = render_scene(o, scene_file(scene_arg, o.scenes_dir))) return rc;
+    std::printf("Total render time: %.2f s\n", seconds_since(total_start));
+    return 0;
+}

@@ -90,7 +90,8 @@ def test_make_kernels_builds_the_code_object_without_scratch(pa, tmp_path):
 
 @pytest.mark.parametrize("extra,reason", [(["--frames", "y4m", "--shard", "0/2"], "a stream needs every frame, in order"),
                                           (["--shard", "1/3", "--frames", "y4m"], "a stream needs every frame, in order"),
-                                          (["--frames", "bogus"], "--frames png|y4m")])
+                                          (["--frames", "bogus"], "--frames png|y4m"),
+                                          (["--concurrent-draws", "2"], "unknown option")])  # (removed: a choice between two paths of which one was never better)
 def test_render_refuses_what_a_stream_cannot_do(pa, tmp_path, extra, reason):
     """Refused while the arguments are parsed: exit status 2, one line of reason, nothing rendered (this machine has no GPU to ask)."""
     exe = os.path.join(os.path.dirname(pa.__file__), "portal-amd")
