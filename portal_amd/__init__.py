@@ -649,6 +649,17 @@ class SceneRenderer:
                                                 C.c_void_p(stream or None), C.byref(ms) if timed else None), "ptl_renderer_draw_adaptive")
         return ms.value if timed else None
 
+    def refine_device(self, frame: Frame, list_ptr: int, count_ptr: int, out_rgba8: int = 0, out_rgba32f: int = 0, segments: int = 0, stream: int = 0,
+                      timed: bool = False):
+        """ptl_kernel_render_refine on the renderer's current kernel (layer 1; FLAG_REFINE renderers): shades the ``*count_ptr`` pixels of the
+        caller's own list with the uniforms the last draw left behind.  All pointers are DEVICE addresses; either output may be 0.
+        Returns the kernel time in ms when ``timed`` (waits for completion), else None."""
+        ms = C.c_float()
+        _check(lib().ptl_kernel_render_refine(lib().ptl_renderer_kernel(self._h), C.byref(frame), C.c_void_p(list_ptr or None), C.c_void_p(count_ptr or None),
+                                              C.c_void_p(out_rgba8 or None), C.c_void_p(out_rgba32f or None), C.c_void_p(segments or None),
+                                              C.c_void_p(stream or None), C.byref(ms) if timed else None), "ptl_kernel_render_refine")
+        return ms.value if timed else None
+
     def adaptive_result(self):
         """Device addresses (list, count) of the last adaptive draw: owned by the renderer, valid until the next adaptive draw."""
         lst, cnt = C.c_void_p(), C.c_void_p()

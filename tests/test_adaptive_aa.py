@@ -271,11 +271,11 @@ DRAW_CASES = [("basics", "baked"), ("monoportal", "baked"), ("portal_in_portal",
 _renderers = {}
 
 
-def _renderer(pa, scene_name, build, options=None):
+def _renderer(pa, scene_name, build, options=None, extra_flags=0):
     """One renderer per (scene, build): P, F and every adaptive frame come from the same one."""
-    key = (scene_name, build, tuple(sorted((options or {}).items())))
+    key = (scene_name, build, tuple(sorted((options or {}).items())), extra_flags)
     if key not in _renderers:
-        flags = pa.FLAG_REFINE | {"baked": BAKED(pa), "unspecialised": 0, "patterns": pa.FLAG_SPECIALIZE_PATTERNS}[build]
+        flags = pa.FLAG_REFINE | extra_flags | {"baked": BAKED(pa), "unspecialised": 0, "patterns": pa.FLAG_SPECIALIZE_PATTERNS}[build]
         r = pa.SceneRenderer(pa.Scene.from_file(pa.scene_path(scene_name)), device=0, flags=flags, options=options)
         r.set_option("render_depth", 12)
         _renderers[key] = r
@@ -355,6 +355,165 @@ def test_adaptive_draw_with_both_eyes_in_one_wave(gpu):
         left = np.array([(out["list"][c:c + 64] % w < w // 2).any() for c in range(0, out["count"], 64)])
         right = np.array([(out["list"][c:c + 64] % w >= w // 2).any() for c in range(0, out["count"], 64)])
         assert (left & right).any(), "no wave of the refine pass holds pixels of both eyes"
+
+
+# ---- the refine entry through layer 1: lists the caller made ---------------------------------------
+def _refine_grid_cap():
+    """`std::min<long long>(chunks, 2048)` of ptl_kernel_render_refine (portal_amd/csrc/host/kernel.cpp): the workgroups of a refine launch
+    at most, 256 entries each and trip.  Read from the source, so a changed cap fails the second-trip test instead of leaving it vacuous."""
+    src = open(os.path.join(ROOT, "portal_amd", "csrc", "host", "kernel.cpp")).read()
+    m = re.findall(r"const unsigned grid = \(unsigned\)std::min<long long>\(chunks, (\d+)\);", src)
+    assert len(m) == 1, "ptl_kernel_render_refine no longer spells its grid as min(chunks, N)"
+    return int(m[0])
+
+
+def test_refine_grid_cap_is_what_the_second_trip_test_crosses():
+    assert _refine_grid_cap() == 2048
+    assert 1024 * 513 == 525312 > 2048 * 256 == 524288 and (1024 * 513 + 255) // 256 > 2048
+
+
+GUARD_PIXELS = 16  # behind both outputs: entry W*H, if it were not skipped, would land on the first of them
+
+
+def _cuda_words(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32).copy()).cuda()
+
+
+def _refine_through_layer_one(pa, r, w, h, entries, count, start8=None, start32=None, segments=False):
+    """ptl_kernel_render_refine on `entries` (uint32, all uploaded) with *count = `count`, over device copies of the given start frames (None: that
+    output is null).  -> (rgba8 or None, rgba32f bits or None, segment count or None); the guard pixels behind the outputs and the words
+    behind the count must survive."""
+    import torch
+
+    lst = _cuda_words(np.concatenate([entries.astype(np.uint32), np.full(4, 0xDEADBEEF, np.uint32)]))
+    cnt = _cuda_words(np.array([count, 0x5A5A5A5A, 0x5A5A5A5A, 0x5A5A5A5A], np.uint32))
+    d8 = _cuda_words(np.concatenate([_bits(start8).reshape(-1), np.full(GUARD_PIXELS, 0xA5A5A5A5, np.uint32)])) if start8 is not None else None
+    d32 = _cuda_words(np.concatenate([_bits(start32).reshape(-1), np.full(4 * GUARD_PIXELS, 0xA5A5A5A5, np.uint32)])) if start32 is not None else None
+    seg = torch.zeros(2, dtype=torch.int64, device="cuda") if segments else None
+    r.refine_device(pa.Frame(w, h, 0, 1, 0), lst.data_ptr(), cnt.data_ptr(), out_rgba8=d8.data_ptr() if d8 is not None else 0,
+                    out_rgba32f=d32.data_ptr() if d32 is not None else 0, segments=seg.data_ptr() if segments else 0,
+                    stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(lst.cpu().numpy().view(np.uint32)[:-4], entries) and np.array_equal(cnt.cpu().numpy().view(np.uint32)[1:], [0x5A5A5A5A] * 3)
+    out8 = out32 = None
+    if d8 is not None:
+        words = d8.cpu().numpy().view(np.uint32)
+        assert (words[w * h:] == 0xA5A5A5A5).all(), "RGBA8 written behind the frame"
+        out8 = words[: w * h].view(np.uint8).reshape(h, w, 4)
+    if d32 is not None:
+        words = d32.cpu().numpy().view(np.uint32)
+        assert (words[4 * w * h:] == 0xA5A5A5A5).all(), "RGBA32F written behind the frame"
+        out32 = words[: 4 * w * h].reshape(h, w, 4)
+    if segments:
+        assert int(seg[1].item()) == 0
+    return out8, out32, int(seg[0].item()) if segments else None
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene_name,build", [("basics", "baked"), ("monoportal", "unspecialised")], ids=["basics-baked", "monoportal-unspecialised"])
+def test_refine_entry_shades_exactly_the_callers_list(gpu, scene_name, build):
+    """ptl_kernel_render_refine with lists no classification kernel wrote, at 70x37 over device copies of P: duplicates, entries outside the
+    frame (W*H and 0xFFFFFFFF: skipped, as device/ptl_refine_entry.h promises), a count below the buffer's length, a count of 0, one
+    output null.  The result is where(listed, F, P) in bytes and float bits.  The full list is 3 885 entries for a grid of 11
+    workgroups: the stride loop takes a second trip here as well."""
+    pa = gpu
+    w, h = 70, 37
+    pixels = w * h
+    r = _renderer(pa, scene_name, build)
+    p, f = _plain_and_full(r, w, h)  # F last: the kernel's `_aa_count` is 4, its resolution 70x37
+    p8, f8, p32, f32 = p["rgba8"], f["rgba8"], _bits(p["rgba32f"]), _bits(f["rgba32f"])
+    differs = (f8 != p8).any(axis=2) | (f32 != p32).any(axis=2)
+    rng = np.random.default_rng(7037)
+    half = rng.permutation(pixels)[: pixels // 2].astype(np.uint32)
+    body = rng.permutation(np.concatenate([half, half]))  # a shuffled half of the pixels, each of them twice
+    outside = np.where(np.arange(body.size // 2) % 2 == 0, pixels, 0xFFFFFFFF).astype(np.uint32)
+    entries = np.stack([body[0::2], body[1::2], outside], axis=1).reshape(-1)  # every third entry names no pixel
+    assert entries.size == 3885 > ((pixels + 255) // 256) * 256 and (entries == pixels).sum() > 600 and (entries == 0xFFFFFFFF).sum() > 600
+    assert np.array_equal(np.unique(entries[entries < pixels]), np.sort(half)) and (np.bincount(entries[entries < pixels], minlength=pixels).max() == 2)
+
+    def expect(count):
+        named = entries[:count]
+        listed = np.zeros(pixels, bool)
+        listed[named[named < pixels]] = True
+        listed = listed.reshape(h, w)
+        return listed, ar.select(listed, f8, p8), ar.select(listed, f32, p32)
+
+    for count in (entries.size, entries.size // 2, 0):
+        listed, want8, want32 = expect(count)
+        stats = dict(count=count, listed=int(listed.sum()), listed_and_different=int((listed & differs).sum()), unlisted_and_different=int((~listed & differs).sum()))
+        print(stats)
+        if count:  # shading nothing, or everything, must not pass
+            assert stats["listed_and_different"] >= 10 and stats["unlisted_and_different"] >= 10, stats
+            assert (entries[:count] >= pixels).any()
+        else:
+            assert not listed.any()
+        if count == entries.size // 2:  # some pixel that differs is named only beyond the count: it stays P
+            all_listed = expect(entries.size)[0]
+            assert (all_listed & ~listed & differs).sum() >= 5
+        out8, out32, _ = _refine_through_layer_one(pa, r, w, h, entries, count, start8=p8, start32=p32)
+        bad = np.argwhere((out8 != want8).any(axis=2) | (out32 != want32).any(axis=2))
+        assert bad.size == 0, f"count {count}: {len(bad)} pixels differ, first (y, x) = {bad[0].tolist()}, listed there: {bool(listed[tuple(bad[0])])}"
+    listed, want8, want32 = expect(entries.size)
+    out8, out32, _ = _refine_through_layer_one(pa, r, w, h, entries, entries.size, start8=p8)  # RGBA8 only
+    assert out32 is None and np.array_equal(out8, want8)
+    out8, out32, _ = _refine_through_layer_one(pa, r, w, h, entries, entries.size, start32=p32)  # float only
+    assert out8 is None and np.array_equal(out32, want32)
+    again = r.draw(w, h, rgba8=True, rgba32f=True)  # the plain draw path is what it was
+    assert np.array_equal(again["rgba8"], f8) and np.array_equal(_bits(again["rgba32f"]), f32)
+
+
+@pytest.mark.gpu
+def test_refine_entry_takes_a_second_trip_over_a_long_list(gpu):
+    """1024x513: 525 312 pixels, above the 2 048 workgroups x 256 entries of a refine launch (`std::min<long long>(chunks, 2048)` in
+    ptl_kernel_render_refine), so `first += gridDim.x * 256` goes round again.  With T = -1 every pixel is listed: the adaptive frame is the
+    plain aa-4 draw bit for bit; the same through layer 1 with a permuted list of all pixels over frames of another content."""
+    pa = gpu
+    w, h = 1024, 513
+    pixels = w * h
+    r = _renderer(pa, "basics", "baked")
+    r.set_option("aa_count", 4)
+    f = r.draw(w, h, rgba8=True, rgba32f=True)
+    f8, f32 = f["rgba8"], _bits(f["rgba32f"])
+    out = r.draw_adaptive(w, h, threshold=-1, rgba32f=True)
+    assert out["count"] == pixels == 525312 and out["count"] > _refine_grid_cap() * 256 and _refine_grid_cap() == 2048
+    assert np.array_equal(np.sort(out["list"]), np.arange(pixels, dtype=np.uint32))
+    assert np.array_equal(out["rgba8"], f8) and np.array_equal(_bits(out["rgba32f"]), f32)
+    entries = np.random.default_rng(513).permutation(pixels).astype(np.uint32)
+    start8 = np.full((h, w, 4), 0x3C, np.uint8)
+    start32 = np.full((h, w, 4), 0x7FC00000, np.uint32)
+    assert (start8 != f8).any(axis=2).all() and (start32 != f32).any(axis=2).all()  # every pixel has to be written
+    out8, out32, _ = _refine_through_layer_one(pa, r, w, h, entries, pixels, start8=start8, start32=start32)
+    assert np.array_equal(out8, f8) and np.array_equal(out32, f32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene_name,build", [("basics", "baked"), ("monoportal", "unspecialised")], ids=["basics-baked", "monoportal-unspecialised"])
+def test_refine_entry_counts_the_segments_of_its_list(gpu, scene_name, build):
+    """Under PTL_COUNT_SEGMENTS the refine entry reduces the lanes' trip counts with __shfl_down behind a loop whose lanes `continue`;
+    ptl_renderer_draw_adaptive never passes a counter.  A pixel's trips do not depend on the lanes around it: a permutation of all pixels
+    counts what the render entry counts for the aa-4 frame, two disjoint halves (lists that end inside a wave) add up to it."""
+    pa = gpu
+    w, h = 70, 37
+    pixels = w * h
+    r = _renderer(pa, scene_name, build, extra_flags=pa.FLAG_COUNT_SEGMENTS)
+    r.set_option("aa_count", 4)
+    f = r.draw(w, h, rgba8=True, segments=True)  # last draw: `_aa_count` 4
+    total = f["segments"]
+    assert total > 4 * pixels  # at least one trip per sample
+    entries = np.random.default_rng(3770).permutation(pixels).astype(np.uint32)
+    start8 = np.full((h, w, 4), 0x3C, np.uint8)
+    out8, _, counted = _refine_through_layer_one(pa, r, w, h, entries, pixels, start8=start8, segments=True)
+    assert counted == total and np.array_equal(out8, f["rgba8"])
+    first, second = entries[: pixels // 2], entries[pixels // 2:]
+    assert first.size % 64 and second.size % 64 and not np.intersect1d(first, second).size
+    a = _refine_through_layer_one(pa, r, w, h, first, first.size, start8=start8, segments=True)[2]
+    b = _refine_through_layer_one(pa, r, w, h, second, second.size, start8=start8, segments=True)[2]
+    assert 0 < a < total and 0 < b < total and a + b == total, (a, b, total)
+    # ... and entries that name no pixel count nothing
+    padded = np.concatenate([first, np.full(100, pixels, np.uint32), np.full(100, 0xFFFFFFFF, np.uint32)])
+    assert _refine_through_layer_one(pa, r, w, h, padded, padded.size, start8=start8, segments=True)[2] == a
 
 
 @pytest.mark.gpu

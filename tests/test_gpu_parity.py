@@ -354,6 +354,63 @@ def test_average_images_kernel_matches_oracle(gpu, n):
     assert np.array_equal(out.cpu().numpy(), want)
 
 
+_stride_cases = {}
+
+
+def _stride_case(w, h, n):
+    """Sub-frames and the reference frame, computed once per (shape, n) and shared by the caps."""
+    from oracle import postprocess as pp
+
+    if (w, h, n) not in _stride_cases:
+        rng = np.random.default_rng(4000 + 100 * n + w)
+        frames = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(n)]
+        want = pp.average_images(frames) if n > 1 else np.concatenate([frames[0][..., :3], np.full((h, w, 1), 255, np.uint8)], axis=2)
+        _stride_cases[w, h, n] = (frames, want)
+    return _stride_cases[w, h, n]
+
+
+@pytest.mark.parametrize("n", [1, 3, 65])
+@pytest.mark.parametrize("cap", [1, 3])
+@pytest.mark.parametrize("w,h", [(244, 135), (13, 11), (1023, 7)])
+def test_average_images_grid_stride_with_the_cap_knob(gpu, monkeypatch, w, h, cap, n):
+    """The grid-stride loop of ptl_average_all against the reference (at 4K, where the shipped grid strides, only properties are checked):
+    PTL_AVERAGE_IMAGES_GRID_CAP, read by launch_over_subframes at each call, shrinks the grid to 1 and 3 workgroups.  244x135 is 8 235
+    vectors (11 trips of 3 workgroups, the last ends inside a wave), 1023x7 is 1 790 vectors and one tail pixel (3 trips of 3 workgroups, 7 of one),
+    13x11 is 35 vectors and three tail pixels in ONE workgroup with or without the knob: the tail beside a capped grid, no stride.
+    Equal to the reference and to the same call with the shipped grid, nothing written behind the frame."""
+    import ctypes as C
+
+    import torch
+
+    pa = gpu
+    knob = "PTL_AVERAGE_IMAGES_GRID_CAP"
+    libc = C.CDLL(None)
+    libc.getenv.restype, libc.getenv.argtypes = C.c_char_p, [C.c_char_p]
+    frames, want = _stride_case(w, h, n)
+    dev = [torch.from_numpy(f).cuda() for f in frames]
+    vectors = w * h // 4
+    if (w, h) != (13, 11):
+        assert vectors > 2 * cap * 256, "the knob makes no third trip at this shape"
+    assert (vectors, (w * h) % 4) == {(244, 135): (8235, 0), (13, 11): (35, 3), (1023, 7): (1790, 1)}[w, h]
+
+    def run():
+        guard = torch.full((h * w * 4 + 64,), 77, dtype=torch.uint8, device="cuda")
+        pa.average_images_device([d.data_ptr() for d in dev], guard.data_ptr(), w, h, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        host = guard.cpu().numpy()
+        assert (host[h * w * 4:] == 77).all(), "written behind the frame"
+        return host[: h * w * 4].reshape(h, w, 4)
+
+    monkeypatch.delenv(knob, raising=False)
+    assert libc.getenv(knob.encode()) is None
+    shipped = run()
+    monkeypatch.setenv(knob, str(cap))
+    assert libc.getenv(knob.encode()) == str(cap).encode()
+    got = run()
+    assert np.array_equal(got, want)
+    assert np.array_equal(got, shipped)
+
+
 def test_average_images_full_size_properties(gpu):
     """4K, 4 sub-frames: averaging identical frames is the identity on RGB; permuting the inputs changes nothing."""
     import torch

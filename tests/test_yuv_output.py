@@ -129,6 +129,117 @@ def test_reference_helper_against_the_real_valued_definition():
     assert np.array_equal(cb[0], np.minimum(1023, (131458 * s + (512 << 19) + (1 << 18)) >> 19))
 
 
+CORNERS = [(r, g, b) for r in (0, 255) for g in (0, 255) for b in (0, 255)]  # the eight corners of the RGB cube
+BLUE, RED, YELLOW, CYAN = (0, 0, 255), (255, 0, 0), (255, 255, 0), (0, 255, 255)
+SATURATION_SHAPES = {"bands-128x4": (128, 4), "flat-16x2": (16, 2), "flat-5x3": (5, 3), "flat-1x1": (1, 1)}  # the first two take the block path
+
+
+def _flat_frame(w, h, rgb, alpha=255):
+    return np.tile(np.array(tuple(rgb) + (alpha,), np.uint8), (h, w, 1))
+
+
+def _corner_bands(w=128, h=4):
+    """Eight flat bands of 16 columns, one cube corner each: chroma sample i of band k sees one colour for 8k < i < 8k + 8."""
+    frame = np.empty((h, w, 4), np.uint8)
+    for k, rgb in enumerate(CORNERS):
+        frame[:, 16 * k: 16 * (k + 1)] = rgb + (255,)
+    return frame
+
+
+def _saturation_inputs(shape):
+    """[(label, sub-frames)] of one shape: every saturated frame as n = 1 and as 2 and 3 identical sub-frames (the mean of n equal squares
+    is that square: the averaged frame is the frame), and white + black, which averages to code 180."""
+    w, h = SATURATION_SHAPES[shape]
+    singles = [("bands", _corner_bands(w, h))] if shape.startswith("bands") else [(str(rgb), _flat_frame(w, h, rgb)) for rgb in CORNERS]
+    inputs = [(f"{label} n={n}", [frame] * n) for label, frame in singles for n in (1, 2, 3)]
+    return inputs + [("white+black", [_flat_frame(w, h, (255, 255, 255)), _flat_frame(w, h, (0, 0, 0))])]
+
+
+def _averaged(frames):
+    from oracle import postprocess as pp
+
+    return pp.average_images(frames) if len(frames) > 1 else frames[0]
+
+
+def test_saturated_colours_reach_both_ends_of_the_chroma_range():
+    """The clamp of the contract is needed and the inputs of test_saturated_colours_on_the_gpu reach it: six taps of pure blue give an
+    unclamped Cb of 1024, pure red a Cr of 1024; the clamped planes hold 1023; yellow gives Cb 0 and cyan Cr 0 (accumulator 523 280, just
+    above the shift).  A reference without the clamp differs from the reference on these inputs, so a kernel without it would too."""
+    for rgb in CORNERS:
+        frame = _flat_frame(2, 2, rgb)
+        _, cb, cr = yr.yuv_planes(frame)
+        _, ucb, ucr = yr.yuv_planes(frame, clamp=False)
+        assert cb.shape == (1, 1) and 0 <= cb[0, 0] <= 1023 and 0 <= cr[0, 0] <= 1023
+        assert (ucb[0, 0] == 1024) == (rgb == BLUE) and (ucr[0, 0] == 1024) == (rgb == RED), rgb
+        assert ucb[0, 0] <= 1024 and ucr[0, 0] <= 1024 and ucb[0, 0] >= 0 and ucr[0, 0] >= 0
+        assert cb[0, 0] == min(1023, ucb[0, 0]) and cr[0, 0] == min(1023, ucr[0, 0])
+        assert (cb[0, 0] == 0) == (rgb == YELLOW) and (cr[0, 0] == 0) == (rgb == CYAN), rgb
+        if rgb == YELLOW:  # S_R = S_G = 2040, S_B = 0: what is left of the bias
+            assert (512 << 19) + (1 << 18) - (30123 + 101335) * 2040 == 523280 and 523280 >> 19 == 0
+        if rgb in (BLUE, RED):
+            assert (cb if rgb == BLUE else cr)[0, 0] == 1023
+    for shape, (w, h) in SATURATION_SHAPES.items():
+        reached = {"cb_clamp": 0, "cr_clamp": 0, "cb_zero": 0, "cr_zero": 0}
+        for label, frames in _saturation_inputs(shape):
+            a = _averaged(frames)
+            if len(frames) > 1 and label != "white+black":
+                assert np.array_equal(a[..., :3], frames[0][..., :3]), (shape, label)  # identical sub-frames: exact
+            if label == "white+black":
+                assert (a[..., :3] == 180).all()
+            _, cb, cr = yr.yuv_planes(a)
+            _, ucb, ucr = yr.yuv_planes(a, clamp=False)
+            clamped = (ucb == 1024).any() or (ucr == 1024).any()
+            assert clamped == (label != "white+black" and (shape.startswith("bands") or label.startswith((str(BLUE), str(RED))))), (shape, label)
+            without = b"".join(p.astype("<u2").tobytes() for p in yr.yuv_planes(a, clamp=False))
+            assert (without != yr.yuv_reference(a)) == clamped, (shape, label)  # the guard: dropping the clamp changes the payload
+            reached["cb_clamp"] += int((ucb == 1024).sum())
+            reached["cr_clamp"] += int((ucr == 1024).sum())
+            reached["cb_zero"] += int((cb == 0).sum())
+            reached["cr_zero"] += int((cr == 0).sum())
+        assert all(reached.values()), (shape, reached)
+    # the bands: the seven interior samples of a band (and sample 0 of the first, whose left tap clamps to the frame) see one colour
+    _, ucb, ucr = yr.yuv_planes(_corner_bands(), clamp=False)
+    k_blue, k_red = CORNERS.index(BLUE), CORNERS.index(RED)
+    assert (ucb[:, 8 * k_blue + 1: 8 * k_blue + 8] == 1024).all() and (ucr[:, 8 * k_red + 1: 8 * k_red + 8] == 1024).all()
+    assert int((ucb == 1024).sum()) == 2 * 7 and int((ucr == 1024).sum()) == 2 * 7
+
+
+def _shipped_grid_cap():
+    """`long cap = 256 * 16;` of launch_over_subframes (portal_amd/csrc/host/postprocess.cpp): the workgroups a post-process launch gets at
+    most.  The tests that cross it read it from the source, so a changed cap fails them instead of leaving them vacuous."""
+    src = open(os.path.join(ROOT, "portal_amd", "csrc", "host", "postprocess.cpp")).read()
+    m = re.findall(r"long cap = (\d+) \* (\d+);", src)
+    assert len(m) == 1, "launch_over_subframes no longer spells its grid cap as `long cap = A * B;`"
+    return int(m[0][0]) * int(m[0][1])
+
+
+def _yuv_lanes(w, h):
+    """The lanes ptl_average_to_yuv420p10 asks for: 8x2 blocks on the block path, chroma samples on the general path."""
+    return (w // 8) * (h // 2) if w % 16 == 0 and h % 2 == 0 else ((w + 1) // 2) * ((h + 1) // 2)
+
+
+CAP_CROSSING = {"general-2050x2049": (2050, 2049), "block-4096x4112": (4096, 4112)}
+KNOB = "PTL_AVERAGE_IMAGES_GRID_CAP"
+KNOB_SHAPES = {"block-256x134": (256, 134), "general-244x135": (244, 135)}
+
+
+def test_stride_shapes_cross_the_grid_cap():
+    """The shapes of the GPU stride tests against the cap in the host code: two that cross the shipped one by less than a grid, and trips
+    of the knob's caps that end inside a wave on the block path."""
+    cap = _shipped_grid_cap()
+    assert cap == 4096
+    for name, (w, h) in CAP_CROSSING.items():
+        assert (name.startswith("block")) == (w % 16 == 0 and h % 2 == 0)
+        assert cap * 256 < _yuv_lanes(w, h) < 2 * cap * 256, name  # a second trip that ends inside the grid
+    assert _yuv_lanes(2050, 2049) == 1050625 and _yuv_lanes(4096, 4112) == 1052672
+    assert _yuv_lanes(4096, 4096) == cap * 256  # (test_every_colour_once fills the grid exactly: one trip)
+    assert _yuv_lanes(256, 134) == 2144 and _yuv_lanes(244, 135) == 8296
+    for knob in (1, 3):
+        for w, h in KNOB_SHAPES.values():
+            assert _yuv_lanes(w, h) > 2 * knob * 256  # at least three trips
+    assert 2144 % (3 * 256) == 608 and 608 % 64 == 32 and 2144 % 256 == 96 and 96 % 64 == 32  # the last trip ends in the middle of a wave
+
+
 # ---------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------
@@ -230,6 +341,103 @@ def test_every_colour_once(gpu):
     _assert_same_payload(got, yr.yuv_reference(frame), w, h, "every colour")
     y, cb, cr = yr.split_planes(got, w, h)
     assert y.min() == 0 and y.max() == 1023 and cb.max() <= 1023 and cr.max() <= 1023
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", list(SATURATION_SHAPES))
+def test_saturated_colours_on_the_gpu(gpu, shape):
+    """The min(1023, .) of ptl_cb10 / ptl_cr10 and the zero end, on both paths: flat cube corners (the bands and the 16x2 frames take the
+    block path, where every left tap of the 16x2 frames clamps and lane 0 loads its own left column; 5x3 and 1x1 the general one), as one
+    sub-frame, as identical sub-frames and as white + black.  No random or every-colour frame gets there (unclamped Cb <= 1011, Cr <= 1007)."""
+    w, h = SATURATION_SHAPES[shape]
+    assert (w % 16 == 0 and h % 2 == 0) == (shape in ("bands-128x4", "flat-16x2"))
+    reached = {"cb_clamp": 0, "cr_clamp": 0, "cb_zero": 0, "cr_zero": 0}
+    for label, frames in _saturation_inputs(shape):
+        a = _averaged(frames)
+        got = _convert(gpu, frames, w, h)
+        _assert_same_payload(got, yr.yuv_reference(a), w, h, f"{shape} {label}")
+        _, cb, cr = yr.split_planes(got, w, h)
+        _, ucb, ucr = yr.yuv_planes(a, clamp=False)
+        assert ucb.max() <= 1024 and ucr.max() <= 1024
+        assert np.array_equal(cb == 1023, ucb >= 1023) and np.array_equal(cr == 1023, ucr >= 1023), (shape, label)
+        assert (cb[ucb == 1024] == 1023).all() and (cr[ucr == 1024] == 1023).all()
+        assert cb.max() <= 1023 and cr.max() <= 1023
+        reached["cb_clamp"] += int((ucb == 1024).sum())
+        reached["cr_clamp"] += int((ucr == 1024).sum())
+        reached["cb_zero"] += int((cb == 0).sum())
+        reached["cr_zero"] += int((cr == 0).sum())
+        if label == "white+black":
+            y, _, _ = yr.split_planes(got, w, h)
+            assert (a[..., :3] == 180).all() and (y == (262915 * 180 + 32768) >> 16).all() and (cb == 512).all() and (cr == 512).all()
+    assert all(reached.values()), (shape, reached)  # not vacuous: the clamp was reached (unclamped 1024) in both planes, and so was 0
+
+
+def _c_getenv(name):
+    """What std::getenv of the library sees (monkeypatch.setenv goes through os.environ, which calls putenv)."""
+    import ctypes as C
+
+    libc = C.CDLL(None)
+    libc.getenv.restype, libc.getenv.argtypes = C.c_char_p, [C.c_char_p]
+    return libc.getenv(name.encode())
+
+
+_knob_cases = {}
+
+
+def _knob_case(kind, n):
+    """Sub-frames, the reference payload: computed once per (shape, n), shared by the caps, never modified."""
+    from oracle import postprocess as pp
+
+    if (kind, n) not in _knob_cases:
+        w, h = KNOB_SHAPES[kind]
+        rng = np.random.default_rng(3000 + 10 * n + len(kind))
+        frames = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(n)]
+        _knob_cases[kind, n] = (frames, yr.yuv_reference(pp.average_images(frames) if n > 1 else frames[0]))
+    return _knob_cases[kind, n]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 3, 65])
+@pytest.mark.parametrize("cap", [1, 3])
+@pytest.mark.parametrize("kind", list(KNOB_SHAPES))
+def test_grid_stride_with_the_cap_knob(gpu, monkeypatch, kind, cap, n):
+    """`for (b = first; b < n_blocks; b += stride)` of ptl_yuv_frame going round more than twice, on both paths and both entries (n = 65: the
+    pointer table): PTL_AVERAGE_IMAGES_GRID_CAP, which launch_over_subframes reads at each call, shrinks the grid to 1 and 3 workgroups.
+    256x134 is 2 144 blocks: with 3 workgroups the third trip ends after 608 lanes, in the middle of a wave, and the __shfl_up of the
+    block path still finds its lower neighbour.  Equal to the reference and to the same call with the shipped grid."""
+    w, h = KNOB_SHAPES[kind]
+    frames, want = _knob_case(kind, n)
+    monkeypatch.delenv(KNOB, raising=False)
+    assert _c_getenv(KNOB) is None
+    shipped = _convert(gpu, frames, w, h)
+    monkeypatch.setenv(KNOB, str(cap))
+    assert _c_getenv(KNOB) == str(cap).encode()
+    lanes = _yuv_lanes(w, h)
+    assert lanes > 2 * cap * 256 and lanes <= _shipped_grid_cap() * 256  # the knob makes the trips, not the shape
+    got = _convert(gpu, frames, w, h)  # (checks the guard bytes behind the frame)
+    _assert_same_payload(got, want, w, h, f"{kind} cap={cap} n={n}")
+    assert got == shipped
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", list(CAP_CROSSING))
+def test_grid_stride_at_the_shipped_cap(gpu, monkeypatch, kind):
+    """The second trip of the grid-stride loop as an 8K clip runs it, with no knob: launch_over_subframes caps the grid at
+    `long cap = 256 * 16` workgroups = 2^20 lanes, 2050x2049 has 1 050 625 chroma samples (general path) and 4096x4112 has 1 052 672
+    blocks (block path).  n = 2, against the reference."""
+    import torch
+    from oracle import postprocess as pp
+
+    w, h = CAP_CROSSING[kind]
+    monkeypatch.delenv(KNOB, raising=False)
+    assert _c_getenv(KNOB) is None
+    lanes = _yuv_lanes(w, h)
+    assert _shipped_grid_cap() == 4096 and lanes > 4096 * 256
+    g = torch.Generator(device="cuda").manual_seed(w)
+    frames = [torch.randint(0, 256, (h, w, 4), dtype=torch.uint8, device="cuda", generator=g) for _ in range(2)]
+    got = _convert(gpu, frames, w, h)
+    want = yr.yuv_reference(pp.average_images([f.cpu().numpy() for f in frames]))
+    _assert_same_payload(got, want, w, h, kind)
 
 
 @pytest.mark.gpu

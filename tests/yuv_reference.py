@@ -15,8 +15,9 @@ import numpy as np
 KR, KG, KB = 0.2126, 0.7152, 0.0722
 
 
-def yuv_planes(rgba8):
-    """(H, W, >=3) uint8 -> (Y (H, W), Cb (ch, cw), Cr (ch, cw)) as int32."""
+def yuv_planes(rgba8, clamp=True):
+    """(H, W, >=3) uint8 -> (Y (H, W), Cb (ch, cw), Cr (ch, cw)) as int32.  clamp=False: the chroma values before min(1023, .) -- not
+    what the kernel writes; tests use it to show that an input reaches the clamp (pure blue and pure red give 1024)."""
     a = np.asarray(rgba8)[..., :3].astype(np.int32)
     h, w = a.shape[:2]
     y = (55896 * a[..., 0] + 188037 * a[..., 1] + 18982 * a[..., 2] + 32768) >> 16
@@ -26,8 +27,10 @@ def yuv_planes(rgba8):
     cols = 2 * np.arange(cw)
     s = two_rows[:, np.maximum(cols - 1, 0)] + 2 * two_rows[:, cols] + two_rows[:, np.minimum(cols + 1, w - 1)]  # (ch, cw, 3), 0..2040
     bias = (512 << 19) + (1 << 18)
-    cb = np.minimum(1023, (-30123 * s[..., 0] - 101335 * s[..., 1] + 131458 * s[..., 2] + bias) >> 19)
-    cr = np.minimum(1023, (131458 * s[..., 0] - 119404 * s[..., 1] - 12054 * s[..., 2] + bias) >> 19)
+    cb = (-30123 * s[..., 0] - 101335 * s[..., 1] + 131458 * s[..., 2] + bias) >> 19
+    cr = (131458 * s[..., 0] - 119404 * s[..., 1] - 12054 * s[..., 2] + bias) >> 19
+    if clamp:
+        cb, cr = np.minimum(1023, cb), np.minimum(1023, cr)
     return y, cb, cr
 
 
