@@ -258,6 +258,7 @@ int ptl_scene_texture(ptl_scene* s, int index, char* name, size_t name_cap, char
 #define PTL_FLAG_MATERIAL_TABLE_LDS (1u << 26)
 #define PTL_FLAG_MATERIAL_TABLE_SCALAR (1u << 27)
 #define PTL_FLAG_REFINE (1u << 28)
+#define PTL_FLAG_REFINE_SLICES (1u << 29)
 
 /* Scene::generate_shader_code: returns a malloc'ed NUL-terminated HIP C++ source (free with
  * ptl_free).  flags: bit0 = bake Bool/Int scene uniforms as literals, bit1 = count segments,
@@ -570,10 +571,57 @@ int ptl_kernel_render_refine(ptl_kernel* k, const ptl_frame* frame, const void* 
  * ptl_renderer_adaptive_times hands out the three).  Whole frames only; frame groups and slices (PTL_FLAG_SLICES cannot be combined
  * with PTL_FLAG_REFINE) are out of scope.
  * ptl_renderer_adaptive_result: the list and the count of the last adaptive draw, DEVICE pointers owned and reused by the renderer,
- * ordered on that draw's stream and valid until the next adaptive draw or destroy. */
+ * ordered on that draw's stream and valid until the next adaptive draw or destroy.
+ * (Adaptive draws of a batch of slices: PTL_FLAG_REFINE_SLICES and ptl_renderer_draw_slices_adaptive below.) */
 int ptl_renderer_draw_adaptive(ptl_renderer* r, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* stream, float* elapsed_ms);
 int ptl_renderer_adaptive_result(ptl_renderer* r, void** list, void** count);
 int ptl_renderer_adaptive_times(ptl_renderer* r, float ms3[3]); /* pass 1, classification, refine pass of the last TIMED adaptive draw */
+
+/* ---- adaptive anti-aliasing of a batch of slices: the motion-blur sub-frames of a clip frame (opt-in, approximate by design) --------
+ * A source generated with flag bit 29 (PTL_FLAG_REFINE_SLICES) is the PTL_FLAG_SLICES source (the flag implies the slices entry) plus ONE
+ * more entry, `ptl_render_refine_slices_kernel`: the refine entry over the slices of a launch.  Bit 29 cannot be combined with bit 28.
+ * Contract, integers only, PER SLICE: for slice z of a batch of n (1 .. 16) take the state staged for it (uniforms, camera, `_aa_start`,
+ * textures as bound when it was staged).  P_z = the RGBA8 frame ptl_renderer_draw_slices writes for slice z with `_aa_count` = 1, F_z =
+ * the one it writes with the staged `_aa_count` = N, T = the option "adaptive_aa_threshold";  out_z = where(refine(P_z), F_z, P_z) with
+ * `refine` the rule above applied to each slice ON ITS OWN (a frame's border clamps to that frame).  RGBA8 bytes and, where asked for,
+ * RGBA32F bits.  T = -1: out_z == F_z; T = 255: out_z == P_z; every staged N = 1: a plain ptl_renderer_draw_slices with all counts 0.
+ * The averaging kernels (ptl_average_images, ptl_average_to_yuv420p10) consume out_z unchanged.
+ *
+ * ONE LIST PER SLICE (lists + z * list_stride entries, counts[z] entries used), not one merged list with the slice packed into the
+ * entry: every lane of a workgroup then shades with the same uniform block, the block pointer stays workgroup-uniform and the uniform
+ * reads stay scalar loads -- what the slices entry exists for.
+ *
+ * ptl_aa_edges_slices: the classification of ptl_aa_edges over a stack of n frames in one launch, grid (ceil(W/64), ceil(H/32), n).
+ * Slice z reads frames_rgba8 + z * slice_pixels pixels, appends to lists + z * list_stride and counts in counts[z]; counts[0 .. n) are
+ * reset on `stream` by the call itself.  PTL_ERR_INVALID before any GPU call: null pointers or pointers that are not 4-byte aligned, n
+ * outside 1 .. 16, sizes <= 0, W*H > 2^31, slice_pixels < W*H, list_stride < W*H, T outside -1 .. 255.
+ * ptl_kernel_set_staged_uniform: one uniform inside the ALREADY STAGED slice `index` (the codes of ptl_kernel_set_uniform; an unknown
+ * name is the same no-op code, PTL_UNKNOWN_UNIFORM); PTL_ERR_INVALID for an index outside 0 .. 15 or when nothing is staged.
+ * ptl_kernel_render_slices_refine: uploads the staged slices 0 .. n-1 and runs their prologue exactly as ptl_kernel_render_slices does,
+ * then launches the entry: slice z shades the counts[z] pixels of lists + z * list_stride (counts read on the device; an entry >= W*H
+ * is skipped) into out_* + z * slice_pixels pixels (either output may be NULL).  Grid (gx, 1, n) with gx = min(ceil(W*H / 256), 2048 / n)
+ * (integer division): at most 2 048 workgroups per launch, the single-frame entry's 8 per CU, shared evenly by the slices -- a starting
+ * rule (profiles/r09).  PTL_ERR_INVALID, in this order: null pointers / sizes <= 0, a sharded or in-place frame, W*H > 2^31,
+ * list_stride or slice_pixels < W*H, n outside 1 .. 16, a kernel without the entry, nothing staged; only then PTL_ERR_NO_DEVICE. */
+int ptl_aa_edges_slices(int device, const void* frames_rgba8, unsigned long long slice_pixels, int n, int width, int height, int threshold, void* lists,
+                        unsigned long long list_stride, void* counts, void* stream, float* elapsed_ms);
+int ptl_kernel_set_staged_uniform(ptl_kernel* k, int index, const char* name, ptl_type type, const void* value);
+int ptl_kernel_render_slices_refine(ptl_kernel* k, const ptl_frame* frame, int n, const void* lists, unsigned long long list_stride, const void* counts,
+                                    void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels, void* segments, void* stream, float* elapsed_ms);
+/* ptl_renderer_draw_slices_adaptive: ptl_renderer_draw_slices with adaptive anti-aliasing, for renderers created with
+ * PTL_FLAG_REFINE_SLICES (without it: PTL_ERR_INVALID and a message that names the flag).  Three launches per run of slices on the caller's
+ * stream, behind a join of the lanes: pass 1 (every slice with `_aa_count` 1), ptl_aa_edges_slices on the sub-frames it wrote, the refine
+ * pass (the slices re-staged with their own `_aa_count`).  Nothing is read back and no kernel is rebuilt or adopted between the passes
+ * (ptl_renderer_stage_slice did that); consecutive slices staged with the same kernel form a run, and BOTH passes of a run go to the
+ * kernel its slices were staged with.  Texel buffers a staged slice names live until behind the refine launch.  PTL_ERR_INVALID before any
+ * GPU call: a null out_rgba8 (the classification reads it), anything but a whole frame, slice_pixels < W*H, a threshold outside
+ * -1 .. 255, slices 0 .. n-1 not all staged.  elapsed_ms: the sum of all launches; ptl_renderer_adaptive_times then reports the three
+ * passes summed over the runs.
+ * ptl_renderer_adaptive_slices_result: the lists (n * W*H uint32, list z at z * *list_stride entries) and the counts (16 words) of the
+ * last such draw, DEVICE pointers owned and reused by the renderer, ordered on that draw's stream; PTL_ERR_INVALID before the first. */
+int ptl_renderer_draw_slices_adaptive(ptl_renderer* r, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
+                                      void* stream, float* elapsed_ms);
+int ptl_renderer_adaptive_slices_result(ptl_renderer* r, void** lists, unsigned long long* list_stride, void** counts);
 
 /* The Y4M stream such frames travel in: "YUV4MPEG2 W<w> H<h> F<fps>:1 Ip A1:1 C420p10 XYSCSS=420P10 XCOLORRANGE=FULL\n" once, then
  * "FRAME\n" + payload per frame.  Writes the header (NUL-terminated) into buf and returns its length; PTL_ERR_INVALID when it does not fit. */
@@ -685,7 +733,7 @@ int ptl_strstore_get_identifier(const ptl_strstore* s, int line, char* kind, siz
 
 /* The fixed device sources embedded in the library: "glsl" (types + numerics contract),
  * "library" (prelude), "trace" (kernel template), "entry" (launchable entry points),
- * "refine_entry" (the list-driven render entry of PTL_FLAG_REFINE builds).
+ * "refine_entry" (the list-driven render entry of PTL_FLAG_REFINE builds), "refine_slices_entry" (the one over slices of PTL_FLAG_REFINE_SLICES builds).
  * Returns NULL for an unknown name.  Lets a caller write its own kernel against the same
  * conventions and hand it to ptl_kernel_compile. */
 const char* ptl_device_source(const char* which);

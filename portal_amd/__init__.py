@@ -65,6 +65,7 @@ FLAG_MATERIAL_TABLE_SCALAR = 1 << 27  # A/B (measured: no gain): the same table 
 FLAG_CHECK_AFFINE = 1 << 25  # diagnostics: general products, and `segments` counts the ray halves that meet a product / the bounce loop with a w that is not 1 / 0
 FLAG_NO_AFFINE_RAYS = 8388608  # A/B: matrix-times-ray products never assume o.w = 1 / d.w = 0 (default in specialised builds of affine scenes: they do; identical frames)
 FLAG_REFINE = 1 << 28  # adaptive anti-aliasing: a second render entry that shades a device-side list of pixels (SceneRenderer.draw_adaptive)
+FLAG_REFINE_SLICES = 1 << 29  # FLAG_SLICES (implied) plus the refine entry over the slices of a launch (SceneRenderer.draw_slices_adaptive); not with FLAG_REFINE
 FLAG_SLICES = 4194304  # the render entry reads its uniform block from a buffer of blocks (one per blockIdx.z): stage_slice / draw_slices, one launch for several draws
 FLAG_NO_ZERO_MASKS = 524288  # A/B: run-time matrices keep their full products although their zero pattern is known (KernelOptions::mask_zero_elements)
 FLAG_ASYNC_REJIT = 131072  # a specialised renderer never stalls on a rebuild: it draws with the un-specialised kernel until a worker thread has the new one
@@ -188,6 +189,11 @@ def _load() -> C.CDLL:
         "ptl_renderer_draw_adaptive": (ci, [vp, P(Frame), vp, vp, vp, P(C.c_float)]),
         "ptl_renderer_adaptive_result": (ci, [vp, P(vp), P(vp)]),
         "ptl_renderer_adaptive_times": (ci, [vp, P(C.c_float)]),
+        "ptl_aa_edges_slices": (ci, [ci, vp, C.c_ulonglong, ci, ci, ci, ci, vp, C.c_ulonglong, vp, vp, P(C.c_float)]),
+        "ptl_kernel_set_staged_uniform": (ci, [vp, ci, cp, ci, vp]),
+        "ptl_kernel_render_slices_refine": (ci, [vp, P(Frame), ci, vp, C.c_ulonglong, vp, vp, vp, C.c_ulonglong, vp, vp, P(C.c_float)]),
+        "ptl_renderer_draw_slices_adaptive": (ci, [vp, P(Frame), ci, vp, vp, C.c_ulonglong, vp, P(C.c_float)]),
+        "ptl_renderer_adaptive_slices_result": (ci, [vp, P(vp), P(C.c_ulonglong), P(vp)]),
         "ptl_y4m_header": (ci, [ci, ci, ci, cp, cs]),
         "ptl_device_alloc": (ci, [ci, cs, P(vp)]),
         "ptl_device_free": (ci, [vp]),
@@ -507,6 +513,43 @@ class SceneRenderer:
         ms = C.c_float()
         _check(lib().ptl_renderer_draw_slices(self._h, C.byref(frame), n, C.c_void_p(out_rgba8 or None), C.c_void_p(out_rgba32f or None), slice_pixels,
                                               C.c_void_p(stream or None), C.byref(ms) if timed else None), "ptl_renderer_draw_slices")
+        return ms.value if timed else None
+
+    def draw_slices_adaptive(self, frame: Frame, n: int, out_rgba8: int, out_rgba32f: int = 0, slice_pixels: int = 0, stream: int = 0, timed: bool = False):
+        """ptl_renderer_draw_slices_adaptive (FLAG_REFINE_SLICES renderers): the staged slices 0 .. n-1 with adaptive anti-aliasing, slice z at
+        out_rgba8 + 4 * z * slice_pixels bytes (device addresses; ``slice_pixels`` 0 = width * height).  The threshold is the option
+        ``adaptive_aa_threshold``.  Returns the summed GPU time of the launches in ms when ``timed`` (waits), else None."""
+        ms = C.c_float()
+        _check(lib().ptl_renderer_draw_slices_adaptive(self._h, C.byref(frame), n, C.c_void_p(out_rgba8 or None), C.c_void_p(out_rgba32f or None),
+                                                       slice_pixels or frame.width * frame.height, C.c_void_p(stream or None), C.byref(ms) if timed else None),
+               "ptl_renderer_draw_slices_adaptive")
+        return ms.value if timed else None
+
+    def adaptive_slices_result(self):
+        """Device addresses and stride (lists, list_stride in entries, counts) of the last draw_slices_adaptive: owned by the renderer."""
+        lst, cnt, stride = C.c_void_p(), C.c_void_p(), C.c_ulonglong()
+        _check(lib().ptl_renderer_adaptive_slices_result(self._h, C.byref(lst), C.byref(stride), C.byref(cnt)), "ptl_renderer_adaptive_slices_result")
+        return int(lst.value), int(stride.value), int(cnt.value)
+
+    def set_staged_uniform(self, index: int, name: str, value: int) -> int:
+        """ptl_kernel_set_staged_uniform on the renderer's current kernel (layer 1): one Int uniform inside the already staged slice `index`.
+        Returns the C code (0, or 1 = the kernel has no such uniform)."""
+        v = C.c_int(int(value))
+        rc = lib().ptl_kernel_set_staged_uniform(lib().ptl_renderer_kernel(self._h), index, name.encode(), PTL_I32, C.byref(v))
+        if rc < 0:
+            _check(rc, "ptl_kernel_set_staged_uniform")
+        return rc
+
+    def refine_slices_device(self, frame: Frame, n: int, lists_ptr: int, list_stride: int, counts_ptr: int, out_rgba8: int = 0, out_rgba32f: int = 0,
+                             slice_pixels: int = 0, segments: int = 0, stream: int = 0, timed: bool = False):
+        """ptl_kernel_render_slices_refine on the renderer's current kernel (layer 1; FLAG_REFINE_SLICES renderers): slice z of the kernel's
+        staged slices shades the ``counts_ptr[z]`` pixels of the caller's list at ``lists_ptr + 4 * z * list_stride`` into
+        ``out_* + z * slice_pixels`` pixels.  All pointers are DEVICE addresses; either output may be 0."""
+        ms = C.c_float()
+        _check(lib().ptl_kernel_render_slices_refine(lib().ptl_renderer_kernel(self._h), C.byref(frame), n, C.c_void_p(lists_ptr or None), list_stride,
+                                                     C.c_void_p(counts_ptr or None), C.c_void_p(out_rgba8 or None), C.c_void_p(out_rgba32f or None),
+                                                     slice_pixels or frame.width * frame.height, C.c_void_p(segments or None), C.c_void_p(stream or None),
+                                                     C.byref(ms) if timed else None), "ptl_kernel_render_slices_refine")
         return ms.value if timed else None
 
     def join(self, stream: int = 0) -> None:
@@ -834,6 +877,16 @@ def average_to_yuv420p10_device(frame_ptrs, out_ptr: int, width: int, height: in
     ms = C.c_float()
     _check(lib().ptl_average_to_yuv420p10(device, arr, len(frame_ptrs), C.c_void_p(out_ptr), width, height, C.c_void_p(stream or None), C.byref(ms) if timed else None),
            "average_to_yuv420p10")
+    return ms.value if timed else None
+
+
+def aa_edges_slices_device(frames_ptr: int, slice_pixels: int, n: int, width: int, height: int, threshold: int, lists_ptr: int, list_stride: int, counts_ptr: int,
+                           device: int = 0, stream: int = 0, timed: bool = False):
+    """ptl_aa_edges_slices on DEVICE buffers given as integer addresses: aa_edges_device over a stack of ``n`` frames in one launch, slice z
+    reading ``frames_ptr + 4 * z * slice_pixels``, listing at ``lists_ptr + 4 * z * list_stride`` and counting in ``counts_ptr[z]``."""
+    ms = C.c_float()
+    _check(lib().ptl_aa_edges_slices(device, C.c_void_p(frames_ptr or None), slice_pixels, n, width, height, threshold, C.c_void_p(lists_ptr or None), list_stride,
+                                     C.c_void_p(counts_ptr or None), C.c_void_p(stream or None), C.byref(ms) if timed else None), "aa_edges_slices")
     return ms.value if timed else None
 
 

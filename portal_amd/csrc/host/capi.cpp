@@ -223,6 +223,12 @@ struct ptl_renderer {
     size_t adaptive_capacity = 0;  // entries
     int adaptive_threshold = 4;    // option "adaptive_aa_threshold"
     float adaptive_ms[3] = {0.0f, 0.0f, 0.0f};  // the last timed adaptive draw: pass 1, classification, refine pass
+    // ptl_renderer_draw_slices_adaptive: one list per slice (list z at z * adaptive_slices_stride entries) and 16 counts; owned here, reused
+    void* adaptive_slices_lists = nullptr;
+    void* adaptive_slices_counts = nullptr;
+    size_t adaptive_slices_capacity = 0;          // entries, all lists together
+    unsigned long long adaptive_slices_stride = 0;  // entries between two lists of the last draw
+    int staged_aa_count[16] = {};                 // `_aa_count` of each staged slice (ptl_renderer_stage_slice)
 };
 
 namespace {
@@ -529,6 +535,8 @@ static KernelOptions options_from_flags(unsigned flags) {
     o.mask_zero_elements = specialised(flags) && !on(PTL_FLAG_NO_ZERO_MASKS);
     o.slices_entry = on(PTL_FLAG_SLICES);  // the render entry reads its uniform block from a buffer of blocks, one per blockIdx.z
     o.refine_entry = on(PTL_FLAG_REFINE);  // a second render entry over a device-side list of pixels (ptl_renderer_draw_adaptive)
+    o.refine_slices_entry = on(PTL_FLAG_REFINE_SLICES);  // the slices entry plus the list-driven entry over slices (ptl_renderer_draw_slices_adaptive)
+    o.slices_entry = o.slices_entry || o.refine_slices_entry;
     o.bound_snippets = on(PTL_FLAG_BOUNDED_SNIPPETS);  // scene_intersect first, its distance bounds the intersection-material snippets (opt-in: measured, no gain)
     // Round 6: the first-trip forms -- a second copy of scene_intersect and of every intersection-material snippet for the trip on which all rays of a
     // wave still start at the camera -- are OPT-IN IN THE UN-SPECIALISED KERNEL (bit 24, PTL_FLAG_KEEP_TRANSFORM_DODGES) and stay the default of the
@@ -1042,7 +1050,11 @@ extern "C" int ptl_renderer_create_with_options(ptl_scene* s, int device, const 
         r->flags = flags;
         r->asset_root = asset_root ? asset_root : "";
         if ((flags & PTL_FLAG_REFINE) && (flags & PTL_FLAG_SLICES)) {
-            set_last_error("ptl_renderer_create: PTL_FLAG_REFINE and PTL_FLAG_SLICES cannot be combined (the refine entry reads the module's own uniform block)");
+            set_last_error("ptl_renderer_create: PTL_FLAG_REFINE and PTL_FLAG_SLICES cannot be combined (the refine entry reads the module's own uniform block; PTL_FLAG_REFINE_SLICES has the entry over slices)");
+            return (int)PTL_ERR_INVALID;
+        }
+        if ((flags & PTL_FLAG_REFINE) && (flags & PTL_FLAG_REFINE_SLICES)) {
+            set_last_error("ptl_renderer_create: PTL_FLAG_REFINE and PTL_FLAG_REFINE_SLICES cannot be combined (one refine entry per module)");
             return (int)PTL_ERR_INVALID;
         }
         if (const char* e = std::getenv("PTL_CHECK_AFFINE"); e && e[0] == '1') r->check_affine_on_new_source = true;
@@ -1374,6 +1386,7 @@ extern "C" int ptl_renderer_stage_slice(ptl_renderer* r, const ptl_frame* frame,
         // the block names the texel buffers bound NOW (a video texture may step before the next stage call): they stay until the launch
         ptl_kernel_hold_textures(r->kernel, 1);
         r->staged_kernels[index] = r->kernel;
+        r->staged_aa_count[index] = r->opt.aa_count;
         r->staged_mask |= 1u << index;
         return (int)PTL_OK;
     });
@@ -1421,7 +1434,7 @@ extern "C" int ptl_renderer_join(ptl_renderer* r, void* stream) {
 // other values for this very state -- the renderer then switches affine rays off for its stage and rebuilds (one re-JIT, the frames stay right).
 static int check_affine_now(ptl_renderer* r, int width, int height, unsigned long long* violations) {
     if (r->device < 0) return PTL_ERR_NO_DEVICE;
-    const unsigned flags = (r->flags & ~(PTL_FLAG_ASYNC_REJIT | PTL_FLAG_SLICES | PTL_FLAG_REFINE | PTL_FLAG_NO_AFFINE_RAYS)) | PTL_FLAG_CHECK_AFFINE | PTL_FLAG_COUNT_SEGMENTS |
+    const unsigned flags = (r->flags & ~(PTL_FLAG_ASYNC_REJIT | PTL_FLAG_SLICES | PTL_FLAG_REFINE | PTL_FLAG_REFINE_SLICES | PTL_FLAG_NO_AFFINE_RAYS)) | PTL_FLAG_CHECK_AFFINE | PTL_FLAG_COUNT_SEGMENTS |
                            PTL_FLAG_QUICK_JIT;  // not async, no slices entry; checking + counting, quick JIT
     std::vector<char> log(1 << 16);
     ptl_renderer* sib = nullptr;
@@ -1547,6 +1560,99 @@ extern "C" int ptl_renderer_adaptive_result(ptl_renderer* r, void** list, void**
 extern "C" int ptl_renderer_adaptive_times(ptl_renderer* r, float ms3[3]) {
     if (!r || !ms3) return PTL_ERR_INVALID;
     std::copy(r->adaptive_ms, r->adaptive_ms + 3, ms3);
+    return PTL_OK;
+}
+// Adaptive anti-aliasing of a batch of staged slices (include/portal_amd.h has the contract): per run of slices staged with the same kernel,
+// pass 1 with every slice's `_aa_count` set to 1, the classification of the sub-frames it wrote, and the refine pass with the slices
+// re-staged from the snapshots -- their own `_aa_count` -- on the kernel the run was staged with.  Nothing is read back, nothing is rebuilt.
+// The texture holds of ptl_renderer_stage_slice stay until drop_staged_slices at the end: pass 1's launch releases no texel buffer.
+extern "C" int ptl_renderer_draw_slices_adaptive(ptl_renderer* r, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
+                                                 void* stream, float* elapsed_ms) {
+    if (!r || !frame || !out_rgba8 || n < 1 || n > 16 || frame->width <= 0 || frame->height <= 0) return PTL_ERR_INVALID;
+    if (frame->rb_stride != 1 || frame->rb_phase != 0 || frame->in_place) {
+        set_last_error("ptl_renderer_draw_slices_adaptive: a whole frame only (rb_phase 0, rb_stride 1, not in_place)");
+        return PTL_ERR_INVALID;
+    }
+    if ((long long)frame->width * frame->height > (1LL << 31)) return PTL_ERR_INVALID;
+    const size_t pixels = (size_t)frame->width * (size_t)frame->height;
+    if (slice_pixels < pixels) {
+        set_last_error("ptl_renderer_draw_slices_adaptive: slice_pixels is smaller than width * height");
+        return PTL_ERR_INVALID;
+    }
+    if (r->adaptive_threshold < -1 || r->adaptive_threshold > 255) {
+        set_last_error("ptl_renderer_draw_slices_adaptive: option adaptive_aa_threshold is outside -1 .. 255");
+        return PTL_ERR_INVALID;
+    }
+    if (!(r->flags & PTL_FLAG_REFINE_SLICES)) {
+        set_last_error("ptl_renderer_draw_slices_adaptive: the renderer was created without PTL_FLAG_REFINE_SLICES: its kernel has no refine entry over slices");
+        return PTL_ERR_INVALID;
+    }
+    const unsigned want = (1u << n) - 1u;
+    if ((r->staged_mask & want) != want) {
+        set_last_error("ptl_renderer_draw_slices_adaptive: slices 0 .. n-1 are not all staged (ptl_renderer_stage_slice) since the last launch");
+        return PTL_ERR_INVALID;
+    }
+    if (r->device < 0) return PTL_ERR_NO_DEVICE;
+    return guarded([&] {
+        if (int jrc = join_lanes(r, stream); jrc != PTL_OK) return jrc;
+        int rc = PTL_OK;
+        if (r->adaptive_slices_capacity < pixels * (size_t)n) {
+            if (r->adaptive_slices_lists) ptl_device_free(r->adaptive_slices_lists);
+            r->adaptive_slices_lists = nullptr;
+            r->adaptive_slices_capacity = 0;
+            if (rc = ptl_device_alloc(r->device, pixels * (size_t)n * 4, &r->adaptive_slices_lists); rc != PTL_OK) return rc;
+            r->adaptive_slices_capacity = pixels * (size_t)n;
+        }
+        if (!r->adaptive_slices_counts)
+            if (rc = ptl_device_alloc(r->device, 16 * 4, &r->adaptive_slices_counts); rc != PTL_OK) return rc;
+        const unsigned long long stride = pixels;
+        r->adaptive_slices_stride = stride;
+        // With N = 1 in every slice the call is a plain draw_slices and the lists are empty: T = 255 flags nothing, no refine launch.
+        bool plain = true;
+        for (int j = 0; j < n; ++j) plain = plain && r->staged_aa_count[j] <= 1;
+        float ms[3] = {0.0f, 0.0f, 0.0f};
+        const int one = 1;
+        for (int j0 = 0; j0 < n && rc == PTL_OK;) {  // run by run, as ptl_renderer_draw_slices
+            ptl_kernel* k = r->staged_kernels[j0];
+            int j1 = j0 + 1;
+            while (j1 < n && r->staged_kernels[j1] == k) ++j1;
+            const int count = j1 - j0;
+            void* out8 = static_cast<unsigned char*>(out_rgba8) + (size_t)j0 * slice_pixels * 4;
+            void* out32 = out_rgba32f ? static_cast<float*>(out_rgba32f) + (size_t)j0 * slice_pixels * 4 : nullptr;
+            void* lists = static_cast<unsigned int*>(r->adaptive_slices_lists) + (size_t)j0 * stride;
+            void* counts = static_cast<unsigned int*>(r->adaptive_slices_counts) + j0;
+            float t[3] = {0.0f, 0.0f, 0.0f};
+            auto stage_run = [&] {
+                int src = PTL_OK;
+                for (int j = j0; j < j1 && src == PTL_OK; ++j) src = ptl_kernel_stage_slice_from(k, j - j0, r->staged_blocks[j].data(), r->staged_blocks[j].size());
+                return src;
+            };
+            rc = stage_run();
+            for (int j = j0; j < j1 && rc == PTL_OK && !plain; ++j) rc = ptl_kernel_set_staged_uniform(k, j - j0, "_aa_count", PTL_I32, &one);
+            if (rc == PTL_OK) rc = ptl_kernel_render_slices(k, frame, count, out8, out32, slice_pixels, stream, elapsed_ms ? &t[0] : nullptr);
+            if (rc == PTL_OK)
+                rc = ptl_aa_edges_slices(r->device, out8, slice_pixels, count, frame->width, frame->height, plain ? 255 : r->adaptive_threshold, lists, stride, counts, stream,
+                                         elapsed_ms ? &t[1] : nullptr);
+            if (rc == PTL_OK && !plain) {
+                rc = stage_run();  // the snapshots again: every slice's own `_aa_count`
+                if (rc == PTL_OK) rc = ptl_kernel_render_slices_refine(k, frame, count, lists, stride, counts, out8, out32, slice_pixels, nullptr, stream, elapsed_ms ? &t[2] : nullptr);
+            }
+            for (int p = 0; p < 3; ++p) ms[p] += t[p];
+            j0 = j1;
+        }
+        if (elapsed_ms) {
+            *elapsed_ms = ms[0] + ms[1] + ms[2];
+            std::copy(ms, ms + 3, r->adaptive_ms);
+        }
+        drop_staged_slices(r);
+        return rc;
+    });
+}
+extern "C" int ptl_renderer_adaptive_slices_result(ptl_renderer* r, void** lists, unsigned long long* list_stride, void** counts) {
+    if (!r || !r->adaptive_slices_lists || !r->adaptive_slices_counts) return PTL_ERR_INVALID;
+    if (lists) *lists = r->adaptive_slices_lists;
+    if (list_stride) *list_stride = r->adaptive_slices_stride;
+    if (counts) *counts = r->adaptive_slices_counts;
     return PTL_OK;
 }
 extern "C" int ptl_renderer_draw_to_host(ptl_renderer* r, const ptl_frame* frame, uint8_t* host_rgba8, float* host_rgba32f,
@@ -1900,6 +2006,8 @@ extern "C" void ptl_renderer_destroy(ptl_renderer* r) {
     if (r->fence) ptl_event_destroy(r->fence);
     if (r->adaptive_list) ptl_device_free(r->adaptive_list);  // (hipFree waits for the device: the last adaptive draw has finished)
     if (r->adaptive_count) ptl_device_free(r->adaptive_count);
+    if (r->adaptive_slices_lists) ptl_device_free(r->adaptive_slices_lists);
+    if (r->adaptive_slices_counts) ptl_device_free(r->adaptive_slices_counts);
     if (r->spec_kernel || r->dyn_kernel) {  // background re-JIT: `kernel` is one of these two
         ptl_kernel_destroy(r->spec_kernel);
         ptl_kernel_destroy(r->dyn_kernel);
@@ -1966,6 +2074,7 @@ extern "C" const char* ptl_device_source(const char* which) {
     if (w == "trace") return device_source_trace_template();
     if (w == "entry") return device_source_entry();
     if (w == "refine_entry") return device_source_refine_entry();
+    if (w == "refine_slices_entry") return device_source_refine_slices_entry();
     return nullptr;
 }
 

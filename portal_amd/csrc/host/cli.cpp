@@ -21,7 +21,7 @@ int usage() {  // (and the exit status that goes with it)
                  "                  [--gpus N | --devices a,b,..] [--transport stores|copy|rccl] [--multi-process]   one frame across the GPUs of a node\n"
                  "                  [--specialize 0] do NOT bake the scene state into the kernel   [--fast] tolerance mode   [--exact-cr] numerics contract 1   [--opt3] JIT at -O3 like the library default (render-frame: -O1)   [--timing] where the wall time went\n"
                  "                  [--adaptive-aa [T]]  one sample per pixel, --aa-count samples only where a pixel differs from a neighbour by more than T codes (default 4, -1 .. 255); one GPU\n"
-                 "       portal-amd precompile <scene.ron> [--stage NAME] [--specialize 0]      fill the code-object cache (no GPU needed)\n"
+                 "       portal-amd precompile <scene.ron> [--stage NAME] [--specialize 0]      fill the code-object cache (no GPU needed; render's options choose render's kernels)\n"
                  "       portal-amd render <scene[,scene..]> [clip[,clip..]] [--width 3840] [--height 2160] [--fps 60] [--motion-blur-frames 1]\n"
                  "                  [--stereoimage] [--batch-subframes 0|1] [--no-skip-existing] [--filter-starts-with P] [--aa-count 4] [--render-depth 150]\n"
                  "                  [--scenes-dir DIR] [--out-dir DIR] [--device I] [--shard K/N] [--max-frames N] [--asset-root DIR]\n"
@@ -31,6 +31,8 @@ int usage() {  // (and the exit status that goes with it)
                  "                  [--frames png|y4m]   png (default): anim/frame_%%d.png, then ffmpeg.  y4m: YUV 4:2:0 10-bit frames from the GPU, streamed in order\n"
                  "                                       into ffmpeg's stdin while the clip renders (or to video/<scene>/<clip>.y4m without ffmpeg, with --max-frames).\n"
                  "                                       Not with --shard K/N, N > 1 (a stream needs every frame, in order); a clip is not resumed, it starts at frame 0\n"
+                 "                  [--clip-adaptive-aa [T]]  adaptive anti-aliasing of every sub-frame: one sample per pixel, --aa-count samples only where a pixel differs\n"
+                 "                                       from a neighbour by more than T codes (default 4, -1 .. 255); opt-in, approximate by design\n"
                  "       portal-amd emit-source <scene.ron> [--stage NAME]     print the generated HIP kernel source\n"
                  "       portal-amd check <scene.ron> [--stage NAME]           compile for gfx950 (no GPU needed); errors by scene element\n"
                  "       portal-amd write <scene.ron> [--stage NAME] [--set UNIFORM=VALUE ...] --output out.ron     the reference's RON writer\n"
@@ -453,6 +455,18 @@ int main(int argc, char** argv) {
                 }
             }
         }
+        else if (a == "--clip-adaptive-aa") {
+            o.clip_adaptive = true;
+            if (i + 1 < argc) {  // the optional threshold, as for --adaptive-aa
+                char* end = nullptr;
+                const long t = std::strtol(argv[i + 1], &end, 10);
+                if (end != argv[i + 1] && *end == '\0') {
+                    ++i;
+                    if (t < -1 || t > 255) return refuse("--clip-adaptive-aa T: the threshold is an integer in -1 .. 255");
+                    o.clip_adaptive_t = (int)t;
+                }
+            }
+        }
         else if (a == "--fast") o.fast = true;
         else if (a == "--exact-cr") o.exact_cr = true;
         else if (a == "--opt3") o.opt3 = true;
@@ -476,7 +490,8 @@ int main(int argc, char** argv) {
     if (!o.stage.empty() && !o.animation.empty()) return refuse("--stage and --animation exclude each other");
     if (o.blur < 1 || o.blur > 256) return refuse("--motion-blur-frames must be 1..256");
     if (o.y4m && o.shards > 1) return refuse("--frames y4m cannot be combined with --shard K/N, N > 1: a stream needs every frame, in order");
-    if (o.adaptive && cmd != "render-frame") return refuse("--adaptive-aa is an option of render-frame: clips trace their sub-frames through the slices entry, which has no refine pass");
+    if (o.adaptive && cmd != "render-frame") return refuse("--adaptive-aa is an option of render-frame: a clip's sub-frames go through the slices entry, whose adaptive form is `render --clip-adaptive-aa [T]`");
+    if (o.clip_adaptive && cmd != "render" && cmd != "precompile") return refuse("--clip-adaptive-aa is an option of render (and of precompile, which builds render's kernels); a single frame takes render-frame --adaptive-aa");
     if (o.adaptive && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.shards > 1)) return refuse("--adaptive-aa draws whole frames on one GPU: it cannot be combined with --gpus N, N > 1, several --devices or --shard");
     if (cmd == "render") return render(o);
     if (o.transport != "stores" && o.transport != "copy" && o.transport != "rccl") return refuse("--transport stores|copy|rccl");

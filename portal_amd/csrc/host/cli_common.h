@@ -31,6 +31,8 @@ struct Options {
     bool multi_process = false, fast = false, exact_cr = false, opt3 = false;
     bool adaptive = false;   // render-frame --adaptive-aa [T]: one sample per pixel, the full --aa-count only where a pixel differs from a neighbour by more than T codes
     int adaptive_t = 4;
+    bool clip_adaptive = false;  // render --clip-adaptive-aa [T]: the same for every sub-frame of a clip (batched: the refine entry over slices)
+    int clip_adaptive_t = 4;
     std::vector<std::string> argv;  // the command line as given (handed on to shard processes)
 };
 
@@ -98,8 +100,11 @@ inline unsigned quick_jit_flag(const Options& o) { return o.opt3 ? 0u : PTL_FLAG
 // the clips to come: a difference is a miss in the code-object cache and a clip that waits for the JIT the others were meant to hide.
 // `clip_constant`: with what is constant within the clip baked in ("specialize_static").  A renderer that starts drawing on the build
 // right away adds quick_jit_flag().
+// --clip-adaptive-aa: where the sub-frames are batched the module has the slices entry AND the refine entry over slices (bit 29, which implies
+// bit 22), else the single-frame refine entry (bit 28) and every sub-frame is a ptl_renderer_draw_adaptive.  Without the option: what it was.
 inline unsigned clip_flags(const Options& o, bool clip_constant) {
-    return kClipFlags | (batch_subframes(o) ? kSlicesFlag : 0u) | numerics_flags(o) | (clip_constant ? PTL_FLAG_SPECIALIZE_STATIC : 0u);
+    const unsigned entries = o.clip_adaptive ? (batch_subframes(o) ? PTL_FLAG_REFINE_SLICES : PTL_FLAG_REFINE) : (batch_subframes(o) ? kSlicesFlag : 0u);
+    return kClipFlags | entries | numerics_flags(o) | (clip_constant ? PTL_FLAG_SPECIALIZE_STATIC : 0u);
 }
 
 // SceneRenderer::update_inner_variables (src/main.rs:1688-1756): per-clip settings the reference hard-codes for its

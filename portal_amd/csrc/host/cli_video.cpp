@@ -494,6 +494,22 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
     int count = std::max(1, (int)((float)clip.duration * (float)clip.fps));  // ((duration_seconds * fps as f32) as usize).max(1)
     double gpu_ms = 0.0;
     long traced = 0, drawn_frames = 0;
+    // --clip-adaptive-aa under --timing: refined entries of all sub-frames, and the three passes' GPU ms summed (each frame is synchronised anyway)
+    unsigned long long refined = 0;
+    double pass_ms[3] = {0.0, 0.0, 0.0};
+    auto account_adaptive = [&](bool slices, int n) {
+        unsigned int counts[16] = {};
+        void* dev_counts = nullptr;
+        if ((slices ? ptl_renderer_adaptive_slices_result(r, nullptr, nullptr, &dev_counts) : ptl_renderer_adaptive_result(r, nullptr, &dev_counts)) != PTL_OK ||
+            ptl_device_download(counts, dev_counts, sizeof(unsigned int) * (size_t)n, nullptr) != PTL_OK)
+            return fail("refined count");
+        for (int z = 0; z < n; ++z) refined += counts[z];
+        float ms3[3] = {0.0f, 0.0f, 0.0f};
+        ptl_renderer_adaptive_times(r, ms3);
+        for (int p = 0; p < 3; ++p) pass_ms[p] += ms3[p];
+        return 0;
+    };
+    if (o.clip_adaptive) ptl_renderer_set_option(r, "adaptive_aa_threshold", o.clip_adaptive_t);
     ptl_frame frame{run.width, run.height, 0, 1, 0};
     int last = o.max_frames >= 0 ? std::min(count, o.max_frames) : count;
     const bool batched = batch_subframes(o), direct = out.draws_result();
@@ -521,8 +537,18 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
             if (batched) {
                 // everything a draw does short of launching; the launch follows behind the last sub-frame, once for all of them
                 if (ptl_renderer_stage_slice(r, &frame, j) != PTL_OK) return fail("stage");
-                if (j == o.blur - 1 && ptl_renderer_draw_slices(r, &frame, o.blur, run.subframes[0], nullptr, (unsigned long long)run.width * run.height, nullptr, o.timing ? &ms : nullptr) != PTL_OK)
-                    return fail("render");
+                const unsigned long long slice_pixels = (unsigned long long)run.width * run.height;
+                if (j == o.blur - 1) {
+                    if ((o.clip_adaptive ? ptl_renderer_draw_slices_adaptive(r, &frame, o.blur, run.subframes[0], nullptr, slice_pixels, nullptr, o.timing ? &ms : nullptr)
+                                         : ptl_renderer_draw_slices(r, &frame, o.blur, run.subframes[0], nullptr, slice_pixels, nullptr, o.timing ? &ms : nullptr)) != PTL_OK)
+                        return fail("render");
+                    if (o.clip_adaptive && o.timing)
+                        if (int rc = account_adaptive(true, o.blur)) return rc;
+                }
+            } else if (o.clip_adaptive) {  // (blur 1, blur > 16, --batch-subframes 0: the single-frame adaptive draw per sub-frame)
+                if (ptl_renderer_draw_adaptive(r, &frame, target, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) return fail("render");
+                if (o.timing)
+                    if (int rc = account_adaptive(false, 1)) return rc;
             } else if (ptl_renderer_draw(r, &frame, target, nullptr, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) {
                 // (without --timing the launch is not waited for: the host evaluates the next sub-frame's uniforms while this one traces)
                 return fail("render");
@@ -559,6 +585,11 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
     if (o.timing) std::snprintf(gpu_time, sizeof gpu_time, ", GPU %.1f ms (%.3f ms each),", gpu_ms, traced ? gpu_ms / traced : 0.0);
     std::printf("Traced `%s/%s`: %ld sub-frames %dx%d%s submitted after %.2f s, kernel rebuilt %d times\n", run.name.c_str(), clip.name.c_str(), traced, run.width,
                 run.height, gpu_time, seconds_since(started), ptl_renderer_rejit_count(r) - rejits_before);
+    if (o.clip_adaptive && o.timing) {
+        const unsigned long long pixels = (unsigned long long)traced * (unsigned long long)run.width * (unsigned long long)run.height;
+        std::printf("adaptive aa: threshold %d, %llu of %llu pixels refined (%.2f %%); GPU ms: one-sample pass %.3f, classification %.3f, refine pass %.3f\n", o.clip_adaptive_t,
+                    refined, pixels, pixels ? 100.0 * (double)refined / (double)pixels : 0.0, pass_ms[0], pass_ms[1], pass_ms[2]);
+    }
     return 0;
 }
 

@@ -441,11 +441,12 @@ static void apply_slices_entry(std::string& src) {
 }
 
 // KernelOptions::refine_entry: the list-driven render entry of the adaptive anti-aliasing, in front of the host half of ptl_entry.h.
-static void apply_refine_entry(std::string& src) {
+// (KernelOptions::refine_slices_entry: the same place, the entry over the slices of a batch -- behind `apply_slices_entry`, whose shade_pixel_in it calls)
+static void apply_refine_entry(std::string& src, const char* entry) {
     const std::string anchor = "#else  // host build of the same source (oracle/host_build): rows [row_begin, row_end) of the frame\n";
     const size_t at = src.find(anchor);
     if (at == std::string::npos || src.find(anchor, at + 1) != std::string::npos) throw SceneError("refine entry: the kernel template no longer has its `#else  // host build` line");
-    src.insert(at, device_source_refine_entry());
+    src.insert(at, entry);
 }
 
 static void apply_zero_masks(std::string& src, const std::vector<std::pair<std::string, MatrixPattern>>& masked) {
@@ -1688,9 +1689,12 @@ GeneratedKernel generate_kernel_source(const Scene& scene, const CodegenFlags& f
     gk.source = std::move(body.storage);
     gk.line_numbers = std::move(body.line_numbers);
     apply_zero_masks(gk.source, gk.masked);
-    if (opts.slices_entry && opts.refine_entry) throw SceneError("PTL_FLAG_REFINE and PTL_FLAG_SLICES cannot be combined: the refine entry reads the module's own uniform block");
-    if (opts.slices_entry) apply_slices_entry(gk.source);
-    if (opts.refine_entry) apply_refine_entry(gk.source);
+    if (opts.refine_slices_entry && opts.refine_entry)
+        throw SceneError("PTL_FLAG_REFINE and PTL_FLAG_REFINE_SLICES cannot be combined: a module has the refine entry over its own uniform block or the one over slices");
+    if (opts.slices_entry && opts.refine_entry) throw SceneError("PTL_FLAG_REFINE and PTL_FLAG_SLICES cannot be combined: the refine entry reads the module's own uniform block (PTL_FLAG_REFINE_SLICES has the entry over slices)");
+    if (opts.slices_entry || opts.refine_slices_entry) apply_slices_entry(gk.source);
+    if (opts.refine_entry) apply_refine_entry(gk.source, device_source_refine_entry());
+    if (opts.refine_slices_entry) apply_refine_entry(gk.source, device_source_refine_slices_entry());
     return gk;
 }
 

@@ -158,6 +158,10 @@ struct KernelOptions {
     // shades the pixels of a device-side list instead of a rectangle.  Spliced into the generated text like the slices entry (codegen.cpp
     // `apply_refine_entry`): kernels built without it are byte for byte what they were.  Not together with slices_entry.
     bool refine_entry = false;
+    // Adaptive anti-aliasing of a batch of slices (PTL_FLAG_REFINE_SLICES): the slices entry (implied) plus a list-driven entry over the same
+    // buffer of blocks, `ptl_render_refine_slices_kernel` (device/ptl_refine_slices_entry.h): slice z shades the pixels of ITS list with ITS
+    // block.  `apply_slices_entry` first, then the new entry spliced in where `apply_refine_entry` puts its own.  Not together with refine_entry.
+    bool refine_slices_entry = false;
     // Affine rays (round 5): in a kernel whose every scene matrix is KNOWN to have the bottom row 0 0 0 1 (baked, or through its pattern) and
     // whose scene snippets never write a ray's w, every origin has w = 1 and every direction w = 0, and the products of a matrix with a ray
     // say so (device/ptl_glsl.h PTL_AFFINE_RAYS): the translation column costs a direction nothing, the w row folds to a constant.  Exact for
@@ -246,5 +250,6 @@ const char* device_source_library();
 const char* device_source_trace_template();
 const char* device_source_entry();
 const char* device_source_refine_entry();
+const char* device_source_refine_slices_entry();
 
 }  // namespace ptl

@@ -44,6 +44,8 @@ struct ptl_kernel {
     hip::hipFunction_t derive_fn = nullptr;    // optional: ptl_derive_kernel, the uniform prologue (runs after every upload)
     hip::hipFunction_t refine_fn = nullptr;    // optional: ptl_render_refine_kernel, the list-driven render entry (sources generated with PTL_FLAG_REFINE)
     bool has_refine = false;                   // the source names that entry (known without a device)
+    hip::hipFunction_t refine_slices_fn = nullptr;  // optional: ptl_render_refine_slices_kernel, the list-driven entry over slices (PTL_FLAG_REFINE_SLICES)
+    bool has_refine_slices = false;                 // the source names that entry (known without a device); such a source has the slices entry too
     void* dev_block = nullptr;  // address of __constant__ ptl_u
     size_t dev_block_size = 0;
     std::vector<unsigned char> shadow;  // host copy of the uniform block
@@ -444,7 +446,8 @@ int bind_module(ptl_kernel* k, const hip::Runtime* rt, RenderEntry entry, size_t
             return PTL_ERR_HIP;
         k->sliced = true;
     }
-    for (auto [fn, name] : {std::pair{&k->teleport_fn, "ptl_teleport_kernel"}, std::pair{&k->derive_fn, "ptl_derive_kernel"}, std::pair{&k->refine_fn, "ptl_render_refine_kernel"}})
+    for (auto [fn, name] : {std::pair{&k->teleport_fn, "ptl_teleport_kernel"}, std::pair{&k->derive_fn, "ptl_derive_kernel"}, std::pair{&k->refine_fn, "ptl_render_refine_kernel"},
+                           std::pair{&k->refine_slices_fn, "ptl_render_refine_slices_kernel"}})
         if (rt->hipModuleGetFunction(fn, k->module, name) != 0) {
             *fn = nullptr;          // hand-written layer-1 kernels need not have the other entry points
             rt->hipGetLastError();  // ... and the expected hipErrorNotFound must not stay behind as the thread's sticky
@@ -483,6 +486,7 @@ int compile_kernel(const CompileRequest& rq, const std::vector<char>* prebuilt, 
     k->affine_rays = traits.affine_rays;
     k->split = traits.split;
     k->has_refine = !traits.teleport_only && std::strstr(rq.source, "ptl_render_refine_kernel(") != nullptr;
+    k->has_refine_slices = !traits.teleport_only && std::strstr(rq.source, "ptl_render_refine_slices_kernel(") != nullptr;
     if (k->split) {
         k->source = rq.source;
         k->defines.assign(rq.defines, rq.defines + rq.n_defines);
@@ -575,6 +579,7 @@ extern "C" int ptl_kernel_clone(ptl_kernel* src, ptl_kernel** out) {
     k->block_waves = src->block_waves;
     k->split = src->split;
     k->has_refine = src->has_refine;
+    k->has_refine_slices = src->has_refine_slices;
     k->source = src->source;
     k->defines = src->defines;
     // (affine_rays is NOT inherited: a clone accepts matrices through ptl_kernel_set_uniform that its original refuses)
@@ -626,12 +631,11 @@ extern "C" int ptl_kernel_resources(ptl_kernel* k, int* registers, int* scratch_
     return PTL_OK;
 }
 
-extern "C" int ptl_kernel_set_uniform(ptl_kernel* k, const char* name, ptl_type type, const void* value) {
-    if (!k || !name || !value) return PTL_ERR_INVALID;
+// What ptl_kernel_set_uniform and ptl_kernel_set_staged_uniform check alike; PTL_OK: `*offset` is where the value goes in a block.
+static int settable_uniform(ptl_kernel* k, const char* name, ptl_type type, const void* value, size_t* offset) {
     auto it = k->slots.find(name);
     if (it == k->slots.end()) return PTL_UNKNOWN_UNIFORM;
     if (it->second.type != type || type == PTL_SAMPLER) return PTL_ERR_TYPE;
-    size_t n = type_size(type);
     if (k->affine_rays && type == PTL_MAT4) {
         // a layer-1 caller owns `_camera` and every run-time `X_mat`; a kernel with affine rays is only valid for matrices that map
         // w = 1 to 1 and w = 0 to 0 (or are NaN throughout: a switched-off object).  The layer-2 renderer rebuilds BEFORE it uploads such a matrix
@@ -644,8 +648,17 @@ extern "C" int ptl_kernel_set_uniform(ptl_kernel* k, const char* name, ptl_type 
             return PTL_ERR_INVALID;
         }
     }
-    if (std::memcmp(k->shadow.data() + it->second.offset, value, n) != 0) {
-        std::memcpy(k->shadow.data() + it->second.offset, value, n);
+    *offset = it->second.offset;
+    return PTL_OK;
+}
+
+extern "C" int ptl_kernel_set_uniform(ptl_kernel* k, const char* name, ptl_type type, const void* value) {
+    if (!k || !name || !value) return PTL_ERR_INVALID;
+    size_t offset = 0;
+    if (int rc = settable_uniform(k, name, type, value, &offset); rc != PTL_OK) return rc;
+    const size_t n = type_size(type);
+    if (std::memcmp(k->shadow.data() + offset, value, n) != 0) {
+        std::memcpy(k->shadow.data() + offset, value, n);
         k->dirty = true;
         k->slice0_dirty = true;
     }
@@ -891,6 +904,70 @@ extern "C" int ptl_kernel_render_refine(ptl_kernel* k, const ptl_frame* frame, c
     if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
     if (!hip_ok(rt, rt->hipModuleLaunchKernel(k->refine_fn, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr), "hipModuleLaunchKernel(ptl_render_refine_kernel)"))
         return PTL_ERR_HIP;
+    k->last_stream = stream;
+    k->launched = true;
+    if (k->ev_done) rt->hipEventRecord(k->ev_done, stream);
+    if (elapsed_ms) {
+        rt->hipEventRecord(k->ev1, stream);
+        if (!hip_ok(rt, rt->hipEventSynchronize(k->ev1), "hipEventSynchronize")) return PTL_ERR_HIP;
+        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
+    }
+    return PTL_OK;
+}
+
+// One uniform inside slice `index` as it is staged now (not the kernel's current values): what a caller changes between two launches over
+// the same staged slices -- layer 2 sets `_aa_count` = 1 for pass 1 of an adaptive batch.  The codes of ptl_kernel_set_uniform.
+extern "C" int ptl_kernel_set_staged_uniform(ptl_kernel* k, int index, const char* name, ptl_type type, const void* value) {
+    if (!k || !name || !value || index < 0 || index >= kMaxSlices) return PTL_ERR_INVALID;
+    size_t offset = 0;
+    if (int rc = settable_uniform(k, name, type, value, &offset); rc != PTL_OK) return rc;
+    if (k->staged.empty()) {
+        set_last_error("ptl_kernel_set_staged_uniform: no staged slices (PTL_FLAG_SLICES build + ptl_kernel_stage_slice)");
+        return PTL_ERR_INVALID;
+    }
+    std::memcpy(k->staged.data() + k->dev_block_size * (size_t)index + offset, value, type_size(type));
+    return PTL_OK;
+}
+
+// The refine pass of an adaptive batch: the module's list-driven entry over slices (device/ptl_refine_slices_entry.h) shades, for every
+// staged slice z < n, the counts[z] pixels of lists + z * list_stride with that slice's uniforms into out_* + z * slice_pixels pixels.
+// Uploads the staged slices and runs their prologue like ptl_kernel_render_slices.  Grid (gx, 1, n), gx = min(ceil(W H / 256), 2048 / n):
+// at most 2 048 workgroups per launch (8 per CU, what the single-frame entry launches), split evenly over the slices.
+extern "C" int ptl_kernel_render_slices_refine(ptl_kernel* k, const ptl_frame* frame, int n, const void* lists, unsigned long long list_stride, const void* counts,
+                                               void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels, void* segments, void* stream, float* elapsed_ms) {
+    if (!k || !frame || !lists || !counts || frame->width <= 0 || frame->height <= 0) return PTL_ERR_INVALID;
+    if (frame->rb_stride != 1 || frame->rb_phase != 0 || frame->in_place) {
+        set_last_error("ptl_kernel_render_slices_refine: the lists name pixels of a whole frame (rb_phase 0, rb_stride 1, not in_place)");
+        return PTL_ERR_INVALID;
+    }
+    if ((long long)frame->width * frame->height > (1LL << 31)) return PTL_ERR_INVALID;  // an entry is a 32-bit pixel index
+    const unsigned long long pixels = (unsigned long long)frame->width * (unsigned long long)frame->height;
+    if (list_stride < pixels || slice_pixels < pixels) {
+        set_last_error("ptl_kernel_render_slices_refine: list_stride and slice_pixels must be at least width * height");
+        return PTL_ERR_INVALID;
+    }
+    if (n < 1 || n > kMaxSlices) return PTL_ERR_INVALID;
+    if (!k->has_refine_slices) {
+        set_last_error("ptl_kernel_render_slices_refine: the kernel was not generated with the refine entry over slices (PTL_FLAG_REFINE_SLICES)");
+        return PTL_ERR_INVALID;
+    }
+    if (k->staged.empty()) {
+        set_last_error("ptl_kernel_render_slices_refine: no staged slices (ptl_kernel_stage_slice)");
+        return PTL_ERR_INVALID;
+    }
+    if (k->device < 0 || !k->refine_slices_fn || !k->sliced) return PTL_ERR_NO_DEVICE;
+    const hip::Runtime* rt = hip::runtime(nullptr);
+    if (!hip_ok(rt, rt->hipSetDevice(k->device), "hipSetDevice")) return PTL_ERR_HIP;
+    if (int rc = upload_slices(k, rt, stream, n, false); rc != PTL_OK) return rc;
+    int width = frame->width, height = frame->height;
+    void* blocks = k->dev_slices;
+    void* args[] = {&blocks, &slice_pixels, &lists, &list_stride, &counts, &out_rgba8, &out_rgba32f, &width, &height, &segments};
+    const long long chunks = ((long long)pixels + 255) / 256;
+    const unsigned gx = (unsigned)std::min<long long>(chunks, 2048 / n);
+    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
+    if (!hip_ok(rt, rt->hipModuleLaunchKernel(k->refine_slices_fn, gx, 1, (unsigned)n, 256, 1, 1, 0, stream, args, nullptr), "hipModuleLaunchKernel(ptl_render_refine_slices_kernel)"))
+        return PTL_ERR_HIP;
+    k->staged_since_launch = false;  // what was staged is launched (launch_render)
     k->last_stream = stream;
     k->launched = true;
     if (k->ev_done) rt->hipEventRecord(k->ev_done, stream);

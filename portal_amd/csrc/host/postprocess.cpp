@@ -200,6 +200,39 @@ extern "C" int ptl_aa_edges(int device, const void* frame_rgba8, int width, int 
     return PTL_OK;
 }
 
+// ptl_aa_edges_slices: the same classification over a stack of `n` frames in one launch (portal_amd/csrc/kernels/aa_edges_slices.hip):
+// slice z reads frames + z * slice_pixels pixels, appends to lists + z * list_stride entries and counts in counts[z].  counts[0 .. n) are
+// reset on `stream` by the call itself.
+extern "C" int ptl_aa_edges_slices(int device, const void* frames_rgba8, unsigned long long slice_pixels, int n, int width, int height, int threshold, void* lists,
+                                   unsigned long long list_stride, void* counts, void* stream, float* elapsed_ms) {
+    if (!frames_rgba8 || !lists || !counts || n < 1 || n > 16 || width <= 0 || height <= 0 || threshold < -1 || threshold > 255) return PTL_ERR_INVALID;
+    if ((long long)width * height > (1LL << 31)) return PTL_ERR_INVALID;  // an entry is a 32-bit pixel index
+    const unsigned long long pixels = (unsigned long long)width * (unsigned long long)height;
+    if (slice_pixels < pixels || list_stride < pixels) return PTL_ERR_INVALID;  // a slice's frame and list hold a whole frame: neighbours never overlap
+    if ((reinterpret_cast<uintptr_t>(frames_rgba8) | reinterpret_cast<uintptr_t>(lists) | reinterpret_cast<uintptr_t>(counts)) & 3u) return PTL_ERR_INVALID;
+    if (device < 0) return PTL_ERR_NO_DEVICE;
+    LoadedKernel* k = nullptr;
+    if (int rc = load_kernel(device, "aa_edges_slices.hsaco", "ptl_aa_edges_slices_kernel", &k); rc != PTL_OK) return rc;
+    const hip::Runtime* rt = hip::runtime(nullptr);
+    rt->hipSetDevice(device);
+    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
+    int err = rt->hipMemsetAsync(counts, 0, 4 * (size_t)n, stream);
+    void* args[] = {&frames_rgba8, &slice_pixels, &width, &height, &threshold, &lists, &list_stride, &counts};
+    if (err == 0)
+        err = rt->hipModuleLaunchKernel(k->fn, (unsigned)((width + 63) / 64), (unsigned)((height + 31) / 32), (unsigned)n, 256, 1, 1, 0, stream, args, nullptr);
+    if (err != 0) {
+        set_last_error(std::string("hipModuleLaunchKernel(aa_edges_slices): ") + rt->hipGetErrorString(err));
+        rt->hipGetLastError();
+        return PTL_ERR_HIP;
+    }
+    if (elapsed_ms) {
+        rt->hipEventRecord(k->ev1, stream);
+        rt->hipEventSynchronize(k->ev1);
+        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
+    }
+    return PTL_OK;
+}
+
 extern "C" int ptl_y4m_header(int width, int height, int fps, char* buf, size_t cap) {
     if (width <= 0 || height <= 0 || fps <= 0 || !buf) return PTL_ERR_INVALID;
     int len = std::snprintf(buf, cap, "YUV4MPEG2 W%d H%d F%d:1 Ip A1:1 C420p10 XYSCSS=420P10 XCOLORRANGE=FULL\n", width, height, fps);
