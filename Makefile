@@ -15,10 +15,10 @@ KERNELS  := portal_amd/kernels/fb_store.hsaco portal_amd/kernels/average_images.
 
 all: $(LIB) $(CLI)
 
-$(HOST)/embedded_device_sources.inc: $(DEVICE)/ptl_glsl.h $(DEVICE)/ptl_library.h $(DEVICE)/ptl_trace.tpl $(DEVICE)/ptl_entry.h $(DEVICE)/ptl_refine_entry.h $(DEVICE)/ptl_refine_slices_entry.h portal_amd/csrc/embed_sources.py
+$(HOST)/embedded_device_sources.inc: $(DEVICE)/ptl_glsl.h $(DEVICE)/ptl_library.h $(DEVICE)/ptl_trace.tpl $(DEVICE)/ptl_entry.h $(DEVICE)/ptl_refine_common.h $(DEVICE)/ptl_refine_entry.h $(DEVICE)/ptl_refine_slices_entry.h portal_amd/csrc/embed_sources.py
 	python3 portal_amd/csrc/embed_sources.py $@ device_source_glsl=$(DEVICE)/ptl_glsl.h device_source_library=$(DEVICE)/ptl_library.h \
-	    device_source_trace_template=$(DEVICE)/ptl_trace.tpl device_source_entry=$(DEVICE)/ptl_entry.h device_source_refine_entry=$(DEVICE)/ptl_refine_entry.h \
-	    device_source_refine_slices_entry=$(DEVICE)/ptl_refine_slices_entry.h
+	    device_source_trace_template=$(DEVICE)/ptl_trace.tpl device_source_entry=$(DEVICE)/ptl_entry.h device_source_refine_entry=$(DEVICE)/ptl_refine_common.h+$(DEVICE)/ptl_refine_entry.h \
+	    device_source_refine_slices_entry=$(DEVICE)/ptl_refine_common.h+$(DEVICE)/ptl_refine_slices_entry.h
 
 $(OBJDIR)/embedded.o: $(HOST)/embedded_device_sources.inc
 $(OBJDIR)/%.o: $(HOST)/%.cpp $(wildcard $(HOST)/*.h) include/portal_amd.h

@@ -217,17 +217,15 @@ struct ptl_renderer {
         long bound = -1;
     };
     std::vector<VideoState> videos;
-    // ptl_renderer_draw_adaptive: the list of refined pixels and their count, in device memory; owned here, reused from draw to draw
-    void* adaptive_list = nullptr;
-    void* adaptive_count = nullptr;
-    size_t adaptive_capacity = 0;  // entries
-    int adaptive_threshold = 4;    // option "adaptive_aa_threshold"
+    // The adaptive draws: the lists of refined pixels (list z at z * adaptive_stride entries; a single frame has list 0 alone) and 16
+    // counts, in device memory; owned here, reused from draw to draw.  A renderer has bit 28 or bit 29, so one kind of draw fills them.
+    void* adaptive_lists = nullptr;
+    void* adaptive_counts = nullptr;
+    size_t adaptive_capacity = 0;            // entries, all lists together
+    unsigned long long adaptive_stride = 0;  // entries between two lists of the last draw
+    enum class AdaptiveDraw { none, frame, slices } adaptive_filled = AdaptiveDraw::none;  // the kind of draw they were last made ready for
+    int adaptive_threshold = 4;                 // option "adaptive_aa_threshold"
     float adaptive_ms[3] = {0.0f, 0.0f, 0.0f};  // the last timed adaptive draw: pass 1, classification, refine pass
-    // ptl_renderer_draw_slices_adaptive: one list per slice (list z at z * adaptive_slices_stride entries) and 16 counts; owned here, reused
-    void* adaptive_slices_lists = nullptr;
-    void* adaptive_slices_counts = nullptr;
-    size_t adaptive_slices_capacity = 0;          // entries, all lists together
-    unsigned long long adaptive_slices_stride = 0;  // entries between two lists of the last draw
     int staged_aa_count[16] = {};                 // `_aa_count` of each staged slice (ptl_renderer_stage_slice)
 };
 
@@ -1391,6 +1389,28 @@ extern "C" int ptl_renderer_stage_slice(ptl_renderer* r, const ptl_frame* frame,
         return (int)PTL_OK;
     });
 }
+// The staged slices 0 .. n-1 as runs [j0, j1) of consecutive slices staged with the same kernel: each run goes out on the kernel it was
+// staged with -- one run for all n unless a rebuild fell between two stage calls (then the earlier slices keep the state THEIR kernel has
+// compiled in).  `run(k, j0, j1)` for one after the other, until one fails.
+template <typename Run>
+static int for_each_staged_run(ptl_renderer* r, int n, Run run) {
+    int rc = PTL_OK;
+    for (int j0 = 0; j0 < n && rc == PTL_OK;) {
+        ptl_kernel* k = r->staged_kernels[j0];
+        int j1 = j0 + 1;
+        while (j1 < n && r->staged_kernels[j1] == k) ++j1;
+        rc = run(k, j0, j1);
+        j0 = j1;
+    }
+    return rc;
+}
+// The snapshots of the run's slices become slices 0 .. j1-j0-1 of its kernel.
+static int stage_run(ptl_renderer* r, ptl_kernel* k, int j0, int j1) {
+    int rc = PTL_OK;
+    for (int j = j0; j < j1 && rc == PTL_OK; ++j) rc = ptl_kernel_stage_slice_from(k, j - j0, r->staged_blocks[j].data(), r->staged_blocks[j].size());
+    return rc;
+}
+
 extern "C" int ptl_renderer_draw_slices(ptl_renderer* r, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
                                         void* stream, float* elapsed_ms) {
     if (!r || !frame || n < 1 || n > 16) return PTL_ERR_INVALID;
@@ -1401,22 +1421,16 @@ extern "C" int ptl_renderer_draw_slices(ptl_renderer* r, const ptl_frame* frame,
             return (int)PTL_ERR_INVALID;
         }
         if (int jrc = join_lanes(r, stream); jrc != PTL_OK) return jrc;
-        // runs of consecutive slices staged with the same kernel go out as one launch each, on the kernel they were staged with -- one launch
-        // for all n unless a rebuild fell between two stage calls (then the earlier slices keep the state THEIR kernel has compiled in)
-        int rc = PTL_OK;
         float total_ms = 0.0f;
-        for (int j0 = 0; j0 < n && rc == PTL_OK;) {
-            ptl_kernel* k = r->staged_kernels[j0];
-            int j1 = j0 + 1;
-            while (j1 < n && r->staged_kernels[j1] == k) ++j1;
-            for (int j = j0; j < j1 && rc == PTL_OK; ++j) rc = ptl_kernel_stage_slice_from(k, j - j0, r->staged_blocks[j].data(), r->staged_blocks[j].size());
+        const int rc = for_each_staged_run(r, n, [&](ptl_kernel* k, int j0, int j1) {
+            int rc = stage_run(r, k, j0, j1);
             float ms = 0.0f;
             void* out8 = out_rgba8 ? static_cast<unsigned char*>(out_rgba8) + (size_t)j0 * slice_pixels * 4 : nullptr;
             void* out32 = out_rgba32f ? static_cast<float*>(out_rgba32f) + (size_t)j0 * slice_pixels * 4 : nullptr;
             if (rc == PTL_OK) rc = ptl_kernel_render_slices(k, frame, j1 - j0, out8, out32, slice_pixels, stream, elapsed_ms ? &ms : nullptr);
             total_ms += ms;
-            j0 = j1;
-        }
+            return rc;
+        });
         if (elapsed_ms) *elapsed_ms = total_ms;
         drop_staged_slices(r);
         return rc;
@@ -1497,41 +1511,57 @@ extern "C" int ptl_renderer_draw(ptl_renderer* r, const ptl_frame* frame, void* 
         return ptl_kernel_render(r->kernel, frame, out_rgba8, out_rgba32f, segments, stream, elapsed_ms);
     });
 }
-// Adaptive anti-aliasing (include/portal_amd.h has the contract): the frame with one sample per pixel, the classification of its RGBA8
-// bytes, and the flagged pixels again with the full `_aa_count` -- three launches on the caller's stream, nothing read back in between.
-// `_aa_count` is a run-time builtin in every build, so ONE kernel serves both passes: prepare_draw runs once, in front of pass 1, and is the
-// only place where a kernel is rebuilt or a background build adopted -- never between the passes.
+// ---- adaptive anti-aliasing (include/portal_amd.h has the contract) ------------------------------------------------------------------
+// What both adaptive draws refuse, in this order: a frame that is not whole or has more than 2^31 pixels, room for less than a frame
+// between two slices (`slice_pixels`; null for a single frame), a threshold outside its range, a renderer without the draw's flag
+// (`without_flag`: the rest of that sentence).
+static int check_adaptive_draw(const char* who, const ptl_renderer* r, const ptl_frame* frame, const unsigned long long* slice_pixels, unsigned flag, const char* without_flag) {
+    auto refuse = [&](const std::string& why) {
+        set_last_error(std::string(who) + ": " + why);
+        return (int)PTL_ERR_INVALID;
+    };
+    if (frame->rb_stride != 1 || frame->rb_phase != 0 || frame->in_place) return refuse("a whole frame only (rb_phase 0, rb_stride 1, not in_place)");
+    if ((long long)frame->width * frame->height > (1LL << 31)) return PTL_ERR_INVALID;
+    if (slice_pixels && *slice_pixels < (unsigned long long)frame->width * (unsigned long long)frame->height) return refuse("slice_pixels is smaller than width * height");
+    if (r->adaptive_threshold < -1 || r->adaptive_threshold > 255) return refuse("option adaptive_aa_threshold is outside -1 .. 255");
+    if (!(r->flags & flag)) return refuse(std::string("the renderer was created without ") + without_flag);
+    return PTL_OK;
+}
+// The device buffers of an adaptive draw of `n` frames of `pixels` pixels: grown when they are too small, reused otherwise.
+static int reserve_adaptive_lists(ptl_renderer* r, size_t pixels, int n, ptl_renderer::AdaptiveDraw kind) {
+    if (r->adaptive_capacity < pixels * (size_t)n) {
+        if (r->adaptive_lists) ptl_device_free(r->adaptive_lists);
+        r->adaptive_lists = nullptr;
+        r->adaptive_capacity = 0;
+        if (int rc = ptl_device_alloc(r->device, pixels * (size_t)n * 4, &r->adaptive_lists); rc != PTL_OK) return rc;
+        r->adaptive_capacity = pixels * (size_t)n;
+    }
+    if (!r->adaptive_counts)
+        if (int rc = ptl_device_alloc(r->device, 16 * 4, &r->adaptive_counts); rc != PTL_OK) return rc;
+    r->adaptive_stride = pixels;
+    r->adaptive_filled = kind;
+    return PTL_OK;
+}
+static void report_adaptive_times(ptl_renderer* r, const float ms[3], float* elapsed_ms) {
+    if (!elapsed_ms) return;
+    *elapsed_ms = ms[0] + ms[1] + ms[2];
+    std::copy(ms, ms + 3, r->adaptive_ms);
+}
+
+// One frame: the frame with one sample per pixel, the classification of its RGBA8 bytes, and the flagged pixels again with the full
+// `_aa_count` -- three launches on the caller's stream, nothing read back in between.  `_aa_count` is a run-time builtin in every build, so
+// ONE kernel serves both passes: prepare_draw runs once, in front of pass 1, and is the only place where a kernel is rebuilt or a
+// background build adopted -- never between the passes.
 extern "C" int ptl_renderer_draw_adaptive(ptl_renderer* r, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* stream, float* elapsed_ms) {
     if (!r || !frame || !out_rgba8 || frame->width <= 0 || frame->height <= 0) return PTL_ERR_INVALID;
-    if (frame->rb_stride != 1 || frame->rb_phase != 0 || frame->in_place) {
-        set_last_error("ptl_renderer_draw_adaptive: a whole frame only (rb_phase 0, rb_stride 1, not in_place)");
-        return PTL_ERR_INVALID;
-    }
-    if ((long long)frame->width * frame->height > (1LL << 31)) return PTL_ERR_INVALID;
-    if (r->adaptive_threshold < -1 || r->adaptive_threshold > 255) {
-        set_last_error("ptl_renderer_draw_adaptive: option adaptive_aa_threshold is outside -1 .. 255");
-        return PTL_ERR_INVALID;
-    }
-    if (!(r->flags & PTL_FLAG_REFINE)) {
-        set_last_error("ptl_renderer_draw_adaptive: the renderer was created without PTL_FLAG_REFINE: its kernel has no refine entry");
-        return PTL_ERR_INVALID;
-    }
+    if (int rc = check_adaptive_draw("ptl_renderer_draw_adaptive", r, frame, nullptr, PTL_FLAG_REFINE, "PTL_FLAG_REFINE: its kernel has no refine entry"); rc != PTL_OK) return rc;
     if (r->device < 0) return PTL_ERR_NO_DEVICE;
     return guarded([&] {
         int rc = prepare_draw(r, frame);
         if (rc < 0) return rc;
         if (rc = check_affine_if_asked(r, frame); rc < 0) return rc;
         if (int jrc = join_lanes(r, stream); jrc != PTL_OK) return jrc;
-        const size_t pixels = (size_t)frame->width * (size_t)frame->height;
-        if (r->adaptive_capacity < pixels) {
-            if (r->adaptive_list) ptl_device_free(r->adaptive_list);
-            r->adaptive_list = nullptr;
-            r->adaptive_capacity = 0;
-            if (rc = ptl_device_alloc(r->device, pixels * 4, &r->adaptive_list); rc != PTL_OK) return rc;
-            r->adaptive_capacity = pixels;
-        }
-        if (!r->adaptive_count)
-            if (rc = ptl_device_alloc(r->device, 16, &r->adaptive_count); rc != PTL_OK) return rc;
+        if (rc = reserve_adaptive_lists(r, (size_t)frame->width * (size_t)frame->height, 1, ptl_renderer::AdaptiveDraw::frame); rc != PTL_OK) return rc;
         float ms[3] = {0.0f, 0.0f, 0.0f};
         const int full = r->opt.aa_count, one = 1;
         // With N = 1 the call is a plain draw and the list is empty: T = 255 flags nothing, and the refine pass is not launched.
@@ -1540,21 +1570,18 @@ extern "C" int ptl_renderer_draw_adaptive(ptl_renderer* r, const ptl_frame* fram
         rc = ptl_kernel_render(r->kernel, frame, out_rgba8, out_rgba32f, nullptr, stream, elapsed_ms ? &ms[0] : nullptr);
         if (!plain) ptl_kernel_set_uniform(r->kernel, "_aa_count", PTL_I32, &full);  // (the host copy is again what prepare_draw left; uploaded in front of the refine pass)
         if (rc == PTL_OK)
-            rc = ptl_aa_edges(r->device, out_rgba8, frame->width, frame->height, plain ? 255 : r->adaptive_threshold, r->adaptive_list, r->adaptive_count, stream,
+            rc = ptl_aa_edges(r->device, out_rgba8, frame->width, frame->height, plain ? 255 : r->adaptive_threshold, r->adaptive_lists, r->adaptive_counts, stream,
                               elapsed_ms ? &ms[1] : nullptr);
         if (rc == PTL_OK && !plain)
-            rc = ptl_kernel_render_refine(r->kernel, frame, r->adaptive_list, r->adaptive_count, out_rgba8, out_rgba32f, nullptr, stream, elapsed_ms ? &ms[2] : nullptr);
-        if (elapsed_ms) {
-            *elapsed_ms = ms[0] + ms[1] + ms[2];
-            std::copy(ms, ms + 3, r->adaptive_ms);
-        }
+            rc = ptl_kernel_render_refine(r->kernel, frame, r->adaptive_lists, r->adaptive_counts, out_rgba8, out_rgba32f, nullptr, stream, elapsed_ms ? &ms[2] : nullptr);
+        report_adaptive_times(r, ms, elapsed_ms);
         return rc;
     });
 }
 extern "C" int ptl_renderer_adaptive_result(ptl_renderer* r, void** list, void** count) {
-    if (!r || !r->adaptive_list || !r->adaptive_count) return PTL_ERR_INVALID;
-    if (list) *list = r->adaptive_list;
-    if (count) *count = r->adaptive_count;
+    if (!r || r->adaptive_filled != ptl_renderer::AdaptiveDraw::frame) return PTL_ERR_INVALID;
+    if (list) *list = r->adaptive_lists;
+    if (count) *count = r->adaptive_counts;
     return PTL_OK;
 }
 extern "C" int ptl_renderer_adaptive_times(ptl_renderer* r, float ms3[3]) {
@@ -1562,31 +1589,17 @@ extern "C" int ptl_renderer_adaptive_times(ptl_renderer* r, float ms3[3]) {
     std::copy(r->adaptive_ms, r->adaptive_ms + 3, ms3);
     return PTL_OK;
 }
-// Adaptive anti-aliasing of a batch of staged slices (include/portal_amd.h has the contract): per run of slices staged with the same kernel,
-// pass 1 with every slice's `_aa_count` set to 1, the classification of the sub-frames it wrote, and the refine pass with the slices
-// re-staged from the snapshots -- their own `_aa_count` -- on the kernel the run was staged with.  Nothing is read back, nothing is rebuilt.
-// The texture holds of ptl_renderer_stage_slice stay until drop_staged_slices at the end: pass 1's launch releases no texel buffer.
+// A batch of staged slices: per run of slices staged with the same kernel, pass 1 with every slice's `_aa_count` set to 1, the
+// classification of the sub-frames it wrote, and the refine pass with the slices re-staged from the snapshots -- their own `_aa_count` --
+// on the kernel the run was staged with.  Nothing is read back, nothing is rebuilt.  The texture holds of ptl_renderer_stage_slice stay
+// until drop_staged_slices at the end: pass 1's launch releases no texel buffer.
 extern "C" int ptl_renderer_draw_slices_adaptive(ptl_renderer* r, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
                                                  void* stream, float* elapsed_ms) {
     if (!r || !frame || !out_rgba8 || n < 1 || n > 16 || frame->width <= 0 || frame->height <= 0) return PTL_ERR_INVALID;
-    if (frame->rb_stride != 1 || frame->rb_phase != 0 || frame->in_place) {
-        set_last_error("ptl_renderer_draw_slices_adaptive: a whole frame only (rb_phase 0, rb_stride 1, not in_place)");
-        return PTL_ERR_INVALID;
-    }
-    if ((long long)frame->width * frame->height > (1LL << 31)) return PTL_ERR_INVALID;
-    const size_t pixels = (size_t)frame->width * (size_t)frame->height;
-    if (slice_pixels < pixels) {
-        set_last_error("ptl_renderer_draw_slices_adaptive: slice_pixels is smaller than width * height");
-        return PTL_ERR_INVALID;
-    }
-    if (r->adaptive_threshold < -1 || r->adaptive_threshold > 255) {
-        set_last_error("ptl_renderer_draw_slices_adaptive: option adaptive_aa_threshold is outside -1 .. 255");
-        return PTL_ERR_INVALID;
-    }
-    if (!(r->flags & PTL_FLAG_REFINE_SLICES)) {
-        set_last_error("ptl_renderer_draw_slices_adaptive: the renderer was created without PTL_FLAG_REFINE_SLICES: its kernel has no refine entry over slices");
-        return PTL_ERR_INVALID;
-    }
+    if (int rc = check_adaptive_draw("ptl_renderer_draw_slices_adaptive", r, frame, &slice_pixels, PTL_FLAG_REFINE_SLICES,
+                                     "PTL_FLAG_REFINE_SLICES: its kernel has no refine entry over slices");
+        rc != PTL_OK)
+        return rc;
     const unsigned want = (1u << n) - 1u;
     if ((r->staged_mask & want) != want) {
         set_last_error("ptl_renderer_draw_slices_adaptive: slices 0 .. n-1 are not all staged (ptl_renderer_stage_slice) since the last launch");
@@ -1595,64 +1608,43 @@ extern "C" int ptl_renderer_draw_slices_adaptive(ptl_renderer* r, const ptl_fram
     if (r->device < 0) return PTL_ERR_NO_DEVICE;
     return guarded([&] {
         if (int jrc = join_lanes(r, stream); jrc != PTL_OK) return jrc;
-        int rc = PTL_OK;
-        if (r->adaptive_slices_capacity < pixels * (size_t)n) {
-            if (r->adaptive_slices_lists) ptl_device_free(r->adaptive_slices_lists);
-            r->adaptive_slices_lists = nullptr;
-            r->adaptive_slices_capacity = 0;
-            if (rc = ptl_device_alloc(r->device, pixels * (size_t)n * 4, &r->adaptive_slices_lists); rc != PTL_OK) return rc;
-            r->adaptive_slices_capacity = pixels * (size_t)n;
-        }
-        if (!r->adaptive_slices_counts)
-            if (rc = ptl_device_alloc(r->device, 16 * 4, &r->adaptive_slices_counts); rc != PTL_OK) return rc;
-        const unsigned long long stride = pixels;
-        r->adaptive_slices_stride = stride;
+        if (int arc = reserve_adaptive_lists(r, (size_t)frame->width * (size_t)frame->height, n, ptl_renderer::AdaptiveDraw::slices); arc != PTL_OK) return arc;
+        const unsigned long long stride = r->adaptive_stride;
         // With N = 1 in every slice the call is a plain draw_slices and the lists are empty: T = 255 flags nothing, no refine launch.
         bool plain = true;
         for (int j = 0; j < n; ++j) plain = plain && r->staged_aa_count[j] <= 1;
         float ms[3] = {0.0f, 0.0f, 0.0f};
         const int one = 1;
-        for (int j0 = 0; j0 < n && rc == PTL_OK;) {  // run by run, as ptl_renderer_draw_slices
-            ptl_kernel* k = r->staged_kernels[j0];
-            int j1 = j0 + 1;
-            while (j1 < n && r->staged_kernels[j1] == k) ++j1;
+        const int rc = for_each_staged_run(r, n, [&](ptl_kernel* k, int j0, int j1) {
             const int count = j1 - j0;
             void* out8 = static_cast<unsigned char*>(out_rgba8) + (size_t)j0 * slice_pixels * 4;
             void* out32 = out_rgba32f ? static_cast<float*>(out_rgba32f) + (size_t)j0 * slice_pixels * 4 : nullptr;
-            void* lists = static_cast<unsigned int*>(r->adaptive_slices_lists) + (size_t)j0 * stride;
-            void* counts = static_cast<unsigned int*>(r->adaptive_slices_counts) + j0;
+            void* lists = static_cast<unsigned int*>(r->adaptive_lists) + (size_t)j0 * stride;
+            void* counts = static_cast<unsigned int*>(r->adaptive_counts) + j0;
             float t[3] = {0.0f, 0.0f, 0.0f};
-            auto stage_run = [&] {
-                int src = PTL_OK;
-                for (int j = j0; j < j1 && src == PTL_OK; ++j) src = ptl_kernel_stage_slice_from(k, j - j0, r->staged_blocks[j].data(), r->staged_blocks[j].size());
-                return src;
-            };
-            rc = stage_run();
+            int rc = stage_run(r, k, j0, j1);
             for (int j = j0; j < j1 && rc == PTL_OK && !plain; ++j) rc = ptl_kernel_set_staged_uniform(k, j - j0, "_aa_count", PTL_I32, &one);
             if (rc == PTL_OK) rc = ptl_kernel_render_slices(k, frame, count, out8, out32, slice_pixels, stream, elapsed_ms ? &t[0] : nullptr);
             if (rc == PTL_OK)
                 rc = ptl_aa_edges_slices(r->device, out8, slice_pixels, count, frame->width, frame->height, plain ? 255 : r->adaptive_threshold, lists, stride, counts, stream,
                                          elapsed_ms ? &t[1] : nullptr);
             if (rc == PTL_OK && !plain) {
-                rc = stage_run();  // the snapshots again: every slice's own `_aa_count`
+                rc = stage_run(r, k, j0, j1);  // the snapshots again: every slice's own `_aa_count`
                 if (rc == PTL_OK) rc = ptl_kernel_render_slices_refine(k, frame, count, lists, stride, counts, out8, out32, slice_pixels, nullptr, stream, elapsed_ms ? &t[2] : nullptr);
             }
             for (int p = 0; p < 3; ++p) ms[p] += t[p];
-            j0 = j1;
-        }
-        if (elapsed_ms) {
-            *elapsed_ms = ms[0] + ms[1] + ms[2];
-            std::copy(ms, ms + 3, r->adaptive_ms);
-        }
+            return rc;
+        });
+        report_adaptive_times(r, ms, elapsed_ms);
         drop_staged_slices(r);
         return rc;
     });
 }
 extern "C" int ptl_renderer_adaptive_slices_result(ptl_renderer* r, void** lists, unsigned long long* list_stride, void** counts) {
-    if (!r || !r->adaptive_slices_lists || !r->adaptive_slices_counts) return PTL_ERR_INVALID;
-    if (lists) *lists = r->adaptive_slices_lists;
-    if (list_stride) *list_stride = r->adaptive_slices_stride;
-    if (counts) *counts = r->adaptive_slices_counts;
+    if (!r || r->adaptive_filled != ptl_renderer::AdaptiveDraw::slices) return PTL_ERR_INVALID;
+    if (lists) *lists = r->adaptive_lists;
+    if (list_stride) *list_stride = r->adaptive_stride;
+    if (counts) *counts = r->adaptive_counts;
     return PTL_OK;
 }
 extern "C" int ptl_renderer_draw_to_host(ptl_renderer* r, const ptl_frame* frame, uint8_t* host_rgba8, float* host_rgba32f,
@@ -2004,10 +1996,8 @@ extern "C" void ptl_renderer_destroy(ptl_renderer* r) {
     for (auto& l : r->lanes)
         if (l.done) ptl_event_destroy(l.done);  // (the lanes' streams belong to the process-wide pool)
     if (r->fence) ptl_event_destroy(r->fence);
-    if (r->adaptive_list) ptl_device_free(r->adaptive_list);  // (hipFree waits for the device: the last adaptive draw has finished)
-    if (r->adaptive_count) ptl_device_free(r->adaptive_count);
-    if (r->adaptive_slices_lists) ptl_device_free(r->adaptive_slices_lists);
-    if (r->adaptive_slices_counts) ptl_device_free(r->adaptive_slices_counts);
+    if (r->adaptive_lists) ptl_device_free(r->adaptive_lists);  // (hipFree waits for the device: the last adaptive draw has finished)
+    if (r->adaptive_counts) ptl_device_free(r->adaptive_counts);
     if (r->spec_kernel || r->dyn_kernel) {  // background re-JIT: `kernel` is one of these two
         ptl_kernel_destroy(r->spec_kernel);
         ptl_kernel_destroy(r->dyn_kernel);

@@ -442,6 +442,7 @@ static void apply_slices_entry(std::string& src) {
 
 // KernelOptions::refine_entry: the list-driven render entry of the adaptive anti-aliasing, in front of the host half of ptl_entry.h.
 // (KernelOptions::refine_slices_entry: the same place, the entry over the slices of a batch -- behind `apply_slices_entry`, whose shade_pixel_in it calls)
+// `entry`: device/ptl_refine_common.h followed by the entry's own header, as ONE text (embed_sources.py joins them; device_source() hands it out).
 static void apply_refine_entry(std::string& src, const char* entry) {
     const std::string anchor = "#else  // host build of the same source (oracle/host_build): rows [row_begin, row_end) of the frame\n";
     const size_t at = src.find(anchor);

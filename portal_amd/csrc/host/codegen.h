@@ -154,13 +154,14 @@ struct KernelOptions {
     // frame (src/main.rs:1798 re-draws with `_aa_start` windows one after the other) -- so that their ramps and tails overlap.  Applied to the
     // generated text by substitution (codegen.cpp `apply_slices_entry`): kernels built without it are byte for byte what they were.
     bool slices_entry = false;
-    // Adaptive anti-aliasing (PTL_FLAG_REFINE): the module gets a second render entry, `ptl_render_refine_kernel` (device/ptl_refine_entry.h), which
-    // shades the pixels of a device-side list instead of a rectangle.  Spliced into the generated text like the slices entry (codegen.cpp
-    // `apply_refine_entry`): kernels built without it are byte for byte what they were.  Not together with slices_entry.
+    // Adaptive anti-aliasing (PTL_FLAG_REFINE): the module gets a second render entry, `ptl_render_refine_kernel` (device/ptl_refine_entry.h, a thin
+    // entry around the list walk of device/ptl_refine_common.h), which shades the pixels of a device-side list instead of a rectangle.  Both texts are
+    // spliced in as one, like the slices entry (codegen.cpp `apply_refine_entry`): kernels built without it are byte for byte what they were.  Not
+    // together with slices_entry.
     bool refine_entry = false;
     // Adaptive anti-aliasing of a batch of slices (PTL_FLAG_REFINE_SLICES): the slices entry (implied) plus a list-driven entry over the same
-    // buffer of blocks, `ptl_render_refine_slices_kernel` (device/ptl_refine_slices_entry.h): slice z shades the pixels of ITS list with ITS
-    // block.  `apply_slices_entry` first, then the new entry spliced in where `apply_refine_entry` puts its own.  Not together with refine_entry.
+    // buffer of blocks, `ptl_render_refine_slices_kernel` (device/ptl_refine_slices_entry.h, the same walk once per slice): slice z shades the pixels
+    // of ITS list with ITS block.  `apply_slices_entry` first, then `apply_refine_entry` with this entry's text.  Not together with refine_entry.
     bool refine_slices_entry = false;
     // Affine rays (round 5): in a kernel whose every scene matrix is KNOWN to have the bottom row 0 0 0 1 (baked, or through its pattern) and
     // whose scene snippets never write a ray's w, every origin has w = 1 and every direction w = 0, and the products of a matrix with a ray

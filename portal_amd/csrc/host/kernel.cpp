@@ -772,6 +772,23 @@ static int upload_slices(ptl_kernel* k, const hip::Runtime* rt, void* stream, in
 
 static const char* const kSlicesLaunch = "hipModuleLaunchKernel(ptl_render_slices_kernel)";
 
+// One launch of an entry of the module, timed between the kernel's two events when `elapsed_ms` is given (the call then waits for it), and
+// marked as the kernel's most recent launch.  `label`: what a refused launch is reported as.
+static int timed_launch(ptl_kernel* k, const hip::Runtime* rt, hip::hipFunction_t fn, unsigned gx, unsigned gy, unsigned gz, unsigned threads, void** args, void* stream,
+                        float* elapsed_ms, const char* label) {
+    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
+    if (!hip_ok(rt, rt->hipModuleLaunchKernel(fn, gx, gy, gz, threads, 1, 1, 0, stream, args, nullptr), label)) return PTL_ERR_HIP;
+    k->last_stream = stream;
+    k->launched = true;
+    if (k->ev_done) rt->hipEventRecord(k->ev_done, stream);
+    if (elapsed_ms) {
+        rt->hipEventRecord(k->ev1, stream);
+        if (!hip_ok(rt, rt->hipEventSynchronize(k->ev1), "hipEventSynchronize")) return PTL_ERR_HIP;
+        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
+    }
+    return PTL_OK;
+}
+
 // The one render launch.  A module with the slices entry traces slices 0 .. n-1 of its buffer of blocks, slice z into out_rgba8 + z * slice_pixels
 // pixels; the plain entry (n = 1) reads the module's own block.  `label`: what a refused launch is reported as.
 static int launch_render(ptl_kernel* k, const hip::Runtime* rt, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
@@ -788,18 +805,9 @@ static int launch_render(ptl_kernel* k, const hip::Runtime* rt, const ptl_frame*
     // 256 threads = four 8x8 tiles side by side.  PTL_BLOCK_WAVES=1|2 (experiment, tools/variants.py) launches narrower workgroups.
     const unsigned waves = k->block_waves;
     unsigned gx = (unsigned)((width + 8 * waves - 1) / (8 * waves)), gy = (unsigned)nby;
-    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
-    if (!hip_ok(rt, rt->hipModuleLaunchKernel(k->fn, gx, gy, (unsigned)n, 64 * waves, 1, 1, 0, stream, k->sliced ? args : args + 2, nullptr), label)) return PTL_ERR_HIP;
-    if (k->sliced) k->staged_since_launch = false;  // what was staged is launched: retired texel buffers go with the next re-bind (hipFree waits for this launch)
-    k->last_stream = stream;
-    k->launched = true;
-    if (k->ev_done) rt->hipEventRecord(k->ev_done, stream);
-    if (elapsed_ms) {
-        rt->hipEventRecord(k->ev1, stream);
-        if (!hip_ok(rt, rt->hipEventSynchronize(k->ev1), "hipEventSynchronize")) return PTL_ERR_HIP;
-        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
-    }
-    return PTL_OK;
+    const int rc = timed_launch(k, rt, k->fn, gx, gy, (unsigned)n, 64 * waves, k->sliced ? args : args + 2, stream, elapsed_ms, label);
+    if (rc == PTL_OK && k->sliced) k->staged_since_launch = false;  // what was staged is launched: retired texel buffers go with the next re-bind (hipFree waits for this launch)
+    return rc;
 }
 
 extern "C" int ptl_kernel_max_slices(ptl_kernel* k) { return (k && k->sliced) ? kMaxSlices : 0; }
@@ -877,42 +885,48 @@ extern "C" int ptl_kernel_render(ptl_kernel* k, const ptl_frame* frame, void* ou
     return launch_render(k, rt, frame, 1, out_rgba8, out_rgba32f, 0, segments, stream, elapsed_ms, k->sliced ? kSlicesLaunch : "hipModuleLaunchKernel");
 }
 
-// The refine pass of the adaptive anti-aliasing: the module's second render entry (device/ptl_refine_entry.h) shades the `*count` pixels of
-// `list` -- both in device memory, read on the device -- with the uniforms set now, each lane storing its own pixel into the full frame.
-// A grid of fixed size, chosen from the frame size; the workgroups stride over the list.
-extern "C" int ptl_kernel_render_refine(ptl_kernel* k, const ptl_frame* frame, const void* list, const void* count, void* out_rgba8, void* out_rgba32f,
-                                        void* segments, void* stream, float* elapsed_ms) {
-    if (!k || !frame || !list || !count || frame->width <= 0 || frame->height <= 0) return PTL_ERR_INVALID;
+// ---- the refine pass of the adaptive anti-aliasing: the list-driven entries (device/ptl_refine_common.h) -----------------------------
+// A list names pixels of a whole frame, each as a 32-bit index.  `who`, `lists`: how the refusal names the caller and its argument.
+static int check_listed_frame(const char* who, const char* lists, const ptl_frame* frame) {
     if (frame->rb_stride != 1 || frame->rb_phase != 0 || frame->in_place) {
-        set_last_error("ptl_kernel_render_refine: the list names pixels of a whole frame (rb_phase 0, rb_stride 1, not in_place)");
+        set_last_error(std::string(who) + ": " + lists + " pixels of a whole frame (rb_phase 0, rb_stride 1, not in_place)");
         return PTL_ERR_INVALID;
     }
     if ((long long)frame->width * frame->height > (1LL << 31)) return PTL_ERR_INVALID;  // an entry is a 32-bit pixel index
+    return PTL_OK;
+}
+
+// The one refine launch: for every slice z < n, the counts[z] pixels of lists + z * list_stride -- both in device memory, read on the
+// device -- are shaded again, each lane storing its own pixel into out_* + z * slice_pixels pixels.  `over_slices`: the entry over the
+// module's buffer of blocks, whose staged slices are uploaded (with their prologue) like ptl_kernel_render_slices does; else the entry on
+// the module's own block with the uniforms set now, n = 1.  A grid of fixed size (gx, 1, n): a chunk of 256 entries per workgroup and
+// trip, at most 2 048 workgroups per launch (8 per CU) split evenly over the slices, which cover a frame's worth of entries in a few trips.
+static int launch_refine(ptl_kernel* k, bool over_slices, const ptl_frame* frame, int n, const void* lists, unsigned long long list_stride, const void* counts,
+                         void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels, void* segments, void* stream, float* elapsed_ms) {
+    const hip::Runtime* rt = hip::runtime(nullptr);
+    if (!hip_ok(rt, rt->hipSetDevice(k->device), "hipSetDevice")) return PTL_ERR_HIP;
+    if (int rc = over_slices ? upload_slices(k, rt, stream, n, false) : upload_uniforms(k, rt, stream); rc != PTL_OK) return rc;
+    int width = frame->width, height = frame->height;
+    void* blocks = k->dev_slices;
+    void* own_block[] = {&lists, &counts, &out_rgba8, &out_rgba32f, &width, &height, &segments};
+    void* slices[] = {&blocks, &slice_pixels, &lists, &list_stride, &counts, &out_rgba8, &out_rgba32f, &width, &height, &segments};
+    const long long chunks = ((long long)width * height + 255) / 256;
+    const unsigned gx = (unsigned)std::min<long long>(chunks, 2048 / n);
+    return timed_launch(k, rt, over_slices ? k->refine_slices_fn : k->refine_fn, gx, 1, (unsigned)n, 256, over_slices ? slices : own_block, stream, elapsed_ms,
+                        over_slices ? "hipModuleLaunchKernel(ptl_render_refine_slices_kernel)" : "hipModuleLaunchKernel(ptl_render_refine_kernel)");
+}
+
+// The refine pass of one frame: the `*count` pixels of `list`, with the uniforms set now.
+extern "C" int ptl_kernel_render_refine(ptl_kernel* k, const ptl_frame* frame, const void* list, const void* count, void* out_rgba8, void* out_rgba32f,
+                                        void* segments, void* stream, float* elapsed_ms) {
+    if (!k || !frame || !list || !count || frame->width <= 0 || frame->height <= 0) return PTL_ERR_INVALID;
+    if (int rc = check_listed_frame("ptl_kernel_render_refine", "the list names", frame); rc != PTL_OK) return rc;
     if (!k->has_refine) {
         set_last_error("ptl_kernel_render_refine: the kernel was not generated with the refine entry (PTL_FLAG_REFINE)");
         return PTL_ERR_INVALID;
     }
     if (k->device < 0 || !k->refine_fn) return PTL_ERR_NO_DEVICE;
-    const hip::Runtime* rt = hip::runtime(nullptr);
-    if (!hip_ok(rt, rt->hipSetDevice(k->device), "hipSetDevice")) return PTL_ERR_HIP;
-    if (int rc = upload_uniforms(k, rt, stream); rc != PTL_OK) return rc;
-    int width = frame->width, height = frame->height;
-    void* args[] = {&list, &count, &out_rgba8, &out_rgba32f, &width, &height, &segments};
-    // a chunk of 256 entries per workgroup and trip; 2 048 workgroups (8 per CU) cover a frame's worth of entries in a few trips
-    const long long chunks = ((long long)width * height + 255) / 256;
-    const unsigned grid = (unsigned)std::min<long long>(chunks, 2048);
-    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
-    if (!hip_ok(rt, rt->hipModuleLaunchKernel(k->refine_fn, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr), "hipModuleLaunchKernel(ptl_render_refine_kernel)"))
-        return PTL_ERR_HIP;
-    k->last_stream = stream;
-    k->launched = true;
-    if (k->ev_done) rt->hipEventRecord(k->ev_done, stream);
-    if (elapsed_ms) {
-        rt->hipEventRecord(k->ev1, stream);
-        if (!hip_ok(rt, rt->hipEventSynchronize(k->ev1), "hipEventSynchronize")) return PTL_ERR_HIP;
-        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
-    }
-    return PTL_OK;
+    return launch_refine(k, false, frame, 1, list, 0, count, out_rgba8, out_rgba32f, 0, segments, stream, elapsed_ms);
 }
 
 // One uniform inside slice `index` as it is staged now (not the kernel's current values): what a caller changes between two launches over
@@ -929,18 +943,12 @@ extern "C" int ptl_kernel_set_staged_uniform(ptl_kernel* k, int index, const cha
     return PTL_OK;
 }
 
-// The refine pass of an adaptive batch: the module's list-driven entry over slices (device/ptl_refine_slices_entry.h) shades, for every
-// staged slice z < n, the counts[z] pixels of lists + z * list_stride with that slice's uniforms into out_* + z * slice_pixels pixels.
-// Uploads the staged slices and runs their prologue like ptl_kernel_render_slices.  Grid (gx, 1, n), gx = min(ceil(W H / 256), 2048 / n):
-// at most 2 048 workgroups per launch (8 per CU, what the single-frame entry launches), split evenly over the slices.
+// The refine pass of an adaptive batch: for every staged slice z < n, the counts[z] pixels of lists + z * list_stride with that slice's
+// uniforms into out_* + z * slice_pixels pixels.
 extern "C" int ptl_kernel_render_slices_refine(ptl_kernel* k, const ptl_frame* frame, int n, const void* lists, unsigned long long list_stride, const void* counts,
                                                void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels, void* segments, void* stream, float* elapsed_ms) {
     if (!k || !frame || !lists || !counts || frame->width <= 0 || frame->height <= 0) return PTL_ERR_INVALID;
-    if (frame->rb_stride != 1 || frame->rb_phase != 0 || frame->in_place) {
-        set_last_error("ptl_kernel_render_slices_refine: the lists name pixels of a whole frame (rb_phase 0, rb_stride 1, not in_place)");
-        return PTL_ERR_INVALID;
-    }
-    if ((long long)frame->width * frame->height > (1LL << 31)) return PTL_ERR_INVALID;  // an entry is a 32-bit pixel index
+    if (int rc = check_listed_frame("ptl_kernel_render_slices_refine", "the lists name", frame); rc != PTL_OK) return rc;
     const unsigned long long pixels = (unsigned long long)frame->width * (unsigned long long)frame->height;
     if (list_stride < pixels || slice_pixels < pixels) {
         set_last_error("ptl_kernel_render_slices_refine: list_stride and slice_pixels must be at least width * height");
@@ -956,27 +964,9 @@ extern "C" int ptl_kernel_render_slices_refine(ptl_kernel* k, const ptl_frame* f
         return PTL_ERR_INVALID;
     }
     if (k->device < 0 || !k->refine_slices_fn || !k->sliced) return PTL_ERR_NO_DEVICE;
-    const hip::Runtime* rt = hip::runtime(nullptr);
-    if (!hip_ok(rt, rt->hipSetDevice(k->device), "hipSetDevice")) return PTL_ERR_HIP;
-    if (int rc = upload_slices(k, rt, stream, n, false); rc != PTL_OK) return rc;
-    int width = frame->width, height = frame->height;
-    void* blocks = k->dev_slices;
-    void* args[] = {&blocks, &slice_pixels, &lists, &list_stride, &counts, &out_rgba8, &out_rgba32f, &width, &height, &segments};
-    const long long chunks = ((long long)pixels + 255) / 256;
-    const unsigned gx = (unsigned)std::min<long long>(chunks, 2048 / n);
-    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
-    if (!hip_ok(rt, rt->hipModuleLaunchKernel(k->refine_slices_fn, gx, 1, (unsigned)n, 256, 1, 1, 0, stream, args, nullptr), "hipModuleLaunchKernel(ptl_render_refine_slices_kernel)"))
-        return PTL_ERR_HIP;
-    k->staged_since_launch = false;  // what was staged is launched (launch_render)
-    k->last_stream = stream;
-    k->launched = true;
-    if (k->ev_done) rt->hipEventRecord(k->ev_done, stream);
-    if (elapsed_ms) {
-        rt->hipEventRecord(k->ev1, stream);
-        if (!hip_ok(rt, rt->hipEventSynchronize(k->ev1), "hipEventSynchronize")) return PTL_ERR_HIP;
-        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
-    }
-    return PTL_OK;
+    const int rc = launch_refine(k, true, frame, n, lists, list_stride, counts, out_rgba8, out_rgba32f, slice_pixels, segments, stream, elapsed_ms);
+    if (rc == PTL_OK) k->staged_since_launch = false;  // what was staged is launched (launch_render)
+    return rc;
 }
 
 extern "C" int ptl_kernel_render_to_host(ptl_kernel* k, const ptl_frame* frame, uint8_t* host_rgba8, float* host_rgba32f,

@@ -78,6 +78,20 @@ int load_kernel(int device, const char* file, const char* entry, LoadedKernel** 
     return PTL_OK;
 }
 
+// `launch` (the stream work of one call, -> a HIP error code) between the kernel's two events when `elapsed_ms` is given: the call then
+// waits for it and reads the time.  -> what `launch` returned.
+template <typename Launch>
+int timed(const hip::Runtime* rt, LoadedKernel* k, void* stream, float* elapsed_ms, Launch launch) {
+    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
+    const int err = launch();
+    if (err == 0 && elapsed_ms) {
+        rt->hipEventRecord(k->ev1, stream);
+        rt->hipEventSynchronize(k->ev1);
+        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
+    }
+    return err;
+}
+
 // What ptl_average_images and ptl_average_to_yuv420p10 share: a kernel over N sub-frames with two entries (up to 64 pointers in the
 // kernel arguments, beyond in a device table), launched as `lanes` lanes in workgroups of 256 (grid-stride beyond the cap) on `stream`.
 // The kernel's arguments are (frames, n, tail...).
@@ -124,21 +138,35 @@ int launch_over_subframes(int device, const SubframeKernel& kernel, const void* 
     long cap = 256 * 16;  // grid-stride beyond 16 workgroups per CU
     if (const char* c = std::getenv("PTL_AVERAGE_IMAGES_GRID_CAP")) cap = std::atol(c) > 0 ? std::atol(c) : cap;
     if (blocks > cap) blocks = cap;
-    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
-    int err = rt->hipModuleLaunchKernel(k->fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream, args.data(), nullptr);
+    const int err = timed(rt, k, stream, elapsed_ms, [&] { return rt->hipModuleLaunchKernel(k->fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream, args.data(), nullptr); });
     if (err != 0) {
         if (dev_table) rt->hipFree(dev_table);
         set_last_error(std::string("hipModuleLaunchKernel(") + kernel.what + "): " + rt->hipGetErrorString(err));
         return PTL_ERR_HIP;
     }
-    if (elapsed_ms) {
-        rt->hipEventRecord(k->ev1, stream);
-        rt->hipEventSynchronize(k->ev1);
-        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
-    }
     if (dev_table) {
         rt->hipStreamSynchronize(stream);  // hipFree would wait for the device anyway
         rt->hipFree(dev_table);
+    }
+    return PTL_OK;
+}
+
+// What ptl_aa_edges and ptl_aa_edges_slices share: the classification kernel in `file` over `n` frames, a 256-thread workgroup per 64x32
+// pixel region and frame.  The `n` counts are reset on `stream` by the call itself, inside the time it reports.
+int launch_aa_edges(int device, const char* file, const char* entry, const char* what, void** args, void* counts, int n, int width, int height, void* stream,
+                    float* elapsed_ms) {
+    LoadedKernel* k = nullptr;
+    if (int rc = load_kernel(device, file, entry, &k); rc != PTL_OK) return rc;
+    const hip::Runtime* rt = hip::runtime(nullptr);
+    rt->hipSetDevice(device);
+    const int err = timed(rt, k, stream, elapsed_ms, [&] {
+        const int reset = rt->hipMemsetAsync(counts, 0, 4 * (size_t)n, stream);
+        return reset != 0 ? reset : rt->hipModuleLaunchKernel(k->fn, (unsigned)((width + 63) / 64), (unsigned)((height + 31) / 32), (unsigned)n, 256, 1, 1, 0, stream, args, nullptr);
+    });
+    if (err != 0) {
+        set_last_error(std::string("hipModuleLaunchKernel(") + what + "): " + rt->hipGetErrorString(err));
+        rt->hipGetLastError();
+        return PTL_ERR_HIP;
     }
     return PTL_OK;
 }
@@ -179,25 +207,8 @@ extern "C" int ptl_aa_edges(int device, const void* frame_rgba8, int width, int 
     if (!frame_rgba8 || !list || !count || width <= 0 || height <= 0 || threshold < -1 || threshold > 255) return PTL_ERR_INVALID;
     if ((long long)width * height > (1LL << 31)) return PTL_ERR_INVALID;  // an entry is a 32-bit pixel index
     if ((reinterpret_cast<uintptr_t>(frame_rgba8) | reinterpret_cast<uintptr_t>(list) | reinterpret_cast<uintptr_t>(count)) & 3u) return PTL_ERR_INVALID;
-    LoadedKernel* k = nullptr;
-    if (int rc = load_kernel(device, "aa_edges.hsaco", "ptl_aa_edges_kernel", &k); rc != PTL_OK) return rc;
-    const hip::Runtime* rt = hip::runtime(nullptr);
-    rt->hipSetDevice(device);
-    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
-    int err = rt->hipMemsetAsync(count, 0, 4, stream);
     void* args[] = {&frame_rgba8, &width, &height, &threshold, &list, &count};
-    if (err == 0) err = rt->hipModuleLaunchKernel(k->fn, (unsigned)((width + 63) / 64), (unsigned)((height + 31) / 32), 1, 256, 1, 1, 0, stream, args, nullptr);
-    if (err != 0) {
-        set_last_error(std::string("hipModuleLaunchKernel(aa_edges): ") + rt->hipGetErrorString(err));
-        rt->hipGetLastError();
-        return PTL_ERR_HIP;
-    }
-    if (elapsed_ms) {
-        rt->hipEventRecord(k->ev1, stream);
-        rt->hipEventSynchronize(k->ev1);
-        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
-    }
-    return PTL_OK;
+    return launch_aa_edges(device, "aa_edges.hsaco", "ptl_aa_edges_kernel", "aa_edges", args, count, 1, width, height, stream, elapsed_ms);
 }
 
 // ptl_aa_edges_slices: the same classification over a stack of `n` frames in one launch (portal_amd/csrc/kernels/aa_edges_slices.hip):
@@ -211,26 +222,8 @@ extern "C" int ptl_aa_edges_slices(int device, const void* frames_rgba8, unsigne
     if (slice_pixels < pixels || list_stride < pixels) return PTL_ERR_INVALID;  // a slice's frame and list hold a whole frame: neighbours never overlap
     if ((reinterpret_cast<uintptr_t>(frames_rgba8) | reinterpret_cast<uintptr_t>(lists) | reinterpret_cast<uintptr_t>(counts)) & 3u) return PTL_ERR_INVALID;
     if (device < 0) return PTL_ERR_NO_DEVICE;
-    LoadedKernel* k = nullptr;
-    if (int rc = load_kernel(device, "aa_edges_slices.hsaco", "ptl_aa_edges_slices_kernel", &k); rc != PTL_OK) return rc;
-    const hip::Runtime* rt = hip::runtime(nullptr);
-    rt->hipSetDevice(device);
-    if (elapsed_ms) rt->hipEventRecord(k->ev0, stream);
-    int err = rt->hipMemsetAsync(counts, 0, 4 * (size_t)n, stream);
     void* args[] = {&frames_rgba8, &slice_pixels, &width, &height, &threshold, &lists, &list_stride, &counts};
-    if (err == 0)
-        err = rt->hipModuleLaunchKernel(k->fn, (unsigned)((width + 63) / 64), (unsigned)((height + 31) / 32), (unsigned)n, 256, 1, 1, 0, stream, args, nullptr);
-    if (err != 0) {
-        set_last_error(std::string("hipModuleLaunchKernel(aa_edges_slices): ") + rt->hipGetErrorString(err));
-        rt->hipGetLastError();
-        return PTL_ERR_HIP;
-    }
-    if (elapsed_ms) {
-        rt->hipEventRecord(k->ev1, stream);
-        rt->hipEventSynchronize(k->ev1);
-        rt->hipEventElapsedTime(elapsed_ms, k->ev0, k->ev1);
-    }
-    return PTL_OK;
+    return launch_aa_edges(device, "aa_edges_slices.hsaco", "ptl_aa_edges_slices_kernel", "aa_edges_slices", args, counts, n, width, height, stream, elapsed_ms);
 }
 
 extern "C" int ptl_y4m_header(int width, int height, int fps, char* buf, size_t cap) {

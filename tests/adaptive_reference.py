@@ -6,7 +6,12 @@
 
 P: the RGBA8 frame drawn with one sample per pixel, F: the frame drawn with the full `aa_count`, T: an integer in -1 .. 255.
 Coordinates clamp to the frame, alpha is ignored.
+
+Behind the contract: the small helpers tests/test_adaptive_aa.py and tests/test_adaptive_slices.py share.
 """
+import os
+import re
+
 import numpy as np
 
 
@@ -42,3 +47,31 @@ def adaptive_frame(p: np.ndarray, f: np.ndarray, threshold: int) -> np.ndarray:
 def select(mask: np.ndarray, f: np.ndarray, p: np.ndarray) -> np.ndarray:
     assert mask.shape == f.shape[:2] == p.shape[:2]
     return np.where(mask[:, :, None], f, p)
+
+
+# ---- shared by the two test files -------------------------------------------------------------------
+def resource_usage(stderr):
+    """hipcc -Rpass-analysis=kernel-resource-usage -> {kernel: {"VGPRs" | "ScratchSize [bytes/lane]" | "LDS Size [bytes/block]": value}}."""
+    usage, name = {}, None
+    for line in stderr.splitlines():
+        m = re.search(r"Function Name: (\w+)", line)
+        if m:
+            name = m.group(1)
+        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|VGPRs): (\d+)", line)
+        if m and name:
+            usage.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    return usage
+
+
+def exe(pa):
+    return os.path.join(os.path.dirname(pa.__file__), "portal-amd")
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def cuda_words(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32).copy()).cuda()

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import adaptive_reference as ar
+from tests.adaptive_reference import bits as _bits, cuda_words as _cuda_words, exe as _exe, resource_usage as _resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -120,18 +121,6 @@ def test_layer_two_validates_before_any_gpu_call(pa):
         pa.SceneRenderer(pa.Scene.from_file(pa.scene_path("basics")), device=-1, flags=pa.FLAG_REFINE | pa.FLAG_SLICES)
 
 
-def _resource_usage(stderr):
-    usage, name = {}, None
-    for line in stderr.splitlines():
-        m = re.search(r"Function Name: (\w+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|VGPRs): (\d+)", line)
-        if m and name:
-            usage.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    return usage
-
-
 def test_make_kernels_builds_aa_edges_without_scratch(pa, tmp_path):
     subprocess.run(["make", "kernels"], cwd=ROOT, check=True, capture_output=True)
     assert os.path.getsize(os.path.join(ROOT, "portal_amd", "kernels", "aa_edges.hsaco")) > 1000
@@ -177,10 +166,6 @@ def test_source_with_the_flag_compiles_for_gfx950_without_scratch(pa, scene_name
     assert refine[".private_segment_fixed_size"] == 0 and refine[".vgpr_spill_count"] == 0
     assert render[".private_segment_fixed_size"] == 0
     assert 0 < refine[".vgpr_count"] <= 128  # (the render entry's launch bounds: 256 threads)
-
-
-def _exe(pa):
-    return os.path.join(os.path.dirname(pa.__file__), "portal-amd")
 
 
 @pytest.mark.parametrize("cmd,extra,reason", [("render-frame", ["--adaptive-aa", "-2"], "-1 .. 255"), ("render-frame", ["--adaptive-aa", "256"], "-1 .. 255"),
@@ -282,10 +267,6 @@ def _renderer(pa, scene_name, build, options=None, extra_flags=0):
     return _renderers[key]
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _plain_and_full(r, w, h):
     r.set_option("aa_count", 1)
     p = r.draw(w, h, rgba8=True, rgba32f=True)
@@ -359,11 +340,13 @@ def test_adaptive_draw_with_both_eyes_in_one_wave(gpu):
 
 # ---- the refine entry through layer 1: lists the caller made ---------------------------------------
 def _refine_grid_cap():
-    """`std::min<long long>(chunks, 2048)` of ptl_kernel_render_refine (portal_amd/csrc/host/kernel.cpp): the workgroups of a refine launch
-    at most, 256 entries each and trip.  Read from the source, so a changed cap fails the second-trip test instead of leaving it vacuous."""
+    """`std::min<long long>(chunks, 2048 / n)` of the refine launcher behind ptl_kernel_render_refine (portal_amd/csrc/host/kernel.cpp), which has
+    n = 1: the workgroups of a refine launch at most, 256 entries each and trip.  Read from the source, so a changed cap fails the second-trip
+    test instead of leaving it vacuous."""
     src = open(os.path.join(ROOT, "portal_amd", "csrc", "host", "kernel.cpp")).read()
-    m = re.findall(r"const unsigned grid = \(unsigned\)std::min<long long>\(chunks, (\d+)\);", src)
-    assert len(m) == 1, "ptl_kernel_render_refine no longer spells its grid as min(chunks, N)"
+    m = re.findall(r"const unsigned gx = \(unsigned\)std::min<long long>\(chunks, (\d+) / n\);", src)
+    assert len(m) == 1, "the refine launcher no longer spells its grid as min(chunks, N / n)"
+    assert "return launch_refine(k, false, frame, 1, list, 0, count," in src, "ptl_kernel_render_refine no longer launches with n = 1"
     return int(m[0])
 
 
@@ -373,12 +356,6 @@ def test_refine_grid_cap_is_what_the_second_trip_test_crosses():
 
 
 GUARD_PIXELS = 16  # behind both outputs: entry W*H, if it were not skipped, would land on the first of them
-
-
-def _cuda_words(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32).copy()).cuda()
 
 
 def _refine_through_layer_one(pa, r, w, h, entries, count, start8=None, start32=None, segments=False):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import adaptive_reference as ar
+from tests.adaptive_reference import bits as _bits, cuda_words as _cuda_words, exe as _exe, resource_usage as _resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -72,18 +73,6 @@ def test_source_with_the_flag_compiles_for_gfx950_without_scratch(pa, scene_name
 
 def test_source_with_the_flag_and_the_segment_counter_compiles(pa):
     _compiles_with_both_entries(pa, "basics", pa.FLAG_COUNT_SEGMENTS | pa.FLAG_REFINE_SLICES, "count segments")
-
-
-def _resource_usage(stderr):
-    usage, name = {}, None
-    for line in stderr.splitlines():
-        m = re.search(r"Function Name: (\w+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|VGPRs): (\d+)", line)
-        if m and name:
-            usage.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    return usage
 
 
 def test_make_kernels_builds_aa_edges_slices_without_scratch(pa, tmp_path):
@@ -190,10 +179,6 @@ def test_layer_two_validates_before_any_gpu_call(pa):
     assert L.ptl_renderer_adaptive_slices_result(r._h, None, None, None) == INVALID  # still no adaptive draw
 
 
-def _exe(pa):
-    return os.path.join(os.path.dirname(pa.__file__), "portal-amd")
-
-
 @pytest.mark.parametrize("cmd,extra,reason", [("render", ["--clip-adaptive-aa", "256"], "-1 .. 255"), ("render", ["--clip-adaptive-aa", "-2"], "-1 .. 255"),
                                               ("render-frame", ["--clip-adaptive-aa"], "render"), ("render-frame", ["--clip-adaptive-aa", "4"], "render")])
 def test_cli_refuses_while_the_arguments_are_parsed(pa, tmp_path, cmd, extra, reason):
@@ -213,16 +198,6 @@ def gpu(pa):
     if pa.device_count() < 1:
         pytest.fail("no HIP device visible: the render path has no CPU fallback")
     return pa
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _cuda_words(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32).copy()).cuda()
 
 
 def _words(t):
@@ -536,11 +511,11 @@ def test_refine_entry_over_slices_counts_the_segments_of_its_lists(gpu):
 
 # ---- layer 2 ------------------------------------------------------------------------------------------
 def _refine_slices_grid(n, pixels):
-    """The grid rule of ptl_kernel_render_slices_refine, read from the source so that a changed rule fails the second-trip test instead of
-    leaving it vacuous."""
+    """The grid rule of the refine launcher behind ptl_kernel_render_slices_refine, read from the source so that a changed rule fails the
+    second-trip test instead of leaving it vacuous."""
     src = open(os.path.join(ROOT, "portal_amd", "csrc", "host", "kernel.cpp")).read()
     m = re.findall(r"const unsigned gx = \(unsigned\)std::min<long long>\(chunks, (\d+) / n\);", src)
-    assert len(m) == 1, "ptl_kernel_render_slices_refine no longer spells its grid as min(chunks, N / n)"
+    assert len(m) == 1, "the refine launcher no longer spells its grid as min(chunks, N / n)"
     return min((pixels + 255) // 256, int(m[0]) // n)
 
 
@@ -627,6 +602,43 @@ def test_adaptive_slices_are_the_reference_selection_of_draws_one_by_one(gpu, sc
     with pytest.raises(pa.PortalError, match="not all staged"):  # launching again without staging: refused
         r.draw_slices_adaptive(frame, n, d8.data_ptr(), slice_pixels=pixels)
     r.set_option("aa_count", aa)
+
+
+@pytest.mark.gpu
+def test_each_kind_of_adaptive_draw_hands_out_its_own_result_only(gpu):
+    """basics, unspecialised, 64x36, aa 2, T = 4, two slices.  The renderer keeps ONE set of list buffers for both kinds of adaptive draw:
+    after draw_slices_adaptive on a FLAG_REFINE_SLICES renderer adaptive_slices_result() hands them out and adaptive_result() refuses; after
+    draw_adaptive on a FLAG_REFINE renderer it is the other way round."""
+    pa = gpu
+    w, h, n, aa, t = 64, 36, 2, 2, 4
+
+    def fresh(flags):  # renderers of their own: no earlier adaptive draw of another test
+        scene = pa.Scene.from_file(pa.scene_path("basics"))
+        scene.init_animation(scene.animations()[0][0])
+        r = pa.SceneRenderer(scene, device=0, flags=flags)
+        r.set_option("render_depth", 12)
+        for result in (r.adaptive_result, r.adaptive_slices_result):
+            with pytest.raises(pa.PortalError):
+                result()
+        return r
+
+    r = fresh(pa.FLAG_REFINE_SLICES)
+    _stage_all(r, pa.Frame(w, h, 0, 1), n, aa)
+    _, _, counts, _ = _draw_slices_adaptive(pa, r, w, h, n, t)  # (reads adaptive_slices_result itself)
+    assert all(0 < c < w * h for c in counts), counts  # a refined edge in both slices
+    lists_ptr, stride, counts_ptr = r.adaptive_slices_result()
+    assert lists_ptr and counts_ptr and stride >= w * h
+    with pytest.raises(pa.PortalError):
+        r.adaptive_result()
+    single = fresh(pa.FLAG_REFINE)
+    _enter_state(single, 0, n)
+    single.set_option("aa_count", aa)
+    one = single.draw_adaptive(w, h, threshold=t)
+    assert one["count"] == int(counts[0])
+    list_ptr, count_ptr = single.adaptive_result()
+    assert list_ptr and count_ptr
+    with pytest.raises(pa.PortalError):
+        single.adaptive_slices_result()
 
 
 @pytest.mark.gpu
