@@ -11,7 +11,7 @@ SRCS     := ron.cpp formula.cpp scene.cpp glsl_translate.cpp glsl_bound.cpp glsl
 OBJS     := $(SRCS:%.cpp=$(OBJDIR)/%.o)
 LIB      := portal_amd/libportal_amd.so
 CLI      := portal_amd/portal-amd
-KERNELS  := portal_amd/kernels/fb_store.hsaco portal_amd/kernels/average_images.hsaco portal_amd/kernels/yuv420p10.hsaco portal_amd/kernels/aa_edges.hsaco portal_amd/kernels/aa_edges_slices.hsaco
+KERNELS  := portal_amd/kernels/fb_store.hsaco portal_amd/kernels/average_images.hsaco portal_amd/kernels/yuv420p10.hsaco portal_amd/kernels/yuv420p10_f32.hsaco portal_amd/kernels/aa_edges.hsaco portal_amd/kernels/aa_edges_slices.hsaco
 
 all: $(LIB) $(CLI)
 

@@ -534,6 +534,25 @@ int ptl_average_images(int device, const void* const* frames_rgba8, int n_frames
 int ptl_average_to_yuv420p10(int device, const void* const* frames_rgba8, int n_frames, void* out_yuv, int width, int height, void* stream,
                              float* elapsed_ms);
 size_t ptl_yuv420p10_frame_bytes(int width, int height);
+/* Deep colour: the same frame made from the UN-QUANTISED sub-frames, so that its 10 bits carry 10 bits of signal (the frame above is a
+ * function of 8-bit values: a 1024-step grey ramp gives 256 luma codes there, 1024 here).  Input: n_frames (1 .. 256) RGBA32F sub-frames
+ * (DEVICE pointers, 16-byte aligned, W*H pixels of four binary32 values) as the out_rgba32f argument of any render call writes them:
+ * gamma-2 encoded values, alpha ignored.  ONE quantisation, to 16 bits, per channel value v of a sub-frame (unorm8's rule at 16 bits):
+ *   q(v) = 0 if !(v > 0) (NaN, -0, negatives), 65535 if v >= 1 (+inf), else (u32) floor(v * 65535.0f + 0.5f)
+ * with the product and the sum each rounded to binary32 (no fused multiply-add).  Integers from there on, per pixel and channel:
+ *   M = floor((sum over the sub-frames of q^2) / n)           (64-bit: the sum stays below 2^40)
+ *   E = the integer e with e (e - 1) < M <= e (e + 1)         (= floor(sqrt(M) + 1/2); E = 0 for M = 0; for n = 1, E = q)
+ * A(x, y) = (E_R, E_G, E_B), 16-bit gamma-encoded.  BT.709 on these, full range, 10 bit, siting and layout as above:
+ *   Y  = (13920 E_R + 46826 E_G + 4727 E_B + (1 << 21)) >> 22                                 per pixel, unsigned 32-bit
+ *   S_c = sum over dy = 0, 1 of A_c(2i-1, 2j+dy) + 2 A_c(2i, 2j+dy) + A_c(2i+1, 2j+dy)         coordinates clamped (0 .. 524 280)
+ *   Cb = min(1023, (-15003 S_R - 50470 S_G + 65473 S_B + (512 << 26) + (1 << 25)) >> 26)      64-bit; both accumulators stay positive
+ *   Cr = min(1023, ( 65473 S_R - 59470 S_G -  6003 S_B + (512 << 26) + (1 << 25)) >> 26)
+ * (coefficients round(K * 1023 / 65535 * 2^22); every grey q gives Y = round(1023 q / 65535) and Cb = Cr = 512; within 0.53 codes of the
+ * real-valued H.273 definition).  out_yuv: ptl_yuv420p10_frame_bytes(w, h) bytes, the layout above; the Y4M header is the same.
+ * Any width, height >= 1 with W*H <= 2^28 (a sub-frame is addressed with 32-bit byte offsets).  Validation, stream and timing are
+ * those of ptl_average_to_yuv420p10.  (`portal-amd render --frames y4m --deep-colour`.) */
+int ptl_average_f32_to_yuv420p10(int device, const void* const* frames_rgba32f, int n_frames, void* out_yuv, int width, int height, void* stream,
+                                 float* elapsed_ms);
 /* ---- adaptive anti-aliasing: supersample only the pixels that sit on an edge (opt-in, approximate by design) ------------------------
  * Every anti-aliasing sample costs a full trace, and most pixels of a frame are flat walls and smooth gradients whose centre sample is
  * already the final 8-bit colour.  An adaptive draw traces ONE sample per pixel, classifies the frame it got, and traces the full

@@ -183,6 +183,7 @@ def _load() -> C.CDLL:
         "ptl_deinterleave_rows": (ci, [vp, P(Frame), vp]),
         "ptl_average_images": (ci, [ci, P(vp), ci, vp, ci, ci, vp, P(C.c_float)]),
         "ptl_average_to_yuv420p10": (ci, [ci, P(vp), ci, vp, ci, ci, vp, P(C.c_float)]),
+        "ptl_average_f32_to_yuv420p10": (ci, [ci, P(vp), ci, vp, ci, ci, vp, P(C.c_float)]),
         "ptl_yuv420p10_frame_bytes": (cs, [ci, ci]),
         "ptl_aa_edges": (ci, [ci, vp, ci, ci, ci, vp, vp, vp, P(C.c_float)]),
         "ptl_kernel_render_refine": (ci, [vp, P(Frame), vp, vp, vp, vp, vp, vp, P(C.c_float)]),
@@ -877,6 +878,17 @@ def average_to_yuv420p10_device(frame_ptrs, out_ptr: int, width: int, height: in
     ms = C.c_float()
     _check(lib().ptl_average_to_yuv420p10(device, arr, len(frame_ptrs), C.c_void_p(out_ptr), width, height, C.c_void_p(stream or None), C.byref(ms) if timed else None),
            "average_to_yuv420p10")
+    return ms.value if timed else None
+
+
+def average_f32_to_yuv420p10_device(frame_ptrs, out_ptr: int, width: int, height: int, device: int = 0, stream: int = 0, timed: bool = False):
+    """ptl_average_f32_to_yuv420p10 on DEVICE buffers given as integer addresses: the deep-colour form of `average_to_yuv420p10_device`.
+    The sub-frames are RGBA32F (what a draw writes as `rgba32f`, 16 bytes per pixel); they are quantised once, to 16 bits, before the
+    10-bit frame (`yuv420p10_frame_bytes` bytes at out_ptr, the same layout)."""
+    arr = (C.c_void_p * len(frame_ptrs))(*frame_ptrs)
+    ms = C.c_float()
+    _check(lib().ptl_average_f32_to_yuv420p10(device, arr, len(frame_ptrs), C.c_void_p(out_ptr), width, height, C.c_void_p(stream or None), C.byref(ms) if timed else None),
+           "average_f32_to_yuv420p10")
     return ms.value if timed else None
 
 

@@ -19,6 +19,7 @@ struct Options {
     std::string scene, clips, output = "frame.png", asset_root = ".", stage, animation, camera, scenes_dir = "scenes", out_dir = ".", starts_with;
     bool have_camera = false, stereo = false, skip_existing = true;
     bool y4m = false;     // render --frames y4m: frames leave as one Y4M stream instead of PNG files
+    bool deep_colour = false;  // render --frames y4m --deep-colour: the stream's frames are made from the float sub-frames (ptl_average_f32_to_yuv420p10)
     int batch = -1;       // render --batch-subframes 0|1: one launch for a frame's blur sub-frames (default: on where 2 <= blur <= 16)
     std::vector<std::pair<std::string, double>> sets;  // --set name=value
     bool timing = false;  // --timing: wait for every kernel and report GPU milliseconds (serialises host and GPU)

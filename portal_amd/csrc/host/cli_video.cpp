@@ -1,6 +1,6 @@
 // cli_video.cpp -- `portal-amd render <scenes> [clips]`, the offline counterpart of the reference's `portal render` (src/main.rs:2757-2874 +
 // render_animation src/main.rs:1758-1873).  What is here: the host side of the clip pipeline (EncoderPool, PinnedFrames, FramePipeline), the
-// two forms a clip's frames leave in (FrameOutput: PNG files for ffmpeg, or one Y4M stream), what lives as long as a scene's clips (SceneRun)
+// forms a clip's frames leave in (FrameOutput: PNG files for ffmpeg, or one Y4M stream made from the RGBA8 or from the float sub-frames), what lives as long as a scene's clips (SceneRun)
 // and as long as one clip (ClipRun), the clip loop (render_clip), the workers that compile the next clips' kernels (Prefetcher) and `render`.
 // Argument parsing and every other command are in cli.cpp; what both share is in cli_common.h.
 //
@@ -297,7 +297,7 @@ struct Clip {
     bool specialise = false;  // it gets a clip-constant kernel: that repays its extra JIT (~1 s) only on a clip with enough work
 };
 
-// What lives as long as a scene's clips.  Released in reverse order: the pipeline, the sub-frame block, the renderer, the scene.
+// What lives as long as a scene's clips.  Released in reverse order: the pipeline, the sub-frame blocks, the renderer, the scene.
 struct SceneRun {
     SceneRun(const Options& o, std::string name) : o(o), name(std::move(name)) {}
     const Options& o;
@@ -311,10 +311,12 @@ struct SceneRun {
     RendererPtr r;
     std::unique_ptr<void, HandleFree> subframe_block;  // ONE allocation, sub-frame j at j * bytes: what the one-launch form writes (slice z behind slice z - 1)
     std::vector<void*> subframes;
+    std::unique_ptr<void, HandleFree> float_block;  // --deep-colour only: the same sub-frames as RGBA32F (16 bytes per pixel), one allocation, laid out the same way
+    std::vector<void*> float_subframes;             // (empty without the option)
     FramePipeline pipe;
 };
 
-// ---- the two forms a clip's frames leave in ------------------------------------------------------
+// ---- the forms a clip's frames leave in ------------------------------------------------------
 // One object per clip.  It alone knows how the clip opens, whether a frame is already there, where a sub-frame is drawn and which kernel
 // makes the result of them, how many bytes leave the card, what the host does with a downloaded frame, and how the clip ends.
 class FrameOutput {
@@ -326,6 +328,7 @@ public:
     virtual int open() = 0;                   // 0, or the exit status
     virtual int check() { return 0; }         // before every frame: 0 while frames can still leave, else the exit status (reported)
     virtual bool have(int i) const = 0;       // frame i is already there: it is not drawn again
+    virtual bool wants_float() const { return false; }  // the sub-frames are also drawn as RGBA32F (run.float_subframes): make_result() reads those
     virtual bool draws_result() const = 0;    // a frame of ONE sub-frame that needs no kernel is drawn where the result is expected, make_result() not called
     virtual int make_result(void* result, float* ms) = 0;  // the kernel that turns the --motion-blur-frames sub-frames into the result
     // the host's part: `pixels` (page-locked, to give back) hold frame i once `arrived` (an event, to destroy) has happened
@@ -444,7 +447,19 @@ private:
     EncoderPool writer_;  // (declared behind the stream: it finishes before the stream closes)
 };
 
-std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, size_t max_pending) {  // the ONE place that knows there are two
+// The same stream with frames made from the float sub-frames (--deep-colour): quantised once, to 16 bits, instead of twice to 8 bits.  The RGBA8
+// sub-frames are still drawn: the stills come from them, and the classification of --clip-adaptive-aa reads them.
+class DeepY4mOutput : public Y4mOutput {
+public:
+    using Y4mOutput::Y4mOutput;
+    bool wants_float() const override { return true; }
+    int make_result(void* result, float* ms) override {
+        return ptl_average_f32_to_yuv420p10(o_.device, run_.float_subframes.data(), o_.blur, result, run_.width, run_.height, nullptr, ms) == PTL_OK ? 0 : fail("average_f32_to_yuv420p10");
+    }
+};
+
+std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, size_t max_pending) {  // the ONE place that knows there are three
+    if (run.o.y4m && run.o.deep_colour) return std::make_unique<DeepY4mOutput>(run, clip, max_pending);
     if (run.o.y4m) return std::make_unique<Y4mOutput>(run, clip, max_pending);
     return std::make_unique<PngOutput>(run, clip);
 }
@@ -512,7 +527,7 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
     if (o.clip_adaptive) ptl_renderer_set_option(r, "adaptive_aa_threshold", o.clip_adaptive_t);
     ptl_frame frame{run.width, run.height, 0, 1, 0};
     int last = o.max_frames >= 0 ? std::min(count, o.max_frames) : count;
-    const bool batched = batch_subframes(o), direct = out.draws_result();
+    const bool batched = batch_subframes(o), direct = out.draws_result(), with_float = out.wants_float();
     for (int i = 0; i < last; ++i) {
         if (int rc = out.check()) return rc;
         if (i % o.shards != o.shard || out.have(i)) {
@@ -533,23 +548,25 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
             ptl_renderer_set_option(r, "aa_start", j);
             if (ptl_renderer_update(r, subframe_time(i, j, count, o.blur) * (double)(float)clip.duration, nullptr, nullptr) != PTL_OK) return fail("update");
             void* target = direct ? pipe.results[slot] : run.subframes[j];
+            void* target_f32 = with_float ? run.float_subframes[j] : nullptr;  // out_rgba32f of the draw
+            void* block_f32 = with_float ? run.float_subframes[0] : nullptr;   // ... of a batched one: slice z behind slice z - 1
             float ms = 0.0f;
             if (batched) {
                 // everything a draw does short of launching; the launch follows behind the last sub-frame, once for all of them
                 if (ptl_renderer_stage_slice(r, &frame, j) != PTL_OK) return fail("stage");
                 const unsigned long long slice_pixels = (unsigned long long)run.width * run.height;
                 if (j == o.blur - 1) {
-                    if ((o.clip_adaptive ? ptl_renderer_draw_slices_adaptive(r, &frame, o.blur, run.subframes[0], nullptr, slice_pixels, nullptr, o.timing ? &ms : nullptr)
-                                         : ptl_renderer_draw_slices(r, &frame, o.blur, run.subframes[0], nullptr, slice_pixels, nullptr, o.timing ? &ms : nullptr)) != PTL_OK)
+                    if ((o.clip_adaptive ? ptl_renderer_draw_slices_adaptive(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, o.timing ? &ms : nullptr)
+                                         : ptl_renderer_draw_slices(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, o.timing ? &ms : nullptr)) != PTL_OK)
                         return fail("render");
                     if (o.clip_adaptive && o.timing)
                         if (int rc = account_adaptive(true, o.blur)) return rc;
                 }
             } else if (o.clip_adaptive) {  // (blur 1, blur > 16, --batch-subframes 0: the single-frame adaptive draw per sub-frame)
-                if (ptl_renderer_draw_adaptive(r, &frame, target, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) return fail("render");
+                if (ptl_renderer_draw_adaptive(r, &frame, target, target_f32, nullptr, o.timing ? &ms : nullptr) != PTL_OK) return fail("render");
                 if (o.timing)
                     if (int rc = account_adaptive(false, 1)) return rc;
-            } else if (ptl_renderer_draw(r, &frame, target, nullptr, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) {
+            } else if (ptl_renderer_draw(r, &frame, target, target_f32, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) {
                 // (without --timing the launch is not waited for: the host evaluates the next sub-frame's uniforms while this one traces)
                 return fail("render");
             }
@@ -725,6 +742,13 @@ int render_scene(const Options& o, const std::string& path) {
     if (ptl_device_alloc(o.device, run.frame_bytes * run.subframes.size(), &block) != PTL_OK) return fail("alloc");
     run.subframe_block.reset(block);
     for (size_t j = 0; j < run.subframes.size(); ++j) run.subframes[j] = static_cast<char*>(block) + j * run.frame_bytes;
+    if (o.deep_colour) {
+        const size_t float_bytes = run.frame_bytes * 4;  // RGBA32F
+        void* floats = nullptr;
+        if (ptl_device_alloc(o.device, float_bytes * run.subframes.size(), &floats) != PTL_OK) return fail("alloc");
+        run.float_block.reset(floats);
+        for (size_t j = 0; j < run.subframes.size(); ++j) run.float_subframes.push_back(static_cast<char*>(floats) + j * float_bytes);
+    }
     if (!run.pipe.create(o.device, run.result_bytes)) return fail("pipeline");
     Prefetcher prefetch;
     prefetch.start(o, path, todo);

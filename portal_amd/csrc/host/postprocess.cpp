@@ -200,6 +200,18 @@ extern "C" int ptl_average_to_yuv420p10(int device, const void* const* frames_rg
     return launch_over_subframes(device, kernel, frames_rgba8, n_frames, {&out_yuv, &width, &height}, lanes, stream, elapsed_ms);
 }
 
+// ptl_average_f32_to_yuv420p10: the deep-colour form (portal_amd/csrc/kernels/yuv420p10_f32.hip, the contract is in include/portal_amd.h): the
+// sub-frames are the RGBA32F frames a render call stores as out_rgba32f, 16 bytes per pixel.  A lane owns a 2x2 block where both sizes are
+// even, else one chroma sample: the same count either way.
+extern "C" int ptl_average_f32_to_yuv420p10(int device, const void* const* frames_rgba32f, int n_frames, void* out_yuv, int width, int height, void* stream,
+                                            float* elapsed_ms) {
+    if (int rc = check_subframes(frames_rgba32f, n_frames, out_yuv, width, height)) return rc;
+    if ((long)width * height > (1L << 28)) return PTL_ERR_INVALID;  // the kernel addresses a sub-frame with 32-bit byte offsets, 16 bytes per pixel
+    const SubframeKernel kernel{"yuv420p10_f32.hsaco", "ptl_average_f32_to_yuv420p10_kernel", "ptl_average_f32_to_yuv420p10_table_kernel", "average_f32_to_yuv420p10"};
+    long lanes = (long)((width + 1) / 2) * ((height + 1) / 2);
+    return launch_over_subframes(device, kernel, frames_rgba32f, n_frames, {&out_yuv, &width, &height}, lanes, stream, elapsed_ms);
+}
+
 // ptl_aa_edges: the classification pass of the adaptive anti-aliasing (portal_amd/csrc/kernels/aa_edges.hip; the contract is in
 // include/portal_amd.h).  The count is reset on `stream` by the call itself; a 256-thread workgroup per 64x32 pixel region.
 extern "C" int ptl_aa_edges(int device, const void* frame_rgba8, int width, int height, int threshold, void* list, void* count, void* stream,

@@ -6,8 +6,10 @@ Algorithmic bytes per launch: (4 N + 3) W H for the fused kernel (N RGBA8 sub-fr
 per pixel), (4 N + 4) W H for averaging (one RGBA8 frame written).  N = 1 has no averaging counterpart worth timing (callers skip it).
 Each cell: warm-up launches, then `--launches` launches back to back between ONE pair of events, `--repeats` times, the two kernels
 alternating; the median is reported, the spread beside it.  One JSON line per cell and kernel.
+--deep adds the deep-colour kernel (ptl_average_f32_to_yuv420p10, yuv420p10_f32.hip) to the alternation, on float sub-frames of its own:
+(16 N + 3) W H bytes per launch, and its bandwidth over the averaging kernel's as a third line.
 
-    python tools/yuv_bench.py [--launches 200] [--repeats 7] [--sizes 3840x2160,7680x4320] [--subframes 1,4,16]
+    python tools/yuv_bench.py [--launches 200] [--repeats 7] [--sizes 3840x2160,7680x4320] [--subframes 1,4,16] [--deep]
 """
 import argparse
 import json
@@ -36,6 +38,7 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--sizes", default="3840x2160,7680x4320")
     ap.add_argument("--subframes", default="1,4,16")
+    ap.add_argument("--deep", action="store_true")
     args = ap.parse_args()
     import torch
 
@@ -55,6 +58,10 @@ if __name__ == "__main__":
             kernels = {"ptl_average_to_yuv420p10": (lambda: pa.average_to_yuv420p10_device(ptrs, yuv.data_ptr(), w, h, stream=raw), (4 * n + 3) * w * h)}
             if n > 1:
                 kernels["ptl_average_images"] = (lambda: pa.average_images_device(ptrs, rgba.data_ptr(), w, h, stream=raw), (4 * n + 4) * w * h)
+            if args.deep:
+                floats = [torch.rand((h, w, 4), dtype=torch.float32, device=dev, generator=g) for _ in range(n)]
+                float_ptrs = [f.data_ptr() for f in floats]
+                kernels["ptl_average_f32_to_yuv420p10"] = (lambda: pa.average_f32_to_yuv420p10_device(float_ptrs, yuv.data_ptr(), w, h, stream=raw), (16 * n + 3) * w * h)
             times = {name: [] for name in kernels}
             for name, (launch, _) in kernels.items():  # warm-up: code object loaded, clocks up, every buffer touched
                 for _ in range(20):
@@ -69,5 +76,7 @@ if __name__ == "__main__":
                 cell[name] = nbytes / ms / 1e9
                 print(json.dumps({"kernel": name, "frame": f"{w}x{h}", "subframes": n, "bytes": nbytes, "launches": args.launches, "repeats": args.repeats,
                                   "ms": round(ms, 5), "ms_min": round(min(times[name]), 5), "ms_max": round(max(times[name]), 5), "TB/s": round(nbytes / ms / 1e9, 3)}), flush=True)
-            if len(cell) == 2:
+            if "ptl_average_images" in cell:
                 print(json.dumps({"frame": f"{w}x{h}", "subframes": n, "fused_over_averaging_bandwidth": round(cell["ptl_average_to_yuv420p10"] / cell["ptl_average_images"], 4)}), flush=True)
+            if "ptl_average_images" in cell and "ptl_average_f32_to_yuv420p10" in cell:
+                print(json.dumps({"frame": f"{w}x{h}", "subframes": n, "deep_over_averaging_bandwidth": round(cell["ptl_average_f32_to_yuv420p10"] / cell["ptl_average_images"], 4)}), flush=True)
