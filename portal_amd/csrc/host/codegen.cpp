@@ -1084,7 +1084,7 @@ std::vector<std::pair<std::string, MatrixPattern>> plan_zero_patterns(const Scen
 bool plan_affine_rays(const std::vector<UniformUpload>& values, const std::vector<SceneSnippet>& snippets, bool full_chains, const KernelOptions& opts, std::string* refused_because) {
     if (!opts.affine_rays || opts.check_affine || opts.exact_cr || full_chains || !may_shorten_products(opts)) return false;
     // (a matrix that stays a run-time value: what holds now is checked again by the renderer before every upload that could change it
-    // -- capi.cpp `zero_patterns_broken` for the builds that keep their kernel across scene states; the others come back here)
+    // -- renderer_builds.cpp `zero_patterns_broken` for the builds that keep their kernel across scene states; the others come back here)
     for (auto& up : values)
         if (up.type == UniformType::Mat4 && !matrix_keeps_rays_affine(up.f)) return false;
     if (opts.skip_affine_scan) return true;

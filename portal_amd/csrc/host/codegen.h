@@ -173,7 +173,7 @@ struct KernelOptions {
     // the matrix-times-ray products, the bounce loop -- count the ray halves that arrive with another w than 1 / 0 into the `segments` counter
     // (device/ptl_glsl.h PTL_CHECK_AFFINE).  Its frame is right either way; a non-zero count says an affine-rays kernel's would not be.
     bool check_affine = false;
-    // A TEST hook (PTL_AFFINE_RAYS_SKIP_SCAN=1, read by capi.cpp `options_from_flags`): the snippets are not scanned, the matrices alone decide --
+    // A TEST hook (PTL_AFFINE_RAYS_SKIP_SCAN=1, read by renderer_builds.cpp `options_from_flags`): the snippets are not scanned, the matrices alone decide --
     // tests/test_affine_guard_fuzz.py shows what a snippet the scan refuses would draw with the assumption.
     bool skip_affine_scan = false;
     // Round 6: the Simple materials' literals in a per-workgroup LDS table, one material_simple2 call for all of them (codegen.cpp, materials).

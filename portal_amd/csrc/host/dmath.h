@@ -191,6 +191,14 @@ struct DMat4 {
             out[4 * k + 3] = (float)c[k].w;
         }
     }
+    void to_cols_array(double out[16]) const {  // column-major, like glam's to_cols_array
+        for (int k = 0; k < 4; ++k) {
+            out[4 * k + 0] = c[k].x;
+            out[4 * k + 1] = c[k].y;
+            out[4 * k + 2] = c[k].z;
+            out[4 * k + 3] = c[k].w;
+        }
+    }
 };
 
 }  // namespace ptl

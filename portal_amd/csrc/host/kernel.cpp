@@ -552,7 +552,7 @@ extern "C" int ptl_kernel_compile(int device, const char* hip_source, const ptl_
     return compile_kernel({device, hip_source, uniforms, n_uniforms, uniform_block_size, defines, n_defines, log, log_cap}, nullptr, true, out);
 }
 
-// Layer-1 internal (capi.cpp's background re-JIT): load a code object that another thread compiled from exactly `hip_source` with
+// Layer-1 internal (renderer_builds.cpp's background re-JIT): load a code object that another thread compiled from exactly `hip_source` with
 // exactly these defines (a compile-only handle, device = -1) instead of compiling again.
 extern "C" int ptl_kernel_compile_prebuilt(int device, const char* hip_source, const ptl_uniform_desc* uniforms, int n_uniforms, size_t uniform_block_size,
                                            const char* const* defines, int n_defines, const void* code, size_t code_size, ptl_kernel** out, char* log,
@@ -639,7 +639,7 @@ static int settable_uniform(ptl_kernel* k, const char* name, ptl_type type, cons
     if (k->affine_rays && type == PTL_MAT4) {
         // a layer-1 caller owns `_camera` and every run-time `X_mat`; a kernel with affine rays is only valid for matrices that map
         // w = 1 to 1 and w = 0 to 0 (or are NaN throughout: a switched-off object).  The layer-2 renderer rebuilds BEFORE it uploads such a matrix
-        // (capi.cpp `camera_is_affine`, `zero_patterns_broken`); a direct caller gets the refusal instead of silently wrong frames.
+        // (renderer_camera.cpp `camera_is_affine`, renderer_builds.cpp `zero_patterns_broken`); a direct caller gets the refusal instead of silently wrong frames.
         const std::string nm = name;
         auto tail = [&](const char* e) { const size_t m = std::strlen(e); return nm.size() >= m && nm.compare(nm.size() - m, m, e) == 0; };
         if ((nm == "_camera" || tail("_mat") || tail("_mat_inv") || tail("_mat_teleport")) && !matrix_keeps_rays_affine(static_cast<const float*>(value))) {

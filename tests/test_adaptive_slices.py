@@ -641,6 +641,18 @@ def test_each_kind_of_adaptive_draw_hands_out_its_own_result_only(gpu):
         single.adaptive_slices_result()
 
 
+def _moving_state(k):
+    """State k of the rebuild tests: the compiled-in `portal_rotate_angle` moves between k = 1 and k = 2, the camera with every k."""
+    return (0.0 if k < 2 else 0.6), ((0.02 * k, 0.1 - 0.01 * k, -0.3), 0.9 + 0.05 * k, 1.2, 3.1 - 0.1 * k)
+
+
+def _monoportal(pa, flags):
+    scene = pa.Scene.from_file(pa.scene_path("monoportal"))
+    r = pa.SceneRenderer(scene, device=0, flags=flags)
+    r.set_option("render_depth", 12)
+    return scene, r
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("t", [-1, 4])
 def test_a_rebuild_between_two_stage_calls_keeps_both_passes_on_the_slices_own_kernel(gpu, t):
@@ -651,19 +663,10 @@ def test_a_rebuild_between_two_stage_calls_keeps_both_passes_on_the_slices_own_k
     w, h, n, aa = 64, 36, 4, 4
     frame = pa.Frame(w, h, 0, 1)
 
-    def state(k):
-        return (0.0 if k < 2 else 0.6), ((0.02 * k, 0.1 - 0.01 * k, -0.3), 0.9 + 0.05 * k, 1.2, 3.1 - 0.1 * k)
-
-    def make(flags):
-        scene = pa.Scene.from_file(pa.scene_path("monoportal"))
-        r = pa.SceneRenderer(scene, device=0, flags=flags)
-        r.set_option("render_depth", 12)
-        return scene, r
-
-    scene_a, ra = make(0)
+    scene_a, ra = _monoportal(pa, 0)
     p, f = [], []
     for k in range(n):
-        angle, cam = state(k)
+        angle, cam = _moving_state(k)
         assert scene_a.set_uniform("portal_rotate_angle", angle)
         ra.set_camera(*cam)
         ra.set_option("aa_start", k)
@@ -671,11 +674,11 @@ def test_a_rebuild_between_two_stage_calls_keeps_both_passes_on_the_slices_own_k
         p.append(ra.draw(w, h, rgba8=True, rgba32f=True))
         ra.set_option("aa_count", aa)
         f.append(ra.draw(w, h, rgba8=True, rgba32f=True))
-    scene_b, rb = make(pa.FLAG_SPECIALIZE_STATIC | pa.FLAG_REFINE_SLICES)
+    scene_b, rb = _monoportal(pa, pa.FLAG_SPECIALIZE_STATIC | pa.FLAG_REFINE_SLICES)
     rb.set_option("aa_count", aa)
     kernels = []
     for k in range(n):
-        angle, cam = state(k)
+        angle, cam = _moving_state(k)
         assert scene_b.set_uniform("portal_rotate_angle", angle)
         rb.set_camera(*cam)
         rb.set_option("aa_start", k)
@@ -689,6 +692,53 @@ def test_a_rebuild_between_two_stage_calls_keeps_both_passes_on_the_slices_own_k
         assert np.array_equal(out8[z], ar.adaptive_frame(p[z]["rgba8"], f[z]["rgba8"], t)), z
         assert np.array_equal(out32[z], ar.select(mask, _bits(f[z]["rgba32f"]), _bits(p[z]["rgba32f"]))), z
     assert not np.array_equal(f[1]["rgba8"], f[2]["rgba8"])
+
+
+@pytest.mark.gpu
+def test_a_renderer_destroyed_with_staged_slices_a_parked_kernel_and_used_lanes_leaves_the_device_sound(gpu):
+    """The teardown nothing else reaches: a FLAG_SPECIALIZE_STATIC | FLAG_REFINE_SLICES renderer at 64x36 whose lanes have drawn, with two
+    slices staged and never launched and a rebuild between the two stage calls (the first slice's kernel is parked, both hold their texel
+    buffers), is destroyed.  A fresh renderer of the same scene then draws the frame of a renderer that never staged anything."""
+    import gc
+
+    import torch
+
+    pa = gpu
+    w, h = 64, 36
+    frame = pa.Frame(w, h, 0, 1)
+    flags = pa.FLAG_SPECIALIZE_STATIC | pa.FLAG_REFINE_SLICES
+
+    def enter(scene, r, k):
+        angle, cam = _moving_state(k)
+        assert scene.set_uniform("portal_rotate_angle", angle)
+        r.set_camera(*cam)
+
+    scene_a, ra = _monoportal(pa, 0)
+    enter(scene_a, ra, 2)
+    want = ra.draw(w, h, rgba8=True, rgba32f=True)
+
+    scene_b, rb = _monoportal(pa, flags)
+    rb.set_option("concurrent_draws", 2)
+    targets = torch.zeros((2, h, w, 4), dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    for j in range(2):  # lane 0 (the kernel itself) and lane 1 (its clone), not joined
+        enter(scene_b, rb, 0)
+        rb.draw_device(frame, out_rgba8=targets[j].data_ptr())
+    kernels = []
+    for j, k in enumerate((1, 2)):
+        enter(scene_b, rb, k)
+        rb.stage_slice(frame, j)
+        kernels.append(pa.lib().ptl_renderer_kernel(rb._h))
+    assert kernels[0] != kernels[1] and rb.rejit_count() >= 1  # slice 0's kernel is parked
+    del rb, scene_b
+    gc.collect()
+    torch.cuda.synchronize()
+
+    scene_c, rc = _monoportal(pa, flags)
+    enter(scene_c, rc, 2)
+    got = rc.draw(w, h, rgba8=True, rgba32f=True)
+    assert np.array_equal(got["rgba8"], want["rgba8"])
+    assert np.array_equal(_bits(got["rgba32f"]), _bits(want["rgba32f"]))
 
 
 @pytest.mark.gpu
