@@ -553,6 +553,34 @@ size_t ptl_yuv420p10_frame_bytes(int width, int height);
  * those of ptl_average_to_yuv420p10.  (`portal-amd render --frames y4m --deep-colour`.) */
 int ptl_average_f32_to_yuv420p10(int device, const void* const* frames_rgba32f, int n_frames, void* out_yuv, int width, int height, void* stream,
                                  float* elapsed_ms);
+/* The same two frames with another chroma sampling, `chroma` = PTL_CHROMA_420, _422 or _444.  The averaged frame A(x, y),
+ * the luma formula, the plane order and the full-range 10-bit coding stay what they are above: for RGBA8 sub-frames those of
+ * ptl_average_to_yuv420p10, for RGBA32F sub-frames those of ptl_average_f32_to_yuv420p10 (q, M, E).  Only the chroma planes change:
+ *   chroma  cw       ch       S_c
+ *   422     (W+1)/2  H        A_c(2i-1, y) + 2 A_c(2i, y) + A_c(2i+1, y)     co-sited with luma column 2i (as 4:2:0 is horizontally), columns
+ *                                                                            clamped to the frame, nothing vertical
+ *   444     W        H        A_c(x, y)
+ * RGBA8 sub-frames, 32-bit integers, k = 18 for 422 and 16 for 444 (the 4:2:0 form above is k = 19):
+ *   Cb = min(1023, (-30123 S_R - 101335 S_G + 131458 S_B + (512 << k) + (1 << (k-1))) >> k)
+ *   Cr = min(1023, (131458 S_R - 119404 S_G -  12054 S_B + (512 << k) + (1 << (k-1))) >> k)
+ * RGBA32F sub-frames, 64-bit integers, k = 25 for 422 and 23 for 444 (the 4:2:0 form above is k = 26):
+ *   Cb = min(1023, (-15003 S_R - 50470 S_G + 65473 S_B + (512 << k) + (1 << (k-1))) >> k)
+ *   Cr = min(1023, ( 65473 S_R - 59470 S_G -  6003 S_B + (512 << k) + (1 << (k-1))) >> k)
+ * Every accumulator stays positive (minima 261 640 and 65 410, 33 554 180 and 8 388 545), so >> is a plain shift; pure blue and pure red
+ * reach exactly 1024 before the min and nothing exceeds it; every grey gives 512; within 0.51 codes of the real-valued H.273 definition.
+ * out_yuv: the Y plane (W*H little-endian uint16), then Cb, then Cr (cw*ch each) = ptl_yuv10_frame_bytes(w, h, chroma) =
+ * 2 (W H + 2 cw ch) bytes: 4 bytes per pixel at 422 and 6 at 444 for even W.  The stream header names the sampling
+ * (ptl_y4m_header_chroma).  chroma == PTL_CHROMA_420 IS the entry above: same kernel, same bytes.  Validation, limits (W*H <= 2^29 for
+ * RGBA8, <= 2^28 for float sub-frames), stream and timing are those of ptl_average_to_yuv420p10; any other `chroma` is PTL_ERR_INVALID.
+ * (`portal-amd render --frames y4m --chroma 420|422|444 [--deep-colour]`.) */
+#define PTL_CHROMA_420 420
+#define PTL_CHROMA_422 422
+#define PTL_CHROMA_444 444
+int ptl_average_to_yuv10(int device, const void* const* frames_rgba8, int n_frames, void* out_yuv, int width, int height, int chroma, void* stream,
+                         float* elapsed_ms);
+int ptl_average_f32_to_yuv10(int device, const void* const* frames_rgba32f, int n_frames, void* out_yuv, int width, int height, int chroma, void* stream,
+                             float* elapsed_ms);
+size_t ptl_yuv10_frame_bytes(int width, int height, int chroma); /* 0 for an unknown chroma */
 /* ---- adaptive anti-aliasing: supersample only the pixels that sit on an edge (opt-in, approximate by design) ------------------------
  * Every anti-aliasing sample costs a full trace, and most pixels of a frame are flat walls and smooth gradients whose centre sample is
  * already the final 8-bit colour.  An adaptive draw traces ONE sample per pixel, classifies the frame it got, and traces the full
@@ -645,6 +673,9 @@ int ptl_renderer_adaptive_slices_result(ptl_renderer* r, void** lists, unsigned 
 /* The Y4M stream such frames travel in: "YUV4MPEG2 W<w> H<h> F<fps>:1 Ip A1:1 C420p10 XYSCSS=420P10 XCOLORRANGE=FULL\n" once, then
  * "FRAME\n" + payload per frame.  Writes the header (NUL-terminated) into buf and returns its length; PTL_ERR_INVALID when it does not fit. */
 int ptl_y4m_header(int width, int height, int fps, char* buf, size_t cap);
+/* The same with the sampling of ptl_average_to_yuv10 named: "... C422p10 XYSCSS=422P10 XCOLORRANGE=FULL\n", "... C444p10 XYSCSS=444P10
+ * XCOLORRANGE=FULL\n"; chroma == PTL_CHROMA_420 gives the line above.  PTL_ERR_INVALID for any other chroma. */
+int ptl_y4m_header_chroma(int width, int height, int fps, int chroma, char* buf, size_t cap);
 
 /* Device frame buffers for callers that keep frames on the GPU between kernels (sub-frames -> ptl_average_images ->
  * one download); the reference's counterpart is the macroquad render target + Texture2D::get_texture_data()

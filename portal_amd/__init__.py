@@ -185,6 +185,9 @@ def _load() -> C.CDLL:
         "ptl_average_to_yuv420p10": (ci, [ci, P(vp), ci, vp, ci, ci, vp, P(C.c_float)]),
         "ptl_average_f32_to_yuv420p10": (ci, [ci, P(vp), ci, vp, ci, ci, vp, P(C.c_float)]),
         "ptl_yuv420p10_frame_bytes": (cs, [ci, ci]),
+        "ptl_average_to_yuv10": (ci, [ci, P(vp), ci, vp, ci, ci, ci, vp, P(C.c_float)]),
+        "ptl_average_f32_to_yuv10": (ci, [ci, P(vp), ci, vp, ci, ci, ci, vp, P(C.c_float)]),
+        "ptl_yuv10_frame_bytes": (cs, [ci, ci, ci]),
         "ptl_aa_edges": (ci, [ci, vp, ci, ci, ci, vp, vp, vp, P(C.c_float)]),
         "ptl_kernel_render_refine": (ci, [vp, P(Frame), vp, vp, vp, vp, vp, vp, P(C.c_float)]),
         "ptl_renderer_draw_adaptive": (ci, [vp, P(Frame), vp, vp, vp, P(C.c_float)]),
@@ -196,6 +199,7 @@ def _load() -> C.CDLL:
         "ptl_renderer_draw_slices_adaptive": (ci, [vp, P(Frame), ci, vp, vp, C.c_ulonglong, vp, P(C.c_float)]),
         "ptl_renderer_adaptive_slices_result": (ci, [vp, P(vp), P(C.c_ulonglong), P(vp)]),
         "ptl_y4m_header": (ci, [ci, ci, ci, cp, cs]),
+        "ptl_y4m_header_chroma": (ci, [ci, ci, ci, ci, cp, cs]),
         "ptl_device_alloc": (ci, [ci, cs, P(vp)]),
         "ptl_device_free": (ci, [vp]),
         "ptl_device_download": (ci, [vp, vp, cs, vp]),
@@ -917,10 +921,34 @@ def yuv420p10_frame_bytes(width: int, height: int) -> int:
     return int(lib().ptl_yuv420p10_frame_bytes(width, height))
 
 
-def y4m_header(width: int, height: int, fps: int) -> bytes:
+def _average_to_yuv10(entry, frame_ptrs, out_ptr, width, height, chroma, device, stream, timed):
+    arr = (C.c_void_p * len(frame_ptrs))(*frame_ptrs)
+    ms = C.c_float()
+    _check(getattr(lib(), "ptl_" + entry)(device, arr, len(frame_ptrs), C.c_void_p(out_ptr), width, height, chroma, C.c_void_p(stream or None),
+                                          C.byref(ms) if timed else None), entry)
+    return ms.value if timed else None
+
+
+def average_to_yuv10_device(frame_ptrs, out_ptr: int, width: int, height: int, chroma: int, device: int = 0, stream: int = 0, timed: bool = False):
+    """ptl_average_to_yuv10 on DEVICE buffers given as integer addresses: `average_to_yuv420p10_device` with the chroma sampling chosen,
+    `chroma` = 420, 422 or 444 (`yuv10_frame_bytes(width, height, chroma)` bytes at out_ptr).  420 is the same kernel, the same bytes."""
+    return _average_to_yuv10("average_to_yuv10", frame_ptrs, out_ptr, width, height, chroma, device, stream, timed)
+
+
+def average_f32_to_yuv10_device(frame_ptrs, out_ptr: int, width: int, height: int, chroma: int, device: int = 0, stream: int = 0, timed: bool = False):
+    """ptl_average_f32_to_yuv10: the deep-colour form (RGBA32F sub-frames, see `average_f32_to_yuv420p10_device`) with the sampling chosen."""
+    return _average_to_yuv10("average_f32_to_yuv10", frame_ptrs, out_ptr, width, height, chroma, device, stream, timed)
+
+
+def yuv10_frame_bytes(width: int, height: int, chroma: int) -> int:
+    """Bytes of one frame as `average_to_yuv10_device` writes it at that sampling; 0 for a sampling that is none of 420, 422, 444."""
+    return int(lib().ptl_yuv10_frame_bytes(width, height, chroma))
+
+
+def y4m_header(width: int, height: int, fps: int, chroma: int = 420) -> bytes:
     """The header line of the Y4M stream those frames travel in (each frame: b"FRAME\\n" + payload)."""
     buf = C.create_string_buffer(128)
-    n = _check(lib().ptl_y4m_header(width, height, fps, buf, len(buf)), "y4m_header")
+    n = _check(lib().ptl_y4m_header_chroma(width, height, fps, chroma, buf, len(buf)), "y4m_header")
     return buf.raw[:n]
 
 

@@ -33,6 +33,8 @@ int usage() {  // (and the exit status that goes with it)
                  "                                       Not with --shard K/N, N > 1 (a stream needs every frame, in order); a clip is not resumed, it starts at frame 0\n"
                  "                  [--deep-colour]      with --frames y4m: the 10-bit frames are made from the un-quantised float sub-frames (one quantisation, to 16 bits,\n"
                  "                                       instead of two to 8 bits): a smooth gradient keeps 1024 luma codes instead of 256.  16 more bytes per pixel and sub-frame on the card\n"
+                 "                  [--chroma 420|422|444]  with --frames y4m: the chroma sampling of the stream (default 420).  422 keeps every row of chroma, 444 every sample:\n"
+                 "                                       4 and 6 bytes per pixel leave the card instead of 3, and the encoder is told yuv422p10le / yuv444p10le\n"
                  "                  [--clip-adaptive-aa [T]]  adaptive anti-aliasing of every sub-frame: one sample per pixel, --aa-count samples only where a pixel differs\n"
                  "                                       from a neighbour by more than T codes (default 4, -1 .. 255); opt-in, approximate by design\n"
                  "       portal-amd emit-source <scene.ron> [--stage NAME]     print the generated HIP kernel source\n"
@@ -442,6 +444,12 @@ int main(int argc, char** argv) {
             o.y4m = form == "y4m";
         }
         else if (a == "--deep-colour") o.deep_colour = true;
+        else if (a == "--chroma") {
+            std::string sampling = next();
+            if (sampling != "420" && sampling != "422" && sampling != "444") return refuse("--chroma 420|422|444");
+            o.chroma = std::atoi(sampling.c_str());
+            o.have_chroma = true;
+        }
         else if (a == "--gpus") o.gpus = std::atoi(next());
         else if (a == "--devices") o.devices = next();
         else if (a == "--transport") o.transport = next();
@@ -495,6 +503,8 @@ int main(int argc, char** argv) {
     if (o.y4m && o.shards > 1) return refuse("--frames y4m cannot be combined with --shard K/N, N > 1: a stream needs every frame, in order");
     if (o.deep_colour && cmd != "render") return refuse("--deep-colour is an option of render: it chooses how the frames of a clip's Y4M stream are made");
     if (o.deep_colour && !o.y4m) return refuse("--deep-colour needs --frames y4m: PNG frames hold 8 bits per channel, only the 10-bit stream can carry what the float sub-frames add");
+    if (o.have_chroma && cmd != "render") return refuse("--chroma is an option of render: it chooses the chroma sampling of a clip's Y4M stream");
+    if (o.have_chroma && !o.y4m) return refuse("--chroma needs --frames y4m: it chooses the chroma sampling of the stream (4:2:0, 4:2:2 or 4:4:4); PNG frames have none");
     if (o.adaptive && cmd != "render-frame") return refuse("--adaptive-aa is an option of render-frame: a clip's sub-frames go through the slices entry, whose adaptive form is `render --clip-adaptive-aa [T]`");
     if (o.clip_adaptive && cmd != "render" && cmd != "precompile") return refuse("--clip-adaptive-aa is an option of render (and of precompile, which builds render's kernels); a single frame takes render-frame --adaptive-aa");
     if (o.adaptive && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.shards > 1)) return refuse("--adaptive-aa draws whole frames on one GPU: it cannot be combined with --gpus N, N > 1, several --devices or --shard");

@@ -7,7 +7,7 @@
 // Video pipeline: for every frame i of a clip, `motion_blur_frames` sub-frames are traced straight into device buffers (aa_start = j,
 // time = subframe_time(i, j)), averaged on the GPU (ptl_average_images), downloaded once, and PNG-encoded on a pool of host threads while
 // the GPU already traces the next frame.  With --frames y4m the averaging kernel is the fused one (ptl_average_to_yuv420p10): what is
-// downloaded is the planar 4:2:0 10-bit frame the encoder consumes, and one writer thread streams the frames in order into ffmpeg's stdin
+// downloaded is the planar 10-bit frame the encoder consumes (4:2:0, or what --chroma asks for: ptl_average_to_yuv10), and one writer thread streams the frames in order into ffmpeg's stdin
 // (or a .y4m file) while the clip is still rendering: no PNG files, no anim/ directory, no zscale pass.
 #include <dirent.h>
 #include <fcntl.h>
@@ -229,9 +229,10 @@ void remove_tree(const std::string& path) {  // rm -rf of a directory we created
     ::rmdir(path.c_str());
 }
 
-// the reference's encoder settings (src/main.rs:1843-1857), from -c:v onwards: what follows the input, whichever form the input has
-std::vector<std::string> encoder_arguments(const std::string& video) {
-    return {"-c:v", "libx265", "-pix_fmt", "yuv420p10le", "-crf", "15", "-preset", "slow", "-x265-params",
+// the reference's encoder settings (src/main.rs:1843-1857), from -c:v onwards: what follows the input, whichever form the input has.
+// `pix_fmt`: the reference's yuv420p10le, or what --chroma makes of the stream
+std::vector<std::string> encoder_arguments(const std::string& video, const std::string& pix_fmt) {
+    return {"-c:v", "libx265", "-pix_fmt", pix_fmt, "-crf", "15", "-preset", "slow", "-x265-params",
             "colorprim=bt709:transfer=iec61966-2-1:colormatrix=bt709:range=full", "-colorspace", "bt709", "-color_primaries", "bt709", "-color_trc",
             "iec61966-2-1", "-color_range", "pc", "-movflags", "+write_colr+faststart", "-tag:v", "hvc1", "-y", video};
 }
@@ -254,7 +255,7 @@ int encode_video(const Options& o, const std::string& scene_name, const std::str
         "ffmpeg", "-framerate", std::to_string(fps), "-i", anim + "/frame_%d.png", "-vf",
         "zscale=primariesin=bt709:transferin=iec61966-2-1:matrixin=bt709:rangein=full:primaries=bt709:transfer=iec61966-2-1:matrix=bt709:range=full,"
         "format=yuv420p10le"};
-    for (const std::string& a : encoder_arguments(video)) command.push_back(a);
+    for (const std::string& a : encoder_arguments(video, "yuv420p10le")) command.push_back(a);
     int status = run_program(command, true);
     std::printf("ffmpeg status: %d\nffmpeg time: %.2f s\n", status, std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count());
     remove_tree(anim);  // like the reference, whatever ffmpeg said (src/main.rs:1860)
@@ -384,16 +385,16 @@ private:
 class Y4mOutput : public FrameOutput {
 public:
     Y4mOutput(const SceneRun& run, const Clip& clip, size_t max_pending) : FrameOutput(run, clip), writer_(1, max_pending) {}
-    size_t result_bytes() const override { return ptl_yuv420p10_frame_bytes(run_.width, run_.height); }
+    size_t result_bytes() const override { return ptl_yuv10_frame_bytes(run_.width, run_.height, o_.chroma); }
     int open() override {
         ::signal(SIGPIPE, SIG_IGN);  // an encoder that dies is a failed write (EPIPE), reported by the clip
         // Where the stream goes: into an encoder when there is one and the clip is whole, else into a file an encoder can read later.
         // The encoder is told nothing about scaling or pixel formats: the stream is what it encodes, the -color_* tags say what it is.
         char header[128];
-        int header_len = ptl_y4m_header(run_.width, run_.height, fps_, header, sizeof header);
+        int header_len = ptl_y4m_header_chroma(run_.width, run_.height, fps_, o_.chroma, header, sizeof header);
         if (header_len < 0) return fail("y4m header");
         std::vector<std::string> encode = {"ffmpeg", "-f", "yuv4mpegpipe", "-i", "-"};
-        for (const std::string& a : encoder_arguments(video_base + ".mov")) encode.push_back(a);
+        for (const std::string& a : encoder_arguments(video_base + ".mov", "yuv" + std::to_string(o_.chroma) + "p10le")) encode.push_back(a);
         if (o_.max_frames < 0 && o_.shards == 1 && run_program({"ffmpeg", "-version"}, true) == 0) {
             std::printf("Start ffmpeg to encode the frames as they arrive\n");
             stream_.open_program(encode);
@@ -413,7 +414,7 @@ public:
     bool have(int) const override { return false; }
     bool draws_result() const override { return false; }  // (one sub-frame is converted with n = 1)
     int make_result(void* result, float* ms) override {
-        return ptl_average_to_yuv420p10(o_.device, run_.subframes.data(), o_.blur, result, run_.width, run_.height, nullptr, ms) == PTL_OK ? 0 : fail("average_to_yuv420p10");
+        return ptl_average_to_yuv10(o_.device, run_.subframes.data(), o_.blur, result, run_.width, run_.height, o_.chroma, nullptr, ms) == PTL_OK ? 0 : fail("average_to_yuv10");
     }
     void submit(int, uint8_t* pixels, void* arrived, EncoderPool&, PinnedFrames& pinned) override {  // frames of a stream arrive in order: one writer thread, jobs in submission order
         writer_.submit([this, pixels, arrived, bytes = result_bytes(), &pinned] {
@@ -454,7 +455,7 @@ public:
     using Y4mOutput::Y4mOutput;
     bool wants_float() const override { return true; }
     int make_result(void* result, float* ms) override {
-        return ptl_average_f32_to_yuv420p10(o_.device, run_.float_subframes.data(), o_.blur, result, run_.width, run_.height, nullptr, ms) == PTL_OK ? 0 : fail("average_f32_to_yuv420p10");
+        return ptl_average_f32_to_yuv10(o_.device, run_.float_subframes.data(), o_.blur, result, run_.width, run_.height, o_.chroma, nullptr, ms) == PTL_OK ? 0 : fail("average_f32_to_yuv10");
     }
 };
 

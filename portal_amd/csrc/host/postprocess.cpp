@@ -212,6 +212,54 @@ extern "C" int ptl_average_f32_to_yuv420p10(int device, const void* const* frame
     return launch_over_subframes(device, kernel, frames_rgba32f, n_frames, {&out_yuv, &width, &height}, lanes, stream, elapsed_ms);
 }
 
+// ptl_average_to_yuv10 / ptl_average_f32_to_yuv10: the same two frames with the chroma sampling chosen (portal_amd/csrc/kernels/yuv4xxp10.hip,
+// yuv4xxp10_f32.hip; the contract is in include/portal_amd.h).  420 is the entry above.  A lane owns 8x1 (RGBA8, W % 8 == 0) or 4x1 (float,
+// W % 4 == 0) pixels where the width allows it, else one pixel (444) or one chroma sample (422): the kernels take the same decision.
+namespace {
+bool known_chroma(int chroma, const char* what) {
+    if (chroma == PTL_CHROMA_420 || chroma == PTL_CHROMA_422 || chroma == PTL_CHROMA_444) return true;
+    set_last_error(std::string(what) + ": chroma " + std::to_string(chroma) + " is none of 420, 422, 444");
+    return false;
+}
+long lanes_4xx(int width, int height, int chroma, int block) {
+    if (width % block == 0) return (long)(width / block) * height;
+    return chroma == PTL_CHROMA_444 ? (long)width * height : (long)((width + 1) / 2) * height;
+}
+}  // namespace
+
+extern "C" size_t ptl_yuv10_frame_bytes(int width, int height, int chroma) {
+    if (width <= 0 || height <= 0) return 0;
+    if (chroma == PTL_CHROMA_420) return ptl_yuv420p10_frame_bytes(width, height);
+    if (chroma != PTL_CHROMA_422 && chroma != PTL_CHROMA_444) return 0;
+    const size_t cw = chroma == PTL_CHROMA_444 ? (size_t)width : ((size_t)width + 1) / 2;
+    return 2 * ((size_t)width * (size_t)height + 2 * cw * (size_t)height);
+}
+
+extern "C" int ptl_average_to_yuv10(int device, const void* const* frames_rgba8, int n_frames, void* out_yuv, int width, int height, int chroma, void* stream,
+                                    float* elapsed_ms) {
+    if (!known_chroma(chroma, "average_to_yuv10")) return PTL_ERR_INVALID;
+    if (chroma == PTL_CHROMA_420) return ptl_average_to_yuv420p10(device, frames_rgba8, n_frames, out_yuv, width, height, stream, elapsed_ms);
+    if (int rc = check_subframes(frames_rgba8, n_frames, out_yuv, width, height)) return rc;
+    if ((long)width * height > (1L << 29)) return PTL_ERR_INVALID;  // the kernel addresses a sub-frame with 32-bit byte offsets
+    const bool half = chroma == PTL_CHROMA_422;
+    const SubframeKernel kernel{"yuv4xxp10.hsaco", half ? "ptl_average_to_yuv422p10_kernel" : "ptl_average_to_yuv444p10_kernel",
+                                half ? "ptl_average_to_yuv422p10_table_kernel" : "ptl_average_to_yuv444p10_table_kernel", half ? "average_to_yuv422p10" : "average_to_yuv444p10"};
+    return launch_over_subframes(device, kernel, frames_rgba8, n_frames, {&out_yuv, &width, &height}, lanes_4xx(width, height, chroma, 8), stream, elapsed_ms);
+}
+
+extern "C" int ptl_average_f32_to_yuv10(int device, const void* const* frames_rgba32f, int n_frames, void* out_yuv, int width, int height, int chroma, void* stream,
+                                        float* elapsed_ms) {
+    if (!known_chroma(chroma, "average_f32_to_yuv10")) return PTL_ERR_INVALID;
+    if (chroma == PTL_CHROMA_420) return ptl_average_f32_to_yuv420p10(device, frames_rgba32f, n_frames, out_yuv, width, height, stream, elapsed_ms);
+    if (int rc = check_subframes(frames_rgba32f, n_frames, out_yuv, width, height)) return rc;
+    if ((long)width * height > (1L << 28)) return PTL_ERR_INVALID;  // the kernel addresses a sub-frame with 32-bit byte offsets, 16 bytes per pixel
+    const bool half = chroma == PTL_CHROMA_422;
+    const SubframeKernel kernel{"yuv4xxp10_f32.hsaco", half ? "ptl_average_f32_to_yuv422p10_kernel" : "ptl_average_f32_to_yuv444p10_kernel",
+                                half ? "ptl_average_f32_to_yuv422p10_table_kernel" : "ptl_average_f32_to_yuv444p10_table_kernel",
+                                half ? "average_f32_to_yuv422p10" : "average_f32_to_yuv444p10"};
+    return launch_over_subframes(device, kernel, frames_rgba32f, n_frames, {&out_yuv, &width, &height}, lanes_4xx(width, height, chroma, 4), stream, elapsed_ms);
+}
+
 // ptl_aa_edges: the classification pass of the adaptive anti-aliasing (portal_amd/csrc/kernels/aa_edges.hip; the contract is in
 // include/portal_amd.h).  The count is reset on `stream` by the call itself; a 256-thread workgroup per 64x32 pixel region.
 extern "C" int ptl_aa_edges(int device, const void* frame_rgba8, int width, int height, int threshold, void* list, void* count, void* stream,
@@ -241,6 +289,13 @@ extern "C" int ptl_aa_edges_slices(int device, const void* frames_rgba8, unsigne
 extern "C" int ptl_y4m_header(int width, int height, int fps, char* buf, size_t cap) {
     if (width <= 0 || height <= 0 || fps <= 0 || !buf) return PTL_ERR_INVALID;
     int len = std::snprintf(buf, cap, "YUV4MPEG2 W%d H%d F%d:1 Ip A1:1 C420p10 XYSCSS=420P10 XCOLORRANGE=FULL\n", width, height, fps);
+    return len > 0 && (size_t)len < cap ? len : PTL_ERR_INVALID;  // (the terminating NUL has to fit as well)
+}
+
+extern "C" int ptl_y4m_header_chroma(int width, int height, int fps, int chroma, char* buf, size_t cap) {
+    if (chroma == PTL_CHROMA_420) return ptl_y4m_header(width, height, fps, buf, cap);
+    if (!known_chroma(chroma, "y4m_header") || width <= 0 || height <= 0 || fps <= 0 || !buf) return PTL_ERR_INVALID;
+    int len = std::snprintf(buf, cap, "YUV4MPEG2 W%d H%d F%d:1 Ip A1:1 C%dp10 XYSCSS=%dP10 XCOLORRANGE=FULL\n", width, height, fps, chroma, chroma);
     return len > 0 && (size_t)len < cap ? len : PTL_ERR_INVALID;  // (the terminating NUL has to fit as well)
 }
 

@@ -18,37 +18,11 @@
 // (4-byte loads that hit the lines the neighbours stream anyway).  General path (any W, H >= 1): a lane owns one chroma
 // sample = a 2x2 luma block with 4-byte loads and 2-byte stores, every coordinate clamped.  No LDS, no atomics, no scratch.
 #include "average_common.h"  // pointer lists, ptl_accumulate, ptl_div_n, ptl_l_to_s -- the same functions ptl_average_images runs
-
-typedef unsigned int ptl_u32x2 __attribute__((ext_vector_type(2)));
+#include "yuv_common.h"      // luma, the chroma pair (shift 19 here), the 32-bit-offset loads, ptl_encode3: shared with yuv4xxp10.hip
 
 #ifndef PTL_YUV_UNROLL
 #define PTL_YUV_UNROLL 2  // sub-frames per group: 4 x 16-byte loads per lane each
 #endif
-
-__device__ __forceinline__ unsigned int ptl_luma10(const unsigned int (&a)[3]) {
-    return (55896u * a[0] + 188037u * a[1] + 18982u * a[2] + 32768u) >> 16;
-}
-// s: the 1-2-1 x 1-1 weighted sums (0..2040).  Both accumulators stay positive (>= 523 280), so >> is a plain shift.
-__device__ __forceinline__ unsigned int ptl_cb10(const int (&s)[3]) {
-    return (unsigned int)min(1023, (-30123 * s[0] - 101335 * s[1] + 131458 * s[2] + (512 << 19) + (1 << 18)) >> 19);
-}
-__device__ __forceinline__ unsigned int ptl_cr10(const int (&s)[3]) {
-    return (unsigned int)min(1023, (131458 * s[0] - 119404 * s[1] - 12054 * s[2] + (512 << 19) + (1 << 18)) >> 19);
-}
-// A sub-frame is addressed as "uniform base + 32-bit byte offset of the lane" (W*H <= 2^29, the entry point refuses more): the base stays
-// in scalar registers and a lane keeps one 32-bit offset per row instead of a 64-bit address per load.
-__device__ __forceinline__ ptl_u32x4 ptl_load16(const ptl_u32x4* frame, unsigned int byte_offset) {
-    return ptl_stream_load(reinterpret_cast<const ptl_u32x4*>(reinterpret_cast<const char*>(frame) + byte_offset));
-}
-__device__ __forceinline__ unsigned int ptl_load4(const ptl_u32x4* frame, unsigned int byte_offset) {
-    return *reinterpret_cast<const unsigned int*>(reinterpret_cast<const char*>(frame) + byte_offset);
-}
-
-// channel sums of the sub-frames -> the bytes ptl_average_images writes
-__device__ __forceinline__ void ptl_encode3(unsigned int (&a)[3], const unsigned int* sum, unsigned int magic) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) a[c] = ptl_l_to_s(ptl_div_n(sum[c], magic));
-}
 
 // Fast path: block b = (row pair j, 8-pixel column group bx), bw = W / 8 groups per row.
 template <class Frames>
@@ -125,8 +99,8 @@ __device__ __forceinline__ void ptl_yuv_block(const Frames& frames, int n, unsig
     unsigned int cb[4], cr[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        cb[i] = ptl_cb10(s[i]);
-        cr[i] = ptl_cr10(s[i]);
+        cb[i] = ptl_cb10<19>(s[i]);
+        cr[i] = ptl_cr10<19>(s[i]);
     }
     const unsigned int n_px = (unsigned)w * (unsigned)h, c_px = n_px >> 2;  // cw * ch with both even
     const unsigned int ci = j * ((unsigned)w >> 1) + 4u * bx;                // a multiple of 4: 8-byte stores
@@ -172,8 +146,8 @@ __device__ __forceinline__ void ptl_yuv_sample(const Frames& frames, int n, unsi
 #pragma unroll
     for (int c = 0; c < 3; ++c) s[c] = (int)(a[0][0][c] + 2u * a[0][1][c] + a[0][2][c] + a[1][0][c] + 2u * a[1][1][c] + a[1][2][c]);
     const unsigned int n_px = (unsigned)w * (unsigned)h, c_px = cw * ch;
-    out[n_px + t] = (unsigned short)ptl_cb10(s);
-    out[n_px + c_px + t] = (unsigned short)ptl_cr10(s);
+    out[n_px + t] = (unsigned short)ptl_cb10<19>(s);
+    out[n_px + c_px + t] = (unsigned short)ptl_cr10<19>(s);
 }
 
 template <class Frames>

@@ -20,80 +20,12 @@
 // clamps to its own column 0.  General path (any W, H >= 1): a lane owns one chroma sample with every coordinate clamped, six 16-byte
 // loads per sub-frame, 2-byte stores.  No LDS, no atomics, no scratch.
 #include "average_common.h"     // the pointer lists (a sub-frame pointer is typed as 16-byte vectors there; here the four words are floats)
-
-typedef float ptl_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long ptl_u64;
+#include "yuv_common.h"         // ptl_q16 .. ptl_encode16, luma, the chroma pair (shift 26 here), ptl_load_pixel: shared with yuv4xxp10_f32.hip
 
 #ifndef PTL_YUVF_UNROLL
 #define PTL_YUVF_UNROLL 2  // sub-frames per group: 4 x 16-byte loads per lane each.  Measured at 4K, N = 4 (profiles/r11): 1 (95 VGPRs, five waves per SIMD) 5.53 TB/s,
                            // 2 (107, four waves) 5.12, 4 (150, three waves) 4.90; N = 1 and N = 16 do not tell them apart.  1 is the candidate; 2 is what the tests ran on
 #endif
-
-// unorm8 of the render entries at 16 bits.  v >= 1 (+inf too) goes through 1.0f: 65535.0f + 0.5f = 65535.5 exactly, truncated to 65535; the
-// largest v < 1 gives 65535.496.  The value converted is never negative, so the truncation is the floor.
-// The product and the sum are each rounded to binary32.  A --genco build contracts by default, and this toolchain's __fmul_rn / __fadd_rn are
-// a plain `*` and `+` compiled WITH that default (they came out as one v_pk_fma_f32): the two operations stand here, under the pragma.
-__device__ __forceinline__ unsigned int ptl_q16(float v) {
-#pragma clang fp contract(off)
-    const float above = v > 0.0f ? v : 0.0f;  // NaN, -0, negatives, -inf -> 0
-    const float c = above >= 1.0f ? 1.0f : above;
-    const float scaled = c * 65535.0f;
-    return (unsigned int)(scaled + 0.5f);
-}
-
-// One: n == 1, decided once per launch.  E = q then (q (q - 1) < q^2 <= q (q + 1)), so a "sum" holds q itself and nothing is squared,
-// divided or rooted: a plain conversion.
-template <bool One>
-__device__ __forceinline__ void ptl_accumulate_f32(ptl_u64 (&sum)[3], ptl_f32x4 p) {
-    const unsigned int q[3] = {ptl_q16(p.x), ptl_q16(p.y), ptl_q16(p.z)};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) sum[c] += One ? (ptl_u64)q[c] : (ptl_u64)q[c] * q[c];  // (one v_mad_u64_u32)
-}
-
-// floor(sum / n) for sum <= 256 * 65535^2 < 2^40 and 2 <= n <= 256, with inv_n = 1.0 / n (binary64, once per lane).  (double)sum is exact.
-// x = sum * inv_n + 2^-10 carries two roundings of 2^-53 relative on a value < 2^39 and inv_n's own: off by less than 2^-12 from
-// sum / n + 2^-10.  sum / n is an integer k, or at least 1/n >= 2^-8 away from one: x lies in (k, k + 1) either way and truncates to k.
-// k <= 65535^2 fits 32 bits.  (A 64-bit `/` would be a call's worth of VALU, twelve times per lane.)
-__device__ __forceinline__ unsigned int ptl_mean_n(ptl_u64 sum, double inv_n) {
-    return (unsigned int)__fma_rn((double)sum, inv_n, 0x1p-10);
-}
-
-// floor(sqrt(m) + 1/2) in integers for m <= 65535^2: the hardware estimate of the root is within 0.02 of it ((float)m and v_sqrt_f32 are
-// good to 2^-24 relative each, the sum to 2^-9 absolute), so e is at most one off and the two comparisons of the definition settle it.
-// e <= 65535 here (sqrt(m) + 0.52 < 65536), so e (e + 1) <= 65535 * 65536 fits 32 bits.
-__device__ __forceinline__ unsigned int ptl_root_nearest(unsigned int m) {
-    unsigned int e = (unsigned int)(__builtin_amdgcn_sqrtf((float)m) + 0.5f);
-    const unsigned int above = e * e + e;  // e (e + 1); e (e - 1) = above - 2 e
-    if (m > above) ++e;
-    else if (e != 0u && m <= above - 2u * e) --e;
-    return e;
-}
-
-template <bool One>
-__device__ __forceinline__ void ptl_encode16(unsigned int (&a)[3], const ptl_u64 (&sum)[3], double inv_n) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) a[c] = One ? (unsigned int)sum[c] : ptl_root_nearest(ptl_mean_n(sum[c], inv_n));
-}
-
-// The largest accumulator is 65473 * 65535 + 2^21 = 4 292 870 207 < 2^32.
-__device__ __forceinline__ unsigned int ptl_luma10_16(const unsigned int (&a)[3]) {
-    return (13920u * a[0] + 46826u * a[1] + 4727u * a[2] + (1u << 21)) >> 22;
-}
-// s: the 1-2-1 x 1-1 weighted sums (0 .. 524 280).  Both accumulators stay positive (>= 33 553 928), so >> is a plain shift.
-__device__ __forceinline__ unsigned int ptl_cb10_16(const unsigned int (&s)[3]) {
-    const long long acc = -15003ll * s[0] - 50470ll * s[1] + 65473ll * s[2] + (512ll << 26) + (1ll << 25);
-    return (unsigned int)min(1023ll, acc >> 26);
-}
-__device__ __forceinline__ unsigned int ptl_cr10_16(const unsigned int (&s)[3]) {
-    const long long acc = 65473ll * s[0] - 59470ll * s[1] - 6003ll * s[2] + (512ll << 26) + (1ll << 25);
-    return (unsigned int)min(1023ll, acc >> 26);
-}
-
-// A sub-frame is addressed as "uniform base + 32-bit byte offset of the lane" (16 W*H <= 2^32, the entry point refuses more): the base
-// stays in scalar registers and a lane keeps one 32-bit offset per row instead of a 64-bit address per load.
-__device__ __forceinline__ ptl_f32x4 ptl_load_pixel(const ptl_u32x4* frame, unsigned int byte_offset) {
-    return *reinterpret_cast<const ptl_f32x4*>(reinterpret_cast<const char*>(frame) + byte_offset);
-}
 
 // Fast path: block b = (row pair j, column pair i), bw = W / 2 blocks per row; b is also the index of its chroma sample.
 template <bool One, class Frames>
@@ -169,8 +101,8 @@ __device__ __forceinline__ void ptl_yuvf_block(const Frames& frames, int n, doub
         for (int c = 0; c < 3; ++c) s[c] += a[row][0][c] + 2u * a[row][1][c] + a[row][2][c];
     }
     const unsigned int n_px = (unsigned)w * (unsigned)h, c_px = n_px >> 2;  // cw * ch with both even
-    out[n_px + b] = (unsigned short)ptl_cb10_16(s);
-    out[n_px + c_px + b] = (unsigned short)ptl_cr10_16(s);
+    out[n_px + b] = (unsigned short)ptl_cb10_16<26>(s);
+    out[n_px + c_px + b] = (unsigned short)ptl_cr10_16<26>(s);
 }
 
 // General path: chroma sample t = (i, j) with its up-to-2x2 luma pixels; coordinates clamped, 2-byte stores.
@@ -209,8 +141,8 @@ __device__ __forceinline__ void ptl_yuvf_sample(const Frames& frames, int n, dou
 #pragma unroll
     for (int c = 0; c < 3; ++c) s[c] = a[0][0][c] + 2u * a[0][1][c] + a[0][2][c] + a[1][0][c] + 2u * a[1][1][c] + a[1][2][c];
     const unsigned int n_px = (unsigned)w * (unsigned)h, c_px = cw * ch;
-    out[n_px + t] = (unsigned short)ptl_cb10_16(s);
-    out[n_px + c_px + t] = (unsigned short)ptl_cr10_16(s);
+    out[n_px + t] = (unsigned short)ptl_cb10_16<26>(s);
+    out[n_px + c_px + t] = (unsigned short)ptl_cr10_16<26>(s);
 }
 
 template <bool One, class Frames>

@@ -1,0 +1,106 @@
+// yuv_common.h -- what the kernels that turn N sub-frames into one planar Y'CbCr 10-bit frame share (yuv420p10.hip, yuv420p10_f32.hip,
+// yuv4xxp10.hip, yuv4xxp10_f32.hip): the loads through a 32-bit lane offset, the encode of the averaged frame A (8 bit from RGBA8 sums, 16 bit
+// from RGBA32F sub-frames), luma, and the chroma pair with the shift of the sampling as a template parameter.  The weights of a chroma
+// sample's sum S_c add up to 2^(K - 16) (RGBA8) or 2^(K - 23) (float): 8 at 4:2:0, 4 at 4:2:2, 1 at 4:4:4.
+#pragma once
+#include "average_common.h"  // pointer lists, ptl_accumulate, ptl_div_n, ptl_l_to_s -- the same functions ptl_average_images runs
+
+typedef unsigned int ptl_u32x2 __attribute__((ext_vector_type(2)));
+typedef float ptl_f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned long long ptl_u64;
+
+// ---- RGBA8 sub-frames: A holds 8-bit values, 32-bit integer arithmetic ----------------------------------------------------------------
+__device__ __forceinline__ unsigned int ptl_luma10(const unsigned int (&a)[3]) {
+    return (55896u * a[0] + 188037u * a[1] + 18982u * a[2] + 32768u) >> 16;
+}
+// s: the weighted sums of a chroma sample, 0 .. 255 * 2^(K - 16).  Both accumulators stay positive (>= 65 410 << (K - 16)), so >> is a plain shift.
+template <int K>
+__device__ __forceinline__ unsigned int ptl_cb10(const int (&s)[3]) {
+    return (unsigned int)min(1023, (-30123 * s[0] - 101335 * s[1] + 131458 * s[2] + (512 << K) + (1 << (K - 1))) >> K);
+}
+template <int K>
+__device__ __forceinline__ unsigned int ptl_cr10(const int (&s)[3]) {
+    return (unsigned int)min(1023, (131458 * s[0] - 119404 * s[1] - 12054 * s[2] + (512 << K) + (1 << (K - 1))) >> K);
+}
+// A sub-frame is addressed as "uniform base + 32-bit byte offset of the lane" (W*H <= 2^29, the entry point refuses more): the base stays
+// in scalar registers and a lane keeps one 32-bit offset per row instead of a 64-bit address per load.
+__device__ __forceinline__ ptl_u32x4 ptl_load16(const ptl_u32x4* frame, unsigned int byte_offset) {
+    return ptl_stream_load(reinterpret_cast<const ptl_u32x4*>(reinterpret_cast<const char*>(frame) + byte_offset));
+}
+__device__ __forceinline__ unsigned int ptl_load4(const ptl_u32x4* frame, unsigned int byte_offset) {
+    return *reinterpret_cast<const unsigned int*>(reinterpret_cast<const char*>(frame) + byte_offset);
+}
+
+// channel sums of the sub-frames -> the bytes ptl_average_images writes
+__device__ __forceinline__ void ptl_encode3(unsigned int (&a)[3], const unsigned int* sum, unsigned int magic) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a[c] = ptl_l_to_s(ptl_div_n(sum[c], magic));
+}
+
+// ---- RGBA32F sub-frames: A holds 16-bit values, chroma in 64-bit integers -------------------------------------------------------------
+// unorm8 of the render entries at 16 bits.  v >= 1 (+inf too) goes through 1.0f: 65535.0f + 0.5f = 65535.5 exactly, truncated to 65535; the
+// largest v < 1 gives 65535.496.  The value converted is never negative, so the truncation is the floor.
+// The product and the sum are each rounded to binary32.  A --genco build contracts by default, and this toolchain's __fmul_rn / __fadd_rn are
+// a plain `*` and `+` compiled WITH that default (they came out as one v_pk_fma_f32): the two operations stand here, under the pragma.
+__device__ __forceinline__ unsigned int ptl_q16(float v) {
+#pragma clang fp contract(off)
+    const float above = v > 0.0f ? v : 0.0f;  // NaN, -0, negatives, -inf -> 0
+    const float c = above >= 1.0f ? 1.0f : above;
+    const float scaled = c * 65535.0f;
+    return (unsigned int)(scaled + 0.5f);
+}
+
+// One: n == 1, decided once per launch.  E = q then (q (q - 1) < q^2 <= q (q + 1)), so a "sum" holds q itself and nothing is squared,
+// divided or rooted: a plain conversion.
+template <bool One>
+__device__ __forceinline__ void ptl_accumulate_f32(ptl_u64 (&sum)[3], ptl_f32x4 p) {
+    const unsigned int q[3] = {ptl_q16(p.x), ptl_q16(p.y), ptl_q16(p.z)};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) sum[c] += One ? (ptl_u64)q[c] : (ptl_u64)q[c] * q[c];  // (one v_mad_u64_u32)
+}
+
+// floor(sum / n) for sum <= 256 * 65535^2 < 2^40 and 2 <= n <= 256, with inv_n = 1.0 / n (binary64, once per lane).  (double)sum is exact.
+// x = sum * inv_n + 2^-10 carries two roundings of 2^-53 relative on a value < 2^39 and inv_n's own: off by less than 2^-12 from
+// sum / n + 2^-10.  sum / n is an integer k, or at least 1/n >= 2^-8 away from one: x lies in (k, k + 1) either way and truncates to k.
+// k <= 65535^2 fits 32 bits.  (A 64-bit `/` would be a call's worth of VALU, twelve times per lane.)
+__device__ __forceinline__ unsigned int ptl_mean_n(ptl_u64 sum, double inv_n) {
+    return (unsigned int)__fma_rn((double)sum, inv_n, 0x1p-10);
+}
+
+// floor(sqrt(m) + 1/2) in integers for m <= 65535^2: the hardware estimate of the root is within 0.02 of it ((float)m and v_sqrt_f32 are
+// good to 2^-24 relative each, the sum to 2^-9 absolute), so e is at most one off and the two comparisons of the definition settle it.
+// e <= 65535 here (sqrt(m) + 0.52 < 65536), so e (e + 1) <= 65535 * 65536 fits 32 bits.
+__device__ __forceinline__ unsigned int ptl_root_nearest(unsigned int m) {
+    unsigned int e = (unsigned int)(__builtin_amdgcn_sqrtf((float)m) + 0.5f);
+    const unsigned int above = e * e + e;  // e (e + 1); e (e - 1) = above - 2 e
+    if (m > above) ++e;
+    else if (e != 0u && m <= above - 2u * e) --e;
+    return e;
+}
+
+template <bool One>
+__device__ __forceinline__ void ptl_encode16(unsigned int (&a)[3], const ptl_u64 (&sum)[3], double inv_n) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a[c] = One ? (unsigned int)sum[c] : ptl_root_nearest(ptl_mean_n(sum[c], inv_n));
+}
+
+// The largest accumulator is 65473 * 65535 + 2^21 = 4 292 870 207 < 2^32.
+__device__ __forceinline__ unsigned int ptl_luma10_16(const unsigned int (&a)[3]) {
+    return (13920u * a[0] + 46826u * a[1] + 4727u * a[2] + (1u << 21)) >> 22;
+}
+// s: the weighted sums of a chroma sample, 0 .. 65535 * 2^(K - 23).  Both accumulators stay positive (>= 8 388 545 << (K - 23)), so >> is a plain shift.
+template <int K>
+__device__ __forceinline__ unsigned int ptl_cb10_16(const unsigned int (&s)[3]) {
+    const long long acc = -15003ll * s[0] - 50470ll * s[1] + 65473ll * s[2] + (512ll << K) + (1ll << (K - 1));
+    return (unsigned int)min(1023ll, acc >> K);
+}
+template <int K>
+__device__ __forceinline__ unsigned int ptl_cr10_16(const unsigned int (&s)[3]) {
+    const long long acc = 65473ll * s[0] - 59470ll * s[1] - 6003ll * s[2] + (512ll << K) + (1ll << (K - 1));
+    return (unsigned int)min(1023ll, acc >> K);
+}
+
+// A float sub-frame through the same kind of offset (16 W*H <= 2^32, the entry point refuses more), 16 bytes per pixel.
+__device__ __forceinline__ ptl_f32x4 ptl_load_pixel(const ptl_u32x4* frame, unsigned int byte_offset) {
+    return *reinterpret_cast<const ptl_f32x4*>(reinterpret_cast<const char*>(frame) + byte_offset);
+}
