@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../../include/portal_amd.h"
+#include "../kernels/yuv_shape.h"
 #include "hip_api.h"
 #include "internal.h"
 
@@ -29,9 +30,12 @@ constexpr int kMaxSubframes = 64;        // PTL_MAX_SUBFRAMES in average_images.
 constexpr int kMaxSubframesTable = 256;  // beyond: a pointer table in device memory; 256 is where the exact multiply-high mean ends
 
 struct LoadedKernel {
-    hip::hipModule_t module = nullptr;
     hip::hipFunction_t fn = nullptr;
     hip::hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+struct LoadedModule {
+    hip::hipModule_t module = nullptr;
+    std::map<std::string, LoadedKernel> entries;
 };
 
 std::string library_dir() {
@@ -42,39 +46,41 @@ std::string library_dir() {
     return p == std::string::npos ? "." : path.substr(0, p);
 }
 
-// one module per (device, kernel file)
+// one module per (device, kernel file), read and loaded once; its functions by entry, each with its own pair of timing events
 int load_kernel(int device, const char* file, const char* entry, LoadedKernel** out) {
     static std::mutex mu;
-    static std::map<std::string, LoadedKernel> cache;
+    static std::map<std::string, LoadedModule> cache;
     std::lock_guard<std::mutex> lock(mu);
-    std::string key = std::to_string(device) + ":" + file + ":" + entry;
-    auto it = cache.find(key);
-    if (it != cache.end()) {
-        *out = &it->second;
-        return PTL_OK;
-    }
     std::string err;
     const hip::Runtime* rt = hip::runtime(&err);
     if (!rt) {
         set_last_error(err);
         return PTL_ERR_NO_DEVICE;
     }
-    std::string path = library_dir() + "/kernels/" + file;
-    std::ifstream f(path, std::ios::binary);
-    if (!f) {
-        set_last_error("missing gfx950 code object `" + path + "`: run `make kernels` (no CPU fallback)");
-        return PTL_ERR_INVALID;
+    LoadedModule& m = cache[std::to_string(device) + ":" + file];  // (a module that failed to load stays null here and is tried again)
+    if (auto it = m.entries.find(entry); it != m.entries.end()) {
+        *out = &it->second;
+        return PTL_OK;
     }
-    std::vector<char> code((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    std::string path = library_dir() + "/kernels/" + file;
     LoadedKernel k;
-    if (rt->hipSetDevice(device) != 0 || rt->hipModuleLoadData(&k.module, code.data()) != 0 ||
-        rt->hipModuleGetFunction(&k.fn, k.module, entry) != 0) {
+    bool ok = rt->hipSetDevice(device) == 0;
+    if (!m.module) {
+        std::ifstream f(path, std::ios::binary);
+        if (!f) {
+            set_last_error("missing gfx950 code object `" + path + "`: run `make kernels` (no CPU fallback)");
+            return PTL_ERR_INVALID;
+        }
+        std::vector<char> code((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        ok = ok && rt->hipModuleLoadData(&m.module, code.data()) == 0;
+    }
+    if (!ok || rt->hipModuleGetFunction(&k.fn, m.module, entry) != 0) {
         set_last_error("cannot load `" + path + "` on device " + std::to_string(device));
         return PTL_ERR_HIP;
     }
     rt->hipEventCreate(&k.ev0);
     rt->hipEventCreate(&k.ev1);
-    *out = &cache.emplace(key, k).first->second;
+    *out = &m.entries.emplace(entry, k).first->second;
     return PTL_OK;
 }
 
@@ -92,7 +98,7 @@ int timed(const hip::Runtime* rt, LoadedKernel* k, void* stream, float* elapsed_
     return err;
 }
 
-// What ptl_average_images and ptl_average_to_yuv420p10 share: a kernel over N sub-frames with two entries (up to 64 pointers in the
+// What ptl_average_images and the ptl_average_*_to_yuv* family share: a kernel over N sub-frames with two entries (up to 64 pointers in the
 // kernel arguments, beyond in a device table), launched as `lanes` lanes in workgroups of 256 (grid-stride beyond the cap) on `stream`.
 // The kernel's arguments are (frames, n, tail...).
 struct SubframeKernel {
@@ -182,82 +188,57 @@ extern "C" int ptl_average_images(int device, const void* const* frames_rgba8, i
     return launch_over_subframes(device, kernel, frames_rgba8, n_frames, {&out_rgba8, &n_px}, n_px / 4, stream, elapsed_ms);  // a lane per 16-byte vector
 }
 
-// ptl_average_to_yuv420p10: the same averaging fused with the conversion to planar Y'CbCr 4:2:0 10 bit (portal_amd/csrc/kernels/yuv420p10.hip,
-// the contract is in include/portal_amd.h).  A lane owns an 8x2 block where the frame allows it (W % 16 == 0, H even), else one chroma sample.
-extern "C" size_t ptl_yuv420p10_frame_bytes(int width, int height) {
-    if (width <= 0 || height <= 0) return 0;
-    const size_t cw = ((size_t)width + 1) / 2, ch = ((size_t)height + 1) / 2;
-    return 2 * ((size_t)width * (size_t)height + 2 * cw * ch);
-}
-
-extern "C" int ptl_average_to_yuv420p10(int device, const void* const* frames_rgba8, int n_frames, void* out_yuv, int width, int height, void* stream,
-                                        float* elapsed_ms) {
-    if (int rc = check_subframes(frames_rgba8, n_frames, out_yuv, width, height)) return rc;
-    if ((long)width * height > (1L << 29)) return PTL_ERR_INVALID;  // the kernel addresses a sub-frame with 32-bit byte offsets
-    const SubframeKernel kernel{"yuv420p10.hsaco", "ptl_average_to_yuv420p10_kernel", "ptl_average_to_yuv420p10_table_kernel", "average_to_yuv420p10"};
-    const bool blocks_8x2 = width % 16 == 0 && height % 2 == 0;  // the kernel takes the same decision
-    long lanes = blocks_8x2 ? (long)(width / 8) * (height / 2) : (long)((width + 1) / 2) * ((height + 1) / 2);
-    return launch_over_subframes(device, kernel, frames_rgba8, n_frames, {&out_yuv, &width, &height}, lanes, stream, elapsed_ms);
-}
-
-// ptl_average_f32_to_yuv420p10: the deep-colour form (portal_amd/csrc/kernels/yuv420p10_f32.hip, the contract is in include/portal_amd.h): the
-// sub-frames are the RGBA32F frames a render call stores as out_rgba32f, 16 bytes per pixel.  A lane owns a 2x2 block where both sizes are
-// even, else one chroma sample: the same count either way.
-extern "C" int ptl_average_f32_to_yuv420p10(int device, const void* const* frames_rgba32f, int n_frames, void* out_yuv, int width, int height, void* stream,
-                                            float* elapsed_ms) {
-    if (int rc = check_subframes(frames_rgba32f, n_frames, out_yuv, width, height)) return rc;
-    if ((long)width * height > (1L << 28)) return PTL_ERR_INVALID;  // the kernel addresses a sub-frame with 32-bit byte offsets, 16 bytes per pixel
-    const SubframeKernel kernel{"yuv420p10_f32.hsaco", "ptl_average_f32_to_yuv420p10_kernel", "ptl_average_f32_to_yuv420p10_table_kernel", "average_f32_to_yuv420p10"};
-    long lanes = (long)((width + 1) / 2) * ((height + 1) / 2);
-    return launch_over_subframes(device, kernel, frames_rgba32f, n_frames, {&out_yuv, &width, &height}, lanes, stream, elapsed_ms);
-}
-
-// ptl_average_to_yuv10 / ptl_average_f32_to_yuv10: the same two frames with the chroma sampling chosen (portal_amd/csrc/kernels/yuv4xxp10.hip,
-// yuv4xxp10_f32.hip; the contract is in include/portal_amd.h).  420 is the entry above.  A lane owns 8x1 (RGBA8, W % 8 == 0) or 4x1 (float,
-// W % 4 == 0) pixels where the width allows it, else one pixel (444) or one chroma sample (422): the kernels take the same decision.
+// The Y4M hand-off: the same averaging fused with the conversion to planar Y'CbCr 10 bit, from RGBA8 sub-frames (portal_amd/csrc/kernels/yuv10.hip)
+// or from the RGBA32F frames a render call stores as out_rgba32f (yuv10_f32.hip), at 4:2:0, 4:2:2 or 4:4:4; the contract is in
+// include/portal_amd.h.  Which frames take the fast path, and how many lanes a frame needs either way, is yuv_shape.h's to say: the kernels'
+// dispatcher reads the same header.
 namespace {
+#define PTL_YUV_KERNEL(file, name) SubframeKernel{file, "ptl_" name "_kernel", "ptl_" name "_table_kernel", name}
+const SubframeKernel kYuvKernels[2][3] = {
+    {PTL_YUV_KERNEL("yuv10.hsaco", "average_to_yuv420p10"), PTL_YUV_KERNEL("yuv10.hsaco", "average_to_yuv422p10"), PTL_YUV_KERNEL("yuv10.hsaco", "average_to_yuv444p10")},
+    {PTL_YUV_KERNEL("yuv10_f32.hsaco", "average_f32_to_yuv420p10"), PTL_YUV_KERNEL("yuv10_f32.hsaco", "average_f32_to_yuv422p10"),
+     PTL_YUV_KERNEL("yuv10_f32.hsaco", "average_f32_to_yuv444p10")}};
+#undef PTL_YUV_KERNEL
+
+bool is_chroma(int chroma) { return chroma == PTL_CHROMA_420 || chroma == PTL_CHROMA_422 || chroma == PTL_CHROMA_444; }
 bool known_chroma(int chroma, const char* what) {
-    if (chroma == PTL_CHROMA_420 || chroma == PTL_CHROMA_422 || chroma == PTL_CHROMA_444) return true;
+    if (is_chroma(chroma)) return true;
     set_last_error(std::string(what) + ": chroma " + std::to_string(chroma) + " is none of 420, 422, 444");
     return false;
 }
-long lanes_4xx(int width, int height, int chroma, int block) {
-    if (width % block == 0) return (long)(width / block) * height;
-    return chroma == PTL_CHROMA_444 ? (long)width * height : (long)((width + 1) / 2) * height;
+
+int average_to_yuv(bool f32, int chroma, int device, const void* const* frames, int n_frames, void* out_yuv, int width, int height, void* stream, float* elapsed_ms) {
+    if (!known_chroma(chroma, f32 ? "average_f32_to_yuv10" : "average_to_yuv10")) return PTL_ERR_INVALID;
+    if (int rc = check_subframes(frames, n_frames, out_yuv, width, height)) return rc;
+    if ((long)width * height > ptl_yuv_max_pixels(f32)) return PTL_ERR_INVALID;  // the kernel addresses a sub-frame with 32-bit byte offsets
+    const SubframeKernel& kernel = kYuvKernels[f32][chroma == PTL_CHROMA_420 ? 0 : chroma == PTL_CHROMA_422 ? 1 : 2];
+    const long lanes = ptl_yuv_lanes(f32, chroma, (unsigned)width, (unsigned)height);
+    return launch_over_subframes(device, kernel, frames, n_frames, {&out_yuv, &width, &height}, lanes, stream, elapsed_ms);
 }
 }  // namespace
 
 extern "C" size_t ptl_yuv10_frame_bytes(int width, int height, int chroma) {
-    if (width <= 0 || height <= 0) return 0;
-    if (chroma == PTL_CHROMA_420) return ptl_yuv420p10_frame_bytes(width, height);
-    if (chroma != PTL_CHROMA_422 && chroma != PTL_CHROMA_444) return 0;
-    const size_t cw = chroma == PTL_CHROMA_444 ? (size_t)width : ((size_t)width + 1) / 2;
-    return 2 * ((size_t)width * (size_t)height + 2 * cw * (size_t)height);
+    if (width <= 0 || height <= 0 || !is_chroma(chroma)) return 0;
+    const size_t cw = ptl_yuv_cw(chroma, (unsigned)width), ch = ptl_yuv_ch(chroma, (unsigned)height);
+    return 2 * ((size_t)width * (size_t)height + 2 * cw * ch);
 }
+extern "C" size_t ptl_yuv420p10_frame_bytes(int width, int height) { return ptl_yuv10_frame_bytes(width, height, PTL_CHROMA_420); }
 
 extern "C" int ptl_average_to_yuv10(int device, const void* const* frames_rgba8, int n_frames, void* out_yuv, int width, int height, int chroma, void* stream,
                                     float* elapsed_ms) {
-    if (!known_chroma(chroma, "average_to_yuv10")) return PTL_ERR_INVALID;
-    if (chroma == PTL_CHROMA_420) return ptl_average_to_yuv420p10(device, frames_rgba8, n_frames, out_yuv, width, height, stream, elapsed_ms);
-    if (int rc = check_subframes(frames_rgba8, n_frames, out_yuv, width, height)) return rc;
-    if ((long)width * height > (1L << 29)) return PTL_ERR_INVALID;  // the kernel addresses a sub-frame with 32-bit byte offsets
-    const bool half = chroma == PTL_CHROMA_422;
-    const SubframeKernel kernel{"yuv4xxp10.hsaco", half ? "ptl_average_to_yuv422p10_kernel" : "ptl_average_to_yuv444p10_kernel",
-                                half ? "ptl_average_to_yuv422p10_table_kernel" : "ptl_average_to_yuv444p10_table_kernel", half ? "average_to_yuv422p10" : "average_to_yuv444p10"};
-    return launch_over_subframes(device, kernel, frames_rgba8, n_frames, {&out_yuv, &width, &height}, lanes_4xx(width, height, chroma, 8), stream, elapsed_ms);
+    return average_to_yuv(false, chroma, device, frames_rgba8, n_frames, out_yuv, width, height, stream, elapsed_ms);
 }
-
 extern "C" int ptl_average_f32_to_yuv10(int device, const void* const* frames_rgba32f, int n_frames, void* out_yuv, int width, int height, int chroma, void* stream,
                                         float* elapsed_ms) {
-    if (!known_chroma(chroma, "average_f32_to_yuv10")) return PTL_ERR_INVALID;
-    if (chroma == PTL_CHROMA_420) return ptl_average_f32_to_yuv420p10(device, frames_rgba32f, n_frames, out_yuv, width, height, stream, elapsed_ms);
-    if (int rc = check_subframes(frames_rgba32f, n_frames, out_yuv, width, height)) return rc;
-    if ((long)width * height > (1L << 28)) return PTL_ERR_INVALID;  // the kernel addresses a sub-frame with 32-bit byte offsets, 16 bytes per pixel
-    const bool half = chroma == PTL_CHROMA_422;
-    const SubframeKernel kernel{"yuv4xxp10_f32.hsaco", half ? "ptl_average_f32_to_yuv422p10_kernel" : "ptl_average_f32_to_yuv444p10_kernel",
-                                half ? "ptl_average_f32_to_yuv422p10_table_kernel" : "ptl_average_f32_to_yuv444p10_table_kernel",
-                                half ? "average_f32_to_yuv422p10" : "average_f32_to_yuv444p10"};
-    return launch_over_subframes(device, kernel, frames_rgba32f, n_frames, {&out_yuv, &width, &height}, lanes_4xx(width, height, chroma, 4), stream, elapsed_ms);
+    return average_to_yuv(true, chroma, device, frames_rgba32f, n_frames, out_yuv, width, height, stream, elapsed_ms);
+}
+extern "C" int ptl_average_to_yuv420p10(int device, const void* const* frames_rgba8, int n_frames, void* out_yuv, int width, int height, void* stream,
+                                        float* elapsed_ms) {
+    return average_to_yuv(false, PTL_CHROMA_420, device, frames_rgba8, n_frames, out_yuv, width, height, stream, elapsed_ms);
+}
+extern "C" int ptl_average_f32_to_yuv420p10(int device, const void* const* frames_rgba32f, int n_frames, void* out_yuv, int width, int height, void* stream,
+                                            float* elapsed_ms) {
+    return average_to_yuv(true, PTL_CHROMA_420, device, frames_rgba32f, n_frames, out_yuv, width, height, stream, elapsed_ms);
 }
 
 // ptl_aa_edges: the classification pass of the adaptive anti-aliasing (portal_amd/csrc/kernels/aa_edges.hip; the contract is in
@@ -286,18 +267,12 @@ extern "C" int ptl_aa_edges_slices(int device, const void* frames_rgba8, unsigne
     return launch_aa_edges(device, "aa_edges_slices.hsaco", "ptl_aa_edges_slices_kernel", "aa_edges_slices", args, counts, n, width, height, stream, elapsed_ms);
 }
 
-extern "C" int ptl_y4m_header(int width, int height, int fps, char* buf, size_t cap) {
-    if (width <= 0 || height <= 0 || fps <= 0 || !buf) return PTL_ERR_INVALID;
-    int len = std::snprintf(buf, cap, "YUV4MPEG2 W%d H%d F%d:1 Ip A1:1 C420p10 XYSCSS=420P10 XCOLORRANGE=FULL\n", width, height, fps);
-    return len > 0 && (size_t)len < cap ? len : PTL_ERR_INVALID;  // (the terminating NUL has to fit as well)
-}
-
 extern "C" int ptl_y4m_header_chroma(int width, int height, int fps, int chroma, char* buf, size_t cap) {
-    if (chroma == PTL_CHROMA_420) return ptl_y4m_header(width, height, fps, buf, cap);
     if (!known_chroma(chroma, "y4m_header") || width <= 0 || height <= 0 || fps <= 0 || !buf) return PTL_ERR_INVALID;
     int len = std::snprintf(buf, cap, "YUV4MPEG2 W%d H%d F%d:1 Ip A1:1 C%dp10 XYSCSS=%dP10 XCOLORRANGE=FULL\n", width, height, fps, chroma, chroma);
     return len > 0 && (size_t)len < cap ? len : PTL_ERR_INVALID;  // (the terminating NUL has to fit as well)
 }
+extern "C" int ptl_y4m_header(int width, int height, int fps, char* buf, size_t cap) { return ptl_y4m_header_chroma(width, height, fps, PTL_CHROMA_420, buf, cap); }
 
 // Device frame buffers for callers that keep frames on the GPU between kernels (the video pipeline: sub-frames ->
 // ptl_average_images -> one download).  The reference's counterpart is the macroquad render target and

@@ -1,5 +1,5 @@
 // average_common.h -- what the kernels that average RGBA8 sub-frames in linear light share (average_images.hip,
-// yuv420p10.hip): the sub-frame pointer lists, the 16-byte accumulate, the multiply-high mean and the gamma-2 encode.
+// yuv10.hip): the sub-frame pointer lists, the 16-byte accumulate, the multiply-high mean and the gamma-2 encode.
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>

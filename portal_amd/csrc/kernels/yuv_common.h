@@ -1,9 +1,18 @@
-// yuv_common.h -- what the kernels that turn N sub-frames into one planar Y'CbCr 10-bit frame share (yuv420p10.hip, yuv420p10_f32.hip,
-// yuv4xxp10.hip, yuv4xxp10_f32.hip): the loads through a 32-bit lane offset, the encode of the averaged frame A (8 bit from RGBA8 sums, 16 bit
-// from RGBA32F sub-frames), luma, and the chroma pair with the shift of the sampling as a template parameter.  The weights of a chroma
-// sample's sum S_c add up to 2^(K - 16) (RGBA8) or 2^(K - 23) (float): 8 at 4:2:0, 4 at 4:2:2, 1 at 4:4:4.
+// yuv_common.h -- what the kernels that turn N sub-frames into one planar Y'CbCr 10-bit frame share (yuv10.hip: RGBA8 sub-frames,
+// yuv10_f32.hip: RGBA32F ones).  Per sub-frame format: the loads through a 32-bit lane offset, the encode of the averaged frame A (8 bit
+// from RGBA8 sums, 16 bit from RGBA32F sub-frames), luma, and the chroma pair with the shift of the sampling as a template parameter.  Written
+// once for both formats, at the end: the n == 1 split and the entries, over each source's dispatchers.  The weights of a chroma sample's sum S_c add up to 2^(K - 16) (RGBA8) or 2^(K - 23) (float): 8 at 4:2:0, 4 at
+// 4:2:2, 1 at 4:4:4.
+//
+// Contract (include/portal_amd.h).  A(x, y) is the averaged frame of the format (yuv10.hip, yuv10_f32.hip).  Layout:
+// Y plane W*H little-endian u16, then Cb and Cr, cw*ch each.  The samplings differ in the chroma sample's tap window alone (yuv_shape.h):
+//   4:2:0  cw = (W+1)/2, ch = (H+1)/2   S_c = sum over rows 2j, 2j+1 of A_c(2i-1, .) + 2 A_c(2i, .) + A_c(2i+1, .)   MPEG-2 ("left") siting
+//   4:2:2  cw = (W+1)/2, ch = H         S_c = A_c(2i-1, y) + 2 A_c(2i, y) + A_c(2i+1, y)                             co-sited with luma column 2i
+//   4:4:4  cw = W,       ch = H         S_c = A_c(x, y)
+// with every coordinate clamped to the frame.
 #pragma once
 #include "average_common.h"  // pointer lists, ptl_accumulate, ptl_div_n, ptl_l_to_s -- the same functions ptl_average_images runs
+#include "yuv_shape.h"       // the samplings, the fast-path predicate and the block shapes: the host sizes the launch by the same text
 
 typedef unsigned int ptl_u32x2 __attribute__((ext_vector_type(2)));
 typedef float ptl_f32x4 __attribute__((ext_vector_type(4)));
@@ -104,3 +113,39 @@ __device__ __forceinline__ unsigned int ptl_cr10_16(const unsigned int (&s)[3]) 
 __device__ __forceinline__ ptl_f32x4 ptl_load_pixel(const ptl_u32x4* frame, unsigned int byte_offset) {
     return *reinterpret_cast<const ptl_f32x4*>(reinterpret_cast<const char*>(frame) + byte_offset);
 }
+
+// ---- what a launch is, written once for both formats: the n == 1 split and the entries ----------------------------------------------------
+// A format: what a launch computes once for its encode -- the multiply-high magic of ptl_div_n (RGBA8) or nothing (float: the dispatcher
+// takes 1.0 / n itself) -- and One (float only): n == 1, compiled in.  Each source specialises ptl_yuv_frame<format, sampling>, its
+// dispatcher, once for 4:2:0 and once for the other two samplings: the split below reaches them without a forwarding layer.
+struct ptl_rgba8 {
+    static __device__ __forceinline__ unsigned int param(int n) { return 0xffffffffu / (unsigned)n + 1u; }
+    static constexpr unsigned int kParamOne = 0u;  // ptl_div_n's "no division"
+};
+template <bool One>
+struct ptl_rgba32f {
+    static __device__ __forceinline__ int param(int) { return 0; }
+    static constexpr int kParamOne = 0;
+};
+template <class Format, int Chroma>
+struct ptl_yuv_frame;  // run(frames, n, param, out, w, h): one frame, grid-stride
+
+// Many, Single: the format for n > 1 and for n == 1 (the same struct where the format has no One).
+template <class Many, class Single, int Chroma, class Frames>
+__device__ __forceinline__ void ptl_yuv_all(const Frames& frames, int n, unsigned short* __restrict__ out, int w, int h) {
+    // wave-uniform, as in ptl_average_all.  ptl_div_n tests its magic per value (54 of them per 8x2 block): one test per launch instead,
+    // each side with the answer compiled in -- n == 1, a plain conversion, has no multiply at all
+    if (n > 1) ptl_yuv_frame<Many, Chroma>::run(frames, n, Many::param(n), out, w, h);
+    else ptl_yuv_frame<Single, Chroma>::run(frames, n, Single::kParamOne, out, w, h);
+}
+
+// The two entries of a sampling: up to 64 sub-frames travel in the kernel arguments; for 65..256 the pointers no longer fit them and
+// come from a table in device memory (as for ptl_average_images_table_kernel).
+#define PTL_YUV_ENTRIES(name, Many, Single, Chroma)                                                                                               \
+    extern "C" __global__ void __launch_bounds__(256) name##_kernel(ptl_frame_list frames, int n, unsigned short* __restrict__ out, int w, int h) { \
+        ptl_yuv_all<Many, Single, Chroma>(frames, n, out, w, h);                                                                         \
+    }                                                                                                                                        \
+    extern "C" __global__ void __launch_bounds__(256)                                                                                        \
+    name##_table_kernel(const ptl_u32x4* const* table, int n, unsigned short* __restrict__ out, int w, int h) {                             \
+        ptl_yuv_all<Many, Single, Chroma>(ptl_frame_table{table}, n, out, w, h);                                                         \
+    }

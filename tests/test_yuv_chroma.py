@@ -1,10 +1,8 @@
-"""`render --frames y4m --chroma 420|422|444`: the 4:2:2 and 4:4:4 kernels (portal_amd/csrc/kernels/yuv4xxp10.hip, yuv4xxp10_f32.hip), their C
+"""`render --frames y4m --chroma 420|422|444`: the 4:2:2 and 4:4:4 kernels (portal_amd/csrc/kernels/yuv10.hip, yuv10_f32.hip), their C
 ABI (ptl_average_to_yuv10, ptl_average_f32_to_yuv10, ptl_yuv10_frame_bytes, ptl_y4m_header_chroma), the Python mirror and the CLI option,
 against tests/yuv_chroma_reference.py (a numpy restatement of the contract in DESIGN.md 2.3.3).  Every comparison of a payload is byte
 equality."""
 import os
-import re
-import stat
 import subprocess
 
 import numpy as np
@@ -13,9 +11,9 @@ import pytest
 from tests import yuv_chroma_reference as cr
 from tests import yuv_deep_reference as dr
 from tests import yuv_reference as yr
+from tests.yuv_harness import (KNOB, ROOT, _assert_same_payload, _averaged, _c_getenv, _case, _check_stream, _compile_with_usage, _convert, _copying_stub, _entries,
+                               _expected_stream, _frame_from_values, _render, _special_values, gpu)  # noqa: F401 (gpu: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 NEW = (422, 444)
 KERNELS = [(False, 422), (False, 444), (True, 422), (True, 444)]  # (float sub-frames, sampling): the four new kernels
 KERNEL_IDS = ["rgba8-422", "rgba8-444", "f32-422", "f32-444"]
@@ -177,32 +175,22 @@ def test_entry_points_refuse_before_any_gpu_call(pa, deep):
     assert "#define PTL_CHROMA_420 420" in header and "#define PTL_CHROMA_422 422" in header and "#define PTL_CHROMA_444 444" in header
 
 
-@pytest.mark.parametrize("source,prefix", [("yuv4xxp10", "ptl_average_to_yuv"), ("yuv4xxp10_f32", "ptl_average_f32_to_yuv")])
+@pytest.mark.parametrize("source,prefix", [("yuv10", "ptl_average_to_yuv"), ("yuv10_f32", "ptl_average_f32_to_yuv")])
 def test_make_kernels_builds_the_code_objects_without_scratch(pa, tmp_path, source, prefix):
-    """`make kernels` leaves the code object; the file has exactly its four entries, each with 0 bytes of scratch, no LDS and at most 128
-    VGPRs (the compiler's own notes, printed); the shared device functions live in yuv_common.h, which the 4:2:0 files include as well."""
+    """`make kernels` leaves the code object; the file has exactly its six entries, the four of 4:2:2 and 4:4:4 among them, each with 0 bytes
+    of scratch, no LDS and at most 128 VGPRs (the compiler's own notes, printed); the shared device functions live in yuv_common.h."""
+    import re
+
     subprocess.run(["make", "kernels"], cwd=ROOT, check=True, capture_output=True)
     assert os.path.getsize(os.path.join(ROOT, "portal_amd", "kernels", source + ".hsaco")) > 1000
-    src = os.path.join(ROOT, "portal_amd", "csrc", "kernels", source + ".hip")
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-vgpr-regalloc=basic", "--genco", "--no-gpu-bundle-output",
-                          "-Rpass-analysis=kernel-resource-usage", src, "-o", str(tmp_path / (source + ".hsaco"))], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr
-    usage, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\w+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|VGPRs): (\d+)", line)
-        if m and name:
-            usage.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    print(usage)
-    assert set(usage) == {f"{prefix}{c}p10{t}_kernel" for c in NEW for t in ("", "_table")}
+    usage = _compile_with_usage(source, tmp_path)
+    assert set(usage) == _entries(prefix) > {f"{prefix}{c}p10{t}_kernel" for c in NEW for t in ("", "_table")}
     for entry, u in usage.items():
         assert u["ScratchSize [bytes/lane]"] == 0 and u["LDS Size [bytes/block]"] == 0, (entry, u)
         assert u["VGPRs"] <= 128, (entry, u)  # four waves per SIMD
     makefile = open(os.path.join(ROOT, "Makefile")).read()
     assert f"portal_amd/kernels/{source}.hsaco" in re.search(r"^KERNELS\s*:=(.*)$", makefile, re.M).group(1)
-    for kernel in ("yuv420p10.hip", "yuv420p10_f32.hip", source + ".hip"):
+    for kernel in ("yuv10.hip", "yuv10_f32.hip"):
         text = open(os.path.join(ROOT, "portal_amd", "csrc", "kernels", kernel)).read()
         assert '#include "average_common.h"' in text and '#include "yuv_common.h"' in text
 
@@ -229,79 +217,9 @@ def test_cli_refuses_chroma_where_it_means_nothing(pa, tmp_path, cmd, extra, rea
 # ---------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------
-GUARD = 0xA5
-KNOB = "PTL_AVERAGE_IMAGES_GRID_CAP"
-
-
-@pytest.fixture(scope="module")
-def gpu(pa):
-    if pa.device_count() < 1:
-        pytest.fail("no HIP device visible: the render path has no CPU fallback")
-    return pa
-
-
 def _is_fast(deep, w):
     """The decision of the kernels and of the host: 8x1 pixels per lane (RGBA8) or 4x1 (float) where the width allows it."""
     return w % (4 if deep else 8) == 0
-
-
-def _convert(pa, deep, chroma, frames, w, h, offset=0):
-    """Sub-frames (numpy (h, w, 4) uint8 / float32, or cuda tensors; the same object may appear more than once) -> payload bytes; the 64
-    guard bytes behind the frame (and `offset` before it) must survive."""
-    import torch
-
-    staged = {}
-    for f in frames:
-        if id(f) not in staged:
-            staged[id(f)] = f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f, np.float32 if deep else np.uint8)).cuda()
-            assert staged[id(f)].numel() == w * h * 4 and staged[id(f)].dtype == (torch.float32 if deep else torch.uint8) and staged[id(f)].data_ptr() % 16 == 0
-    nbytes = pa.yuv10_frame_bytes(w, h, chroma)
-    assert nbytes == cr.frame_bytes(w, h, chroma)
-    buf = torch.full((offset + nbytes + 64,), GUARD, dtype=torch.uint8, device="cuda")
-    assert buf.data_ptr() % 256 == 0
-    call = pa.average_f32_to_yuv10_device if deep else pa.average_to_yuv10_device
-    call([staged[id(f)].data_ptr() for f in frames], buf.data_ptr() + offset, w, h, chroma, stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    host = buf.cpu().numpy()
-    assert (host[:offset] == GUARD).all() and (host[offset + nbytes:] == GUARD).all(), "written outside the frame"
-    return host[offset: offset + nbytes].tobytes()
-
-
-def _assert_same_payload(got: bytes, want: bytes, w, h, chroma, what):
-    if got == want:
-        return
-    assert len(got) == len(want), (what, len(got), len(want))
-    for name, g, r in zip(("Y", "Cb", "Cr"), cr.split_planes(got, w, h, chroma), cr.split_planes(want, w, h, chroma)):
-        bad = np.argwhere(g != r)
-        if len(bad):
-            y, x = bad[0]
-            pytest.fail(f"{what}: plane {name} differs in {len(bad)} of {g.size} samples, first at x={x} y={y}: got {g[y, x]}, want {r[y, x]}")
-
-
-def _averaged(deep, frames):
-    """A: the averaged frame the contract starts from, by the shipped references."""
-    if deep:
-        return dr.encode16(frames)
-    from oracle import postprocess as pp
-
-    return pp.average_images(frames) if len(frames) > 1 else frames[0]
-
-
-_cases = {}
-
-
-def _case(deep, seed, n, w, h):
-    """(sub-frames, A): computed once per key, shared by the samplings and the caps, never modified."""
-    key = (deep, seed, n, w, h)
-    if key not in _cases:
-        rng = np.random.default_rng(seed)
-        if deep:  # mostly [0, 1), a band beyond both ends
-            frames = [rng.random((h, w, 4), dtype=np.float32) for _ in range(n)]
-            frames[0][: (h + 3) // 4] = rng.uniform(-0.25, 1.25, ((h + 3) // 4, w, 4)).astype(np.float32)
-        else:
-            frames = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(n)]
-        _cases[key] = (frames, _averaged(deep, frames))
-    return _cases[key]
 
 
 def _bits(deep):
@@ -317,7 +235,7 @@ def test_kernel_matches_reference_for_every_subframe_count(gpu, deep, chroma, n)
     assert not _is_fast(deep, 13) and _is_fast(deep, 32) and (32 // (4 if deep else 8)) * 34 == (272 if deep else 136)
     for w, h in ((13, 11), (32, 34)):
         frames, a = _case(deep, 100 * n + w, n, w, h)
-        _assert_same_payload(_convert(gpu, deep, chroma, frames, w, h), cr.payload(a, chroma, _bits(deep)), w, h, chroma, f"{w}x{h} n={n}")
+        _assert_same_payload(_convert(gpu, deep, chroma, frames, w, h), cr.payload(a, chroma, _bits(deep)), w, h, f"{w}x{h} n={n}", chroma)
 
 
 SIZES = [(1, 1), (2, 1), (1, 2), (5, 3), (13, 11), (8, 1), (24, 3), (128, 5), (1032, 3), (244, 135)]
@@ -335,7 +253,7 @@ def test_kernel_matches_reference_at_any_frame_size(gpu, deep, chroma, w, h):
     offset = 0 if _is_fast(deep, w) else 16
     if (w, h) in ((1, 1), (5, 3), (13, 11)):
         assert offset == 16 and (offset + 2 * w * h) % 4 == 2
-    _assert_same_payload(_convert(gpu, deep, chroma, frames, w, h, offset=offset), cr.payload(a, chroma, _bits(deep)), w, h, chroma, f"{w}x{h}")
+    _assert_same_payload(_convert(gpu, deep, chroma, frames, w, h, offset=offset), cr.payload(a, chroma, _bits(deep)), w, h, f"{w}x{h}", chroma)
 
 
 def _saturation_frames(deep, w, h, bands):
@@ -366,7 +284,7 @@ def test_saturated_colours(gpu, deep, chroma, shape):
             a = _averaged(deep, [frame] * n)
             assert np.array_equal(np.asarray(a)[..., :3], (np.asarray(frame)[..., :3] * (65535 if deep else 1)).astype(np.int64))  # identical sub-frames: exact
             got = _convert(gpu, deep, chroma, [frame] * n, w, h)
-            _assert_same_payload(got, cr.payload(a, chroma, _bits(deep)), w, h, chroma, f"{shape} {label} n={n}")
+            _assert_same_payload(got, cr.payload(a, chroma, _bits(deep)), w, h, f"{shape} {label} n={n}", chroma)
             _, cb, crr = cr.split_planes(got, w, h, chroma)
             _, ucb, ucr = cr.planes(a, chroma, _bits(deep), clamp=False)
             assert ucb.max() <= 1024 and ucr.max() <= 1024 and cb.max() <= 1023 and crr.max() <= 1023
@@ -386,7 +304,7 @@ def test_every_8_bit_colour_once_at_444(gpu):
     frame = np.arange(1 << 24, dtype="<u4").view(np.uint8).reshape(h, w, 4)
     assert frame[0, 1].tolist() == [1, 0, 0, 0] and frame[-1, -1].tolist() == [255, 255, 255, 0]
     got = _convert(gpu, False, 444, [frame], w, h)
-    _assert_same_payload(got, cr.payload(frame, 444, 8), w, h, 444, "every colour")
+    _assert_same_payload(got, cr.payload(frame, 444, 8), w, h, "every colour", 444)
     y, cb, crr = cr.split_planes(got, w, h, 444)
     assert y.min() == 0 and y.max() == 1023 and cb.min() == 0 and cb.max() == 1023 and crr.min() == 0 and crr.max() == 1023
 
@@ -404,25 +322,9 @@ def test_every_16_bit_value_once(gpu, chroma):
     assert np.array_equal(dr.encode16([frame]), q)
     for c in range(3):
         assert np.array_equal(np.sort(q[..., c].ravel()), p)
-    _assert_same_payload(_convert(gpu, True, chroma, [frame], w, h), cr.payload(q, chroma, 16), w, h, chroma, "every q")
+    _assert_same_payload(_convert(gpu, True, chroma, [frame], w, h), cr.payload(q, chroma, 16), w, h, "every q", chroma)
     narrow = np.ascontiguousarray(frame[:, : w - 1])
-    _assert_same_payload(_convert(gpu, True, chroma, [narrow], w - 1, h), cr.payload(q[:, : w - 1], chroma, 16), w - 1, h, chroma, "every q, general path")
-
-
-def _special_values():
-    """The special bit patterns of tests/test_yuv_deep.py: NaN of both signs, both infinities, both zeros, negatives, denormals, 1.0 and
-    its neighbours, values above 1, and for a few hundred k the floats on both sides of the rounding boundary (k + 1/2) / 65535."""
-    bits = np.array([0x7fc00000, 0xffc00000, 0x7f800001, 0xff800001, 0x7fffffff, 0x7f800000, 0xff800000, 0x00000000, 0x80000000, 0xbf800000, 0xb3000000, 0xff7fffff,
-                     0x00000001, 0x007fffff, 0x80000001, 0x807fffff, 0x00800000, 0x3f800000, 0x3f7fffff, 0x3f800001, 0x40000000, 0x7f7fffff, 0x3f000000], np.uint32)
-    k = np.unique(np.concatenate([np.arange(0, 40), np.arange(65495, 65535), np.random.default_rng(5).integers(0, 65535, 240)]))
-    lo, hi = (k / 65535.0).astype(np.float32).view(np.uint32).astype(np.int64), ((k + 1) / 65535.0).astype(np.float32).view(np.uint32).astype(np.int64)
-    while (hi - lo > 1).any():  # bisection over the bit patterns: the first float that gives k + 1 and the last that gives k
-        mid = (lo + hi) // 2
-        up = dr.quantise16(mid.astype(np.uint32).view(np.float32)) > k
-        lo, hi = np.where(up, lo, mid), np.where(up, mid, hi)
-    first, last = hi.astype(np.uint32).view(np.float32), lo.astype(np.uint32).view(np.float32)
-    assert np.array_equal(dr.quantise16(first), k + 1) and np.array_equal(dr.quantise16(last), k) and len(k) >= 300
-    return np.concatenate([bits.view(np.float32), first, last, np.nextafter(first, np.float32(2))]).astype(np.float32)
+    _assert_same_payload(_convert(gpu, True, chroma, [narrow], w - 1, h), cr.payload(q[:, : w - 1], chroma, 16), w - 1, h, "every q, general path", chroma)
 
 
 @pytest.mark.gpu
@@ -432,26 +334,9 @@ def test_special_float_inputs_as_bit_patterns(gpu, chroma, w, h):
     """As one sub-frame, as two (the values reversed in the second) and as three; 32x12 the fast path, 33x11 the general one."""
     values = _special_values()
     assert values.size <= 3 * w * h and _is_fast(True, w) == (w == 32)
-
-    def frame_of(v):
-        rgb = np.full(3 * w * h, 0.5, np.float32)
-        rgb[: v.size] = v
-        frame = np.full((h, w, 4), np.nan, np.float32)  # alpha: NaN, which is ignored
-        frame[..., :3] = rgb.reshape(h, w, 3)
-        return frame
-
-    frame, reversed_frame = frame_of(values), frame_of(values[::-1])
+    frame, reversed_frame = _frame_from_values(values, w, h), _frame_from_values(values[::-1], w, h)
     for frames in ([frame], [frame, reversed_frame], [frame, frame, reversed_frame]):
-        _assert_same_payload(_convert(gpu, True, chroma, frames, w, h), cr.payload(dr.encode16(frames), chroma, 16), w, h, chroma, f"special n={len(frames)}")
-
-
-def _c_getenv(name):
-    """What std::getenv of the library sees (monkeypatch.setenv goes through os.environ, which calls putenv)."""
-    import ctypes as C
-
-    libc = C.CDLL(None)
-    libc.getenv.restype, libc.getenv.argtypes = C.c_char_p, [C.c_char_p]
-    return libc.getenv(name.encode())
+        _assert_same_payload(_convert(gpu, True, chroma, frames, w, h), cr.payload(dr.encode16(frames), chroma, 16), w, h, f"special n={len(frames)}", chroma)
 
 
 def _lanes(deep, chroma, w, h):
@@ -486,7 +371,7 @@ def test_grid_stride_with_the_cap_knob(gpu, monkeypatch, kind, cap, n):
         monkeypatch.setenv(KNOB, str(cap))
         assert _c_getenv(KNOB) == str(cap).encode()
         got = _convert(gpu, deep, chroma, frames, w, h)
-        _assert_same_payload(got, want, w, h, chroma, f"{kind} deep={deep} cap={cap} n={n}")
+        _assert_same_payload(got, want, w, h, f"{kind} deep={deep} cap={cap} n={n}", chroma)
         assert got == shipped
 
 
@@ -538,78 +423,10 @@ def test_elapsed_ms_and_a_stream_of_the_callers(gpu, deep, chroma):
         side.synchronize()
         assert out.cpu().numpy().tobytes() == got
     a = _averaged(deep, [f.cpu().numpy() for f in frames])
-    _assert_same_payload(got, cr.payload(a, chroma, _bits(deep)), w, h, chroma, "side stream")
+    _assert_same_payload(got, cr.payload(a, chroma, _bits(deep)), w, h, "side stream", chroma)
 
 
 # ---- the CLI ---------------------------------------------------------------------------------
-W, H, FPS = 64, 36, 2
-
-
-def _path_without_ffmpeg():
-    return os.pathsep.join(d for d in os.environ.get("PATH", "").split(os.pathsep) if d and not os.path.exists(os.path.join(d, "ffmpeg")))
-
-
-def _render(pa, out_dir, blur, extra, path):
-    exe = os.path.join(os.path.dirname(pa.__file__), "portal-amd")
-    scene = pa.scene_path("basics")
-    clip = pa.Scene.from_file(scene).animations()[0][0]
-    cmd = ["timeout", "-k", "10", "300", exe, "render", scene, clip, "--width", str(W), "--height", str(H), "--fps", str(FPS), "--motion-blur-frames", str(blur),
-           "--aa-count", "2", "--render-depth", "12", "--frames", "y4m", "--out-dir", str(out_dir), "--asset-root", os.path.dirname(os.path.dirname(scene))] + extra
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=dict(os.environ, PATH=path))
-    assert out.returncode == 0, out.stderr + out.stdout
-    return out
-
-
-_drawn = {}
-
-
-def _drawn_clip(pa, blur):
-    """The clip drawn through the Python mirror, as _expected_stream of tests/test_yuv_output.py does, once per blur: per frame the RGBA8
-    and the float sub-frames.  -> (frames, clip name)"""
-    if blur not in _drawn:
-        clip, duration = pa.Scene.from_file(pa.scene_path("basics")).animations()[0]
-        count = max(1, int(np.float32(duration) * np.float32(FPS)))
-        scene = pa.Scene.from_file(pa.scene_path("basics"))
-        r = pa.SceneRenderer(scene, device=0)
-        r.set_option("aa_count", 2)
-        r.set_option("render_depth", 12)
-        scene.init_animation(clip)
-        r.update(0.0)
-        frames = []
-        for i in range(count):
-            subs8, subs32 = [], []
-            for j in range(blur):
-                r.set_option("aa_start", j)
-                r.update((i / count + j / blur / count * 0.5) * float(np.float32(duration)))
-                drawn = r.draw(W, H, rgba8=True, rgba32f=True)
-                subs8.append(np.array(drawn["rgba8"]))
-                subs32.append(np.array(drawn["rgba32f"]))
-            frames.append((subs8, subs32))
-        _drawn[blur] = (frames, clip)
-    return _drawn[blur]
-
-
-def _expected_stream(pa, blur, chroma, deep):
-    """Header plus, per frame, FRAME and the numpy reference of the sub-frames the library draws."""
-    frames, clip = _drawn_clip(pa, blur)
-    stream = cr.y4m_header(W, H, FPS, chroma)
-    for subs8, subs32 in frames:
-        stream += b"FRAME\n" + cr.payload(_averaged(deep, subs32 if deep else subs8), chroma, _bits(deep))
-    return stream, len(frames), clip
-
-
-def _check_stream(got: bytes, want: bytes, count, chroma):
-    header = cr.y4m_header(W, H, FPS, chroma)
-    size = 6 + cr.frame_bytes(W, H, chroma)
-    assert got[: len(header)] == header
-    assert len(got) == len(header) + count * size, "not exactly `count` frames"
-    for i in range(count):
-        at = len(header) + i * size
-        assert got[at: at + 6] == b"FRAME\n", i
-        _assert_same_payload(got[at + 6: at + size], want[at + 6: at + size], W, H, chroma, f"frame {i}")
-    assert got == want
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("deep", [False, True], ids=["plain", "deep-colour"])
 @pytest.mark.parametrize("chroma", [444, 422])
@@ -620,21 +437,17 @@ def test_render_cli_streams_the_sampling_it_is_asked_for(gpu, tmp_path, blur, ch
     that records its arguments and copies stdin to its last argument -- the encoder is told the stream's pixel format and is piped the
     same bytes."""
     pa = gpu
-    want, count, clip = _expected_stream(pa, blur, chroma, deep)
-    extra = ["--chroma", str(chroma)] + (["--deep-colour"] if deep else [])
-    out = _render(pa, tmp_path / "file", blur, extra, _path_without_ffmpeg())
+    want, frames, clip = _expected_stream(pa, blur, chroma, lambda subs8, subs32: cr.payload(_averaged(deep, subs32 if deep else subs8), chroma, _bits(deep)))
+    options = ["--motion-blur-frames", str(blur), "--aa-count", "2", "--render-depth", "12", "--chroma", str(chroma)] + (["--deep-colour"] if deep else [])
+    out = _render(pa, tmp_path / "file", clip, options)
     video = tmp_path / "file" / "video" / "basics"
     in_file = (video / f"{clip}.y4m").read_bytes()
-    _check_stream(in_file, want, count, chroma)
+    _check_stream(in_file, want, len(frames), chroma)
     assert f"-pix_fmt yuv{chroma}p10le" in out.stdout and "yuv420p10le" not in out.stdout  # the message names the command that would encode the file
     assert not (video / f"{clip}.mov").exists()
 
     args_file = tmp_path / "stub_args.txt"
-    os.makedirs(tmp_path / "bin")
-    stub = tmp_path / "bin" / "ffmpeg"
-    stub.write_text(f'#!/bin/sh\nif [ "$1" = "-version" ]; then exit 0; fi\nprintf \'%s\\n\' "$@" > "{args_file}"\nfor last; do :; done\nexec cat > "$last"\n')
-    os.chmod(stub, os.stat(stub).st_mode | stat.S_IXUSR | stat.S_IXGRP | stat.S_IXOTH)
-    out = _render(pa, tmp_path / "pipe", blur, extra, str(tmp_path / "bin") + os.pathsep + os.environ.get("PATH", ""))
+    out = _render(pa, tmp_path / "pipe", clip, options, path=_copying_stub(tmp_path / "bin", args_file))
     video = tmp_path / "pipe" / "video" / "basics"
     assert (video / f"{clip}.mov").read_bytes() == in_file  # the piped bytes are the file's
     args = args_file.read_text().splitlines()

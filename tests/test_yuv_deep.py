@@ -1,4 +1,4 @@
-"""`render --frames y4m --deep-colour`: the kernel that makes 10-bit frames from float sub-frames (portal_amd/csrc/kernels/yuv420p10_f32.hip), its C
+"""`render --frames y4m --deep-colour`: the kernel that makes 10-bit frames from float sub-frames (portal_amd/csrc/kernels/yuv10_f32.hip), its C
 ABI, the Python mirror and the CLI option, against tests/yuv_deep_reference.py (a numpy restatement of the contract in DESIGN.md 2.3.2).
 Every comparison of a payload is byte equality."""
 import os
@@ -11,9 +11,9 @@ import pytest
 
 from tests import yuv_deep_reference as dr
 from tests import yuv_reference as yr
+from tests.yuv_harness import (FPS, H, HIPCC, KNOB, ROOT, W, _assert_same_payload, _c_getenv, _case_payload, _convert, _entries, _frame_from_values, _random_frames, _render,
+                               _resource_usage, _shipped_grid_cap, _special_values, gpu)  # noqa: F401 (gpu: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CORNERS = [(r, g, b) for r in (0, 65535) for g in (0, 65535) for b in (0, 65535)]  # the eight corners of the RGB cube, 16 bit
 BLUE, RED, YELLOW, CYAN, WHITE = (0, 0, 65535), (65535, 0, 0), (65535, 65535, 0), (0, 65535, 65535), (65535, 65535, 65535)
 
@@ -156,26 +156,18 @@ def test_entry_point_refuses_before_any_gpu_call(pa):
 
 
 def test_make_builds_the_code_object_without_scratch(tmp_path):
-    """`make portal_amd/kernels/yuv420p10_f32.hsaco` in a copy of the tree's Makefile and kernel sources: both entries compile for gfx950
+    """`make portal_amd/kernels/yuv10_f32.hsaco` in a copy of the tree's Makefile and kernel sources: its six entries compile for gfx950
     with 0 bytes of scratch, no SGPR or VGPR spills, no LDS and at most 128 VGPRs; the numbers are printed from the compiler's own notes.
     The object holds no fused or contracted binary32 multiply-add: the quantisation is a product and a sum, each rounded (a toolchain
     that contracts them again fails here, before any GPU run), and the packed or plain multiply it is made of is there."""
     shutil.copy(os.path.join(ROOT, "Makefile"), tmp_path / "Makefile")
     shutil.copytree(os.path.join(ROOT, "portal_amd", "csrc", "kernels"), tmp_path / "portal_amd" / "csrc" / "kernels")
-    target = "portal_amd/kernels/yuv420p10_f32.hsaco"
+    target = "portal_amd/kernels/yuv10_f32.hsaco"
     out = subprocess.run(["make", target, f"HIPCC={HIPCC} -Rpass-analysis=kernel-resource-usage"], cwd=tmp_path, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr
     assert os.path.getsize(tmp_path / target) > 1000
-    usage, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\w+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|SGPRs Spill|VGPRs Spill|VGPRs): (\d+)", line)
-        if m and name:
-            usage.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    print(usage)
-    assert set(usage) == {"ptl_average_f32_to_yuv420p10_kernel", "ptl_average_f32_to_yuv420p10_table_kernel"}
+    usage = _resource_usage(out.stderr)
+    assert set(usage) == _entries("ptl_average_f32_to_yuv") >= {"ptl_average_f32_to_yuv420p10_kernel", "ptl_average_f32_to_yuv420p10_table_kernel"}
     for entry, u in usage.items():
         assert u["ScratchSize [bytes/lane]"] == 0 and u["LDS Size [bytes/block]"] == 0, (entry, u)
         assert u["SGPRs Spill"] == 0 and u["VGPRs Spill"] == 0, (entry, u)
@@ -190,7 +182,7 @@ def test_make_builds_the_code_object_without_scratch(tmp_path):
     assert any(m.startswith(("v_pk_mul_f32", "v_mul_f32")) for m in mnemonics) and any(m.startswith(("v_pk_add_f32", "v_add_f32")) for m in mnemonics)
     makefile = open(os.path.join(ROOT, "Makefile")).read()
     assert target in re.search(r"^KERNELS\s*:=(.*)$", makefile, re.M).group(1)
-    assert '#include "average_common.h"' in open(os.path.join(ROOT, "portal_amd", "csrc", "kernels", "yuv420p10_f32.hip")).read()
+    assert '#include "average_common.h"' in open(os.path.join(ROOT, "portal_amd", "csrc", "kernels", "yuv10_f32.hip")).read()
 
 
 @pytest.mark.parametrize("cmd,extra,reason", [("render", ["--deep-colour"], "--deep-colour needs --frames y4m"),
@@ -210,69 +202,8 @@ def test_cli_refuses_deep_colour_where_it_means_nothing(pa, tmp_path, cmd, extra
 # ---------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------
-GUARD = 0xA5
-KNOB = "PTL_AVERAGE_IMAGES_GRID_CAP"
-
-
-@pytest.fixture(scope="module")
-def gpu(pa):
-    if pa.device_count() < 1:
-        pytest.fail("no HIP device visible: the render path has no CPU fallback")
-    return pa
-
-
-def _convert(pa, frames, w, h, offset=0):
-    """Float sub-frames (numpy (h, w, 4) float32, or cuda tensors; the same object may appear more than once) -> payload bytes; the 64 guard
-    bytes behind the frame (and `offset` before it) must survive."""
-    import torch
-
-    staged = {}
-    for f in frames:
-        if id(f) not in staged:
-            staged[id(f)] = f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f, np.float32)).cuda()
-            assert staged[id(f)].numel() == w * h * 4 and staged[id(f)].dtype == torch.float32 and staged[id(f)].data_ptr() % 16 == 0
-    nbytes = pa.yuv420p10_frame_bytes(w, h)
-    buf = torch.full((offset + nbytes + 64,), GUARD, dtype=torch.uint8, device="cuda")
-    assert buf.data_ptr() % 256 == 0
-    pa.average_f32_to_yuv420p10_device([staged[id(f)].data_ptr() for f in frames], buf.data_ptr() + offset, w, h, stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    host = buf.cpu().numpy()
-    assert (host[:offset] == GUARD).all() and (host[offset + nbytes:] == GUARD).all(), "written outside the frame"
-    return host[offset: offset + nbytes].tobytes()
-
-
-def _assert_same_payload(got: bytes, want: bytes, w, h, what):
-    if got == want:
-        return
-    assert len(got) == len(want), (what, len(got), len(want))
-    for name, g, r in zip(("Y", "Cb", "Cr"), yr.split_planes(got, w, h), yr.split_planes(want, w, h)):
-        bad = np.argwhere(g != r)
-        if len(bad):
-            y, x = bad[0]
-            pytest.fail(f"{what}: plane {name} differs in {len(bad)} of {g.size} samples, first at x={x} y={y}: got {g[y, x]}, want {r[y, x]}")
-
-
-def _random_frames(seed, n, w, h):
-    """Mostly [0, 1), a band beyond both ends."""
-    rng = np.random.default_rng(seed)
-    frames = [rng.random((h, w, 4), dtype=np.float32) for _ in range(n)]
-    frames[0][: (h + 3) // 4] = rng.uniform(-0.25, 1.25, ((h + 3) // 4, w, 4)).astype(np.float32)
-    return frames
-
-
 def _is_fast(w, h):
     return w % 2 == 0 and h % 2 == 0
-
-
-def _frame_from_values(values, w, h, fill=0.5):
-    """A float frame whose R, G, B channels hold `values` in order (alpha: NaN, which is ignored); the rest is `fill`."""
-    values = np.asarray(values, np.float32)
-    assert values.size <= 3 * w * h
-    rgb = np.full(3 * w * h, fill, np.float32)
-    rgb[: values.size] = values
-    frame = np.full((h, w, 4), np.nan, np.float32)
-    frame[..., :3] = rgb.reshape(h, w, 3)
-    return frame
 
 
 @pytest.mark.gpu
@@ -282,7 +213,7 @@ def test_kernel_matches_reference_for_every_subframe_count(gpu, w, h, n):
     """37x23: the general path.  256x6: the fast path, 128 blocks = two waves per row pair.  Beyond 64 sub-frames the pointer-table entry."""
     assert _is_fast(w, h) == ((w, h) == (256, 6))
     frames = _random_frames(100 * n + w, n, w, h)
-    _assert_same_payload(_convert(gpu, frames, w, h), dr.deep_reference(frames), w, h, f"{w}x{h} n={n}")
+    _assert_same_payload(_convert(gpu, True, None, frames, w, h), dr.deep_reference(frames), w, h, f"{w}x{h} n={n}")
 
 
 @pytest.mark.gpu
@@ -293,27 +224,8 @@ def test_kernel_matches_reference_at_any_frame_size(gpu, w, h):
     the frame 16 bytes into its buffer: nothing before or behind it is written."""
     assert _is_fast(w, h) == ((w, h) in ((2, 2), (130, 6)))
     frames = _random_frames(w * 1000 + h, 3, w, h)
-    _assert_same_payload(_convert(gpu, frames, w, h, offset=16), dr.deep_reference(frames), w, h, f"{w}x{h}")
-    _assert_same_payload(_convert(gpu, frames[:1], w, h), dr.deep_reference(frames[:1]), w, h, f"{w}x{h} n=1")
-
-
-def _special_values():
-    bits = np.array([0x7fc00000, 0xffc00000, 0x7f800001, 0xff800001, 0x7fffffff, 0x7f800000, 0xff800000, 0x00000000, 0x80000000, 0xbf800000, 0xb3000000, 0xff7fffff,
-                     0x00000001, 0x007fffff, 0x80000001, 0x807fffff, 0x00800000, 0x3f800000, 0x3f7fffff, 0x3f800001, 0x40000000, 0x7f7fffff, 0x3f000000], np.uint32)
-    k = np.unique(np.concatenate([np.arange(0, 40), np.arange(65495, 65535), np.random.default_rng(5).integers(0, 65535, 240)]))
-    # where the quantisation decides: the smallest float that gives k + 1, found by bisection over the bit patterns between k / 65535 (which
-    # gives k) and (k + 1) / 65535 (which gives k + 1) -- it lies next to (k + 1/2) / 65535 -- with its two neighbours
-    lo, hi = (k / 65535.0).astype(np.float32).view(np.uint32).astype(np.int64), ((k + 1) / 65535.0).astype(np.float32).view(np.uint32).astype(np.int64)
-    assert np.array_equal(dr.quantise16(lo.astype(np.uint32).view(np.float32)), k) and np.array_equal(dr.quantise16(hi.astype(np.uint32).view(np.float32)), k + 1)
-    while (hi - lo > 1).any():
-        mid = (lo + hi) // 2
-        up = dr.quantise16(mid.astype(np.uint32).view(np.float32)) > k
-        lo, hi = np.where(up, lo, mid), np.where(up, mid, hi)
-    first, last = hi.astype(np.uint32).view(np.float32), lo.astype(np.uint32).view(np.float32)  # the first float of k + 1, the last of k
-    assert np.array_equal(dr.quantise16(first), k + 1) and np.array_equal(dr.quantise16(last), k) and len(k) >= 300
-    assert (np.abs(first.astype(np.float64) * 65535.0 - (k + 0.5)) < 0.01).all()
-    values = np.concatenate([bits.view(np.float32), first, last, np.nextafter(first, np.float32(2))]).astype(np.float32)
-    return values
+    _assert_same_payload(_convert(gpu, True, None, frames, w, h, offset=16), dr.deep_reference(frames), w, h, f"{w}x{h}")
+    _assert_same_payload(_convert(gpu, True, None, frames[:1], w, h), dr.deep_reference(frames[:1]), w, h, f"{w}x{h} n=1")
 
 
 @pytest.mark.gpu
@@ -326,7 +238,7 @@ def test_special_inputs_as_bit_patterns(gpu, w, h):
     assert values.size <= 3 * w * h and _is_fast(w, h) == (w == 32)
     frame, reversed_frame = _frame_from_values(values, w, h), _frame_from_values(values[::-1], w, h)
     for frames in ([frame], [frame, reversed_frame], [frame, frame, reversed_frame]):
-        _assert_same_payload(_convert(gpu, frames, w, h), dr.deep_reference(frames), w, h, f"{w}x{h} special n={len(frames)}")
+        _assert_same_payload(_convert(gpu, True, None, frames, w, h), dr.deep_reference(frames), w, h, f"{w}x{h} special n={len(frames)}")
 
 
 @pytest.mark.gpu
@@ -340,7 +252,7 @@ def test_every_q_once(gpu):
     assert np.array_equal(dr.encode16([frame]), q)
     for c in range(3):
         assert np.array_equal(np.sort(q[..., c].ravel()), p)
-    _assert_same_payload(_convert(gpu, [frame], w, h), dr.payload_from_e(q), w, h, "every q")
+    _assert_same_payload(_convert(gpu, True, None, [frame], w, h), dr.payload_from_e(q), w, h, "every q")
 
 
 @pytest.mark.gpu
@@ -360,9 +272,9 @@ def test_rounding_boundary_of_the_root(gpu):
     assert lower >= 100 and int(hit.sum()) - lower >= 100  # both ends
     frames = [_frame_from_values(pairs[:, 0] / 65535.0, w, h, fill=0.0), _frame_from_values(pairs[:, 1] / 65535.0, w, h, fill=0.0)]
     assert np.array_equal(dr.quantise16(frames[0][..., :3]).ravel()[: len(pairs)], pairs[:, 0])
-    _assert_same_payload(_convert(gpu, frames, w, h), dr.deep_reference(frames), w, h, "root boundary")
+    _assert_same_payload(_convert(gpu, True, None, frames, w, h), dr.deep_reference(frames), w, h, "root boundary")
     general = [f[:, : w - 1] for f in frames]
-    _assert_same_payload(_convert(gpu, general, w - 1, h), dr.deep_reference(general), w - 1, h, "root boundary, general path")
+    _assert_same_payload(_convert(gpu, True, None, general, w - 1, h), dr.deep_reference(general), w - 1, h, "root boundary, general path")
 
 
 @pytest.mark.gpu
@@ -372,7 +284,7 @@ def test_largest_sum(gpu, w, h):
     frame = np.full((h, w, 4), 1.0, np.float32)
     frame[::2, :, 1] = np.inf
     frame[:, ::2, 2] = 3.5
-    got = _convert(gpu, [frame] * 256, w, h)
+    got = _convert(gpu, True, None, [frame] * 256, w, h)
     _assert_same_payload(got, dr.deep_reference([frame] * 256), w, h, "largest sum")
     y, cb, cr = yr.split_planes(got, w, h)
     assert (y == 1023).all() and (cb == 512).all() and (cr == 512).all()
@@ -401,8 +313,8 @@ def test_mean_boundary(gpu, n):
         return int((rest == 0).sum()), int((rest == n - 1).sum())
 
     assert residues(frames) == (half, half) and min(residues(general)) >= 100, (residues(frames), residues(general))
-    _assert_same_payload(_convert(gpu, frames, w, h), dr.deep_reference(frames), w, h, f"mean boundary n={n}")
-    _assert_same_payload(_convert(gpu, general, 15, 5), dr.deep_reference(general), 15, 5, f"mean boundary n={n}, general path")
+    _assert_same_payload(_convert(gpu, True, None, frames, w, h), dr.deep_reference(frames), w, h, f"mean boundary n={n}")
+    _assert_same_payload(_convert(gpu, True, None, general, 15, 5), dr.deep_reference(general), 15, 5, f"mean boundary n={n}, general path")
 
 
 @pytest.mark.gpu
@@ -414,7 +326,7 @@ def test_saturated_colours(gpu, w, h):
     for rgb in CORNERS:
         frame = np.tile(np.array([c / 65535.0 for c in rgb] + [0.25], np.float32), (h, w, 1))
         for n in (1, 2):
-            got = _convert(gpu, [frame] * n, w, h)
+            got = _convert(gpu, True, None, [frame] * n, w, h)
             _assert_same_payload(got, dr.deep_reference([frame] * n), w, h, f"{rgb} n={n}")
             _, cb, cr = yr.split_planes(got, w, h)
             _, ucb, ucr = dr.planes_from_e(dr.encode16([frame] * n), clamp=False)
@@ -427,39 +339,11 @@ def test_saturated_colours(gpu, w, h):
     assert all(reached.values()), reached
 
 
-def _shipped_grid_cap():
-    """`long cap = 256 * 16;` of launch_over_subframes (portal_amd/csrc/host/postprocess.cpp), read from the source: a changed cap fails the
-    tests that cross it instead of leaving them vacuous."""
-    src = open(os.path.join(ROOT, "portal_amd", "csrc", "host", "postprocess.cpp")).read()
-    m = re.findall(r"long cap = (\d+) \* (\d+);", src)
-    assert len(m) == 1, "launch_over_subframes no longer spells its grid cap as `long cap = A * B;`"
-    return int(m[0][0]) * int(m[0][1])
-
-
 def _lanes(w, h):
     return ((w + 1) // 2) * ((h + 1) // 2)
 
 
-def _c_getenv(name):
-    """What std::getenv of the library sees (monkeypatch.setenv goes through os.environ, which calls putenv)."""
-    import ctypes as C
-
-    libc = C.CDLL(None)
-    libc.getenv.restype, libc.getenv.argtypes = C.c_char_p, [C.c_char_p]
-    return libc.getenv(name.encode())
-
-
 KNOB_SHAPES = {"fast-256x134": (256, 134), "general-244x135": (244, 135), "fast-136x70": (136, 70)}
-_knob_cases = {}
-
-
-def _knob_case(kind, n):
-    """Sub-frames and the reference payload: computed once per (shape, n), shared by the caps, never modified."""
-    if (kind, n) not in _knob_cases:
-        w, h = KNOB_SHAPES[kind]
-        frames = _random_frames(7000 + 10 * n + len(kind), n, w, h)
-        _knob_cases[kind, n] = (frames, dr.deep_reference(frames))
-    return _knob_cases[kind, n]
 
 
 def test_knob_shapes_make_the_trips_they_are_meant_to():
@@ -482,13 +366,13 @@ def test_grid_stride_with_the_cap_knob(gpu, monkeypatch, kind, cap, n):
     still finds its lower neighbour.  Equal to the reference and to the same call with the shipped grid."""
     w, h = KNOB_SHAPES[kind]
     assert _is_fast(w, h) == kind.startswith("fast")
-    frames, want = _knob_case(kind, n)
+    frames, want = _case_payload("deep", True, 7000 + 10 * n + len(kind), n, w, h, lambda frames, a: dr.deep_reference(frames))  # once per (shape, n), shared by the caps
     monkeypatch.delenv(KNOB, raising=False)
     assert _c_getenv(KNOB) is None
-    shipped = _convert(gpu, frames, w, h)
+    shipped = _convert(gpu, True, None, frames, w, h)
     monkeypatch.setenv(KNOB, str(cap))
     assert _c_getenv(KNOB) == str(cap).encode()
-    got = _convert(gpu, frames, w, h)
+    got = _convert(gpu, True, None, frames, w, h)
     _assert_same_payload(got, want, w, h, f"{kind} cap={cap} n={n}")
     assert got == shipped
 
@@ -503,7 +387,7 @@ def test_grid_stride_at_the_shipped_cap(gpu, monkeypatch):
     assert _c_getenv(KNOB) is None and _lanes(w, h) > _shipped_grid_cap() * 256
     g = torch.Generator(device="cuda").manual_seed(2050)
     frame = torch.rand((h, w, 4), dtype=torch.float32, device="cuda", generator=g) * 1.25 - 0.125
-    got = _convert(gpu, [frame], w, h)
+    got = _convert(gpu, True, None, [frame], w, h)
     _assert_same_payload(got, dr.deep_reference([frame.cpu().numpy()]), w, h, "2050x2050")
 
 
@@ -532,25 +416,18 @@ def test_elapsed_ms_and_a_stream_of_the_callers(gpu):
 
 
 # ---- the CLI ---------------------------------------------------------------------------------
-W, H, FPS, MAX_FRAMES = 64, 36, 2, 2
+MAX_FRAMES = 2
 SCENE, CLIP = "basics", "anim.4.portals"  # (scenes/monoportal.ron has no clip; this is the clip the other end-to-end tests of `render` draw)
 
 
-def _path_without_ffmpeg():
-    return os.pathsep.join(d for d in os.environ.get("PATH", "").split(os.pathsep) if d and not os.path.exists(os.path.join(d, "ffmpeg")))
-
-
-def _render(pa, out_dir, extra):
-    exe = os.path.join(os.path.dirname(pa.__file__), "portal-amd")
-    scene = pa.scene_path(SCENE)
-    cmd = ["timeout", "-k", "10", "300", exe, "render", scene, CLIP, "--width", str(W), "--height", str(H), "--fps", str(FPS), "--max-frames", str(MAX_FRAMES), "--frames", "y4m",
-           "--out-dir", str(out_dir), "--asset-root", os.path.dirname(os.path.dirname(scene))] + extra
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=dict(os.environ, PATH=_path_without_ffmpeg()))
-    assert out.returncode == 0, out.stderr + out.stdout
+def _render_frames(pa, out_dir, extra):
+    """The first MAX_FRAMES frames of CLIP with the defaults of `render` -> the directory the clip's files are in."""
+    assert SCENE == "basics"
+    _render(pa, out_dir, CLIP, ["--max-frames", str(MAX_FRAMES)] + extra)
     return out_dir / "video" / SCENE
 
 
-def _expected_stream(pa, blur, adaptive):
+def _stream_through_the_entry_point(pa, blur, adaptive):
     """The clip's first frames drawn through the Python mirror with the float output asked for, made into payloads by the new entry point."""
     import torch
 
@@ -589,9 +466,9 @@ def test_render_cli_streams_deep_colour_frames(gpu, tmp_path, blur, adaptive, mo
     --clip-adaptive-aa 4 batched and, with --batch-subframes 0, as one adaptive draw per sub-frame: the four draw calls of the clip loop.  The start still is the one a run without the option writes: the RGBA8 sub-frames are still drawn."""
     pa = gpu
     extra = ["--motion-blur-frames", str(blur)] + (["--clip-adaptive-aa", str(adaptive)] if adaptive is not None else []) + more
-    video = _render(pa, tmp_path / "deep", extra + ["--deep-colour"])
+    video = _render_frames(pa, tmp_path / "deep", extra + ["--deep-colour"])
     got = (video / f"{CLIP}.y4m").read_bytes()
-    want = _expected_stream(pa, blur, adaptive)
+    want = _stream_through_the_entry_point(pa, blur, adaptive)
     header, size = yr.y4m_header(W, H, FPS), 6 + yr.frame_bytes(W, H)
     assert got[: len(header)] == header and len(got) == len(header) + MAX_FRAMES * size
     for i in range(MAX_FRAMES):
@@ -599,7 +476,7 @@ def test_render_cli_streams_deep_colour_frames(gpu, tmp_path, blur, adaptive, mo
         assert got[at: at + 6] == b"FRAME\n", i
         _assert_same_payload(got[at + 6: at + size], want[at + 6: at + size], W, H, f"frame {i}")
     assert got == want
-    plain = _render(pa, tmp_path / "plain", extra)
+    plain = _render_frames(pa, tmp_path / "plain", extra)
     assert (video / f"{CLIP}.start.png").read_bytes() == (plain / f"{CLIP}.start.png").read_bytes()
     eight_bit = (plain / f"{CLIP}.y4m").read_bytes()
     assert len(eight_bit) == len(got) and eight_bit != got  # the option changes the frames, not their form

@@ -1,17 +1,16 @@
-"""`render --frames y4m`: the fused average-and-convert kernel (portal_amd/csrc/kernels/yuv420p10.hip), its C ABI and the Y4M stream
+"""`render --frames y4m`: the fused average-and-convert kernel (portal_amd/csrc/kernels/yuv10.hip), its C ABI and the Y4M stream
 of the CLI, against tests/yuv_reference.py (a numpy restatement of the contract in DESIGN.md 2.3).  Every comparison is byte equality."""
 import os
 import re
-import stat
 import subprocess
 
 import numpy as np
 import pytest
 
 from tests import yuv_reference as yr
+from tests.yuv_harness import (FPS, H, KNOB, ROOT, W, _assert_same_payload, _averaged, _c_getenv, _case_payload, _check_stream, _compile_with_usage, _convert, _copying_stub,
+                               _entries, _expected_stream, _path_without_ffmpeg, _render, _shipped_grid_cap, _write_stub, gpu)  # noqa: F401 (gpu: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SIZES = [(1, 1), (2, 2), (3, 1), (5, 7), (13, 11), (16, 2), (64, 36), (1023, 3), (1920, 1080), (3840, 2160)]
 
 
@@ -62,29 +61,16 @@ def test_entry_points_refuse_what_average_images_refuses(pa):
 
 
 def test_make_kernels_builds_the_code_object_without_scratch(pa, tmp_path):
-    """`make kernels` leaves portal_amd/kernels/yuv420p10.hsaco; both entries compile for gfx950 with 0 bytes of scratch and no LDS,
+    """`make kernels` leaves portal_amd/kernels/yuv10.hsaco; its six entries compile for gfx950 with 0 bytes of scratch and no LDS,
     and average_images.hip still gets its device functions from the header the two kernels share."""
     subprocess.run(["make", "kernels"], cwd=ROOT, check=True, capture_output=True)
-    assert os.path.getsize(os.path.join(ROOT, "portal_amd", "kernels", "yuv420p10.hsaco")) > 1000
-    src = os.path.join(ROOT, "portal_amd", "csrc", "kernels", "yuv420p10.hip")
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-vgpr-regalloc=basic", "--genco", "--no-gpu-bundle-output",
-                          "-Rpass-analysis=kernel-resource-usage", src, "-o", str(tmp_path / "yuv420p10.hsaco")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr
-    usage = {}
-    name = None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\w+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|VGPRs): (\d+)", line)
-        if m and name:
-            usage.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    print(usage)
-    assert set(usage) == {"ptl_average_to_yuv420p10_kernel", "ptl_average_to_yuv420p10_table_kernel"}
+    assert os.path.getsize(os.path.join(ROOT, "portal_amd", "kernels", "yuv10.hsaco")) > 1000
+    usage = _compile_with_usage("yuv10", tmp_path)
+    assert set(usage) == _entries("ptl_average_to_yuv") >= {"ptl_average_to_yuv420p10_kernel", "ptl_average_to_yuv420p10_table_kernel"}
     for entry, u in usage.items():
         assert u["ScratchSize [bytes/lane]"] == 0 and u["LDS Size [bytes/block]"] == 0, (entry, u)
         assert u["VGPRs"] <= 128, (entry, u)  # four waves per SIMD
-    for kernel in ("average_images.hip", "yuv420p10.hip"):
+    for kernel in ("average_images.hip", "yuv10.hip"):
         assert '#include "average_common.h"' in open(os.path.join(ROOT, "portal_amd", "csrc", "kernels", kernel)).read()
 
 
@@ -155,12 +141,6 @@ def _saturation_inputs(shape):
     return inputs + [("white+black", [_flat_frame(w, h, (255, 255, 255)), _flat_frame(w, h, (0, 0, 0))])]
 
 
-def _averaged(frames):
-    from oracle import postprocess as pp
-
-    return pp.average_images(frames) if len(frames) > 1 else frames[0]
-
-
 def test_saturated_colours_reach_both_ends_of_the_chroma_range():
     """The clamp of the contract is needed and the inputs of test_saturated_colours_on_the_gpu reach it: six taps of pure blue give an
     unclamped Cb of 1024, pure red a Cr of 1024; the clamped planes hold 1023; yellow gives Cb 0 and cyan Cr 0 (accumulator 523 280, just
@@ -181,7 +161,7 @@ def test_saturated_colours_reach_both_ends_of_the_chroma_range():
     for shape, (w, h) in SATURATION_SHAPES.items():
         reached = {"cb_clamp": 0, "cr_clamp": 0, "cb_zero": 0, "cr_zero": 0}
         for label, frames in _saturation_inputs(shape):
-            a = _averaged(frames)
+            a = _averaged(False, frames)
             if len(frames) > 1 and label != "white+black":
                 assert np.array_equal(a[..., :3], frames[0][..., :3]), (shape, label)  # identical sub-frames: exact
             if label == "white+black":
@@ -204,22 +184,12 @@ def test_saturated_colours_reach_both_ends_of_the_chroma_range():
     assert int((ucb == 1024).sum()) == 2 * 7 and int((ucr == 1024).sum()) == 2 * 7
 
 
-def _shipped_grid_cap():
-    """`long cap = 256 * 16;` of launch_over_subframes (portal_amd/csrc/host/postprocess.cpp): the workgroups a post-process launch gets at
-    most.  The tests that cross it read it from the source, so a changed cap fails them instead of leaving them vacuous."""
-    src = open(os.path.join(ROOT, "portal_amd", "csrc", "host", "postprocess.cpp")).read()
-    m = re.findall(r"long cap = (\d+) \* (\d+);", src)
-    assert len(m) == 1, "launch_over_subframes no longer spells its grid cap as `long cap = A * B;`"
-    return int(m[0][0]) * int(m[0][1])
-
-
 def _yuv_lanes(w, h):
     """The lanes ptl_average_to_yuv420p10 asks for: 8x2 blocks on the block path, chroma samples on the general path."""
     return (w // 8) * (h // 2) if w % 16 == 0 and h % 2 == 0 else ((w + 1) // 2) * ((h + 1) // 2)
 
 
 CAP_CROSSING = {"general-2050x2049": (2050, 2049), "block-4096x4112": (4096, 4112)}
-KNOB = "PTL_AVERAGE_IMAGES_GRID_CAP"
 KNOB_SHAPES = {"block-256x134": (256, 134), "general-244x135": (244, 135)}
 
 
@@ -243,42 +213,6 @@ def test_stride_shapes_cross_the_grid_cap():
 # ---------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------
-GUARD = 0xA5
-
-
-@pytest.fixture(scope="module")
-def gpu(pa):
-    if pa.device_count() < 1:
-        pytest.fail("no HIP device visible: the render path has no CPU fallback")
-    return pa
-
-
-def _convert(pa, frames, w, h, offset=0):
-    """Sub-frames (numpy or cuda tensors) -> payload bytes; the 64 guard bytes behind the frame (and `offset` before it) must survive."""
-    import torch
-
-    dev = [f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)).cuda() for f in frames]
-    nbytes = pa.yuv420p10_frame_bytes(w, h)
-    buf = torch.full((offset + nbytes + 64,), GUARD, dtype=torch.uint8, device="cuda")
-    assert buf.data_ptr() % 256 == 0
-    pa.average_to_yuv420p10_device([d.data_ptr() for d in dev], buf.data_ptr() + offset, w, h, stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    host = buf.cpu().numpy()
-    assert (host[:offset] == GUARD).all() and (host[offset + nbytes:] == GUARD).all(), "written outside the frame"
-    return host[offset: offset + nbytes].tobytes()
-
-
-def _assert_same_payload(got: bytes, want: bytes, w, h, what):
-    if got == want:
-        return
-    assert len(got) == len(want), (what, len(got), len(want))
-    for name, g, r in zip(("Y", "Cb", "Cr"), yr.split_planes(got, w, h), yr.split_planes(want, w, h)):
-        bad = np.argwhere(g != r)
-        if len(bad):
-            y, x = bad[0]
-            pytest.fail(f"{what}: plane {name} differs in {len(bad)} of {g.size} samples, first at x={x} y={y}: got {g[y, x]}, want {r[y, x]}")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [1, 2, 3, 4, 7, 16, 64, 65, 256])
 def test_kernel_matches_reference_for_every_subframe_count(gpu, n):
@@ -292,7 +226,7 @@ def test_kernel_matches_reference_for_every_subframe_count(gpu, n):
     frames[0][:4] = 255
     frames[-1][-4:] = 0
     want = yr.yuv_reference(pp.average_images(frames) if n > 1 else frames[0])
-    _assert_same_payload(_convert(gpu, frames, w, h), want, w, h, f"n={n}")
+    _assert_same_payload(_convert(gpu, False, None, frames, w, h), want, w, h, f"n={n}")
 
 
 @pytest.mark.gpu
@@ -305,7 +239,7 @@ def test_block_path_matches_reference_for_every_subframe_count(gpu, n):
     rng = np.random.default_rng(2000 + n)
     frames = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(n)]
     want = yr.yuv_reference(pp.average_images(frames) if n > 1 else frames[0])
-    _assert_same_payload(_convert(gpu, frames, w, h), want, w, h, f"n={n}")
+    _assert_same_payload(_convert(gpu, False, None, frames, w, h), want, w, h, f"n={n}")
 
 
 @pytest.mark.gpu
@@ -316,7 +250,7 @@ def test_kernel_matches_reference_at_any_frame_size(gpu, w, h):
 
     rng = np.random.default_rng(w * 100 + h)
     frames = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(3)]
-    _assert_same_payload(_convert(gpu, frames, w, h), yr.yuv_reference(pp.average_images(frames)), w, h, f"{w}x{h}")
+    _assert_same_payload(_convert(gpu, False, None, frames, w, h), yr.yuv_reference(pp.average_images(frames)), w, h, f"{w}x{h}")
 
 
 @pytest.mark.gpu
@@ -328,7 +262,7 @@ def test_chroma_planes_need_no_alignment(gpu, w, h):
     assert (w * h) % 2 == 1
     rng = np.random.default_rng(77 + w)
     frames = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(3)]
-    _assert_same_payload(_convert(gpu, frames, w, h, offset=16), yr.yuv_reference(pp.average_images(frames)), w, h, f"{w}x{h} at +16")
+    _assert_same_payload(_convert(gpu, False, None, frames, w, h, offset=16), yr.yuv_reference(pp.average_images(frames)), w, h, f"{w}x{h} at +16")
 
 
 @pytest.mark.gpu
@@ -337,7 +271,7 @@ def test_every_colour_once(gpu):
     w = h = 4096
     frame = np.arange(1 << 24, dtype="<u4").view(np.uint8).reshape(h, w, 4)
     assert frame[0, 1].tolist() == [1, 0, 0, 0] and frame[-1, -1].tolist() == [255, 255, 255, 0]
-    got = _convert(gpu, [frame], w, h)
+    got = _convert(gpu, False, None, [frame], w, h)
     _assert_same_payload(got, yr.yuv_reference(frame), w, h, "every colour")
     y, cb, cr = yr.split_planes(got, w, h)
     assert y.min() == 0 and y.max() == 1023 and cb.max() <= 1023 and cr.max() <= 1023
@@ -353,8 +287,8 @@ def test_saturated_colours_on_the_gpu(gpu, shape):
     assert (w % 16 == 0 and h % 2 == 0) == (shape in ("bands-128x4", "flat-16x2"))
     reached = {"cb_clamp": 0, "cr_clamp": 0, "cb_zero": 0, "cr_zero": 0}
     for label, frames in _saturation_inputs(shape):
-        a = _averaged(frames)
-        got = _convert(gpu, frames, w, h)
+        a = _averaged(False, frames)
+        got = _convert(gpu, False, None, frames, w, h)
         _assert_same_payload(got, yr.yuv_reference(a), w, h, f"{shape} {label}")
         _, cb, cr = yr.split_planes(got, w, h)
         _, ucb, ucr = yr.yuv_planes(a, clamp=False)
@@ -372,30 +306,6 @@ def test_saturated_colours_on_the_gpu(gpu, shape):
     assert all(reached.values()), (shape, reached)  # not vacuous: the clamp was reached (unclamped 1024) in both planes, and so was 0
 
 
-def _c_getenv(name):
-    """What std::getenv of the library sees (monkeypatch.setenv goes through os.environ, which calls putenv)."""
-    import ctypes as C
-
-    libc = C.CDLL(None)
-    libc.getenv.restype, libc.getenv.argtypes = C.c_char_p, [C.c_char_p]
-    return libc.getenv(name.encode())
-
-
-_knob_cases = {}
-
-
-def _knob_case(kind, n):
-    """Sub-frames, the reference payload: computed once per (shape, n), shared by the caps, never modified."""
-    from oracle import postprocess as pp
-
-    if (kind, n) not in _knob_cases:
-        w, h = KNOB_SHAPES[kind]
-        rng = np.random.default_rng(3000 + 10 * n + len(kind))
-        frames = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(n)]
-        _knob_cases[kind, n] = (frames, yr.yuv_reference(pp.average_images(frames) if n > 1 else frames[0]))
-    return _knob_cases[kind, n]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [1, 3, 65])
 @pytest.mark.parametrize("cap", [1, 3])
@@ -406,15 +316,15 @@ def test_grid_stride_with_the_cap_knob(gpu, monkeypatch, kind, cap, n):
     256x134 is 2 144 blocks: with 3 workgroups the third trip ends after 608 lanes, in the middle of a wave, and the __shfl_up of the
     block path still finds its lower neighbour.  Equal to the reference and to the same call with the shipped grid."""
     w, h = KNOB_SHAPES[kind]
-    frames, want = _knob_case(kind, n)
+    frames, want = _case_payload("yuv420", False, 3000 + 10 * n + len(kind), n, w, h, lambda frames, a: yr.yuv_reference(a))  # once per (shape, n), shared by the caps
     monkeypatch.delenv(KNOB, raising=False)
     assert _c_getenv(KNOB) is None
-    shipped = _convert(gpu, frames, w, h)
+    shipped = _convert(gpu, False, None, frames, w, h)
     monkeypatch.setenv(KNOB, str(cap))
     assert _c_getenv(KNOB) == str(cap).encode()
     lanes = _yuv_lanes(w, h)
     assert lanes > 2 * cap * 256 and lanes <= _shipped_grid_cap() * 256  # the knob makes the trips, not the shape
-    got = _convert(gpu, frames, w, h)  # (checks the guard bytes behind the frame)
+    got = _convert(gpu, False, None, frames, w, h)  # (checks the guard bytes behind the frame)
     _assert_same_payload(got, want, w, h, f"{kind} cap={cap} n={n}")
     assert got == shipped
 
@@ -435,7 +345,7 @@ def test_grid_stride_at_the_shipped_cap(gpu, monkeypatch, kind):
     assert _shipped_grid_cap() == 4096 and lanes > 4096 * 256
     g = torch.Generator(device="cuda").manual_seed(w)
     frames = [torch.randint(0, 256, (h, w, 4), dtype=torch.uint8, device="cuda", generator=g) for _ in range(2)]
-    got = _convert(gpu, frames, w, h)
+    got = _convert(gpu, False, None, frames, w, h)
     want = yr.yuv_reference(pp.average_images([f.cpu().numpy() for f in frames]))
     _assert_same_payload(got, want, w, h, kind)
 
@@ -448,10 +358,10 @@ def test_full_size_properties(gpu):
     w, h = 3840, 2160
     g = torch.Generator(device="cuda").manual_seed(5)
     frames = [torch.randint(0, 256, (h, w, 4), dtype=torch.uint8, device="cuda", generator=g) for _ in range(4)]
-    forward = _convert(gpu, frames, w, h)
-    assert forward == _convert(gpu, list(reversed(frames)), w, h)
-    one = _convert(gpu, [frames[0]], w, h)
-    assert one == _convert(gpu, [frames[0]] * 4, w, h)
+    forward = _convert(gpu, False, None, frames, w, h)
+    assert forward == _convert(gpu, False, None, list(reversed(frames)), w, h)
+    one = _convert(gpu, False, None, [frames[0]], w, h)
+    assert one == _convert(gpu, False, None, [frames[0]] * 4, w, h)
     _assert_same_payload(one, yr.yuv_reference(frames[0].cpu().numpy()), w, h, "4K n=1")
     assert forward != one
 
@@ -483,67 +393,8 @@ def test_elapsed_ms_and_a_stream_of_the_callers(gpu):
 
 
 # ---- the CLI ---------------------------------------------------------------------------------
-W, H, FPS = 64, 36, 2
-
-
-def _path_without_ffmpeg():
-    return os.pathsep.join(d for d in os.environ.get("PATH", "").split(os.pathsep) if d and not os.path.exists(os.path.join(d, "ffmpeg")))
-
-
-def _render(pa, out_dir, blur, path, timeout=600):
-    exe = os.path.join(os.path.dirname(pa.__file__), "portal-amd")
-    scene = pa.scene_path("basics")
-    clip = pa.Scene.from_file(scene).animations()[0][0]
-    env = dict(os.environ, PATH=path)
-    return subprocess.run([exe, "render", scene, clip, "--width", str(W), "--height", str(H), "--fps", str(FPS), "--motion-blur-frames", str(blur), "--aa-count", "2",
-                           "--render-depth", "12", "--frames", "y4m", "--out-dir", str(out_dir), "--asset-root", os.path.dirname(os.path.dirname(scene))],
-                          capture_output=True, text=True, timeout=timeout, env=env)
-
-
-def _expected_stream(pa, blur):
-    """The clip drawn through the Python mirror, as test_render_cli_writes_the_frames_the_library_draws does: (stream bytes, first and last sub-frame, count)."""
-    from oracle import postprocess as pp
-
-    clip, duration = pa.Scene.from_file(pa.scene_path("basics")).animations()[0]
-    count = max(1, int(np.float32(duration) * np.float32(FPS)))
-    scene = pa.Scene.from_file(pa.scene_path("basics"))
-    r = pa.SceneRenderer(scene, device=0)
-    r.set_option("aa_count", 2)
-    r.set_option("render_depth", 12)
-    scene.init_animation(clip)
-    r.update(0.0)
-    stream, first, last = yr.y4m_header(W, H, FPS), None, None
-    for i in range(count):
-        subs = []
-        for j in range(blur):
-            r.set_option("aa_start", j)
-            r.update((i / count + j / blur / count * 0.5) * float(np.float32(duration)))
-            subs.append(r.draw(W, H)["rgba8"])
-        first = subs[0] if first is None else first
-        last = subs[-1]
-        stream += b"FRAME\n" + yr.yuv_reference(pp.average_images(subs))
-    return stream, first, last, count, clip
-
-
-def _check_stream(got: bytes, want: bytes, count):
-    header = yr.y4m_header(W, H, FPS)
-    size = 6 + yr.frame_bytes(W, H)
-    assert got[: len(header)] == header
-    assert len(got) == len(header) + count * size, "not exactly `count` frames"
-    for i in range(count):
-        a = len(header) + i * size
-        assert got[a: a + 6] == b"FRAME\n", i
-        _assert_same_payload(got[a + 6: a + size], want[a + 6: a + size], W, H, f"frame {i}")
-    assert got == want
-
-
-def _write_stub(directory, body):
-    os.makedirs(directory, exist_ok=True)
-    stub = os.path.join(directory, "ffmpeg")
-    with open(stub, "w") as f:
-        f.write("#!/bin/sh\n" + body)
-    os.chmod(stub, os.stat(stub).st_mode | stat.S_IXUSR | stat.S_IXGRP | stat.S_IXOTH)
-    return stub
+def _options(blur):
+    return ["--motion-blur-frames", str(blur), "--aa-count", "2", "--render-depth", "12"]
 
 
 @pytest.mark.gpu
@@ -552,11 +403,14 @@ def test_render_cli_streams_the_frames_the_library_draws(gpu, tmp_path, blur):
     """`portal-amd render --frames y4m` end to end, with motion blur (a, b) and with --motion-blur-frames 1 (c): without an ffmpeg the
     stream is <clip>.y4m; with one it goes through the encoder's stdin -- here a stub that copies stdin to its last argument, so the
     .mov holds the stream byte for byte.  Header, frame count, every payload, the PNG stills; no anim/ directory."""
+    from oracle import postprocess as pp
+
     pa = gpu
-    want, first, last, count, clip = _expected_stream(pa, blur)
+    want, frames, clip = _expected_stream(pa, blur, 420, lambda subs8, subs32: yr.yuv_reference(pp.average_images(subs8)))
+    assert want.startswith(yr.y4m_header(W, H, FPS) + b"FRAME\n")
+    first, last, count = frames[0][0][0], frames[-1][0][-1], len(frames)
     video = tmp_path / "file" / "video" / "basics"
-    out = _render(pa, tmp_path / "file", blur, _path_without_ffmpeg())
-    assert out.returncode == 0, out.stderr + out.stdout
+    out = _render(pa, tmp_path / "file", clip, _options(blur))
     _check_stream((video / f"{clip}.y4m").read_bytes(), want, count)
     assert "ffmpeg -f yuv4mpegpipe -i" in out.stdout  # the message names the command that would encode the file
     assert np.array_equal(pa.png_read(str(video / f"{clip}.start.png")), first)
@@ -564,9 +418,7 @@ def test_render_cli_streams_the_frames_the_library_draws(gpu, tmp_path, blur):
     assert not (tmp_path / "file" / "anim").exists() and not (video / f"{clip}.frames").exists() and not (video / f"{clip}.mov").exists()
 
     args_file = tmp_path / "stub_args.txt"
-    _write_stub(tmp_path / "bin", f'if [ "$1" = "-version" ]; then exit 0; fi\nprintf \'%s\\n\' "$@" > "{args_file}"\nfor last; do :; done\nexec cat > "$last"\n')
-    out = _render(pa, tmp_path / "pipe", blur, str(tmp_path / "bin") + os.pathsep + os.environ.get("PATH", ""))
-    assert out.returncode == 0, out.stderr + out.stdout
+    out = _render(pa, tmp_path / "pipe", clip, _options(blur), path=_copying_stub(tmp_path / "bin", args_file))
     video = tmp_path / "pipe" / "video" / "basics"
     _check_stream((video / f"{clip}.mov").read_bytes(), want, count)
     args = args_file.read_text().splitlines()
@@ -581,7 +433,8 @@ def test_render_cli_streams_the_frames_the_library_draws(gpu, tmp_path, blur):
 @pytest.mark.gpu
 def test_render_cli_fails_when_the_encoder_dies(gpu, tmp_path):
     """(d) An encoder that exits at once: the CLI reports it and returns non-zero, within the timeout, instead of blocking on the pipe."""
-    _write_stub(tmp_path / "bin", 'if [ "$1" = "-version" ]; then exit 0; fi\nexit 1\n')
-    out = _render(gpu, tmp_path / "dead", 3, str(tmp_path / "bin") + os.pathsep + os.environ.get("PATH", ""), timeout=300)
+    pa = gpu
+    clip = pa.Scene.from_file(pa.scene_path("basics")).animations()[0][0]
+    out = _render(pa, tmp_path / "dead", clip, _options(3), path=_write_stub(tmp_path / "bin", 'if [ "$1" = "-version" ]; then exit 0; fi\nexit 1\n'), check=False)
     assert out.returncode not in (0, 2), out.stderr + out.stdout
     assert "encoder" in out.stderr

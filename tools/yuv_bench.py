@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""tools/yuv_bench.py -- the fused average-and-convert kernel (ptl_average_to_yuv420p10, portal_amd/csrc/kernels/yuv420p10.hip) beside
+"""tools/yuv_bench.py -- the fused average-and-convert kernel (ptl_average_to_yuv420p10, portal_amd/csrc/kernels/yuv10.hip) beside
 the averaging kernel it grew from (ptl_average_images), on the same inputs, through the C ABI.
 
 Algorithmic bytes per launch: (4 N + 3) W H for the fused kernel (N RGBA8 sub-frames read once, 3 bytes of planar 4:2:0 10 bit written
 per pixel), (4 N + 4) W H for averaging (one RGBA8 frame written).  N = 1 has no averaging counterpart worth timing (callers skip it).
 Each cell: warm-up launches, then `--launches` launches back to back between ONE pair of events, `--repeats` times, the two kernels
 alternating; the median is reported, the spread beside it.  One JSON line per cell and kernel.
---deep adds the deep-colour kernel (ptl_average_f32_to_yuv420p10, yuv420p10_f32.hip) to the alternation, on float sub-frames of its own:
+--deep adds the deep-colour kernel (ptl_average_f32_to_yuv420p10, yuv10_f32.hip) to the alternation, on float sub-frames of its own:
 (16 N + 3) W H bytes per launch, and its bandwidth over the averaging kernel's as a third line.
---chroma 422,444 adds the other samplings (ptl_average_to_yuv10, yuv4xxp10.hip; with --deep ptl_average_f32_to_yuv10, yuv4xxp10_f32.hip) to
+--chroma 422,444 adds the other samplings (ptl_average_to_yuv10, yuv10.hip; with --deep ptl_average_f32_to_yuv10, yuv10_f32.hip) to
 the same alternation: they write 4 and 6 bytes per pixel instead of 3, and each gets a line with its bandwidth over the 4:2:0 kernel's.
 
     python tools/yuv_bench.py [--launches 200] [--repeats 7] [--sizes 3840x2160,7680x4320] [--subframes 1,4,16] [--deep] [--chroma 422,444]
