@@ -129,11 +129,36 @@ struct SurfaceIntersection {
 PTL_FN SurfaceIntersection ptl_intersection_none() { return SurfaceIntersection{false, 1e10f, 0.0f, 0.0f, vec3(0.0f)}; }
 #define intersection_none (ptl_intersection_none())
 
+// The hit helpers below are written WITHOUT early returns and conditional blocks: every field of the result is one select on the
+// verdict, with the value the reference's text gives it for every input (NaN t, +-0, infinities, d.z == 0, non-hits).  An early
+// return makes every field of the record a phi, so the compiler materialises u, v, n and the none-values before the caller's
+// nearer() is known -- and most waves then throw them away; as selects of float arithmetic they sink into the branch that reads
+// them.  -DPTL_EARLY_RETURN_HITS restores the reference's control flow (same values; the A/B of DESIGN.md 2.1.3).
 PTL_FN SurfaceIntersection plane_intersect_normalized(const Ray& r) {
     float t = ptl_div(-r.o.z, r.d.z);
+#if defined(PTL_EARLY_RETURN_HITS)
     if (t < 0.0f) return intersection_none;
     vec4 pos = r.o + r.d * t;
     return SurfaceIntersection{true, t, pos.x, pos.y, vec3(0.0f, 0.0f, 1.0f)};
+#else
+    const bool miss = t < 0.0f;  // (false for a NaN t: a hit with NaN fields, as with the early return)
+    vec4 pos = r.o + r.d * t;
+    return SurfaceIntersection{!miss, miss ? 1e10f : t, miss ? 0.0f : pos.x, miss ? 0.0f : pos.y, vec3(0.0f, 0.0f, miss ? 0.0f : 1.0f)};
+#endif
+}
+// `if (result.hit) { result.t = result.t / len; result.n = normal; }` of the plane_intersect family
+PTL_FN SurfaceIntersection ptl_plane_hit_tail(SurfaceIntersection result, float len, vec3 normal) {
+#if defined(PTL_EARLY_RETURN_HITS)
+    if (result.hit) {
+        result.t = ptl_div(result.t, len);
+        result.n = normal;
+    }
+#else
+    const bool hit = result.hit;
+    result.t = hit ? ptl_div(result.t, len) : result.t;
+    result.n = vec3(hit ? normal.x : result.n.x, hit ? normal.y : result.n.y, hit ? normal.z : result.n.z);
+#endif
+    return result;
 }
 
 // Ray against the z = 0 plane of `plane` given `plane_inv` = inverse(plane).
@@ -155,12 +180,7 @@ PTL_FN SurfaceIntersection plane_intersect(Ray r, const mat4& plane_inv, vec3 no
     r = transform(plane_inv, r);
     float len = length(r.d);
     r.d = normalize(r.d);
-    SurfaceIntersection result = plane_intersect_normalized(r);
-    if (result.hit) {
-        result.t = ptl_div(result.t, len);
-        result.n = normal;
-    }
-    return result;
+    return ptl_plane_hit_tail(plane_intersect_normalized(r), len, normal);
 }
 #endif
 
@@ -225,12 +245,7 @@ template <ptl_mask_t MASK = 0xffffu> PTL_FN SurfaceIntersection plane_intersect_
     r = ptl_transform_m<MASK>(plane_inv, r);
     float len = length(r.d);
     r.d = normalize(r.d);
-    SurfaceIntersection result = plane_intersect_normalized(r);
-    if (result.hit) {
-        result.t = ptl_div(result.t, len);
-        result.n = unit_normal;
-    }
-    return result;
+    return ptl_plane_hit_tail(plane_intersect_normalized(r), len, unit_normal);
 }
 
 // plane_intersect / plane_intersect_derived for a ray whose origin in the plane's frame is already known (first-trip plane tests,
@@ -244,12 +259,7 @@ PTL_FN SurfaceIntersection plane_intersect_o(Ray r, const mat4& plane_inv, vec3 
     r = Ray{o_in_plane, ptl_mul_direction(plane_inv, r.d), r.tmul, r.in_subspace};
     float len = length(r.d);
     r.d = normalize(r.d);
-    SurfaceIntersection result = plane_intersect_normalized(r);
-    if (result.hit) {
-        result.t = ptl_div(result.t, len);
-        result.n = normal;
-    }
-    return result;
+    return ptl_plane_hit_tail(plane_intersect_normalized(r), len, normal);
 }
 template <ptl_mask_t MASK = 0xffffu> PTL_FN SurfaceIntersection plane_intersect_derived_o(Ray r, const mat4& plane_inv, vec3 unit_normal, bool& flipped, const vec4& o_in_plane) {
 #if PTL_DEVICE_BUILD && defined(PTL_FAST_MATH)
@@ -261,12 +271,7 @@ template <ptl_mask_t MASK = 0xffffu> PTL_FN SurfaceIntersection plane_intersect_
     r = Ray{o_in_plane, ptl_mul_direction<MASK>(plane_inv, r.d), r.tmul, r.in_subspace};
     float len = length(r.d);
     r.d = normalize(r.d);
-    SurfaceIntersection result = plane_intersect_normalized(r);
-    if (result.hit) {
-        result.t = ptl_div(result.t, len);
-        result.n = unit_normal;
-    }
-    return result;
+    return ptl_plane_hit_tail(plane_intersect_normalized(r), len, unit_normal);
 }
 
 // Staged forms of three library functions for calls whose normal argument is a uniform-only expression of a scene snippet
@@ -501,13 +506,24 @@ PTL_FN SceneIntersection debug_intersect(Ray r) {
 }
 
 // library.glsl:560-589 -- what an is_inside_N() verdict does to the running nearest hit
+PTL_FN SurfaceIntersection ptl_select_hit(bool take, const SurfaceIntersection& a, const SurfaceIntersection& b) {  // take ? a : b, field by field
+    return SurfaceIntersection{take ? a.hit : b.hit, take ? a.t : b.t, take ? a.u : b.u, take ? a.v : b.v,
+                               vec3(take ? a.n.x : b.n.x, take ? a.n.y : b.n.y, take ? a.n.z : b.n.z)};
+}
 PTL_FN SceneIntersection process_plane_intersection(SceneIntersection i, SurfaceIntersection hit, int inside) {
+#if defined(PTL_EARLY_RETURN_HITS)
     if (inside != NOT_INSIDE && inside != TELEPORT && inside != TELEPORT_SUBSPACE) {
         i.hit = hit;
         i.material = inside;
     }
     return i;
+#else
+    const bool take = inside != NOT_INSIDE && inside != TELEPORT && inside != TELEPORT_SUBSPACE;
+    return SceneIntersection{take ? inside : i.material, ptl_select_hit(take, hit, i.hit), i.in_subspace};
+#endif
 }
+// (process_portal_intersection keeps the reference's control flow: as selects it saves 64 of the headline's 7 892 instructions and none of the
+// spine, and costs portal_in_portal_plus_ultra's Int-baked build its fourth wave per SIMD -- 138 VGPRs that no rung of the occupancy ladder caps.)
 PTL_FN SceneIntersection process_portal_intersection(SceneIntersection i, SurfaceIntersection hit, int inside, int teleport_material) {
     if (inside == NOT_INSIDE) return i;
     i.hit = hit;

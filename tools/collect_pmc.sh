@@ -17,6 +17,9 @@ i=0
 IFS=';' read -r -a GROUPS_ <<< "${PMC_GROUPS:-SQ_WAVES SQ_INSTS_VALU;SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES;SQ_THREAD_CYCLES_VALU;SQ_INSTS_SALU SQ_INSTS_VALU_TRANS_F32;SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32;SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_INT32;GRBM_GUI_ACTIVE SQ_WAIT_INST_ANY;SQ_WAVE_CYCLES SQ_INSTS_BRANCH;FETCH_SIZE;WRITE_SIZE}"
 for group in "${GROUPS_[@]}"; do
     i=$((i + 1))
-    rocprofv3 --pmc $group --output-format csv -d /tmp/pmc_$NAME/p$i -o p -- python $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-segments --no-second-workload --build $BUILD ${BENCH_ARGS:-} > /tmp/pmc_$NAME.log 2>&1 || tail -3 /tmp/pmc_$NAME.log
+    # every pass under a time limit of its own (PMC_PASS_SECONDS); a pass that fails or runs into it ends the collection: nothing more is started on that GPU
+    timeout -k 10 ${PMC_PASS_SECONDS:-240} rocprofv3 --pmc $group --output-format csv -d /tmp/pmc_$NAME/p$i -o p -- python $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-segments --no-second-workload --build $BUILD ${BENCH_ARGS:-} > /tmp/pmc_$NAME.log 2>&1
+    rc=$?
+    if [ $rc -ne 0 ]; then echo "pass $i ($group) ended with status $rc"; tail -3 /tmp/pmc_$NAME.log; exit $rc; fi
 done
 PMC_BENCH_LOG=/tmp/pmc_$NAME.log python $R/tools/pmc_summary.py $O/$NAME.json "${WORKLOAD:-portal_in_portal 3840x2160 depth 40, all scene uniforms baked, build $BUILD, flags '${PTL_HIPRTC_FLAGS:-}', 1 GPU; the 5 timed launches of each pass; FETCH_SIZE / WRITE_SIZE in KB}" 5 /tmp/pmc_$NAME/p*
