@@ -581,6 +581,28 @@ int ptl_average_to_yuv10(int device, const void* const* frames_rgba8, int n_fram
 int ptl_average_f32_to_yuv10(int device, const void* const* frames_rgba32f, int n_frames, void* out_yuv, int width, int height, int chroma, void* stream,
                              float* elapsed_ms);
 size_t ptl_yuv10_frame_bytes(int width, int height, int chroma); /* 0 for an unknown chroma */
+/* The same averaged frame as RGB: N RGBA32F sub-frames -> the scanlines of one 16-bit PNG (colour type 2, bit depth 16), unfiltered or with
+ * PNG's Sub filter already applied, so that the host only deflates them (ptl_png_write_rgb48 below).  Unfiltered 16-bit rows
+ * hardly compress (a 1080p frame: 8.1 MB at deflate level 3, 2.1 MB with Sub), so the filter is part of the hot path, and the kernel applies
+ * it, with the byte order, while the values are in registers.
+ * Contract (tests/png16_reference.py restates it in numpy).  A(x, y) = (E_R, E_G, E_B) is exactly the averaged frame of
+ * ptl_average_f32_to_yuv420p10 above: q per channel value of a sub-frame, M = floor(sum q^2 / n), E = floor(sqrt(M) + 1/2); for n = 1,
+ * E = q.  Alpha is ignored.  Raw row y, bytes 6x .. 6x+5:
+ *   E_R >> 8, E_R & 255, E_G >> 8, E_G & 255, E_B >> 8, E_B & 255                    big-endian samples
+ * `filter` selects the transform of the raw rows:
+ *   PTL_PNG_FILTER_NONE (0)  out = raw
+ *   PTL_PNG_FILTER_SUB  (1)  out[y][i] = (raw[y][i] - (i >= 6 ? raw[y][i - 6] : 0)) mod 256     per byte, no borrow between bytes; every
+ *                                                                                                row starts from zero
+ * out_rows: DEVICE pointer, 16-byte aligned, H rows of 6 W bytes, packed = ptl_rgb48_frame_bytes(w, h) = 6 W H bytes.  There are no
+ * filter-type bytes: the writer adds them (rows stay 8-byte aligned for W % 4 == 0).  Any width, height >= 1 with W*H <= 2^28 (a sub-frame
+ * is addressed with 32-bit byte offsets).  HBM-bound: reads 16 N and writes 6 bytes per pixel, the traffic of the 4:4:4 form above.
+ * 1 <= n_frames <= 256; validation, stream and timing are those of ptl_average_f32_to_yuv10; any other `filter` is PTL_ERR_INVALID before
+ * any GPU call.  (`portal-amd render --png-depth 16`, `portal-amd render-frame --png-depth 16`.) */
+#define PTL_PNG_FILTER_NONE 0
+#define PTL_PNG_FILTER_SUB 1
+int ptl_average_f32_to_rgb48(int device, const void* const* frames_rgba32f, int n_frames, void* out_rows, int width, int height, int filter, void* stream,
+                             float* elapsed_ms);
+size_t ptl_rgb48_frame_bytes(int width, int height); /* 6 W H; 0 for a size that is not positive */
 /* ---- adaptive anti-aliasing: supersample only the pixels that sit on an edge (opt-in, approximate by design) ------------------------
  * Every anti-aliasing sample costs a full trace, and most pixels of a frame are flat walls and smooth gradients whose centre sample is
  * already the final 8-bit colour.  An adaptive draw traces ONE sample per pixel, classifies the frame it got, and traces the full
@@ -765,6 +787,10 @@ int ptl_png_read(const char* path, uint8_t** rgba8, int* width, int* height); /*
 int ptl_png_write(const char* path, const uint8_t* rgba8, int width, int height); /* deflate level 6 */
 /* the same with an explicit deflate level 0..9 (frame sequences that an encoder consumes and deletes: level 3 is 2.3x faster) */
 int ptl_png_write_level(const char* path, const uint8_t* rgba8, int width, int height, int level);
+/* A 16-bit RGB file (IHDR: bit depth 16, colour type 2) from HOST rows exactly as ptl_average_f32_to_rgb48 wrote them with the same
+ * `filter` (PTL_PNG_FILTER_NONE or _SUB): per row the filter-type byte `filter`, then the row's 6 W bytes; one zlib stream at `level`
+ * 0 .. 9; IEND.  No per-pixel work on the host.  ptl_png_read opens such a file by its high bytes. */
+int ptl_png_write_rgb48(const char* path, const uint8_t* rows, int width, int height, int filter, int level);
 
 /* ---- template engine test hooks (src/code_generation.rs) ----------------------------------- */
 typedef struct ptl_strstore ptl_strstore;

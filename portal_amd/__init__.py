@@ -188,6 +188,9 @@ def _load() -> C.CDLL:
         "ptl_average_to_yuv10": (ci, [ci, P(vp), ci, vp, ci, ci, ci, vp, P(C.c_float)]),
         "ptl_average_f32_to_yuv10": (ci, [ci, P(vp), ci, vp, ci, ci, ci, vp, P(C.c_float)]),
         "ptl_yuv10_frame_bytes": (cs, [ci, ci, ci]),
+        "ptl_average_f32_to_rgb48": (ci, [ci, P(vp), ci, vp, ci, ci, ci, vp, P(C.c_float)]),
+        "ptl_rgb48_frame_bytes": (cs, [ci, ci]),
+        "ptl_png_write_rgb48": (ci, [cp, vp, ci, ci, ci, ci]),
         "ptl_aa_edges": (ci, [ci, vp, ci, ci, ci, vp, vp, vp, P(C.c_float)]),
         "ptl_kernel_render_refine": (ci, [vp, P(Frame), vp, vp, vp, vp, vp, vp, P(C.c_float)]),
         "ptl_renderer_draw_adaptive": (ci, [vp, P(Frame), vp, vp, vp, P(C.c_float)]),
@@ -943,6 +946,30 @@ def average_f32_to_yuv10_device(frame_ptrs, out_ptr: int, width: int, height: in
 def yuv10_frame_bytes(width: int, height: int, chroma: int) -> int:
     """Bytes of one frame as `average_to_yuv10_device` writes it at that sampling; 0 for a sampling that is none of 420, 422, 444."""
     return int(lib().ptl_yuv10_frame_bytes(width, height, chroma))
+
+
+PNG_FILTER_NONE, PNG_FILTER_SUB = 0, 1
+
+
+def average_f32_to_rgb48_device(frame_ptrs, out_ptr: int, width: int, height: int, filter: int = PNG_FILTER_SUB, device: int = 0, stream: int = 0, timed: bool = False):
+    """ptl_average_f32_to_rgb48 on DEVICE buffers given as integer addresses: the averaged frame of the RGBA32F sub-frames (that of
+    `average_f32_to_yuv420p10_device`) as the scanlines of a 16-bit RGB PNG, `rgb48_frame_bytes(width, height)` bytes at out_ptr: big-endian
+    samples, unfiltered (`PNG_FILTER_NONE`) or with PNG's Sub filter applied (`PNG_FILTER_SUB`), no filter-type bytes."""
+    return _average_to_yuv10("average_f32_to_rgb48", frame_ptrs, out_ptr, width, height, filter, device, stream, timed)
+
+
+def rgb48_frame_bytes(width: int, height: int) -> int:
+    """Bytes of one frame as `average_f32_to_rgb48_device` writes it: 6 per pixel."""
+    return int(lib().ptl_rgb48_frame_bytes(width, height))
+
+
+def png_write_rgb48(path: str, rows, width: int, height: int, filter: int = PNG_FILTER_SUB, level: int = 6) -> None:
+    """ptl_png_write_rgb48: a 16-bit RGB PNG from HOST rows (bytes or a uint8 array of 6 * width * height) exactly as
+    `average_f32_to_rgb48_device` wrote them with the same `filter`; deflate `level` 0 .. 9."""
+    a = np.ascontiguousarray(np.frombuffer(rows, dtype=np.uint8) if isinstance(rows, (bytes, bytearray, memoryview)) else rows, dtype=np.uint8)
+    if width > 0 and height > 0 and a.size != 6 * width * height:
+        raise PortalError(f"png_write_rgb48: {a.size} bytes are not {width} x {height} pixels of 6 bytes")
+    _check(lib().ptl_png_write_rgb48(path.encode(), a.ctypes.data, width, height, filter, level), "png_write_rgb48")
 
 
 def y4m_header(width: int, height: int, fps: int, chroma: int = 420) -> bytes:

@@ -21,6 +21,7 @@ int usage() {  // (and the exit status that goes with it)
                  "                  [--gpus N | --devices a,b,..] [--transport stores|copy|rccl] [--multi-process]   one frame across the GPUs of a node\n"
                  "                  [--specialize 0] do NOT bake the scene state into the kernel   [--fast] tolerance mode   [--exact-cr] numerics contract 1   [--opt3] JIT at -O3 like the library default (render-frame: -O1)   [--timing] where the wall time went\n"
                  "                  [--adaptive-aa [T]]  one sample per pixel, --aa-count samples only where a pixel differs from a neighbour by more than T codes (default 4, -1 .. 255); one GPU\n"
+                 "                  [--png-depth 8|16]   16: a 16-bit RGB file made on the GPU from the frame's float output (one quantisation, to 16 bits); one GPU\n"
                  "       portal-amd precompile <scene.ron> [--stage NAME] [--specialize 0]      fill the code-object cache (no GPU needed; render's options choose render's kernels)\n"
                  "       portal-amd render <scene[,scene..]> [clip[,clip..]] [--width 3840] [--height 2160] [--fps 60] [--motion-blur-frames 1]\n"
                  "                  [--stereoimage] [--batch-subframes 0|1] [--no-skip-existing] [--filter-starts-with P] [--aa-count 4] [--render-depth 150]\n"
@@ -35,6 +36,9 @@ int usage() {  // (and the exit status that goes with it)
                  "                                       instead of two to 8 bits): a smooth gradient keeps 1024 luma codes instead of 256.  16 more bytes per pixel and sub-frame on the card\n"
                  "                  [--chroma 420|422|444]  with --frames y4m: the chroma sampling of the stream (default 420).  422 keeps every row of chroma, 444 every sample:\n"
                  "                                       4 and 6 bytes per pixel leave the card instead of 3, and the encoder is told yuv422p10le / yuv444p10le\n"
+                 "                  [--png-depth 8|16]   with --frames png: 16 makes anim/frame_%%d.png 16-bit RGB files from the un-quantised float sub-frames (the averaged\n"
+                 "                                       frame of --deep-colour), Sub-filtered on the GPU; works with --shard K/N and resumes.  16 more bytes per pixel and\n"
+                 "                                       sub-frame on the card, 6 instead of 4 bytes per pixel leave it, and the files are 4 - 7 times larger to deflate\n"
                  "                  [--clip-adaptive-aa [T]]  adaptive anti-aliasing of every sub-frame: one sample per pixel, --aa-count samples only where a pixel differs\n"
                  "                                       from a neighbour by more than T codes (default 4, -1 .. 255); opt-in, approximate by design\n"
                  "       portal-amd emit-source <scene.ron> [--stage NAME]     print the generated HIP kernel source\n"
@@ -234,7 +238,29 @@ int render_frame(const Options& o) {
     float ms = 0.0f;
     unsigned int refined = 0;
     float pass_ms[3] = {0.0f, 0.0f, 0.0f};
-    if (o.adaptive) {  // one sample per pixel, classification, the flagged pixels again with --aa-count samples: three launches, one download
+    std::vector<uint8_t> rows16;  // --png-depth 16: the frame as the scanlines of a 16-bit PNG, Sub-filtered on the card
+    if (o.png_depth == 16) {
+        // drawn on the device with an RGBA32F target next to the RGBA8 one (which the adaptive classification reads), converted there with
+        // n = 1 (ptl_average_f32_to_rgb48), downloaded at 6 bytes per pixel
+        void *dev8 = nullptr, *dev32 = nullptr, *dev_rows = nullptr, *list = nullptr, *count = nullptr;
+        rows16.resize(ptl_rgb48_frame_bytes(o.width, o.height));
+        if (ptl_device_alloc(devices[0], img.size(), &dev8) != PTL_OK) return fail("device frame");
+        std::unique_ptr<void, HandleFree> own8(dev8);
+        if (ptl_device_alloc(devices[0], img.size() * 4, &dev32) != PTL_OK) return fail("device frame");
+        std::unique_ptr<void, HandleFree> own32(dev32);
+        if (ptl_device_alloc(devices[0], rows16.size(), &dev_rows) != PTL_OK) return fail("device frame");
+        std::unique_ptr<void, HandleFree> own_rows(dev_rows);
+        if (o.adaptive) {
+            ptl_renderer_set_option(r, "adaptive_aa_threshold", o.adaptive_t);
+            if (ptl_renderer_draw_adaptive(r, &frame, dev8, dev32, nullptr, &ms) != PTL_OK) return fail("render");
+            if (ptl_renderer_adaptive_result(r, &list, &count) != PTL_OK || ptl_device_download(&refined, count, sizeof refined, nullptr) != PTL_OK) return fail("refined count");
+            ptl_renderer_adaptive_times(r, pass_ms);
+        } else if (ptl_renderer_draw(r, &frame, dev8, dev32, nullptr, nullptr, &ms) != PTL_OK)
+            return fail("render");
+        const void* one[1] = {dev32};
+        if (ptl_average_f32_to_rgb48(devices[0], one, 1, dev_rows, o.width, o.height, PTL_PNG_FILTER_SUB, nullptr, nullptr) != PTL_OK) return fail("average_f32_to_rgb48");
+        if (ptl_device_download(rows16.data(), dev_rows, rows16.size(), nullptr) != PTL_OK) return fail("download");
+    } else if (o.adaptive) {  // one sample per pixel, classification, the flagged pixels again with --aa-count samples: three launches, one download
         void *dev = nullptr, *list = nullptr, *count = nullptr;
         ptl_renderer_set_option(r, "adaptive_aa_threshold", o.adaptive_t);
         if (ptl_device_alloc(devices[0], img.size(), &dev) != PTL_OK) return fail("device frame");
@@ -246,7 +272,11 @@ int render_frame(const Options& o) {
     } else if (ptl_renderer_draw_to_host(r, &frame, img.data(), nullptr, nullptr, &ms) != PTL_OK)
         return fail("render");
     double t_draw = seconds_since(t0);
-    if (int rc = write_png(o.output, img.data(), o.width, o.height)) return rc;
+    if (o.png_depth == 16) {
+        if (!dir_of(o.output).empty()) make_dirs(dir_of(o.output));
+        if (ptl_png_write_rgb48(o.output.c_str(), rows16.data(), o.width, o.height, PTL_PNG_FILTER_SUB, 6) != PTL_OK) return fail("png");
+    } else if (int rc = write_png(o.output, img.data(), o.width, o.height))
+        return rc;
     double total = seconds_since(t0);
     std::printf("Rendered `%s` to `%s` (%dx%d, aa %d, depth %d): kernel %.3f ms, %.1f Mray/s; total %.2f s\n", o.scene.c_str(), o.output.c_str(),
                 o.width, o.height, o.aa, o.depth, ms, (double)o.width * o.height * o.aa / (ms * 1e3), total);
@@ -450,6 +480,12 @@ int main(int argc, char** argv) {
             o.chroma = std::atoi(sampling.c_str());
             o.have_chroma = true;
         }
+        else if (a == "--png-depth") {
+            std::string depth = next();
+            if (depth != "8" && depth != "16") return refuse("--png-depth 8|16");
+            o.png_depth = std::atoi(depth.c_str());
+            o.have_png_depth = true;
+        }
         else if (a == "--gpus") o.gpus = std::atoi(next());
         else if (a == "--devices") o.devices = next();
         else if (a == "--transport") o.transport = next();
@@ -505,6 +541,10 @@ int main(int argc, char** argv) {
     if (o.deep_colour && !o.y4m) return refuse("--deep-colour needs --frames y4m: PNG frames hold 8 bits per channel, only the 10-bit stream can carry what the float sub-frames add");
     if (o.have_chroma && cmd != "render") return refuse("--chroma is an option of render: it chooses the chroma sampling of a clip's Y4M stream");
     if (o.have_chroma && !o.y4m) return refuse("--chroma needs --frames y4m: it chooses the chroma sampling of the stream (4:2:0, 4:2:2 or 4:4:4); PNG frames have none");
+    if (o.have_png_depth && cmd != "render" && cmd != "render-frame") return refuse("--png-depth is an option of render and render-frame: it chooses the bit depth of the PNG frames of a clip, or of the one frame");
+    if (o.png_depth == 16 && o.y4m) return refuse("--png-depth 16 cannot be combined with --frames y4m: a stream holds no PNG frames (its deep-colour form is --deep-colour)");
+    if (o.png_depth == 16 && cmd == "render-frame" && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.multi_process || o.shards > 1 || o.transport == "rccl"))
+        return refuse("render-frame --png-depth 16 draws the frame on one GPU: frame groups gather RGBA8, so it cannot be combined with --gpus N, N > 1, several --devices, --multi-process, --transport rccl or --shard");
     if (o.adaptive && cmd != "render-frame") return refuse("--adaptive-aa is an option of render-frame: a clip's sub-frames go through the slices entry, whose adaptive form is `render --clip-adaptive-aa [T]`");
     if (o.clip_adaptive && cmd != "render" && cmd != "precompile") return refuse("--clip-adaptive-aa is an option of render (and of precompile, which builds render's kernels); a single frame takes render-frame --adaptive-aa");
     if (o.adaptive && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.shards > 1)) return refuse("--adaptive-aa draws whole frames on one GPU: it cannot be combined with --gpus N, N > 1, several --devices or --shard");

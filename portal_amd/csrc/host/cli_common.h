@@ -22,6 +22,8 @@ struct Options {
     bool deep_colour = false;  // render --frames y4m --deep-colour: the stream's frames are made from the float sub-frames (ptl_average_f32_to_yuv420p10)
     int chroma = PTL_CHROMA_420;  // render --frames y4m --chroma 420|422|444: the chroma sampling of the stream's frames (ptl_average_to_yuv10)
     bool have_chroma = false;     // --chroma was given
+    int png_depth = 8;            // render / render-frame --png-depth 8|16: 16 makes the PNG frames, or the frame, from the float output (ptl_average_f32_to_rgb48)
+    bool have_png_depth = false;  // --png-depth was given
     int batch = -1;       // render --batch-subframes 0|1: one launch for a frame's blur sub-frames (default: on where 2 <= blur <= 16)
     std::vector<std::pair<std::string, double>> sets;  // --set name=value
     bool timing = false;  // --timing: wait for every kernel and report GPU milliseconds (serialises host and GPU)

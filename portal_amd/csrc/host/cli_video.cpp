@@ -1,6 +1,6 @@
 // cli_video.cpp -- `portal-amd render <scenes> [clips]`, the offline counterpart of the reference's `portal render` (src/main.rs:2757-2874 +
 // render_animation src/main.rs:1758-1873).  What is here: the host side of the clip pipeline (EncoderPool, PinnedFrames, FramePipeline), the
-// forms a clip's frames leave in (FrameOutput: PNG files for ffmpeg, or one Y4M stream made from the RGBA8 or from the float sub-frames), what lives as long as a scene's clips (SceneRun)
+// forms a clip's frames leave in (FrameOutput: PNG files for ffmpeg, 8-bit or 16-bit from the float sub-frames, or one Y4M stream made from the RGBA8 or from the float sub-frames), what lives as long as a scene's clips (SceneRun)
 // and as long as one clip (ClipRun), the clip loop (render_clip), the workers that compile the next clips' kernels (Prefetcher) and `render`.
 // Argument parsing and every other command are in cli.cpp; what both share is in cli_common.h.
 //
@@ -312,7 +312,7 @@ struct SceneRun {
     RendererPtr r;
     std::unique_ptr<void, HandleFree> subframe_block;  // ONE allocation, sub-frame j at j * bytes: what the one-launch form writes (slice z behind slice z - 1)
     std::vector<void*> subframes;
-    std::unique_ptr<void, HandleFree> float_block;  // --deep-colour only: the same sub-frames as RGBA32F (16 bytes per pixel), one allocation, laid out the same way
+    std::unique_ptr<void, HandleFree> float_block;  // --deep-colour and --png-depth 16 only: the same sub-frames as RGBA32F (16 bytes per pixel), one allocation, laid out the same way
     std::vector<void*> float_subframes;             // (empty without the option)
     FramePipeline pipe;
 };
@@ -376,9 +376,31 @@ public:
         return 0;
     }
 
-private:
+protected:
     std::string frame_name(int i) const { return anim_dir_ + "/frame_" + std::to_string(i) + ".png"; }
     const std::string anim_dir_ = o_.out_dir + "/anim";
+};
+
+// The same files at 16 bits per channel (--png-depth 16), made from the float sub-frames: the averaged frame of --deep-colour as RGB.  What leaves
+// the card are the file's scanlines, Sub-filtered and in PNG's byte order (ptl_average_f32_to_rgb48): an encoder thread only deflates them.  The
+// RGBA8 sub-frames are still drawn: the stills come from them, and the classification of --clip-adaptive-aa reads them.
+class Png16Output : public PngOutput {
+public:
+    using PngOutput::PngOutput;
+    size_t result_bytes() const override { return ptl_rgb48_frame_bytes(run_.width, run_.height); }
+    bool wants_float() const override { return true; }
+    bool draws_result() const override { return false; }  // (one sub-frame is converted with n = 1)
+    int make_result(void* result, float* ms) override {
+        return ptl_average_f32_to_rgb48(o_.device, run_.float_subframes.data(), o_.blur, result, run_.width, run_.height, PTL_PNG_FILTER_SUB, nullptr, ms) == PTL_OK ? 0 : fail("average_f32_to_rgb48");
+    }
+    void submit(int i, uint8_t* pixels, void* arrived, EncoderPool& pool, PinnedFrames& pinned) override {
+        pool.submit([pixels, name = frame_name(i), width = run_.width, height = run_.height, arrived, &pinned] {
+            if (ptl_event_synchronize(arrived) != PTL_OK || ptl_png_write_rgb48(name.c_str(), pixels, width, height, PTL_PNG_FILTER_SUB, kFrameDeflateLevel) != PTL_OK)
+                std::fprintf(stderr, "\n%s\n", ptl_last_error());
+            ptl_event_destroy(arrived);
+            pinned.give(pixels);
+        });
+    }
 };
 
 // One Y4M stream, written in frame order by a thread of its own.  (A stream is not resumed: it holds every frame, from frame 0.)
@@ -459,9 +481,10 @@ public:
     }
 };
 
-std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, size_t max_pending) {  // the ONE place that knows there are three
+std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, size_t max_pending) {  // the ONE place that knows there are four
     if (run.o.y4m && run.o.deep_colour) return std::make_unique<DeepY4mOutput>(run, clip, max_pending);
     if (run.o.y4m) return std::make_unique<Y4mOutput>(run, clip, max_pending);
+    if (run.o.png_depth == 16) return std::make_unique<Png16Output>(run, clip);
     return std::make_unique<PngOutput>(run, clip);
 }
 
@@ -737,13 +760,14 @@ int render_scene(const Options& o, const std::string& path) {
     ptl_renderer_set_option(r, "aa_count", o.aa);
     ptl_renderer_set_option(r, "render_depth", o.depth);
     ptl_renderer_set_option(r, "draw_side_by_side", o.stereo ? 1 : 0);
-    run.result_bytes = make_output(run, Clip{}, 1)->result_bytes();  // (an output that is never opened)
+    const std::unique_ptr<FrameOutput> form = make_output(run, Clip{}, 1);  // (an output that is never opened)
+    run.result_bytes = form->result_bytes();
     void* block = nullptr;
     run.subframes.assign((size_t)std::max(1, o.blur), nullptr);
     if (ptl_device_alloc(o.device, run.frame_bytes * run.subframes.size(), &block) != PTL_OK) return fail("alloc");
     run.subframe_block.reset(block);
     for (size_t j = 0; j < run.subframes.size(); ++j) run.subframes[j] = static_cast<char*>(block) + j * run.frame_bytes;
-    if (o.deep_colour) {
+    if (form->wants_float()) {
         const size_t float_bytes = run.frame_bytes * 4;  // RGBA32F
         void* floats = nullptr;
         if (ptl_device_alloc(o.device, float_bytes * run.subframes.size(), &floats) != PTL_OK) return fail("alloc");

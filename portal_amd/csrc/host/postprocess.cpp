@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../../include/portal_amd.h"
+#include "../kernels/rgb48_shape.h"
 #include "../kernels/yuv_shape.h"
 #include "hip_api.h"
 #include "internal.h"
@@ -98,7 +99,7 @@ int timed(const hip::Runtime* rt, LoadedKernel* k, void* stream, float* elapsed_
     return err;
 }
 
-// What ptl_average_images and the ptl_average_*_to_yuv* family share: a kernel over N sub-frames with two entries (up to 64 pointers in the
+// What ptl_average_images, the ptl_average_*_to_yuv* family and ptl_average_f32_to_rgb48 share: a kernel over N sub-frames with two entries (up to 64 pointers in the
 // kernel arguments, beyond in a device table), launched as `lanes` lanes in workgroups of 256 (grid-stride beyond the cap) on `stream`.
 // The kernel's arguments are (frames, n, tail...).
 struct SubframeKernel {
@@ -239,6 +240,25 @@ extern "C" int ptl_average_to_yuv420p10(int device, const void* const* frames_rg
 extern "C" int ptl_average_f32_to_yuv420p10(int device, const void* const* frames_rgba32f, int n_frames, void* out_yuv, int width, int height, void* stream,
                                             float* elapsed_ms) {
     return average_to_yuv(true, PTL_CHROMA_420, device, frames_rgba32f, n_frames, out_yuv, width, height, stream, elapsed_ms);
+}
+
+// The 16-bit PNG hand-off: the averaged frame of the float sub-frames as RGB scanlines, unfiltered or with PNG's Sub filter applied
+// (portal_amd/csrc/kernels/rgb48_f32.hip; the contract is in include/portal_amd.h).  The fast path and the lane count are rgb48_shape.h's to say.
+extern "C" size_t ptl_rgb48_frame_bytes(int width, int height) { return width <= 0 || height <= 0 ? 0 : 6 * (size_t)width * (size_t)height; }
+
+extern "C" int ptl_average_f32_to_rgb48(int device, const void* const* frames_rgba32f, int n_frames, void* out_rows, int width, int height, int filter, void* stream,
+                                        float* elapsed_ms) {
+    if (!ptl_rgb48_is_filter(filter)) {
+        set_last_error("average_f32_to_rgb48: filter " + std::to_string(filter) + " is neither PTL_PNG_FILTER_NONE (0) nor PTL_PNG_FILTER_SUB (1)");
+        return PTL_ERR_INVALID;
+    }
+    if (int rc = check_subframes(frames_rgba32f, n_frames, out_rows, width, height)) return rc;
+    if ((long)width * height > ptl_rgb48_max_pixels()) return PTL_ERR_INVALID;  // the kernel addresses a sub-frame with 32-bit byte offsets
+    static const SubframeKernel kKernels[2] = {
+        {"rgb48_f32.hsaco", "ptl_average_f32_to_rgb48_none_kernel", "ptl_average_f32_to_rgb48_none_table_kernel", "average_f32_to_rgb48"},
+        {"rgb48_f32.hsaco", "ptl_average_f32_to_rgb48_sub_kernel", "ptl_average_f32_to_rgb48_sub_table_kernel", "average_f32_to_rgb48"}};
+    const long lanes = ptl_rgb48_lanes((unsigned)width, (unsigned)height);
+    return launch_over_subframes(device, kKernels[filter == PTL_PNG_FILTER_SUB], frames_rgba32f, n_frames, {&out_rows, &width, &height}, lanes, stream, elapsed_ms);
 }
 
 // ptl_aa_edges: the classification pass of the adaptive anti-aliasing (portal_amd/csrc/kernels/aa_edges.hip; the contract is in
