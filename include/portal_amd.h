@@ -93,7 +93,8 @@ int ptl_kernel_code_object(ptl_kernel* k, const void** data, size_t* size);
 int ptl_code_object_note(const void* code, size_t size, const char* key, const char* kernel_prefix);
 /* Per-lane resources of the loaded render kernel (hipFuncGetAttribute): vector registers, scratch
  * (private segment) bytes -- non-zero means register spills that travel through the memory hierarchy --
- * and static LDS bytes per workgroup.  -1 where the runtime cannot tell. */
+ * and static LDS bytes per workgroup.  -1 where the runtime cannot tell.  A compile-only handle (device -1) answers from the
+ * code object's metadata: the largest values over its render entries. */
 int ptl_kernel_resources(ptl_kernel* k, int* registers, int* scratch_bytes, int* lds_bytes);
 
 /* value points at 16 floats (column-major) / 1 float / 1 int32 / 2 floats / 3 floats. */
@@ -259,6 +260,7 @@ int ptl_scene_texture(ptl_scene* s, int index, char* name, size_t name_cap, char
 #define PTL_FLAG_MATERIAL_TABLE_SCALAR (1u << 27)
 #define PTL_FLAG_REFINE (1u << 28)
 #define PTL_FLAG_REFINE_SLICES (1u << 29)
+#define PTL_FLAG_PASSES (1u << 30)
 
 /* Scene::generate_shader_code: returns a malloc'ed NUL-terminated HIP C++ source (free with
  * ptl_free).  flags: bit0 = bake Bool/Int scene uniforms as literals, bit1 = count segments,
@@ -350,6 +352,9 @@ int ptl_scene_texture(ptl_scene* s, int index, char* name, size_t name_cap, char
  * un-specialised one above all: 0.70 against 0.89 ms) keep the deferral anyway,
  * bit28 = REFINE: the module gets a second render entry, `ptl_render_refine_kernel`, which shades a device-side list of pixels instead of a
  * rectangle (ptl_kernel_render_refine, ptl_renderer_draw_adaptive below).  A source generated without it is byte for byte what it was.  Not with bit22,
+ * bit30 = PASSES: the tracer keeps a 16-byte record per pixel -- nearest final depth, bounce-loop trips, how its paths ended -- and the render
+ * entries store it through one more pointer (ptl_pass_record, ptl_kernel_render_passes below).  Same colours.  A source generated without it is byte
+ * for byte what it was.  Not with bit4, bit25, bit28 or bit29 (PTL_ERR_SCENE and a message),
  * bit15 = NO unrolling of baked loops: by default (with bit0) a counting loop of a scene snippet whose bound is a baked Int uniform
  * (<= 16 iterations) is unrolled -- the same operations in the same order, identical frames; every iteration then has its own
  * constants (scenes/portal_in_portal.ron's `size` drives an inner loop and a material index).
@@ -603,6 +608,81 @@ size_t ptl_yuv10_frame_bytes(int width, int height, int chroma); /* 0 for an unk
 int ptl_average_f32_to_rgb48(int device, const void* const* frames_rgba32f, int n_frames, void* out_rows, int width, int height, int filter, void* stream,
                              float* elapsed_ms);
 size_t ptl_rgb48_frame_bytes(int width, int height); /* 6 W H; 0 for a size that is not positive */
+
+/* ---- trace passes: what the tracer knows about a pixel beside its colour (opt-in, flag bit 30) ------------------------------------------
+ * A source generated with PTL_FLAG_PASSES keeps one record per pixel while it traces and stores it through one more pointer of the render
+ * entry, `out_passes`, addressed exactly like out_rgba32f (16 bytes per pixel, one 16-byte store per lane; rb_phase / rb_stride / in_place are
+ * honoured; in the slices entry slice z lands behind slice z - 1, at out_passes + z * slice_pixels records).  A "path" is one call of the
+ * tracer's bounce loop: one per anti-aliasing sample of the window `_aa_start` .. `_aa_start + _aa_count - 1`.  Every path of a pixel ends in
+ * exactly one of four ways, so final + escaped + exhausted + outside = `_aa_count`:
+ *   final      a final material ended it (the result has a depth),
+ *   escaped    it left the scene (the sky colour; black inside a subspace),
+ *   exhausted  it was still alive when the bounce loop reached `_ray_tracing_depth` trips -- the pixel is drawn black for this sample, and
+ *              nothing else says so; a path that ends ON trip `_ray_tracing_depth` is final or escaped, never exhausted,
+ *   outside    the sample never traced: it lies in the black bars of a 360 / 180 degree frame.
+ * The four counts saturate at 65 535.  depth_near is a minimum (taken with `<`, so a NaN depth never enters it) and the rest are integers:
+ * every field is exact, the host build of the same source (ptl_host_render_passes) gives the same bytes, and with PTL_FLAG_COUNT_SEGMENTS also
+ * on, the launch's segment sum equals the sum of `trips`.  Colours are those of the build without the flag.  Generation refuses bit 30
+ * together with PTL_FLAG_ANAGLYPH (two paths per sample), PTL_FLAG_REFINE / _REFINE_SLICES (the list-driven entries store no records) and
+ * PTL_FLAG_CHECK_AFFINE.  Without the flag, sources and code objects are byte for byte what they were. */
+typedef struct ptl_pass_record {
+    float depth_near;           /* min over the pixel's FINAL paths of path length / max(camera scale, 1e-6); +inf if it has none */
+    uint32_t trips;             /* bounce-loop trips over all paths of the pixel (what PTL_FLAG_COUNT_SEGMENTS sums per launch) */
+    uint32_t final_escaped;     /* low 16 bits: final paths; high 16: escaped paths */
+    uint32_t exhausted_outside; /* low 16 bits: exhausted paths; high 16: outside samples */
+} ptl_pass_record;
+size_t ptl_pass_record_bytes(int width, int height); /* 16 W H; 0 for a size that is not positive */
+/* ptl_kernel_render and ptl_kernel_render_slices with the records: out_passes is a DEVICE pointer, 16-byte aligned, of passes_bytes bytes --
+ * at least 16 bytes per pixel the launch stores: shard_rows * width records (frame->in_place: height * width), for slices
+ * (n - 1) * slice_pixels more.  Refused before any GPU call (PTL_ERR_INVALID, ptl_last_error): a kernel generated without bit 30, a null or
+ * misaligned pointer, a buffer that is too small.  The plain calls still work on such a kernel and store no records. */
+int ptl_kernel_render_passes(ptl_kernel* k, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* out_passes, size_t passes_bytes, void* segments,
+                             void* stream, float* elapsed_ms);
+int ptl_kernel_render_slices_passes(ptl_kernel* k, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, void* out_passes, size_t passes_bytes,
+                                    unsigned long long slice_pixels, void* stream, float* elapsed_ms);
+/* Layer 2: ptl_renderer_draw and ptl_renderer_draw_slices with the records, for a renderer created with PTL_FLAG_PASSES or switched with the
+ * option "passes" = 1 (ptl_renderer_set_option: the flag joins the next build, which happens at once; 0 takes it out again; a combination the
+ * generator refuses leaves the renderer as it was).  A pass draw goes on the caller's stream after joining the lanes ("concurrent_draws"), as
+ * a timed draw does.  Frame groups draw no records: ptl_frame_group_create refuses the flag and ptl_frame_group_set_option the option. */
+int ptl_renderer_draw_passes(ptl_renderer* r, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* out_passes, size_t passes_bytes, void* segments,
+                             void* stream, float* elapsed_ms);
+int ptl_renderer_draw_slices_passes(ptl_renderer* r, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, void* out_passes, size_t passes_bytes,
+                                    unsigned long long slice_pixels, void* stream, float* elapsed_ms);
+/* ptl_pass_stats: one sweep over n records (DEVICE pointer, 16-byte aligned) added into a ptl_pass_stats_block in DEVICE memory that the
+ * caller zeroed once (hipMemset) -- a clip keeps one block on the card, adds the launch behind every draw and downloads it at its end.
+ * per_launch (DEVICE pointer to uint64 counters the caller zeroed, or NULL): per_launch[slot] receives the exhausted paths of THIS sweep,
+ * so the worst frame of a clip can be named.  Integers only; the result does not depend on the order of the adds.  Launched on `stream`;
+ * with elapsed_ms the call waits.  HBM-bound: 16 bytes per record in.  n <= 2^31. */
+#define PTL_PASS_HIST_BINS 256
+typedef struct ptl_pass_stats_block {
+    uint64_t pixels, paths, trips;                   /* records seen, their paths (the four counts added up), their trips */
+    uint64_t final_paths, escaped, exhausted, outside;
+    uint64_t exhausted_pixels;                       /* records with at least one exhausted path */
+    uint32_t max_trips;                              /* the largest `trips` of a record */
+    /* the range of depth_near over the records where it is finite, as order-preserving keys (depths need not be positive): zero = none yet.
+     * key(bits) = bits has the sign bit ? ~bits : bits | 0x80000000; depth_max_key = the largest key, depth_min_key_inv = the largest ~key.
+     * ptl_pass_stats_depth_range decodes both. */
+    uint32_t depth_max_key, depth_min_key_inv;
+    uint32_t reserved;
+    uint64_t trips_histogram[PTL_PASS_HIST_BINS];    /* records by `trips`; the last bin collects trips >= 255 */
+} ptl_pass_stats_block;
+int ptl_pass_stats(int device, const void* records, long n, void* stats_block, void* per_launch, int slot, void* stream, float* elapsed_ms);
+/* HOST copy of a block -> the smallest and largest finite depth_near; returns 1, or 0 (and leaves lo / hi alone) when no record had one */
+int ptl_pass_stats_depth_range(const ptl_pass_stats_block* block, float* lo, float* hi);
+/* ptl_passes_to_gray16: n records -> the scanlines of a 16-bit greyscale PNG (colour type 0, bit depth 16, filter None: 2 n bytes, big-endian
+ * samples, rows packed without filter-type bytes), `which`:
+ *   PTL_PASS_DEPTH  a record without a final path gives 0; otherwise q((depth_near - lo) / max(1e-6f, hi - lo)): difference, divisor and ONE
+ *                   IEEE division in binary32, then q of ptl_average_f32_to_yuv420p10 (0 if !(v > 0), 65535 if v >= 1, else
+ *                   (u32) floor(v * 65535.0f + 0.5f), product and sum each rounded to binary32) -- round(65535 clamp(., 0, 1)).
+ *                   The renderer's defaults for lo / hi are its "depth_map_min" / "depth_map_max" options.
+ *   PTL_PASS_TRIPS  min(trips, 65535): lossless up to there; lo and hi are ignored.
+ * records, out_rows: DEVICE pointers, 16-byte aligned.  Any other `which`: PTL_ERR_INVALID before any GPU call.  HBM-bound: 16 bytes in,
+ * 2 out.  ptl_png_write_gray16 adds the filter-type bytes and deflates (`level` 0 .. 9), like ptl_png_write_rgb48.
+ * (`portal-amd render-frame --passes depth,trips`.) */
+#define PTL_PASS_DEPTH 0
+#define PTL_PASS_TRIPS 1
+int ptl_passes_to_gray16(int device, const void* records, long n, void* out_rows, int which, float lo, float hi, void* stream, float* elapsed_ms);
+int ptl_png_write_gray16(const char* path, const uint8_t* rows, int width, int height, int level);
 /* ---- adaptive anti-aliasing: supersample only the pixels that sit on an edge (opt-in, approximate by design) ------------------------
  * Every anti-aliasing sample costs a full trace, and most pixels of a frame are flat walls and smooth gradients whose centre sample is
  * already the final 8-bit colour.  An adaptive draw traces ONE sample per pixel, classifies the frame it got, and traces the full
@@ -705,6 +785,8 @@ int ptl_y4m_header_chroma(int width, int height, int fps, int chroma, char* buf,
 int ptl_device_alloc(int device, size_t bytes, void** out);
 int ptl_device_free(void* p);
 int ptl_device_download(void* host_dst, const void* device_src, size_t bytes, void* stream);
+/* hipMemsetAsync on `stream`: every byte of the range becomes `value` (a ptl_pass_stats_block and its per-launch counters start as zeros). */
+int ptl_device_memset(void* device_dst, int value, size_t bytes, void* stream);
 /* Streams and events, 1:1 over HIP, for callers that overlap the download of frame i (on its own non-blocking stream, into
  * page-locked memory) with the tracing of frame i+1: record an event behind the producer, make the copy stream wait for it,
  * ptl_device_download_async, record a second event behind the copy and ptl_event_synchronize on it where the pixels are

@@ -66,6 +66,7 @@ FLAG_CHECK_AFFINE = 1 << 25  # diagnostics: general products, and `segments` cou
 FLAG_NO_AFFINE_RAYS = 8388608  # A/B: matrix-times-ray products never assume o.w = 1 / d.w = 0 (default in specialised builds of affine scenes: they do; identical frames)
 FLAG_REFINE = 1 << 28  # adaptive anti-aliasing: a second render entry that shades a device-side list of pixels (SceneRenderer.draw_adaptive)
 FLAG_REFINE_SLICES = 1 << 29  # FLAG_SLICES (implied) plus the refine entry over the slices of a launch (SceneRenderer.draw_slices_adaptive); not with FLAG_REFINE
+FLAG_PASSES = 1 << 30  # trace passes: a 16-byte record per pixel beside the colour (PASS_RECORD; SceneRenderer.draw_passes); not with FLAG_ANAGLYPH / _REFINE / _REFINE_SLICES / _CHECK_AFFINE
 FLAG_SLICES = 4194304  # the render entry reads its uniform block from a buffer of blocks (one per blockIdx.z): stage_slice / draw_slices, one launch for several draws
 FLAG_NO_ZERO_MASKS = 524288  # A/B: run-time matrices keep their full products although their zero pattern is known (KernelOptions::mask_zero_elements)
 FLAG_ASYNC_REJIT = 131072  # a specialised renderer never stalls on a rebuild: it draws with the un-specialised kernel until a worker thread has the new one
@@ -191,6 +192,15 @@ def _load() -> C.CDLL:
         "ptl_average_f32_to_rgb48": (ci, [ci, P(vp), ci, vp, ci, ci, ci, vp, P(C.c_float)]),
         "ptl_rgb48_frame_bytes": (cs, [ci, ci]),
         "ptl_png_write_rgb48": (ci, [cp, vp, ci, ci, ci, ci]),
+        "ptl_pass_record_bytes": (cs, [ci, ci]),
+        "ptl_kernel_render_passes": (ci, [vp, P(Frame), vp, vp, vp, cs, vp, vp, P(C.c_float)]),
+        "ptl_kernel_render_slices_passes": (ci, [vp, P(Frame), ci, vp, vp, vp, cs, C.c_ulonglong, vp, P(C.c_float)]),
+        "ptl_renderer_draw_passes": (ci, [vp, P(Frame), vp, vp, vp, cs, vp, vp, P(C.c_float)]),
+        "ptl_renderer_draw_slices_passes": (ci, [vp, P(Frame), ci, vp, vp, vp, cs, C.c_ulonglong, vp, P(C.c_float)]),
+        "ptl_pass_stats": (ci, [ci, vp, C.c_long, vp, vp, ci, vp, P(C.c_float)]),
+        "ptl_pass_stats_depth_range": (ci, [vp, P(C.c_float), P(C.c_float)]),
+        "ptl_passes_to_gray16": (ci, [ci, vp, C.c_long, vp, ci, C.c_float, C.c_float, vp, P(C.c_float)]),
+        "ptl_png_write_gray16": (ci, [cp, vp, ci, ci, ci]),
         "ptl_aa_edges": (ci, [ci, vp, ci, ci, ci, vp, vp, vp, P(C.c_float)]),
         "ptl_kernel_render_refine": (ci, [vp, P(Frame), vp, vp, vp, vp, vp, vp, P(C.c_float)]),
         "ptl_renderer_draw_adaptive": (ci, [vp, P(Frame), vp, vp, vp, P(C.c_float)]),
@@ -206,6 +216,7 @@ def _load() -> C.CDLL:
         "ptl_device_alloc": (ci, [ci, cs, P(vp)]),
         "ptl_device_free": (ci, [vp]),
         "ptl_device_download": (ci, [vp, vp, cs, vp]),
+        "ptl_device_memset": (ci, [vp, ci, cs, vp]),
         "ptl_device_copy2d_async": (ci, [vp, cs, vp, cs, cs, cs, vp]),
         "ptl_ipc_export": (ci, [vp, cp]),
         "ptl_ipc_open": (ci, [ci, cp, P(vp)]),
@@ -692,6 +703,49 @@ class SceneRenderer:
         _check(rc, "draw_texture")
         return {"rgba8": a8, "rgba32f": a32, "segments": seg.value if segments else None, "ms": ms.value}
 
+    def draw_passes_device(self, frame: Frame, out_passes: int, passes_bytes: int, out_rgba8: int = 0, out_rgba32f: int = 0, segments: int = 0, stream: int = 0,
+                           timed: bool = False):
+        """ptl_renderer_draw_passes into DEVICE buffers given as integer addresses (FLAG_PASSES renderers, or option ``passes`` = 1): the draw of
+        ``draw_device`` plus a PASS_RECORD per pixel at ``out_passes`` (``passes_bytes`` bytes, 16 per pixel the launch stores, addressed like
+        ``out_rgba32f``).  Returns the kernel time in ms when ``timed`` (waits for completion), else None."""
+        ms = C.c_float()
+        _check(lib().ptl_renderer_draw_passes(self._h, C.byref(frame), C.c_void_p(out_rgba8 or None), C.c_void_p(out_rgba32f or None), C.c_void_p(out_passes or None),
+                                              passes_bytes, C.c_void_p(segments or None), C.c_void_p(stream or None), C.byref(ms) if timed else None),
+               "ptl_renderer_draw_passes")
+        return ms.value if timed else None
+
+    def draw_slices_passes(self, frame: Frame, n: int, out_passes: int, passes_bytes: int, out_rgba8: int = 0, out_rgba32f: int = 0, slice_pixels: int = 0,
+                           stream: int = 0, timed: bool = False):
+        """ptl_renderer_draw_slices_passes: ``draw_slices`` plus the records, slice z at ``out_passes + 16 * z * slice_pixels`` bytes."""
+        ms = C.c_float()
+        _check(lib().ptl_renderer_draw_slices_passes(self._h, C.byref(frame), n, C.c_void_p(out_rgba8 or None), C.c_void_p(out_rgba32f or None),
+                                                     C.c_void_p(out_passes or None), passes_bytes, slice_pixels, C.c_void_p(stream or None),
+                                                     C.byref(ms) if timed else None), "ptl_renderer_draw_slices_passes")
+        return ms.value if timed else None
+
+    def draw_passes(self, width: int, height: int, rgba8: bool = True, rgba32f: bool = False, segments: bool = False, rb_phase: int = 0, rb_stride: int = 1):
+        """A pass draw read back to numpy.  Returns dict(passes=HxW structured array of PASS_RECORD, rgba8=HxWx4 u8 or None, rgba32f=HxWx4 f32
+        or None, segments=int or None, ms=float); H = rows of the shard."""
+        frame = Frame(width, height, rb_phase, rb_stride)
+        rows = shard_rows(frame)
+        if rows < 0:
+            raise PortalError("bad frame")
+        n = rows * width
+        bufs = [device_alloc(max(n, 1) * 16, self.device), device_alloc(n * 4, self.device) if rgba8 and n else 0, device_alloc(n * 16, self.device) if rgba32f and n else 0,
+                device_alloc(8, self.device) if segments else 0]
+        try:
+            if segments:
+                device_memset(bufs[3], 0, 8)
+            ms = self.draw_passes_device(frame, bufs[0], max(n, 1) * 16, bufs[1], bufs[2], bufs[3], timed=True)
+            return {"passes": device_download(bufs[0], n * 16).view(PASS_RECORD).reshape(rows, width),
+                    "rgba8": device_download(bufs[1], n * 4).reshape(rows, width, 4) if bufs[1] else None,
+                    "rgba32f": device_download(bufs[2], n * 16).view(np.float32).reshape(rows, width, 4) if bufs[2] else None,
+                    "segments": int(device_download(bufs[3], 8).view(np.uint64)[0]) if segments else None, "ms": ms}
+        finally:
+            for b in bufs:
+                if b:
+                    device_free(b)
+
     def draw_adaptive_device(self, frame: Frame, out_rgba8: int, out_rgba32f: int = 0, stream: int = 0, timed: bool = False):
         """ptl_renderer_draw_adaptive into DEVICE buffers given as integer addresses (FLAG_REFINE renderers; the threshold is the option
         ``adaptive_aa_threshold``).  Returns the summed GPU time of the three launches in ms when ``timed`` (waits), else None."""
@@ -972,6 +1026,57 @@ def png_write_rgb48(path: str, rows, width: int, height: int, filter: int = PNG_
     _check(lib().ptl_png_write_rgb48(path.encode(), a.ctypes.data, width, height, filter, level), "png_write_rgb48")
 
 
+# ---- trace passes (include/portal_amd.h: ptl_pass_record, ptl_pass_stats_block) ------------------------------------------------------
+PASS_RECORD = np.dtype([("depth_near", "<f4"), ("trips", "<u4"), ("final_escaped", "<u4"), ("exhausted_outside", "<u4")])
+PASS_HIST_BINS = 256
+PASS_STATS_BLOCK = np.dtype([("pixels", "<u8"), ("paths", "<u8"), ("trips", "<u8"), ("final_paths", "<u8"), ("escaped", "<u8"), ("exhausted", "<u8"), ("outside", "<u8"),
+                             ("exhausted_pixels", "<u8"), ("max_trips", "<u4"), ("depth_max_key", "<u4"), ("depth_min_key_inv", "<u4"), ("reserved", "<u4"),
+                             ("trips_histogram", "<u8", (PASS_HIST_BINS,))])
+PASS_DEPTH, PASS_TRIPS = 0, 1
+
+
+def pass_counts(records: np.ndarray) -> dict:
+    """The four path counts of PASS_RECORD records, unpacked: dict(final, escaped, exhausted, outside) of uint32 arrays."""
+    fe, xo = records["final_escaped"], records["exhausted_outside"]
+    return {"final": fe & 0xFFFF, "escaped": fe >> 16, "exhausted": xo & 0xFFFF, "outside": xo >> 16}
+
+
+def pass_record_bytes(width: int, height: int) -> int:
+    return int(lib().ptl_pass_record_bytes(width, height))
+
+
+def pass_stats_device(records_ptr: int, n: int, block_ptr: int, per_launch_ptr: int = 0, slot: int = 0, device: int = 0, stream: int = 0, timed: bool = False):
+    """ptl_pass_stats: n records (DEVICE address) added into a PASS_STATS_BLOCK in device memory the caller zeroed; ``per_launch_ptr[slot]``
+    (uint64 counters, or 0) receives this sweep's exhausted paths.  Returns the kernel time in ms when ``timed`` (waits), else None."""
+    ms = C.c_float()
+    _check(lib().ptl_pass_stats(device, C.c_void_p(records_ptr or None), n, C.c_void_p(block_ptr or None), C.c_void_p(per_launch_ptr or None), slot,
+                                C.c_void_p(stream or None), C.byref(ms) if timed else None), "ptl_pass_stats")
+    return ms.value if timed else None
+
+
+def pass_stats_depth_range(block: np.ndarray):
+    """(lo, hi) of the finite depth_near values a downloaded PASS_STATS_BLOCK has seen, or None."""
+    b = np.ascontiguousarray(block).view(PASS_STATS_BLOCK).reshape(-1)[:1]
+    lo, hi = C.c_float(), C.c_float()
+    return (lo.value, hi.value) if lib().ptl_pass_stats_depth_range(b.ctypes.data, C.byref(lo), C.byref(hi)) == 1 else None
+
+
+def passes_to_gray16_device(records_ptr: int, n: int, out_ptr: int, which: int, lo: float = 0.0, hi: float = 1.0, device: int = 0, stream: int = 0, timed: bool = False):
+    """ptl_passes_to_gray16: n records -> 2 n bytes, the big-endian samples of a 16-bit greyscale PNG (``which``: PASS_DEPTH or PASS_TRIPS)."""
+    ms = C.c_float()
+    _check(lib().ptl_passes_to_gray16(device, C.c_void_p(records_ptr or None), n, C.c_void_p(out_ptr or None), which, lo, hi, C.c_void_p(stream or None),
+                                      C.byref(ms) if timed else None), "ptl_passes_to_gray16")
+    return ms.value if timed else None
+
+
+def png_write_gray16(path: str, rows, width: int, height: int, level: int = 6) -> None:
+    """ptl_png_write_gray16: ``rows`` = height * width big-endian 16-bit samples (bytes or a uint8 array), colour type 0, bit depth 16."""
+    a = np.ascontiguousarray(np.frombuffer(rows, np.uint8) if isinstance(rows, (bytes, bytearray)) else rows, dtype=np.uint8)
+    if a.size != 2 * width * height:
+        raise PortalError("png_write_gray16: rows must hold 2 * width * height bytes")
+    _check(lib().ptl_png_write_gray16(path.encode(), a.ctypes.data, width, height, level), "ptl_png_write_gray16")
+
+
 def y4m_header(width: int, height: int, fps: int, chroma: int = 420) -> bytes:
     """The header line of the Y4M stream those frames travel in (each frame: b"FRAME\\n" + payload)."""
     buf = C.create_string_buffer(128)
@@ -994,6 +1099,10 @@ def device_download(ptr: int, nbytes: int, stream: int = 0) -> np.ndarray:
     out = np.empty(nbytes, dtype=np.uint8)
     _check(lib().ptl_device_download(out.ctypes.data, C.c_void_p(ptr), nbytes, C.c_void_p(stream or None)), "device_download")
     return out
+
+
+def device_memset(ptr: int, value: int, nbytes: int, stream: int = 0) -> None:
+    _check(lib().ptl_device_memset(C.c_void_p(ptr), value, nbytes, C.c_void_p(stream or None)), "device_memset")
 
 
 def device_copy2d_async(dst: int, dst_pitch: int, src: int, src_pitch: int, width_bytes: int, rows: int, stream: int = 0) -> None:

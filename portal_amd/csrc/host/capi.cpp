@@ -337,7 +337,8 @@ static int set_plain_option(ptl_renderer* r, const std::string& n, double v) {
 extern "C" int ptl_renderer_set_option(ptl_renderer* r, const char* name, double v) {
     if (!r || !name) return PTL_ERR_INVALID;
     std::string n = name;
-    if (n == "specialize_static") return set_specialize_static(r, v > 0.5);
+    if (n == "specialize_static") return set_build_flag(r, PTL_FLAG_SPECIALIZE_STATIC, v > 0.5);
+    if (n == "passes") return set_build_flag(r, PTL_FLAG_PASSES, v > 0.5);  // pass records beside the colour from the next build on (ptl_renderer_draw_passes)
     return set_plain_option(r, n, v);
 }
 

@@ -22,6 +22,9 @@ int usage() {  // (and the exit status that goes with it)
                  "                  [--specialize 0] do NOT bake the scene state into the kernel   [--fast] tolerance mode   [--exact-cr] numerics contract 1   [--opt3] JIT at -O3 like the library default (render-frame: -O1)   [--timing] where the wall time went\n"
                  "                  [--adaptive-aa [T]]  one sample per pixel, --aa-count samples only where a pixel differs from a neighbour by more than T codes (default 4, -1 .. 255); one GPU\n"
                  "                  [--png-depth 8|16]   16: a 16-bit RGB file made on the GPU from the frame's float output (one quantisation, to 16 bits); one GPU\n"
+                 "                  [--passes depth,trips]  beside the frame: <output stem>.depth.png (nearest final depth, scaled between the scene's depth-map bounds) and\n"
+                 "                                       <output stem>.trips.png (bounce-loop trips per pixel), 16-bit greyscale, from the tracer's pass records; one GPU\n"
+                 "                  [--depth-report]     one line: how many paths --render-depth cut short (they are drawn black), in how many pixels; the deepest pixel; the depth range\n"
                  "       portal-amd precompile <scene.ron> [--stage NAME] [--specialize 0]      fill the code-object cache (no GPU needed; render's options choose render's kernels)\n"
                  "       portal-amd render <scene[,scene..]> [clip[,clip..]] [--width 3840] [--height 2160] [--fps 60] [--motion-blur-frames 1]\n"
                  "                  [--stereoimage] [--batch-subframes 0|1] [--no-skip-existing] [--filter-starts-with P] [--aa-count 4] [--render-depth 150]\n"
@@ -39,6 +42,7 @@ int usage() {  // (and the exit status that goes with it)
                  "                  [--png-depth 8|16]   with --frames png: 16 makes anim/frame_%%d.png 16-bit RGB files from the un-quantised float sub-frames (the averaged\n"
                  "                                       frame of --deep-colour), Sub-filtered on the GPU; works with --shard K/N and resumes.  16 more bytes per pixel and\n"
                  "                                       sub-frame on the card, 6 instead of 4 bytes per pixel leave it, and the files are 4 - 7 times larger to deflate\n"
+                 "                  [--depth-report]     one line per clip: how many paths --render-depth cut short, in how many pixels, and the frame that lost most\n"
                  "                  [--clip-adaptive-aa [T]]  adaptive anti-aliasing of every sub-frame: one sample per pixel, --aa-count samples only where a pixel differs\n"
                  "                                       from a neighbour by more than T codes (default 4, -1 .. 255); opt-in, approximate by design\n"
                  "       portal-amd emit-source <scene.ron> [--stage NAME]     print the generated HIP kernel source\n"
@@ -81,6 +85,7 @@ unsigned frame_flags(const Options& o) {
     if (o.specialize != 0) f |= PTL_FLAG_SPECIALIZE_INTS | PTL_FLAG_SPECIALIZE_ALL;
     f |= numerics_flags(o) | quick_jit_flag(o);
     if (o.adaptive) f |= PTL_FLAG_REFINE;  // the kernel's second render entry, over the list of flagged pixels
+    if (o.have_passes || o.depth_report) f |= PTL_FLAG_PASSES;  // the tracer's record per pixel, stored beside the colour
     return f;
 }
 
@@ -239,6 +244,12 @@ int render_frame(const Options& o) {
     unsigned int refined = 0;
     float pass_ms[3] = {0.0f, 0.0f, 0.0f};
     std::vector<uint8_t> rows16;  // --png-depth 16: the frame as the scanlines of a 16-bit PNG, Sub-filtered on the card
+    // --passes / --depth-report: the draw also stores the pass records, which stay on the card for the two kernels that read them
+    const bool with_records = o.have_passes || o.depth_report;
+    const size_t n_px = (size_t)o.width * o.height, record_bytes = ptl_pass_record_bytes(o.width, o.height);
+    void* records = nullptr;
+    if (with_records && ptl_device_alloc(devices[0], record_bytes, &records) != PTL_OK) return fail("device records");
+    std::unique_ptr<void, HandleFree> own_records(records);
     if (o.png_depth == 16) {
         // drawn on the device with an RGBA32F target next to the RGBA8 one (which the adaptive classification reads), converted there with
         // n = 1 (ptl_average_f32_to_rgb48), downloaded at 6 bytes per pixel
@@ -255,7 +266,8 @@ int render_frame(const Options& o) {
             if (ptl_renderer_draw_adaptive(r, &frame, dev8, dev32, nullptr, &ms) != PTL_OK) return fail("render");
             if (ptl_renderer_adaptive_result(r, &list, &count) != PTL_OK || ptl_device_download(&refined, count, sizeof refined, nullptr) != PTL_OK) return fail("refined count");
             ptl_renderer_adaptive_times(r, pass_ms);
-        } else if (ptl_renderer_draw(r, &frame, dev8, dev32, nullptr, nullptr, &ms) != PTL_OK)
+        } else if ((with_records ? ptl_renderer_draw_passes(r, &frame, dev8, dev32, records, record_bytes, nullptr, nullptr, &ms) : ptl_renderer_draw(r, &frame, dev8, dev32, nullptr, nullptr, &ms)) !=
+                   PTL_OK)
             return fail("render");
         const void* one[1] = {dev32};
         if (ptl_average_f32_to_rgb48(devices[0], one, 1, dev_rows, o.width, o.height, PTL_PNG_FILTER_SUB, nullptr, nullptr) != PTL_OK) return fail("average_f32_to_rgb48");
@@ -269,20 +281,56 @@ int render_frame(const Options& o) {
         if (ptl_renderer_adaptive_result(r, &list, &count) != PTL_OK || ptl_device_download(&refined, count, sizeof refined, nullptr) != PTL_OK) return fail("refined count");
         ptl_renderer_adaptive_times(r, pass_ms);
         ptl_device_free(dev);
+    } else if (with_records) {
+        void* dev = nullptr;
+        if (ptl_device_alloc(devices[0], img.size(), &dev) != PTL_OK) return fail("device frame");
+        std::unique_ptr<void, HandleFree> own(dev);
+        if (ptl_renderer_draw_passes(r, &frame, dev, nullptr, records, record_bytes, nullptr, nullptr, &ms) != PTL_OK) return fail("render");
+        if (ptl_device_download(img.data(), dev, img.size(), nullptr) != PTL_OK) return fail("download");
     } else if (ptl_renderer_draw_to_host(r, &frame, img.data(), nullptr, nullptr, &ms) != PTL_OK)
         return fail("render");
+    // the pass images: the records as 16-bit grey scanlines, made on the card, 2 bytes per pixel downloaded
+    const std::string stem = o.output.size() > 4 && o.output.compare(o.output.size() - 4, 4, ".png") == 0 ? o.output.substr(0, o.output.size() - 4) : o.output;
+    std::vector<uint8_t> grey[2];
+    if (o.have_passes) {
+        void* dev_grey = nullptr;
+        if (ptl_device_alloc(devices[0], 2 * n_px, &dev_grey) != PTL_OK) return fail("device pass image");
+        std::unique_ptr<void, HandleFree> own_grey(dev_grey);
+        float lo[16] = {0.0f}, hi[16] = {1.0f};  // the scene's depth-map bounds, as a draw uploads them
+        ptl_renderer_uniform_value(r, o.width, o.height, "_depth_map_min", lo, nullptr);
+        ptl_renderer_uniform_value(r, o.width, o.height, "_depth_map_max", hi, nullptr);
+        for (int which : {PTL_PASS_DEPTH, PTL_PASS_TRIPS}) {
+            if (!(which == PTL_PASS_DEPTH ? o.pass_depth : o.pass_trips)) continue;
+            grey[which].resize(2 * n_px);
+            if (ptl_passes_to_gray16(devices[0], records, (long)n_px, dev_grey, which, lo[0], hi[0], nullptr, nullptr) != PTL_OK) return fail("passes_to_gray16");
+            if (ptl_device_download(grey[which].data(), dev_grey, grey[which].size(), nullptr) != PTL_OK) return fail("download");
+        }
+    }
+    ptl_pass_stats_block stats{};
+    if (o.depth_report) {
+        void* dev_stats = nullptr;
+        if (ptl_device_alloc(devices[0], sizeof stats, &dev_stats) != PTL_OK) return fail("device statistics");
+        std::unique_ptr<void, HandleFree> own_stats(dev_stats);
+        if (ptl_device_memset(dev_stats, 0, sizeof stats, nullptr) != PTL_OK || ptl_pass_stats(devices[0], records, (long)n_px, dev_stats, nullptr, 0, nullptr, nullptr) != PTL_OK ||
+            ptl_device_download(&stats, dev_stats, sizeof stats, nullptr) != PTL_OK)
+            return fail("pass_stats");
+    }
     double t_draw = seconds_since(t0);
     if (o.png_depth == 16) {
         if (!dir_of(o.output).empty()) make_dirs(dir_of(o.output));
         if (ptl_png_write_rgb48(o.output.c_str(), rows16.data(), o.width, o.height, PTL_PNG_FILTER_SUB, 6) != PTL_OK) return fail("png");
     } else if (int rc = write_png(o.output, img.data(), o.width, o.height))
         return rc;
+    for (int which : {PTL_PASS_DEPTH, PTL_PASS_TRIPS})
+        if (!grey[which].empty() && ptl_png_write_gray16((stem + (which == PTL_PASS_DEPTH ? ".depth.png" : ".trips.png")).c_str(), grey[which].data(), o.width, o.height, 6) != PTL_OK)
+            return fail("png");
     double total = seconds_since(t0);
     std::printf("Rendered `%s` to `%s` (%dx%d, aa %d, depth %d): kernel %.3f ms, %.1f Mray/s; total %.2f s\n", o.scene.c_str(), o.output.c_str(),
                 o.width, o.height, o.aa, o.depth, ms, (double)o.width * o.height * o.aa / (ms * 1e3), total);
     if (o.adaptive && o.timing)
         std::printf("adaptive aa: threshold %d, %u of %zu pixels refined (%.2f %%); GPU ms: one-sample pass %.3f, classification %.3f, refine pass %.3f\n", o.adaptive_t,
                     refined, (size_t)o.width * o.height, 100.0 * refined / ((double)o.width * o.height), pass_ms[0], pass_ms[1], pass_ms[2]);
+    if (o.depth_report) print_depth_report(stats, render_depth_of(r, o.width, o.height));
     if (o.timing)  // where the wall time went: the JIT (or the code-object cache) dominates a single frame
         std::printf("timing: scene load %.3f s, generate + compile/load kernel %.3f s, update + draw + download %.3f s, png %.3f s\n", t_load,
                     t_build - t_load, t_draw - t_build, total - t_draw);
@@ -514,6 +562,20 @@ int main(int argc, char** argv) {
                 }
             }
         }
+        else if (a == "--passes") {
+            const std::string list = next();
+            for (const std::string& pass : split_list(list)) {
+                if (pass == "depth") o.pass_depth = true;
+                else if (pass == "trips") o.pass_trips = true;
+                else {
+                    std::fprintf(stderr, "--passes depth,trips: unknown pass `%s`\n", pass.c_str());
+                    return 2;
+                }
+            }
+            if (!o.pass_depth && !o.pass_trips) return refuse("--passes depth,trips: name at least one pass");
+            o.have_passes = true;
+        }
+        else if (a == "--depth-report") o.depth_report = true;
         else if (a == "--fast") o.fast = true;
         else if (a == "--exact-cr") o.exact_cr = true;
         else if (a == "--opt3") o.opt3 = true;
@@ -548,6 +610,12 @@ int main(int argc, char** argv) {
     if (o.adaptive && cmd != "render-frame") return refuse("--adaptive-aa is an option of render-frame: a clip's sub-frames go through the slices entry, whose adaptive form is `render --clip-adaptive-aa [T]`");
     if (o.clip_adaptive && cmd != "render" && cmd != "precompile") return refuse("--clip-adaptive-aa is an option of render (and of precompile, which builds render's kernels); a single frame takes render-frame --adaptive-aa");
     if (o.adaptive && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.shards > 1)) return refuse("--adaptive-aa draws whole frames on one GPU: it cannot be combined with --gpus N, N > 1, several --devices or --shard");
+    if (o.have_passes && cmd != "render-frame") return refuse("--passes is an option of render-frame: a clip writes no pass images per frame (render --depth-report gives a clip's line)");
+    if (o.depth_report && cmd != "render" && cmd != "render-frame") return refuse("--depth-report is an option of render and render-frame");
+    if ((o.have_passes || o.depth_report) && (o.adaptive || o.clip_adaptive))
+        return refuse("--passes and --depth-report cannot be combined with --adaptive-aa / --clip-adaptive-aa: the list-driven refine entry stores no pass records");
+    if ((o.have_passes || o.depth_report) && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.multi_process || o.shards > 1 || o.transport == "rccl"))
+        return refuse("--passes and --depth-report draw on one GPU: they cannot be combined with --gpus N, N > 1, several --devices, --multi-process, --transport rccl or --shard");
     if (cmd == "render") return render(o);
     if (o.transport != "stores" && o.transport != "copy" && o.transport != "rccl") return refuse("--transport stores|copy|rccl");
     if (cmd == "render-frame") return render_frame(o);

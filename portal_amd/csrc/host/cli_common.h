@@ -38,6 +38,9 @@ struct Options {
     int adaptive_t = 4;
     bool clip_adaptive = false;  // render --clip-adaptive-aa [T]: the same for every sub-frame of a clip (batched: the refine entry over slices)
     int clip_adaptive_t = 4;
+    bool pass_depth = false, pass_trips = false;  // render-frame --passes depth,trips: <output stem>.depth.png / .trips.png, 16-bit grey, from the tracer's pass records
+    bool have_passes = false;                     // --passes was given
+    bool depth_report = false;                    // render-frame / render --depth-report: one line on the paths that --render-depth cut short
     std::vector<std::string> argv;  // the command line as given (handed on to shard processes)
 };
 
@@ -107,9 +110,27 @@ inline unsigned quick_jit_flag(const Options& o) { return o.opt3 ? 0u : PTL_FLAG
 // right away adds quick_jit_flag().
 // --clip-adaptive-aa: where the sub-frames are batched the module has the slices entry AND the refine entry over slices (bit 29, which implies
 // bit 22), else the single-frame refine entry (bit 28) and every sub-frame is a ptl_renderer_draw_adaptive.  Without the option: what it was.
+// --depth-report: the kernel also stores the pass records (bit 30) the report is made from.
 inline unsigned clip_flags(const Options& o, bool clip_constant) {
     const unsigned entries = o.clip_adaptive ? (batch_subframes(o) ? PTL_FLAG_REFINE_SLICES : PTL_FLAG_REFINE) : (batch_subframes(o) ? kSlicesFlag : 0u);
-    return kClipFlags | entries | numerics_flags(o) | (clip_constant ? PTL_FLAG_SPECIALIZE_STATIC : 0u);
+    return kClipFlags | entries | numerics_flags(o) | (clip_constant ? PTL_FLAG_SPECIALIZE_STATIC : 0u) | (o.depth_report ? PTL_FLAG_PASSES : 0u);
+}
+
+// --depth-report: the one line a downloaded statistics block makes (ptl_pass_stats).  "traced" are the paths that entered the bounce loop
+// (the samples in the bars of a 360 / 180 degree frame never do); `tail`: what a clip adds about its worst frame.
+inline void print_depth_report(const ptl_pass_stats_block& b, int render_depth, const std::string& tail = "") {
+    const unsigned long long traced = b.paths - b.outside;
+    float lo = 0.0f, hi = 0.0f;
+    char range[64] = "none";
+    if (ptl_pass_stats_depth_range(&b, &lo, &hi) == 1) std::snprintf(range, sizeof range, "%g \xe2\x80\xa6 %g", lo, hi);
+    std::printf("Paths: %llu traced, %llu cut at depth %d (%.2f %%) in %llu pixels; deepest pixel %u trips; depth %s%s\n", traced, (unsigned long long)b.exhausted, render_depth,
+                traced ? 100.0 * (double)b.exhausted / (double)traced : 0.0, (unsigned long long)b.exhausted_pixels, b.max_trips, range, tail.c_str());
+}
+// the `_ray_tracing_depth` a draw of `r` uploads (--render-depth, or what a clip's override made of it)
+inline int render_depth_of(ptl_renderer* r, int width, int height) {
+    float v[16] = {};
+    int n = 0;
+    return ptl_renderer_uniform_value(r, width, height, "_ray_tracing_depth", v, &n) == PTL_OK ? (int)v[0] : -1;
 }
 
 // SceneRenderer::update_inner_variables (src/main.rs:1688-1756): per-clip settings the reference hard-codes for its

@@ -314,6 +314,9 @@ struct SceneRun {
     std::vector<void*> subframes;
     std::unique_ptr<void, HandleFree> float_block;  // --deep-colour and --png-depth 16 only: the same sub-frames as RGBA32F (16 bytes per pixel), one allocation, laid out the same way
     std::vector<void*> float_subframes;             // (empty without the option)
+    // --depth-report only: the sub-frames' pass records (16 bytes per pixel, laid out the same way), and what a clip accumulates from them on the
+    // card: one statistics block and a counter per frame (ptl_pass_stats), downloaded once at the end of the clip
+    std::unique_ptr<void, HandleFree> record_block, pass_stats;
     FramePipeline pipe;
 };
 
@@ -551,6 +554,19 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
     if (o.clip_adaptive) ptl_renderer_set_option(r, "adaptive_aa_threshold", o.clip_adaptive_t);
     ptl_frame frame{run.width, run.height, 0, 1, 0};
     int last = o.max_frames >= 0 ? std::min(count, o.max_frames) : count;
+    // --depth-report: the stats kernel runs behind every launch into the clip's block; per_launch[i] collects frame i's exhausted paths
+    const size_t frame_records = ptl_pass_record_bytes(run.width, run.height);
+    std::unique_ptr<void, HandleFree> per_launch;
+    if (o.depth_report) {
+        void* counters = nullptr;
+        if (ptl_device_alloc(o.device, sizeof(uint64_t) * (size_t)count, &counters) != PTL_OK) return fail("alloc");
+        per_launch.reset(counters);
+        if (ptl_device_memset(counters, 0, sizeof(uint64_t) * (size_t)count, nullptr) != PTL_OK || ptl_device_memset(run.pass_stats.get(), 0, sizeof(ptl_pass_stats_block), nullptr) != PTL_OK)
+            return fail("memset");
+    }
+    auto account_passes = [&](int i, int n) {  // the records of the launch that just went out: n sub-frames of frame i, one behind the other
+        return ptl_pass_stats(o.device, run.record_block.get(), (long)n * run.width * run.height, run.pass_stats.get(), per_launch.get(), i, nullptr, nullptr) == PTL_OK ? 0 : fail("pass_stats");
+    };
     const bool batched = batch_subframes(o), direct = out.draws_result(), with_float = out.wants_float();
     for (int i = 0; i < last; ++i) {
         if (int rc = out.check()) return rc;
@@ -580,9 +596,13 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
                 if (ptl_renderer_stage_slice(r, &frame, j) != PTL_OK) return fail("stage");
                 const unsigned long long slice_pixels = (unsigned long long)run.width * run.height;
                 if (j == o.blur - 1) {
-                    if ((o.clip_adaptive ? ptl_renderer_draw_slices_adaptive(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, o.timing ? &ms : nullptr)
-                                         : ptl_renderer_draw_slices(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, o.timing ? &ms : nullptr)) != PTL_OK)
+                    if ((o.clip_adaptive  ? ptl_renderer_draw_slices_adaptive(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, o.timing ? &ms : nullptr)
+                         : o.depth_report ? ptl_renderer_draw_slices_passes(r, &frame, o.blur, run.subframes[0], block_f32, run.record_block.get(), frame_records * (size_t)o.blur, slice_pixels,
+                                                                            nullptr, o.timing ? &ms : nullptr)
+                                          : ptl_renderer_draw_slices(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, o.timing ? &ms : nullptr)) != PTL_OK)
                         return fail("render");
+                    if (o.depth_report)
+                        if (int rc = account_passes(i, o.blur)) return rc;
                     if (o.clip_adaptive && o.timing)
                         if (int rc = account_adaptive(true, o.blur)) return rc;
                 }
@@ -590,6 +610,9 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
                 if (ptl_renderer_draw_adaptive(r, &frame, target, target_f32, nullptr, o.timing ? &ms : nullptr) != PTL_OK) return fail("render");
                 if (o.timing)
                     if (int rc = account_adaptive(false, 1)) return rc;
+            } else if (o.depth_report) {  // (the unbatched sub-frame with its records, and the stats kernel behind it)
+                if (ptl_renderer_draw_passes(r, &frame, target, target_f32, run.record_block.get(), frame_records, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) return fail("render");
+                if (int rc = account_passes(i, 1)) return rc;
             } else if (ptl_renderer_draw(r, &frame, target, target_f32, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) {
                 // (without --timing the launch is not waited for: the host evaluates the next sub-frame's uniforms while this one traces)
                 return fail("render");
@@ -626,6 +649,15 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
     if (o.timing) std::snprintf(gpu_time, sizeof gpu_time, ", GPU %.1f ms (%.3f ms each),", gpu_ms, traced ? gpu_ms / traced : 0.0);
     std::printf("Traced `%s/%s`: %ld sub-frames %dx%d%s submitted after %.2f s, kernel rebuilt %d times\n", run.name.c_str(), clip.name.c_str(), traced, run.width,
                 run.height, gpu_time, seconds_since(started), ptl_renderer_rejit_count(r) - rejits_before);
+    if (o.depth_report) {  // one download, one line: the clip's block, and the frame whose launches cut most paths
+        ptl_pass_stats_block stats{};
+        std::vector<uint64_t> cut((size_t)count, 0);
+        if (ptl_device_download(&stats, run.pass_stats.get(), sizeof stats, nullptr) != PTL_OK || ptl_device_download(cut.data(), per_launch.get(), sizeof(uint64_t) * cut.size(), nullptr) != PTL_OK)
+            return fail("download");
+        const size_t worst = (size_t)(std::max_element(cut.begin(), cut.end()) - cut.begin());
+        print_depth_report(stats, render_depth_of(r, run.width, run.height),
+                           "; `" + clip.name + "`: " + std::to_string(traced) + " sub-frames, worst frame " + std::to_string(worst) + " (" + std::to_string(cut[worst]) + " paths cut)");
+    }
     if (o.clip_adaptive && o.timing) {
         const unsigned long long pixels = (unsigned long long)traced * (unsigned long long)run.width * (unsigned long long)run.height;
         std::printf("adaptive aa: threshold %d, %llu of %llu pixels refined (%.2f %%); GPU ms: one-sample pass %.3f, classification %.3f, refine pass %.3f\n", o.clip_adaptive_t,
@@ -773,6 +805,13 @@ int render_scene(const Options& o, const std::string& path) {
         if (ptl_device_alloc(o.device, float_bytes * run.subframes.size(), &floats) != PTL_OK) return fail("alloc");
         run.float_block.reset(floats);
         for (size_t j = 0; j < run.subframes.size(); ++j) run.float_subframes.push_back(static_cast<char*>(floats) + j * float_bytes);
+    }
+    if (o.depth_report) {
+        void *records = nullptr, *stats = nullptr;
+        if (ptl_device_alloc(o.device, ptl_pass_record_bytes(run.width, run.height) * run.subframes.size(), &records) != PTL_OK) return fail("alloc");
+        run.record_block.reset(records);
+        if (ptl_device_alloc(o.device, sizeof(ptl_pass_stats_block), &stats) != PTL_OK) return fail("alloc");
+        run.pass_stats.reset(stats);
     }
     if (!run.pipe.create(o.device, run.result_bytes)) return fail("pipeline");
     Prefetcher prefetch;

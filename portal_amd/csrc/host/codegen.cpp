@@ -450,7 +450,111 @@ static void apply_refine_entry(std::string& src, const char* entry) {
     src.insert(at, entry);
 }
 
-static void apply_zero_masks(std::string& src, const std::vector<std::pair<std::string, MatrixPattern>>& masked) {
+// KernelOptions::passes: the tracer fills a ptl_pass_record per pixel and the render entries store it through one more pointer, `out_passes`.
+// Done on the finished text, behind `apply_slices_entry` (whose entry it extends in the same way), so that every build without the option
+// stays exactly what it was; the record's type and `#define PTL_PASSES 1` come from emit_uniforms.  Each anchor must be there once.
+static void apply_passes(std::string& src) {
+    auto replace = [&](const std::string& from, const std::string& to, int times) {
+        int n = 0;
+        for (size_t pos = 0; (pos = src.find(from, pos)) != std::string::npos; pos += to.size()) {
+            src.replace(pos, from.size(), to);
+            ++n;
+        }
+        if (n != times) throw SceneError("trace passes: the kernel template no longer has `" + from.substr(0, 60) + "` " + std::to_string(times) + " time(s)");
+    };
+    auto replace_either = [&](const std::string& a, const std::string& a_to, const std::string& b, const std::string& b_to) {
+        if (src.find(a) != std::string::npos) replace(a, a_to, 1);
+        else replace(b, b_to, 1);
+    };
+    // -- the tracer: the pixel's record as a member (on the line of the uniform pointer: the snippets keep their line numbers) ...
+    replace_either("    const ptl_uniform_block* ptl_ubp;\n", "    const ptl_uniform_block* ptl_ubp; ptl_pass_record ptl_pass = ptl_pass_record{__builtin_inff(), 0u, 0u, 0u};\n",
+                   "    const ptl_uniform_block* ptl_ubp; const ptl_uniform_block* ptl_home;\n",
+                   "    const ptl_uniform_block* ptl_ubp; const ptl_uniform_block* ptl_home; ptl_pass_record ptl_pass = ptl_pass_record{__builtin_inff(), 0u, 0u, 0u};\n");
+    // ... a path's result says how many trips it took and how it ended (a result nobody overwrote is a path the loop ran out on) ...
+    replace("struct RayTraceResult {\n    vec3 color;\n    float depth;\n    bool has_depth;\n};\n",
+            "struct RayTraceResult {\n    vec3 color;\n    float depth;\n    bool has_depth;\n    unsigned int trips;\n    int end_class;  // PTL_PATH_*\n};\n"
+            "enum { PTL_PATH_EXHAUSTED = 0, PTL_PATH_FINAL = 1, PTL_PATH_ESCAPED = 2 };\n"
+            "// one 16-bit count of a record word, saturating\n"
+            "PTL_FN static unsigned int ptl_pass_bump(unsigned int word, int shift) { return ((word >> shift) & 0xffffu) != 0xffffu ? word + (1u << shift) : word; }\n"
+            "// a finished path into the pixel's record (`<` keeps a NaN depth out of the minimum)\n"
+            "PTL_FN void ptl_pass_account(const RayTraceResult& path) {\n"
+            "    ptl_pass.trips += path.trips;\n"
+            "    if (path.end_class == PTL_PATH_FINAL) {\n"
+            "        ptl_pass.depth_near = path.depth < ptl_pass.depth_near ? path.depth : ptl_pass.depth_near;\n"
+            "        ptl_pass.final_escaped = ptl_pass_bump(ptl_pass.final_escaped, 0);\n"
+            "    } else if (path.end_class == PTL_PATH_ESCAPED) {\n"
+            "        ptl_pass.final_escaped = ptl_pass_bump(ptl_pass.final_escaped, 16);\n"
+            "    } else {\n"
+            "        ptl_pass.exhausted_outside = ptl_pass_bump(ptl_pass.exhausted_outside, 0);\n"
+            "    }\n"
+            "}\n",
+            1);
+    replace("        out = r.in_subspace ? RayTraceResult{color(0.0f, 0.0f, 0.0f), 0.0f, false} : RayTraceResult{current_color * not_found_color, 0.0f, false};\n",
+            "        out = r.in_subspace ? RayTraceResult{color(0.0f, 0.0f, 0.0f), 0.0f, false, 0u, PTL_PATH_ESCAPED} : RayTraceResult{current_color * not_found_color, 0.0f, false, 0u, PTL_PATH_ESCAPED};\n", 1);
+    replace(", depth, true};\n", ", depth, true, 0u, PTL_PATH_FINAL};\n", 2);
+    // ... the bounce loop counts its trips where PTL_COUNT_SEGMENT() does and hands the count out with the result ...
+    {
+        const size_t begin = src.find("    RayTraceResult result = RayTraceResult{color(0.0f, 0.0f, 0.0f), 0.0f, false};  // depth exhausted\n");
+        const size_t end = src.find("// --- camera teleportation");
+        if (begin == std::string::npos || end == std::string::npos || end < begin) throw SceneError("trace passes: the kernel template no longer has its bounce loop where it was");
+        std::string loop = src.substr(begin, end - begin);
+        auto within = [&](const std::string& from, const std::string& to, int times) {
+            int n = 0;
+            for (size_t pos = 0; (pos = loop.find(from, pos)) != std::string::npos; pos += to.size()) {
+                loop.replace(pos, from.size(), to);
+                ++n;
+            }
+            if (n != times) throw SceneError("trace passes: the bounce loop no longer has `" + from + "` " + std::to_string(times) + " time(s)");
+        };
+        within("  // depth exhausted\n", "  // depth exhausted\n    unsigned int ptl_path_trips = 0u;\n", 1);
+        within("PTL_COUNT_SEGMENT();", "PTL_COUNT_SEGMENT(); ++ptl_path_trips;", 4);
+        within("return result;", "{ result.trips = ptl_path_trips; return result; }", 3);
+        src.replace(begin, end - begin, loop);
+    }
+    // ... and get_color2 books every sample: the traced ones by their result, the ones in the bars of a 360 / 180 degree frame as `outside`
+    replace("        if (abs(image_position.x) > rx || abs(image_position.y) > ry) return vec3(0.0f);\n",
+            "        if (abs(image_position.x) > rx || abs(image_position.y) > ry) { ptl_pass.exhausted_outside = ptl_pass_bump(ptl_pass.exhausted_outside, 16); return vec3(0.0f); }\n", 1);
+    replace("        if (abs(image_position.x) > 1.0f || abs(image_position.y) > 1.0f) return vec3(0.0f);\n",
+            "        if (abs(image_position.x) > 1.0f || abs(image_position.y) > 1.0f) { ptl_pass.exhausted_outside = ptl_pass_bump(ptl_pass.exhausted_outside, 16); return vec3(0.0f); }\n", 1);
+    replace("#endif\n    if (_draw_depth_map == 1) {\n", "#endif\n    ptl_pass_account(trace);\n    if (_draw_depth_map == 1) {\n", 1);
+    // -- the free functions the entries call hand the record out
+    replace_either("PTL_FN vec4 shade_pixel(vec2 position) {\n    ptl_tracer t{&ptl_u};\n    return t.shade_pixel(position);\n}\n",
+                   "PTL_FN vec4 shade_pixel(vec2 position, ptl_pass_record* ptl_rec = nullptr) {\n    ptl_tracer t{&ptl_u};\n    const vec4 ptl_c = t.shade_pixel(position);\n    if (ptl_rec) *ptl_rec = t.ptl_pass;\n    return ptl_c;\n}\n",
+                   "PTL_FN vec4 shade_pixel(vec2 position) {\n    ptl_tracer t{&ptl_u, &ptl_u};\n    return t.shade_pixel(position);\n}\n",
+                   "PTL_FN vec4 shade_pixel(vec2 position, ptl_pass_record* ptl_rec = nullptr) {\n    ptl_tracer t{&ptl_u, &ptl_u};\n    const vec4 ptl_c = t.shade_pixel(position);\n    if (ptl_rec) *ptl_rec = t.ptl_pass;\n    return ptl_c;\n}\n");
+    const bool sliced = src.find("PTL_FN vec4 shade_pixel_in(vec2 position, const ptl_uniform_block* home) {\n") != std::string::npos;
+    if (sliced)
+        replace("PTL_FN vec4 shade_pixel_in(vec2 position, const ptl_uniform_block* home) {\n    ptl_tracer t{home, home};\n    return t.shade_pixel(position);\n}\n",
+                "PTL_FN vec4 shade_pixel_in(vec2 position, const ptl_uniform_block* home, ptl_pass_record* ptl_rec = nullptr) {\n    ptl_tracer t{home, home};\n    const vec4 ptl_c = t.shade_pixel(position);\n"
+                "    if (ptl_rec) *ptl_rec = t.ptl_pass;\n    return ptl_c;\n}\n", 1);
+    // -- the render entry: one more pointer, addressed like out_rgba32f (a 16-byte store per lane: 8 lanes = one 128 B line per tile row)
+    replace("                  int in_place) {  ", "                  int in_place, glsl::ptl_pass_record* __restrict__ out_passes) {  ", 1);
+    if (sliced)
+        replace("    if (out_rgba32f != nullptr) out_rgba32f += 4ull * blockIdx.z * ptl_slice_pixels;\n",
+                "    if (out_rgba32f != nullptr) out_rgba32f += 4ull * blockIdx.z * ptl_slice_pixels;\n    if (out_passes != nullptr) out_passes += (unsigned long long)blockIdx.z * ptl_slice_pixels;\n", 1);
+    replace("    glsl::vec4 c = glsl::vec4(0.0f);\n    if (live) c = glsl::shade_pixel", "    glsl::vec4 c = glsl::vec4(0.0f);\n    glsl::ptl_pass_record ptl_rec = {__builtin_inff(), 0u, 0u, 0u};\n    if (live) c = glsl::shade_pixel", 1);
+    if (sliced) replace("(float)py + 0.5f), ptl_slice_block);\n\n    const int out_block", "(float)py + 0.5f), ptl_slice_block, &ptl_rec);\n\n    const int out_block", 1);
+    else replace("(float)py + 0.5f));\n\n    const int out_block", "(float)py + 0.5f), &ptl_rec);\n\n    const int out_block", 1);
+    replace("    if (out_rgba32f != nullptr && live) {\n        float4 v = make_float4(c.x, c.y, c.z, c.w);\n",
+            "    if (out_passes != nullptr && live) out_passes[shard_row * width + px] = ptl_rec;\n    if (out_rgba32f != nullptr && live) {\n        float4 v = make_float4(c.x, c.y, c.z, c.w);\n", 1);
+    // -- the host build: ptl_host_render becomes the body of two entries, the old one and its sibling with the records
+    replace("extern \"C\" unsigned long long ptl_host_render(uint8_t* out_rgba8, float* out_rgba32f, int width, int height,\n",
+            "static unsigned long long ptl_host_render_both(glsl::ptl_pass_record* out_passes, uint8_t* out_rgba8, float* out_rgba32f, int width, int height,\n", 1);
+    replace("            glsl::vec4 c = glsl::shade_pixel(glsl::vec2((float)px + 0.5f, (float)py + 0.5f));\n            long idx = (long)i * cols + (px - col_begin);\n",
+            "            glsl::ptl_pass_record ptl_rec = {__builtin_inff(), 0u, 0u, 0u};\n            glsl::vec4 c = glsl::shade_pixel(glsl::vec2((float)px + 0.5f, (float)py + 0.5f), &ptl_rec);\n"
+            "            long idx = (long)i * cols + (px - col_begin);\n            if (out_passes) out_passes[idx] = ptl_rec;\n", 1);
+    const size_t last = src.rfind("#endif\n");
+    if (last == std::string::npos) throw SceneError("trace passes: the kernel template no longer ends in `#endif`");
+    src.insert(last,
+               "extern \"C\" unsigned long long ptl_host_render(uint8_t* out_rgba8, float* out_rgba32f, int width, int height, const int* rows, int n_rows, int col_begin, int col_end, int threads) {\n"
+               "    return ptl_host_render_both(nullptr, out_rgba8, out_rgba32f, width, height, rows, n_rows, col_begin, col_end, threads);\n}\n"
+               "// ... and the same rows with the pixels' pass records (16 bytes each, 16-byte aligned, laid out like out_rgba32f)\n"
+               "extern \"C\" unsigned long long ptl_host_render_passes(uint8_t* out_rgba8, float* out_rgba32f, void* out_passes, int width, int height, const int* rows, int n_rows, int col_begin,\n"
+               "                                                     int col_end, int threads) {\n"
+               "    return ptl_host_render_both(static_cast<glsl::ptl_pass_record*>(out_passes), out_rgba8, out_rgba32f, width, height, rows, n_rows, col_begin, col_end, threads);\n}\n\n");
+}
+
+static void apply_zero_masks(std::string& src,const std::vector<std::pair<std::string, MatrixPattern>>& masked) {
     auto ident = [](char c) { return std::isalnum((unsigned char)c) || c == '_'; };
     for (auto& [name, mask] : masked) {
         (void)mask;
@@ -1275,6 +1379,9 @@ StringStorage emit_uniforms(const Scene& scene, const BuildPlan& plan, const Ker
     if (plan.affine_rays) s.add_string("#define PTL_AFFINE_RAYS 1\n");
     if (opts.check_affine) s.add_string("#define PTL_CHECK_AFFINE 1\n");  // (implies PTL_COUNT_SEGMENTS: the counter counts rays whose w is not 1 / 0)
     if (opts.derived_uniforms) s.add_string("#define PTL_DERIVED_BUILTINS 1\n");
+    // (trace passes: the define in the text for the same reason, and the record the tracer fills per pixel -- include/portal_amd.h has its contract)
+    if (opts.passes)
+        s.add_string("#define PTL_PASSES 1\nstruct alignas(16) ptl_pass_record {\n    float depth_near;\n    unsigned int trips;\n    unsigned int final_escaped;\n    unsigned int exhausted_outside;\n};\n");
     if (plan.first_trip_plane_tests > 0) s.add_string("#define PTL_FIRST_TRIP_PLANES 1\n#ifndef PTL_FIRST_TRIP\n#define PTL_FIRST_TRIP 1\n#endif\n");
     if (plan.any_first_snippet()) s.add_string("#define PTL_FIRST_TRIP_SNIPPETS 1\n#ifndef PTL_FIRST_TRIP\n#define PTL_FIRST_TRIP 1\n#endif\n");
     s.add_string("struct ptl_uniform_block {\n");
@@ -1693,7 +1800,13 @@ GeneratedKernel generate_kernel_source(const Scene& scene, const CodegenFlags& f
     if (opts.refine_slices_entry && opts.refine_entry)
         throw SceneError("PTL_FLAG_REFINE and PTL_FLAG_REFINE_SLICES cannot be combined: a module has the refine entry over its own uniform block or the one over slices");
     if (opts.slices_entry && opts.refine_entry) throw SceneError("PTL_FLAG_REFINE and PTL_FLAG_SLICES cannot be combined: the refine entry reads the module's own uniform block (PTL_FLAG_REFINE_SLICES has the entry over slices)");
+    if (opts.passes && (opts.anaglyph || opts.refine_entry || opts.refine_slices_entry || opts.check_affine))
+        throw SceneError(std::string("PTL_FLAG_PASSES cannot be combined with ") + (opts.anaglyph ? "PTL_FLAG_ANAGLYPH: an anaglyph sample traces two paths, a pass record books one per sample"
+                                                                                    : opts.check_affine ? "PTL_FLAG_CHECK_AFFINE: that build counts ray halves where the record counts trips"
+                                                                                    : opts.refine_entry ? "PTL_FLAG_REFINE: the list-driven entry stores no records"
+                                                                                                        : "PTL_FLAG_REFINE_SLICES: the list-driven entry stores no records"));
     if (opts.slices_entry || opts.refine_slices_entry) apply_slices_entry(gk.source);
+    if (opts.passes) apply_passes(gk.source);
     if (opts.refine_entry) apply_refine_entry(gk.source, device_source_refine_entry());
     if (opts.refine_slices_entry) apply_refine_entry(gk.source, device_source_refine_slices_entry());
     return gk;

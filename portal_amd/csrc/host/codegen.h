@@ -163,6 +163,11 @@ struct KernelOptions {
     // buffer of blocks, `ptl_render_refine_slices_kernel` (device/ptl_refine_slices_entry.h, the same walk once per slice): slice z shades the pixels
     // of ITS list with ITS block.  `apply_slices_entry` first, then `apply_refine_entry` with this entry's text.  Not together with refine_entry.
     bool refine_slices_entry = false;
+    // Trace passes (PTL_FLAG_PASSES): the tracer keeps a 16-byte record per pixel -- nearest final depth, bounce-loop trips, how its paths ended
+    // (include/portal_amd.h `ptl_pass_record`) -- and the render entry (the slices entry too) takes one more pointer, `out_passes`, stored like
+    // out_rgba32f.  Applied to the finished text like the slices entry (codegen.cpp `apply_passes`), and `#define PTL_PASSES 1` stands in the text:
+    // kernels built without it are byte for byte what they were.  Not with anaglyph (two paths per sample), the refine entries or check_affine.
+    bool passes = false;
     // Affine rays (round 5): in a kernel whose every scene matrix is KNOWN to have the bottom row 0 0 0 1 (baked, or through its pattern) and
     // whose scene snippets never write a ray's w, every origin has w = 1 and every direction w = 0, and the products of a matrix with a ray
     // say so (device/ptl_glsl.h PTL_AFFINE_RAYS): the translation column costs a direction nothing, the w row folds to a constant.  Exact for

@@ -46,6 +46,7 @@ struct ptl_kernel {
     bool has_refine = false;                   // the source names that entry (known without a device)
     hip::hipFunction_t refine_slices_fn = nullptr;  // optional: ptl_render_refine_slices_kernel, the list-driven entry over slices (PTL_FLAG_REFINE_SLICES)
     bool has_refine_slices = false;                 // the source names that entry (known without a device); such a source has the slices entry too
+    bool has_passes = false;                        // the source was generated with PTL_FLAG_PASSES: its render entry takes `out_passes` behind `in_place`
     void* dev_block = nullptr;  // address of __constant__ ptl_u
     size_t dev_block_size = 0;
     std::vector<unsigned char> shadow;  // host copy of the uniform block
@@ -487,6 +488,7 @@ int compile_kernel(const CompileRequest& rq, const std::vector<char>* prebuilt, 
     k->split = traits.split;
     k->has_refine = !traits.teleport_only && std::strstr(rq.source, "ptl_render_refine_kernel(") != nullptr;
     k->has_refine_slices = !traits.teleport_only && std::strstr(rq.source, "ptl_render_refine_slices_kernel(") != nullptr;
+    k->has_passes = !traits.teleport_only && std::strstr(rq.source, "#define PTL_PASSES 1\n") != nullptr;
     if (k->split) {
         k->source = rq.source;
         k->defines.assign(rq.defines, rq.defines + rq.n_defines);
@@ -580,6 +582,7 @@ extern "C" int ptl_kernel_clone(ptl_kernel* src, ptl_kernel** out) {
     k->split = src->split;
     k->has_refine = src->has_refine;
     k->has_refine_slices = src->has_refine_slices;
+    k->has_passes = src->has_passes;
     k->source = src->source;
     k->defines = src->defines;
     // (affine_rays is NOT inherited: a clone accepts matrices through ptl_kernel_set_uniform that its original refuses)
@@ -622,6 +625,12 @@ extern "C" int ptl_code_object_note(const void* code, size_t size, const char* k
 
 extern "C" int ptl_kernel_resources(ptl_kernel* k, int* registers, int* scratch_bytes, int* lds_bytes) {
     if (!k) return PTL_ERR_INVALID;
+    if (k->device < 0 && !k->code.empty()) {  // a compile-only handle: what the code object's metadata says about its render entries
+        if (registers) *registers = render_note(k->code, ".vgpr_count");
+        if (scratch_bytes) *scratch_bytes = render_note(k->code, ".private_segment_fixed_size");
+        if (lds_bytes) *lds_bytes = render_note(k->code, ".group_segment_fixed_size");
+        return PTL_OK;
+    }
     if (k->device < 0 || !k->fn) return PTL_ERR_NO_DEVICE;
     const hip::Runtime* rt = hip::runtime(nullptr);
     int v = 0;
@@ -791,7 +800,8 @@ static int timed_launch(ptl_kernel* k, const hip::Runtime* rt, hip::hipFunction_
 
 // The one render launch.  A module with the slices entry traces slices 0 .. n-1 of its buffer of blocks, slice z into out_rgba8 + z * slice_pixels
 // pixels; the plain entry (n = 1) reads the module's own block.  `label`: what a refused launch is reported as.
-static int launch_render(ptl_kernel* k, const hip::Runtime* rt, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
+// `out_passes`: the pass records of a PTL_FLAG_PASSES module (null: none wanted); every other module's entry ends before that argument.
+static int launch_render(ptl_kernel* k, const hip::Runtime* rt, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, void* out_passes, unsigned long long slice_pixels,
                          void* segments, void* stream, float* elapsed_ms, const char* label) {
     int nby = shard_blocks(frame);
     if (nby == 0) {
@@ -801,7 +811,7 @@ static int launch_render(ptl_kernel* k, const hip::Runtime* rt, const ptl_frame*
     int width = frame->width, height = frame->height, phase = frame->rb_phase, stride = frame->rb_stride;
     int in_place = frame->in_place ? 1 : 0;
     void* blocks = k->dev_slices;
-    void* args[] = {&blocks, &slice_pixels, &out_rgba8, &out_rgba32f, &width, &height, &phase, &stride, &segments, &in_place};  // the plain entry takes the last eight
+    void* args[] = {&blocks, &slice_pixels, &out_rgba8, &out_rgba32f, &width, &height, &phase, &stride, &segments, &in_place, &out_passes};  // the plain entry starts at out_rgba8
     // 256 threads = four 8x8 tiles side by side.  PTL_BLOCK_WAVES=1|2 (experiment, tools/variants.py) launches narrower workgroups.
     const unsigned waves = k->block_waves;
     unsigned gx = (unsigned)((width + 8 * waves - 1) / (8 * waves)), gy = (unsigned)nby;
@@ -860,8 +870,8 @@ extern "C" int ptl_kernel_snapshot_uniforms(ptl_kernel* k, void* dst, size_t cap
 
 // ONE launch for the staged slices 0 .. n-1: slice z renders `frame` with its own uniforms into out_rgba8 + z * slice_pixels pixels
 // (and out_rgba32f + 4 * z * slice_pixels floats).
-extern "C" int ptl_kernel_render_slices(ptl_kernel* k, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
-                                        void* stream, float* elapsed_ms) {
+static int render_slices(ptl_kernel* k, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, void* out_passes, unsigned long long slice_pixels, void* stream,
+                         float* elapsed_ms) {
     if (!k || !frame || ptl_frame_shard_rows(frame) < 0 || n < 1 || n > kMaxSlices) return PTL_ERR_INVALID;
     if (!k->sliced || k->staged.empty()) {
         set_last_error("ptl_kernel_render_slices: no staged slices (PTL_FLAG_SLICES build + ptl_kernel_stage_slice)");
@@ -871,18 +881,59 @@ extern "C" int ptl_kernel_render_slices(ptl_kernel* k, const ptl_frame* frame, i
     const hip::Runtime* rt = hip::runtime(nullptr);
     if (!hip_ok(rt, rt->hipSetDevice(k->device), "hipSetDevice")) return PTL_ERR_HIP;
     if (int rc = upload_slices(k, rt, stream, n, false); rc != PTL_OK) return rc;
-    return launch_render(k, rt, frame, n, out_rgba8, out_rgba32f, slice_pixels, nullptr, stream, elapsed_ms, kSlicesLaunch);
+    return launch_render(k, rt, frame, n, out_rgba8, out_rgba32f, out_passes, slice_pixels, nullptr, stream, elapsed_ms, kSlicesLaunch);
 }
 
-extern "C" int ptl_kernel_render(ptl_kernel* k, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* segments,
-                                 void* stream, float* elapsed_ms) {
+extern "C" int ptl_kernel_render_slices(ptl_kernel* k, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
+                                        void* stream, float* elapsed_ms) {
+    return render_slices(k, frame, n, out_rgba8, out_rgba32f, nullptr, slice_pixels, stream, elapsed_ms);
+}
+
+static int render_single(ptl_kernel* k, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* out_passes, void* segments, void* stream, float* elapsed_ms) {
     if (!k || !frame || ptl_frame_shard_rows(frame) < 0) return PTL_ERR_INVALID;
     if (k->device < 0 || !k->fn) return PTL_ERR_NO_DEVICE;
     const hip::Runtime* rt = hip::runtime(nullptr);
     if (!hip_ok(rt, rt->hipSetDevice(k->device), "hipSetDevice")) return PTL_ERR_HIP;
     // (a single draw of a module with the slices entry: slice 0 of its buffer, one slice)
     if (int rc = k->sliced ? upload_slices(k, rt, stream, 1, true) : upload_uniforms(k, rt, stream); rc != PTL_OK) return rc;
-    return launch_render(k, rt, frame, 1, out_rgba8, out_rgba32f, 0, segments, stream, elapsed_ms, k->sliced ? kSlicesLaunch : "hipModuleLaunchKernel");
+    return launch_render(k, rt, frame, 1, out_rgba8, out_rgba32f, out_passes, 0, segments, stream, elapsed_ms, k->sliced ? kSlicesLaunch : "hipModuleLaunchKernel");
+}
+
+extern "C" int ptl_kernel_render(ptl_kernel* k, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* segments,
+                                 void* stream, float* elapsed_ms) {
+    return render_single(k, frame, out_rgba8, out_rgba32f, nullptr, segments, stream, elapsed_ms);
+}
+
+// ---- trace passes: the same two launches with the records of a PTL_FLAG_PASSES module (codegen.cpp `apply_passes`) ---------------------
+extern "C" size_t ptl_pass_record_bytes(int width, int height) { return (width > 0 && height > 0) ? sizeof(ptl_pass_record) * (size_t)width * (size_t)height : 0; }
+
+// What both refuse before any GPU call: a module without the records, a missing or misaligned buffer, one too small for what the launch stores
+// (`pixels`: the last slice's offset plus the rows this shard writes -- all of the frame's when it stores in place).
+static int check_passes(const char* who, const ptl_kernel* k, const ptl_frame* frame, const void* out_passes, size_t passes_bytes, unsigned long long slice_offset) {
+    if (!k || !frame || ptl_frame_shard_rows(frame) < 0) return PTL_ERR_INVALID;
+    if (!k->has_passes) {
+        set_last_error(std::string(who) + ": the kernel was not generated with pass records (PTL_FLAG_PASSES)");
+        return PTL_ERR_INVALID;
+    }
+    const unsigned long long rows = frame->in_place ? (unsigned long long)frame->height : (unsigned long long)ptl_frame_shard_rows(frame);
+    if (!out_passes || (reinterpret_cast<uintptr_t>(out_passes) & 15u) || passes_bytes < sizeof(ptl_pass_record) * (slice_offset + rows * (unsigned long long)frame->width)) {
+        set_last_error(std::string(who) + ": out_passes must be a 16-byte aligned buffer of 16 bytes per pixel the launch stores (ptl_pass_record_bytes)");
+        return PTL_ERR_INVALID;
+    }
+    return PTL_OK;
+}
+
+extern "C" int ptl_kernel_render_passes(ptl_kernel* k, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* out_passes, size_t passes_bytes, void* segments,
+                                        void* stream, float* elapsed_ms) {
+    if (int rc = check_passes("ptl_kernel_render_passes", k, frame, out_passes, passes_bytes, 0); rc != PTL_OK) return rc;
+    return render_single(k, frame, out_rgba8, out_rgba32f, out_passes, segments, stream, elapsed_ms);
+}
+
+extern "C" int ptl_kernel_render_slices_passes(ptl_kernel* k, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, void* out_passes, size_t passes_bytes,
+                                               unsigned long long slice_pixels, void* stream, float* elapsed_ms) {
+    if (n < 1 || n > kMaxSlices) return PTL_ERR_INVALID;
+    if (int rc = check_passes("ptl_kernel_render_slices_passes", k, frame, out_passes, passes_bytes, (unsigned long long)(n - 1) * slice_pixels); rc != PTL_OK) return rc;
+    return render_slices(k, frame, n, out_rgba8, out_rgba32f, out_passes, slice_pixels, stream, elapsed_ms);
 }
 
 // ---- the refine pass of the adaptive anti-aliasing: the list-driven entries (device/ptl_refine_common.h) -----------------------------

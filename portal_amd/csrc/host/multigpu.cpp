@@ -120,6 +120,10 @@ extern "C" int ptl_frame_group_create(ptl_scene* scene, const int* devices, int 
     if (!scene || !devices || n_devices < 1 || n_devices > 64 || !out) return PTL_ERR_INVALID;
     if (transport != PTL_GROUP_PEER_STORES && transport != PTL_GROUP_COPY_GATHER && transport != PTL_GROUP_RCCL_GATHER) return PTL_ERR_INVALID;
     *out = nullptr;
+    if (flags & PTL_FLAG_PASSES) {
+        set_last_error("ptl_frame_group_create: a frame group draws no pass records (PTL_FLAG_PASSES belongs to a single renderer)");
+        return PTL_ERR_INVALID;
+    }
     std::string err;
     const hip::Runtime* rt = hip::runtime(&err);
     if (!rt) {
@@ -211,6 +215,10 @@ extern "C" ptl_renderer* ptl_frame_group_renderer(ptl_frame_group* g, int rank) 
 
 extern "C" int ptl_frame_group_set_option(ptl_frame_group* g, const char* name, double value) {
     if (!g) return PTL_ERR_INVALID;
+    if (name && std::string(name) == "passes") {
+        set_last_error("ptl_frame_group_set_option: a frame group draws no pass records (option `passes` belongs to a single renderer)");
+        return PTL_ERR_INVALID;
+    }
     for (ptl_renderer* r : g->renderers)
         if (int rc = ptl_renderer_set_option(r, name, value); rc != PTL_OK) return rc;
     return PTL_OK;

@@ -221,4 +221,18 @@ extern "C" int ptl_png_write_rgb48(const char* path, const uint8_t* rows, int wi
     return write_png_file(path, raw, comp, width, height, 16, 2, level);
 }
 
+// 16-bit greyscale from the samples ptl_passes_to_gray16 left in PNG's byte order (a depth or trip-count pass): filter None on every row.
+extern "C" int ptl_png_write_gray16(const char* path, const uint8_t* rows, int width, int height, int level) {
+    if (!path || !rows || width <= 0 || height <= 0 || level < 0 || level > 9) return PTL_ERR_INVALID;
+    const size_t stride = (size_t)width * 2;
+    auto& [raw, comp] = writer_scratch();
+    raw.resize((stride + 1) * height);
+    for (int y = 0; y < height; ++y) {
+        unsigned char* dst = &raw[(size_t)y * (stride + 1)];
+        dst[0] = 0;
+        std::memcpy(dst + 1, rows + (size_t)y * stride, stride);
+    }
+    return write_png_file(path, raw, comp, width, height, 16, 0, level);
+}
+
 extern "C" int ptl_png_write(const char* path, const uint8_t* rgba8, int width, int height) { return ptl_png_write_level(path, rgba8, width, height, 6); }

@@ -7,6 +7,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "../../../include/portal_amd.h"
+#include "../kernels/pass_key.h"
 #include "../kernels/rgb48_shape.h"
 #include "../kernels/yuv_shape.h"
 #include "hip_api.h"
@@ -99,6 +101,14 @@ int timed(const hip::Runtime* rt, LoadedKernel* k, void* stream, float* elapsed_
     return err;
 }
 
+// Workgroups of 256 for `lanes` lanes: the kernels stride over the grid beyond 16 workgroups per CU (PTL_AVERAGE_IMAGES_GRID_CAP, read at each
+// call: tuning, and the tests that make the stride loops go round).
+long grid_blocks(long lanes) {
+    long cap = 256 * 16;
+    if (const char* c = std::getenv("PTL_AVERAGE_IMAGES_GRID_CAP")) cap = std::atol(c) > 0 ? std::atol(c) : cap;
+    return std::min(cap, std::max(1L, (lanes + 255) / 256));
+}
+
 // What ptl_average_images, the ptl_average_*_to_yuv* family and ptl_average_f32_to_rgb48 share: a kernel over N sub-frames with two entries (up to 64 pointers in the
 // kernel arguments, beyond in a device table), launched as `lanes` lanes in workgroups of 256 (grid-stride beyond the cap) on `stream`.
 // The kernel's arguments are (frames, n, tail...).
@@ -141,10 +151,7 @@ int launch_over_subframes(int device, const SubframeKernel& kernel, const void* 
     }
     std::vector<void*> args = {table ? static_cast<void*>(&dev_table) : static_cast<void*>(&list), &n};
     args.insert(args.end(), tail.begin(), tail.end());
-    long blocks = std::max(1L, (lanes + 255) / 256);
-    long cap = 256 * 16;  // grid-stride beyond 16 workgroups per CU
-    if (const char* c = std::getenv("PTL_AVERAGE_IMAGES_GRID_CAP")) cap = std::atol(c) > 0 ? std::atol(c) : cap;
-    if (blocks > cap) blocks = cap;
+    const long blocks = grid_blocks(lanes);
     const int err = timed(rt, k, stream, elapsed_ms, [&] { return rt->hipModuleLaunchKernel(k->fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream, args.data(), nullptr); });
     if (err != 0) {
         if (dev_table) rt->hipFree(dev_table);
@@ -259,6 +266,59 @@ extern "C" int ptl_average_f32_to_rgb48(int device, const void* const* frames_rg
         {"rgb48_f32.hsaco", "ptl_average_f32_to_rgb48_sub_kernel", "ptl_average_f32_to_rgb48_sub_table_kernel", "average_f32_to_rgb48"}};
     const long lanes = ptl_rgb48_lanes((unsigned)width, (unsigned)height);
     return launch_over_subframes(device, kKernels[filter == PTL_PNG_FILTER_SUB], frames_rgba32f, n_frames, {&out_rows, &width, &height}, lanes, stream, elapsed_ms);
+}
+
+// ---- trace passes: the records a PTL_FLAG_PASSES render entry stores (portal_amd/csrc/kernels/pass_stats.hip, pass_gray16.hip; the contracts are
+// in include/portal_amd.h).  Both kernels sweep `n` records with a strided grid of 256-thread workgroups.
+namespace {
+static_assert(sizeof(ptl_pass_record) == 16 && sizeof(ptl_pass_stats_block) == 64 + 16 + 8 * PTL_PASS_HIST_BINS, "the layouts the kernels read and write");
+// pass_stats.hip adds its totals as eight uint64 from `pixels` on and its maxima as three uint32 from `max_trips` on (pass_key.h)
+static_assert(offsetof(ptl_pass_stats_block, pixels) == ptl_pass_block_totals && offsetof(ptl_pass_stats_block, exhausted_pixels) == ptl_pass_block_totals + 56 &&
+                  offsetof(ptl_pass_stats_block, max_trips) == ptl_pass_block_maxima && offsetof(ptl_pass_stats_block, depth_min_key_inv) == ptl_pass_block_maxima + 8 &&
+                  offsetof(ptl_pass_stats_block, trips_histogram) == ptl_pass_block_histogram && PTL_PASS_HIST_BINS == ptl_pass_hist_bins,
+              "");
+static_assert(PTL_PASS_DEPTH == ptl_pass_which_depth && PTL_PASS_TRIPS == ptl_pass_which_trips, "");
+
+int launch_over_records(int device, const char* file, const char* entry, const char* what, void** args, long lanes, void* stream, float* elapsed_ms) {
+    if (device < 0) return PTL_ERR_NO_DEVICE;
+    LoadedKernel* k = nullptr;
+    if (int rc = load_kernel(device, file, entry, &k); rc != PTL_OK) return rc;
+    const hip::Runtime* rt = hip::runtime(nullptr);
+    rt->hipSetDevice(device);
+    const int err = timed(rt, k, stream, elapsed_ms, [&] { return rt->hipModuleLaunchKernel(k->fn, (unsigned)grid_blocks(lanes), 1, 1, 256, 1, 1, 0, stream, args, nullptr); });
+    if (err != 0) {
+        set_last_error(std::string("hipModuleLaunchKernel(") + what + "): " + rt->hipGetErrorString(err));
+        rt->hipGetLastError();
+        return PTL_ERR_HIP;
+    }
+    return PTL_OK;
+}
+}  // namespace
+
+extern "C" int ptl_pass_stats(int device, const void* records, long n, void* stats_block, void* per_launch, int slot, void* stream, float* elapsed_ms) {
+    if (!records || !stats_block || n < 1 || n > (1L << 31) || slot < 0) return PTL_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(records) & 15u) || (reinterpret_cast<uintptr_t>(stats_block) & 7u) || (reinterpret_cast<uintptr_t>(per_launch) & 7u)) return PTL_ERR_INVALID;
+    void* args[] = {&records, &n, &stats_block, &per_launch, &slot};
+    return launch_over_records(device, "pass_stats.hsaco", "ptl_pass_stats_kernel", "pass_stats", args, n, stream, elapsed_ms);
+}
+
+extern "C" int ptl_pass_stats_depth_range(const ptl_pass_stats_block* block, float* lo, float* hi) {
+    if (!block || !lo || !hi || block->depth_max_key == 0u || block->depth_min_key_inv == 0u) return 0;
+    const unsigned int lo_bits = ptl_pass_depth_bits(~block->depth_min_key_inv), hi_bits = ptl_pass_depth_bits(block->depth_max_key);
+    std::memcpy(lo, &lo_bits, 4);
+    std::memcpy(hi, &hi_bits, 4);
+    return 1;
+}
+
+extern "C" int ptl_passes_to_gray16(int device, const void* records, long n, void* out_rows, int which, float lo, float hi, void* stream, float* elapsed_ms) {
+    if (which != PTL_PASS_DEPTH && which != PTL_PASS_TRIPS) {
+        set_last_error("passes_to_gray16: which " + std::to_string(which) + " is neither PTL_PASS_DEPTH (0) nor PTL_PASS_TRIPS (1)");
+        return PTL_ERR_INVALID;
+    }
+    if (!records || !out_rows || n < 1 || n > (1L << 31)) return PTL_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(out_rows)) & 15u) return PTL_ERR_INVALID;
+    void* args[] = {&records, &n, &out_rows, &which, &lo, &hi};
+    return launch_over_records(device, "pass_gray16.hsaco", "ptl_passes_to_gray16_kernel", "passes_to_gray16", args, (n + 3) / 4, stream, elapsed_ms);  // a lane per four records
 }
 
 // ptl_aa_edges: the classification pass of the adaptive anti-aliasing (portal_amd/csrc/kernels/aa_edges.hip; the contract is in
@@ -408,6 +468,12 @@ extern "C" int ptl_event_synchronize(void* event) {
 extern "C" int ptl_stream_wait_event(void* stream, void* event) {
     const hip::Runtime* rt = hip::runtime(nullptr);
     return rt ? hip_status(rt, rt->hipStreamWaitEvent(stream, event, 0), "hipStreamWaitEvent") : PTL_ERR_NO_DEVICE;
+}
+extern "C" int ptl_device_memset(void* device_dst, int value, size_t bytes, void* stream) {
+    if (!device_dst) return PTL_ERR_INVALID;
+    const hip::Runtime* rt = hip::runtime(nullptr);
+    if (!rt) return PTL_ERR_NO_DEVICE;
+    return hip_status(rt, rt->hipMemsetAsync(device_dst, value, bytes, stream), "hipMemsetAsync");
 }
 extern "C" int ptl_device_download_async(void* host_dst, const void* device_src, size_t bytes, void* stream) {
     if (!host_dst || !device_src) return PTL_ERR_INVALID;

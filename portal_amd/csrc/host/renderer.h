@@ -303,7 +303,7 @@ int update_videos(ptl_renderer* r);
 int update_kernel(ptl_renderer* r, const std::vector<UniformUpload>* values, Rebuild forced = Rebuild::none, char* log = nullptr, size_t log_cap = 0);
 int async_select_kernel(ptl_renderer* r, const std::vector<UniformUpload>* values);
 int rebuild_now(ptl_renderer* r, Rebuild why, char* log, size_t log_cap);
-int set_specialize_static(ptl_renderer* r, bool on);   // option "specialize_static"
+int set_build_flag(ptl_renderer* r, unsigned bit, bool on);   // options "specialize_static" (PTL_FLAG_SPECIALIZE_STATIC) and "passes" (PTL_FLAG_PASSES)
 int rebuild_without_affine_rays(ptl_renderer* r);      // the check-affine belt counted a violation
 
 // renderer_draw.cpp

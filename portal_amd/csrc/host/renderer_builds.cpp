@@ -48,6 +48,7 @@ static KernelOptions options_from_flags(unsigned flags) {
     o.refine_entry = on(PTL_FLAG_REFINE);  // a second render entry over a device-side list of pixels (ptl_renderer_draw_adaptive)
     o.refine_slices_entry = on(PTL_FLAG_REFINE_SLICES);  // the slices entry plus the list-driven entry over slices (ptl_renderer_draw_slices_adaptive)
     o.slices_entry = o.slices_entry || o.refine_slices_entry;
+    o.passes = on(PTL_FLAG_PASSES);  // a 16-byte record per pixel beside the colour: nearest depth, trips, how the paths ended (ptl_renderer_draw_passes)
     o.bound_snippets = on(PTL_FLAG_BOUNDED_SNIPPETS);  // scene_intersect first, its distance bounds the intersection-material snippets (opt-in: measured, no gain)
     // Round 6: the first-trip forms -- a second copy of scene_intersect and of every intersection-material snippet for the trip on which all rays of a
     // wave still start at the camera -- are OPT-IN IN THE UN-SPECIALISED KERNEL (bit 24, PTL_FLAG_KEEP_TRANSFORM_DODGES) and stay the default of the
@@ -399,16 +400,26 @@ int rebuild_now(ptl_renderer* r, Rebuild why, char* log, size_t log_cap) {
     return PTL_OK;
 }
 
-// Option "specialize_static": clip-constant specialisation (flags bit 3) on or off for what follows.
+// Options that are flag bits of the build: "specialize_static" (clip-constant specialisation, bit 3) and "passes" (pass records, bit 30), on or
+// off for what follows.  A combination the generator refuses (passes with anaglyph or a refine entry) leaves the renderer as it was.
 // (with PTL_FLAG_ASYNC_REJIT a worker may be compiling for the old flags: rebuilt synchronously like at creation)
-int set_specialize_static(ptl_renderer* r, bool on) {
-    unsigned want = on ? (r->flags | PTL_FLAG_SPECIALIZE_STATIC) : (r->flags & ~PTL_FLAG_SPECIALIZE_STATIC);
-    if (want == r->flags) return PTL_OK;
+int set_build_flag(ptl_renderer* r, unsigned bit, bool on) {
+    const unsigned before = r->flags, want = on ? (before | bit) : (before & ~bit);
+    if (want == before) return PTL_OK;
     return guarded([&] {
         r->flags = want;
-        r->builds.stage.keep_dynamic.clear();
-        int rc = rebuild_now(r, Rebuild::quiet, nullptr, 0);
-        if (rc != PTL_OK) return rc;
+        if (bit == PTL_FLAG_SPECIALIZE_STATIC) r->builds.stage.keep_dynamic.clear();
+        int rc = PTL_OK;
+        try {
+            rc = rebuild_now(r, Rebuild::quiet, nullptr, 0);
+        } catch (...) {
+            r->flags = before;
+            throw;
+        }
+        if (rc != PTL_OK) {
+            r->flags = before;
+            return rc;
+        }
         ++r->options_version;
         return (int)PTL_OK;
     });

@@ -168,6 +168,35 @@ extern "C" int ptl_renderer_draw_slices(ptl_renderer* r, const ptl_frame* frame,
     });
 }
 
+// The same batch with the slices' pass records (renderers with PTL_FLAG_PASSES / option "passes"): slice z at out_passes + z * slice_pixels records.
+extern "C" int ptl_renderer_draw_slices_passes(ptl_renderer* r, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, void* out_passes, size_t passes_bytes,
+                                               unsigned long long slice_pixels, void* stream, float* elapsed_ms) {
+    if (!r || !frame || n < 1 || n > 16) return PTL_ERR_INVALID;
+    if (!out_passes || passes_bytes < sizeof(ptl_pass_record) * (unsigned long long)(n - 1) * slice_pixels) return PTL_ERR_INVALID;  // (layer 1 checks the last run's share)
+    return guarded([&] {
+        if (!r->slices.all_staged(n)) {
+            set_last_error("ptl_renderer_draw_slices_passes: slices 0 .. n-1 are not all staged (ptl_renderer_stage_slice) since the last launch");
+            return (int)PTL_ERR_INVALID;
+        }
+        if (int jrc = r->lanes.join(stream); jrc != PTL_OK) return jrc;
+        float total_ms = 0.0f;
+        const int rc = r->slices.for_each_run(n, [&](ptl_kernel* k, int j0, int j1) {
+            int rc = r->slices.stage_run(k, j0, j1);
+            float ms = 0.0f;
+            void* out8 = out_rgba8 ? static_cast<unsigned char*>(out_rgba8) + (size_t)j0 * slice_pixels * 4 : nullptr;
+            void* out32 = out_rgba32f ? static_cast<float*>(out_rgba32f) + (size_t)j0 * slice_pixels * 4 : nullptr;
+            void* outp = static_cast<ptl_pass_record*>(out_passes) + (size_t)j0 * slice_pixels;
+            const size_t left = passes_bytes - sizeof(ptl_pass_record) * (size_t)j0 * slice_pixels;
+            if (rc == PTL_OK) rc = ptl_kernel_render_slices_passes(k, frame, j1 - j0, out8, out32, outp, left, slice_pixels, stream, elapsed_ms ? &ms : nullptr);
+            total_ms += ms;
+            return rc;
+        });
+        if (elapsed_ms) *elapsed_ms = total_ms;
+        r->slices.drop();
+        return rc;
+    });
+}
+
 extern "C" int ptl_renderer_join(ptl_renderer* r, void* stream) {
     if (!r) return PTL_ERR_INVALID;
     return guarded([&] { return r->lanes.join(stream); });
@@ -239,6 +268,19 @@ extern "C" int ptl_renderer_draw(ptl_renderer* r, const ptl_frame* frame, void* 
         // (a timed or counting draw, and every draw of a renderer without lanes: on the caller's stream, behind what the lanes still hold)
         if (int jrc = r->lanes.join(stream); jrc != PTL_OK) return jrc;
         return ptl_kernel_render(r->builds.kernel, frame, out_rgba8, out_rgba32f, segments, stream, elapsed_ms);
+    });
+}
+// A draw with the pass records (renderers with PTL_FLAG_PASSES / option "passes"): on the caller's stream behind what the lanes still hold,
+// like a timed draw.  Layer 1 refuses a kernel without the records and a buffer that is too small.
+extern "C" int ptl_renderer_draw_passes(ptl_renderer* r, const ptl_frame* frame, void* out_rgba8, void* out_rgba32f, void* out_passes, size_t passes_bytes, void* segments,
+                                        void* stream, float* elapsed_ms) {
+    if (!r || !frame) return PTL_ERR_INVALID;
+    return guarded([&] {
+        int rc = prepare_draw(r, frame);
+        if (rc < 0) return rc;
+        if (rc = check_affine_if_asked(r, frame); rc < 0) return rc;
+        if (int jrc = r->lanes.join(stream); jrc != PTL_OK) return jrc;
+        return ptl_kernel_render_passes(r->builds.kernel, frame, out_rgba8, out_rgba32f, out_passes, passes_bytes, segments, stream, elapsed_ms);
     });
 }
 // ---- adaptive anti-aliasing (include/portal_amd.h has the contract) ------------------------------------------------------------------
