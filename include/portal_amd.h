@@ -888,10 +888,16 @@ int ptl_strstore_current_line(const ptl_strstore* s);
 int ptl_strstore_range(const ptl_strstore* s, const char* kind, const char* name, int* start, int* end);
 int ptl_strstore_get_identifier(const ptl_strstore* s, int line, char* kind, size_t kind_cap, char* name, size_t name_cap,
                                 int* local_line);
+/* The conditional sections of a template (`//%if NAME` or `//%if !NAME`, `//%else`, `//%end`, each on a line of its own, nesting) resolved for
+ * the n names given: malloc'ed (ptl_free).  NULL + ptl_last_error() for a section left open, an else / end without an if, a second else, or a
+ * name -- in the text or among `names` -- other than slices, passes, refine, refine_slices. */
+char* ptl_select_sections(const char* text, const char* const* names, int n);
 
 /* The fixed device sources embedded in the library: "glsl" (types + numerics contract),
  * "library" (prelude), "trace" (kernel template), "entry" (launchable entry points),
  * "refine_entry" (the list-driven render entry of PTL_FLAG_REFINE builds), "refine_slices_entry" (the one over slices of PTL_FLAG_REFINE_SLICES builds).
+ * "library" and "entry" are the texts of a build without PTL_FLAG_SLICES / _PASSES / _REFINE / _REFINE_SLICES (their conditional sections
+ * resolved for no name, no marker left); "trace" is the template as embedded, its conditional sections and slot markers included.
  * Returns NULL for an unknown name.  Lets a caller write its own kernel against the same
  * conventions and hand it to ptl_kernel_compile. */
 const char* ptl_device_source(const char* which);

@@ -248,6 +248,7 @@ def _load() -> C.CDLL:
         "ptl_strstore_current_line": (ci, [vp]),
         "ptl_strstore_range": (ci, [vp, cp, cp, P(ci), P(ci)]),
         "ptl_strstore_get_identifier": (ci, [vp, ci, cp, cs, cp, cs, P(ci)]),
+        "ptl_select_sections": (vp, [cp, P(cp), ci]),
         "ptl_device_source": (cp, [cp]),
         "ptl_translate_glsl": (vp, [cp]),
         "ptl_translate_library_glsl": (vp, [cp]),
@@ -917,6 +918,18 @@ def device_source(which: str) -> str:
     if p is None:
         raise PortalError(f"no device source `{which}`")
     return p.decode("utf-8")
+
+
+def select_sections(text: str, names=()) -> str:
+    """The conditional sections of a template (``//%if NAME``, ``//%else``, ``//%end``) resolved for ``names``; PortalError where the engine refuses the text."""
+    arr = (C.c_char_p * len(names))(*[n.encode() for n in names])
+    p = lib().ptl_select_sections(text.encode("utf-8"), arr, len(names))
+    if not p:
+        raise PortalError(_err())
+    try:
+        return C.string_at(p).decode("utf-8")
+    finally:
+        lib().ptl_free(p)
 
 
 def deinterleave_rows(shard: np.ndarray, frame: Frame, full: np.ndarray) -> None:

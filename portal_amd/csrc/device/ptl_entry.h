@@ -26,17 +26,36 @@
 // -DPTL_TELEPORT_MODULE the render entry; the prologue entry is in both.  Without either define the module has all three.
 #if !defined(PTL_TELEPORT_MODULE)
 extern "C" __global__ void PTL_LAUNCH_BOUNDS
+//%if slices
+// (slices entry: another name -- layer 1 tells the two kinds of module apart by it -- and in front the buffer of uniform blocks, one per
+// blockIdx.z, and the pixels of one slice's frame)
+ptl_render_slices_kernel(const glsl::ptl_uniform_block* __restrict__ ptl_slices, unsigned long long ptl_slice_pixels, unsigned int* __restrict__ out_rgba8,
+//%else
 ptl_render_kernel(unsigned int* __restrict__ out_rgba8,   // packed rows of this shard, or null
+//%end
                   float* __restrict__ out_rgba32f,        // same, 4 floats per pixel, or null
                   int width, int height,                   // full frame size
                   int rb_phase, int rb_stride,             // row-block interleave
                   unsigned long long* __restrict__ segment_counter,
+//%if passes
+                  int in_place,                            // 1: out_* address the full frame (maybe a peer GPU's), rows go where they belong
+                  glsl::ptl_pass_record* __restrict__ out_passes) {  // (trace passes) a record per pixel, addressed like out_rgba32f, or null
+//%else
                   int in_place) {                          // 1: out_* address the full frame (maybe a peer GPU's), rows go where they belong
+//%end
 #ifndef PTL_DIRECT_STORE
     __shared__ unsigned int tile[8][32 + 1];
 #endif
     const int t = (int)threadIdx.x;
     const int wave = t >> 6, lane = t & 63;
+//%if slices
+    if (out_rgba8 != nullptr) out_rgba8 += (unsigned long long)blockIdx.z * ptl_slice_pixels;      // slice z of the launch: its own frame ...
+    if (out_rgba32f != nullptr) out_rgba32f += 4ull * blockIdx.z * ptl_slice_pixels;
+//%if passes
+    if (out_passes != nullptr) out_passes += (unsigned long long)blockIdx.z * ptl_slice_pixels;
+//%end
+    const glsl::ptl_uniform_block* const ptl_slice_block = ptl_slices + blockIdx.z;                // ... and its own uniforms
+//%end
     const int lx = wave * 8 + (lane & 7);
     const int ly = lane >> 3;
 #ifdef PTL_XCD_SWIZZLE
@@ -79,10 +98,26 @@ ptl_render_kernel(unsigned int* __restrict__ out_rgba8,   // packed rows of this
     }
 #endif
     glsl::vec4 c = glsl::vec4(0.0f);
+//%if passes
+    glsl::ptl_pass_record ptl_rec = {__builtin_inff(), 0u, 0u, 0u};
+//%if slices
+    if (live) c = glsl::shade_pixel_in(glsl::vec2((float)px + 0.5f, (float)py + 0.5f), ptl_slice_block, &ptl_rec);
+//%else
+    if (live) c = glsl::shade_pixel(glsl::vec2((float)px + 0.5f, (float)py + 0.5f), &ptl_rec);
+//%end
+//%else
+//%if slices
+    if (live) c = glsl::shade_pixel_in(glsl::vec2((float)px + 0.5f, (float)py + 0.5f), ptl_slice_block);
+//%else
     if (live) c = glsl::shade_pixel(glsl::vec2((float)px + 0.5f, (float)py + 0.5f));
+//%end
+//%end
 
     const int out_block = in_place ? rb_phase + local_block * rb_stride : local_block;  // wave-uniform
     const long shard_row = (long)out_block * 8 + ly;
+//%if passes
+    if (out_passes != nullptr && live) out_passes[shard_row * width + px] = ptl_rec;  // a 16-byte store per lane: 8 lanes = one 128 B line per tile row
+//%end
     if (out_rgba32f != nullptr && live) {
         float4 v = make_float4(c.x, c.y, c.z, c.w);
         *reinterpret_cast<float4*>(out_rgba32f + 4 * (shard_row * width + px)) = v;  // 8 lanes x 16 B = one 128 B line per tile row
@@ -156,7 +191,14 @@ extern "C" __global__ void __launch_bounds__(64) ptl_derive_kernel(glsl::ptl_uni
 }
 #endif
 
-#else  // host build of the same source (oracle/host_build): rows [row_begin, row_end) of the frame
+//%if slices
+// (slices entry) the prologue of a batch: one workgroup per slice fills the derived members of that slice's block
+extern "C" __global__ void __launch_bounds__(64) ptl_derive_slices_kernel(glsl::ptl_uniform_block* blocks) {
+    if (threadIdx.x == 0) glsl::derive_uniforms_in(blocks + blockIdx.x);
+}
+
+//%end
+//%refine_entry//%#else  // host build of the same source (oracle/host_build): rows [row_begin, row_end) of the frame
 
 #include <cstdint>
 #include <cstring>
@@ -180,7 +222,12 @@ extern "C" void ptl_host_teleport(float*) {}
 // Renders the listed pixel rows x columns [col_begin, col_end) of a width x height frame into
 // out_* (output row i = rows[i]) with `threads` OpenMP threads.  Returns the number of
 // bounce-loop trips when compiled with PTL_COUNT_SEGMENTS, else 0.
+//%if passes
+// (trace passes: the body of two entries at the end of this file, the one above and its sibling with the pixels' records)
+static unsigned long long ptl_host_render_both(glsl::ptl_pass_record* out_passes, uint8_t* out_rgba8, float* out_rgba32f, int width, int height,
+//%else
 extern "C" unsigned long long ptl_host_render(uint8_t* out_rgba8, float* out_rgba32f, int width, int height,
+//%end
                                               const int* rows, int n_rows, int col_begin, int col_end, int threads) {
     unsigned long long segments = 0;
     (void)width;
@@ -197,8 +244,16 @@ extern "C" unsigned long long ptl_host_render(uint8_t* out_rgba8, float* out_rgb
         ptl_segments_tls = 0;
 #endif
         for (int px = col_begin; px < col_end; ++px) {
+//%if passes
+            glsl::ptl_pass_record ptl_rec = {__builtin_inff(), 0u, 0u, 0u};
+            glsl::vec4 c = glsl::shade_pixel(glsl::vec2((float)px + 0.5f, (float)py + 0.5f), &ptl_rec);
+//%else
             glsl::vec4 c = glsl::shade_pixel(glsl::vec2((float)px + 0.5f, (float)py + 0.5f));
+//%end
             long idx = (long)i * cols + (px - col_begin);
+//%if passes
+            if (out_passes) out_passes[idx] = ptl_rec;
+//%end
             if (out_rgba32f) {
                 float v[4] = {c.x, c.y, c.z, c.w};
                 std::memcpy(out_rgba32f + 4 * idx, v, sizeof v);
@@ -215,4 +270,15 @@ extern "C" unsigned long long ptl_host_render(uint8_t* out_rgba8, float* out_rgb
     return segments;
 }
 
+//%if passes
+extern "C" unsigned long long ptl_host_render(uint8_t* out_rgba8, float* out_rgba32f, int width, int height, const int* rows, int n_rows, int col_begin, int col_end, int threads) {
+    return ptl_host_render_both(nullptr, out_rgba8, out_rgba32f, width, height, rows, n_rows, col_begin, col_end, threads);
+}
+// ... and the same rows with the pixels' pass records (16 bytes each, 16-byte aligned, laid out like out_rgba32f)
+extern "C" unsigned long long ptl_host_render_passes(uint8_t* out_rgba8, float* out_rgba32f, void* out_passes, int width, int height, const int* rows, int n_rows, int col_begin,
+                                                     int col_end, int threads) {
+    return ptl_host_render_both(static_cast<glsl::ptl_pass_record*>(out_passes), out_rgba8, out_rgba32f, width, height, rows, n_rows, col_begin, col_end, threads);
+}
+
+//%end
 #endif

@@ -10,7 +10,11 @@
 // _angle_color_disable, _offset_after_material, _black_border_disable defined by the
 // generated uniform block (codegen.cpp).
 
+//%if slices
+// (slices entry: this text stands inside the tracer struct, as member functions -- no namespace; one line for one line, the scene's lines keep their numbers)
+//%else
 namespace glsl {
+//%end
 
 #define PI acos(-1.0f)            /* src/library.glsl:15 */
 #define PI2 ptl_div(acos(-1.0f), 2.0f)  /* src/library.glsl:16 */
@@ -544,4 +548,6 @@ struct SceneIntersectionWithMaterial {
     MaterialProcessing material;
 };
 
+//%if !slices
 }  // namespace glsl
+//%end

@@ -26,7 +26,14 @@ namespace glsl {
 // where hipcc would otherwise keep hundreds of SGPRs live and spill them to VGPR lanes
 // (measured: triple_portal 4K 3.36 ms -> 1.2 ms, profiles/r01/variants5_uniform_reload.jsonl).
 struct ptl_tracer {
+//%if slices
+    const ptl_uniform_block* ptl_ubp; const ptl_uniform_block* ptl_home;  // (slices entry) where the block of THIS launch lives: PTL_RELAUNDER starts from there
+//%else
     const ptl_uniform_block* ptl_ubp;
+//%end
+//%if passes
+    ptl_pass_record ptl_pass = ptl_pass_record{__builtin_inff(), 0u, 0u, 0u};  // (trace passes) the record of the pixel this tracer shades
+//%end
 #if !(PTL_DEVICE_BUILD && (defined(PTL_UNIFORMS_IN_LDS) || defined(PTL_UNIFORM_RELOAD) || defined(PTL_UNIFORM_HOIST)))
 #undef PTL_U
 #define PTL_U (*ptl_ubp)
@@ -42,7 +49,11 @@ struct ptl_tracer {
     do {                                                  \
         int ptl_zero = 0;                                 \
         asm volatile("" : "+s"(ptl_zero));                \
+//%if slices
+        ptl_ubp = reinterpret_cast<const ptl_uniform_block*>(reinterpret_cast<const char*>(ptl_home) + ptl_zero); \
+//%else
         ptl_ubp = reinterpret_cast<const ptl_uniform_block*>(reinterpret_cast<const char*>(&ptl_u) + ptl_zero); \
+//%end
     } while (0)
 #else
 #define PTL_RELAUNDER()                                   \
@@ -62,6 +73,9 @@ struct ptl_tracer {
 #define PTL_PIXEL_RELAUNDER() PTL_RELAUNDER()
 #endif
 
+//%if slices
+//%prelude_in_tracer//%
+//%end
 // Scene snippets are plain GLSL functions without HIP attributes: let clang treat every
 // function declared in this region as __host__ __device__.
 #if PTL_DEVICE_BUILD
@@ -227,7 +241,29 @@ struct RayTraceResult {
     vec3 color;
     float depth;
     bool has_depth;
+//%if passes
+    // (trace passes) how many trips the path took and how it ended: a result nobody overwrote is a path the loop ran out on
+    unsigned int trips;
+    int end_class;  // PTL_PATH_*
+//%end
 };
+//%if passes
+enum { PTL_PATH_EXHAUSTED = 0, PTL_PATH_FINAL = 1, PTL_PATH_ESCAPED = 2 };
+// one 16-bit count of a record word, saturating
+PTL_FN static unsigned int ptl_pass_bump(unsigned int word, int shift) { return ((word >> shift) & 0xffffu) != 0xffffu ? word + (1u << shift) : word; }
+// a finished path into the pixel's record (`<` keeps a NaN depth out of the minimum)
+PTL_FN void ptl_pass_account(const RayTraceResult& path) {
+    ptl_pass.trips += path.trips;
+    if (path.end_class == PTL_PATH_FINAL) {
+        ptl_pass.depth_near = path.depth < ptl_pass.depth_near ? path.depth : ptl_pass.depth_near;
+        ptl_pass.final_escaped = ptl_pass_bump(ptl_pass.final_escaped, 0);
+    } else if (path.end_class == PTL_PATH_ESCAPED) {
+        ptl_pass.final_escaped = ptl_pass_bump(ptl_pass.final_escaped, 16);
+    } else {
+        ptl_pass.exhausted_outside = ptl_pass_bump(ptl_pass.exhausted_outside, 0);
+    }
+}
+//%end
 
 PTL_FN float normalize_depth_value(float depth) {  // frag.glsl:80-84
     float depth_min = min(_depth_map_min, _depth_map_max);
@@ -315,7 +351,11 @@ PTL_FN bool trace_segment(Ray& r, vec3& current_color, float& all_t, float camer
     }
 
     if (!(i.hit.hit || i2.scene.hit.hit)) {  // escaped the scene
+//%if passes
+        out = r.in_subspace ? RayTraceResult{color(0.0f, 0.0f, 0.0f), 0.0f, false, 0u, PTL_PATH_ESCAPED} : RayTraceResult{current_color * not_found_color, 0.0f, false, 0u, PTL_PATH_ESCAPED};
+//%else
         out = r.in_subspace ? RayTraceResult{color(0.0f, 0.0f, 0.0f), 0.0f, false} : RayTraceResult{current_color * not_found_color, 0.0f, false};
+//%end
         return true;
     }
     current_color *= m.mul_to_color;
@@ -324,10 +364,18 @@ PTL_FN bool trace_segment(Ray& r, vec3& current_color, float& all_t, float camer
         if (all_t > _t_start * camera_scale && _darken_by_distance == 1) {  // fade to black with distance
             if (all_t > _t_end * camera_scale) all_t = _t_end * camera_scale;
             float gray_t = ptl_div(ptl_div(all_t - _t_start * camera_scale, _t_end - _t_start), camera_scale);
+//%if passes
+            out = RayTraceResult{color(0.0f, 0.0f, 0.0f) * sqr(sqr(gray_t)) + current_color * sqr(sqr(1.0f - gray_t)), depth, true, 0u, PTL_PATH_FINAL};
+//%else
             out = RayTraceResult{color(0.0f, 0.0f, 0.0f) * sqr(sqr(gray_t)) + current_color * sqr(sqr(1.0f - gray_t)), depth, true};
+//%end
             return true;
         }
+//%if passes
+        out = RayTraceResult{current_color, depth, true, 0u, PTL_PATH_FINAL};
+//%else
         out = RayTraceResult{current_color, depth, true};
+//%end
         return true;
     }
     r = m.new_ray;
@@ -349,6 +397,9 @@ PTL_FN RayTraceResult ray_tracing(Ray r, float camera_scale) {
     vec3 current_color = vec3(1.0f);
     float all_t = 0.0f;
     RayTraceResult result = RayTraceResult{color(0.0f, 0.0f, 0.0f), 0.0f, false};  // depth exhausted
+//%if passes
+    unsigned int ptl_path_trips = 0u;  // (trace passes) counted where PTL_COUNT_SEGMENT() counts, handed out with the result
+//%end
 #if PTL_DEVICE_BUILD && !defined(PTL_NO_WAVE_LOOP)
     bool alive = true;
 #ifdef PTL_FIRST_TRIP
@@ -362,6 +413,9 @@ PTL_FN RayTraceResult ray_tracing(Ray r, float camera_scale) {
     if (_ray_tracing_depth > 0) {
         PTL_RELAUNDER();
         PTL_COUNT_SEGMENT();
+//%if passes
+        ++ptl_path_trips;
+//%end
         alive = !trace_segment(r, current_color, all_t, camera_scale, not_found_color, result, first_form);
         j = 1;
     }
@@ -370,6 +424,9 @@ PTL_FN RayTraceResult ray_tracing(Ray r, float camera_scale) {
         PTL_RELAUNDER();
         if (alive) {
             PTL_COUNT_SEGMENT();
+//%if passes
+            ++ptl_path_trips;
+//%end
             alive = !trace_segment(r, current_color, all_t, camera_scale, not_found_color, result, false);
         }
     }
@@ -379,6 +436,9 @@ PTL_FN RayTraceResult ray_tracing(Ray r, float camera_scale) {
         PTL_RELAUNDER();
         if (alive) {
             PTL_COUNT_SEGMENT();
+//%if passes
+            ++ptl_path_trips;
+//%end
 #ifdef PTL_FIRST_TRIP
             alive = !trace_segment(r, current_color, all_t, camera_scale, not_found_color, result, j == 0 && first_form);
 #else
@@ -391,14 +451,29 @@ PTL_FN RayTraceResult ray_tracing(Ray r, float camera_scale) {
     for (int j = 0; j < _ray_tracing_depth; j++) {
         PTL_RELAUNDER();
         PTL_COUNT_SEGMENT();
+//%if passes
+        ++ptl_path_trips;
+//%end
 #ifdef PTL_FIRST_TRIP
+//%if passes
+        if (trace_segment(r, current_color, all_t, camera_scale, not_found_color, result, j == 0 && origin_is_camera)) { result.trips = ptl_path_trips; return result; }
+//%else
         if (trace_segment(r, current_color, all_t, camera_scale, not_found_color, result, j == 0 && origin_is_camera)) return result;
+//%end
 #else
+//%if passes
+        if (trace_segment(r, current_color, all_t, camera_scale, not_found_color, result)) { result.trips = ptl_path_trips; return result; }
+//%else
         if (trace_segment(r, current_color, all_t, camera_scale, not_found_color, result)) return result;
+//%end
 #endif
     }
 #endif
+//%if passes
+    { result.trips = ptl_path_trips; return result; }
+//%else
     return result;
+//%end
 }
 
 // --- camera teleportation -------------------------------------------- src/frag.glsl:199-257
@@ -585,13 +660,22 @@ PTL_FN vec3 get_color2(vec2 image_position, const mat4& camera_matrix, bool in_s
             rx = ax;
             ry = ptl_div(ax, 2.0f);
         }
+//%if passes
+        // (trace passes: a sample in the bars of a 360 / 180 degree frame traces nothing; the record books it as `outside`)
+        if (abs(image_position.x) > rx || abs(image_position.y) > ry) { ptl_pass.exhausted_outside = ptl_pass_bump(ptl_pass.exhausted_outside, 16); return vec3(0.0f); }
+//%else
         if (abs(image_position.x) > rx || abs(image_position.y) > ry) return vec3(0.0f);
+//%end
         float yaw = ptl_div(image_position.x, rx) * Pi;
         float pitch = ptl_div(image_position.y, ry) * Pi05;
         vec3 dir_local = vec3(sin(yaw) * cos(pitch), sin(pitch), cos(yaw) * cos(pitch));
         d = normalize(camera_times(camera_matrix, which_eye, vec4(dir_local, 0.0f)));
     } else if (_use_180_camera == 1) {  // VR180 front hemisphere
+//%if passes
+        if (abs(image_position.x) > 1.0f || abs(image_position.y) > 1.0f) { ptl_pass.exhausted_outside = ptl_pass_bump(ptl_pass.exhausted_outside, 16); return vec3(0.0f); }
+//%else
         if (abs(image_position.x) > 1.0f || abs(image_position.y) > 1.0f) return vec3(0.0f);
+//%end
         float yaw = image_position.x * Pi05;
         float pitch = image_position.y * Pi05;
         vec3 dir_local = vec3(sin(yaw) * cos(pitch), sin(pitch), cos(yaw) * cos(pitch));
@@ -610,6 +694,9 @@ PTL_FN vec3 get_color2(vec2 image_position, const mat4& camera_matrix, bool in_s
 #else
     RayTraceResult trace = ray_tracing(Ray{o, d, 1.0f, in_subspace}, camera_scale);
 #endif
+//%if passes
+    ptl_pass_account(trace);
+//%end
     if (_draw_depth_map == 1) {
         if (trace.has_depth) return sample_depth_gradient(trace.depth);
         return vec3(0.0f);
@@ -713,18 +800,61 @@ PTL_FN vec4 shade_pixel(vec2 position) {
 #undef PTL_U
 #define PTL_U ptl_u
 
+//%if passes
+// (trace passes: the free functions the entries call hand the pixel's record out)
+PTL_FN vec4 shade_pixel(vec2 position, ptl_pass_record* ptl_rec = nullptr) {
+//%else
 PTL_FN vec4 shade_pixel(vec2 position) {
+//%end
+//%if slices
+    ptl_tracer t{&ptl_u, &ptl_u};
+//%else
     ptl_tracer t{&ptl_u};
+//%end
+//%if passes
+    const vec4 ptl_c = t.shade_pixel(position);
+    if (ptl_rec) *ptl_rec = t.ptl_pass;
+    return ptl_c;
+//%else
     return t.shade_pixel(position);
+//%end
 }
 PTL_FN void teleport_external_ray_entry(float* out6) {
+//%if slices
+    ptl_tracer t{&ptl_u, &ptl_u};
+//%else
     ptl_tracer t{&ptl_u};
+//%end
     t.teleport_external_ray_entry(out6);
 }
 PTL_FN void derive_uniforms(ptl_uniform_block* block) {
+//%if slices
+    ptl_tracer t{&ptl_u, &ptl_u};
+//%else
     ptl_tracer t{&ptl_u};
+//%end
     t.derive(block);
 }
+//%if slices
+// (slices entry: the block of a slice is read where it lies in the launch's buffer, and its derived members are written there)
+//%if passes
+PTL_FN vec4 shade_pixel_in(vec2 position, const ptl_uniform_block* home, ptl_pass_record* ptl_rec = nullptr) {
+    ptl_tracer t{home, home};
+    const vec4 ptl_c = t.shade_pixel(position);
+    if (ptl_rec) *ptl_rec = t.ptl_pass;
+    return ptl_c;
+}
+//%else
+PTL_FN vec4 shade_pixel_in(vec2 position, const ptl_uniform_block* home) {
+    ptl_tracer t{home, home};
+    return t.shade_pixel(position);
+}
+//%end
+PTL_FN void derive_uniforms_in(ptl_uniform_block* block) {
+    ptl_tracer t{block, block};
+    t.derive(block);
+}
+//%end
 
 // GL fixed-point conversion of one channel: clamp to [0,1], scale, round to nearest.
 PTL_FN unsigned int unorm8(float v) {

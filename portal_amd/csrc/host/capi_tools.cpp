@@ -1,5 +1,6 @@
 // capi_tools.cpp -- entry points that are no part of a renderer: hooks for the tests and the tools into the template engine, the GLSL passes,
 // the RON writer, the formula evaluator, the binary64 matrix primitives and the embedded device sources.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -91,6 +92,19 @@ extern "C" ptl_strstore* ptl_apply_template(const char* tmpl, const char* const*
         return nullptr;
     }
 }
+// select_sections on a text of the caller's: malloc'd (ptl_free), or NULL + ptl_last_error() where the engine throws
+extern "C" char* ptl_select_sections(const char* text, const char* const* names, int n) {
+    if (!text || (n > 0 && !names)) return nullptr;
+    try {
+        const std::string out = select_sections(text, std::set<std::string>(names, names + std::max(n, 0)));
+        char* p = (char*)std::malloc(out.size() + 1);
+        std::memcpy(p, out.c_str(), out.size() + 1);
+        return p;
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return nullptr;
+    }
+}
 extern "C" const char* ptl_strstore_text(const ptl_strstore* s) { return s ? s->s.storage.c_str() : ""; }
 extern "C" int ptl_strstore_current_line(const ptl_strstore* s) { return s ? s->s.current_line_no : 0; }
 extern "C" int ptl_strstore_range(const ptl_strstore* s, const char* kind, const char* name, int* start, int* end) {
@@ -117,9 +131,9 @@ extern "C" const char* ptl_device_source(const char* which) {
     if (!which) return nullptr;
     std::string w = which;
     if (w == "glsl") return device_source_glsl();
-    if (w == "library") return device_source_library();
-    if (w == "trace") return device_source_trace_template();
-    if (w == "entry") return device_source_entry();
+    if (w == "library") return plain_library_source().c_str();  // (no section selected: what a hand-written kernel pastes in)
+    if (w == "trace") return device_source_trace_template();     // the template as embedded, conditional sections included
+    if (w == "entry") return plain_entry_source().c_str();      // (no section selected, the refine slot empty)
     if (w == "refine_entry") return device_source_refine_entry();
     if (w == "refine_slices_entry") return device_source_refine_slices_entry();
     return nullptr;

@@ -81,6 +81,55 @@ StringStorage apply_template(const std::string& tmpl, std::map<std::string, Stri
     return result;
 }
 
+const std::set<std::string>& section_names() {
+    static const std::set<std::string> known = {"slices", "passes", "refine", "refine_slices"};
+    return known;
+}
+
+std::string select_sections(const std::string& text, const std::set<std::string>& names) {
+    auto known = [](const std::string& name) {
+        if (!section_names().count(name)) throw std::logic_error("select_sections: unknown section name `" + name + "`");
+    };
+    for (const std::string& n : names) known(n);
+    struct Section {
+        bool outer, condition, in_else;  // the enclosing sections are selected; what `if` asked for held; behind its `else`
+    };
+    std::vector<Section> open;
+    bool selected = true;
+    std::string out;
+    for (size_t pos = 0, line_no = 1; pos < text.size(); ++line_no) {
+        const size_t eol = text.find('\n', pos);
+        const size_t next = eol == std::string::npos ? text.size() : eol + 1;
+        size_t b = pos, e = eol == std::string::npos ? text.size() : eol;
+        while (b < e && (text[b] == ' ' || text[b] == '\t')) ++b;
+        while (e > b && (text[e - 1] == ' ' || text[e - 1] == '\t' || text[e - 1] == '\r')) --e;
+        const std::string line = text.substr(b, e - b);
+        auto fail = [&](const char* what) { throw std::logic_error("select_sections: line " + std::to_string(line_no) + ": " + what); };
+        if (line.compare(0, 6, "//%if ") == 0) {
+            std::string name = line.substr(6);
+            const bool negated = !name.empty() && name[0] == '!';
+            if (negated) name.erase(0, 1);
+            known(name);
+            open.push_back({selected, (names.count(name) != 0) != negated, false});
+            selected = open.back().outer && open.back().condition;
+        } else if (line == "//%else") {
+            if (open.empty()) fail("`else` without an `if`");
+            if (open.back().in_else) fail("a second `else`");
+            open.back().in_else = true;
+            selected = open.back().outer && !open.back().condition;
+        } else if (line == "//%end") {
+            if (open.empty()) fail("`end` without an `if`");
+            selected = open.back().outer;
+            open.pop_back();
+        } else if (selected) {
+            out.append(text, pos, next - pos);
+        }
+        pos = next;
+    }
+    if (!open.empty()) throw std::logic_error("select_sections: " + std::to_string(open.size()) + " section(s) not closed");
+    return out;
+}
+
 // ------------------------------------------------------------------------------------------
 // helpers
 // ------------------------------------------------------------------------------------------
@@ -382,178 +431,6 @@ void functions_with_out_params(const std::string& glsl, std::set<std::string>& n
 //   transform(NAME, ...)                                  -> ptl_transform_m<PTL_MASK_NAME>(NAME, ...)        (scene snippets, Complex objects)
 //   ptl_plane_cull[_o] / plane_intersect_derived[_o](r, NAME, ...) -> ...<PTL_MASK_NAME>(r, NAME, ...)     (generated plane tests)
 // Every other use of the matrix (a product written out in a snippet, a copy into a local) keeps the full chain: correct, just not shortened.
-// KernelOptions::slices_entry: the render entry takes its uniform block from a buffer of blocks (one per slice of the launch, blockIdx.z).
-// Done on the finished text, so that every other build stays exactly what it was; each anchor must be there (the template is ours).
-static void apply_slices_entry(std::string& src) {
-    auto replace_all = [&](const std::string& from, const std::string& to, int at_least) {
-        int n = 0;
-        for (size_t pos = 0; (pos = src.find(from, pos)) != std::string::npos; pos += to.size()) {
-            src.replace(pos, from.size(), to);
-            ++n;
-        }
-        if (n < at_least) throw SceneError("slices entry: the kernel template no longer has `" + from.substr(0, 60) + "`");
-    };
-    // The prelude (device/ptl_library.h) sits in front of the tracer struct as free functions, and three of them read renderer uniforms
-    // (`_grid_disable`, `_angle_color_disable`, `_offset_after_material`) -- through the module's global block, which a slice does not use.
-    // It moves INTO the struct, in front of the scene snippets: as member functions they read the block the tracer points at, like
-    // everything else.  Same text, same line count behind it (the scene's own lines keep their numbers for diagnostics).
-    {
-        const std::string tail = "}  // namespace glsl\n";
-        const std::string anchor = "// Scene snippets are plain GLSL functions without HIP attributes: let clang treat every\n";
-        const size_t begin = src.find("// ptl_library.h -- the fixed prelude every generated portal kernel starts with.");
-        const size_t ns_open = begin == std::string::npos ? std::string::npos : src.find("namespace glsl {\n", begin);
-        // the prelude's own closing line is the one in front of the `namespace glsl {` the generator re-opens behind it
-        const size_t reopen = begin == std::string::npos ? std::string::npos : src.find("\n" + tail + "\nnamespace glsl {\n", begin);
-        const size_t into = src.find(anchor);
-        if (begin == std::string::npos || ns_open == std::string::npos || reopen == std::string::npos || into == std::string::npos || into < reopen)
-            throw SceneError("slices entry: the prelude is not where the kernel template used to put it");
-        const size_t lib_end = reopen + 1 + tail.size();  // one past the prelude's closing line
-        std::string lib = src.substr(begin, lib_end - begin);
-        lib.replace(lib.size() - tail.size(), tail.size() - 1, "");                   // a class body has no namespaces: the wrapper's two
-        lib.replace(ns_open - begin, std::string("namespace glsl {").size(), "");     // lines stay as empty lines
-        src.erase(begin, lib_end - begin);
-        src.insert(src.find(anchor), lib);  // cut N lines above, paste N lines above: every line from here on keeps its number
-    }
-    // the tracer remembers where the block of THIS launch lives; the once-per-trip re-laundering starts from there
-    replace_all("    const ptl_uniform_block* ptl_ubp;\n", "    const ptl_uniform_block* ptl_ubp; const ptl_uniform_block* ptl_home;\n", 1);  // (same line: the snippets keep their line numbers)
-    replace_all("reinterpret_cast<const char*>(&ptl_u) + ptl_zero", "reinterpret_cast<const char*>(ptl_home) + ptl_zero", 1);
-    replace_all("ptl_tracer t{&ptl_u};", "ptl_tracer t{&ptl_u, &ptl_u};", 3);
-    replace_all("PTL_FN void derive_uniforms(ptl_uniform_block* block) {\n    ptl_tracer t{&ptl_u, &ptl_u};\n    t.derive(block);\n}\n",
-                "PTL_FN void derive_uniforms(ptl_uniform_block* block) {\n    ptl_tracer t{&ptl_u, &ptl_u};\n    t.derive(block);\n}\n"
-                "// (slices entry: the block of a slice is read where it lies in the launch's buffer, and its derived members are written there)\n"
-                "PTL_FN vec4 shade_pixel_in(vec2 position, const ptl_uniform_block* home) {\n    ptl_tracer t{home, home};\n    return t.shade_pixel(position);\n}\n"
-                "PTL_FN void derive_uniforms_in(ptl_uniform_block* block) {\n    ptl_tracer t{block, block};\n    t.derive(block);\n}\n",
-                1);
-    // the entry: another name (layer 1 tells the two kinds of module apart by it), two more arguments, one slice per blockIdx.z
-    replace_all("ptl_render_kernel(unsigned int* __restrict__ out_rgba8,", "ptl_render_slices_kernel(const glsl::ptl_uniform_block* __restrict__ ptl_slices, unsigned long long ptl_slice_pixels, unsigned int* __restrict__ out_rgba8,", 1);
-    replace_all("    const int t = (int)threadIdx.x;\n    const int wave = t >> 6, lane = t & 63;\n",
-                "    const int t = (int)threadIdx.x;\n    const int wave = t >> 6, lane = t & 63;\n"
-                "    if (out_rgba8 != nullptr) out_rgba8 += (unsigned long long)blockIdx.z * ptl_slice_pixels;      // slice z of the launch: its own frame ...\n"
-                "    if (out_rgba32f != nullptr) out_rgba32f += 4ull * blockIdx.z * ptl_slice_pixels;\n"
-                "    const glsl::ptl_uniform_block* const ptl_slice_block = ptl_slices + blockIdx.z;                // ... and its own uniforms\n", 1);
-    replace_all("    if (live) c = glsl::shade_pixel(glsl::vec2((float)px + 0.5f, (float)py + 0.5f));\n\n    const int out_block",
-                "    if (live) c = glsl::shade_pixel_in(glsl::vec2((float)px + 0.5f, (float)py + 0.5f), ptl_slice_block);\n\n    const int out_block", 1);
-    // the prologue of a batch: one workgroup per slice fills the derived members of that slice's block
-    replace_all("#else  // host build of the same source (oracle/host_build): rows [row_begin, row_end) of the frame\n",
-                "extern \"C\" __global__ void __launch_bounds__(64) ptl_derive_slices_kernel(glsl::ptl_uniform_block* blocks) {\n"
-                "    if (threadIdx.x == 0) glsl::derive_uniforms_in(blocks + blockIdx.x);\n}\n\n"
-                "#else  // host build of the same source (oracle/host_build): rows [row_begin, row_end) of the frame\n", 1);
-}
-
-// KernelOptions::refine_entry: the list-driven render entry of the adaptive anti-aliasing, in front of the host half of ptl_entry.h.
-// (KernelOptions::refine_slices_entry: the same place, the entry over the slices of a batch -- behind `apply_slices_entry`, whose shade_pixel_in it calls)
-// `entry`: device/ptl_refine_common.h followed by the entry's own header, as ONE text (embed_sources.py joins them; device_source() hands it out).
-static void apply_refine_entry(std::string& src, const char* entry) {
-    const std::string anchor = "#else  // host build of the same source (oracle/host_build): rows [row_begin, row_end) of the frame\n";
-    const size_t at = src.find(anchor);
-    if (at == std::string::npos || src.find(anchor, at + 1) != std::string::npos) throw SceneError("refine entry: the kernel template no longer has its `#else  // host build` line");
-    src.insert(at, entry);
-}
-
-// KernelOptions::passes: the tracer fills a ptl_pass_record per pixel and the render entries store it through one more pointer, `out_passes`.
-// Done on the finished text, behind `apply_slices_entry` (whose entry it extends in the same way), so that every build without the option
-// stays exactly what it was; the record's type and `#define PTL_PASSES 1` come from emit_uniforms.  Each anchor must be there once.
-static void apply_passes(std::string& src) {
-    auto replace = [&](const std::string& from, const std::string& to, int times) {
-        int n = 0;
-        for (size_t pos = 0; (pos = src.find(from, pos)) != std::string::npos; pos += to.size()) {
-            src.replace(pos, from.size(), to);
-            ++n;
-        }
-        if (n != times) throw SceneError("trace passes: the kernel template no longer has `" + from.substr(0, 60) + "` " + std::to_string(times) + " time(s)");
-    };
-    auto replace_either = [&](const std::string& a, const std::string& a_to, const std::string& b, const std::string& b_to) {
-        if (src.find(a) != std::string::npos) replace(a, a_to, 1);
-        else replace(b, b_to, 1);
-    };
-    // -- the tracer: the pixel's record as a member (on the line of the uniform pointer: the snippets keep their line numbers) ...
-    replace_either("    const ptl_uniform_block* ptl_ubp;\n", "    const ptl_uniform_block* ptl_ubp; ptl_pass_record ptl_pass = ptl_pass_record{__builtin_inff(), 0u, 0u, 0u};\n",
-                   "    const ptl_uniform_block* ptl_ubp; const ptl_uniform_block* ptl_home;\n",
-                   "    const ptl_uniform_block* ptl_ubp; const ptl_uniform_block* ptl_home; ptl_pass_record ptl_pass = ptl_pass_record{__builtin_inff(), 0u, 0u, 0u};\n");
-    // ... a path's result says how many trips it took and how it ended (a result nobody overwrote is a path the loop ran out on) ...
-    replace("struct RayTraceResult {\n    vec3 color;\n    float depth;\n    bool has_depth;\n};\n",
-            "struct RayTraceResult {\n    vec3 color;\n    float depth;\n    bool has_depth;\n    unsigned int trips;\n    int end_class;  // PTL_PATH_*\n};\n"
-            "enum { PTL_PATH_EXHAUSTED = 0, PTL_PATH_FINAL = 1, PTL_PATH_ESCAPED = 2 };\n"
-            "// one 16-bit count of a record word, saturating\n"
-            "PTL_FN static unsigned int ptl_pass_bump(unsigned int word, int shift) { return ((word >> shift) & 0xffffu) != 0xffffu ? word + (1u << shift) : word; }\n"
-            "// a finished path into the pixel's record (`<` keeps a NaN depth out of the minimum)\n"
-            "PTL_FN void ptl_pass_account(const RayTraceResult& path) {\n"
-            "    ptl_pass.trips += path.trips;\n"
-            "    if (path.end_class == PTL_PATH_FINAL) {\n"
-            "        ptl_pass.depth_near = path.depth < ptl_pass.depth_near ? path.depth : ptl_pass.depth_near;\n"
-            "        ptl_pass.final_escaped = ptl_pass_bump(ptl_pass.final_escaped, 0);\n"
-            "    } else if (path.end_class == PTL_PATH_ESCAPED) {\n"
-            "        ptl_pass.final_escaped = ptl_pass_bump(ptl_pass.final_escaped, 16);\n"
-            "    } else {\n"
-            "        ptl_pass.exhausted_outside = ptl_pass_bump(ptl_pass.exhausted_outside, 0);\n"
-            "    }\n"
-            "}\n",
-            1);
-    replace("        out = r.in_subspace ? RayTraceResult{color(0.0f, 0.0f, 0.0f), 0.0f, false} : RayTraceResult{current_color * not_found_color, 0.0f, false};\n",
-            "        out = r.in_subspace ? RayTraceResult{color(0.0f, 0.0f, 0.0f), 0.0f, false, 0u, PTL_PATH_ESCAPED} : RayTraceResult{current_color * not_found_color, 0.0f, false, 0u, PTL_PATH_ESCAPED};\n", 1);
-    replace(", depth, true};\n", ", depth, true, 0u, PTL_PATH_FINAL};\n", 2);
-    // ... the bounce loop counts its trips where PTL_COUNT_SEGMENT() does and hands the count out with the result ...
-    {
-        const size_t begin = src.find("    RayTraceResult result = RayTraceResult{color(0.0f, 0.0f, 0.0f), 0.0f, false};  // depth exhausted\n");
-        const size_t end = src.find("// --- camera teleportation");
-        if (begin == std::string::npos || end == std::string::npos || end < begin) throw SceneError("trace passes: the kernel template no longer has its bounce loop where it was");
-        std::string loop = src.substr(begin, end - begin);
-        auto within = [&](const std::string& from, const std::string& to, int times) {
-            int n = 0;
-            for (size_t pos = 0; (pos = loop.find(from, pos)) != std::string::npos; pos += to.size()) {
-                loop.replace(pos, from.size(), to);
-                ++n;
-            }
-            if (n != times) throw SceneError("trace passes: the bounce loop no longer has `" + from + "` " + std::to_string(times) + " time(s)");
-        };
-        within("  // depth exhausted\n", "  // depth exhausted\n    unsigned int ptl_path_trips = 0u;\n", 1);
-        within("PTL_COUNT_SEGMENT();", "PTL_COUNT_SEGMENT(); ++ptl_path_trips;", 4);
-        within("return result;", "{ result.trips = ptl_path_trips; return result; }", 3);
-        src.replace(begin, end - begin, loop);
-    }
-    // ... and get_color2 books every sample: the traced ones by their result, the ones in the bars of a 360 / 180 degree frame as `outside`
-    replace("        if (abs(image_position.x) > rx || abs(image_position.y) > ry) return vec3(0.0f);\n",
-            "        if (abs(image_position.x) > rx || abs(image_position.y) > ry) { ptl_pass.exhausted_outside = ptl_pass_bump(ptl_pass.exhausted_outside, 16); return vec3(0.0f); }\n", 1);
-    replace("        if (abs(image_position.x) > 1.0f || abs(image_position.y) > 1.0f) return vec3(0.0f);\n",
-            "        if (abs(image_position.x) > 1.0f || abs(image_position.y) > 1.0f) { ptl_pass.exhausted_outside = ptl_pass_bump(ptl_pass.exhausted_outside, 16); return vec3(0.0f); }\n", 1);
-    replace("#endif\n    if (_draw_depth_map == 1) {\n", "#endif\n    ptl_pass_account(trace);\n    if (_draw_depth_map == 1) {\n", 1);
-    // -- the free functions the entries call hand the record out
-    replace_either("PTL_FN vec4 shade_pixel(vec2 position) {\n    ptl_tracer t{&ptl_u};\n    return t.shade_pixel(position);\n}\n",
-                   "PTL_FN vec4 shade_pixel(vec2 position, ptl_pass_record* ptl_rec = nullptr) {\n    ptl_tracer t{&ptl_u};\n    const vec4 ptl_c = t.shade_pixel(position);\n    if (ptl_rec) *ptl_rec = t.ptl_pass;\n    return ptl_c;\n}\n",
-                   "PTL_FN vec4 shade_pixel(vec2 position) {\n    ptl_tracer t{&ptl_u, &ptl_u};\n    return t.shade_pixel(position);\n}\n",
-                   "PTL_FN vec4 shade_pixel(vec2 position, ptl_pass_record* ptl_rec = nullptr) {\n    ptl_tracer t{&ptl_u, &ptl_u};\n    const vec4 ptl_c = t.shade_pixel(position);\n    if (ptl_rec) *ptl_rec = t.ptl_pass;\n    return ptl_c;\n}\n");
-    const bool sliced = src.find("PTL_FN vec4 shade_pixel_in(vec2 position, const ptl_uniform_block* home) {\n") != std::string::npos;
-    if (sliced)
-        replace("PTL_FN vec4 shade_pixel_in(vec2 position, const ptl_uniform_block* home) {\n    ptl_tracer t{home, home};\n    return t.shade_pixel(position);\n}\n",
-                "PTL_FN vec4 shade_pixel_in(vec2 position, const ptl_uniform_block* home, ptl_pass_record* ptl_rec = nullptr) {\n    ptl_tracer t{home, home};\n    const vec4 ptl_c = t.shade_pixel(position);\n"
-                "    if (ptl_rec) *ptl_rec = t.ptl_pass;\n    return ptl_c;\n}\n", 1);
-    // -- the render entry: one more pointer, addressed like out_rgba32f (a 16-byte store per lane: 8 lanes = one 128 B line per tile row)
-    replace("                  int in_place) {  ", "                  int in_place, glsl::ptl_pass_record* __restrict__ out_passes) {  ", 1);
-    if (sliced)
-        replace("    if (out_rgba32f != nullptr) out_rgba32f += 4ull * blockIdx.z * ptl_slice_pixels;\n",
-                "    if (out_rgba32f != nullptr) out_rgba32f += 4ull * blockIdx.z * ptl_slice_pixels;\n    if (out_passes != nullptr) out_passes += (unsigned long long)blockIdx.z * ptl_slice_pixels;\n", 1);
-    replace("    glsl::vec4 c = glsl::vec4(0.0f);\n    if (live) c = glsl::shade_pixel", "    glsl::vec4 c = glsl::vec4(0.0f);\n    glsl::ptl_pass_record ptl_rec = {__builtin_inff(), 0u, 0u, 0u};\n    if (live) c = glsl::shade_pixel", 1);
-    if (sliced) replace("(float)py + 0.5f), ptl_slice_block);\n\n    const int out_block", "(float)py + 0.5f), ptl_slice_block, &ptl_rec);\n\n    const int out_block", 1);
-    else replace("(float)py + 0.5f));\n\n    const int out_block", "(float)py + 0.5f), &ptl_rec);\n\n    const int out_block", 1);
-    replace("    if (out_rgba32f != nullptr && live) {\n        float4 v = make_float4(c.x, c.y, c.z, c.w);\n",
-            "    if (out_passes != nullptr && live) out_passes[shard_row * width + px] = ptl_rec;\n    if (out_rgba32f != nullptr && live) {\n        float4 v = make_float4(c.x, c.y, c.z, c.w);\n", 1);
-    // -- the host build: ptl_host_render becomes the body of two entries, the old one and its sibling with the records
-    replace("extern \"C\" unsigned long long ptl_host_render(uint8_t* out_rgba8, float* out_rgba32f, int width, int height,\n",
-            "static unsigned long long ptl_host_render_both(glsl::ptl_pass_record* out_passes, uint8_t* out_rgba8, float* out_rgba32f, int width, int height,\n", 1);
-    replace("            glsl::vec4 c = glsl::shade_pixel(glsl::vec2((float)px + 0.5f, (float)py + 0.5f));\n            long idx = (long)i * cols + (px - col_begin);\n",
-            "            glsl::ptl_pass_record ptl_rec = {__builtin_inff(), 0u, 0u, 0u};\n            glsl::vec4 c = glsl::shade_pixel(glsl::vec2((float)px + 0.5f, (float)py + 0.5f), &ptl_rec);\n"
-            "            long idx = (long)i * cols + (px - col_begin);\n            if (out_passes) out_passes[idx] = ptl_rec;\n", 1);
-    const size_t last = src.rfind("#endif\n");
-    if (last == std::string::npos) throw SceneError("trace passes: the kernel template no longer ends in `#endif`");
-    src.insert(last,
-               "extern \"C\" unsigned long long ptl_host_render(uint8_t* out_rgba8, float* out_rgba32f, int width, int height, const int* rows, int n_rows, int col_begin, int col_end, int threads) {\n"
-               "    return ptl_host_render_both(nullptr, out_rgba8, out_rgba32f, width, height, rows, n_rows, col_begin, col_end, threads);\n}\n"
-               "// ... and the same rows with the pixels' pass records (16 bytes each, 16-byte aligned, laid out like out_rgba32f)\n"
-               "extern \"C\" unsigned long long ptl_host_render_passes(uint8_t* out_rgba8, float* out_rgba32f, void* out_passes, int width, int height, const int* rows, int n_rows, int col_begin,\n"
-               "                                                     int col_end, int threads) {\n"
-               "    return ptl_host_render_both(static_cast<glsl::ptl_pass_record*>(out_passes), out_rgba8, out_rgba32f, width, height, rows, n_rows, col_begin, col_end, threads);\n}\n\n");
-}
-
 static void apply_zero_masks(std::string& src,const std::vector<std::pair<std::string, MatrixPattern>>& masked) {
     auto ident = [](char c) { return std::isalnum((unsigned char)c) || c == '_'; };
     for (auto& [name, mask] : masked) {
@@ -1372,6 +1249,18 @@ std::string translate_snippet(const BuildPlan& plan, const std::string& glsl, bo
 }
 std::string translate_snippet(const BuildPlan& plan, const SceneSnippet& s) { return translate_snippet(plan, s.glsl(), s.kind == SceneSnippet::Library); }
 
+// The entry variants of a build as the names the device files' sections go by (select_sections); the entry over slices brings the slices entry along.
+// (No section asks for one of the two refine names today -- their text is a whole file, and fills a slot: emit_refine_entry.)
+bool sliced(const KernelOptions& opts) { return opts.slices_entry || opts.refine_slices_entry; }
+std::set<std::string> variant_sections(const KernelOptions& opts) {
+    std::set<std::string> names;
+    if (sliced(opts)) names.insert("slices");
+    if (opts.passes) names.insert("passes");
+    if (opts.refine_entry) names.insert("refine");
+    if (opts.refine_slices_entry) names.insert("refine_slices");
+    return names;
+}
+
 StringStorage emit_uniforms(const Scene& scene, const BuildPlan& plan, const KernelOptions& opts) {
     StringStorage s;
     // (in the TEXT as well as among the defines: a renderer tells "nothing compiled in changed" by comparing sources, and a kernel with and
@@ -1531,9 +1420,10 @@ std::pair<StringStorage, StringStorage> emit_materials(const Scene& scene, const
     // The prelude needs the uniform accessors, so the library header goes after the uniform
     // block: splice it at the head of the `materials_defines` slot (order in the reference:
     // predefined library -> uniforms -> textures -> material defines -> library -> ...).
+    // (With the slices entry the prelude is in the tracer struct instead: emit_prelude_in_tracer.)
     StringStorage spliced;
     spliced.add_string("}  // namespace glsl\n");
-    spliced.add_string(device_source_library());
+    if (!sliced(opts)) spliced.add_string(plain_library_source());
     spliced.add_string("\nnamespace glsl {\n");
     spliced.add_string_storage(std::move(defines));
     return {std::move(processing), std::move(spliced)};
@@ -1707,6 +1597,25 @@ StringStorage emit_predefined_library(const Scene&, const BuildPlan&, const Kern
     return s;
 }
 
+// The slices entry: three functions of the prelude (device/ptl_library.h) read renderer uniforms (`_grid_disable`, `_angle_color_disable`,
+// `_offset_after_material`) -- as free functions through the module's global block, which a slice does not use.  So the prelude goes INTO
+// the tracer struct, in front of the scene snippets (the template's `prelude_in_tracer` slot): member functions read the block the tracer
+// points at, like everything else.  The same text without its namespace wrapper (its `slices` sections), as many lines as emit_materials leaves out.
+StringStorage emit_prelude_in_tracer(const Scene&, const BuildPlan&, const KernelOptions&) {
+    StringStorage s;
+    s.add_string(select_sections(device_source_library(), {"slices"}));
+    return s;
+}
+
+// The list-driven render entry of the adaptive anti-aliasing, for the slot in front of the host half of device/ptl_entry.h: device/ptl_refine_common.h
+// followed by the entry's own header, as ONE text (embed_sources.py joins them), or nothing.
+StringStorage emit_refine_entry(const KernelOptions& opts) {
+    StringStorage s;
+    if (opts.refine_entry) s.add_string(device_source_refine_entry());
+    if (opts.refine_slices_entry) s.add_string(device_source_refine_slices_entry());
+    return s;
+}
+
 StringStorage emit_skybox_processing(const Scene& scene, const BuildPlan&, const KernelOptions&) {
     StringStorage s;
     if (scene.skybox) {
@@ -1772,7 +1681,24 @@ GeneratedKernel describe_kernel(const BuildPlan& plan, const KernelOptions& opts
 
 }  // namespace
 
+const std::string& plain_library_source() {
+    static const std::string text = select_sections(device_source_library(), {});
+    return text;
+}
+const std::string& plain_entry_source() {
+    static const std::string text = apply_template(select_sections(device_source_entry(), {}), {{"refine_entry", StringStorage()}}).storage;
+    return text;
+}
+
 GeneratedKernel generate_kernel_source(const Scene& scene, const CodegenFlags& flags, const KernelOptions& opts) {
+    if (opts.refine_slices_entry && opts.refine_entry)
+        throw SceneError("PTL_FLAG_REFINE and PTL_FLAG_REFINE_SLICES cannot be combined: a module has the refine entry over its own uniform block or the one over slices");
+    if (opts.slices_entry && opts.refine_entry) throw SceneError("PTL_FLAG_REFINE and PTL_FLAG_SLICES cannot be combined: the refine entry reads the module's own uniform block (PTL_FLAG_REFINE_SLICES has the entry over slices)");
+    if (opts.passes && (opts.anaglyph || opts.refine_entry || opts.refine_slices_entry || opts.check_affine))
+        throw SceneError(std::string("PTL_FLAG_PASSES cannot be combined with ") + (opts.anaglyph ? "PTL_FLAG_ANAGLYPH: an anaglyph sample traces two paths, a pass record books one per sample"
+                                                                                    : opts.check_affine ? "PTL_FLAG_CHECK_AFFINE: that build counts ray halves where the record counts trips"
+                                                                                    : opts.refine_entry ? "PTL_FLAG_REFINE: the list-driven entry stores no records"
+                                                                                                        : "PTL_FLAG_REFINE_SLICES: the list-driven entry stores no records"));
     const std::vector<UniformUpload> values = evaluate_scene_uniforms(scene, nullptr);
     const BuildPlan plan = plan_build(scene, flags, opts, values);
 
@@ -1789,26 +1715,16 @@ GeneratedKernel generate_kernel_source(const Scene& scene, const CodegenFlags& f
     slots["library"] = emit_library(scene, plan, opts);
     slots["predefined_library"] = emit_predefined_library(scene, plan, opts);
     slots["skybox_processing"] = emit_skybox_processing(scene, plan, opts);
+    if (sliced(opts)) slots["prelude_in_tracer"] = emit_prelude_in_tracer(scene, plan, opts);
+    slots["refine_entry"] = emit_refine_entry(opts);
 
-    StringStorage body = apply_template(device_source_trace_template(), std::move(slots));
-    body.add_string("\n");
-    body.add_string(device_source_entry());
+    // the trace template and the entries behind it as one text: the sections of this build's variants, then the slots
+    const std::string tmpl = select_sections(std::string(device_source_trace_template()) + "\n" + device_source_entry(), variant_sections(opts));
+    StringStorage body = apply_template(tmpl, std::move(slots));
     GeneratedKernel gk = describe_kernel(plan, opts);
     gk.source = std::move(body.storage);
     gk.line_numbers = std::move(body.line_numbers);
     apply_zero_masks(gk.source, gk.masked);
-    if (opts.refine_slices_entry && opts.refine_entry)
-        throw SceneError("PTL_FLAG_REFINE and PTL_FLAG_REFINE_SLICES cannot be combined: a module has the refine entry over its own uniform block or the one over slices");
-    if (opts.slices_entry && opts.refine_entry) throw SceneError("PTL_FLAG_REFINE and PTL_FLAG_SLICES cannot be combined: the refine entry reads the module's own uniform block (PTL_FLAG_REFINE_SLICES has the entry over slices)");
-    if (opts.passes && (opts.anaglyph || opts.refine_entry || opts.refine_slices_entry || opts.check_affine))
-        throw SceneError(std::string("PTL_FLAG_PASSES cannot be combined with ") + (opts.anaglyph ? "PTL_FLAG_ANAGLYPH: an anaglyph sample traces two paths, a pass record books one per sample"
-                                                                                    : opts.check_affine ? "PTL_FLAG_CHECK_AFFINE: that build counts ray halves where the record counts trips"
-                                                                                    : opts.refine_entry ? "PTL_FLAG_REFINE: the list-driven entry stores no records"
-                                                                                                        : "PTL_FLAG_REFINE_SLICES: the list-driven entry stores no records"));
-    if (opts.slices_entry || opts.refine_slices_entry) apply_slices_entry(gk.source);
-    if (opts.passes) apply_passes(gk.source);
-    if (opts.refine_entry) apply_refine_entry(gk.source, device_source_refine_entry());
-    if (opts.refine_slices_entry) apply_refine_entry(gk.source, device_source_refine_slices_entry());
     return gk;
 }
 

@@ -53,6 +53,16 @@ public:
 // Splits `tmpl` on "//%"; odd pieces are slot names looked up in `storages`.
 StringStorage apply_template(const std::string& tmpl, std::map<std::string, StringStorage> storages);
 
+// Conditional sections of a template, resolved line by line BEFORE apply_template (whose slot scanner never sees a directive):
+//     //%if NAME   (or //%if !NAME)        the lines down to the matching else / end stay if NAME is (is not) in `names`
+//     //%else                              optional, once: the lines that stay otherwise
+//     //%end
+// Sections nest.  A directive line goes with its newline, a deselected section with all of its lines; everything else comes back as it is.
+// std::logic_error (the templates are ours): a section left open, an else / end without an if, a second else, a name that is not one of
+// section_names() -- in a directive or in `names`.
+const std::set<std::string>& section_names();  // slices, passes, refine, refine_slices: the entry variants of KernelOptions
+std::string select_sections(const std::string& text, const std::set<std::string>& names);
+
 // --- uniforms ------------------------------------------------------------------------------
 enum class UniformType { Mat4 = 0, Float1 = 1, Int1 = 2, Float2 = 3, Float3 = 4, Sampler = 5 };
 struct UniformDesc {
@@ -151,21 +161,21 @@ struct KernelOptions {
     bool bound_snippets = false;
     // The render entry reads its uniform block from a device BUFFER of blocks instead of the module's one global, indexed by blockIdx.z
     // (`ptl_render_slices_kernel`): ONE launch then traces several frames that differ in their uniforms -- the motion-blur sub-frames of a clip
-    // frame (src/main.rs:1798 re-draws with `_aa_start` windows one after the other) -- so that their ramps and tails overlap.  Applied to the
-    // generated text by substitution (codegen.cpp `apply_slices_entry`): kernels built without it are byte for byte what they were.
+    // frame (src/main.rs:1798 re-draws with `_aa_start` windows one after the other) -- so that their ramps and tails overlap.  Its text is the
+    // `slices` sections of device/ptl_trace.tpl, ptl_entry.h and ptl_library.h (select_sections): kernels built without it are byte for byte what they were.
     bool slices_entry = false;
     // Adaptive anti-aliasing (PTL_FLAG_REFINE): the module gets a second render entry, `ptl_render_refine_kernel` (device/ptl_refine_entry.h, a thin
-    // entry around the list walk of device/ptl_refine_common.h), which shades the pixels of a device-side list instead of a rectangle.  Both texts are
-    // spliced in as one, like the slices entry (codegen.cpp `apply_refine_entry`): kernels built without it are byte for byte what they were.  Not
-    // together with slices_entry.
+    // entry around the list walk of device/ptl_refine_common.h), which shades the pixels of a device-side list instead of a rectangle.  Both texts
+    // fill, as one, the `refine_entry` slot in front of the host half of device/ptl_entry.h: kernels built without it are byte for byte what they were.
+    // Not together with slices_entry.
     bool refine_entry = false;
     // Adaptive anti-aliasing of a batch of slices (PTL_FLAG_REFINE_SLICES): the slices entry (implied) plus a list-driven entry over the same
     // buffer of blocks, `ptl_render_refine_slices_kernel` (device/ptl_refine_slices_entry.h, the same walk once per slice): slice z shades the pixels
-    // of ITS list with ITS block.  `apply_slices_entry` first, then `apply_refine_entry` with this entry's text.  Not together with refine_entry.
+    // of ITS list with ITS block.  The `slices` sections, and this entry's text in the `refine_entry` slot.  Not together with refine_entry.
     bool refine_slices_entry = false;
     // Trace passes (PTL_FLAG_PASSES): the tracer keeps a 16-byte record per pixel -- nearest final depth, bounce-loop trips, how its paths ended
     // (include/portal_amd.h `ptl_pass_record`) -- and the render entry (the slices entry too) takes one more pointer, `out_passes`, stored like
-    // out_rgba32f.  Applied to the finished text like the slices entry (codegen.cpp `apply_passes`), and `#define PTL_PASSES 1` stands in the text:
+    // out_rgba32f.  Its text is the `passes` sections of device/ptl_trace.tpl and ptl_entry.h, and `#define PTL_PASSES 1` stands in the text:
     // kernels built without it are byte for byte what they were.  Not with anaglyph (two paths per sample), the refine entries or check_affine.
     bool passes = false;
     // Affine rays (round 5): in a kernel whose every scene matrix is KNOWN to have the bottom row 0 0 0 1 (baked, or through its pattern) and
@@ -250,12 +260,17 @@ std::vector<UniformUpload> evaluate_scene_uniforms(const Scene& scene, std::vect
 // Rust `{:e}` formatting of an f64 (shortest round-trip digits, exponent without padding).
 std::string format_lower_exp(double v);
 
-// The fixed device sources (embedded at build time from csrc/device/).
+// The fixed device sources (embedded at build time from csrc/device/), as the files are: the trace template, the entry and the library with their
+// conditional sections (select_sections), the entry with its `refine_entry` slot.
 const char* device_source_glsl();
 const char* device_source_library();
 const char* device_source_trace_template();
 const char* device_source_entry();
 const char* device_source_refine_entry();
 const char* device_source_refine_slices_entry();
+// ... and what a hand-written kernel pastes around its own shade_pixel: the library / the entry of a build without any variant (no section
+// selected, the slot empty) -- byte for byte the texts these two files were before they had sections.
+const std::string& plain_library_source();
+const std::string& plain_entry_source();
 
 }  // namespace ptl

@@ -66,7 +66,7 @@ struct ptl_kernel {
     hip::hipEvent_t ev_done = nullptr;  // recorded behind every render launch: what destroy / a teleport query wait for.  Owned here, so it
                                         // stays valid when the caller has already destroyed the stream it launched on (a torch stream, a
                                         // user stream freed before the renderer: Python __del__ order is unspecified).
-    // A module generated with the slices entry (codegen.cpp `apply_slices_entry`): its render entry `ptl_render_slices_kernel` reads the uniform
+    // A module generated with the slices entry (the `slices` sections of device/ptl_entry.h): its render entry `ptl_render_slices_kernel` reads the uniform
     // block of slice blockIdx.z from a device buffer of blocks, so one launch can trace several frames with different uniforms.  The module's
     // own global block stays what the camera-teleport query uses.
     bool sliced = false;
@@ -428,7 +428,7 @@ int obtain_code(const CompileRequest& rq, const BuildTraits& traits, bool read_c
 }
 
 // Loads k->code on the current device and binds what the host side uses of it: entries, uniform block, events.  `Discover`: the plain render
-// entry, else the slices entry (codegen.cpp `apply_slices_entry`).  A code object the runtime refuses leaves k->module null.
+// entry, else the slices entry (the `slices` sections of device/ptl_entry.h).  A code object the runtime refuses leaves k->module null.
 enum class RenderEntry { None, Plain, Sliced, Discover };
 int bind_module(ptl_kernel* k, const hip::Runtime* rt, RenderEntry entry, size_t declared_block_size) {
     if (!hip_ok(rt, rt->hipModuleLoadData(&k->module, k->code.data()), "hipModuleLoadData")) return k->module = nullptr, PTL_ERR_HIP;
@@ -904,7 +904,7 @@ extern "C" int ptl_kernel_render(ptl_kernel* k, const ptl_frame* frame, void* ou
     return render_single(k, frame, out_rgba8, out_rgba32f, nullptr, segments, stream, elapsed_ms);
 }
 
-// ---- trace passes: the same two launches with the records of a PTL_FLAG_PASSES module (codegen.cpp `apply_passes`) ---------------------
+// ---- trace passes: the same two launches with the records of a PTL_FLAG_PASSES module (the `passes` sections of device/ptl_entry.h) ------
 extern "C" size_t ptl_pass_record_bytes(int width, int height) { return (width > 0 && height > 0) ? sizeof(ptl_pass_record) * (size_t)width * (size_t)height : 0; }
 
 // What both refuse before any GPU call: a module without the records, a missing or misaligned buffer, one too small for what the launch stores

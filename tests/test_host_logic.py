@@ -1572,7 +1572,7 @@ def test_bounded_snippets_draw_the_frames_of_the_snippets_as_written(pa, flags_n
 
 
 def test_slices_entry_is_a_substitution_that_keeps_the_scene_lines_and_the_pictures(pa):
-    """PTL_FLAG_SLICES (codegen.cpp `apply_slices_entry`): the render entry `ptl_render_slices_kernel` reads the uniform block of slice blockIdx.z
+    """PTL_FLAG_SLICES (the `slices` sections of the device files, codegen.h `select_sections`): the render entry `ptl_render_slices_kernel` reads the uniform block of slice blockIdx.z
     from a buffer of blocks.  Without the flag the source is byte for byte what it was; with it the scene's own lines keep their numbers (compiler
     diagnostics map back to scene elements by line), the prelude sits inside the tracer struct (its uniform-reading functions see the slice), the
     classic entry is gone, a per-slice prologue entry is there -- and the host build of that source still draws the oracle's bits."""
