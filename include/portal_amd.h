@@ -874,6 +874,43 @@ int ptl_png_write_level(const char* path, const uint8_t* rgba8, int width, int h
  * 0 .. 9; IEND.  No per-pixel work on the host.  ptl_png_read opens such a file by its high bytes. */
 int ptl_png_write_rgb48(const char* path, const uint8_t* rows, int width, int height, int filter, int level);
 
+/* ---- GPU deflate of an 8-bit PNG frame: run-length fixed-Huffman streams (opt-in: `--png-encoder gpu`) ------------------
+ * ptl_png_deflate_rgba8 turns an RGBA8 frame that is already on the card into the deflate stream of its filtered scanlines, so that the host's
+ * part of the file is a CRC and an fwrite (ptl_png_write_stream).  The stream is stated bit for bit; tests/png_deflate_reference.py restates it
+ * in numpy, and any inflater returns `raw` from it.
+ * Input.  frame_rgba8: DEVICE pointer, W x H pixels of 4 bytes, packed.  Its raw scanlines `raw`, H (4 W + 1) bytes, are what
+ *   ptl_png_write_level deflates: per row a filter-type byte, 0 for row 0 and 2 (Up) for every other row, then the row's 4 W bytes, each minus
+ *   the byte above it mod 256 (row 0 unchanged).
+ * Bands.  `raw` is cut into bands of whole rows, ptl_png_stream_band_rows(W) = max(1, floor(16384 / (4 W + 1))) rows each (the last band may
+ *   have fewer); inside a band `raw` is cut into segments of 4096 bytes (the last of a band may be shorter).  Runs never cross a segment
+ *   boundary: the parse stays local, and a segment's Adler-32 partial sums stay within 32 bits (255 * 4096 * 4097 / 2 < 2^32).
+ * Tokens of a segment.  For every maximal run of L equal bytes v: literal v; m = L - 1; while m >= 3, a match of length min(m, 258) at
+ *   distance 1, m less that length; the remaining m (0, 1 or 2) bytes as literals v.
+ * Bits of a band (RFC 1951 3.2.5 - 3.2.6, fixed codes): block header BFINAL = 0, BTYPE = 01; the tokens (Huffman codes most-significant bit
+ *   first, extra bits least-significant bit first, distance code 0 without extra bits); end-of-block (seven 0 bits); an empty stored block
+ *   (three 0 bits, zero padding to the byte, 00 00 FF FF).  Every band is a whole number of bytes, and bands concatenate.
+ * The zlib stream of the file: 78 01, the bands in order, 03 00 (an empty final fixed block), Adler-32 of `raw`, big-endian.
+ * Capacity.  A token never costs more than 9 bits per raw byte it covers (a match: at most 18 bits for at least 3 bytes), so a band of n raw
+ *   bytes needs at most ceil((9 n + 20) / 8) + 4 bytes.  Every band's slot is sized from that bound (rounded up to 16): no input overruns it.
+ * out: DEVICE pointer, 16-byte aligned, ptl_png_stream_bytes(W, H) bytes:
+ *   bytes 0 .. 63   header, little-endian uint32: "PTLZ" (0x5a4c5450), W, H, the stream's byte count n, Adler-32 of `raw`, rows per band,
+ *                   number of bands, nine zero words
+ *   bytes 64 .. 64 + n   the bands in order (without 78 01 / 03 00 / Adler-32: the writer adds them); room for the sum of the band bounds
+ *   behind it       scratch: a 16-byte table entry per band (bytes used, Adler s1, s2, raw bytes) and the bands' slots.  Nothing in `out` has
+ *                   to be cleared between calls.
+ * Refused before any GPU call (PTL_ERR_INVALID): null or not 16-byte aligned pointers, sizes <= 0, H (4 W + 1) > 2^31 (the kernels address
+ * `raw` with 32-bit offsets; ptl_png_stream_bytes is 0 for such a size).  Stream and timing as for ptl_average_images: two kernels
+ * (portal_amd/csrc/kernels/png_deflate.hip) on `stream`, elapsed_ms != NULL waits and reports both. */
+#define PTL_PNG_STREAM_HEADER_BYTES 64 /* the stream starts this far into the result buffer; its byte count is header word 3 */
+size_t ptl_png_stream_bytes(int width, int height);
+int ptl_png_stream_band_rows(int width); /* rows per band; 0 for a width that is not positive */
+int ptl_png_deflate_rgba8(int device, const void* frame_rgba8, int width, int height, void* out, void* stream, float* elapsed_ms);
+/* The file from a HOST copy of that buffer (the header and the stream's n bytes are read, nothing behind them): signature, IHDR (bit depth 8,
+ * colour type 6), ONE IDAT = 78 01 + stream + 03 00 + Adler-32, IEND.  No per-pixel work and no zlib call but crc32.  A header that does not
+ * match -- the magic word, W, H, the band cut, or a byte count beyond the room ptl_png_stream_bytes leaves for the stream -- is
+ * PTL_ERR_INVALID, and nothing is written. */
+int ptl_png_write_stream(const char* path, const uint8_t* result, int width, int height);
+
 /* ---- template engine test hooks (src/code_generation.rs) ----------------------------------- */
 typedef struct ptl_strstore ptl_strstore;
 ptl_strstore* ptl_strstore_new(void);

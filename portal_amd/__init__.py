@@ -192,6 +192,10 @@ def _load() -> C.CDLL:
         "ptl_average_f32_to_rgb48": (ci, [ci, P(vp), ci, vp, ci, ci, ci, vp, P(C.c_float)]),
         "ptl_rgb48_frame_bytes": (cs, [ci, ci]),
         "ptl_png_write_rgb48": (ci, [cp, vp, ci, ci, ci, ci]),
+        "ptl_png_stream_bytes": (cs, [ci, ci]),
+        "ptl_png_stream_band_rows": (ci, [ci]),
+        "ptl_png_deflate_rgba8": (ci, [ci, vp, ci, ci, vp, vp, P(C.c_float)]),
+        "ptl_png_write_stream": (ci, [cp, vp, ci, ci]),
         "ptl_pass_record_bytes": (cs, [ci, ci]),
         "ptl_kernel_render_passes": (ci, [vp, P(Frame), vp, vp, vp, cs, vp, vp, P(C.c_float)]),
         "ptl_kernel_render_slices_passes": (ci, [vp, P(Frame), ci, vp, vp, vp, cs, C.c_ulonglong, vp, P(C.c_float)]),
@@ -1037,6 +1041,39 @@ def png_write_rgb48(path: str, rows, width: int, height: int, filter: int = PNG_
     if width > 0 and height > 0 and a.size != 6 * width * height:
         raise PortalError(f"png_write_rgb48: {a.size} bytes are not {width} x {height} pixels of 6 bytes")
     _check(lib().ptl_png_write_rgb48(path.encode(), a.ctypes.data, width, height, filter, level), "png_write_rgb48")
+
+
+PNG_STREAM_HEADER_BYTES = 64
+
+
+def png_stream_bytes(width: int, height: int) -> int:
+    """Bytes of the result buffer of `png_deflate_rgba8_device`: header, room for the longest stream, and the kernels' scratch behind it;
+    0 for a size that is not positive or whose scanlines exceed 2^31 bytes."""
+    return int(lib().ptl_png_stream_bytes(width, height))
+
+
+def png_stream_band_rows(width: int) -> int:
+    """Rows of the frame per band of the stream (each band is a deflate block of its own)."""
+    return int(lib().ptl_png_stream_band_rows(width))
+
+
+def png_deflate_rgba8_device(frame_ptr: int, out_ptr: int, width: int, height: int, device: int = 0, stream: int = 0, timed: bool = False):
+    """ptl_png_deflate_rgba8 on DEVICE buffers given as integer addresses: the RGBA8 frame at frame_ptr -> at out_ptr
+    (`png_stream_bytes(width, height)` bytes) a 64-byte header and the deflate stream of the frame's Up-filtered scanlines (fixed Huffman
+    codes, runs only; the contract is in include/portal_amd.h).  Returns the time of both kernels in ms when ``timed`` (waits), else None."""
+    ms = C.c_float()
+    _check(lib().ptl_png_deflate_rgba8(device, C.c_void_p(frame_ptr or None), width, height, C.c_void_p(out_ptr or None), C.c_void_p(stream or None),
+                                       C.byref(ms) if timed else None), "png_deflate_rgba8")
+    return ms.value if timed else None
+
+
+def png_write_stream(path: str, result, width: int, height: int) -> None:
+    """ptl_png_write_stream: an 8-bit RGBA PNG from a HOST copy of the result buffer (bytes or a uint8 array: the header and the stream it
+    announces, at least); the host adds the chunk framing and CRCs, nothing else."""
+    a = np.ascontiguousarray(np.frombuffer(result, dtype=np.uint8) if isinstance(result, (bytes, bytearray, memoryview)) else result, dtype=np.uint8)
+    if a.size < PNG_STREAM_HEADER_BYTES or a.size < PNG_STREAM_HEADER_BYTES + int(a[12:16].view("<u4")[0]):
+        raise PortalError("png_write_stream: the buffer is shorter than its header and the stream the header announces")
+    _check(lib().ptl_png_write_stream(path.encode(), a.ctypes.data, width, height), "png_write_stream")
 
 
 # ---- trace passes (include/portal_amd.h: ptl_pass_record, ptl_pass_stats_block) ------------------------------------------------------

@@ -22,6 +22,8 @@ int usage() {  // (and the exit status that goes with it)
                  "                  [--specialize 0] do NOT bake the scene state into the kernel   [--fast] tolerance mode   [--exact-cr] numerics contract 1   [--opt3] JIT at -O3 like the library default (render-frame: -O1)   [--timing] where the wall time went\n"
                  "                  [--adaptive-aa [T]]  one sample per pixel, --aa-count samples only where a pixel differs from a neighbour by more than T codes (default 4, -1 .. 255); one GPU\n"
                  "                  [--png-depth 8|16]   16: a 16-bit RGB file made on the GPU from the frame's float output (one quantisation, to 16 bits); one GPU\n"
+                 "                  [--png-encoder host|gpu]  gpu: the 8-bit file's deflate stream is made on the GPU (fixed Huffman codes, runs only: about twice the size);\n"
+                 "                                       the host adds the chunk framing and CRCs.  One GPU; not with --png-depth 16\n"
                  "                  [--passes depth,trips]  beside the frame: <output stem>.depth.png (nearest final depth, scaled between the scene's depth-map bounds) and\n"
                  "                                       <output stem>.trips.png (bounce-loop trips per pixel), 16-bit greyscale, from the tracer's pass records; one GPU\n"
                  "                  [--depth-report]     one line: how many paths --render-depth cut short (they are drawn black), in how many pixels; the deepest pixel; the depth range\n"
@@ -42,6 +44,9 @@ int usage() {  // (and the exit status that goes with it)
                  "                  [--png-depth 8|16]   with --frames png: 16 makes anim/frame_%%d.png 16-bit RGB files from the un-quantised float sub-frames (the averaged\n"
                  "                                       frame of --deep-colour), Sub-filtered on the GPU; works with --shard K/N and resumes.  16 more bytes per pixel and\n"
                  "                                       sub-frame on the card, 6 instead of 4 bytes per pixel leave it, and the files are 4 - 7 times larger to deflate\n"
+                 "                  [--png-encoder host|gpu]  with --frames png: gpu deflates every 8-bit frame on the GPU (fixed Huffman codes, runs only), so an encoder thread\n"
+                 "                                       only frames the stream and computes its CRC; the files are about twice the size.  Works with --shard K/N and resumes;\n"
+                 "                                       the stills stay host-encoded.  Not with --frames y4m or --png-depth 16\n"
                  "                  [--depth-report]     one line per clip: how many paths --render-depth cut short, in how many pixels, and the frame that lost most\n"
                  "                  [--clip-adaptive-aa [T]]  adaptive anti-aliasing of every sub-frame: one sample per pixel, --aa-count samples only where a pixel differs\n"
                  "                                       from a neighbour by more than T codes (default 4, -1 .. 255); opt-in, approximate by design\n"
@@ -250,7 +255,35 @@ int render_frame(const Options& o) {
     void* records = nullptr;
     if (with_records && ptl_device_alloc(devices[0], record_bytes, &records) != PTL_OK) return fail("device records");
     std::unique_ptr<void, HandleFree> own_records(records);
-    if (o.png_depth == 16) {
+    std::vector<uint8_t> deflated;  // --png-encoder gpu: the result buffer of ptl_png_deflate_rgba8, its header and its stream
+    if (o.png_gpu) {
+        // drawn into a frame on the device, deflated there; the header comes down first, then exactly the stream it announces
+        void *dev = nullptr, *dev_result = nullptr, *list = nullptr, *count = nullptr;
+        const size_t result_bytes = ptl_png_stream_bytes(o.width, o.height);
+        if (result_bytes == 0) return fail("--png-encoder gpu: the frame's scanlines exceed 2^31 bytes");
+        if (ptl_device_alloc(devices[0], img.size(), &dev) != PTL_OK) return fail("device frame");
+        std::unique_ptr<void, HandleFree> own(dev);
+        if (ptl_device_alloc(devices[0], result_bytes, &dev_result) != PTL_OK) return fail("device stream");
+        std::unique_ptr<void, HandleFree> own_result(dev_result);
+        if (o.adaptive) {
+            ptl_renderer_set_option(r, "adaptive_aa_threshold", o.adaptive_t);
+            if (ptl_renderer_draw_adaptive(r, &frame, dev, nullptr, nullptr, &ms) != PTL_OK) return fail("render");
+            if (ptl_renderer_adaptive_result(r, &list, &count) != PTL_OK || ptl_device_download(&refined, count, sizeof refined, nullptr) != PTL_OK) return fail("refined count");
+            ptl_renderer_adaptive_times(r, pass_ms);
+        } else if ((with_records ? ptl_renderer_draw_passes(r, &frame, dev, nullptr, records, record_bytes, nullptr, nullptr, &ms) : ptl_renderer_draw(r, &frame, dev, nullptr, nullptr, nullptr, &ms)) != PTL_OK)
+            return fail("render");
+        float deflate_ms = 0.0f;
+        if (ptl_png_deflate_rgba8(devices[0], dev, o.width, o.height, dev_result, nullptr, o.timing ? &deflate_ms : nullptr) != PTL_OK) return fail("png_deflate_rgba8");
+        const size_t header_bytes = PTL_PNG_STREAM_HEADER_BYTES;
+        deflated.resize(header_bytes);
+        if (ptl_device_download(deflated.data(), dev_result, header_bytes, nullptr) != PTL_OK) return fail("download");
+        unsigned int stream_bytes = 0;
+        std::memcpy(&stream_bytes, deflated.data() + 12, 4);
+        if (header_bytes + stream_bytes > result_bytes) return fail("png_deflate_rgba8: the header's byte count");
+        deflated.resize(header_bytes + stream_bytes);
+        if (ptl_device_download(deflated.data() + header_bytes, static_cast<const char*>(dev_result) + header_bytes, stream_bytes, nullptr) != PTL_OK) return fail("download");
+        if (o.timing) std::printf("png encoder gpu: deflate %.3f ms, %u bytes of stream downloaded\n", deflate_ms, stream_bytes);
+    } else if (o.png_depth == 16) {
         // drawn on the device with an RGBA32F target next to the RGBA8 one (which the adaptive classification reads), converted there with
         // n = 1 (ptl_average_f32_to_rgb48), downloaded at 6 bytes per pixel
         void *dev8 = nullptr, *dev32 = nullptr, *dev_rows = nullptr, *list = nullptr, *count = nullptr;
@@ -319,6 +352,9 @@ int render_frame(const Options& o) {
     if (o.png_depth == 16) {
         if (!dir_of(o.output).empty()) make_dirs(dir_of(o.output));
         if (ptl_png_write_rgb48(o.output.c_str(), rows16.data(), o.width, o.height, PTL_PNG_FILTER_SUB, 6) != PTL_OK) return fail("png");
+    } else if (o.png_gpu) {
+        if (!dir_of(o.output).empty()) make_dirs(dir_of(o.output));
+        if (ptl_png_write_stream(o.output.c_str(), deflated.data(), o.width, o.height) != PTL_OK) return fail("png");
     } else if (int rc = write_png(o.output, img.data(), o.width, o.height))
         return rc;
     for (int which : {PTL_PASS_DEPTH, PTL_PASS_TRIPS})
@@ -534,6 +570,12 @@ int main(int argc, char** argv) {
             o.png_depth = std::atoi(depth.c_str());
             o.have_png_depth = true;
         }
+        else if (a == "--png-encoder") {
+            std::string encoder = next();
+            if (encoder != "host" && encoder != "gpu") return refuse("--png-encoder host|gpu");
+            o.png_gpu = encoder == "gpu";
+            o.have_png_encoder = true;
+        }
         else if (a == "--gpus") o.gpus = std::atoi(next());
         else if (a == "--devices") o.devices = next();
         else if (a == "--transport") o.transport = next();
@@ -607,6 +649,13 @@ int main(int argc, char** argv) {
     if (o.png_depth == 16 && o.y4m) return refuse("--png-depth 16 cannot be combined with --frames y4m: a stream holds no PNG frames (its deep-colour form is --deep-colour)");
     if (o.png_depth == 16 && cmd == "render-frame" && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.multi_process || o.shards > 1 || o.transport == "rccl"))
         return refuse("render-frame --png-depth 16 draws the frame on one GPU: frame groups gather RGBA8, so it cannot be combined with --gpus N, N > 1, several --devices, --multi-process, --transport rccl or --shard");
+    if (o.have_png_encoder && cmd != "render" && cmd != "render-frame") return refuse("--png-encoder is an option of render and render-frame: it chooses who deflates the PNG frames of a clip, or the one frame");
+    if (o.png_gpu && o.y4m) return refuse("--png-encoder gpu cannot be combined with --frames y4m: a stream holds no PNG frames");
+    if (o.png_gpu && o.png_depth == 16) return refuse("--png-encoder gpu cannot be combined with --png-depth 16: the GPU deflates 8-bit frames only (runs at distance 1 do not catch the 16-bit rows)");
+    if (o.png_gpu && cmd == "render-frame" && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.multi_process || o.shards > 1 || o.transport == "rccl"))
+        return refuse("render-frame --png-encoder gpu deflates the frame on the one GPU that drew it: it cannot be combined with --gpus N, N > 1, several --devices, --multi-process, --transport rccl or --shard");
+    if (o.png_gpu && ptl_png_stream_bytes(o.stereo ? 2 * o.width : o.width, o.height) == 0)
+        return refuse("--png-encoder gpu needs a frame whose scanlines, H (4 W + 1) bytes, number at most 2^31: the kernels address them with 32-bit offsets");
     if (o.adaptive && cmd != "render-frame") return refuse("--adaptive-aa is an option of render-frame: a clip's sub-frames go through the slices entry, whose adaptive form is `render --clip-adaptive-aa [T]`");
     if (o.clip_adaptive && cmd != "render" && cmd != "precompile") return refuse("--clip-adaptive-aa is an option of render (and of precompile, which builds render's kernels); a single frame takes render-frame --adaptive-aa");
     if (o.adaptive && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.shards > 1)) return refuse("--adaptive-aa draws whole frames on one GPU: it cannot be combined with --gpus N, N > 1, several --devices or --shard");

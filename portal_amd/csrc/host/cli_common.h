@@ -24,6 +24,8 @@ struct Options {
     bool have_chroma = false;     // --chroma was given
     int png_depth = 8;            // render / render-frame --png-depth 8|16: 16 makes the PNG frames, or the frame, from the float output (ptl_average_f32_to_rgb48)
     bool have_png_depth = false;  // --png-depth was given
+    bool png_gpu = false;         // render / render-frame --png-encoder host|gpu: gpu deflates the 8-bit frames on the card (ptl_png_deflate_rgba8), the host only frames the stream
+    bool have_png_encoder = false;  // --png-encoder was given
     int batch = -1;       // render --batch-subframes 0|1: one launch for a frame's blur sub-frames (default: on where 2 <= blur <= 16)
     std::vector<std::pair<std::string, double>> sets;  // --set name=value
     bool timing = false;  // --timing: wait for every kernel and report GPU milliseconds (serialises host and GPU)

@@ -406,6 +406,42 @@ public:
     }
 };
 
+// The same 8-bit files with the deflate done on the card (--png-encoder gpu): the frame -- averaged into one device frame where blur > 1, else the
+// single sub-frame -- goes through ptl_png_deflate_rgba8, what leaves the card is its result buffer (the whole of it: a budgeted download is a
+// follow-up), and an encoder thread only frames the stream (ptl_png_write_stream).  Names, have(), shards, resume and encode_video are PngOutput's.
+class PngGpuOutput : public PngOutput {
+public:
+    using PngOutput::PngOutput;
+    size_t result_bytes() const override { return ptl_png_stream_bytes(run_.width, run_.height); }
+    bool draws_result() const override { return false; }  // (one sub-frame is deflated where it was drawn)
+    int make_result(void* result, float* ms) override {
+        const void* frame = run_.subframes[0];
+        float average_ms = 0.0f, deflate_ms = 0.0f;
+        if (o_.blur > 1) {
+            if (!averaged_) {
+                void* p = nullptr;
+                if (ptl_device_alloc(o_.device, run_.frame_bytes, &p) != PTL_OK) return fail("alloc");
+                averaged_.reset(p);
+            }
+            if (ptl_average_images(o_.device, run_.subframes.data(), o_.blur, averaged_.get(), run_.width, run_.height, nullptr, ms ? &average_ms : nullptr) != PTL_OK) return fail("average_images");
+            frame = averaged_.get();
+        }
+        if (ptl_png_deflate_rgba8(o_.device, frame, run_.width, run_.height, result, nullptr, ms ? &deflate_ms : nullptr) != PTL_OK) return fail("png_deflate_rgba8");
+        if (ms) *ms = average_ms + deflate_ms;
+        return 0;
+    }
+    void submit(int i, uint8_t* pixels, void* arrived, EncoderPool& pool, PinnedFrames& pinned) override {
+        pool.submit([pixels, name = frame_name(i), width = run_.width, height = run_.height, arrived, &pinned] {
+            if (ptl_event_synchronize(arrived) != PTL_OK || ptl_png_write_stream(name.c_str(), pixels, width, height) != PTL_OK) std::fprintf(stderr, "\n%s\n", ptl_last_error());
+            ptl_event_destroy(arrived);
+            pinned.give(pixels);
+        });
+    }
+
+private:
+    std::unique_ptr<void, HandleFree> averaged_;  // blur > 1: the averaged RGBA8 frame, on the card
+};
+
 // One Y4M stream, written in frame order by a thread of its own.  (A stream is not resumed: it holds every frame, from frame 0.)
 class Y4mOutput : public FrameOutput {
 public:
@@ -484,10 +520,11 @@ public:
     }
 };
 
-std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, size_t max_pending) {  // the ONE place that knows there are four
+std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, size_t max_pending) {  // the ONE place that knows there are five
     if (run.o.y4m && run.o.deep_colour) return std::make_unique<DeepY4mOutput>(run, clip, max_pending);
     if (run.o.y4m) return std::make_unique<Y4mOutput>(run, clip, max_pending);
     if (run.o.png_depth == 16) return std::make_unique<Png16Output>(run, clip);
+    if (run.o.png_gpu) return std::make_unique<PngGpuOutput>(run, clip);
     return std::make_unique<PngOutput>(run, clip);
 }
 

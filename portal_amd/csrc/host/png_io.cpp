@@ -3,9 +3,11 @@
 // Stands in for the third-party image code behind the reference's
 // Texture2D::from_file_with_format (src/main.rs:1075) and Image::export_png
 // (src/main.rs:2939-2943).  Reads 8/16-bit grey, grey+alpha, RGB, RGBA and 1/2/4/8-bit
-// palette images, non-interlaced; writes RGBA8, and 16-bit RGB from rows the GPU has filtered (ptl_png_write_rgb48).
+// palette images, non-interlaced; writes RGBA8, 16-bit RGB from rows the GPU has filtered (ptl_png_write_rgb48), and RGBA8 around a stream
+// the GPU has deflated (ptl_png_write_stream).
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "../../../include/portal_amd.h"
+#include "../kernels/png_deflate_shape.h"
 #include "internal.h"
 
 namespace {
@@ -233,6 +236,46 @@ extern "C" int ptl_png_write_gray16(const char* path, const uint8_t* rows, int w
         std::memcpy(dst + 1, rows + (size_t)y * stride, stride);
     }
     return write_png_file(path, raw, comp, width, height, 16, 0, level);
+}
+
+// An 8-bit RGBA file from a HOST copy of the result buffer of ptl_png_deflate_rgba8: the GPU has filtered and deflated, the host checks the
+// header, frames the stream as one IDAT (78 01 | stream | 03 00 | Adler-32) and computes the chunk CRCs.  No per-pixel work, no deflate.
+extern "C" int ptl_png_write_stream(const char* path, const uint8_t* result, int width, int height) {
+    if (!path || !result || width <= 0 || height <= 0 || !ptl_png_fits((unsigned)width, (unsigned)height)) return PTL_ERR_INVALID;
+    unsigned word[7];
+    std::memcpy(word, result, sizeof word);  // (little-endian, as the card wrote them)
+    const unsigned w = (unsigned)width, h = (unsigned)height;
+    if (word[0] != ptl_png_magic || word[1] != w || word[2] != h || word[5] != ptl_png_band_rows(w) || word[6] != ptl_png_bands(w, h) ||
+        word[3] > ptl_png_stream_capacity(w, h) || word[3] < 6ull * ptl_png_bands(w, h)) {
+        ptl::set_last_error("png_write_stream: the buffer's header is not that of a " + std::to_string(width) + " x " + std::to_string(height) + " frame from ptl_png_deflate_rgba8");
+        return PTL_ERR_INVALID;
+    }
+    const size_t n = word[3];
+    std::vector<unsigned char> out = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    out.reserve(n + 80);
+    std::vector<unsigned char> ihdr;
+    put_be32(ihdr, w);
+    put_be32(ihdr, h);
+    ihdr.insert(ihdr.end(), {8, 6, 0, 0, 0});
+    write_chunk(out, "IHDR", ihdr.data(), ihdr.size());
+    put_be32(out, (unsigned)(n + 8));
+    const size_t start = out.size();
+    out.insert(out.end(), {'I', 'D', 'A', 'T', 0x78, 0x01});
+    out.insert(out.end(), result + ptl_png_header_bytes, result + ptl_png_header_bytes + n);
+    out.insert(out.end(), {0x03, 0x00});  // an empty final block with the fixed codes
+    put_be32(out, word[4]);
+    uLong crc = crc32(0L, Z_NULL, 0);
+    for (size_t at = start; at < out.size(); at += 1u << 30) crc = crc32(crc, out.data() + at, (uInt)std::min<size_t>(out.size() - at, 1u << 30));
+    put_be32(out, (unsigned)crc);
+    write_chunk(out, "IEND", nullptr, 0);
+    FILE* f = std::fopen(path, "wb");
+    if (!f) {
+        ptl::set_last_error(std::string("cannot write `") + path + "`");
+        return PTL_ERR_INVALID;
+    }
+    const bool ok = std::fwrite(out.data(), 1, out.size(), f) == out.size();
+    std::fclose(f);
+    return ok ? PTL_OK : PTL_ERR_INVALID;
 }
 
 extern "C" int ptl_png_write(const char* path, const uint8_t* rgba8, int width, int height) { return ptl_png_write_level(path, rgba8, width, height, 6); }

@@ -20,6 +20,7 @@
 
 #include "../../../include/portal_amd.h"
 #include "../kernels/pass_key.h"
+#include "../kernels/png_deflate_shape.h"
 #include "../kernels/rgb48_shape.h"
 #include "../kernels/yuv_shape.h"
 #include "hip_api.h"
@@ -266,6 +267,47 @@ extern "C" int ptl_average_f32_to_rgb48(int device, const void* const* frames_rg
         {"rgb48_f32.hsaco", "ptl_average_f32_to_rgb48_sub_kernel", "ptl_average_f32_to_rgb48_sub_table_kernel", "average_f32_to_rgb48"}};
     const long lanes = ptl_rgb48_lanes((unsigned)width, (unsigned)height);
     return launch_over_subframes(device, kKernels[filter == PTL_PNG_FILTER_SUB], frames_rgba32f, n_frames, {&out_rows, &width, &height}, lanes, stream, elapsed_ms);
+}
+
+// The GPU deflate of an 8-bit PNG frame (portal_amd/csrc/kernels/png_deflate.hip; the stream contract is in include/portal_amd.h): the bands
+// kernel, a workgroup per band (grid-stride beyond the cap), then the pack kernel, on the same stream.  The cut into bands and the layout of
+// the result buffer are png_deflate_shape.h's to say: the kernels read the same header.
+static_assert(PTL_PNG_STREAM_HEADER_BYTES == ptl_png_header_bytes, "the header the kernels write");
+extern "C" size_t ptl_png_stream_bytes(int width, int height) {
+    return width > 0 && height > 0 && ptl_png_fits((unsigned)width, (unsigned)height) ? (size_t)ptl_png_result_bytes((unsigned)width, (unsigned)height) : 0;
+}
+extern "C" int ptl_png_stream_band_rows(int width) { return width > 0 && width <= (1 << 29) ? (int)ptl_png_band_rows((unsigned)width) : 0; }
+
+extern "C" int ptl_png_deflate_rgba8(int device, const void* frame_rgba8, int width, int height, void* out, void* stream, float* elapsed_ms) {
+    if (!frame_rgba8 || !out || width <= 0 || height <= 0) return PTL_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(frame_rgba8) | reinterpret_cast<uintptr_t>(out)) & 15u) return PTL_ERR_INVALID;
+    if (!ptl_png_fits((unsigned)width, (unsigned)height)) {  // the kernels address the raw scanlines with 32-bit offsets
+        set_last_error("png_deflate_rgba8: " + std::to_string(width) + " x " + std::to_string(height) + " has more than 2^31 bytes of scanlines");
+        return PTL_ERR_INVALID;
+    }
+    if (device < 0) return PTL_ERR_NO_DEVICE;
+    LoadedKernel *bands_kernel = nullptr, *pack_kernel = nullptr;
+    if (int rc = load_kernel(device, "png_deflate.hsaco", "ptl_png_deflate_bands_kernel", &bands_kernel); rc != PTL_OK) return rc;
+    if (int rc = load_kernel(device, "png_deflate.hsaco", "ptl_png_deflate_pack_kernel", &pack_kernel); rc != PTL_OK) return rc;
+    const hip::Runtime* rt = hip::runtime(nullptr);
+    rt->hipSetDevice(device);
+    unsigned w = (unsigned)width, h = (unsigned)height, rows = ptl_png_band_rows(w), n_bands = ptl_png_bands(w, h);
+    unsigned long long table_offset = ptl_png_table_offset(w, h), slots_offset = ptl_png_slots_offset(w, h), slot_stride = ptl_png_slot_stride(w);
+    void* table = static_cast<char*>(out) + table_offset;
+    void* slots = static_cast<char*>(out) + slots_offset;
+    void* bands_args[] = {&frame_rgba8, &w, &h, &rows, &n_bands, &table, &slots, &slot_stride};
+    void* pack_args[] = {&out, &w, &h, &rows, &n_bands, &table_offset, &slots_offset, &slot_stride};
+    const unsigned blocks = (unsigned)grid_blocks(256L * n_bands);  // a workgroup per band
+    const int err = timed(rt, bands_kernel, stream, elapsed_ms, [&] {
+        const int e = rt->hipModuleLaunchKernel(bands_kernel->fn, blocks, 1, 1, 256, 1, 1, 0, stream, bands_args, nullptr);
+        return e != 0 ? e : rt->hipModuleLaunchKernel(pack_kernel->fn, blocks, 1, 1, 256, 1, 1, 0, stream, pack_args, nullptr);
+    });
+    if (err != 0) {
+        set_last_error(std::string("hipModuleLaunchKernel(png_deflate): ") + rt->hipGetErrorString(err));
+        rt->hipGetLastError();
+        return PTL_ERR_HIP;
+    }
+    return PTL_OK;
 }
 
 // ---- trace passes: the records a PTL_FLAG_PASSES render entry stores (portal_amd/csrc/kernels/pass_stats.hip, pass_gray16.hip; the contracts are
