@@ -903,8 +903,40 @@ int ptl_png_write_rgb48(const char* path, const uint8_t* rows, int width, int he
  * (portal_amd/csrc/kernels/png_deflate.hip) on `stream`, elapsed_ms != NULL waits and reports both. */
 #define PTL_PNG_STREAM_HEADER_BYTES 64 /* the stream starts this far into the result buffer; its byte count is header word 3 */
 size_t ptl_png_stream_bytes(int width, int height);
+/* What a host needs of the result buffer: the header and the room for the longest stream (rounded up to 16), without the scratch behind them;
+ * 0 where ptl_png_stream_bytes is 0. */
+size_t ptl_png_stream_download_bytes(int width, int height);
 int ptl_png_stream_band_rows(int width); /* rows per band; 0 for a width that is not positive */
 int ptl_png_deflate_rgba8(int device, const void* frame_rgba8, int width, int height, void* out, void* stream, float* elapsed_ms);
+/* ---- The same with per-band dynamic Huffman codes (opt-in: `--png-codes dynamic`) -----------------------------------------
+ * ptl_png_deflate_rgba8_codes(codes = PTL_PNG_CODES_FIXED) IS ptl_png_deflate_rgba8: the same kernels, the same bytes.  With
+ * PTL_PNG_CODES_DYNAMIC every band is emitted as a dynamic block (RFC 1951 3.2.7) or as the fixed block above, whichever has fewer bits.
+ * Unchanged: `raw`, the bands and segments, the tokens, the Adler-32, the band's trailing empty stored block, 78 01 ... 03 00, the 64-byte
+ * header (its reserved words zero), the layout of `out` and ptl_png_stream_bytes; ptl_png_write_stream reads either.
+ * tests/png_huffman_reference.py restates what follows.  Per band:
+ * Histogram.  count[s], s = 0 .. 285: how often literal/length symbol s occurs among the band's tokens; end-of-block (256) counts once.
+ * Literal/length code.  The used symbols (count > 0; at least two) sorted by (count, symbol) are the leaves of a Huffman tree built with two
+ *   queues: the leaves in that order, and the merged nodes in the order they are made.  Each merge takes, twice, the lighter of the two queue
+ *   heads -- the leaf where the weights are equal -- and appends a node of the summed weight.  A leaf's depth is its number of edges to the
+ *   root.  n[d] = number of leaves of depth d, depths beyond 15 counted as 15.  Repair: while sum n[d] 2^(15 - d) > 2^15: n[15] -= 1; for the
+ *   largest d < 15 with n[d] > 0: n[d] -= 1, n[d + 1] += 2 (each round takes one unit off the sum and keeps the number of leaves).  Lengths go
+ *   to the symbols in the sorted order: the first n[15] symbols (the rarest) get 15, the next n[14] get 14, and so on.  Codes: the canonical
+ *   assignment of RFC 1951 3.2.2.
+ * Distance code.  One code, distance code 0, of length 1 (a 0 bit behind every match).  HDIST = 0.
+ * Block header.  BFINAL = 0, BTYPE = 10, HLIT = (last used symbol + 1) - 257, HDIST = 0, HCLEN = 15; the 19 lengths of the code-length code in
+ *   the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15.  The code-length code is ONE fixed complete code, symbol 0 .. 18:
+ *       lengths   3 7 4 4 4 4 4 4 4 4 5 5 6 6 6 7 4 4 3          (canonical codes, RFC 1951 3.2.2)
+ *   Then the HLIT + 257 literal/length lengths followed by the one distance length (1), as one sequence, greedily per maximal run of r equal
+ *   lengths v.  v = 0: while r >= 138, symbol 18 with 138; then 18 with r if r >= 11, 17 with r if r >= 3, else r times symbol 0.
+ *   v > 0: symbol v; m = r - 1; while m >= 6, symbol 16 with 6; then 16 with m if m >= 3, else m times symbol v.
+ * Choice.  dynamic bits = header + sum count[s] (length[s] + extra bits) + 1 per match; fixed bits = 3 + sum count[s] (fixed length[s] + extra
+ *   bits) + 5 per match, end-of-block in both.  The band is the dynamic block where dynamic bits < fixed bits, else the fixed block: a band
+ *   never exceeds ceil((9 n + 20) / 8) + 4 bytes, and slots and capacities stay as they are.
+ * Any other `codes` is PTL_ERR_INVALID before anything else is looked at; every refusal of ptl_png_deflate_rgba8 carries over.  Two kernels on
+ * `stream`: the bands kernel of portal_amd/csrc/kernels/png_huffman.hip and the pack kernel of png_deflate.hip. */
+#define PTL_PNG_CODES_FIXED 0
+#define PTL_PNG_CODES_DYNAMIC 1
+int ptl_png_deflate_rgba8_codes(int device, const void* frame_rgba8, int width, int height, int codes, void* out, void* stream, float* elapsed_ms);
 /* The file from a HOST copy of that buffer (the header and the stream's n bytes are read, nothing behind them): signature, IHDR (bit depth 8,
  * colour type 6), ONE IDAT = 78 01 + stream + 03 00 + Adler-32, IEND.  No per-pixel work and no zlib call but crc32.  A header that does not
  * match -- the magic word, W, H, the band cut, or a byte count beyond the room ptl_png_stream_bytes leaves for the stream -- is

@@ -194,7 +194,9 @@ def _load() -> C.CDLL:
         "ptl_png_write_rgb48": (ci, [cp, vp, ci, ci, ci, ci]),
         "ptl_png_stream_bytes": (cs, [ci, ci]),
         "ptl_png_stream_band_rows": (ci, [ci]),
+        "ptl_png_stream_download_bytes": (cs, [ci, ci]),
         "ptl_png_deflate_rgba8": (ci, [ci, vp, ci, ci, vp, vp, P(C.c_float)]),
+        "ptl_png_deflate_rgba8_codes": (ci, [ci, vp, ci, ci, ci, vp, vp, P(C.c_float)]),
         "ptl_png_write_stream": (ci, [cp, vp, ci, ci]),
         "ptl_pass_record_bytes": (cs, [ci, ci]),
         "ptl_kernel_render_passes": (ci, [vp, P(Frame), vp, vp, vp, cs, vp, vp, P(C.c_float)]),
@@ -1052,18 +1054,31 @@ def png_stream_bytes(width: int, height: int) -> int:
     return int(lib().ptl_png_stream_bytes(width, height))
 
 
+def png_stream_download_bytes(width: int, height: int) -> int:
+    """The part of the result buffer a host needs: the header and the room for the longest stream, without the kernels' scratch behind them."""
+    return int(lib().ptl_png_stream_download_bytes(width, height))
+
+
 def png_stream_band_rows(width: int) -> int:
     """Rows of the frame per band of the stream (each band is a deflate block of its own)."""
     return int(lib().ptl_png_stream_band_rows(width))
 
 
-def png_deflate_rgba8_device(frame_ptr: int, out_ptr: int, width: int, height: int, device: int = 0, stream: int = 0, timed: bool = False):
+PNG_CODES_FIXED, PNG_CODES_DYNAMIC = 0, 1
+
+
+def png_deflate_rgba8_device(frame_ptr: int, out_ptr: int, width: int, height: int, device: int = 0, stream: int = 0, timed: bool = False, codes: int = PNG_CODES_FIXED):
     """ptl_png_deflate_rgba8 on DEVICE buffers given as integer addresses: the RGBA8 frame at frame_ptr -> at out_ptr
-    (`png_stream_bytes(width, height)` bytes) a 64-byte header and the deflate stream of the frame's Up-filtered scanlines (fixed Huffman
-    codes, runs only; the contract is in include/portal_amd.h).  Returns the time of both kernels in ms when ``timed`` (waits), else None."""
+    (`png_stream_bytes(width, height)` bytes) a 64-byte header and the deflate stream of the frame's Up-filtered scanlines (runs only; fixed
+    Huffman codes, or with ``codes=PNG_CODES_DYNAMIC`` a code per band through ptl_png_deflate_rgba8_codes; the contracts are in
+    include/portal_amd.h).  Returns the time of both kernels in ms when ``timed`` (waits), else None."""
     ms = C.c_float()
-    _check(lib().ptl_png_deflate_rgba8(device, C.c_void_p(frame_ptr or None), width, height, C.c_void_p(out_ptr or None), C.c_void_p(stream or None),
-                                       C.byref(ms) if timed else None), "png_deflate_rgba8")
+    if codes == PNG_CODES_FIXED:
+        _check(lib().ptl_png_deflate_rgba8(device, C.c_void_p(frame_ptr or None), width, height, C.c_void_p(out_ptr or None), C.c_void_p(stream or None),
+                                           C.byref(ms) if timed else None), "png_deflate_rgba8")
+    else:
+        _check(lib().ptl_png_deflate_rgba8_codes(device, C.c_void_p(frame_ptr or None), width, height, int(codes), C.c_void_p(out_ptr or None), C.c_void_p(stream or None),
+                                                 C.byref(ms) if timed else None), "png_deflate_rgba8_codes")
     return ms.value if timed else None
 
 

@@ -24,6 +24,8 @@ int usage() {  // (and the exit status that goes with it)
                  "                  [--png-depth 8|16]   16: a 16-bit RGB file made on the GPU from the frame's float output (one quantisation, to 16 bits); one GPU\n"
                  "                  [--png-encoder host|gpu]  gpu: the 8-bit file's deflate stream is made on the GPU (fixed Huffman codes, runs only: about twice the size);\n"
                  "                                       the host adds the chunk framing and CRCs.  One GPU; not with --png-depth 16\n"
+                 "                  [--png-codes fixed|dynamic]  with the gpu encoder: fixed (default) or dynamic, a Huffman code per band of the stream, made on the GPU:\n"
+                 "                                       the same pixels in a file of about the host encoder's size at 4K\n"
                  "                  [--passes depth,trips]  beside the frame: <output stem>.depth.png (nearest final depth, scaled between the scene's depth-map bounds) and\n"
                  "                                       <output stem>.trips.png (bounce-loop trips per pixel), 16-bit greyscale, from the tracer's pass records; one GPU\n"
                  "                  [--depth-report]     one line: how many paths --render-depth cut short (they are drawn black), in how many pixels; the deepest pixel; the depth range\n"
@@ -47,6 +49,8 @@ int usage() {  // (and the exit status that goes with it)
                  "                  [--png-encoder host|gpu]  with --frames png: gpu deflates every 8-bit frame on the GPU (fixed Huffman codes, runs only), so an encoder thread\n"
                  "                                       only frames the stream and computes its CRC; the files are about twice the size.  Works with --shard K/N and resumes;\n"
                  "                                       the stills stay host-encoded.  Not with --frames y4m or --png-depth 16\n"
+                 "                  [--png-codes fixed|dynamic]  with the gpu encoder: fixed (default) or dynamic, a Huffman code per band of every frame's stream, made on\n"
+                 "                                       the GPU: the same pixels, files of about the host encoder's size at 4K instead of twice that\n"
                  "                  [--depth-report]     one line per clip: how many paths --render-depth cut short, in how many pixels, and the frame that lost most\n"
                  "                  [--clip-adaptive-aa [T]]  adaptive anti-aliasing of every sub-frame: one sample per pixel, --aa-count samples only where a pixel differs\n"
                  "                                       from a neighbour by more than T codes (default 4, -1 .. 255); opt-in, approximate by design\n"
@@ -273,7 +277,9 @@ int render_frame(const Options& o) {
         } else if ((with_records ? ptl_renderer_draw_passes(r, &frame, dev, nullptr, records, record_bytes, nullptr, nullptr, &ms) : ptl_renderer_draw(r, &frame, dev, nullptr, nullptr, nullptr, &ms)) != PTL_OK)
             return fail("render");
         float deflate_ms = 0.0f;
-        if (ptl_png_deflate_rgba8(devices[0], dev, o.width, o.height, dev_result, nullptr, o.timing ? &deflate_ms : nullptr) != PTL_OK) return fail("png_deflate_rgba8");
+        if ((o.png_codes == PTL_PNG_CODES_FIXED ? ptl_png_deflate_rgba8(devices[0], dev, o.width, o.height, dev_result, nullptr, o.timing ? &deflate_ms : nullptr)
+                                                : ptl_png_deflate_rgba8_codes(devices[0], dev, o.width, o.height, o.png_codes, dev_result, nullptr, o.timing ? &deflate_ms : nullptr)) != PTL_OK)
+            return fail("png_deflate_rgba8");
         const size_t header_bytes = PTL_PNG_STREAM_HEADER_BYTES;
         deflated.resize(header_bytes);
         if (ptl_device_download(deflated.data(), dev_result, header_bytes, nullptr) != PTL_OK) return fail("download");
@@ -576,6 +582,12 @@ int main(int argc, char** argv) {
             o.png_gpu = encoder == "gpu";
             o.have_png_encoder = true;
         }
+        else if (a == "--png-codes") {
+            std::string codes = next();
+            if (codes != "fixed" && codes != "dynamic") return refuse("--png-codes fixed|dynamic");
+            o.png_codes = codes == "dynamic" ? PTL_PNG_CODES_DYNAMIC : PTL_PNG_CODES_FIXED;
+            o.have_png_codes = true;
+        }
         else if (a == "--gpus") o.gpus = std::atoi(next());
         else if (a == "--devices") o.devices = next();
         else if (a == "--transport") o.transport = next();
@@ -650,6 +662,8 @@ int main(int argc, char** argv) {
     if (o.png_depth == 16 && cmd == "render-frame" && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.multi_process || o.shards > 1 || o.transport == "rccl"))
         return refuse("render-frame --png-depth 16 draws the frame on one GPU: frame groups gather RGBA8, so it cannot be combined with --gpus N, N > 1, several --devices, --multi-process, --transport rccl or --shard");
     if (o.have_png_encoder && cmd != "render" && cmd != "render-frame") return refuse("--png-encoder is an option of render and render-frame: it chooses who deflates the PNG frames of a clip, or the one frame");
+    if (o.have_png_codes && cmd != "render" && cmd != "render-frame") return refuse("--png-codes is an option of render and render-frame: it chooses the Huffman codes of the streams the gpu PNG encoder makes");
+    if (o.have_png_codes && !o.png_gpu) return refuse("--png-codes needs --png-encoder gpu: it chooses the Huffman codes of the deflate streams made on the GPU; the host encoder is zlib");
     if (o.png_gpu && o.y4m) return refuse("--png-encoder gpu cannot be combined with --frames y4m: a stream holds no PNG frames");
     if (o.png_gpu && o.png_depth == 16) return refuse("--png-encoder gpu cannot be combined with --png-depth 16: the GPU deflates 8-bit frames only (runs at distance 1 do not catch the 16-bit rows)");
     if (o.png_gpu && cmd == "render-frame" && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.multi_process || o.shards > 1 || o.transport == "rccl"))

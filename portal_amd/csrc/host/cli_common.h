@@ -26,6 +26,8 @@ struct Options {
     bool have_png_depth = false;  // --png-depth was given
     bool png_gpu = false;         // render / render-frame --png-encoder host|gpu: gpu deflates the 8-bit frames on the card (ptl_png_deflate_rgba8), the host only frames the stream
     bool have_png_encoder = false;  // --png-encoder was given
+    int png_codes = 0;              // render / render-frame --png-codes fixed|dynamic, with --png-encoder gpu: PTL_PNG_CODES_FIXED or _DYNAMIC (ptl_png_deflate_rgba8_codes)
+    bool have_png_codes = false;    // --png-codes was given
     int batch = -1;       // render --batch-subframes 0|1: one launch for a frame's blur sub-frames (default: on where 2 <= blur <= 16)
     std::vector<std::pair<std::string, double>> sets;  // --set name=value
     bool timing = false;  // --timing: wait for every kernel and report GPU milliseconds (serialises host and GPU)

@@ -307,7 +307,8 @@ struct SceneRun {
     const int height = o.height;
     const int threads = (int)std::min(64u, std::max(2u, std::thread::hardware_concurrency() * 3 / 4));  // PNG encoders
     const size_t frame_bytes = (size_t)width * height * 4;   // an RGBA8 frame: a sub-frame, a still
-    size_t result_bytes = 0;                                  // a frame as it leaves the card
+    size_t result_bytes = 0;                                  // a frame's result buffer on the card
+    size_t download_bytes = 0;                                // what of it leaves the card
     ScenePtr scene;
     RendererPtr r;
     std::unique_ptr<void, HandleFree> subframe_block;  // ONE allocation, sub-frame j at j * bytes: what the one-launch form writes (slice z behind slice z - 1)
@@ -328,7 +329,8 @@ public:
     FrameOutput(const SceneRun& run, const Clip& clip)
         : video_base(run.o.out_dir + "/video/" + run.name + "/" + clip.name), run_(run), o_(run.o), clip_(clip.name), fps_(clip.fps) {}
     virtual ~FrameOutput() = default;
-    virtual size_t result_bytes() const = 0;  // one frame as it leaves the card
+    virtual size_t result_bytes() const = 0;  // one frame's result buffer on the card
+    virtual size_t download_bytes() const { return result_bytes(); }  // what of it leaves the card: the page-locked buffers and the copy
     virtual int open() = 0;                   // 0, or the exit status
     virtual int check() { return 0; }         // before every frame: 0 while frames can still leave, else the exit status (reported)
     virtual bool have(int i) const = 0;       // frame i is already there: it is not drawn again
@@ -407,12 +409,14 @@ public:
 };
 
 // The same 8-bit files with the deflate done on the card (--png-encoder gpu): the frame -- averaged into one device frame where blur > 1, else the
-// single sub-frame -- goes through ptl_png_deflate_rgba8, what leaves the card is its result buffer (the whole of it: a budgeted download is a
-// follow-up), and an encoder thread only frames the stream (ptl_png_write_stream).  Names, have(), shards, resume and encode_video are PngOutput's.
+// single sub-frame -- goes through ptl_png_deflate_rgba8 (or, with --png-codes dynamic, ptl_png_deflate_rgba8_codes), what leaves the card is the
+// result buffer's header and the room for the stream, not the kernels' scratch behind them (a download of exactly the stream's bytes, header
+// first, is a follow-up), and an encoder thread only frames the stream (ptl_png_write_stream).  Names, have(), shards, resume and encode_video are PngOutput's.
 class PngGpuOutput : public PngOutput {
 public:
     using PngOutput::PngOutput;
     size_t result_bytes() const override { return ptl_png_stream_bytes(run_.width, run_.height); }
+    size_t download_bytes() const override { return ptl_png_stream_download_bytes(run_.width, run_.height); }
     bool draws_result() const override { return false; }  // (one sub-frame is deflated where it was drawn)
     int make_result(void* result, float* ms) override {
         const void* frame = run_.subframes[0];
@@ -426,7 +430,9 @@ public:
             if (ptl_average_images(o_.device, run_.subframes.data(), o_.blur, averaged_.get(), run_.width, run_.height, nullptr, ms ? &average_ms : nullptr) != PTL_OK) return fail("average_images");
             frame = averaged_.get();
         }
-        if (ptl_png_deflate_rgba8(o_.device, frame, run_.width, run_.height, result, nullptr, ms ? &deflate_ms : nullptr) != PTL_OK) return fail("png_deflate_rgba8");
+        if ((o_.png_codes == PTL_PNG_CODES_FIXED ? ptl_png_deflate_rgba8(o_.device, frame, run_.width, run_.height, result, nullptr, ms ? &deflate_ms : nullptr)
+                                                 : ptl_png_deflate_rgba8_codes(o_.device, frame, run_.width, run_.height, o_.png_codes, result, nullptr, ms ? &deflate_ms : nullptr)) != PTL_OK)
+            return fail("png_deflate_rgba8");
         if (ms) *ms = average_ms + deflate_ms;
         return 0;
     }
@@ -545,7 +551,7 @@ double subframe_time(int i, int j, int count, int blur) {
 // One of the clip's .start.png / .end.png stills: an RGBA8 sub-frame, through the clip's pool and, where one fits, its page-locked buffers
 // (they hold frames as they leave the card; a 4:2:0 one is smaller than an RGBA8 one: the two stills of such a clip take pageable memory)
 int write_still(const SceneRun& run, ClipRun& c, const void* device_frame, const std::string& name) {
-    uint8_t* pinned = run.frame_bytes <= run.result_bytes ? c.pinned.take() : nullptr;
+    uint8_t* pinned = run.frame_bytes <= run.download_bytes ? c.pinned.take() : nullptr;
     auto pageable = std::make_shared<std::vector<uint8_t>>(pinned ? 0 : run.frame_bytes);
     uint8_t* still = pinned ? pinned : pageable->data();
     if (ptl_device_download(still, device_frame, run.frame_bytes, nullptr) != PTL_OK) return fail("download");
@@ -672,7 +678,7 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
         uint8_t* pixels = c.pinned.take();  // blocks while every buffer is still being encoded
         void* arrived = nullptr;
         if (ptl_event_record(pipe.produced, nullptr) != PTL_OK || ptl_stream_wait_event(pipe.copy_stream, pipe.produced) != PTL_OK ||
-            ptl_device_download_async(pixels, pipe.results[slot], run.result_bytes, pipe.copy_stream) != PTL_OK ||
+            ptl_device_download_async(pixels, pipe.results[slot], run.download_bytes, pipe.copy_stream) != PTL_OK ||
             ptl_event_record(pipe.copied[slot], pipe.copy_stream) != PTL_OK || ptl_event_create(pipe.device, &arrived) != PTL_OK ||
             ptl_event_record(arrived, pipe.copy_stream) != PTL_OK)
             return fail("download");
@@ -707,8 +713,8 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
 int render_clip(SceneRun& run, const Clip& clip) {
     auto clip_start = std::chrono::steady_clock::now();
     // frames in flight between download and encode: one per encoder thread, but no more than ~2 GB of page-locked memory
-    int in_flight = (int)std::max<size_t>(4, std::min<size_t>((size_t)run.threads + 2, ((size_t)2 << 30) / run.result_bytes));
-    ClipRun c{{run.result_bytes, in_flight}, {run.threads, (size_t)run.threads * 2}, make_output(run, clip, (size_t)in_flight)};
+    int in_flight = (int)std::max<size_t>(4, std::min<size_t>((size_t)run.threads + 2, ((size_t)2 << 30) / run.download_bytes));
+    ClipRun c{{run.download_bytes, in_flight}, {run.threads, (size_t)run.threads * 2}, make_output(run, clip, (size_t)in_flight)};
     if (!c.pinned.ok()) return fail("pinned host memory");
     return c.out->close(trace_clip(run, c, clip), c.pool, clip_start);
 }
@@ -831,6 +837,7 @@ int render_scene(const Options& o, const std::string& path) {
     ptl_renderer_set_option(r, "draw_side_by_side", o.stereo ? 1 : 0);
     const std::unique_ptr<FrameOutput> form = make_output(run, Clip{}, 1);  // (an output that is never opened)
     run.result_bytes = form->result_bytes();
+    run.download_bytes = form->download_bytes();
     void* block = nullptr;
     run.subframes.assign((size_t)std::max(1, o.blur), nullptr);
     if (ptl_device_alloc(o.device, run.frame_bytes * run.subframes.size(), &block) != PTL_OK) return fail("alloc");

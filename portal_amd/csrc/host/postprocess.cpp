@@ -276,9 +276,18 @@ static_assert(PTL_PNG_STREAM_HEADER_BYTES == ptl_png_header_bytes, "the header t
 extern "C" size_t ptl_png_stream_bytes(int width, int height) {
     return width > 0 && height > 0 && ptl_png_fits((unsigned)width, (unsigned)height) ? (size_t)ptl_png_result_bytes((unsigned)width, (unsigned)height) : 0;
 }
+extern "C" size_t ptl_png_stream_download_bytes(int width, int height) {
+    return width > 0 && height > 0 && ptl_png_fits((unsigned)width, (unsigned)height) ? (size_t)ptl_png_table_offset((unsigned)width, (unsigned)height) : 0;
+}
 extern "C" int ptl_png_stream_band_rows(int width) { return width > 0 && width <= (1 << 29) ? (int)ptl_png_band_rows((unsigned)width) : 0; }
 
-extern "C" int ptl_png_deflate_rgba8(int device, const void* frame_rgba8, int width, int height, void* out, void* stream, float* elapsed_ms) {
+// `codes`: PTL_PNG_CODES_FIXED launches the bands kernel of png_deflate.hip, PTL_PNG_CODES_DYNAMIC the one of png_huffman.hip, which writes the same
+// table entries and slots; the pack kernel is the same for both.
+extern "C" int ptl_png_deflate_rgba8_codes(int device, const void* frame_rgba8, int width, int height, int codes, void* out, void* stream, float* elapsed_ms) {
+    if (codes != PTL_PNG_CODES_FIXED && codes != PTL_PNG_CODES_DYNAMIC) {
+        set_last_error("png_deflate_rgba8_codes: codes " + std::to_string(codes) + " is neither PTL_PNG_CODES_FIXED (0) nor PTL_PNG_CODES_DYNAMIC (1)");
+        return PTL_ERR_INVALID;
+    }
     if (!frame_rgba8 || !out || width <= 0 || height <= 0) return PTL_ERR_INVALID;
     if ((reinterpret_cast<uintptr_t>(frame_rgba8) | reinterpret_cast<uintptr_t>(out)) & 15u) return PTL_ERR_INVALID;
     if (!ptl_png_fits((unsigned)width, (unsigned)height)) {  // the kernels address the raw scanlines with 32-bit offsets
@@ -287,7 +296,10 @@ extern "C" int ptl_png_deflate_rgba8(int device, const void* frame_rgba8, int wi
     }
     if (device < 0) return PTL_ERR_NO_DEVICE;
     LoadedKernel *bands_kernel = nullptr, *pack_kernel = nullptr;
-    if (int rc = load_kernel(device, "png_deflate.hsaco", "ptl_png_deflate_bands_kernel", &bands_kernel); rc != PTL_OK) return rc;
+    if (int rc = codes == PTL_PNG_CODES_DYNAMIC ? load_kernel(device, "png_huffman.hsaco", "ptl_png_huffman_bands_kernel", &bands_kernel)
+                                                : load_kernel(device, "png_deflate.hsaco", "ptl_png_deflate_bands_kernel", &bands_kernel);
+        rc != PTL_OK)
+        return rc;
     if (int rc = load_kernel(device, "png_deflate.hsaco", "ptl_png_deflate_pack_kernel", &pack_kernel); rc != PTL_OK) return rc;
     const hip::Runtime* rt = hip::runtime(nullptr);
     rt->hipSetDevice(device);
@@ -308,6 +320,10 @@ extern "C" int ptl_png_deflate_rgba8(int device, const void* frame_rgba8, int wi
         return PTL_ERR_HIP;
     }
     return PTL_OK;
+}
+
+extern "C" int ptl_png_deflate_rgba8(int device, const void* frame_rgba8, int width, int height, void* out, void* stream, float* elapsed_ms) {
+    return ptl_png_deflate_rgba8_codes(device, frame_rgba8, width, height, PTL_PNG_CODES_FIXED, out, stream, elapsed_ms);
 }
 
 // ---- trace passes: the records a PTL_FLAG_PASSES render entry stores (portal_amd/csrc/kernels/pass_stats.hip, pass_gray16.hip; the contracts are

@@ -7,8 +7,10 @@ warm-up launches, then `--launches` calls back to back between ONE pair of event
 reported with the spread beside it.  A call of ptl_png_deflate_rgba8 is both kernels; their split is read from a kernel trace of this tool
 (rocprofv3 --kernel-trace --stats -- python tools/png_deflate_bench.py --launches 20 --repeats 1).  The stream of every frame is inflated
 with zlib and compared with the frame's raw scanlines, and its size is printed beside zlib's at levels 1 and 3.  One JSON line per cell.
+`--codes dynamic` measures ptl_png_deflate_rgba8_codes with a Huffman code per band (ptl_png_huffman_bands_kernel,
+portal_amd/csrc/kernels/png_huffman.hip, and the same pack kernel) instead; `--codes fixed,dynamic` both, alternating in the one session.
 
-    python tools/png_deflate_bench.py [--launches 200] [--repeats 7] [--sizes 3840x2160] [--subframes 4]
+    python tools/png_deflate_bench.py [--launches 200] [--repeats 7] [--sizes 3840x2160] [--subframes 4] [--codes fixed|dynamic|fixed,dynamic]
 """
 import argparse
 import json
@@ -49,7 +51,13 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--sizes", default="3840x2160")
     ap.add_argument("--subframes", type=int, default=4)
+    ap.add_argument("--codes", default="fixed", help="fixed, dynamic, or both separated by a comma")
     args = ap.parse_args()
+    modes = args.codes.split(",")
+    if not modes or any(m not in ("fixed", "dynamic") for m in modes) or len(set(modes)) != len(modes):
+        sys.exit("png_deflate_bench: --codes fixed|dynamic|fixed,dynamic")
+    CODES = {"fixed": pa.PNG_CODES_FIXED, "dynamic": pa.PNG_CODES_DYNAMIC}
+    label = {"fixed": "ptl_png_deflate_rgba8:", "dynamic": "ptl_png_deflate_rgba8_codes[dynamic]:"}
     import torch
 
     if pa.device_count() < 1:
@@ -71,17 +79,18 @@ if __name__ == "__main__":
         staged = {name: torch.from_numpy(f).to(dev) for name, f in frames.items()}
         kernels = {f"ptl_average_images:n={n}": lambda: pa.average_images_device([s.data_ptr() for s in subs], averaged.data_ptr(), w, h, stream=raw_stream)}
         for name, t in staged.items():
-            kernels["ptl_png_deflate_rgba8:" + name] = lambda t=t: pa.png_deflate_rgba8_device(t.data_ptr(), out.data_ptr(), w, h, stream=raw_stream)
+            for mode in modes:
+                kernels[label[mode] + name] = lambda t=t, mode=mode: pa.png_deflate_rgba8_device(t.data_ptr(), out.data_ptr(), w, h, stream=raw_stream, codes=CODES[mode])
         sizes = {}
-        for name, t in staged.items():  # what the stream is, before anything is timed
-            pa.png_deflate_rgba8_device(t.data_ptr(), out.data_ptr(), w, h, stream=raw_stream)
+        for name, t, mode in [(name, t, mode) for name, t in staged.items() for mode in modes]:  # what the stream is, before anything is timed
+            pa.png_deflate_rgba8_device(t.data_ptr(), out.data_ptr(), w, h, stream=raw_stream, codes=CODES[mode])
             torch.cuda.synchronize()
             host = out[:64].cpu().numpy().tobytes()
             count, adler = struct.unpack("<I", host[12:16])[0], struct.unpack("<I", host[16:20])[0]
             body = out[64: 64 + count].cpu().numpy().tobytes()
             raw = raw_scanlines(frames[name])
             assert zlib.decompress(b"\x78\x01" + body + b"\x03\x00" + struct.pack(">I", adler)) == raw, name
-            sizes[name] = {"raw": len(raw), "stream": count, "zlib1": len(zlib.compress(raw, 1)), "zlib3": len(zlib.compress(raw, 3))}
+            sizes[label[mode] + name] = {"raw": len(raw), "stream": count, "zlib1": len(zlib.compress(raw, 1)), "zlib3": len(zlib.compress(raw, 3))}
         times = {name: [] for name in kernels}
         for launch in kernels.values():  # warm-up: code objects loaded, clocks up, every buffer touched
             for _ in range(20):
@@ -97,7 +106,7 @@ if __name__ == "__main__":
             if name.startswith("ptl_average_images"):
                 line["TB/s"] = round((4 * n + 4) * w * h / ms / 1e9, 3)
             else:
-                s = sizes[name.split(":")[1]]
+                s = sizes[name]
                 line.update(s)
                 line["GB/s_of_raw"] = round(s["raw"] / ms / 1e6, 1)
                 line["result_buffer_bytes"] = pa.png_stream_bytes(w, h)
