@@ -943,6 +943,51 @@ int ptl_png_deflate_rgba8_codes(int device, const void* frame_rgba8, int width, 
  * PTL_ERR_INVALID, and nothing is written. */
 int ptl_png_write_stream(const char* path, const uint8_t* result, int width, int height);
 
+/* ---- GPU deflate of a 16-bit PNG frame: matches at pixel distance (opt-in: `--png16-encoder gpu`) -------------------------
+ * ptl_png_deflate_rgb48 turns the rows of a 16-bit RGB frame that are already on the card into the deflate stream of its filtered scanlines;
+ * ptl_png_write_stream_rgb48 frames it.  In such a row neighbouring samples lie 6 bytes apart, so a run of equal pixels, or a vertical
+ * gradient after the Up filter, repeats with period 6, not 1: every match is at distance 6.  tests/png16_deflate_reference.py restates what
+ * follows, and any inflater returns `raw16` from the stream.
+ * Input.  rows_rgb48: DEVICE pointer, the UNFILTERED rows of ptl_average_f32_to_rgb48(..., PTL_PNG_FILTER_NONE, ...): H rows of 6 W bytes,
+ *   big-endian samples, packed.  Its raw scanlines `raw16`, H (6 W + 1) bytes: per row a filter-type byte, 0 for row 0 and 2 (Up) for every
+ *   other row, then the row's 6 W bytes, each minus the byte above it mod 256 (row 0 unchanged).
+ * Bands.  `raw16` is cut into bands of whole rows, ptl_png_stream16_band_rows(W) = max(1, floor(16384 / (6 W + 1))) rows each (the last band
+ *   may have fewer); inside a band `raw16` is cut into segments of 4096 bytes (the last of a band may be shorter).  No match reaches before
+ *   its segment: the parse stays local, and a segment's Adler-32 partial sums stay within 32 bits.
+ * Tokens of a segment.  Byte i, counted from the segment's start, is covered when i >= 6 and s[i] == s[i - 6].  Every byte that is not covered
+ *   is a literal.  It is followed by the maximal stretch of m covered bytes behind it: while m >= 3, a match of length min(m, 258) at distance
+ *   6, m less that length; the remaining m (0, 1 or 2) bytes as literals.  The first six bytes of a segment are literals.  (With "covered"
+ *   read as "equal to the previous byte" this is the rule of ptl_png_deflate_rgba8.)
+ * Distance code.  Distance 6 is distance symbol 4 with one extra bit of value 1.  Fixed block: the five bits 00100 (most-significant bit
+ *   first, like every Huffman code), then the extra bit.  Dynamic block: HDIST = 4, distance code lengths 0 0 0 0 1 (one code, one bit, sent
+ *   as 0), then the extra bit.
+ * Bits of a band.  As ptl_png_deflate_rgba8_codes states them -- the histogram, the two-queue builder with limit 15 and its repair, the
+ *   canonical codes, the contract's one code-length code, HCLEN = 15 -- with HDIST = 4 in the block header, and the sequence that the greedy
+ *   16 / 17 / 18 rule codes being the HLIT + 257 literal/length lengths followed by the five distance lengths, as one sequence.  Then the
+ *   tokens, end-of-block and an empty stored block (three 0 bits, zero padding to the byte, 00 00 FF FF).
+ * Choice.  dynamic bits = header + sum count[s] (length[s] + extra bits) + 2 per match; fixed bits = 3 + sum count[s] (fixed length[s] + extra
+ *   bits) + 6 per match, end-of-block in both.  With PTL_PNG_CODES_DYNAMIC the band is the dynamic block where dynamic bits < fixed bits, else
+ *   the fixed block; PTL_PNG_CODES_FIXED forces the fixed block in every band, through the same kernel.
+ * The zlib stream of the file: 78 01, the bands in order, 03 00 (an empty final fixed block), Adler-32 of `raw16`, big-endian.
+ * Capacity.  A fixed match costs at most 8 + 5 + 5 + 1 bits for at least 3 bytes, still under 9 per byte, so a band of n raw bytes needs at
+ *   most ceil((9 n + 20) / 8) + 4 bytes, and every band's slot is sized from that bound (rounded up to 16).
+ * out: DEVICE pointer, 16-byte aligned, ptl_png_stream16_bytes(W, H) bytes, laid out as the result buffer of ptl_png_deflate_rgba8: the
+ *   64-byte header, room for the stream, a 16-byte table entry per band, the bands' slots.  The header's magic word is "PTL6" (0x364c5450), so
+ *   that neither writer takes the other's buffer; words 1 .. 6 are W, H, the stream's byte count n, Adler-32 of `raw16`, rows per band, number
+ *   of bands; the remaining nine words are zero.  Nothing in `out` has to be cleared between calls.
+ * Refused before any GPU call (PTL_ERR_INVALID): any `codes` but the two (before anything else is looked at), null or not 16-byte aligned
+ * pointers, sizes <= 0, W H > 2^28 (the rows' own limit), H (6 W + 1) > 2^31; the size functions are 0 for such a size.  Two kernels
+ * (portal_amd/csrc/kernels/png_deflate16.hip) on `stream`, elapsed_ms != NULL waits and reports both. */
+size_t ptl_png_stream16_bytes(int width, int height);
+size_t ptl_png_stream16_download_bytes(int width, int height); /* the header and the room for the longest stream (rounded up to 16) */
+int ptl_png_stream16_band_rows(int width);                     /* rows per band; 0 for a width that is not positive */
+int ptl_png_deflate_rgb48(int device, const void* rows_rgb48, int width, int height, int codes, void* out, void* stream, float* elapsed_ms);
+/* The file from a HOST copy of that buffer (the header and the stream's n bytes are read, nothing behind them): signature, IHDR (bit depth 16,
+ * colour type 2), ONE IDAT = 78 01 + stream + 03 00 + Adler-32, IEND.  No per-pixel work and no zlib call but crc32.  The header checks are
+ * those of ptl_png_write_stream, against the magic word, the band cut and the room of THIS format (an 8-bit "PTLZ" buffer is refused): a
+ * mismatch is PTL_ERR_INVALID, and nothing is written. */
+int ptl_png_write_stream_rgb48(const char* path, const uint8_t* result, int width, int height);
+
 /* ---- template engine test hooks (src/code_generation.rs) ----------------------------------- */
 typedef struct ptl_strstore ptl_strstore;
 ptl_strstore* ptl_strstore_new(void);

@@ -198,6 +198,11 @@ def _load() -> C.CDLL:
         "ptl_png_deflate_rgba8": (ci, [ci, vp, ci, ci, vp, vp, P(C.c_float)]),
         "ptl_png_deflate_rgba8_codes": (ci, [ci, vp, ci, ci, ci, vp, vp, P(C.c_float)]),
         "ptl_png_write_stream": (ci, [cp, vp, ci, ci]),
+        "ptl_png_stream16_bytes": (cs, [ci, ci]),
+        "ptl_png_stream16_band_rows": (ci, [ci]),
+        "ptl_png_stream16_download_bytes": (cs, [ci, ci]),
+        "ptl_png_deflate_rgb48": (ci, [ci, vp, ci, ci, ci, vp, vp, P(C.c_float)]),
+        "ptl_png_write_stream_rgb48": (ci, [cp, vp, ci, ci]),
         "ptl_pass_record_bytes": (cs, [ci, ci]),
         "ptl_kernel_render_passes": (ci, [vp, P(Frame), vp, vp, vp, cs, vp, vp, P(C.c_float)]),
         "ptl_kernel_render_slices_passes": (ci, [vp, P(Frame), ci, vp, vp, vp, cs, C.c_ulonglong, vp, P(C.c_float)]),
@@ -1089,6 +1094,43 @@ def png_write_stream(path: str, result, width: int, height: int) -> None:
     if a.size < PNG_STREAM_HEADER_BYTES or a.size < PNG_STREAM_HEADER_BYTES + int(a[12:16].view("<u4")[0]):
         raise PortalError("png_write_stream: the buffer is shorter than its header and the stream the header announces")
     _check(lib().ptl_png_write_stream(path.encode(), a.ctypes.data, width, height), "png_write_stream")
+
+
+def png_stream16_bytes(width: int, height: int) -> int:
+    """Bytes of the result buffer of `png_deflate_rgb48_device`: header, room for the longest stream, and the kernels' scratch behind it; 0 for
+    a size that is not positive, has more than 2^28 pixels or whose scanlines exceed 2^31 bytes."""
+    return int(lib().ptl_png_stream16_bytes(width, height))
+
+
+def png_stream16_download_bytes(width: int, height: int) -> int:
+    """The part of that result buffer a host needs: the header and the room for the longest stream."""
+    return int(lib().ptl_png_stream16_download_bytes(width, height))
+
+
+def png_stream16_band_rows(width: int) -> int:
+    """Rows of the 16-bit frame per band of the stream."""
+    return int(lib().ptl_png_stream16_band_rows(width))
+
+
+def png_deflate_rgb48_device(rows_ptr: int, out_ptr: int, width: int, height: int, device: int = 0, stream: int = 0, timed: bool = False, codes: int = PNG_CODES_DYNAMIC):
+    """ptl_png_deflate_rgb48 on DEVICE buffers given as integer addresses: the unfiltered rows of `average_f32_to_rgb48_device`
+    (PNG_FILTER_NONE) at rows_ptr -> at out_ptr (`png_stream16_bytes(width, height)` bytes) a 64-byte header ("PTL6") and the deflate stream
+    of the rows' Up-filtered scanlines: literals and matches at distance 6, a Huffman code per band, or with ``codes=PNG_CODES_FIXED`` the
+    fixed block in every band (the contract is in include/portal_amd.h).  Returns the time of both kernels in ms when ``timed`` (waits),
+    else None."""
+    ms = C.c_float()
+    _check(lib().ptl_png_deflate_rgb48(device, C.c_void_p(rows_ptr or None), width, height, int(codes), C.c_void_p(out_ptr or None), C.c_void_p(stream or None),
+                                       C.byref(ms) if timed else None), "png_deflate_rgb48")
+    return ms.value if timed else None
+
+
+def png_write_stream_rgb48(path: str, result, width: int, height: int) -> None:
+    """ptl_png_write_stream_rgb48: a 16-bit RGB PNG from a HOST copy of the result buffer of `png_deflate_rgb48_device` (bytes or a uint8
+    array: the header and the stream it announces, at least); the host adds the chunk framing and CRCs, nothing else."""
+    a = np.ascontiguousarray(np.frombuffer(result, dtype=np.uint8) if isinstance(result, (bytes, bytearray, memoryview)) else result, dtype=np.uint8)
+    if a.size < PNG_STREAM_HEADER_BYTES or a.size < PNG_STREAM_HEADER_BYTES + int(a[12:16].view("<u4")[0]):
+        raise PortalError("png_write_stream_rgb48: the buffer is shorter than its header and the stream the header announces")
+    _check(lib().ptl_png_write_stream_rgb48(path.encode(), a.ctypes.data, width, height), "png_write_stream_rgb48")
 
 
 # ---- trace passes (include/portal_amd.h: ptl_pass_record, ptl_pass_stats_block) ------------------------------------------------------

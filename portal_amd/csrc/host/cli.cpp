@@ -26,6 +26,8 @@ int usage() {  // (and the exit status that goes with it)
                  "                                       the host adds the chunk framing and CRCs.  One GPU; not with --png-depth 16\n"
                  "                  [--png-codes fixed|dynamic]  with the gpu encoder: fixed (default) or dynamic, a Huffman code per band of the stream, made on the GPU:\n"
                  "                                       the same pixels in a file of about the host encoder's size at 4K\n"
+                 "                  [--png16-encoder host|gpu]  with --png-depth 16: gpu deflates the 16-bit file's scanlines on the GPU (Up filter, matches at pixel distance,\n"
+                 "                                       a Huffman code per band); the host adds the chunk framing and CRCs.  host (default): zlib\n"
                  "                  [--passes depth,trips]  beside the frame: <output stem>.depth.png (nearest final depth, scaled between the scene's depth-map bounds) and\n"
                  "                                       <output stem>.trips.png (bounce-loop trips per pixel), 16-bit greyscale, from the tracer's pass records; one GPU\n"
                  "                  [--depth-report]     one line: how many paths --render-depth cut short (they are drawn black), in how many pixels; the deepest pixel; the depth range\n"
@@ -51,6 +53,9 @@ int usage() {  // (and the exit status that goes with it)
                  "                                       the stills stay host-encoded.  Not with --frames y4m or --png-depth 16\n"
                  "                  [--png-codes fixed|dynamic]  with the gpu encoder: fixed (default) or dynamic, a Huffman code per band of every frame's stream, made on\n"
                  "                                       the GPU: the same pixels, files of about the host encoder's size at 4K instead of twice that\n"
+                 "                  [--png16-encoder host|gpu]  with --png-depth 16: gpu deflates every 16-bit frame on the GPU (Up filter, matches at pixel distance, a Huffman\n"
+                 "                                       code per band), so an encoder thread only frames the stream and computes its CRC; files about 1.3 - 1.4 times the\n"
+                 "                                       host encoder's.  Works with --shard K/N and resumes; host (default): zlib level 3 on the encoder threads\n"
                  "                  [--depth-report]     one line per clip: how many paths --render-depth cut short, in how many pixels, and the frame that lost most\n"
                  "                  [--clip-adaptive-aa [T]]  adaptive anti-aliasing of every sub-frame: one sample per pixel, --aa-count samples only where a pixel differs\n"
                  "                                       from a neighbour by more than T codes (default 4, -1 .. 255); opt-in, approximate by design\n"
@@ -309,8 +314,29 @@ int render_frame(const Options& o) {
                    PTL_OK)
             return fail("render");
         const void* one[1] = {dev32};
-        if (ptl_average_f32_to_rgb48(devices[0], one, 1, dev_rows, o.width, o.height, PTL_PNG_FILTER_SUB, nullptr, nullptr) != PTL_OK) return fail("average_f32_to_rgb48");
-        if (ptl_device_download(rows16.data(), dev_rows, rows16.size(), nullptr) != PTL_OK) return fail("download");
+        if (o.png16_gpu) {
+            // --png16-encoder gpu: the rows unfiltered, deflated on the card; the header comes down first, then exactly the stream it announces
+            void* dev_result = nullptr;
+            const size_t result_bytes = ptl_png_stream16_bytes(o.width, o.height);
+            if (result_bytes == 0) return fail("--png16-encoder gpu: the frame's scanlines exceed 2^31 bytes");
+            if (ptl_device_alloc(devices[0], result_bytes, &dev_result) != PTL_OK) return fail("device stream");
+            std::unique_ptr<void, HandleFree> own_result(dev_result);
+            float deflate_ms = 0.0f;
+            if (ptl_average_f32_to_rgb48(devices[0], one, 1, dev_rows, o.width, o.height, PTL_PNG_FILTER_NONE, nullptr, nullptr) != PTL_OK) return fail("average_f32_to_rgb48");
+            if (ptl_png_deflate_rgb48(devices[0], dev_rows, o.width, o.height, PTL_PNG_CODES_DYNAMIC, dev_result, nullptr, o.timing ? &deflate_ms : nullptr) != PTL_OK) return fail("png_deflate_rgb48");
+            const size_t header_bytes = PTL_PNG_STREAM_HEADER_BYTES;
+            deflated.resize(header_bytes);
+            if (ptl_device_download(deflated.data(), dev_result, header_bytes, nullptr) != PTL_OK) return fail("download");
+            unsigned int stream_bytes = 0;
+            std::memcpy(&stream_bytes, deflated.data() + 12, 4);
+            if (header_bytes + stream_bytes > result_bytes) return fail("png_deflate_rgb48: the header's byte count");
+            deflated.resize(header_bytes + stream_bytes);
+            if (ptl_device_download(deflated.data() + header_bytes, static_cast<const char*>(dev_result) + header_bytes, stream_bytes, nullptr) != PTL_OK) return fail("download");
+            if (o.timing) std::printf("png16 encoder gpu: deflate %.3f ms, %u bytes of stream downloaded\n", deflate_ms, stream_bytes);
+        } else {
+            if (ptl_average_f32_to_rgb48(devices[0], one, 1, dev_rows, o.width, o.height, PTL_PNG_FILTER_SUB, nullptr, nullptr) != PTL_OK) return fail("average_f32_to_rgb48");
+            if (ptl_device_download(rows16.data(), dev_rows, rows16.size(), nullptr) != PTL_OK) return fail("download");
+        }
     } else if (o.adaptive) {  // one sample per pixel, classification, the flagged pixels again with --aa-count samples: three launches, one download
         void *dev = nullptr, *list = nullptr, *count = nullptr;
         ptl_renderer_set_option(r, "adaptive_aa_threshold", o.adaptive_t);
@@ -357,7 +383,9 @@ int render_frame(const Options& o) {
     double t_draw = seconds_since(t0);
     if (o.png_depth == 16) {
         if (!dir_of(o.output).empty()) make_dirs(dir_of(o.output));
-        if (ptl_png_write_rgb48(o.output.c_str(), rows16.data(), o.width, o.height, PTL_PNG_FILTER_SUB, 6) != PTL_OK) return fail("png");
+        if ((o.png16_gpu ? ptl_png_write_stream_rgb48(o.output.c_str(), deflated.data(), o.width, o.height)
+                         : ptl_png_write_rgb48(o.output.c_str(), rows16.data(), o.width, o.height, PTL_PNG_FILTER_SUB, 6)) != PTL_OK)
+            return fail("png");
     } else if (o.png_gpu) {
         if (!dir_of(o.output).empty()) make_dirs(dir_of(o.output));
         if (ptl_png_write_stream(o.output.c_str(), deflated.data(), o.width, o.height) != PTL_OK) return fail("png");
@@ -588,6 +616,12 @@ int main(int argc, char** argv) {
             o.png_codes = codes == "dynamic" ? PTL_PNG_CODES_DYNAMIC : PTL_PNG_CODES_FIXED;
             o.have_png_codes = true;
         }
+        else if (a == "--png16-encoder") {
+            std::string encoder = next();
+            if (encoder != "host" && encoder != "gpu") return refuse("--png16-encoder host|gpu");
+            o.png16_gpu = encoder == "gpu";
+            o.have_png16_encoder = true;
+        }
         else if (a == "--gpus") o.gpus = std::atoi(next());
         else if (a == "--devices") o.devices = next();
         else if (a == "--transport") o.transport = next();
@@ -661,6 +695,10 @@ int main(int argc, char** argv) {
     if (o.png_depth == 16 && o.y4m) return refuse("--png-depth 16 cannot be combined with --frames y4m: a stream holds no PNG frames (its deep-colour form is --deep-colour)");
     if (o.png_depth == 16 && cmd == "render-frame" && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.multi_process || o.shards > 1 || o.transport == "rccl"))
         return refuse("render-frame --png-depth 16 draws the frame on one GPU: frame groups gather RGBA8, so it cannot be combined with --gpus N, N > 1, several --devices, --multi-process, --transport rccl or --shard");
+    if (o.have_png16_encoder && cmd != "render" && cmd != "render-frame") return refuse("--png16-encoder is an option of render and render-frame: it chooses who deflates the 16-bit PNG frames of a clip, or the one frame");
+    if (o.have_png16_encoder && o.png_depth != 16) return refuse("--png16-encoder needs --png-depth 16: it chooses who deflates the 16-bit frames (the encoder of 8-bit frames is --png-encoder)");
+    if (o.png16_gpu && ptl_png_stream16_bytes(o.stereo ? 2 * o.width : o.width, o.height) == 0)
+        return refuse("--png16-encoder gpu needs a frame of at most 2^28 pixels whose scanlines, H (6 W + 1) bytes, number at most 2^31: the kernels address them with 32-bit offsets");
     if (o.have_png_encoder && cmd != "render" && cmd != "render-frame") return refuse("--png-encoder is an option of render and render-frame: it chooses who deflates the PNG frames of a clip, or the one frame");
     if (o.have_png_codes && cmd != "render" && cmd != "render-frame") return refuse("--png-codes is an option of render and render-frame: it chooses the Huffman codes of the streams the gpu PNG encoder makes");
     if (o.have_png_codes && !o.png_gpu) return refuse("--png-codes needs --png-encoder gpu: it chooses the Huffman codes of the deflate streams made on the GPU; the host encoder is zlib");

@@ -28,6 +28,8 @@ struct Options {
     bool have_png_encoder = false;  // --png-encoder was given
     int png_codes = 0;              // render / render-frame --png-codes fixed|dynamic, with --png-encoder gpu: PTL_PNG_CODES_FIXED or _DYNAMIC (ptl_png_deflate_rgba8_codes)
     bool have_png_codes = false;    // --png-codes was given
+    bool png16_gpu = false;         // render / render-frame --png16-encoder host|gpu, with --png-depth 16: gpu deflates the 16-bit frames on the card (ptl_png_deflate_rgb48)
+    bool have_png16_encoder = false;  // --png16-encoder was given
     int batch = -1;       // render --batch-subframes 0|1: one launch for a frame's blur sub-frames (default: on where 2 <= blur <= 16)
     std::vector<std::pair<std::string, double>> sets;  // --set name=value
     bool timing = false;  // --timing: wait for every kernel and report GPU milliseconds (serialises host and GPU)

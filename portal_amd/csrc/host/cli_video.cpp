@@ -448,6 +448,42 @@ private:
     std::unique_ptr<void, HandleFree> averaged_;  // blur > 1: the averaged RGBA8 frame, on the card
 };
 
+// The 16-bit files with the deflate done on the card (--png-depth 16 --png16-encoder gpu): the float sub-frames are averaged into one device
+// frame of unfiltered 16-bit rows (ptl_average_f32_to_rgb48 with PTL_PNG_FILTER_NONE), those go through ptl_png_deflate_rgb48 (Up filter, matches
+// at pixel distance, a Huffman code per band), what leaves the card is the result buffer's header and the room for the stream, and an encoder
+// thread only frames the stream (ptl_png_write_stream_rgb48).  Names, have(), shards, resume, stills and encode_video are PngOutput's.
+class Png16GpuOutput : public PngOutput {
+public:
+    using PngOutput::PngOutput;
+    size_t result_bytes() const override { return ptl_png_stream16_bytes(run_.width, run_.height); }
+    size_t download_bytes() const override { return ptl_png_stream16_download_bytes(run_.width, run_.height); }
+    bool wants_float() const override { return true; }
+    bool draws_result() const override { return false; }  // (one sub-frame is converted with n = 1)
+    int make_result(void* result, float* ms) override {
+        float rows_ms = 0.0f, deflate_ms = 0.0f;
+        if (!rows_) {
+            void* p = nullptr;
+            if (ptl_device_alloc(o_.device, ptl_rgb48_frame_bytes(run_.width, run_.height), &p) != PTL_OK) return fail("alloc");
+            rows_.reset(p);
+        }
+        if (ptl_average_f32_to_rgb48(o_.device, run_.float_subframes.data(), o_.blur, rows_.get(), run_.width, run_.height, PTL_PNG_FILTER_NONE, nullptr, ms ? &rows_ms : nullptr) != PTL_OK)
+            return fail("average_f32_to_rgb48");
+        if (ptl_png_deflate_rgb48(o_.device, rows_.get(), run_.width, run_.height, PTL_PNG_CODES_DYNAMIC, result, nullptr, ms ? &deflate_ms : nullptr) != PTL_OK) return fail("png_deflate_rgb48");
+        if (ms) *ms = rows_ms + deflate_ms;
+        return 0;
+    }
+    void submit(int i, uint8_t* pixels, void* arrived, EncoderPool& pool, PinnedFrames& pinned) override {
+        pool.submit([pixels, name = frame_name(i), width = run_.width, height = run_.height, arrived, &pinned] {
+            if (ptl_event_synchronize(arrived) != PTL_OK || ptl_png_write_stream_rgb48(name.c_str(), pixels, width, height) != PTL_OK) std::fprintf(stderr, "\n%s\n", ptl_last_error());
+            ptl_event_destroy(arrived);
+            pinned.give(pixels);
+        });
+    }
+
+private:
+    std::unique_ptr<void, HandleFree> rows_;  // the averaged frame as unfiltered 16-bit rows, on the card
+};
+
 // One Y4M stream, written in frame order by a thread of its own.  (A stream is not resumed: it holds every frame, from frame 0.)
 class Y4mOutput : public FrameOutput {
 public:
@@ -526,9 +562,10 @@ public:
     }
 };
 
-std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, size_t max_pending) {  // the ONE place that knows there are five
+std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, size_t max_pending) {  // the ONE place that knows there are six
     if (run.o.y4m && run.o.deep_colour) return std::make_unique<DeepY4mOutput>(run, clip, max_pending);
     if (run.o.y4m) return std::make_unique<Y4mOutput>(run, clip, max_pending);
+    if (run.o.png_depth == 16 && run.o.png16_gpu) return std::make_unique<Png16GpuOutput>(run, clip);
     if (run.o.png_depth == 16) return std::make_unique<Png16Output>(run, clip);
     if (run.o.png_gpu) return std::make_unique<PngGpuOutput>(run, clip);
     return std::make_unique<PngOutput>(run, clip);

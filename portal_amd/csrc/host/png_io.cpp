@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../../include/portal_amd.h"
+#include "../kernels/png_deflate16_shape.h"
 #include "../kernels/png_deflate_shape.h"
 #include "internal.h"
 
@@ -238,16 +239,17 @@ extern "C" int ptl_png_write_gray16(const char* path, const uint8_t* rows, int w
     return write_png_file(path, raw, comp, width, height, 16, 0, level);
 }
 
-// An 8-bit RGBA file from a HOST copy of the result buffer of ptl_png_deflate_rgba8: the GPU has filtered and deflated, the host checks the
-// header, frames the stream as one IDAT (78 01 | stream | 03 00 | Adler-32) and computes the chunk CRCs.  No per-pixel work, no deflate.
-extern "C" int ptl_png_write_stream(const char* path, const uint8_t* result, int width, int height) {
-    if (!path || !result || width <= 0 || height <= 0 || !ptl_png_fits((unsigned)width, (unsigned)height)) return PTL_ERR_INVALID;
+namespace {
+
+// What the two stream writers share: the header of a HOST copy of a result buffer checked against what a W x H frame of that kind has to say
+// (`magic`, the band cut, the room for the stream), then signature, IHDR (`depth`, `colour`), ONE IDAT = 78 01 | stream | 03 00 | Adler-32 with
+// its CRC, IEND.  No per-pixel work, no deflate.  A header that does not match: PTL_ERR_INVALID, nothing written.
+int write_stream_file(const char* path, const uint8_t* result, unsigned w, unsigned h, unsigned magic, unsigned band_rows, unsigned bands, unsigned long long capacity,
+                      unsigned char depth, unsigned char colour, const char* what, const char* from) {
     unsigned word[7];
     std::memcpy(word, result, sizeof word);  // (little-endian, as the card wrote them)
-    const unsigned w = (unsigned)width, h = (unsigned)height;
-    if (word[0] != ptl_png_magic || word[1] != w || word[2] != h || word[5] != ptl_png_band_rows(w) || word[6] != ptl_png_bands(w, h) ||
-        word[3] > ptl_png_stream_capacity(w, h) || word[3] < 6ull * ptl_png_bands(w, h)) {
-        ptl::set_last_error("png_write_stream: the buffer's header is not that of a " + std::to_string(width) + " x " + std::to_string(height) + " frame from ptl_png_deflate_rgba8");
+    if (word[0] != magic || word[1] != w || word[2] != h || word[5] != band_rows || word[6] != bands || word[3] > capacity || word[3] < 6ull * bands) {
+        ptl::set_last_error(std::string(what) + ": the buffer's header is not that of a " + std::to_string(w) + " x " + std::to_string(h) + " frame from " + from);
         return PTL_ERR_INVALID;
     }
     const size_t n = word[3];
@@ -256,7 +258,7 @@ extern "C" int ptl_png_write_stream(const char* path, const uint8_t* result, int
     std::vector<unsigned char> ihdr;
     put_be32(ihdr, w);
     put_be32(ihdr, h);
-    ihdr.insert(ihdr.end(), {8, 6, 0, 0, 0});
+    ihdr.insert(ihdr.end(), {depth, colour, 0, 0, 0});
     write_chunk(out, "IHDR", ihdr.data(), ihdr.size());
     put_be32(out, (unsigned)(n + 8));
     const size_t start = out.size();
@@ -276,6 +278,24 @@ extern "C" int ptl_png_write_stream(const char* path, const uint8_t* result, int
     const bool ok = std::fwrite(out.data(), 1, out.size(), f) == out.size();
     std::fclose(f);
     return ok ? PTL_OK : PTL_ERR_INVALID;
+}
+
+}  // namespace
+
+// An 8-bit RGBA file from a HOST copy of the result buffer of ptl_png_deflate_rgba8: the GPU has filtered and deflated, the host checks the
+// header, frames the stream as one IDAT (78 01 | stream | 03 00 | Adler-32) and computes the chunk CRCs.  No per-pixel work, no deflate.
+extern "C" int ptl_png_write_stream(const char* path, const uint8_t* result, int width, int height) {
+    if (!path || !result || width <= 0 || height <= 0 || !ptl_png_fits((unsigned)width, (unsigned)height)) return PTL_ERR_INVALID;
+    const unsigned w = (unsigned)width, h = (unsigned)height;
+    return write_stream_file(path, result, w, h, ptl_png_magic, ptl_png_band_rows(w), ptl_png_bands(w, h), ptl_png_stream_capacity(w, h), 8, 6, "png_write_stream", "ptl_png_deflate_rgba8");
+}
+
+// The same for a 16-bit RGB file from the result buffer of ptl_png_deflate_rgb48: the other magic word, the band cut of rows of 6 W bytes.
+extern "C" int ptl_png_write_stream_rgb48(const char* path, const uint8_t* result, int width, int height) {
+    if (!path || !result || width <= 0 || height <= 0 || !ptl_png16_fits((unsigned)width, (unsigned)height)) return PTL_ERR_INVALID;
+    const unsigned w = (unsigned)width, h = (unsigned)height;
+    return write_stream_file(path, result, w, h, ptl_png16_magic, ptl_png16_band_rows(w), ptl_png16_bands(w, h), ptl_png16_stream_capacity(w, h), 16, 2, "png_write_stream_rgb48",
+                             "ptl_png_deflate_rgb48");
 }
 
 extern "C" int ptl_png_write(const char* path, const uint8_t* rgba8, int width, int height) { return ptl_png_write_level(path, rgba8, width, height, 6); }

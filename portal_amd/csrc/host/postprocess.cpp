@@ -20,6 +20,7 @@
 
 #include "../../../include/portal_amd.h"
 #include "../kernels/pass_key.h"
+#include "../kernels/png_deflate16_shape.h"
 #include "../kernels/png_deflate_shape.h"
 #include "../kernels/rgb48_shape.h"
 #include "../kernels/yuv_shape.h"
@@ -324,6 +325,58 @@ extern "C" int ptl_png_deflate_rgba8_codes(int device, const void* frame_rgba8, 
 
 extern "C" int ptl_png_deflate_rgba8(int device, const void* frame_rgba8, int width, int height, void* out, void* stream, float* elapsed_ms) {
     return ptl_png_deflate_rgba8_codes(device, frame_rgba8, width, height, PTL_PNG_CODES_FIXED, out, stream, elapsed_ms);
+}
+
+// The GPU deflate of a 16-bit PNG frame (portal_amd/csrc/kernels/png_deflate16.hip; the stream contract is in include/portal_amd.h): the same
+// two launches over the unfiltered rows of ptl_average_f32_to_rgb48, with a bands kernel and a pack kernel of its own.  The band cut and the
+// layout of the result buffer are png_deflate16_shape.h's to say.
+extern "C" size_t ptl_png_stream16_bytes(int width, int height) {
+    return width > 0 && height > 0 && ptl_png16_fits((unsigned)width, (unsigned)height) ? (size_t)ptl_png16_result_bytes((unsigned)width, (unsigned)height) : 0;
+}
+extern "C" size_t ptl_png_stream16_download_bytes(int width, int height) {
+    return width > 0 && height > 0 && ptl_png16_fits((unsigned)width, (unsigned)height) ? (size_t)ptl_png16_table_offset((unsigned)width, (unsigned)height) : 0;
+}
+extern "C" int ptl_png_stream16_band_rows(int width) { return width > 0 && width <= (1 << 28) ? (int)ptl_png16_band_rows((unsigned)width) : 0; }
+
+extern "C" int ptl_png_deflate_rgb48(int device, const void* rows_rgb48, int width, int height, int codes, void* out, void* stream, float* elapsed_ms) {
+    if (codes != PTL_PNG_CODES_FIXED && codes != PTL_PNG_CODES_DYNAMIC) {
+        set_last_error("png_deflate_rgb48: codes " + std::to_string(codes) + " is neither PTL_PNG_CODES_FIXED (0) nor PTL_PNG_CODES_DYNAMIC (1)");
+        return PTL_ERR_INVALID;
+    }
+    if (!rows_rgb48 || !out || width <= 0 || height <= 0) return PTL_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(rows_rgb48) | reinterpret_cast<uintptr_t>(out)) & 15u) return PTL_ERR_INVALID;
+    if ((long)width * height > ptl_rgb48_max_pixels()) {  // the rows' own limit
+        set_last_error("png_deflate_rgb48: " + std::to_string(width) + " x " + std::to_string(height) + " has more than 2^28 pixels");
+        return PTL_ERR_INVALID;
+    }
+    if (!ptl_png16_fits((unsigned)width, (unsigned)height)) {  // the kernels address the raw scanlines with 32-bit offsets
+        set_last_error("png_deflate_rgb48: " + std::to_string(width) + " x " + std::to_string(height) + " has more than 2^31 bytes of scanlines");
+        return PTL_ERR_INVALID;
+    }
+    if (device < 0) return PTL_ERR_NO_DEVICE;
+    LoadedKernel *bands_kernel = nullptr, *pack_kernel = nullptr;
+    if (int rc = load_kernel(device, "png_deflate16.hsaco", "ptl_png_deflate16_bands_kernel", &bands_kernel); rc != PTL_OK) return rc;
+    if (int rc = load_kernel(device, "png_deflate16.hsaco", "ptl_png_deflate16_pack_kernel", &pack_kernel); rc != PTL_OK) return rc;
+    const hip::Runtime* rt = hip::runtime(nullptr);
+    rt->hipSetDevice(device);
+    unsigned w = (unsigned)width, h = (unsigned)height, rows = ptl_png16_band_rows(w), n_bands = ptl_png16_bands(w, h), mode = (unsigned)codes;
+    unsigned long long table_offset = ptl_png16_table_offset(w, h), slots_offset = ptl_png16_slots_offset(w, h), slot_stride = ptl_png16_slot_stride(w);
+    unsigned long long stream_room = table_offset - ptl_png_header_bytes;
+    void* table = static_cast<char*>(out) + table_offset;
+    void* slots = static_cast<char*>(out) + slots_offset;
+    void* bands_args[] = {&rows_rgb48, &w, &h, &rows, &n_bands, &mode, &table, &slots, &slot_stride};
+    void* pack_args[] = {&out, &w, &h, &rows, &n_bands, &table_offset, &slots_offset, &slot_stride, &stream_room};
+    const unsigned blocks = (unsigned)grid_blocks(256L * n_bands);  // a workgroup per band
+    const int err = timed(rt, bands_kernel, stream, elapsed_ms, [&] {
+        const int e = rt->hipModuleLaunchKernel(bands_kernel->fn, blocks, 1, 1, 256, 1, 1, 0, stream, bands_args, nullptr);
+        return e != 0 ? e : rt->hipModuleLaunchKernel(pack_kernel->fn, blocks, 1, 1, 256, 1, 1, 0, stream, pack_args, nullptr);
+    });
+    if (err != 0) {
+        set_last_error(std::string("hipModuleLaunchKernel(png_deflate16): ") + rt->hipGetErrorString(err));
+        rt->hipGetLastError();
+        return PTL_ERR_HIP;
+    }
+    return PTL_OK;
 }
 
 // ---- trace passes: the records a PTL_FLAG_PASSES render entry stores (portal_amd/csrc/kernels/pass_stats.hip, pass_gray16.hip; the contracts are
