@@ -47,6 +47,9 @@ def compile_host(source: str, count_segments: bool = False, opt: str = "-O2", de
     return so
 
 
+_PRISTINE_BLOCKS = {}  # .so path -> the uniform block's bytes when this process first loaded it
+
+
 class HostKernel:
     """The host-compiled kernel of one scene: set uniforms by name, render pixel windows."""
 
@@ -62,6 +65,9 @@ class HostKernel:
         size = C.c_ulong()
         self.block = self.lib.ptl_host_uniform_block(C.byref(size))
         assert size.value >= block_size, (size.value, block_size)
+        # dlopen hands every HostKernel of one .so the same library, hence the same uniform block (texture bindings included): start each
+        # from the state the library was loaded with, so that what an earlier kernel object of this process set cannot show in this one's frames
+        C.memmove(self.block, _PRISTINE_BLOCKS.setdefault(self.so_path, C.string_at(self.block, size.value)), size.value)
         self.layout = {name: (typ, off) for name, typ, off in layout}
         self._textures = []
 
@@ -112,7 +118,8 @@ class HostKernel:
         return {"rgba8": a8, "rgba32f": a32, "segments": int(seg)}
 
 
-def host_kernel_for(renderer, scene, width: int, height: int, flags: int = 0, count_segments: bool = False, asset_root: str | None = None) -> HostKernel:
+def host_kernel_for(renderer, scene, width: int, height: int, flags: int = 0, count_segments: bool = False, asset_root: str | None = None,
+                    opt: str = "-O2") -> HostKernel:
     """Build the host kernel of `scene` and load it with exactly the uniform values the product
     renderer (`portal_amd.SceneRenderer`, device may be -1) would upload for a width x height frame."""
     import portal_amd as pa
@@ -121,7 +128,7 @@ def host_kernel_for(renderer, scene, width: int, height: int, flags: int = 0, co
     layout, size = scene.uniform_layout()
     # (what the generator asks the JIT for with this source; PTL_COUNT_SEGMENTS comes through `count_segments`, the occupancy hint is the renderer's)
     defines = tuple(d for d in scene.generated_defines() if d != "PTL_COUNT_SEGMENTS" and not d.startswith("PTL_WAVES_PER_EU") and d != "PTL_QUICK_JIT")
-    hk = HostKernel(source, layout, size, count_segments, defines=defines)
+    hk = HostKernel(source, layout, size, count_segments, opt=opt, defines=defines)
     for name, typ, _ in layout:
         if typ == pa.PTL_SAMPLER:
             continue

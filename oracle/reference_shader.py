@@ -13,7 +13,8 @@ that part is Rust in the reference, so it is the one piece that has to be restat
 reference's tagged-line filter and its template engine (`src/code_generation.rs:82-98`), and executes
 the resulting translation unit -- `void main()` included -- with `oracle/glsl_interp.py` under the
 builtin contract of `oracle/glsl_math.py`.  It is the `oracle/_ref` of this repository: the nearest
-thing to "the reference itself, run here" that exists without a GL driver.
+thing to "the reference itself, run here" that exists without a GL driver.  (With one: `oracle/mesa.py` hands the text
+assembled here to Mesa's GLSL compiler; `tests/golden/mesa/` holds what that computed.)
 
 What it pins.  Everything the hand restatement could have got wrong: operation order, operand order,
 branch structure, early returns, the bounce loop, darkening, Panini, side-by-side, encode_float, the

@@ -51,6 +51,21 @@ def test_baseline_scenes_draw_the_same_bits_with_the_early_return_helpers(pa, sc
     assert len(np.unique(new["rgba8"].reshape(-1, 4), axis=0)) > 8  # (a picture, not a flat frame)
 
 
+def test_a_host_kernel_does_not_inherit_the_texture_an_earlier_one_bound(pa):
+    """Every `HostKernel` of one generated source gets the same dlopen'ed library, hence the same uniform block.  A kernel object of the
+    same process that bound the scene's texture (`host_kernel_for`) used to leave it bound for the next one of that source -- the first of
+    `host_frames`'s two, which binds none -- and the two frames differed on the textured wall whenever a worker ran the tests in that order."""
+    from oracle import host_build as hb
+
+    scene = pa.Scene.from_file(pa.scene_path("monoportal"))
+    r = pa.SceneRenderer(scene, device=-1)
+    r.set_option("render_depth", 20)
+    textured = hb.host_kernel_for(r, scene, W, H).render(W, H)["rgba32f"].copy()
+    new, old = host_frames(pa, pa.scene_path("monoportal"), 20, 0, "PTL_EARLY_RETURN_HITS")
+    assert_same_frame(new, old)
+    assert not np.array_equal(textured.view(np.uint32), new["rgba32f"].view(np.uint32))  # (the texture does show where it is bound)
+
+
 @pytest.mark.parametrize("scene_file,depth", CORPUS_SCENES, ids=[os.path.basename(s)[:-4] for s, _ in CORPUS_SCENES])
 def test_corpus_scenes_that_call_the_helpers_draw_the_same_bits(pa, scene_file, depth):
     new, old = host_frames(pa, os.path.join(ROOT, scene_file), depth, 0, "PTL_EARLY_RETURN_HITS", asset_root=os.path.join(ROOT, "tests", "corpus"))
