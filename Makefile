@@ -11,7 +11,7 @@ SRCS     := ron.cpp formula.cpp scene.cpp glsl_translate.cpp glsl_bound.cpp glsl
 OBJS     := $(SRCS:%.cpp=$(OBJDIR)/%.o)
 LIB      := portal_amd/libportal_amd.so
 CLI      := portal_amd/portal-amd
-KERNELS  := portal_amd/kernels/fb_store.hsaco portal_amd/kernels/average_images.hsaco portal_amd/kernels/yuv10.hsaco portal_amd/kernels/yuv10_f32.hsaco portal_amd/kernels/rgb48_f32.hsaco portal_amd/kernels/aa_edges.hsaco portal_amd/kernels/aa_edges_slices.hsaco portal_amd/kernels/pass_stats.hsaco portal_amd/kernels/pass_gray16.hsaco portal_amd/kernels/png_deflate.hsaco portal_amd/kernels/png_huffman.hsaco portal_amd/kernels/png_deflate16.hsaco
+KERNELS  := portal_amd/kernels/fb_store.hsaco portal_amd/kernels/average_images.hsaco portal_amd/kernels/yuv10.hsaco portal_amd/kernels/yuv10_f32.hsaco portal_amd/kernels/rgb48_f32.hsaco portal_amd/kernels/aa_edges.hsaco portal_amd/kernels/aa_edges_slices.hsaco portal_amd/kernels/pass_stats.hsaco portal_amd/kernels/pass_gray16.hsaco portal_amd/kernels/pass_slices_gray16.hsaco portal_amd/kernels/png_deflate.hsaco portal_amd/kernels/png_huffman.hsaco portal_amd/kernels/png_deflate16.hsaco
 
 all: $(LIB) $(CLI)
 

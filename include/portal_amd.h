@@ -683,6 +683,26 @@ int ptl_pass_stats_depth_range(const ptl_pass_stats_block* block, float* lo, flo
 #define PTL_PASS_TRIPS 1
 int ptl_passes_to_gray16(int device, const void* records, long n, void* out_rows, int which, float lo, float hi, void* stream, float* elapsed_ms);
 int ptl_png_write_gray16(const char* path, const uint8_t* rows, int width, int height, int level);
+/* ptl_pass_slices_to_gray16: the pass images of ONE output frame of a clip from the records of its n_slices blur sub-frames, in one sweep.
+ * records: DEVICE pointer, 16-byte aligned; slice z of pixel p is the ptl_pass_record at index z * slice_records + p -- the layout
+ * ptl_renderer_draw_slices_passes writes.  out_depth, out_trips, out_cut: DEVICE pointers, 16-byte aligned, 2 n bytes each, the packed
+ * big-endian samples ptl_passes_to_gray16 writes and ptl_png_write_gray16 reads; any of them may be NULL (that image is not made), not all.
+ * Per pixel, over the slices z = 0 .. n_slices - 1, exact integers unless said otherwise:
+ *   depth  F_z = final paths of slice z (low 16 bits of final_escaped).  0 where every F_z is 0.  Otherwise D starts as depth_near of the
+ *          lowest-numbered slice with F_z > 0, and every later slice with F_z > 0 replaces D where its depth_near < D (so a NaN that came
+ *          first stays); a slice without a final path is never read for depth.  Sample = q((D - lo) / max(1e-6f, hi - lo)), the binary32
+ *          difference, divisor, ONE IEEE division and quantisation of PTL_PASS_DEPTH.  With n_slices = 1: ptl_passes_to_gray16(PTL_PASS_DEPTH)
+ *          for every bit pattern.
+ *   trips  min(sum of trips_z, 65535), the sum exact.  With n_slices = 1: ptl_passes_to_gray16(PTL_PASS_TRIPS).
+ *   cut    E = sum of exhausted_z, P = sum of final_z + escaped_z + exhausted_z (outside samples do not count).  0 where P = 0, else
+ *          ceil(65535 E / P): 0 exactly where no path was cut, at least 1 wherever one was, 65535 where every traced path was (and, being
+ *          a ceiling, where fewer than P / 65535 survived: only beyond 65 535 paths per pixel).
+ * Refused before any GPU call (PTL_ERR_INVALID, ptl_last_error): null records, all three outputs NULL, a pointer that is not 16-byte
+ * aligned, n_slices outside 1 .. 256, n outside 1 .. 2^31, slice_records < n with n_slices > 1.  Launched on `stream`; with elapsed_ms the
+ * call waits.  HBM-bound: 16 n_slices bytes in, 2 per image out.  (`portal-amd render --clip-passes depth,trips,cut`,
+ * `render-frame --passes cut`.) */
+int ptl_pass_slices_to_gray16(int device, const void* records, int n_slices, unsigned long long slice_records, long n, void* out_depth, void* out_trips,
+                              void* out_cut, float lo, float hi, void* stream, float* elapsed_ms);
 /* ---- adaptive anti-aliasing: supersample only the pixels that sit on an edge (opt-in, approximate by design) ------------------------
  * Every anti-aliasing sample costs a full trace, and most pixels of a frame are flat walls and smooth gradients whose centre sample is
  * already the final 8-bit colour.  An adaptive draw traces ONE sample per pixel, classifies the frame it got, and traces the full
@@ -987,6 +1007,12 @@ int ptl_png_deflate_rgb48(int device, const void* rows_rgb48, int width, int hei
  * those of ptl_png_write_stream, against the magic word, the band cut and the room of THIS format (an 8-bit "PTLZ" buffer is refused): a
  * mismatch is PTL_ERR_INVALID, and nothing is written. */
 int ptl_png_write_stream_rgb48(const char* path, const uint8_t* result, int width, int height);
+/* The same stream framed as a 16-bit GREY file (colour type 0) of `width` samples per row: a grey row of W samples is byte for byte an RGB48 row of
+ * W / 3 pixels with the filter-type byte in the same place, so ptl_png_deflate_rgb48(rows, W / 3, H, codes, out) over grey rows (what
+ * ptl_passes_to_gray16 and ptl_pass_slices_to_gray16 write) is a valid stream for the grey image.  `result`: a HOST copy of that buffer's first
+ * ptl_png_stream16_download_bytes(W / 3, H) bytes.  Requires width % 3 == 0 and the "PTL6" header of a (width / 3) x height frame; writes IHDR
+ * with bit depth 16 and colour type 0 and ONE IDAT; anything else: PTL_ERR_INVALID, nothing written.  (`portal-amd render --pass-encoder gpu`.) */
+int ptl_png_write_stream_gray16(const char* path, const uint8_t* result, int width, int height);
 
 /* ---- template engine test hooks (src/code_generation.rs) ----------------------------------- */
 typedef struct ptl_strstore ptl_strstore;

@@ -203,6 +203,7 @@ def _load() -> C.CDLL:
         "ptl_png_stream16_download_bytes": (cs, [ci, ci]),
         "ptl_png_deflate_rgb48": (ci, [ci, vp, ci, ci, ci, vp, vp, P(C.c_float)]),
         "ptl_png_write_stream_rgb48": (ci, [cp, vp, ci, ci]),
+        "ptl_png_write_stream_gray16": (ci, [cp, vp, ci, ci]),
         "ptl_pass_record_bytes": (cs, [ci, ci]),
         "ptl_kernel_render_passes": (ci, [vp, P(Frame), vp, vp, vp, cs, vp, vp, P(C.c_float)]),
         "ptl_kernel_render_slices_passes": (ci, [vp, P(Frame), ci, vp, vp, vp, cs, C.c_ulonglong, vp, P(C.c_float)]),
@@ -212,6 +213,7 @@ def _load() -> C.CDLL:
         "ptl_pass_stats_depth_range": (ci, [vp, P(C.c_float), P(C.c_float)]),
         "ptl_passes_to_gray16": (ci, [ci, vp, C.c_long, vp, ci, C.c_float, C.c_float, vp, P(C.c_float)]),
         "ptl_png_write_gray16": (ci, [cp, vp, ci, ci, ci]),
+        "ptl_pass_slices_to_gray16": (ci, [ci, vp, ci, C.c_ulonglong, C.c_long, vp, vp, vp, C.c_float, C.c_float, vp, P(C.c_float)]),
         "ptl_aa_edges": (ci, [ci, vp, ci, ci, ci, vp, vp, vp, P(C.c_float)]),
         "ptl_kernel_render_refine": (ci, [vp, P(Frame), vp, vp, vp, vp, vp, vp, P(C.c_float)]),
         "ptl_renderer_draw_adaptive": (ci, [vp, P(Frame), vp, vp, vp, P(C.c_float)]),
@@ -1133,6 +1135,15 @@ def png_write_stream_rgb48(path: str, result, width: int, height: int) -> None:
     _check(lib().ptl_png_write_stream_rgb48(path.encode(), a.ctypes.data, width, height), "png_write_stream_rgb48")
 
 
+def png_write_stream_gray16(path: str, result, width: int, height: int) -> None:
+    """ptl_png_write_stream_gray16: a 16-bit grey PNG of ``width`` samples per row (a multiple of 3) from a HOST copy of the result buffer of
+    `png_deflate_rgb48_device` over the same rows taken as width / 3 RGB pixels."""
+    a = np.ascontiguousarray(np.frombuffer(result, dtype=np.uint8) if isinstance(result, (bytes, bytearray, memoryview)) else result, dtype=np.uint8)
+    if a.size < PNG_STREAM_HEADER_BYTES or a.size < PNG_STREAM_HEADER_BYTES + int(a[12:16].view("<u4")[0]):
+        raise PortalError("png_write_stream_gray16: the buffer is shorter than its header and the stream the header announces")
+    _check(lib().ptl_png_write_stream_gray16(path.encode(), a.ctypes.data, width, height), "png_write_stream_gray16")
+
+
 # ---- trace passes (include/portal_amd.h: ptl_pass_record, ptl_pass_stats_block) ------------------------------------------------------
 PASS_RECORD = np.dtype([("depth_near", "<f4"), ("trips", "<u4"), ("final_escaped", "<u4"), ("exhausted_outside", "<u4")])
 PASS_HIST_BINS = 256
@@ -1173,6 +1184,17 @@ def passes_to_gray16_device(records_ptr: int, n: int, out_ptr: int, which: int, 
     ms = C.c_float()
     _check(lib().ptl_passes_to_gray16(device, C.c_void_p(records_ptr or None), n, C.c_void_p(out_ptr or None), which, lo, hi, C.c_void_p(stream or None),
                                       C.byref(ms) if timed else None), "ptl_passes_to_gray16")
+    return ms.value if timed else None
+
+
+def pass_slices_to_gray16_device(records_ptr: int, n_slices: int, slice_records: int, n: int, out_depth_ptr: int = 0, out_trips_ptr: int = 0, out_cut_ptr: int = 0,
+                                 lo: float = 0.0, hi: float = 1.0, device: int = 0, stream: int = 0, timed: bool = False):
+    """ptl_pass_slices_to_gray16: the records of ``n_slices`` sub-frames (slice z of pixel p at index z * slice_records + p) merged per pixel
+    into up to three images of 2 n bytes each -- nearest final depth, summed trips, share of cut paths -- in one sweep; an output of 0 is not made."""
+    ms = C.c_float()
+    _check(lib().ptl_pass_slices_to_gray16(device, C.c_void_p(records_ptr or None), n_slices, slice_records, n, C.c_void_p(out_depth_ptr or None),
+                                           C.c_void_p(out_trips_ptr or None), C.c_void_p(out_cut_ptr or None), lo, hi, C.c_void_p(stream or None),
+                                           C.byref(ms) if timed else None), "ptl_pass_slices_to_gray16")
     return ms.value if timed else None
 
 

@@ -28,8 +28,9 @@ int usage() {  // (and the exit status that goes with it)
                  "                                       the same pixels in a file of about the host encoder's size at 4K\n"
                  "                  [--png16-encoder host|gpu]  with --png-depth 16: gpu deflates the 16-bit file's scanlines on the GPU (Up filter, matches at pixel distance,\n"
                  "                                       a Huffman code per band); the host adds the chunk framing and CRCs.  host (default): zlib\n"
-                 "                  [--passes depth,trips]  beside the frame: <output stem>.depth.png (nearest final depth, scaled between the scene's depth-map bounds) and\n"
-                 "                                       <output stem>.trips.png (bounce-loop trips per pixel), 16-bit greyscale, from the tracer's pass records; one GPU\n"
+                 "                  [--passes depth,trips,cut]  beside the frame: <output stem>.depth.png (nearest final depth, scaled between the scene's depth-map bounds),\n"
+                 "                                       <output stem>.trips.png (bounce-loop trips per pixel) and <output stem>.cut.png (the share of the pixel's traced paths\n"
+                 "                                       that --render-depth cut short: 0 none, 65535 all), 16-bit greyscale, from the tracer's pass records; one GPU\n"
                  "                  [--depth-report]     one line: how many paths --render-depth cut short (they are drawn black), in how many pixels; the deepest pixel; the depth range\n"
                  "       portal-amd precompile <scene.ron> [--stage NAME] [--specialize 0]      fill the code-object cache (no GPU needed; render's options choose render's kernels)\n"
                  "       portal-amd render <scene[,scene..]> [clip[,clip..]] [--width 3840] [--height 2160] [--fps 60] [--motion-blur-frames 1]\n"
@@ -57,6 +58,13 @@ int usage() {  // (and the exit status that goes with it)
                  "                                       code per band), so an encoder thread only frames the stream and computes its CRC; files about 1.3 - 1.4 times the\n"
                  "                                       host encoder's.  Works with --shard K/N and resumes; host (default): zlib level 3 on the encoder threads\n"
                  "                  [--depth-report]     one line per clip: how many paths --render-depth cut short, in how many pixels, and the frame that lost most\n"
+                 "                  [--clip-passes depth,trips,cut]  beside every frame_<i>.png: anim/depth_<i>.png (nearest final depth over the frame's blur sub-frames, scaled\n"
+                 "                                       between the scene's depth-map bounds), anim/trips_<i>.png (bounce-loop trips, summed) and anim/cut_<i>.png (the share of\n"
+                 "                                       the pixel's traced paths that --render-depth cut short), 16-bit greyscale, merged on the GPU from the sub-frames' pass\n"
+                 "                                       records.  Works with --shard K/N, --frames y4m and the report line; a frame with a pass file missing is drawn again; one GPU\n"
+                 "                  [--pass-encoder host|gpu]  with --clip-passes: gpu deflates every pass image on the GPU (its rows taken as W / 3 RGB pixels: Up filter, matches\n"
+                 "                                       at distance 6, a Huffman code per band), so an encoder thread only frames the stream; W must be a multiple of 3.\n"
+                 "                                       The default, host: zlib level 3 on the encoder threads\n"
                  "                  [--clip-adaptive-aa [T]]  adaptive anti-aliasing of every sub-frame: one sample per pixel, --aa-count samples only where a pixel differs\n"
                  "                                       from a neighbour by more than T codes (default 4, -1 .. 255); opt-in, approximate by design\n"
                  "       portal-amd emit-source <scene.ron> [--stage NAME]     print the generated HIP kernel source\n"
@@ -356,7 +364,7 @@ int render_frame(const Options& o) {
         return fail("render");
     // the pass images: the records as 16-bit grey scanlines, made on the card, 2 bytes per pixel downloaded
     const std::string stem = o.output.size() > 4 && o.output.compare(o.output.size() - 4, 4, ".png") == 0 ? o.output.substr(0, o.output.size() - 4) : o.output;
-    std::vector<uint8_t> grey[2];
+    std::vector<uint8_t> grey[2], grey_cut;
     if (o.have_passes) {
         void* dev_grey = nullptr;
         if (ptl_device_alloc(devices[0], 2 * n_px, &dev_grey) != PTL_OK) return fail("device pass image");
@@ -369,6 +377,11 @@ int render_frame(const Options& o) {
             grey[which].resize(2 * n_px);
             if (ptl_passes_to_gray16(devices[0], records, (long)n_px, dev_grey, which, lo[0], hi[0], nullptr, nullptr) != PTL_OK) return fail("passes_to_gray16");
             if (ptl_device_download(grey[which].data(), dev_grey, grey[which].size(), nullptr) != PTL_OK) return fail("download");
+        }
+        if (o.pass_cut) {  // the share of cut paths: the clip's merge over ONE slice
+            grey_cut.resize(2 * n_px);
+            if (ptl_pass_slices_to_gray16(devices[0], records, 1, n_px, (long)n_px, nullptr, nullptr, dev_grey, lo[0], hi[0], nullptr, nullptr) != PTL_OK) return fail("pass_slices_to_gray16");
+            if (ptl_device_download(grey_cut.data(), dev_grey, grey_cut.size(), nullptr) != PTL_OK) return fail("download");
         }
     }
     ptl_pass_stats_block stats{};
@@ -394,6 +407,7 @@ int render_frame(const Options& o) {
     for (int which : {PTL_PASS_DEPTH, PTL_PASS_TRIPS})
         if (!grey[which].empty() && ptl_png_write_gray16((stem + (which == PTL_PASS_DEPTH ? ".depth.png" : ".trips.png")).c_str(), grey[which].data(), o.width, o.height, 6) != PTL_OK)
             return fail("png");
+    if (!grey_cut.empty() && ptl_png_write_gray16((stem + ".cut.png").c_str(), grey_cut.data(), o.width, o.height, 6) != PTL_OK) return fail("png");
     double total = seconds_since(t0);
     std::printf("Rendered `%s` to `%s` (%dx%d, aa %d, depth %d): kernel %.3f ms, %.1f Mray/s; total %.2f s\n", o.scene.c_str(), o.output.c_str(),
                 o.width, o.height, o.aa, o.depth, ms, (double)o.width * o.height * o.aa / (ms * 1e3), total);
@@ -655,13 +669,34 @@ int main(int argc, char** argv) {
             for (const std::string& pass : split_list(list)) {
                 if (pass == "depth") o.pass_depth = true;
                 else if (pass == "trips") o.pass_trips = true;
+                else if (pass == "cut") o.pass_cut = true;
                 else {
-                    std::fprintf(stderr, "--passes depth,trips: unknown pass `%s`\n", pass.c_str());
+                    std::fprintf(stderr, "--passes depth,trips,cut: unknown pass `%s`\n", pass.c_str());
                     return 2;
                 }
             }
-            if (!o.pass_depth && !o.pass_trips) return refuse("--passes depth,trips: name at least one pass");
+            if (!o.pass_depth && !o.pass_trips && !o.pass_cut) return refuse("--passes depth,trips,cut: name at least one pass");
             o.have_passes = true;
+        }
+        else if (a == "--clip-passes") {
+            const std::string list = next();
+            for (const std::string& pass : split_list(list)) {
+                if (pass == "depth") o.clip_pass_depth = true;
+                else if (pass == "trips") o.clip_pass_trips = true;
+                else if (pass == "cut") o.clip_pass_cut = true;
+                else {
+                    std::fprintf(stderr, "--clip-passes depth,trips,cut: unknown pass `%s`\n", pass.c_str());
+                    return 2;
+                }
+            }
+            if (!o.clip_pass_depth && !o.clip_pass_trips && !o.clip_pass_cut) return refuse("--clip-passes depth,trips,cut: name at least one pass");
+            o.have_clip_passes = true;
+        }
+        else if (a == "--pass-encoder") {
+            std::string encoder = next();
+            if (encoder != "host" && encoder != "gpu") return refuse("--pass-encoder host|gpu");
+            o.pass_gpu = encoder == "gpu";
+            o.have_pass_encoder = true;
         }
         else if (a == "--depth-report") o.depth_report = true;
         else if (a == "--fast") o.fast = true;
@@ -717,6 +752,16 @@ int main(int argc, char** argv) {
         return refuse("--passes and --depth-report cannot be combined with --adaptive-aa / --clip-adaptive-aa: the list-driven refine entry stores no pass records");
     if ((o.have_passes || o.depth_report) && (o.gpus > 1 || split_list(o.devices).size() > 1 || o.multi_process || o.shards > 1 || o.transport == "rccl"))
         return refuse("--passes and --depth-report draw on one GPU: they cannot be combined with --gpus N, N > 1, several --devices, --multi-process, --transport rccl or --shard");
+    if (o.have_clip_passes && cmd != "render") return refuse("--clip-passes is an option of render: it writes pass images beside every frame of a clip (one frame takes render-frame --passes)");
+    if (o.have_clip_passes && (o.adaptive || o.clip_adaptive))
+        return refuse("--clip-passes cannot be combined with --adaptive-aa / --clip-adaptive-aa: the list-driven refine entry stores no pass records");
+    if (o.have_clip_passes && (o.gpus > 1 || split_list(o.devices).size() > 1))
+        return refuse("--clip-passes draws a clip on one GPU: it cannot be combined with --gpus N, N > 1, or several --devices (--shard K/N splits a clip)");
+    if (o.have_pass_encoder && !o.have_clip_passes) return refuse("--pass-encoder needs --clip-passes: it chooses who deflates the pass images of a clip's frames");
+    if (o.pass_gpu && (o.stereo ? 2 * o.width : o.width) % 3 != 0)
+        return refuse("--pass-encoder gpu needs a drawn width that is a multiple of 3: the GPU deflates a grey row of W samples as W / 3 RGB pixels (matches at distance 6)");
+    if (o.pass_gpu && ptl_png_stream16_bytes((o.stereo ? 2 * o.width : o.width) / 3, o.height) == 0)
+        return refuse("--pass-encoder gpu needs a frame whose pass image has at most 2^31 bytes of scanlines: the kernels address them with 32-bit offsets");
     if (cmd == "render") return render(o);
     if (o.transport != "stores" && o.transport != "copy" && o.transport != "rccl") return refuse("--transport stores|copy|rccl");
     if (cmd == "render-frame") return render_frame(o);

@@ -45,7 +45,14 @@ struct Options {
     bool clip_adaptive = false;  // render --clip-adaptive-aa [T]: the same for every sub-frame of a clip (batched: the refine entry over slices)
     int clip_adaptive_t = 4;
     bool pass_depth = false, pass_trips = false;  // render-frame --passes depth,trips: <output stem>.depth.png / .trips.png, 16-bit grey, from the tracer's pass records
+    bool pass_cut = false;                        // render-frame --passes cut: <output stem>.cut.png, the share of the pixel's traced paths that --render-depth cut (ptl_pass_slices_to_gray16)
     bool have_passes = false;                     // --passes was given
+    // render --clip-passes depth,trips,cut: anim/depth_<i>.png / trips_<i>.png / cut_<i>.png beside every frame of a clip, 16-bit grey, merged on
+    // the card from the records of the frame's blur sub-frames (ptl_pass_slices_to_gray16)
+    bool clip_pass_depth = false, clip_pass_trips = false, clip_pass_cut = false;
+    bool have_clip_passes = false;                // --clip-passes was given
+    bool pass_gpu = false;                        // render --pass-encoder host|gpu, with --clip-passes: gpu deflates the pass images on the card (ptl_png_deflate_rgb48 on rows of W / 3 pixels)
+    bool have_pass_encoder = false;               // --pass-encoder was given
     bool depth_report = false;                    // render-frame / render --depth-report: one line on the paths that --render-depth cut short
     std::vector<std::string> argv;  // the command line as given (handed on to shard processes)
 };
@@ -116,10 +123,11 @@ inline unsigned quick_jit_flag(const Options& o) { return o.opt3 ? 0u : PTL_FLAG
 // right away adds quick_jit_flag().
 // --clip-adaptive-aa: where the sub-frames are batched the module has the slices entry AND the refine entry over slices (bit 29, which implies
 // bit 22), else the single-frame refine entry (bit 28) and every sub-frame is a ptl_renderer_draw_adaptive.  Without the option: what it was.
-// --depth-report: the kernel also stores the pass records (bit 30) the report is made from.
+// --depth-report, --clip-passes: the kernel also stores the pass records (bit 30) the report and the pass images are made from.
+inline bool clip_records(const Options& o) { return o.depth_report || o.have_clip_passes; }
 inline unsigned clip_flags(const Options& o, bool clip_constant) {
     const unsigned entries = o.clip_adaptive ? (batch_subframes(o) ? PTL_FLAG_REFINE_SLICES : PTL_FLAG_REFINE) : (batch_subframes(o) ? kSlicesFlag : 0u);
-    return kClipFlags | entries | numerics_flags(o) | (clip_constant ? PTL_FLAG_SPECIALIZE_STATIC : 0u) | (o.depth_report ? PTL_FLAG_PASSES : 0u);
+    return kClipFlags | entries | numerics_flags(o) | (clip_constant ? PTL_FLAG_SPECIALIZE_STATIC : 0u) | (clip_records(o) ? PTL_FLAG_PASSES : 0u);
 }
 
 // --depth-report: the one line a downloaded statistics block makes (ptl_pass_stats).  "traced" are the paths that entered the bounce loop

@@ -9,6 +9,8 @@
 // the GPU already traces the next frame.  With --frames y4m the averaging kernel is the fused one (ptl_average_to_yuv420p10): what is
 // downloaded is the planar 10-bit frame the encoder consumes (4:2:0, or what --chroma asks for: ptl_average_to_yuv10), and one writer thread streams the frames in order into ffmpeg's stdin
 // (or a .y4m file) while the clip is still rendering: no PNG files, no anim/ directory, no zscale pass.
+// With --clip-passes every frame also gets up to three 16-bit grey pass images (ClipPasses: anim/depth_<i>.png, trips_<i>.png, cut_<i>.png), merged on
+// the GPU from the pass records of its sub-frames (ptl_pass_slices_to_gray16), downloaded with the frame and encoded by the same pool.
 #include <dirent.h>
 #include <fcntl.h>
 #include <sys/wait.h>
@@ -290,6 +292,41 @@ struct FramePipeline {
     }
 };
 
+// --clip-passes: which pass images a frame gets, where each lies in the buffers a frame's images travel in, and the files they become.
+// ptl_pass_slices_to_gray16 writes the images asked for one behind the other as planes of 16-bit rows (each 16-byte aligned) in one sweep.
+// --pass-encoder host: the planes are what leaves the card (one copy) and an encoder thread deflates each (ptl_png_write_gray16).
+// --pass-encoder gpu: every plane goes through ptl_png_deflate_rgb48 as rows of W / 3 RGB pixels -- byte for byte the same rows -- into a result
+// buffer of its own; what leaves the card is each buffer's header and stream, and an encoder thread only frames it (ptl_png_write_stream_gray16).
+struct ClipPasses {
+    static constexpr int kCount = 3;
+    ClipPasses(const Options& o, int width, int height)
+        : want{o.clip_pass_depth, o.clip_pass_trips, o.clip_pass_cut},
+          gpu(o.pass_gpu),
+          plane_bytes(((size_t)2 * width * height + 15) & ~(size_t)15),
+          device_stride(gpu ? (ptl_png_stream16_bytes(width / 3, height) + 255) & ~(size_t)255 : plane_bytes),
+          download_bytes(gpu ? ptl_png_stream16_download_bytes(width / 3, height) : plane_bytes),
+          host_stride((download_bytes + 15) & ~(size_t)15),
+          anim_dir_(o.out_dir + "/anim") {}
+    int count() const { return (int)want[0] + (int)want[1] + (int)want[2]; }
+    size_t index(int p) const { return (size_t)std::count(want, want + p, true); }  // of image p among those asked for
+    size_t planes_bytes() const { return plane_bytes * (size_t)count(); }           // what the sweep writes
+    size_t device_bytes() const { return device_stride * (size_t)count(); }         // a ring slot: the planes, or the result buffers of their deflate
+    size_t host_bytes() const { return host_stride * (size_t)count(); }             // a page-locked buffer
+    static const char* name(int p) { return p == 0 ? "depth" : p == 1 ? "trips" : "cut"; }
+    std::string file(int p, int i) const { return anim_dir_ + "/" + name(p) + "_" + std::to_string(i) + ".png"; }  // (ffmpeg is given anim/frame_%d.png: no collision)
+    bool have(int i) const {  // every image asked for is there
+        for (int p = 0; p < kCount; ++p)
+            if (want[p] && !exists(file(p, i))) return false;
+        return true;
+    }
+    const bool want[kCount];
+    const bool gpu;
+    const size_t plane_bytes, device_stride, download_bytes, host_stride;
+
+private:
+    const std::string anim_dir_;
+};
+
 // One clip of the run
 struct Clip {
     std::string name;
@@ -318,6 +355,11 @@ struct SceneRun {
     // --depth-report only: the sub-frames' pass records (16 bytes per pixel, laid out the same way), and what a clip accumulates from them on the
     // card: one statistics block and a counter per frame (ptl_pass_stats), downloaded once at the end of the clip
     std::unique_ptr<void, HandleFree> record_block, pass_stats;
+    // --clip-passes only: the record block is kept for the images as well, and a ring like pipe.results holds each frame's pass images (slot k is
+    // free when pipe.copied[k] has happened: the images are copied out in front of that event)
+    const ClipPasses passes{o, width, height};
+    std::unique_ptr<void, HandleFree> pass_results[FramePipeline::kRing];
+    std::unique_ptr<void, HandleFree> pass_planes;  // --pass-encoder gpu: the sweep's planes, deflated into pass_results[k] on the same stream
     FramePipeline pipe;
 };
 
@@ -574,6 +616,7 @@ std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, 
 // What lives as long as a clip.  Released in reverse order: the output (its writer finishes, its stream closes), the pool, the page-locked buffers.
 struct ClipRun {
     PinnedFrames pinned;
+    PinnedFrames pass_pinned;  // --clip-passes: a frame's pass images travel in page-locked buffers of their own (none without the option)
     EncoderPool pool;
     std::unique_ptr<FrameOutput> out;
 };
@@ -644,13 +687,19 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
         if (ptl_device_memset(counters, 0, sizeof(uint64_t) * (size_t)count, nullptr) != PTL_OK || ptl_device_memset(run.pass_stats.get(), 0, sizeof(ptl_pass_stats_block), nullptr) != PTL_OK)
             return fail("memset");
     }
-    auto account_passes = [&](int i, int n) {  // the records of the launch that just went out: n sub-frames of frame i, one behind the other
-        return ptl_pass_stats(o.device, run.record_block.get(), (long)n * run.width * run.height, run.pass_stats.get(), per_launch.get(), i, nullptr, nullptr) == PTL_OK ? 0 : fail("pass_stats");
+    auto account_passes = [&](int i, const void* records, int n) {  // the records of the launch that just went out: n sub-frames of frame i, one behind the other
+        return ptl_pass_stats(o.device, records, (long)n * run.width * run.height, run.pass_stats.get(), per_launch.get(), i, nullptr, nullptr) == PTL_OK ? 0 : fail("pass_stats");
     };
+    // --clip-passes: the block keeps ALL sub-frames of a frame (an unbatched sub-frame j draws its records at slice j, where the batched launch
+    // puts them), and one sweep behind the frame's last sub-frame merges them into the frame's pass images
+    const ClipPasses& passes = run.passes;
+    const bool with_records = clip_records(o), with_passes = o.have_clip_passes;
+    const long n_px = (long)run.width * run.height;
+    if (with_passes) make_dirs(o.out_dir + "/anim");  // (a Y4M clip has no other use for it)
     const bool batched = batch_subframes(o), direct = out.draws_result(), with_float = out.wants_float();
     for (int i = 0; i < last; ++i) {
         if (int rc = out.check()) return rc;
-        if (i % o.shards != o.shard || out.have(i)) {
+        if (i % o.shards != o.shard || (out.have(i) && (!with_passes || passes.have(i)))) {  // (a frame with a pass file missing is drawn again, all its files rewritten)
             // Not ours (shard K of N takes every N-th frame) or already on disk.  The camera is stateful -- where it is relative
             // to the portals depends on the path it took (teleport_camera) -- so the host step still runs for every sub-frame:
             // a shard, or a resumed run, then sees exactly the cameras of an uninterrupted run.  (The reference skips the
@@ -677,12 +726,12 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
                 const unsigned long long slice_pixels = (unsigned long long)run.width * run.height;
                 if (j == o.blur - 1) {
                     if ((o.clip_adaptive  ? ptl_renderer_draw_slices_adaptive(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, o.timing ? &ms : nullptr)
-                         : o.depth_report ? ptl_renderer_draw_slices_passes(r, &frame, o.blur, run.subframes[0], block_f32, run.record_block.get(), frame_records * (size_t)o.blur, slice_pixels,
+                         : with_records   ? ptl_renderer_draw_slices_passes(r, &frame, o.blur, run.subframes[0], block_f32, run.record_block.get(), frame_records * (size_t)o.blur, slice_pixels,
                                                                             nullptr, o.timing ? &ms : nullptr)
                                           : ptl_renderer_draw_slices(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, o.timing ? &ms : nullptr)) != PTL_OK)
                         return fail("render");
                     if (o.depth_report)
-                        if (int rc = account_passes(i, o.blur)) return rc;
+                        if (int rc = account_passes(i, run.record_block.get(), o.blur)) return rc;
                     if (o.clip_adaptive && o.timing)
                         if (int rc = account_adaptive(true, o.blur)) return rc;
                 }
@@ -690,9 +739,11 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
                 if (ptl_renderer_draw_adaptive(r, &frame, target, target_f32, nullptr, o.timing ? &ms : nullptr) != PTL_OK) return fail("render");
                 if (o.timing)
                     if (int rc = account_adaptive(false, 1)) return rc;
-            } else if (o.depth_report) {  // (the unbatched sub-frame with its records, and the stats kernel behind it)
-                if (ptl_renderer_draw_passes(r, &frame, target, target_f32, run.record_block.get(), frame_records, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) return fail("render");
-                if (int rc = account_passes(i, 1)) return rc;
+            } else if (with_records) {  // (the unbatched sub-frame with its records, and the stats kernel behind it)
+                void* records = static_cast<char*>(run.record_block.get()) + (with_passes ? (size_t)j * frame_records : 0);
+                if (ptl_renderer_draw_passes(r, &frame, target, target_f32, records, frame_records, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) return fail("render");
+                if (o.depth_report)
+                    if (int rc = account_passes(i, records, 1)) return rc;
             } else if (ptl_renderer_draw(r, &frame, target, target_f32, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) {
                 // (without --timing the launch is not waited for: the host evaluates the next sub-frame's uniforms while this one traces)
                 return fail("render");
@@ -711,16 +762,57 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
             if (int rc = out.make_result(pipe.results[slot], o.timing ? &ms : nullptr)) return rc;
             gpu_ms += ms;
         }
+        if (with_passes) {  // behind the last sub-frame on the tracing stream: before the next frame overwrites the block
+            float lo[16] = {0.0f}, hi[16] = {1.0f}, ms = 0.0f;  // the scene's depth-map bounds, as the last sub-frame's draw uploaded them
+            ptl_renderer_uniform_value(r, run.width, run.height, "_depth_map_min", lo, nullptr);
+            ptl_renderer_uniform_value(r, run.width, run.height, "_depth_map_max", hi, nullptr);
+            char* results = static_cast<char*>(run.pass_results[slot].get());
+            char* planes = passes.gpu ? static_cast<char*>(run.pass_planes.get()) : results;
+            auto plane = [&](int p) -> void* { return passes.want[p] ? planes + passes.index(p) * passes.plane_bytes : nullptr; };
+            if (ptl_pass_slices_to_gray16(o.device, run.record_block.get(), o.blur, (unsigned long long)n_px, n_px, plane(0), plane(1), plane(2), lo[0], hi[0], nullptr,
+                                          o.timing ? &ms : nullptr) != PTL_OK)
+                return fail("pass_slices_to_gray16");
+            gpu_ms += ms;
+            for (int p = 0; p < ClipPasses::kCount && passes.gpu; ++p) {  // the plane's rows as W / 3 RGB pixels: the same bytes, the filter-type bytes in the same places
+                if (!passes.want[p]) continue;
+                if (ptl_png_deflate_rgb48(o.device, plane(p), run.width / 3, run.height, PTL_PNG_CODES_DYNAMIC, results + passes.index(p) * passes.device_stride, nullptr,
+                                          o.timing ? &ms : nullptr) != PTL_OK)
+                    return fail("png_deflate_rgb48");
+                gpu_ms += ms;
+            }
+        }
         // hand the finished frame to the copy stream and go on tracing; the host job waits for its own event
         uint8_t* pixels = c.pinned.take();  // blocks while every buffer is still being encoded
-        void* arrived = nullptr;
+        uint8_t* pass_pixels = with_passes ? c.pass_pinned.take() : nullptr;
+        void *arrived = nullptr, *passes_arrived = nullptr;
         if (ptl_event_record(pipe.produced, nullptr) != PTL_OK || ptl_stream_wait_event(pipe.copy_stream, pipe.produced) != PTL_OK ||
-            ptl_device_download_async(pixels, pipe.results[slot], run.download_bytes, pipe.copy_stream) != PTL_OK ||
-            ptl_event_record(pipe.copied[slot], pipe.copy_stream) != PTL_OK || ptl_event_create(pipe.device, &arrived) != PTL_OK ||
+            ptl_device_download_async(pixels, pipe.results[slot], run.download_bytes, pipe.copy_stream) != PTL_OK || ptl_event_create(pipe.device, &arrived) != PTL_OK ||
             ptl_event_record(arrived, pipe.copy_stream) != PTL_OK)
             return fail("download");
+        if (with_passes) {  // host: the planes in one copy; gpu: of every result buffer the header and the room for the stream
+            const char* results = static_cast<const char*>(run.pass_results[slot].get());
+            for (int k = 0; k < (passes.gpu ? passes.count() : 1); ++k)
+                if (ptl_device_download_async(pass_pixels + (size_t)k * passes.host_stride, results + (size_t)k * passes.device_stride, passes.gpu ? passes.download_bytes : passes.planes_bytes(),
+                                              pipe.copy_stream) != PTL_OK)
+                    return fail("download");
+            if (ptl_event_create(pipe.device, &passes_arrived) != PTL_OK || ptl_event_record(passes_arrived, pipe.copy_stream) != PTL_OK) return fail("download");
+        }
+        if (ptl_event_record(pipe.copied[slot], pipe.copy_stream) != PTL_OK) return fail("download");  // slot is free: the frame and its pass images have left
         pipe.copy_pending[slot] = true;
         out.submit(i, pixels, arrived, c.pool, c.pinned);
+        if (with_passes)
+            c.pool.submit([pass_pixels, passes_arrived, i, &passes, width = run.width, height = run.height, &pinned = c.pass_pinned] {
+                bool ok = ptl_event_synchronize(passes_arrived) == PTL_OK;
+                for (int p = 0; p < ClipPasses::kCount && ok; ++p)
+                    if (passes.want[p]) {
+                        const uint8_t* image = pass_pixels + passes.index(p) * passes.host_stride;
+                        ok = (passes.gpu ? ptl_png_write_stream_gray16(passes.file(p, i).c_str(), image, width, height)
+                                         : ptl_png_write_gray16(passes.file(p, i).c_str(), image, width, height, kFrameDeflateLevel)) == PTL_OK;
+                    }
+                if (!ok) std::fprintf(stderr, "\n%s\n", ptl_last_error());
+                ptl_event_destroy(passes_arrived);
+                pinned.give(pass_pixels);
+            });
         std::printf("\r%d/%d done      ", i, count);
         std::fflush(stdout);
     }
@@ -746,14 +838,41 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
     return 0;
 }
 
+// --clip-passes, a clip that is whole: its pass files leave anim/ for video/<scene>/<clip>.passes/ before the frames are handed on -- anim/ is
+// removed behind ffmpeg (or parked as <clip>.frames without one), and the next clip must not find this clip's pass files "already there"
+void park_pass_files(const SceneRun& run, const Clip& clip) {
+    const std::string anim = run.o.out_dir + "/anim", parked = run.o.out_dir + "/video/" + run.name + "/" + clip.name + ".passes";
+    std::vector<std::string> names;
+    if (DIR* d = opendir(anim.c_str())) {
+        while (dirent* e = readdir(d)) {
+            const std::string name = e->d_name;
+            for (int p = 0; p < ClipPasses::kCount; ++p)
+                if (name.rfind(std::string(ClipPasses::name(p)) + "_", 0) == 0) names.push_back(name);
+        }
+        closedir(d);
+    }
+    if (names.empty()) return;
+    remove_tree(parked);
+    make_dirs(parked);
+    for (const std::string& name : names)
+        if (::rename((anim + "/" + name).c_str(), (parked + "/" + name).c_str()) != 0) std::fprintf(stderr, "could not move %s to %s\n", name.c_str(), parked.c_str());
+    std::printf("Pass images of `%s` are in `%s`\n", clip.name.c_str(), parked.c_str());
+}
+
 // One clip: its buffers, pools and output for as long as it takes, released on every way out
 int render_clip(SceneRun& run, const Clip& clip) {
     auto clip_start = std::chrono::steady_clock::now();
     // frames in flight between download and encode: one per encoder thread, but no more than ~2 GB of page-locked memory
     int in_flight = (int)std::max<size_t>(4, std::min<size_t>((size_t)run.threads + 2, ((size_t)2 << 30) / run.download_bytes));
-    ClipRun c{{run.download_bytes, in_flight}, {run.threads, (size_t)run.threads * 2}, make_output(run, clip, (size_t)in_flight)};
-    if (!c.pinned.ok()) return fail("pinned host memory");
-    return c.out->close(trace_clip(run, c, clip), c.pool, clip_start);
+    const bool with_passes = run.o.have_clip_passes;
+    ClipRun c{{run.download_bytes, in_flight}, {std::max<size_t>(16, run.passes.host_bytes()), with_passes ? in_flight : 0}, {run.threads, (size_t)run.threads * 2}, make_output(run, clip, (size_t)in_flight)};
+    if (!c.pinned.ok() || (with_passes && !c.pass_pinned.ok())) return fail("pinned host memory");
+    const int rc = trace_clip(run, c, clip);
+    if (with_passes && rc == 0 && run.o.shards == 1 && run.o.max_frames < 0) {
+        c.pool.finish();  // every pass file is on disk
+        park_pass_files(run, clip);
+    }
+    return c.out->close(rc, c.pool, clip_start);
 }
 
 // Warm the code-object cache for the NEXT clip's specialised kernel while the current clip renders: a private copy of the scene
@@ -887,12 +1006,25 @@ int render_scene(const Options& o, const std::string& path) {
         run.float_block.reset(floats);
         for (size_t j = 0; j < run.subframes.size(); ++j) run.float_subframes.push_back(static_cast<char*>(floats) + j * float_bytes);
     }
-    if (o.depth_report) {
-        void *records = nullptr, *stats = nullptr;
+    if (clip_records(o)) {
+        void* records = nullptr;
         if (ptl_device_alloc(o.device, ptl_pass_record_bytes(run.width, run.height) * run.subframes.size(), &records) != PTL_OK) return fail("alloc");
         run.record_block.reset(records);
+    }
+    if (o.depth_report) {
+        void* stats = nullptr;
         if (ptl_device_alloc(o.device, sizeof(ptl_pass_stats_block), &stats) != PTL_OK) return fail("alloc");
         run.pass_stats.reset(stats);
+    }
+    for (int k = 0; k < FramePipeline::kRing && o.have_clip_passes; ++k) {
+        void* images = nullptr;
+        if (ptl_device_alloc(o.device, run.passes.device_bytes(), &images) != PTL_OK) return fail("alloc");
+        run.pass_results[k].reset(images);
+    }
+    if (o.have_clip_passes && o.pass_gpu) {
+        void* planes = nullptr;
+        if (ptl_device_alloc(o.device, run.passes.planes_bytes(), &planes) != PTL_OK) return fail("alloc");
+        run.pass_planes.reset(planes);
     }
     if (!run.pipe.create(o.device, run.result_bytes)) return fail("pipeline");
     Prefetcher prefetch;

@@ -241,11 +241,12 @@ extern "C" int ptl_png_write_gray16(const char* path, const uint8_t* rows, int w
 
 namespace {
 
-// What the two stream writers share: the header of a HOST copy of a result buffer checked against what a W x H frame of that kind has to say
-// (`magic`, the band cut, the room for the stream), then signature, IHDR (`depth`, `colour`), ONE IDAT = 78 01 | stream | 03 00 | Adler-32 with
+// What the stream writers share: the header of a HOST copy of a result buffer checked against what a W x H frame of that kind has to say
+// (`magic`, the band cut, the room for the stream), then signature, IHDR (`image_width` -- W unless the file's samples are grouped otherwise than the
+// stream's pixels -- `depth`, `colour`), ONE IDAT = 78 01 | stream | 03 00 | Adler-32 with
 // its CRC, IEND.  No per-pixel work, no deflate.  A header that does not match: PTL_ERR_INVALID, nothing written.
 int write_stream_file(const char* path, const uint8_t* result, unsigned w, unsigned h, unsigned magic, unsigned band_rows, unsigned bands, unsigned long long capacity,
-                      unsigned char depth, unsigned char colour, const char* what, const char* from) {
+                      unsigned image_width, unsigned char depth, unsigned char colour, const char* what, const char* from) {
     unsigned word[7];
     std::memcpy(word, result, sizeof word);  // (little-endian, as the card wrote them)
     if (word[0] != magic || word[1] != w || word[2] != h || word[5] != band_rows || word[6] != bands || word[3] > capacity || word[3] < 6ull * bands) {
@@ -256,7 +257,7 @@ int write_stream_file(const char* path, const uint8_t* result, unsigned w, unsig
     std::vector<unsigned char> out = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     out.reserve(n + 80);
     std::vector<unsigned char> ihdr;
-    put_be32(ihdr, w);
+    put_be32(ihdr, image_width);
     put_be32(ihdr, h);
     ihdr.insert(ihdr.end(), {depth, colour, 0, 0, 0});
     write_chunk(out, "IHDR", ihdr.data(), ihdr.size());
@@ -287,15 +288,30 @@ int write_stream_file(const char* path, const uint8_t* result, unsigned w, unsig
 extern "C" int ptl_png_write_stream(const char* path, const uint8_t* result, int width, int height) {
     if (!path || !result || width <= 0 || height <= 0 || !ptl_png_fits((unsigned)width, (unsigned)height)) return PTL_ERR_INVALID;
     const unsigned w = (unsigned)width, h = (unsigned)height;
-    return write_stream_file(path, result, w, h, ptl_png_magic, ptl_png_band_rows(w), ptl_png_bands(w, h), ptl_png_stream_capacity(w, h), 8, 6, "png_write_stream", "ptl_png_deflate_rgba8");
+    return write_stream_file(path, result, w, h, ptl_png_magic, ptl_png_band_rows(w), ptl_png_bands(w, h), ptl_png_stream_capacity(w, h), w, 8, 6, "png_write_stream", "ptl_png_deflate_rgba8");
 }
 
 // The same for a 16-bit RGB file from the result buffer of ptl_png_deflate_rgb48: the other magic word, the band cut of rows of 6 W bytes.
 extern "C" int ptl_png_write_stream_rgb48(const char* path, const uint8_t* result, int width, int height) {
     if (!path || !result || width <= 0 || height <= 0 || !ptl_png16_fits((unsigned)width, (unsigned)height)) return PTL_ERR_INVALID;
     const unsigned w = (unsigned)width, h = (unsigned)height;
-    return write_stream_file(path, result, w, h, ptl_png16_magic, ptl_png16_band_rows(w), ptl_png16_bands(w, h), ptl_png16_stream_capacity(w, h), 16, 2, "png_write_stream_rgb48",
+    return write_stream_file(path, result, w, h, ptl_png16_magic, ptl_png16_band_rows(w), ptl_png16_bands(w, h), ptl_png16_stream_capacity(w, h), w, 16, 2, "png_write_stream_rgb48",
                              "ptl_png_deflate_rgb48");
+}
+
+// A 16-bit GREY file of `width` samples per row from the result buffer of ptl_png_deflate_rgb48 over the same rows taken as width / 3 RGB pixels:
+// a grey row of W samples is byte for byte an RGB48 row of W / 3 pixels and the filter-type bytes sit in the same places, so the stream is a
+// valid one for the grey image; only IHDR differs (width W, colour type 0).  width % 3 != 0: PTL_ERR_INVALID, nothing written.
+extern "C" int ptl_png_write_stream_gray16(const char* path, const uint8_t* result, int width, int height) {
+    if (!path || !result || width <= 0 || height <= 0) return PTL_ERR_INVALID;
+    if (width % 3 != 0) {
+        ptl::set_last_error("png_write_stream_gray16: width " + std::to_string(width) + " is not a multiple of 3: the stream is that of rows of width / 3 RGB pixels");
+        return PTL_ERR_INVALID;
+    }
+    const unsigned w = (unsigned)width / 3u, h = (unsigned)height;
+    if (!ptl_png16_fits(w, h)) return PTL_ERR_INVALID;
+    return write_stream_file(path, result, w, h, ptl_png16_magic, ptl_png16_band_rows(w), ptl_png16_bands(w, h), ptl_png16_stream_capacity(w, h), (unsigned)width, 16, 0,
+                             "png_write_stream_gray16", "ptl_png_deflate_rgb48");
 }
 
 extern "C" int ptl_png_write(const char* path, const uint8_t* rgba8, int width, int height) { return ptl_png_write_level(path, rgba8, width, height, 6); }

@@ -432,6 +432,26 @@ extern "C" int ptl_passes_to_gray16(int device, const void* records, long n, voi
     return launch_over_records(device, "pass_gray16.hsaco", "ptl_passes_to_gray16_kernel", "passes_to_gray16", args, (n + 3) / 4, stream, elapsed_ms);  // a lane per four records
 }
 
+// The pass images of a clip's frame: the records of its N blur sub-frames merged per pixel into up to three grey images in one sweep
+// (portal_amd/csrc/kernels/pass_slices_gray16.hip; the contract is in include/portal_amd.h).
+extern "C" int ptl_pass_slices_to_gray16(int device, const void* records, int n_slices, unsigned long long slice_records, long n, void* out_depth, void* out_trips,
+                                         void* out_cut, float lo, float hi, void* stream, float* elapsed_ms) {
+    const auto refuse = [](const std::string& why) {
+        set_last_error("pass_slices_to_gray16: " + why);
+        return PTL_ERR_INVALID;
+    };
+    if (!records) return refuse("records is null");
+    if (!out_depth && !out_trips && !out_cut) return refuse("none of out_depth, out_trips, out_cut is given");
+    if ((reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(out_depth) | reinterpret_cast<uintptr_t>(out_trips) | reinterpret_cast<uintptr_t>(out_cut)) & 15u)
+        return refuse("records and the outputs must be 16-byte aligned");
+    if (n_slices < 1 || n_slices > kMaxSubframesTable) return refuse("n_slices " + std::to_string(n_slices) + " is outside 1 .. 256");
+    if (n < 1 || n > (1L << 31)) return refuse("n " + std::to_string(n) + " is outside 1 .. 2^31");
+    if (n_slices > 1 && slice_records < (unsigned long long)n) return refuse("slice_records " + std::to_string(slice_records) + " is less than n: the slices would overlap");
+    void* args[] = {&records, &n_slices, &slice_records, &n, &out_depth, &out_trips, &out_cut, &lo, &hi};
+    return launch_over_records(device, "pass_slices_gray16.hsaco", "ptl_pass_slices_to_gray16_kernel", "pass_slices_to_gray16", args, (n + 3) / 4, stream,
+                               elapsed_ms);  // a lane per four pixels
+}
+
 // ptl_aa_edges: the classification pass of the adaptive anti-aliasing (portal_amd/csrc/kernels/aa_edges.hip; the contract is in
 // include/portal_amd.h).  The count is reset on `stream` by the call itself; a 256-thread workgroup per 64x32 pixel region.
 extern "C" int ptl_aa_edges(int device, const void* frame_rgba8, int width, int height, int threshold, void* list, void* count, void* stream,
