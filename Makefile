@@ -11,7 +11,7 @@ SRCS     := ron.cpp formula.cpp scene.cpp glsl_translate.cpp glsl_bound.cpp glsl
 OBJS     := $(SRCS:%.cpp=$(OBJDIR)/%.o)
 LIB      := portal_amd/libportal_amd.so
 CLI      := portal_amd/portal-amd
-KERNELS  := portal_amd/kernels/fb_store.hsaco portal_amd/kernels/average_images.hsaco portal_amd/kernels/yuv10.hsaco portal_amd/kernels/yuv10_f32.hsaco portal_amd/kernels/rgb48_f32.hsaco portal_amd/kernels/aa_edges.hsaco portal_amd/kernels/aa_edges_slices.hsaco portal_amd/kernels/pass_stats.hsaco portal_amd/kernels/pass_gray16.hsaco portal_amd/kernels/pass_slices_gray16.hsaco portal_amd/kernels/png_deflate.hsaco portal_amd/kernels/png_huffman.hsaco portal_amd/kernels/png_deflate16.hsaco
+KERNELS  := portal_amd/kernels/fb_store.hsaco portal_amd/kernels/average_images.hsaco portal_amd/kernels/yuv10.hsaco portal_amd/kernels/yuv10_f32.hsaco portal_amd/kernels/rgb48_f32.hsaco portal_amd/kernels/aa_edges.hsaco portal_amd/kernels/aa_edges_slices.hsaco portal_amd/kernels/pass_stats.hsaco portal_amd/kernels/pass_gray16.hsaco portal_amd/kernels/pass_slices_gray16.hsaco portal_amd/kernels/png_deflate.hsaco portal_amd/kernels/png_huffman.hsaco
 
 all: $(LIB) $(CLI)
 
@@ -21,7 +21,7 @@ $(HOST)/embedded_device_sources.inc: $(DEVICE)/ptl_glsl.h $(DEVICE)/ptl_library.
 	    device_source_refine_slices_entry=$(DEVICE)/ptl_refine_common.h+$(DEVICE)/ptl_refine_slices_entry.h
 
 $(OBJDIR)/embedded.o: $(HOST)/embedded_device_sources.inc
-$(OBJDIR)/%.o: $(HOST)/%.cpp $(wildcard $(HOST)/*.h) include/portal_amd.h portal_amd/csrc/kernels/yuv_shape.h portal_amd/csrc/kernels/rgb48_shape.h portal_amd/csrc/kernels/pass_key.h portal_amd/csrc/kernels/png_deflate_shape.h portal_amd/csrc/kernels/png_deflate16_shape.h
+$(OBJDIR)/%.o: $(HOST)/%.cpp $(wildcard $(HOST)/*.h) include/portal_amd.h portal_amd/csrc/kernels/yuv_shape.h portal_amd/csrc/kernels/rgb48_shape.h portal_amd/csrc/kernels/pass_key.h portal_amd/csrc/kernels/png_deflate_shape.h
 	@mkdir -p $(OBJDIR)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
@@ -32,7 +32,7 @@ $(CLI): $(HOST)/cli.cpp $(HOST)/cli_video.cpp $(HOST)/cli_common.h $(LIB) includ
 	$(CXX) $(CXXFLAGS) $(HOST)/cli.cpp $(HOST)/cli_video.cpp -o $@ -Lportal_amd -lportal_amd -Wl,-rpath,'$$ORIGIN'
 
 kernels: $(KERNELS)
-portal_amd/kernels/%.hsaco: portal_amd/csrc/kernels/%.hip portal_amd/csrc/kernels/average_common.h portal_amd/csrc/kernels/yuv_common.h portal_amd/csrc/kernels/yuv_shape.h portal_amd/csrc/kernels/rgb48_shape.h portal_amd/csrc/kernels/aa_edges_common.h portal_amd/csrc/kernels/pass_key.h portal_amd/csrc/kernels/png_deflate_shape.h portal_amd/csrc/kernels/png_deflate_common.h portal_amd/csrc/kernels/png_deflate16_shape.h portal_amd/csrc/kernels/png_deflate16_common.h
+portal_amd/kernels/%.hsaco: portal_amd/csrc/kernels/%.hip portal_amd/csrc/kernels/average_common.h portal_amd/csrc/kernels/yuv_common.h portal_amd/csrc/kernels/yuv_shape.h portal_amd/csrc/kernels/rgb48_shape.h portal_amd/csrc/kernels/aa_edges_common.h portal_amd/csrc/kernels/pass_key.h portal_amd/csrc/kernels/png_deflate_shape.h portal_amd/csrc/kernels/png_deflate_common.h
 	@mkdir -p portal_amd/kernels
 	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -mllvm -vgpr-regalloc=basic --genco --no-gpu-bundle-output $< -o $@  # allocator: see kernel.cpp
 

@@ -996,8 +996,9 @@ int ptl_png_write_stream(const char* path, const uint8_t* result, int width, int
  *   that neither writer takes the other's buffer; words 1 .. 6 are W, H, the stream's byte count n, Adler-32 of `raw16`, rows per band, number
  *   of bands; the remaining nine words are zero.  Nothing in `out` has to be cleared between calls.
  * Refused before any GPU call (PTL_ERR_INVALID): any `codes` but the two (before anything else is looked at), null or not 16-byte aligned
- * pointers, sizes <= 0, W H > 2^28 (the rows' own limit), H (6 W + 1) > 2^31; the size functions are 0 for such a size.  Two kernels
- * (portal_amd/csrc/kernels/png_deflate16.hip) on `stream`, elapsed_ms != NULL waits and reports both. */
+ * pointers, sizes <= 0, W H > 2^28 (the rows' own limit), H (6 W + 1) > 2^31; the size functions are 0 for such a size.  Two kernels on
+ * `stream` (the 16-bit bands kernel of portal_amd/csrc/kernels/png_huffman.hip and the pack kernel of png_deflate.hip), elapsed_ms != NULL
+ * waits and reports both. */
 size_t ptl_png_stream16_bytes(int width, int height);
 size_t ptl_png_stream16_download_bytes(int width, int height); /* the header and the room for the longest stream (rounded up to 16) */
 int ptl_png_stream16_band_rows(int width);                     /* rows per band; 0 for a width that is not positive */

@@ -15,7 +15,6 @@
 #include <vector>
 
 #include "../../../include/portal_amd.h"
-#include "../kernels/png_deflate16_shape.h"
 #include "../kernels/png_deflate_shape.h"
 #include "internal.h"
 
@@ -286,16 +285,17 @@ int write_stream_file(const char* path, const uint8_t* result, unsigned w, unsig
 // An 8-bit RGBA file from a HOST copy of the result buffer of ptl_png_deflate_rgba8: the GPU has filtered and deflated, the host checks the
 // header, frames the stream as one IDAT (78 01 | stream | 03 00 | Adler-32) and computes the chunk CRCs.  No per-pixel work, no deflate.
 extern "C" int ptl_png_write_stream(const char* path, const uint8_t* result, int width, int height) {
-    if (!path || !result || width <= 0 || height <= 0 || !ptl_png_fits((unsigned)width, (unsigned)height)) return PTL_ERR_INVALID;
+    if (!path || !result || width <= 0 || height <= 0 || !ptl_png_fits(ptl_png_pixel8, (unsigned)width, (unsigned)height)) return PTL_ERR_INVALID;
     const unsigned w = (unsigned)width, h = (unsigned)height;
-    return write_stream_file(path, result, w, h, ptl_png_magic, ptl_png_band_rows(w), ptl_png_bands(w, h), ptl_png_stream_capacity(w, h), w, 8, 6, "png_write_stream", "ptl_png_deflate_rgba8");
+    return write_stream_file(path, result, w, h, ptl_png_magic(ptl_png_pixel8), ptl_png_band_rows(ptl_png_pixel8, w), ptl_png_bands(ptl_png_pixel8, w, h), ptl_png_stream_capacity(ptl_png_pixel8, w, h), w, 8, 6,
+                             "png_write_stream", "ptl_png_deflate_rgba8");
 }
 
 // The same for a 16-bit RGB file from the result buffer of ptl_png_deflate_rgb48: the other magic word, the band cut of rows of 6 W bytes.
 extern "C" int ptl_png_write_stream_rgb48(const char* path, const uint8_t* result, int width, int height) {
-    if (!path || !result || width <= 0 || height <= 0 || !ptl_png16_fits((unsigned)width, (unsigned)height)) return PTL_ERR_INVALID;
+    if (!path || !result || width <= 0 || height <= 0 || !ptl_png_fits(ptl_png_pixel16, (unsigned)width, (unsigned)height)) return PTL_ERR_INVALID;
     const unsigned w = (unsigned)width, h = (unsigned)height;
-    return write_stream_file(path, result, w, h, ptl_png16_magic, ptl_png16_band_rows(w), ptl_png16_bands(w, h), ptl_png16_stream_capacity(w, h), w, 16, 2, "png_write_stream_rgb48",
+    return write_stream_file(path, result, w, h, ptl_png_magic(ptl_png_pixel16), ptl_png_band_rows(ptl_png_pixel16, w), ptl_png_bands(ptl_png_pixel16, w, h), ptl_png_stream_capacity(ptl_png_pixel16, w, h), w, 16, 2, "png_write_stream_rgb48",
                              "ptl_png_deflate_rgb48");
 }
 
@@ -309,8 +309,8 @@ extern "C" int ptl_png_write_stream_gray16(const char* path, const uint8_t* resu
         return PTL_ERR_INVALID;
     }
     const unsigned w = (unsigned)width / 3u, h = (unsigned)height;
-    if (!ptl_png16_fits(w, h)) return PTL_ERR_INVALID;
-    return write_stream_file(path, result, w, h, ptl_png16_magic, ptl_png16_band_rows(w), ptl_png16_bands(w, h), ptl_png16_stream_capacity(w, h), (unsigned)width, 16, 0,
+    if (!ptl_png_fits(ptl_png_pixel16, w, h)) return PTL_ERR_INVALID;
+    return write_stream_file(path, result, w, h, ptl_png_magic(ptl_png_pixel16), ptl_png_band_rows(ptl_png_pixel16, w), ptl_png_bands(ptl_png_pixel16, w, h), ptl_png_stream_capacity(ptl_png_pixel16, w, h), (unsigned)width, 16, 0,
                              "png_write_stream_gray16", "ptl_png_deflate_rgb48");
 }
 

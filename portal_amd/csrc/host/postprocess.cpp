@@ -20,7 +20,6 @@
 
 #include "../../../include/portal_amd.h"
 #include "../kernels/pass_key.h"
-#include "../kernels/png_deflate16_shape.h"
 #include "../kernels/png_deflate_shape.h"
 #include "../kernels/rgb48_shape.h"
 #include "../kernels/yuv_shape.h"
@@ -270,113 +269,92 @@ extern "C" int ptl_average_f32_to_rgb48(int device, const void* const* frames_rg
     return launch_over_subframes(device, kKernels[filter == PTL_PNG_FILTER_SUB], frames_rgba32f, n_frames, {&out_rows, &width, &height}, lanes, stream, elapsed_ms);
 }
 
-// The GPU deflate of an 8-bit PNG frame (portal_amd/csrc/kernels/png_deflate.hip; the stream contract is in include/portal_amd.h): the bands
-// kernel, a workgroup per band (grid-stride beyond the cap), then the pack kernel, on the same stream.  The cut into bands and the layout of
-// the result buffer are png_deflate_shape.h's to say: the kernels read the same header.
+// The GPU deflate of a PNG frame (portal_amd/csrc/kernels/png_deflate.hip, png_huffman.hip; the stream contracts are in include/portal_amd.h):
+// a bands kernel, a workgroup per band (grid-stride beyond the cap), then the one pack kernel, on the same stream.  The cut into bands and the
+// layout of the result buffer are png_deflate_shape.h's to say: the kernels read the same header.
+namespace {
 static_assert(PTL_PNG_STREAM_HEADER_BYTES == ptl_png_header_bytes, "the header the kernels write");
-extern "C" size_t ptl_png_stream_bytes(int width, int height) {
-    return width > 0 && height > 0 && ptl_png_fits((unsigned)width, (unsigned)height) ? (size_t)ptl_png_result_bytes((unsigned)width, (unsigned)height) : 0;
-}
-extern "C" size_t ptl_png_stream_download_bytes(int width, int height) {
-    return width > 0 && height > 0 && ptl_png_fits((unsigned)width, (unsigned)height) ? (size_t)ptl_png_table_offset((unsigned)width, (unsigned)height) : 0;
-}
-extern "C" int ptl_png_stream_band_rows(int width) { return width > 0 && width <= (1 << 29) ? (int)ptl_png_band_rows((unsigned)width) : 0; }
 
-// `codes`: PTL_PNG_CODES_FIXED launches the bands kernel of png_deflate.hip, PTL_PNG_CODES_DYNAMIC the one of png_huffman.hip, which writes the same
-// table entries and slots; the pack kernel is the same for both.
-extern "C" int ptl_png_deflate_rgba8_codes(int device, const void* frame_rgba8, int width, int height, int codes, void* out, void* stream, float* elapsed_ms) {
+// What the three entry points differ in: the bytes of a pixel, the bands kernel and whether it takes `codes`, and what error texts call them.
+// (The three names are the error texts of before, message for message: test_entry_point_refuses_before_any_gpu_call of test_png_deflate.py,
+// test_png_huffman.py and test_png16_deflate.py pins them.)
+struct DeflateFormat {
+    unsigned pixel;
+    const char *file, *bands_entry;
+    bool codes_argument;
+    const char *codes_name, *name, *launch_name;
+};
+const DeflateFormat kDeflateFixed8 = {ptl_png_pixel8, "png_deflate.hsaco", "ptl_png_deflate_bands_kernel", false, "png_deflate_rgba8_codes", "png_deflate_rgba8", "png_deflate"};
+const DeflateFormat kDeflateDynamic8 = {ptl_png_pixel8, "png_huffman.hsaco", "ptl_png_huffman_bands_kernel", false, "png_deflate_rgba8_codes", "png_deflate_rgba8", "png_deflate"};
+const DeflateFormat kDeflate16 = {ptl_png_pixel16, "png_huffman.hsaco", "ptl_png_deflate16_bands_kernel", true, "png_deflate_rgb48", "png_deflate_rgb48", "png_deflate16"};
+
+// 0 for a frame that does not fit, else `size` of it.
+size_t deflate_size(unsigned pixel, int width, int height, ptl_png_u64 (*size)(unsigned, unsigned, unsigned)) {
+    return width > 0 && height > 0 && ptl_png_fits(pixel, (unsigned)width, (unsigned)height) ? (size_t)size(pixel, (unsigned)width, (unsigned)height) : 0;
+}
+
+int deflate(const DeflateFormat& f, int device, const void* frame, int width, int height, int codes, void* out, void* stream, float* elapsed_ms) {
     if (codes != PTL_PNG_CODES_FIXED && codes != PTL_PNG_CODES_DYNAMIC) {
-        set_last_error("png_deflate_rgba8_codes: codes " + std::to_string(codes) + " is neither PTL_PNG_CODES_FIXED (0) nor PTL_PNG_CODES_DYNAMIC (1)");
+        set_last_error(std::string(f.codes_name) + ": codes " + std::to_string(codes) + " is neither PTL_PNG_CODES_FIXED (0) nor PTL_PNG_CODES_DYNAMIC (1)");
         return PTL_ERR_INVALID;
     }
-    if (!frame_rgba8 || !out || width <= 0 || height <= 0) return PTL_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(frame_rgba8) | reinterpret_cast<uintptr_t>(out)) & 15u) return PTL_ERR_INVALID;
-    if (!ptl_png_fits((unsigned)width, (unsigned)height)) {  // the kernels address the raw scanlines with 32-bit offsets
-        set_last_error("png_deflate_rgba8: " + std::to_string(width) + " x " + std::to_string(height) + " has more than 2^31 bytes of scanlines");
+    if (!frame || !out || width <= 0 || height <= 0) return PTL_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(frame) | reinterpret_cast<uintptr_t>(out)) & 15u) return PTL_ERR_INVALID;
+    const std::string size = std::string(f.name) + ": " + std::to_string(width) + " x " + std::to_string(height);
+    if (f.pixel == ptl_png_pixel16 && (long)width * height > ptl_rgb48_max_pixels()) {  // the rows' own limit
+        set_last_error(size + " has more than 2^28 pixels");
+        return PTL_ERR_INVALID;
+    }
+    if (!ptl_png_fits(f.pixel, (unsigned)width, (unsigned)height)) {  // the kernels address the raw scanlines with 32-bit offsets
+        set_last_error(size + " has more than 2^31 bytes of scanlines");
         return PTL_ERR_INVALID;
     }
     if (device < 0) return PTL_ERR_NO_DEVICE;
     LoadedKernel *bands_kernel = nullptr, *pack_kernel = nullptr;
-    if (int rc = codes == PTL_PNG_CODES_DYNAMIC ? load_kernel(device, "png_huffman.hsaco", "ptl_png_huffman_bands_kernel", &bands_kernel)
-                                                : load_kernel(device, "png_deflate.hsaco", "ptl_png_deflate_bands_kernel", &bands_kernel);
-        rc != PTL_OK)
-        return rc;
+    if (int rc = load_kernel(device, f.file, f.bands_entry, &bands_kernel); rc != PTL_OK) return rc;
     if (int rc = load_kernel(device, "png_deflate.hsaco", "ptl_png_deflate_pack_kernel", &pack_kernel); rc != PTL_OK) return rc;
     const hip::Runtime* rt = hip::runtime(nullptr);
     rt->hipSetDevice(device);
-    unsigned w = (unsigned)width, h = (unsigned)height, rows = ptl_png_band_rows(w), n_bands = ptl_png_bands(w, h);
-    unsigned long long table_offset = ptl_png_table_offset(w, h), slots_offset = ptl_png_slots_offset(w, h), slot_stride = ptl_png_slot_stride(w);
-    void* table = static_cast<char*>(out) + table_offset;
-    void* slots = static_cast<char*>(out) + slots_offset;
-    void* bands_args[] = {&frame_rgba8, &w, &h, &rows, &n_bands, &table, &slots, &slot_stride};
-    void* pack_args[] = {&out, &w, &h, &rows, &n_bands, &table_offset, &slots_offset, &slot_stride};
-    const unsigned blocks = (unsigned)grid_blocks(256L * n_bands);  // a workgroup per band
-    const int err = timed(rt, bands_kernel, stream, elapsed_ms, [&] {
-        const int e = rt->hipModuleLaunchKernel(bands_kernel->fn, blocks, 1, 1, 256, 1, 1, 0, stream, bands_args, nullptr);
-        return e != 0 ? e : rt->hipModuleLaunchKernel(pack_kernel->fn, blocks, 1, 1, 256, 1, 1, 0, stream, pack_args, nullptr);
-    });
-    if (err != 0) {
-        set_last_error(std::string("hipModuleLaunchKernel(png_deflate): ") + rt->hipGetErrorString(err));
-        rt->hipGetLastError();
-        return PTL_ERR_HIP;
-    }
-    return PTL_OK;
-}
-
-extern "C" int ptl_png_deflate_rgba8(int device, const void* frame_rgba8, int width, int height, void* out, void* stream, float* elapsed_ms) {
-    return ptl_png_deflate_rgba8_codes(device, frame_rgba8, width, height, PTL_PNG_CODES_FIXED, out, stream, elapsed_ms);
-}
-
-// The GPU deflate of a 16-bit PNG frame (portal_amd/csrc/kernels/png_deflate16.hip; the stream contract is in include/portal_amd.h): the same
-// two launches over the unfiltered rows of ptl_average_f32_to_rgb48, with a bands kernel and a pack kernel of its own.  The band cut and the
-// layout of the result buffer are png_deflate16_shape.h's to say.
-extern "C" size_t ptl_png_stream16_bytes(int width, int height) {
-    return width > 0 && height > 0 && ptl_png16_fits((unsigned)width, (unsigned)height) ? (size_t)ptl_png16_result_bytes((unsigned)width, (unsigned)height) : 0;
-}
-extern "C" size_t ptl_png_stream16_download_bytes(int width, int height) {
-    return width > 0 && height > 0 && ptl_png16_fits((unsigned)width, (unsigned)height) ? (size_t)ptl_png16_table_offset((unsigned)width, (unsigned)height) : 0;
-}
-extern "C" int ptl_png_stream16_band_rows(int width) { return width > 0 && width <= (1 << 28) ? (int)ptl_png16_band_rows((unsigned)width) : 0; }
-
-extern "C" int ptl_png_deflate_rgb48(int device, const void* rows_rgb48, int width, int height, int codes, void* out, void* stream, float* elapsed_ms) {
-    if (codes != PTL_PNG_CODES_FIXED && codes != PTL_PNG_CODES_DYNAMIC) {
-        set_last_error("png_deflate_rgb48: codes " + std::to_string(codes) + " is neither PTL_PNG_CODES_FIXED (0) nor PTL_PNG_CODES_DYNAMIC (1)");
-        return PTL_ERR_INVALID;
-    }
-    if (!rows_rgb48 || !out || width <= 0 || height <= 0) return PTL_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(rows_rgb48) | reinterpret_cast<uintptr_t>(out)) & 15u) return PTL_ERR_INVALID;
-    if ((long)width * height > ptl_rgb48_max_pixels()) {  // the rows' own limit
-        set_last_error("png_deflate_rgb48: " + std::to_string(width) + " x " + std::to_string(height) + " has more than 2^28 pixels");
-        return PTL_ERR_INVALID;
-    }
-    if (!ptl_png16_fits((unsigned)width, (unsigned)height)) {  // the kernels address the raw scanlines with 32-bit offsets
-        set_last_error("png_deflate_rgb48: " + std::to_string(width) + " x " + std::to_string(height) + " has more than 2^31 bytes of scanlines");
-        return PTL_ERR_INVALID;
-    }
-    if (device < 0) return PTL_ERR_NO_DEVICE;
-    LoadedKernel *bands_kernel = nullptr, *pack_kernel = nullptr;
-    if (int rc = load_kernel(device, "png_deflate16.hsaco", "ptl_png_deflate16_bands_kernel", &bands_kernel); rc != PTL_OK) return rc;
-    if (int rc = load_kernel(device, "png_deflate16.hsaco", "ptl_png_deflate16_pack_kernel", &pack_kernel); rc != PTL_OK) return rc;
-    const hip::Runtime* rt = hip::runtime(nullptr);
-    rt->hipSetDevice(device);
-    unsigned w = (unsigned)width, h = (unsigned)height, rows = ptl_png16_band_rows(w), n_bands = ptl_png16_bands(w, h), mode = (unsigned)codes;
-    unsigned long long table_offset = ptl_png16_table_offset(w, h), slots_offset = ptl_png16_slots_offset(w, h), slot_stride = ptl_png16_slot_stride(w);
+    unsigned w = (unsigned)width, h = (unsigned)height, pixel = f.pixel, magic = ptl_png_magic(pixel), mode = (unsigned)codes;
+    unsigned rows = ptl_png_band_rows(pixel, w), n_bands = ptl_png_bands(pixel, w, h);
+    unsigned long long table_offset = ptl_png_table_offset(pixel, w, h), slots_offset = ptl_png_slots_offset(pixel, w, h), slot_stride = ptl_png_slot_stride(pixel, w);
     unsigned long long stream_room = table_offset - ptl_png_header_bytes;
     void* table = static_cast<char*>(out) + table_offset;
     void* slots = static_cast<char*>(out) + slots_offset;
-    void* bands_args[] = {&rows_rgb48, &w, &h, &rows, &n_bands, &mode, &table, &slots, &slot_stride};
-    void* pack_args[] = {&out, &w, &h, &rows, &n_bands, &table_offset, &slots_offset, &slot_stride, &stream_room};
+    std::vector<void*> bands_args = {&frame, &w, &h, &rows, &n_bands, &table, &slots, &slot_stride};
+    if (f.codes_argument) bands_args.insert(bands_args.begin() + 5, &mode);
+    void* pack_args[] = {&out, &w, &h, &rows, &n_bands, &pixel, &magic, &table_offset, &slots_offset, &slot_stride, &stream_room};
     const unsigned blocks = (unsigned)grid_blocks(256L * n_bands);  // a workgroup per band
     const int err = timed(rt, bands_kernel, stream, elapsed_ms, [&] {
-        const int e = rt->hipModuleLaunchKernel(bands_kernel->fn, blocks, 1, 1, 256, 1, 1, 0, stream, bands_args, nullptr);
+        const int e = rt->hipModuleLaunchKernel(bands_kernel->fn, blocks, 1, 1, 256, 1, 1, 0, stream, bands_args.data(), nullptr);
         return e != 0 ? e : rt->hipModuleLaunchKernel(pack_kernel->fn, blocks, 1, 1, 256, 1, 1, 0, stream, pack_args, nullptr);
     });
     if (err != 0) {
-        set_last_error(std::string("hipModuleLaunchKernel(png_deflate16): ") + rt->hipGetErrorString(err));
+        set_last_error(std::string("hipModuleLaunchKernel(") + f.launch_name + "): " + rt->hipGetErrorString(err));
         rt->hipGetLastError();
         return PTL_ERR_HIP;
     }
     return PTL_OK;
+}
+}  // namespace
+
+extern "C" size_t ptl_png_stream_bytes(int width, int height) { return deflate_size(ptl_png_pixel8, width, height, ptl_png_result_bytes); }
+extern "C" size_t ptl_png_stream_download_bytes(int width, int height) { return deflate_size(ptl_png_pixel8, width, height, ptl_png_table_offset); }
+extern "C" int ptl_png_stream_band_rows(int width) { return width > 0 && width <= (1 << 29) ? (int)ptl_png_band_rows(ptl_png_pixel8, (unsigned)width) : 0; }
+extern "C" size_t ptl_png_stream16_bytes(int width, int height) { return deflate_size(ptl_png_pixel16, width, height, ptl_png_result_bytes); }
+extern "C" size_t ptl_png_stream16_download_bytes(int width, int height) { return deflate_size(ptl_png_pixel16, width, height, ptl_png_table_offset); }
+extern "C" int ptl_png_stream16_band_rows(int width) { return width > 0 && width <= (1 << 28) ? (int)ptl_png_band_rows(ptl_png_pixel16, (unsigned)width) : 0; }
+
+// `codes`: PTL_PNG_CODES_FIXED launches the one-pass bands kernel of png_deflate.hip, PTL_PNG_CODES_DYNAMIC the two-pass one of png_huffman.hip,
+// which writes the same table entries and slots.  The 16-bit frames go through the two-pass kernel in both modes.
+extern "C" int ptl_png_deflate_rgba8_codes(int device, const void* frame_rgba8, int width, int height, int codes, void* out, void* stream, float* elapsed_ms) {
+    return deflate(codes == PTL_PNG_CODES_DYNAMIC ? kDeflateDynamic8 : kDeflateFixed8, device, frame_rgba8, width, height, codes, out, stream, elapsed_ms);
+}
+extern "C" int ptl_png_deflate_rgba8(int device, const void* frame_rgba8, int width, int height, void* out, void* stream, float* elapsed_ms) {
+    return deflate(kDeflateFixed8, device, frame_rgba8, width, height, PTL_PNG_CODES_FIXED, out, stream, elapsed_ms);
+}
+extern "C" int ptl_png_deflate_rgb48(int device, const void* rows_rgb48, int width, int height, int codes, void* out, void* stream, float* elapsed_ms) {
+    return deflate(kDeflate16, device, rows_rgb48, width, height, codes, out, stream, elapsed_ms);
 }
 
 // ---- trace passes: the records a PTL_FLAG_PASSES render entry stores (portal_amd/csrc/kernels/pass_stats.hip, pass_gray16.hip; the contracts are

@@ -1,7 +1,8 @@
 """GPU deflate of 16-bit PNG frames (`--png-depth 16 --png16-encoder gpu`): the bands and the pack kernel
-(portal_amd/csrc/kernels/png_deflate16.hip) through ptl_png_deflate_rgb48 and the Python mirror, and the CLI.  In every case the whole
+(portal_amd/csrc/kernels/png_huffman.hip, png_deflate.hip) through ptl_png_deflate_rgb48 and the Python mirror, and the CLI.  In every case the whole
 result buffer -- header and stream, up to the header's byte count -- is compared byte for byte with tests/png16_deflate_reference.py, and
 zlib.decompress of the stream has to return the raw scanlines."""
+import functools
 import math
 import os
 import zlib
@@ -12,6 +13,7 @@ import pytest
 from tests import png16_deflate_cases as cs
 from tests import png16_deflate_reference as r6
 from tests import png16_reference as p16
+from tests import png_deflate_harness as hs
 from tests import yuv_deep_reference as dr
 from tests.test_png16 import _clip_frames, _render_clip, _run_cli
 from tests.yuv_harness import GUARD, H, KNOB, W, _c_getenv, _once, _shipped_grid_cap, gpu  # noqa: F401 (gpu: a fixture)
@@ -30,51 +32,15 @@ def _bands(raw, w, h):
     return out
 
 
-def _deflate(pa, a, codes=DYNAMIC, buf=None, timed=False, stream=0):
-    """The unfiltered rows of A through ptl_png_deflate_rgb48 -> the whole result buffer as host bytes; the 64 guard bytes behind it must
-    survive."""
-    import torch
-
+def _encode(a):
     h, w = a.shape[:2]
-    nbytes = pa.png_stream16_bytes(w, h)
-    assert nbytes == r6.result_bytes(w, h)
-    rows = a if isinstance(a, torch.Tensor) else torch.from_numpy(r6.rows_bytes(a)).cuda()
-    if buf is None:
-        buf = torch.full((nbytes + 64,), GUARD, dtype=torch.uint8, device="cuda")
-    assert buf.numel() == nbytes + 64 and buf.data_ptr() % 16 == 0 and rows.data_ptr() % 16 == 0 and rows.numel() == 6 * w * h
-    ms = pa.png_deflate_rgb48_device(rows.data_ptr(), buf.data_ptr(), w, h, stream=stream or torch.cuda.current_stream().cuda_stream, timed=timed, codes=codes)
-    torch.cuda.synchronize()
-    host = buf.cpu().numpy()
-    assert (host[nbytes:] == GUARD).all(), "written behind the result buffer"
-    return (host[:nbytes].tobytes(), ms) if timed else host[:nbytes].tobytes()
+    raw = r6.raw16(a)
+    bands = _bands(raw, w, h)
+    return {False: r6.result(raw, w, h, bands), True: r6.result(raw, w, h, bands, fixed=True)}, bands, raw
 
 
-def _reference(key, a, fixed=False):
-    """(result buffer up to the end of the stream, the bands' details, raw16), computed once per key."""
-    def make():
-        h, w = a.shape[:2]
-        raw = r6.raw16(a)
-        bands = _bands(raw, w, h)
-        return {False: r6.result(raw, w, h, bands), True: r6.result(raw, w, h, bands, fixed=True)}, bands, raw
-
-    results, bands, raw = _once(("png16 deflate", key), make)
-    return results[fixed], bands, raw
-
-
-def _assert_matches(got, a, what, key=None, fixed=False):
-    want, bands, raw = _reference(key or what, a, fixed)
-    n = int(np.frombuffer(got[12:16], "<u4")[0])
-    if got[: r6.HEADER_BYTES + n] != want:
-        g, r = np.frombuffer(got[: len(want)], np.uint8), np.frombuffer(want, np.uint8)
-        assert got[:64] == want[:64], f"{what}: header {np.frombuffer(got[:28], '<u4').tolist()}, want {np.frombuffer(want[:28], '<u4').tolist()} (bands choose {[b['dynamic'] for b in bands][:8]})"
-        first = int(np.flatnonzero(g != r)[0])
-        pytest.fail(f"{what}: {int((g != r).sum())} of {len(want)} bytes differ, the first at {first} (stream byte {first - 64}): got {g[first: first + 8].tolist()}, want {r[first: first + 8].tolist()}")
-    assert r6.inflate(got) == raw, what
-    return bands
-
-
-def _check(pa, a, what, codes=DYNAMIC):
-    return _assert_matches(_deflate(pa, a, codes=codes), a, what, fixed=codes == FIXED)
+RGB48 = hs.Format("png16 deflate", r6, 6, "png_stream16_bytes", "png_stream16_band_rows", "png_deflate_rgb48_device", hs.DYNAMIC, r6.rows_bytes, _encode)
+_deflate, _assert_matches, _check = (functools.partial(f, RGB48) for f in (hs._deflate, hs._assert_matches, hs._check))
 
 
 @pytest.mark.gpu

@@ -1,12 +1,14 @@
 """GPU deflate of 8-bit PNG frames (`--png-encoder gpu`): the kernels (portal_amd/csrc/kernels/png_deflate.hip) through the C
 ABI and the Python mirror, and the CLI.  In every case the whole result buffer -- header and stream, up to the header's byte count -- is
 compared byte for byte with tests/png_deflate_reference.py, and zlib.decompress of the stream has to return the raw scanlines."""
+import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import png_deflate_harness as hs
 from tests import png_deflate_reference as pr
 from tests.yuv_harness import FPS, GUARD, H, KNOB, ROOT, W, _c_getenv, _once, _path_without_ffmpeg, _shipped_grid_cap, gpu  # noqa: F401 (gpu: a fixture)
 
@@ -39,35 +41,9 @@ def _mixed(w, h, seed):
     return _frame_of_raw(flat.reshape(h, 4 * w))
 
 
-def _deflate(pa, frame, buf=None, timed=False, stream=0):
-    """The frame through ptl_png_deflate_rgba8 -> the whole result buffer as host bytes; the 64 guard bytes behind it must survive."""
-    import torch
-
-    h, w = frame.shape[:2]
-    nbytes = pa.png_stream_bytes(w, h)
-    assert nbytes == pr.result_bytes(w, h) and pa.png_stream_band_rows(w) == pr.band_rows(w)
-    staged = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame, np.uint8)).cuda()
-    if buf is None:
-        buf = torch.full((nbytes + 64,), GUARD, dtype=torch.uint8, device="cuda")
-    assert buf.numel() == nbytes + 64 and buf.data_ptr() % 16 == 0 and staged.data_ptr() % 16 == 0
-    ms = pa.png_deflate_rgba8_device(staged.data_ptr(), buf.data_ptr(), w, h, stream=stream or torch.cuda.current_stream().cuda_stream, timed=timed)
-    torch.cuda.synchronize()
-    host = buf.cpu().numpy()
-    assert (host[nbytes:] == GUARD).all(), "written behind the result buffer"
-    return (host[:nbytes].tobytes(), ms) if timed else host[:nbytes].tobytes()
-
-
-def _assert_matches(got, frame, what):
-    """Header and stream against the reference, byte for byte; the stream inflates to the raw scanlines."""
-    frame = frame if isinstance(frame, np.ndarray) else frame.cpu().numpy()
-    want = pr.result(frame)
-    n = int(np.frombuffer(got[12:16], "<u4")[0])
-    if got[: pr.HEADER_BYTES + n] != want:
-        g, r = np.frombuffer(got[: len(want)], np.uint8), np.frombuffer(want, np.uint8)
-        assert got[:64] == want[:64], f"{what}: header {np.frombuffer(got[:28], '<u4').tolist()}, want {np.frombuffer(want[:28], '<u4').tolist()}"
-        first = int(np.flatnonzero(g != r)[0])
-        pytest.fail(f"{what}: {int((g != r).sum())} of {len(want)} bytes differ, the first at {first} (stream byte {first - 64}): got {g[first: first + 8].tolist()}, want {r[first: first + 8].tolist()}")
-    assert pr.inflate(got) == pr.raw_scanlines(frame), what
+FIXED8 = hs.Format("png deflate", pr, 4, "png_stream_bytes", "png_stream_band_rows", "png_deflate_rgba8_device", hs.FIXED, lambda frame: np.ascontiguousarray(frame, np.uint8),
+                  lambda frame: ({True: pr.result(frame)}, None, pr.raw_scanlines(frame)))
+_deflate, _assert_matches = functools.partial(hs._deflate, FIXED8), functools.partial(hs._assert_matches, FIXED8)
 
 
 def _check(pa, frame, what):

@@ -2,62 +2,26 @@
 (portal_amd/csrc/kernels/png_huffman.hip) and the shared pack kernel through ptl_png_deflate_rgba8_codes and the Python mirror, and the CLI.
 In every case the whole result buffer -- header and stream, up to the header's byte count -- is compared byte for byte with
 tests/png_huffman_reference.py, and zlib.decompress of the stream has to return the raw scanlines."""
+import functools
 import os
 
 import numpy as np
 import pytest
 
+from tests import png_deflate_harness as hs
 from tests import png_deflate_reference as pr
 from tests import png_huffman_reference as hr
 from tests.png_huffman_cases import costly_last_segment_frame, fibonacci_frame
 from tests.test_gpu_png_deflate import _frame_of_raw, _mixed, _noise, _pixels, _render_clip, _run_cli, _runs_frame
 from tests.yuv_harness import GUARD, H, KNOB, W, _c_getenv, _once, gpu  # noqa: F401 (gpu: a fixture)
 
-DYNAMIC = 1
+def _encode(frame):
+    bands = hr.encode_bands(frame)
+    return {False: hr.result(frame, bands)}, bands, pr.raw_scanlines(frame)
 
 
-def _deflate(pa, frame, codes=DYNAMIC, buf=None, timed=False, stream=0):
-    """The frame through ptl_png_deflate_rgba8_codes -> the whole result buffer as host bytes; the 64 guard bytes behind it must survive."""
-    import torch
-
-    h, w = frame.shape[:2]
-    nbytes = pa.png_stream_bytes(w, h)
-    assert nbytes == pr.result_bytes(w, h)
-    staged = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame, np.uint8)).cuda()
-    if buf is None:
-        buf = torch.full((nbytes + 64,), GUARD, dtype=torch.uint8, device="cuda")
-    assert buf.numel() == nbytes + 64 and buf.data_ptr() % 16 == 0 and staged.data_ptr() % 16 == 0
-    ms = pa.png_deflate_rgba8_device(staged.data_ptr(), buf.data_ptr(), w, h, stream=stream or torch.cuda.current_stream().cuda_stream, timed=timed, codes=codes)
-    torch.cuda.synchronize()
-    host = buf.cpu().numpy()
-    assert (host[nbytes:] == GUARD).all(), "written behind the result buffer"
-    return (host[:nbytes].tobytes(), ms) if timed else host[:nbytes].tobytes()
-
-
-def _reference(key, frame):
-    """(result buffer up to the end of the stream, the bands' details), computed once per key."""
-    def make():
-        bands = hr.encode_bands(frame)
-        return hr.result(frame, bands), bands
-
-    return _once(("png huffman", key), make)
-
-
-def _assert_matches(got, frame, what, key=None):
-    frame = frame if isinstance(frame, np.ndarray) else frame.cpu().numpy()
-    want, bands = _reference(key or what, frame)
-    n = int(np.frombuffer(got[12:16], "<u4")[0])
-    if got[: pr.HEADER_BYTES + n] != want:
-        g, r = np.frombuffer(got[: len(want)], np.uint8), np.frombuffer(want, np.uint8)
-        assert got[:64] == want[:64], f"{what}: header {np.frombuffer(got[:28], '<u4').tolist()}, want {np.frombuffer(want[:28], '<u4').tolist()} (bands choose {[b['dynamic'] for b in bands][:8]})"
-        first = int(np.flatnonzero(g != r)[0])
-        pytest.fail(f"{what}: {int((g != r).sum())} of {len(want)} bytes differ, the first at {first} (stream byte {first - 64}): got {g[first: first + 8].tolist()}, want {r[first: first + 8].tolist()}")
-    assert pr.inflate(got) == pr.raw_scanlines(frame), what
-    return bands
-
-
-def _check(pa, frame, what):
-    return _assert_matches(_deflate(pa, frame), frame, what)
+DYNAMIC8 = hs.Format("png huffman", pr, 4, "png_stream_bytes", "png_stream_band_rows", "png_deflate_rgba8_device", hs.DYNAMIC, lambda frame: np.ascontiguousarray(frame, np.uint8), _encode)
+_deflate, _assert_matches, _check = (functools.partial(f, DYNAMIC8) for f in (hs._deflate, hs._assert_matches, hs._check))
 
 
 @pytest.mark.gpu

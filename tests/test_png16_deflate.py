@@ -4,8 +4,6 @@ reaches, the host's writer on reference-made buffers (also in a stand-alone prog
 entry point and of the CLI, and the cross-compile of the kernel file."""
 import ctypes as C
 import os
-import re
-import shutil
 import struct
 import subprocess
 import zlib
@@ -19,7 +17,7 @@ from tests import png16_reference as p16
 from tests import png_deflate_reference as pr
 from tests import png_huffman_reference as hr
 from tests import yuv_deep_reference as dr
-from tests.yuv_harness import HIPCC, ROOT, _once, _resource_usage
+from tests.yuv_harness import ROOT, _once
 
 CASES = {"1x1": lambda: cs.noise(1, 1), "2x1": lambda: cs.noise(2, 1), "h=1": lambda: cs.noise(33, 1), "w=1": lambda: cs.noise(1, 9), "w=3": lambda: cs.noise(3, 4),
          "w=5": lambda: cs.noise(5, 70), "w=17": lambda: cs.noise(17, 300), "64x64": lambda: cs.noise(64, 64), "one colour": lambda: cs.one_colour(256, 64),
@@ -351,35 +349,3 @@ def test_stream_writer_under_sanitizers(tmp_path):
         assert "ERROR" not in run.stderr and "runtime error" not in run.stderr
         assert os.listdir(files) == ["ok.png"]
         assert np.array_equal(r6.read_png16_up(str(files / "ok.png")), a)
-
-
-def test_make_builds_the_code_object_without_scratch(tmp_path):
-    """`make portal_amd/kernels/png_deflate16.hsaco` in a copy of the tree's Makefile and kernel sources: both entries compile for gfx950 with
-    0 bytes of scratch and no VGPR spills, the bands kernel's LDS is what the source's header comment states and far under the 64 KB a
-    workgroup may use; no inline assembly; the shared steps come from the common headers, and the 8-bit kernel files are not touched by
-    the new ones."""
-    shutil.copy(os.path.join(ROOT, "Makefile"), tmp_path / "Makefile")
-    shutil.copytree(os.path.join(ROOT, "portal_amd", "csrc", "kernels"), tmp_path / "portal_amd" / "csrc" / "kernels")
-    target = "portal_amd/kernels/png_deflate16.hsaco"
-    out = subprocess.run(["make", target, f"HIPCC={HIPCC} -Rpass-analysis=kernel-resource-usage"], cwd=tmp_path, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr
-    assert os.path.getsize(tmp_path / target) > 1000
-    usage = _resource_usage(out.stderr)
-    assert set(usage) == {"ptl_png_deflate16_bands_kernel", "ptl_png_deflate16_pack_kernel"}
-    kernels = os.path.join(ROOT, "portal_amd", "csrc", "kernels")
-    source, beside = open(os.path.join(kernels, "png_deflate16.hip")).read(), open(os.path.join(kernels, "png_deflate16_common.h")).read()
-    stated = int(re.search(r"= (\d+) bytes\.  No scratch", source).group(1))
-    for entry, u in usage.items():
-        assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0, (entry, u)
-        assert u["LDS Size [bytes/block]"] < 64 * 1024, (entry, u)
-    u = usage["ptl_png_deflate16_bands_kernel"]
-    assert stated <= u["LDS Size [bytes/block]"] <= stated + 16 and 8 * u["LDS Size [bytes/block]"] <= 160 * 1024, u  # (the compiler pads between the arrays); eight workgroups' worth fits a compute unit's LDS
-    print("VGPRs:", {e: v["VGPRs"] for e, v in sorted(usage.items())}, "LDS:", u["LDS Size [bytes/block]"])
-    makefile = open(os.path.join(ROOT, "Makefile")).read()
-    assert target in re.search(r"^KERNELS\s*:=(.*)$", makefile, re.M).group(1) and makefile.count("png_deflate16_shape.h") == 2 and "png_deflate16_common.h" in makefile
-    assert '#include "png_deflate16_common.h"' in source and '#include "png_deflate_common.h"' in beside and '#include "png_deflate16_shape.h"' in beside
-    for text in (source, beside):
-        assert "asm" not in text and "atomicAdd(&table" not in text
-    assert "static_assert(kLimit + 5u + kDynamicDistanceBits <= 24u" in source and "ptl_png_or_bits(bits" in source
-    for host in ("postprocess.cpp", "png_io.cpp"):
-        assert '#include "../kernels/png_deflate16_shape.h"' in open(os.path.join(ROOT, "portal_amd", "csrc", "host", host)).read()

@@ -14,9 +14,6 @@ import pytest
 from tests import png_deflate_reference as pr
 from tests.yuv_harness import HIPCC, ROOT, _compile_with_usage
 
-ENTRIES = {"ptl_png_deflate_bands_kernel", "ptl_png_deflate_pack_kernel"}
-
-
 def _noise(w, h, seed=0):
     return np.random.default_rng(seed + 1000 * w + h).integers(0, 256, (h, w, 4), dtype=np.uint8)
 
@@ -294,32 +291,52 @@ def test_stream_writer_under_sanitizers(tmp_path):
         assert np.array_equal(np.array(Image.open(files / "ok.png")), frame)
 
 
-def test_make_builds_the_code_object_without_scratch(tmp_path):
-    """`make portal_amd/kernels/png_deflate.hsaco` in a copy of the tree's Makefile and kernel sources: both entries compile for gfx950 with 0
-    bytes of scratch and no VGPR spills, and the LDS is what the source's header comment states; no inline assembly."""
+# code object -> its entries; for a bands kernel the place of its LDS figure among the "= N bytes.  No scratch" of the source's header comment
+CODE_OBJECTS = {"png_deflate": {"ptl_png_deflate_bands_kernel": 0, "ptl_png_deflate_pack_kernel": None},
+                "png_huffman": {"ptl_png_huffman_bands_kernel": 0, "ptl_png_deflate16_bands_kernel": 1}}
+
+
+@pytest.mark.parametrize("name", list(CODE_OBJECTS))
+def test_make_builds_the_code_object_without_scratch(tmp_path, name):
+    """`make portal_amd/kernels/<name>.hsaco` in a copy of the tree's Makefile and kernel sources: exactly the entries above compile for gfx950
+    with 0 bytes of scratch and no VGPR spills; a bands kernel's LDS is what the source's header comment states, eight workgroups' worth fits a
+    compute unit's LDS, and three waves fit a SIMD; the pack kernel keeps eight; no inline assembly; the shared steps come from the one
+    common header and the shape from the one shape header, which the host files include as well."""
     import shutil
+
+    from tests.yuv_harness import _resource_usage
 
     shutil.copy(os.path.join(ROOT, "Makefile"), tmp_path / "Makefile")
     shutil.copytree(os.path.join(ROOT, "portal_amd", "csrc", "kernels"), tmp_path / "portal_amd" / "csrc" / "kernels")
-    target = "portal_amd/kernels/png_deflate.hsaco"
+    target = f"portal_amd/kernels/{name}.hsaco"
     out = subprocess.run(["make", target, f"HIPCC={HIPCC} -Rpass-analysis=kernel-resource-usage"], cwd=tmp_path, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr
     assert os.path.getsize(tmp_path / target) > 1000
-    from tests.yuv_harness import _resource_usage
-
     usage = _resource_usage(out.stderr)
-    assert set(usage) == ENTRIES
-    source = open(os.path.join(ROOT, "portal_amd", "csrc", "kernels", "png_deflate.hip")).read()
-    stated = int(re.search(r"= (\d+) bytes\.  No scratch", source).group(1))
-    assert stated <= 10 * 1024 + 512  # "about 10 KB"
-    for entry, u in usage.items():
+    assert set(usage) == set(CODE_OBJECTS[name])
+    kernels = os.path.join(ROOT, "portal_amd", "csrc", "kernels")
+    source, common = open(os.path.join(kernels, name + ".hip")).read(), open(os.path.join(kernels, "png_deflate_common.h")).read()
+    stated = [int(n) for n in re.findall(r"= (\d+) bytes\.  No scratch", source)]
+    assert len(stated) == sum(1 for at in CODE_OBJECTS[name].values() if at is not None)
+    for entry, at in CODE_OBJECTS[name].items():
+        u = usage[entry]
         assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0, (entry, u)
-        assert u["LDS Size [bytes/block]"] <= stated, (entry, u)
-    assert usage["ptl_png_deflate_bands_kernel"]["LDS Size [bytes/block]"] == stated
-    print("VGPRs:", {e: u["VGPRs"] for e, u in sorted(usage.items())})
-    assert _compile_with_usage("png_deflate", tmp_path) == usage  # the harness's own compile line is the Makefile's
+        if at is None:
+            assert u["LDS Size [bytes/block]"] <= min(stated) and u["Occupancy [waves/SIMD]"] == 8, (entry, u)
+        else:
+            assert u["LDS Size [bytes/block]"] == stated[at] and 8 * stated[at] <= 160 * 1024 and u["Occupancy [waves/SIMD]"] >= 3, (entry, u)
+    if name == "png_deflate":
+        assert stated[0] <= 10 * 1024 + 512  # "about 10 KB"
+    print("VGPRs:", {e: u["VGPRs"] for e, u in sorted(usage.items())}, "LDS:", {e: u["LDS Size [bytes/block]"] for e, u in sorted(usage.items())})
+    assert _compile_with_usage(name, tmp_path) == usage  # the harness's own compile line is the Makefile's
     makefile = open(os.path.join(ROOT, "Makefile")).read()
-    assert target in re.search(r"^KERNELS\s*:=(.*)$", makefile, re.M).group(1) and makefile.count("png_deflate_shape.h") == 2
-    assert '#include "png_deflate_shape.h"' in source and "asm" not in source and "atomicOr(&bits[" in source
+    assert target in re.search(r"^KERNELS\s*:=(.*)$", makefile, re.M).group(1) and makefile.count("png_deflate_shape.h") == 2 and "png_deflate_common.h" in makefile
+    assert "deflate16" not in makefile and sorted(f for f in os.listdir(kernels) if "deflate" in f or "huffman" in f) == ["png_deflate.hip", "png_deflate_common.h", "png_deflate_shape.h", "png_huffman.hip"]
+    assert '#include "png_deflate_common.h"' in source and '#include "png_deflate_shape.h"' in common
+    for text in (source, common):
+        assert "asm" not in text and "atomicAdd(&table" not in text
+    assert "atomicOr(&bits[" in common and "ptl_png_or_bits(lds.bits" in common
+    if name == "png_huffman":
+        assert "atomicAdd(&lds.hist[" in source and "static_assert(kLimit + 5u + F::dynamic_distance_bits <= 24u" in source
     for host in ("postprocess.cpp", "png_io.cpp"):
         assert '#include "../kernels/png_deflate_shape.h"' in open(os.path.join(ROOT, "portal_amd", "csrc", "host", host)).read()

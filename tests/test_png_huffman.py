@@ -4,7 +4,6 @@ stream, the sizes the format reaches, the host's writer on reference-made buffer
 cross-compile of the kernel file."""
 import ctypes as C
 import os
-import re
 import struct
 import subprocess
 import zlib
@@ -16,7 +15,7 @@ from tests import png_deflate_reference as pr
 from tests import png_huffman_reference as hr
 from tests.png_huffman_cases import costly_last_segment_frame, fibonacci_frame
 from tests.test_png_deflate import CASES, _chunks
-from tests.yuv_harness import HIPCC, ROOT, _once, _resource_usage
+from tests.yuv_harness import ROOT, _once
 
 ALL_CASES = dict(CASES)
 ALL_CASES.update({"w=1 column": lambda: np.random.default_rng(19).integers(0, 256, (40, 1, 4), dtype=np.uint8), "64x64": lambda: np.random.default_rng(64).integers(0, 256, (64, 64, 4), dtype=np.uint8),
@@ -221,32 +220,3 @@ def test_usage_names_the_option_and_its_default(pa):
     exe = os.path.join(os.path.dirname(pa.__file__), "portal-amd")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 2 and out.stderr.count("--png-codes fixed|dynamic") == 2 and out.stderr.count("fixed (default)") == 2  # render-frame's and render's
-
-
-def test_make_builds_the_code_object_without_scratch(tmp_path):
-    """`make portal_amd/kernels/png_huffman.hsaco` in a copy of the tree's Makefile and kernel sources: the entry compiles for gfx950 with 0 bytes
-    of scratch and no VGPR spills, and its LDS is what the source's header comment states; no inline assembly; the steps shared with the fixed
-    kernel come from the common header."""
-    import shutil
-
-    shutil.copy(os.path.join(ROOT, "Makefile"), tmp_path / "Makefile")
-    shutil.copytree(os.path.join(ROOT, "portal_amd", "csrc", "kernels"), tmp_path / "portal_amd" / "csrc" / "kernels")
-    target = "portal_amd/kernels/png_huffman.hsaco"
-    out = subprocess.run(["make", target, f"HIPCC={HIPCC} -Rpass-analysis=kernel-resource-usage"], cwd=tmp_path, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr
-    assert os.path.getsize(tmp_path / target) > 1000
-    usage = _resource_usage(out.stderr)
-    assert set(usage) == {"ptl_png_huffman_bands_kernel"}
-    source = open(os.path.join(ROOT, "portal_amd", "csrc", "kernels", "png_huffman.hip")).read()
-    common = open(os.path.join(ROOT, "portal_amd", "csrc", "kernels", "png_deflate_common.h")).read()
-    stated = int(re.search(r"= (\d+) bytes\.  No scratch", source).group(1))
-    u = usage["ptl_png_huffman_bands_kernel"]
-    assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0, u
-    assert u["LDS Size [bytes/block]"] == stated and 8 * stated <= 160 * 1024, u  # eight workgroups' worth fits a compute unit's LDS
-    print("VGPRs:", u["VGPRs"], "LDS:", u["LDS Size [bytes/block]"])
-    makefile = open(os.path.join(ROOT, "Makefile")).read()
-    assert target in re.search(r"^KERNELS\s*:=(.*)$", makefile, re.M).group(1) and "png_deflate_common.h" in makefile
-    assert '#include "png_deflate_common.h"' in source and '#include "png_deflate_shape.h"' in common
-    for text in (source, common):
-        assert "asm" not in text and "atomicAdd(&table" not in text
-    assert "atomicOr(&bits[" in common and "atomicAdd(&hist[" in source

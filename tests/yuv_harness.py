@@ -91,7 +91,7 @@ def _resource_usage(notes):
         m = re.search(r"Function Name: (\w+)", line)
         if m:
             name = m.group(1)
-        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|SGPRs Spill|VGPRs Spill|VGPRs): (\d+)", line)
+        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|VGPRs): (\d+)", line)
         if m and name:
             usage.setdefault(name, {})[m.group(1)] = int(m.group(2))
     print(usage)

@@ -6,10 +6,11 @@ Frames: a rendered one (scenes/portal_in_portal.ron, render depth 40, drawn on t
 warm-up launches, then `--launches` calls back to back between ONE pair of events, `--repeats` times, the kernels alternating; the median is
 reported with the spread beside it.  A call of ptl_png_deflate_rgba8 is both kernels; their split is read from a kernel trace of this tool
 (rocprofv3 --kernel-trace --stats -- python tools/png_deflate_bench.py --launches 20 --repeats 1).  The stream of every frame is inflated
-with zlib and compared with the frame's raw scanlines, and its size is printed beside zlib's at levels 1 and 3.  One JSON line per cell.
+with zlib and compared with the frame's raw scanlines, and its size is printed beside zlib's at levels 1 and 3, with the SHA-256 of its 64-byte
+header and its bytes (`stream_sha256`: two builds that agree on it wrote the same stream).  One JSON line per cell.
 `--codes dynamic` measures ptl_png_deflate_rgba8_codes with a Huffman code per band (ptl_png_huffman_bands_kernel,
 portal_amd/csrc/kernels/png_huffman.hip, and the same pack kernel) instead; `--codes fixed,dynamic` both, alternating in the one session.
-`--depth 16` measures ptl_png_deflate_rgb48 (portal_amd/csrc/kernels/png_deflate16.hip: matches at pixel distance, a code per band) on the
+`--depth 16` measures ptl_png_deflate_rgb48 (ptl_png_deflate16_bands_kernel, portal_amd/csrc/kernels/png_huffman.hip: matches at pixel distance, a code per band) on the
 unfiltered 16-bit rows of the same draw's float frame (ptl_average_f32_to_rgb48 with PTL_PNG_FILTER_NONE, made on the card) and on 16-bit
 noise, alternating with the 8-bit dynamic call on the draw's RGBA8 frame; beside the stream's size: zlib at levels 1 and 3 of the same Up
 scanlines, and level 3 of the Sub scanlines the host encoder of --png-depth 16 deflates.
@@ -17,6 +18,7 @@ scanlines, and level 3 of the Sub scanlines the host encoder of --png-depth 16 d
     python tools/png_deflate_bench.py [--launches 200] [--repeats 7] [--sizes 3840x2160] [--subframes 4] [--codes fixed|dynamic|fixed,dynamic] [--depth 8|16 [--scene portal_in_portal] [--render-depth 40]]
 """
 import argparse
+import hashlib
 import json
 import os
 import struct
@@ -82,7 +84,8 @@ def bench16(args, torch, dev, stream):
             body = out16[64: 64 + count].cpu().numpy().tobytes()
             up, sub = raw_scanlines16(t.cpu().numpy().reshape(h, 6 * w))
             assert magic == 0x364C5450 and zlib.decompress(b"\x78\x01" + body + b"\x03\x00" + struct.pack(">I", adler)) == up, name
-            sizes["ptl_png_deflate_rgb48:" + name] = {"raw": len(up), "stream": count, "zlib1": len(zlib.compress(up, 1)), "zlib3": len(zlib.compress(up, 3)), "zlib3_sub": len(zlib.compress(sub, 3))}
+            sizes["ptl_png_deflate_rgb48:" + name] = {"raw": len(up), "stream": count, "zlib1": len(zlib.compress(up, 1)), "zlib3": len(zlib.compress(up, 3)), "zlib3_sub": len(zlib.compress(sub, 3)),
+                                                      "stream_sha256": hashlib.sha256(host + body).hexdigest()}
         times = {name: [] for name in kernels}
         for launch in kernels.values():  # warm-up: code objects loaded, clocks up, every buffer touched
             for _ in range(20):
@@ -166,7 +169,8 @@ if __name__ == "__main__":
             body = out[64: 64 + count].cpu().numpy().tobytes()
             raw = raw_scanlines(frames[name])
             assert zlib.decompress(b"\x78\x01" + body + b"\x03\x00" + struct.pack(">I", adler)) == raw, name
-            sizes[label[mode] + name] = {"raw": len(raw), "stream": count, "zlib1": len(zlib.compress(raw, 1)), "zlib3": len(zlib.compress(raw, 3))}
+            sizes[label[mode] + name] = {"raw": len(raw), "stream": count, "zlib1": len(zlib.compress(raw, 1)), "zlib3": len(zlib.compress(raw, 3)),
+                                         "stream_sha256": hashlib.sha256(host + body).hexdigest()}
         times = {name: [] for name in kernels}
         for launch in kernels.values():  # warm-up: code objects loaded, clocks up, every buffer touched
             for _ in range(20):
