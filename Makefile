@@ -28,7 +28,7 @@ $(OBJDIR)/%.o: $(HOST)/%.cpp $(wildcard $(HOST)/*.h) include/portal_amd.h portal
 $(LIB): $(OBJS)
 	$(CXX) -shared -o $@ $(OBJS) -ldl -lz -lpthread
 
-$(CLI): $(HOST)/cli.cpp $(HOST)/cli_video.cpp $(HOST)/cli_common.h $(LIB) include/portal_amd.h
+$(CLI): $(HOST)/cli.cpp $(HOST)/cli_video.cpp $(wildcard $(HOST)/cli*.h) $(LIB) include/portal_amd.h
 	$(CXX) $(CXXFLAGS) $(HOST)/cli.cpp $(HOST)/cli_video.cpp -o $@ -Lportal_amd -lportal_amd -Wl,-rpath,'$$ORIGIN'
 
 kernels: $(KERNELS)

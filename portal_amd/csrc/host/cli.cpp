@@ -10,7 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "cli_common.h"
+#include "cli_png.h"
 
 namespace {
 
@@ -222,6 +222,19 @@ int render_shard(const Options& o) {
     return 0;
 }
 
+// --png-encoder gpu, --png16-encoder gpu: of a deflate's result buffer the header comes down first, then exactly the stream it announces.
+// `deflate`: the entry that filled the buffer, which the bounds check names
+int download_stream(const void* dev_result, size_t result_bytes, const char* deflate, std::vector<uint8_t>* out, unsigned int* stream_bytes) {
+    const size_t header_bytes = PTL_PNG_STREAM_HEADER_BYTES;
+    out->resize(header_bytes);
+    if (ptl_device_download(out->data(), dev_result, header_bytes, nullptr) != PTL_OK) return fail("download");
+    std::memcpy(stream_bytes, out->data() + 12, 4);
+    if (header_bytes + *stream_bytes > result_bytes) return fail((std::string(deflate) + ": the header's byte count").c_str());
+    out->resize(header_bytes + *stream_bytes);
+    if (ptl_device_download(out->data() + header_bytes, static_cast<const char*>(dev_result) + header_bytes, *stream_bytes, nullptr) != PTL_OK) return fail("download");
+    return 0;
+}
+
 int render_frame(const Options& o) {
     std::vector<int> devices = frame_devices(o);
     if (devices.size() > 1 && o.multi_process) return render_frame_processes(o, devices);
@@ -229,8 +242,8 @@ int render_frame(const Options& o) {
     ScenePtr scene = load_scene(o);
     if (!scene) return 1;
     double t_load = seconds_since(t0);
-    std::vector<uint8_t> img((size_t)o.width * o.height * 4);
     if (devices.size() > 1 || o.transport == "rccl") {  // one process, one renderer per GPU (include/portal_amd.h layer 3); `--transport rccl` also with one
+        std::vector<uint8_t> img((size_t)o.width * o.height * 4);
         std::vector<char> log(1 << 16);
         ptl_frame_group* g = nullptr;
         int transport = o.transport == "copy" ? PTL_GROUP_COPY_GATHER : o.transport == "rccl" ? PTL_GROUP_RCCL_GATHER : PTL_GROUP_PEER_STORES;
@@ -262,148 +275,78 @@ int render_frame(const Options& o) {
     double t_build = seconds_since(t0);
     if (int rc = setup_renderer(o, scene.get(), r, true)) return rc;
     ptl_frame frame{o.width, o.height, 0, 1, 0};
-    float ms = 0.0f;
-    unsigned int refined = 0;
-    float pass_ms[3] = {0.0f, 0.0f, 0.0f};
-    std::vector<uint8_t> rows16;  // --png-depth 16: the frame as the scanlines of a 16-bit PNG, Sub-filtered on the card
+    const int device = devices[0];
+    const PngForm form(o);
     // --passes / --depth-report: the draw also stores the pass records, which stay on the card for the two kernels that read them
     const bool with_records = o.have_passes || o.depth_report;
     const size_t n_px = (size_t)o.width * o.height, record_bytes = ptl_pass_record_bytes(o.width, o.height);
-    void* records = nullptr;
-    if (with_records && ptl_device_alloc(devices[0], record_bytes, &records) != PTL_OK) return fail("device records");
-    std::unique_ptr<void, HandleFree> own_records(records);
-    std::vector<uint8_t> deflated;  // --png-encoder gpu: the result buffer of ptl_png_deflate_rgba8, its header and its stream
-    if (o.png_gpu) {
-        // drawn into a frame on the device, deflated there; the header comes down first, then exactly the stream it announces
-        void *dev = nullptr, *dev_result = nullptr, *list = nullptr, *count = nullptr;
-        const size_t result_bytes = ptl_png_stream_bytes(o.width, o.height);
-        if (result_bytes == 0) return fail("--png-encoder gpu: the frame's scanlines exceed 2^31 bytes");
-        if (ptl_device_alloc(devices[0], img.size(), &dev) != PTL_OK) return fail("device frame");
-        std::unique_ptr<void, HandleFree> own(dev);
-        if (ptl_device_alloc(devices[0], result_bytes, &dev_result) != PTL_OK) return fail("device stream");
-        std::unique_ptr<void, HandleFree> own_result(dev_result);
-        if (o.adaptive) {
-            ptl_renderer_set_option(r, "adaptive_aa_threshold", o.adaptive_t);
-            if (ptl_renderer_draw_adaptive(r, &frame, dev, nullptr, nullptr, &ms) != PTL_OK) return fail("render");
-            if (ptl_renderer_adaptive_result(r, &list, &count) != PTL_OK || ptl_device_download(&refined, count, sizeof refined, nullptr) != PTL_OK) return fail("refined count");
-            ptl_renderer_adaptive_times(r, pass_ms);
-        } else if ((with_records ? ptl_renderer_draw_passes(r, &frame, dev, nullptr, records, record_bytes, nullptr, nullptr, &ms) : ptl_renderer_draw(r, &frame, dev, nullptr, nullptr, nullptr, &ms)) != PTL_OK)
-            return fail("render");
-        float deflate_ms = 0.0f;
-        if ((o.png_codes == PTL_PNG_CODES_FIXED ? ptl_png_deflate_rgba8(devices[0], dev, o.width, o.height, dev_result, nullptr, o.timing ? &deflate_ms : nullptr)
-                                                : ptl_png_deflate_rgba8_codes(devices[0], dev, o.width, o.height, o.png_codes, dev_result, nullptr, o.timing ? &deflate_ms : nullptr)) != PTL_OK)
-            return fail("png_deflate_rgba8");
-        const size_t header_bytes = PTL_PNG_STREAM_HEADER_BYTES;
-        deflated.resize(header_bytes);
-        if (ptl_device_download(deflated.data(), dev_result, header_bytes, nullptr) != PTL_OK) return fail("download");
-        unsigned int stream_bytes = 0;
-        std::memcpy(&stream_bytes, deflated.data() + 12, 4);
-        if (header_bytes + stream_bytes > result_bytes) return fail("png_deflate_rgba8: the header's byte count");
-        deflated.resize(header_bytes + stream_bytes);
-        if (ptl_device_download(deflated.data() + header_bytes, static_cast<const char*>(dev_result) + header_bytes, stream_bytes, nullptr) != PTL_OK) return fail("download");
-        if (o.timing) std::printf("png encoder gpu: deflate %.3f ms, %u bytes of stream downloaded\n", deflate_ms, stream_bytes);
-    } else if (o.png_depth == 16) {
-        // drawn on the device with an RGBA32F target next to the RGBA8 one (which the adaptive classification reads), converted there with
-        // n = 1 (ptl_average_f32_to_rgb48), downloaded at 6 bytes per pixel
-        void *dev8 = nullptr, *dev32 = nullptr, *dev_rows = nullptr, *list = nullptr, *count = nullptr;
-        rows16.resize(ptl_rgb48_frame_bytes(o.width, o.height));
-        if (ptl_device_alloc(devices[0], img.size(), &dev8) != PTL_OK) return fail("device frame");
-        std::unique_ptr<void, HandleFree> own8(dev8);
-        if (ptl_device_alloc(devices[0], img.size() * 4, &dev32) != PTL_OK) return fail("device frame");
-        std::unique_ptr<void, HandleFree> own32(dev32);
-        if (ptl_device_alloc(devices[0], rows16.size(), &dev_rows) != PTL_OK) return fail("device frame");
-        std::unique_ptr<void, HandleFree> own_rows(dev_rows);
-        if (o.adaptive) {
-            ptl_renderer_set_option(r, "adaptive_aa_threshold", o.adaptive_t);
-            if (ptl_renderer_draw_adaptive(r, &frame, dev8, dev32, nullptr, &ms) != PTL_OK) return fail("render");
-            if (ptl_renderer_adaptive_result(r, &list, &count) != PTL_OK || ptl_device_download(&refined, count, sizeof refined, nullptr) != PTL_OK) return fail("refined count");
-            ptl_renderer_adaptive_times(r, pass_ms);
-        } else if ((with_records ? ptl_renderer_draw_passes(r, &frame, dev8, dev32, records, record_bytes, nullptr, nullptr, &ms) : ptl_renderer_draw(r, &frame, dev8, dev32, nullptr, nullptr, &ms)) !=
-                   PTL_OK)
-            return fail("render");
-        const void* one[1] = {dev32};
-        if (o.png16_gpu) {
-            // --png16-encoder gpu: the rows unfiltered, deflated on the card; the header comes down first, then exactly the stream it announces
-            void* dev_result = nullptr;
-            const size_t result_bytes = ptl_png_stream16_bytes(o.width, o.height);
-            if (result_bytes == 0) return fail("--png16-encoder gpu: the frame's scanlines exceed 2^31 bytes");
-            if (ptl_device_alloc(devices[0], result_bytes, &dev_result) != PTL_OK) return fail("device stream");
-            std::unique_ptr<void, HandleFree> own_result(dev_result);
-            float deflate_ms = 0.0f;
-            if (ptl_average_f32_to_rgb48(devices[0], one, 1, dev_rows, o.width, o.height, PTL_PNG_FILTER_NONE, nullptr, nullptr) != PTL_OK) return fail("average_f32_to_rgb48");
-            if (ptl_png_deflate_rgb48(devices[0], dev_rows, o.width, o.height, PTL_PNG_CODES_DYNAMIC, dev_result, nullptr, o.timing ? &deflate_ms : nullptr) != PTL_OK) return fail("png_deflate_rgb48");
-            const size_t header_bytes = PTL_PNG_STREAM_HEADER_BYTES;
-            deflated.resize(header_bytes);
-            if (ptl_device_download(deflated.data(), dev_result, header_bytes, nullptr) != PTL_OK) return fail("download");
-            unsigned int stream_bytes = 0;
-            std::memcpy(&stream_bytes, deflated.data() + 12, 4);
-            if (header_bytes + stream_bytes > result_bytes) return fail("png_deflate_rgb48: the header's byte count");
-            deflated.resize(header_bytes + stream_bytes);
-            if (ptl_device_download(deflated.data() + header_bytes, static_cast<const char*>(dev_result) + header_bytes, stream_bytes, nullptr) != PTL_OK) return fail("download");
-            if (o.timing) std::printf("png16 encoder gpu: deflate %.3f ms, %u bytes of stream downloaded\n", deflate_ms, stream_bytes);
-        } else {
-            if (ptl_average_f32_to_rgb48(devices[0], one, 1, dev_rows, o.width, o.height, PTL_PNG_FILTER_SUB, nullptr, nullptr) != PTL_OK) return fail("average_f32_to_rgb48");
-            if (ptl_device_download(rows16.data(), dev_rows, rows16.size(), nullptr) != PTL_OK) return fail("download");
-        }
-    } else if (o.adaptive) {  // one sample per pixel, classification, the flagged pixels again with --aa-count samples: three launches, one download
-        void *dev = nullptr, *list = nullptr, *count = nullptr;
+    // The plain file needs nothing on the card: its draw downloads the frame.  Every other run draws into an RGBA8 frame there (which the adaptive
+    // classification reads), with an RGBA32F one beside it where the form wants floats, and the form makes its result of them with n = 1
+    const bool to_host = form.draws_result(1) && !o.adaptive && !with_records, made = !form.draws_result(1);
+    const size_t result_bytes = form.result_bytes(o.width, o.height), staging_bytes = form.staging_bytes(o.width, o.height, 1);
+    if (form.gpu && result_bytes == 0) return fail(form.sixteen ? "--png16-encoder gpu: the frame's scanlines exceed 2^31 bytes" : "--png-encoder gpu: the frame's scanlines exceed 2^31 bytes");
+    DevicePtr records, dev8, dev32, staging, result;
+    if (with_records && !(records = device_alloc(device, record_bytes, "device records"))) return 1;
+    if (!to_host && !(dev8 = device_alloc(device, n_px * 4, "device frame"))) return 1;
+    if (form.wants_float() && !(dev32 = device_alloc(device, n_px * 16, "device frame"))) return 1;
+    if (staging_bytes != 0 && !(staging = device_alloc(device, staging_bytes, "device frame"))) return 1;
+    if (made && !(result = device_alloc(device, result_bytes, form.gpu ? "device stream" : "device frame"))) return 1;
+    float ms = 0.0f, pass_ms[3] = {0.0f, 0.0f, 0.0f}, deflate_ms = 0.0f;
+    unsigned int refined = 0;
+    std::vector<uint8_t> img(to_host ? n_px * 4 : 0);  // what the form's host step gets
+    if (o.adaptive) {  // one sample per pixel, classification, the flagged pixels again with --aa-count samples: three launches
+        void *list = nullptr, *count = nullptr;
         ptl_renderer_set_option(r, "adaptive_aa_threshold", o.adaptive_t);
-        if (ptl_device_alloc(devices[0], img.size(), &dev) != PTL_OK) return fail("device frame");
-        if (ptl_renderer_draw_adaptive(r, &frame, dev, nullptr, nullptr, &ms) != PTL_OK) return fail("render");
-        if (ptl_device_download(img.data(), dev, img.size(), nullptr) != PTL_OK) return fail("download");
+        if (ptl_renderer_draw_adaptive(r, &frame, dev8.get(), dev32.get(), nullptr, &ms) != PTL_OK) return fail("render");
         if (ptl_renderer_adaptive_result(r, &list, &count) != PTL_OK || ptl_device_download(&refined, count, sizeof refined, nullptr) != PTL_OK) return fail("refined count");
         ptl_renderer_adaptive_times(r, pass_ms);
-        ptl_device_free(dev);
-    } else if (with_records) {
-        void* dev = nullptr;
-        if (ptl_device_alloc(devices[0], img.size(), &dev) != PTL_OK) return fail("device frame");
-        std::unique_ptr<void, HandleFree> own(dev);
-        if (ptl_renderer_draw_passes(r, &frame, dev, nullptr, records, record_bytes, nullptr, nullptr, &ms) != PTL_OK) return fail("render");
-        if (ptl_device_download(img.data(), dev, img.size(), nullptr) != PTL_OK) return fail("download");
-    } else if (ptl_renderer_draw_to_host(r, &frame, img.data(), nullptr, nullptr, &ms) != PTL_OK)
+    } else if ((to_host        ? ptl_renderer_draw_to_host(r, &frame, img.data(), nullptr, nullptr, &ms)
+                : with_records ? ptl_renderer_draw_passes(r, &frame, dev8.get(), dev32.get(), records.get(), record_bytes, nullptr, nullptr, &ms)
+                               : ptl_renderer_draw(r, &frame, dev8.get(), dev32.get(), nullptr, nullptr, &ms)) != PTL_OK)
         return fail("render");
+    const void *one8[1] = {dev8.get()}, *one32[1] = {dev32.get()};
+    if (made)
+        if (int rc = form.make(device, one8, one32, 1, staging.get(), result.get(), o.width, o.height, nullptr, o.timing ? &deflate_ms : nullptr)) return rc;
+    if (form.gpu) {
+        unsigned int stream_bytes = 0;
+        if (int rc = download_stream(result.get(), result_bytes, form.deflate_name(), &img, &stream_bytes)) return rc;
+        if (o.timing) std::printf("%s encoder gpu: deflate %.3f ms, %u bytes of stream downloaded\n", form.sixteen ? "png16" : "png", deflate_ms, stream_bytes);
+    } else if (!to_host) {
+        img.resize(result_bytes);
+        if (ptl_device_download(img.data(), made ? result.get() : dev8.get(), img.size(), nullptr) != PTL_OK) return fail("download");
+    }
     // the pass images: the records as 16-bit grey scanlines, made on the card, 2 bytes per pixel downloaded
     const std::string stem = o.output.size() > 4 && o.output.compare(o.output.size() - 4, 4, ".png") == 0 ? o.output.substr(0, o.output.size() - 4) : o.output;
     std::vector<uint8_t> grey[2], grey_cut;
     if (o.have_passes) {
-        void* dev_grey = nullptr;
-        if (ptl_device_alloc(devices[0], 2 * n_px, &dev_grey) != PTL_OK) return fail("device pass image");
-        std::unique_ptr<void, HandleFree> own_grey(dev_grey);
+        const DevicePtr dev_grey = device_alloc(device, 2 * n_px, "device pass image");
+        if (!dev_grey) return 1;
         float lo[16] = {0.0f}, hi[16] = {1.0f};  // the scene's depth-map bounds, as a draw uploads them
         ptl_renderer_uniform_value(r, o.width, o.height, "_depth_map_min", lo, nullptr);
         ptl_renderer_uniform_value(r, o.width, o.height, "_depth_map_max", hi, nullptr);
         for (int which : {PTL_PASS_DEPTH, PTL_PASS_TRIPS}) {
             if (!(which == PTL_PASS_DEPTH ? o.pass_depth : o.pass_trips)) continue;
             grey[which].resize(2 * n_px);
-            if (ptl_passes_to_gray16(devices[0], records, (long)n_px, dev_grey, which, lo[0], hi[0], nullptr, nullptr) != PTL_OK) return fail("passes_to_gray16");
-            if (ptl_device_download(grey[which].data(), dev_grey, grey[which].size(), nullptr) != PTL_OK) return fail("download");
+            if (ptl_passes_to_gray16(device, records.get(), (long)n_px, dev_grey.get(), which, lo[0], hi[0], nullptr, nullptr) != PTL_OK) return fail("passes_to_gray16");
+            if (ptl_device_download(grey[which].data(), dev_grey.get(), grey[which].size(), nullptr) != PTL_OK) return fail("download");
         }
         if (o.pass_cut) {  // the share of cut paths: the clip's merge over ONE slice
             grey_cut.resize(2 * n_px);
-            if (ptl_pass_slices_to_gray16(devices[0], records, 1, n_px, (long)n_px, nullptr, nullptr, dev_grey, lo[0], hi[0], nullptr, nullptr) != PTL_OK) return fail("pass_slices_to_gray16");
-            if (ptl_device_download(grey_cut.data(), dev_grey, grey_cut.size(), nullptr) != PTL_OK) return fail("download");
+            if (ptl_pass_slices_to_gray16(device, records.get(), 1, n_px, (long)n_px, nullptr, nullptr, dev_grey.get(), lo[0], hi[0], nullptr, nullptr) != PTL_OK) return fail("pass_slices_to_gray16");
+            if (ptl_device_download(grey_cut.data(), dev_grey.get(), grey_cut.size(), nullptr) != PTL_OK) return fail("download");
         }
     }
     ptl_pass_stats_block stats{};
     if (o.depth_report) {
-        void* dev_stats = nullptr;
-        if (ptl_device_alloc(devices[0], sizeof stats, &dev_stats) != PTL_OK) return fail("device statistics");
-        std::unique_ptr<void, HandleFree> own_stats(dev_stats);
-        if (ptl_device_memset(dev_stats, 0, sizeof stats, nullptr) != PTL_OK || ptl_pass_stats(devices[0], records, (long)n_px, dev_stats, nullptr, 0, nullptr, nullptr) != PTL_OK ||
-            ptl_device_download(&stats, dev_stats, sizeof stats, nullptr) != PTL_OK)
+        const DevicePtr dev_stats = device_alloc(device, sizeof stats, "device statistics");
+        if (!dev_stats) return 1;
+        if (ptl_device_memset(dev_stats.get(), 0, sizeof stats, nullptr) != PTL_OK || ptl_pass_stats(device, records.get(), (long)n_px, dev_stats.get(), nullptr, 0, nullptr, nullptr) != PTL_OK ||
+            ptl_device_download(&stats, dev_stats.get(), sizeof stats, nullptr) != PTL_OK)
             return fail("pass_stats");
     }
     double t_draw = seconds_since(t0);
-    if (o.png_depth == 16) {
-        if (!dir_of(o.output).empty()) make_dirs(dir_of(o.output));
-        if ((o.png16_gpu ? ptl_png_write_stream_rgb48(o.output.c_str(), deflated.data(), o.width, o.height)
-                         : ptl_png_write_rgb48(o.output.c_str(), rows16.data(), o.width, o.height, PTL_PNG_FILTER_SUB, 6)) != PTL_OK)
-            return fail("png");
-    } else if (o.png_gpu) {
-        if (!dir_of(o.output).empty()) make_dirs(dir_of(o.output));
-        if (ptl_png_write_stream(o.output.c_str(), deflated.data(), o.width, o.height) != PTL_OK) return fail("png");
-    } else if (int rc = write_png(o.output, img.data(), o.width, o.height))
-        return rc;
+    if (!dir_of(o.output).empty()) make_dirs(dir_of(o.output));
+    if (form.write(o.output.c_str(), img.data(), o.width, o.height, 6) != PTL_OK) return fail("png");
     for (int which : {PTL_PASS_DEPTH, PTL_PASS_TRIPS})
         if (!grey[which].empty() && ptl_png_write_gray16((stem + (which == PTL_PASS_DEPTH ? ".depth.png" : ".trips.png")).c_str(), grey[which].data(), o.width, o.height, 6) != PTL_OK)
             return fail("png");

@@ -182,6 +182,13 @@ struct HandleFree {
 };
 using ScenePtr = std::unique_ptr<ptl_scene, HandleFree>;
 using RendererPtr = std::unique_ptr<ptl_renderer, HandleFree>;  // (declare it behind its scene: it goes first)
+using DevicePtr = std::unique_ptr<void, HandleFree>;
+
+inline DevicePtr device_alloc(int device, size_t bytes, const char* what) {  // null after "<what>: <error>"
+    void* memory = nullptr;
+    if (ptl_device_alloc(device, bytes, &memory) != PTL_OK) fail(what);
+    return DevicePtr(memory);
+}
 
 inline ScenePtr open_scene(const std::string& path) {  // null: ptl_last_error() says why, the caller says it in its own words
     ptl_scene* scene = nullptr;

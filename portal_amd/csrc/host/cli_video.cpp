@@ -1,36 +1,25 @@
 // cli_video.cpp -- `portal-amd render <scenes> [clips]`, the offline counterpart of the reference's `portal render` (src/main.rs:2757-2874 +
-// render_animation src/main.rs:1758-1873).  What is here: the host side of the clip pipeline (EncoderPool, PinnedFrames, FramePipeline), the
-// forms a clip's frames leave in (FrameOutput: PNG files for ffmpeg, 8-bit or 16-bit from the float sub-frames, or one Y4M stream made from the RGBA8 or from the float sub-frames), what lives as long as a scene's clips (SceneRun)
-// and as long as one clip (ClipRun), the clip loop (render_clip), the workers that compile the next clips' kernels (Prefetcher) and `render`.
-// Argument parsing and every other command are in cli.cpp; what both share is in cli_common.h.
+// render_animation src/main.rs:1758-1873).  What is here: what the clip loop keeps in flight (FramePipeline), the pass images of a clip (PassImages), the
+// forms a clip's frames leave in (FrameOutput: PNG files for ffmpeg in one of the forms of cli_png.h, or one Y4M stream made from the RGBA8 or from the float sub-frames), what lives as long as a scene's clips (SceneRun)
+// and as long as one clip (ClipRun), the sub-frame draws (SubframeDraws), the clip loop (trace_clip, render_clip), the workers that compile the next clips' kernels (Prefetcher) and `render`.
+// Argument parsing and every other command are in cli.cpp; what both share is in cli_common.h and cli_png.h; the encoder pool, the page-locked
+// buffers, child processes and the Y4M stream are in cli_host.h.
 //
 // Video pipeline: for every frame i of a clip, `motion_blur_frames` sub-frames are traced straight into device buffers (aa_start = j,
 // time = subframe_time(i, j)), averaged on the GPU (ptl_average_images), downloaded once, and PNG-encoded on a pool of host threads while
 // the GPU already traces the next frame.  With --frames y4m the averaging kernel is the fused one (ptl_average_to_yuv420p10): what is
 // downloaded is the planar 10-bit frame the encoder consumes (4:2:0, or what --chroma asks for: ptl_average_to_yuv10), and one writer thread streams the frames in order into ffmpeg's stdin
 // (or a .y4m file) while the clip is still rendering: no PNG files, no anim/ directory, no zscale pass.
-// With --clip-passes every frame also gets up to three 16-bit grey pass images (ClipPasses: anim/depth_<i>.png, trips_<i>.png, cut_<i>.png), merged on
+// With --clip-passes every frame also gets up to three 16-bit grey pass images (PassImages: anim/depth_<i>.png, trips_<i>.png, cut_<i>.png), merged on
 // the GPU from the pass records of its sub-frames (ptl_pass_slices_to_gray16), downloaded with the frame and encoded by the same pool.
-#include <dirent.h>
-#include <fcntl.h>
-#include <sys/wait.h>
-#include <unistd.h>
-
 #include <signal.h>
 
 #include <algorithm>
-#include <atomic>
-#include <cerrno>
-#include <condition_variable>
 #include <cstdlib>
-#include <cstring>
-#include <deque>
-#include <functional>
-#include <mutex>
 #include <stop_token>
-#include <thread>
 
-#include "cli_common.h"
+#include "cli_host.h"
+#include "cli_png.h"
 
 namespace {
 
@@ -52,184 +41,8 @@ std::string scene_link(const std::string& path) {  // "dir/name.ron" -> "name"
     return base.size() > 4 && base.substr(base.size() - 4) == ".ron" ? base.substr(0, base.size() - 4) : base;
 }
 
-// Host threads that PNG-encode finished frames while the GPU traces the next ones.
-class EncoderPool {
-public:
-    EncoderPool(int threads, size_t max_pending) : max_pending_(max_pending) {
-        for (int k = 0; k < threads; ++k) workers_.emplace_back([this] { run(); });
-    }
-    ~EncoderPool() { finish(); }
-    void submit(std::function<void()> job) {
-        std::unique_lock<std::mutex> lock(mu_);
-        space_.wait(lock, [&] { return jobs_.size() < max_pending_; });
-        jobs_.push_back(std::move(job));
-        work_.notify_one();
-    }
-    void finish() {
-        {
-            std::unique_lock<std::mutex> lock(mu_);
-            done_ = true;
-        }
-        work_.notify_all();
-        for (auto& t : workers_)
-            if (t.joinable()) t.join();
-    }
-
-private:
-    void run() {
-        for (;;) {
-            std::function<void()> job;
-            {
-                std::unique_lock<std::mutex> lock(mu_);
-                work_.wait(lock, [&] { return done_ || !jobs_.empty(); });
-                if (jobs_.empty()) return;
-                job = std::move(jobs_.front());
-                jobs_.pop_front();
-                space_.notify_one();
-            }
-            job();
-        }
-    }
-    std::mutex mu_;
-    std::condition_variable work_, space_;
-    std::deque<std::function<void()>> jobs_;
-    std::vector<std::thread> workers_;
-    size_t max_pending_;
-    bool done_ = false;
-};
-
-// Page-locked frame buffers recycled between the download and the encoder threads.
-class PinnedFrames {
-public:
-    PinnedFrames(size_t bytes, int count) {
-        for (int k = 0; k < count; ++k) {
-            void* p = nullptr;
-            if (ptl_host_alloc(bytes, &p) != PTL_OK) break;
-            all_.push_back(p);
-            free_.push_back(p);
-        }
-    }
-    ~PinnedFrames() {
-        for (void* p : all_) ptl_host_free(p);
-    }
-    bool ok() const { return !all_.empty(); }
-    uint8_t* take() {
-        std::unique_lock<std::mutex> lock(mu_);
-        cv_.wait(lock, [&] { return !free_.empty(); });
-        void* p = free_.back();
-        free_.pop_back();
-        return static_cast<uint8_t*>(p);
-    }
-    void give(uint8_t* p) {
-        std::unique_lock<std::mutex> lock(mu_);
-        free_.push_back(p);
-        cv_.notify_one();
-    }
-
-private:
-    std::vector<void*> all_, free_;
-    std::mutex mu_;
-    std::condition_variable cv_;
-};
-
 // frames of a clip are intermediates (ffmpeg reads them, then anim/ is removed): fast deflate, 2.3x the encode rate of level 6
 constexpr int kFrameDeflateLevel = 3;
-
-// Start a program without a shell (arguments are passed as they are: no quoting rules to get wrong), as a fresh child process: `stdin_fd` >= 0
-// becomes its stdin, `quiet` sends what it prints to /dev/null.  Its pid, or -1
-pid_t start_program(const std::vector<std::string>& argv, int stdin_fd, bool quiet) {
-    std::vector<char*> args;  // (built before the fork: the child only redirects and executes)
-    for (const std::string& a : argv) args.push_back(const_cast<char*>(a.c_str()));
-    args.push_back(nullptr);
-    pid_t pid = fork();
-    if (pid != 0) return pid;
-    if (stdin_fd >= 0) dup2(stdin_fd, 0);  // (the copy is not close-on-exec)
-    int null_fd = quiet ? open("/dev/null", O_WRONLY) : -1;
-    if (null_fd >= 0) {
-        dup2(null_fd, 1);
-        dup2(null_fd, 2);
-    }
-    execvp(args[0], args.data());
-    _exit(127);
-}
-int wait_program(pid_t pid) {  // its exit status; -1: it did not exit by itself
-    int status = 0;
-    return waitpid(pid, &status, 0) > 0 && WIFEXITED(status) ? WEXITSTATUS(status) : -1;
-}
-int run_program(const std::vector<std::string>& argv, bool quiet) {  // -1 = could not start
-    pid_t pid = start_program(argv, -1, quiet);
-    return pid < 0 ? -1 : wait_program(pid);
-}
-
-// One clip as a Y4M stream (--frames y4m): a file, or the stdin of an encoder started as a fresh child process.  Written by ONE thread
-// in frame order; the first error sticks, later writes do nothing, and the clip loop looks at failed() before every frame -- a dead
-// encoder ends the clip instead of blocking it (SIGPIPE is ignored in this mode: the write returns EPIPE).
-class Y4mStream {
-public:
-    ~Y4mStream() { close(); }
-    bool open_file(const std::string& path) {
-        fd_ = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
-        if (fd_ < 0) fail("cannot write `" + path + "`: " + std::strerror(errno));
-        return fd_ >= 0;
-    }
-    bool open_program(const std::vector<std::string>& argv) {  // our pipe is its stdin
-        int ends[2];
-        if (::pipe2(ends, O_CLOEXEC) != 0) return fail("pipe: " + std::string(std::strerror(errno))), false;
-        started_ = std::chrono::steady_clock::now();
-        child_ = start_program(argv, ends[0], true);  // (the write end is close-on-exec, so the child sees the end of the stream)
-        if (child_ < 0) {
-            ::close(ends[0]);
-            ::close(ends[1]);
-            return fail("fork: " + std::string(std::strerror(errno))), false;
-        }
-        ::close(ends[0]);
-        fd_ = ends[1];
-        return true;
-    }
-    void write(const void* data, size_t n) {
-        const char* p = static_cast<const char*>(data);
-        while (n > 0 && !failed()) {
-            ssize_t done = ::write(fd_, p, n);
-            if (done < 0 && errno == EINTR) continue;
-            if (done < 0) return fail(std::string(child_ > 0 ? "the encoder stopped reading the stream: " : "cannot write the stream: ") + std::strerror(errno));
-            p += done;
-            n -= (size_t)done;
-        }
-    }
-    void fail(const std::string& what) {
-        if (failed()) return;
-        error_ = what;
-        failed_.store(true, std::memory_order_release);
-    }
-    bool failed() const { return failed_.load(std::memory_order_acquire); }
-    const std::string& error() const { return error_; }  // valid once failed()
-    bool to_program() const { return child_ > 0; }
-    double seconds() const { return seconds_since(started_); }
-    // end of stream; for a child its exit status (-1: it did not exit by itself), for a file 0
-    int close() {
-        if (fd_ >= 0 && ::close(fd_) != 0) fail(std::string("cannot write the stream: ") + std::strerror(errno));
-        fd_ = -1;
-        return child_ > 0 ? wait_program(std::exchange(child_, -1)) : 0;
-    }
-
-private:
-    int fd_ = -1;
-    pid_t child_ = -1;
-    std::atomic<bool> failed_{false};
-    std::string error_;
-    std::chrono::steady_clock::time_point started_ = std::chrono::steady_clock::now();
-};
-
-void remove_tree(const std::string& path) {  // rm -rf of a directory we created ourselves (frames only, one level)
-    if (DIR* d = opendir(path.c_str())) {
-        while (dirent* e = readdir(d)) {
-            std::string name = e->d_name;
-            if (name != "." && name != "..") ::unlink((path + "/" + name).c_str());
-        }
-        closedir(d);
-    }
-    ::rmdir(path.c_str());
-}
 
 // the reference's encoder settings (src/main.rs:1843-1857), from -c:v onwards: what follows the input, whichever form the input has.
 // `pix_fmt`: the reference's yuv420p10le, or what --chroma makes of the stream
@@ -282,6 +95,19 @@ struct FramePipeline {
             if (ptl_device_alloc(dev, bytes, &results[k]) != PTL_OK || ptl_event_create(dev, &copied[k]) != PTL_OK) return false;
         return true;
     }
+    // Hand results[k], complete on the tracing stream, to the copy stream and go on tracing: `bytes` of it into `pixels` (page-locked).  The host job
+    // waits for `arrived`, an event of its own to destroy.  0, or 1 after "download: <error>"
+    int hand_off(int k, uint8_t* pixels, size_t bytes, void** arrived) {
+        if (ptl_event_record(produced, nullptr) != PTL_OK || ptl_stream_wait_event(copy_stream, produced) != PTL_OK ||
+            ptl_device_download_async(pixels, results[k], bytes, copy_stream) != PTL_OK || ptl_event_create(device, arrived) != PTL_OK || ptl_event_record(*arrived, copy_stream) != PTL_OK)
+            return fail("download");
+        return 0;
+    }
+    int slot_left(int k) {  // slot k is free once what the copy stream holds now is done: the frame and its pass images have left
+        if (ptl_event_record(copied[k], copy_stream) != PTL_OK) return fail("download");
+        copy_pending[k] = true;
+        return 0;
+    }
     ~FramePipeline() {
         if (copy_stream) ptl_stream_destroy(copy_stream);
         if (produced) ptl_event_destroy(produced);
@@ -292,39 +118,127 @@ struct FramePipeline {
     }
 };
 
-// --clip-passes: which pass images a frame gets, where each lies in the buffers a frame's images travel in, and the files they become.
+// --clip-passes: the pass images of a scene's clips -- which of them a frame gets, the buffers they travel in, the files they become.
 // ptl_pass_slices_to_gray16 writes the images asked for one behind the other as planes of 16-bit rows (each 16-byte aligned) in one sweep.
 // --pass-encoder host: the planes are what leaves the card (one copy) and an encoder thread deflates each (ptl_png_write_gray16).
 // --pass-encoder gpu: every plane goes through ptl_png_deflate_rgb48 as rows of W / 3 RGB pixels -- byte for byte the same rows -- into a result
 // buffer of its own; what leaves the card is each buffer's header and stream, and an encoder thread only frames it (ptl_png_write_stream_gray16).
-struct ClipPasses {
+// On the card: a ring like FramePipeline::results (slot k is free when FramePipeline::copied[k] has happened: the images are copied out in front
+// of that event) and, for the gpu encoder, the sweep's planes.  On the host: page-locked buffers of their own, new for every clip.
+class PassImages {
+public:
     static constexpr int kCount = 3;
-    ClipPasses(const Options& o, int width, int height)
-        : want{o.clip_pass_depth, o.clip_pass_trips, o.clip_pass_cut},
-          gpu(o.pass_gpu),
-          plane_bytes(((size_t)2 * width * height + 15) & ~(size_t)15),
-          device_stride(gpu ? (ptl_png_stream16_bytes(width / 3, height) + 255) & ~(size_t)255 : plane_bytes),
-          download_bytes(gpu ? ptl_png_stream16_download_bytes(width / 3, height) : plane_bytes),
-          host_stride((download_bytes + 15) & ~(size_t)15),
+    PassImages(const Options& o, int width, int height)
+        : on(o.have_clip_passes),
+          device_(o.device),
+          width_(width),
+          height_(height),
+          timing_(o.timing),
+          want_{o.clip_pass_depth, o.clip_pass_trips, o.clip_pass_cut},
+          gpu_(o.pass_gpu),
+          plane_bytes_(((size_t)2 * width * height + 15) & ~(size_t)15),
+          device_stride_(gpu_ ? (ptl_png_stream16_bytes(width / 3, height) + 255) & ~(size_t)255 : plane_bytes_),
+          download_bytes_(gpu_ ? ptl_png_stream16_download_bytes(width / 3, height) : plane_bytes_),
+          host_stride_((download_bytes_ + 15) & ~(size_t)15),
           anim_dir_(o.out_dir + "/anim") {}
-    int count() const { return (int)want[0] + (int)want[1] + (int)want[2]; }
-    size_t index(int p) const { return (size_t)std::count(want, want + p, true); }  // of image p among those asked for
-    size_t planes_bytes() const { return plane_bytes * (size_t)count(); }           // what the sweep writes
-    size_t device_bytes() const { return device_stride * (size_t)count(); }         // a ring slot: the planes, or the result buffers of their deflate
-    size_t host_bytes() const { return host_stride * (size_t)count(); }             // a page-locked buffer
-    static const char* name(int p) { return p == 0 ? "depth" : p == 1 ? "trips" : "cut"; }
-    std::string file(int p, int i) const { return anim_dir_ + "/" + name(p) + "_" + std::to_string(i) + ".png"; }  // (ffmpeg is given anim/frame_%d.png: no collision)
+    const bool on;  // the option was given: nothing below is called without it
+    int allocate() {  // the ring and the planes, once per scene.  0, or 1 after "alloc: <error>"
+        for (DevicePtr& slot : results_)
+            if (!(slot = device_alloc(device_, device_stride_ * (size_t)count(), "alloc"))) return 1;
+        if (gpu_ && !(planes_ = device_alloc(device_, plane_bytes_ * (size_t)count(), "alloc"))) return 1;
+        return 0;
+    }
+    bool open_clip(int in_flight) {  // the page-locked buffers of one clip (the last clip's encoders have finished with theirs)
+        pinned_ = std::make_unique<PinnedFrames>(std::max<size_t>(16, host_stride_ * (size_t)count()), in_flight);
+        return pinned_->ok();
+    }
+    const std::string& anim_dir() const { return anim_dir_; }
     bool have(int i) const {  // every image asked for is there
         for (int p = 0; p < kCount; ++p)
-            if (want[p] && !exists(file(p, i))) return false;
+            if (want_[p] && !exists(file(p, i))) return false;
         return true;
     }
-    const bool want[kCount];
-    const bool gpu;
-    const size_t plane_bytes, device_stride, download_bytes, host_stride;
+    // Behind a frame's last sub-frame on the tracing stream, before the next frame overwrites `records` (ALL `blur` sub-frames of the frame, slice j
+    // where the batched launch puts it): one sweep merges them into the frame's images, in ring slot `slot`.  `gpu_ms`: + theirs, under --timing
+    int make(ptl_renderer* r, const void* records, int blur, int slot, double* gpu_ms) {
+        float lo[16] = {0.0f}, hi[16] = {1.0f}, ms = 0.0f;  // the scene's depth-map bounds, as the last sub-frame's draw uploaded them
+        ptl_renderer_uniform_value(r, width_, height_, "_depth_map_min", lo, nullptr);
+        ptl_renderer_uniform_value(r, width_, height_, "_depth_map_max", hi, nullptr);
+        const long n_px = (long)width_ * height_;
+        char* results = static_cast<char*>(results_[slot].get());
+        char* planes = gpu_ ? static_cast<char*>(planes_.get()) : results;
+        auto plane = [&](int p) -> void* { return want_[p] ? planes + index(p) * plane_bytes_ : nullptr; };
+        if (ptl_pass_slices_to_gray16(device_, records, blur, (unsigned long long)n_px, n_px, plane(0), plane(1), plane(2), lo[0], hi[0], nullptr, timing_ ? &ms : nullptr) != PTL_OK)
+            return fail("pass_slices_to_gray16");
+        *gpu_ms += ms;
+        for (int p = 0; p < kCount && gpu_; ++p) {  // the plane's rows as W / 3 RGB pixels: the same bytes, the filter-type bytes in the same places
+            if (!want_[p]) continue;
+            if (ptl_png_deflate_rgb48(device_, plane(p), width_ / 3, height_, PTL_PNG_CODES_DYNAMIC, results + index(p) * device_stride_, nullptr, timing_ ? &ms : nullptr) != PTL_OK)
+                return fail("png_deflate_rgb48");
+            *gpu_ms += ms;
+        }
+        return 0;
+    }
+    // On the copy stream, behind the frame's own copy and in front of the event that frees the slot.  host: the planes in one copy; gpu: of every
+    // result buffer the header and the room for the stream
+    int copy_out(int slot, void* copy_stream) {
+        pixels_ = pinned_->take();
+        const char* results = static_cast<const char*>(results_[slot].get());
+        for (int k = 0; k < (gpu_ ? count() : 1); ++k)
+            if (ptl_device_download_async(pixels_ + (size_t)k * host_stride_, results + (size_t)k * device_stride_, gpu_ ? download_bytes_ : plane_bytes_ * (size_t)count(), copy_stream) != PTL_OK)
+                return fail("download");
+        if (ptl_event_create(device_, &arrived_) != PTL_OK || ptl_event_record(arrived_, copy_stream) != PTL_OK) return fail("download");
+        return 0;
+    }
+    void submit(int i, EncoderPool& pool) {  // the images copy_out() sent on their way become frame i's files
+        pool.submit([this, i, pixels = pixels_, arrived = arrived_, &pinned = *pinned_] {
+            bool ok = ptl_event_synchronize(arrived) == PTL_OK;
+            for (int p = 0; p < kCount && ok; ++p)
+                if (want_[p]) {
+                    const uint8_t* image = pixels + index(p) * host_stride_;
+                    ok = (gpu_ ? ptl_png_write_stream_gray16(file(p, i).c_str(), image, width_, height_) : ptl_png_write_gray16(file(p, i).c_str(), image, width_, height_, kFrameDeflateLevel)) == PTL_OK;
+                }
+            if (!ok) std::fprintf(stderr, "\n%s\n", ptl_last_error());
+            ptl_event_destroy(arrived);
+            pinned.give(pixels);
+        });
+    }
+    // A clip that is whole: its pass files leave anim/ for `parked` (video/<scene>/<clip>.passes) before the frames are handed on -- anim/ is
+    // removed behind ffmpeg (or parked as <clip>.frames without one), and the next clip must not find this clip's pass files "already there"
+    void park(const std::string& parked, const std::string& clip) const {
+        std::vector<std::string> names;
+        if (DIR* d = opendir(anim_dir_.c_str())) {
+            while (dirent* e = readdir(d)) {
+                const std::string name = e->d_name;
+                for (int p = 0; p < kCount; ++p)
+                    if (name.rfind(std::string(pass_name(p)) + "_", 0) == 0) names.push_back(name);
+            }
+            closedir(d);
+        }
+        if (names.empty()) return;
+        remove_tree(parked);
+        make_dirs(parked);
+        for (const std::string& name : names)
+            if (::rename((anim_dir_ + "/" + name).c_str(), (parked + "/" + name).c_str()) != 0) std::fprintf(stderr, "could not move %s to %s\n", name.c_str(), parked.c_str());
+        std::printf("Pass images of `%s` are in `%s`\n", clip.c_str(), parked.c_str());
+    }
 
 private:
+    int count() const { return (int)want_[0] + (int)want_[1] + (int)want_[2]; }
+    size_t index(int p) const { return (size_t)std::count(want_, want_ + p, true); }  // of image p among those asked for
+    static const char* pass_name(int p) { return p == 0 ? "depth" : p == 1 ? "trips" : "cut"; }
+    std::string file(int p, int i) const { return anim_dir_ + "/" + pass_name(p) + "_" + std::to_string(i) + ".png"; }  // (ffmpeg is given anim/frame_%d.png: no collision)
+    const int device_, width_, height_;
+    const bool timing_;
+    const bool want_[kCount];
+    const bool gpu_;
+    // a plane the sweep writes; a ring slot's share per image (the plane, or the result buffer of its deflate); what of that leaves the card; its share of a page-locked buffer
+    const size_t plane_bytes_, device_stride_, download_bytes_, host_stride_;
     const std::string anim_dir_;
+    DevicePtr results_[FramePipeline::kRing], planes_;
+    std::unique_ptr<PinnedFrames> pinned_;
+    uint8_t* pixels_ = nullptr;  // between copy_out() and submit(): the frame's images on their way, and the event behind their copies
+    void* arrived_ = nullptr;
 };
 
 // One clip of the run
@@ -348,18 +262,14 @@ struct SceneRun {
     size_t download_bytes = 0;                                // what of it leaves the card
     ScenePtr scene;
     RendererPtr r;
-    std::unique_ptr<void, HandleFree> subframe_block;  // ONE allocation, sub-frame j at j * bytes: what the one-launch form writes (slice z behind slice z - 1)
+    DevicePtr subframe_block;  // ONE allocation, sub-frame j at j * bytes: what the one-launch form writes (slice z behind slice z - 1)
     std::vector<void*> subframes;
-    std::unique_ptr<void, HandleFree> float_block;  // --deep-colour and --png-depth 16 only: the same sub-frames as RGBA32F (16 bytes per pixel), one allocation, laid out the same way
+    DevicePtr float_block;  // --deep-colour and --png-depth 16 only: the same sub-frames as RGBA32F (16 bytes per pixel), one allocation, laid out the same way
     std::vector<void*> float_subframes;             // (empty without the option)
     // --depth-report only: the sub-frames' pass records (16 bytes per pixel, laid out the same way), and what a clip accumulates from them on the
     // card: one statistics block and a counter per frame (ptl_pass_stats), downloaded once at the end of the clip
-    std::unique_ptr<void, HandleFree> record_block, pass_stats;
-    // --clip-passes only: the record block is kept for the images as well, and a ring like pipe.results holds each frame's pass images (slot k is
-    // free when pipe.copied[k] has happened: the images are copied out in front of that event)
-    const ClipPasses passes{o, width, height};
-    std::unique_ptr<void, HandleFree> pass_results[FramePipeline::kRing];
-    std::unique_ptr<void, HandleFree> pass_planes;  // --pass-encoder gpu: the sweep's planes, deflated into pass_results[k] on the same stream
+    DevicePtr record_block, pass_stats;
+    PassImages passes{o, width, height};  // --clip-passes only: the record block is kept for the images as well
     FramePipeline pipe;
 };
 
@@ -393,24 +303,33 @@ protected:
     const int fps_;
 };
 
-// anim/frame_<i>.png, encoded in any order by the pool; then ffmpeg reads them (encode_video)
+// anim/frame_<i>.png, encoded in any order by the pool; then ffmpeg reads them (encode_video).  How the sub-frames become a file -- 8 or 16 bits,
+// deflated by an encoder thread or on the card -- is the form's (cli_png.h); names, have(), shards, resume, stills and encode_video are the same
+// for all.  The RGBA8 sub-frames are drawn in every form: the stills come from them, and the classification of --clip-adaptive-aa reads them.
 class PngOutput : public FrameOutput {
 public:
     using FrameOutput::FrameOutput;
-    size_t result_bytes() const override { return run_.frame_bytes; }
+    size_t result_bytes() const override { return form_.result_bytes(run_.width, run_.height); }
+    size_t download_bytes() const override { return form_.download_bytes(run_.width, run_.height); }
     int open() override {
         make_dirs(anim_dir_);
+        const size_t staging_bytes = form_.staging_bytes(run_.width, run_.height, o_.blur);
+        if (staging_bytes != 0 && !(staging_ = device_alloc(o_.device, staging_bytes, "alloc"))) return 1;
         return 0;
     }
     bool have(int i) const override { return exists(frame_name(i)); }
-    bool draws_result() const override { return o_.blur == 1; }  // one image: average_images would hand it back untouched
+    bool wants_float() const override { return form_.wants_float(); }
+    bool draws_result() const override { return form_.draws_result(o_.blur); }
     int make_result(void* result, float* ms) override {
-        return ptl_average_images(o_.device, run_.subframes.data(), o_.blur, result, run_.width, run_.height, nullptr, ms) == PTL_OK ? 0 : fail("average_images");
+        float average_ms = 0.0f, deflate_ms = 0.0f;
+        const int rc = form_.make(o_.device, run_.subframes.data(), run_.float_subframes.data(), o_.blur, staging_.get(), result, run_.width, run_.height, ms ? &average_ms : nullptr,
+                                  ms ? &deflate_ms : nullptr);
+        if (ms) *ms = average_ms + deflate_ms;
+        return rc;
     }
     void submit(int i, uint8_t* pixels, void* arrived, EncoderPool& pool, PinnedFrames& pinned) override {
-        pool.submit([pixels, name = frame_name(i), width = run_.width, height = run_.height, arrived, &pinned] {
-            if (ptl_event_synchronize(arrived) != PTL_OK || ptl_png_write_level(name.c_str(), pixels, width, height, kFrameDeflateLevel) != PTL_OK)
-                std::fprintf(stderr, "\n%s\n", ptl_last_error());
+        pool.submit([form = form_, pixels, name = frame_name(i), width = run_.width, height = run_.height, arrived, &pinned] {
+            if (ptl_event_synchronize(arrived) != PTL_OK || form.write(name.c_str(), pixels, width, height, kFrameDeflateLevel) != PTL_OK) std::fprintf(stderr, "\n%s\n", ptl_last_error());
             ptl_event_destroy(arrived);
             pinned.give(pixels);
         });
@@ -423,107 +342,11 @@ public:
         return 0;
     }
 
-protected:
+private:
     std::string frame_name(int i) const { return anim_dir_ + "/frame_" + std::to_string(i) + ".png"; }
     const std::string anim_dir_ = o_.out_dir + "/anim";
-};
-
-// The same files at 16 bits per channel (--png-depth 16), made from the float sub-frames: the averaged frame of --deep-colour as RGB.  What leaves
-// the card are the file's scanlines, Sub-filtered and in PNG's byte order (ptl_average_f32_to_rgb48): an encoder thread only deflates them.  The
-// RGBA8 sub-frames are still drawn: the stills come from them, and the classification of --clip-adaptive-aa reads them.
-class Png16Output : public PngOutput {
-public:
-    using PngOutput::PngOutput;
-    size_t result_bytes() const override { return ptl_rgb48_frame_bytes(run_.width, run_.height); }
-    bool wants_float() const override { return true; }
-    bool draws_result() const override { return false; }  // (one sub-frame is converted with n = 1)
-    int make_result(void* result, float* ms) override {
-        return ptl_average_f32_to_rgb48(o_.device, run_.float_subframes.data(), o_.blur, result, run_.width, run_.height, PTL_PNG_FILTER_SUB, nullptr, ms) == PTL_OK ? 0 : fail("average_f32_to_rgb48");
-    }
-    void submit(int i, uint8_t* pixels, void* arrived, EncoderPool& pool, PinnedFrames& pinned) override {
-        pool.submit([pixels, name = frame_name(i), width = run_.width, height = run_.height, arrived, &pinned] {
-            if (ptl_event_synchronize(arrived) != PTL_OK || ptl_png_write_rgb48(name.c_str(), pixels, width, height, PTL_PNG_FILTER_SUB, kFrameDeflateLevel) != PTL_OK)
-                std::fprintf(stderr, "\n%s\n", ptl_last_error());
-            ptl_event_destroy(arrived);
-            pinned.give(pixels);
-        });
-    }
-};
-
-// The same 8-bit files with the deflate done on the card (--png-encoder gpu): the frame -- averaged into one device frame where blur > 1, else the
-// single sub-frame -- goes through ptl_png_deflate_rgba8 (or, with --png-codes dynamic, ptl_png_deflate_rgba8_codes), what leaves the card is the
-// result buffer's header and the room for the stream, not the kernels' scratch behind them (a download of exactly the stream's bytes, header
-// first, is a follow-up), and an encoder thread only frames the stream (ptl_png_write_stream).  Names, have(), shards, resume and encode_video are PngOutput's.
-class PngGpuOutput : public PngOutput {
-public:
-    using PngOutput::PngOutput;
-    size_t result_bytes() const override { return ptl_png_stream_bytes(run_.width, run_.height); }
-    size_t download_bytes() const override { return ptl_png_stream_download_bytes(run_.width, run_.height); }
-    bool draws_result() const override { return false; }  // (one sub-frame is deflated where it was drawn)
-    int make_result(void* result, float* ms) override {
-        const void* frame = run_.subframes[0];
-        float average_ms = 0.0f, deflate_ms = 0.0f;
-        if (o_.blur > 1) {
-            if (!averaged_) {
-                void* p = nullptr;
-                if (ptl_device_alloc(o_.device, run_.frame_bytes, &p) != PTL_OK) return fail("alloc");
-                averaged_.reset(p);
-            }
-            if (ptl_average_images(o_.device, run_.subframes.data(), o_.blur, averaged_.get(), run_.width, run_.height, nullptr, ms ? &average_ms : nullptr) != PTL_OK) return fail("average_images");
-            frame = averaged_.get();
-        }
-        if ((o_.png_codes == PTL_PNG_CODES_FIXED ? ptl_png_deflate_rgba8(o_.device, frame, run_.width, run_.height, result, nullptr, ms ? &deflate_ms : nullptr)
-                                                 : ptl_png_deflate_rgba8_codes(o_.device, frame, run_.width, run_.height, o_.png_codes, result, nullptr, ms ? &deflate_ms : nullptr)) != PTL_OK)
-            return fail("png_deflate_rgba8");
-        if (ms) *ms = average_ms + deflate_ms;
-        return 0;
-    }
-    void submit(int i, uint8_t* pixels, void* arrived, EncoderPool& pool, PinnedFrames& pinned) override {
-        pool.submit([pixels, name = frame_name(i), width = run_.width, height = run_.height, arrived, &pinned] {
-            if (ptl_event_synchronize(arrived) != PTL_OK || ptl_png_write_stream(name.c_str(), pixels, width, height) != PTL_OK) std::fprintf(stderr, "\n%s\n", ptl_last_error());
-            ptl_event_destroy(arrived);
-            pinned.give(pixels);
-        });
-    }
-
-private:
-    std::unique_ptr<void, HandleFree> averaged_;  // blur > 1: the averaged RGBA8 frame, on the card
-};
-
-// The 16-bit files with the deflate done on the card (--png-depth 16 --png16-encoder gpu): the float sub-frames are averaged into one device
-// frame of unfiltered 16-bit rows (ptl_average_f32_to_rgb48 with PTL_PNG_FILTER_NONE), those go through ptl_png_deflate_rgb48 (Up filter, matches
-// at pixel distance, a Huffman code per band), what leaves the card is the result buffer's header and the room for the stream, and an encoder
-// thread only frames the stream (ptl_png_write_stream_rgb48).  Names, have(), shards, resume, stills and encode_video are PngOutput's.
-class Png16GpuOutput : public PngOutput {
-public:
-    using PngOutput::PngOutput;
-    size_t result_bytes() const override { return ptl_png_stream16_bytes(run_.width, run_.height); }
-    size_t download_bytes() const override { return ptl_png_stream16_download_bytes(run_.width, run_.height); }
-    bool wants_float() const override { return true; }
-    bool draws_result() const override { return false; }  // (one sub-frame is converted with n = 1)
-    int make_result(void* result, float* ms) override {
-        float rows_ms = 0.0f, deflate_ms = 0.0f;
-        if (!rows_) {
-            void* p = nullptr;
-            if (ptl_device_alloc(o_.device, ptl_rgb48_frame_bytes(run_.width, run_.height), &p) != PTL_OK) return fail("alloc");
-            rows_.reset(p);
-        }
-        if (ptl_average_f32_to_rgb48(o_.device, run_.float_subframes.data(), o_.blur, rows_.get(), run_.width, run_.height, PTL_PNG_FILTER_NONE, nullptr, ms ? &rows_ms : nullptr) != PTL_OK)
-            return fail("average_f32_to_rgb48");
-        if (ptl_png_deflate_rgb48(o_.device, rows_.get(), run_.width, run_.height, PTL_PNG_CODES_DYNAMIC, result, nullptr, ms ? &deflate_ms : nullptr) != PTL_OK) return fail("png_deflate_rgb48");
-        if (ms) *ms = rows_ms + deflate_ms;
-        return 0;
-    }
-    void submit(int i, uint8_t* pixels, void* arrived, EncoderPool& pool, PinnedFrames& pinned) override {
-        pool.submit([pixels, name = frame_name(i), width = run_.width, height = run_.height, arrived, &pinned] {
-            if (ptl_event_synchronize(arrived) != PTL_OK || ptl_png_write_stream_rgb48(name.c_str(), pixels, width, height) != PTL_OK) std::fprintf(stderr, "\n%s\n", ptl_last_error());
-            ptl_event_destroy(arrived);
-            pinned.give(pixels);
-        });
-    }
-
-private:
-    std::unique_ptr<void, HandleFree> rows_;  // the averaged frame as unfiltered 16-bit rows, on the card
+    const PngForm form_{o_};
+    DevicePtr staging_;  // the form's staging buffer on the card (none for the host forms)
 };
 
 // One Y4M stream, written in frame order by a thread of its own.  (A stream is not resumed: it holds every frame, from frame 0.)
@@ -604,19 +427,15 @@ public:
     }
 };
 
-std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, size_t max_pending) {  // the ONE place that knows there are six
+std::unique_ptr<FrameOutput> make_output(const SceneRun& run, const Clip& clip, size_t max_pending) {  // the ONE place that knows there are three
     if (run.o.y4m && run.o.deep_colour) return std::make_unique<DeepY4mOutput>(run, clip, max_pending);
     if (run.o.y4m) return std::make_unique<Y4mOutput>(run, clip, max_pending);
-    if (run.o.png_depth == 16 && run.o.png16_gpu) return std::make_unique<Png16GpuOutput>(run, clip);
-    if (run.o.png_depth == 16) return std::make_unique<Png16Output>(run, clip);
-    if (run.o.png_gpu) return std::make_unique<PngGpuOutput>(run, clip);
     return std::make_unique<PngOutput>(run, clip);
 }
 
 // What lives as long as a clip.  Released in reverse order: the output (its writer finishes, its stream closes), the pool, the page-locked buffers.
 struct ClipRun {
     PinnedFrames pinned;
-    PinnedFrames pass_pinned;  // --clip-passes: a frame's pass images travel in page-locked buffers of their own (none without the option)
     EncoderPool pool;
     std::unique_ptr<FrameOutput> out;
 };
@@ -642,27 +461,76 @@ int write_still(const SceneRun& run, ClipRun& c, const void* device_frame, const
     return 0;
 }
 
-// render_animation (src/main.rs:1758-1873): every frame of the clip traced, made and handed to the output
-int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
-    const Options& o = run.o;
-    ptl_renderer* r = run.r.get();
-    FramePipeline& pipe = run.pipe;
-    FrameOutput& out = *c.out;
-    auto started = std::chrono::steady_clock::now();
-    int rejits_before = ptl_renderer_rejit_count(r);
-    if (o.skip_existing && exists(out.video_base + ".mov")) {
-        std::printf("Skip `%s/%s`, because it's already exists\n", run.name.c_str(), clip.name.c_str());
-        return 0;
-    }
-    make_dirs(dir_of(out.video_base));
-    if (int rc = out.open()) return rc;
-    int count = std::max(1, (int)((float)clip.duration * (float)clip.fps));  // ((duration_seconds * fps as f32) as usize).max(1)
-    double gpu_ms = 0.0;
-    long traced = 0, drawn_frames = 0;
+// The sub-frame draws of one clip: "draw sub-frame j of frame i" in the form the options ask for -- staged and launched once per frame, adaptive,
+// with pass records, or plain -- what --depth-report and --clip-adaptive-aa --timing account behind every launch, and their lines at the end.
+struct SubframeDraws {
+    SubframeDraws(SceneRun& run, const Clip& clip, int count, bool with_float)
+        : run(run), o(run.o), r(run.r.get()), seconds((double)(float)clip.duration), clip_name(clip.name), count(count), with_float(with_float) {}
+    SceneRun& run;
+    const Options& o;
+    ptl_renderer* const r;
+    const double seconds;  // the clip's duration
+    const std::string& clip_name;
+    const int count;  // the clip's frames
+    const bool with_float, batched = batch_subframes(o), with_records = clip_records(o);
+    const size_t frame_records = ptl_pass_record_bytes(run.width, run.height);
+    ptl_frame frame{run.width, run.height, 0, 1, 0};
+    long traced = 0;
     // --clip-adaptive-aa under --timing: refined entries of all sub-frames, and the three passes' GPU ms summed (each frame is synchronised anyway)
     unsigned long long refined = 0;
     double pass_ms[3] = {0.0, 0.0, 0.0};
-    auto account_adaptive = [&](bool slices, int n) {
+    DevicePtr per_launch;  // --depth-report: the stats kernel runs behind every launch into the clip's block; per_launch[i] collects frame i's exhausted paths
+
+    int open() {
+        if (o.clip_adaptive) ptl_renderer_set_option(r, "adaptive_aa_threshold", o.clip_adaptive_t);
+        if (!o.depth_report) return 0;
+        if (!(per_launch = device_alloc(o.device, sizeof(uint64_t) * (size_t)count, "alloc"))) return 1;
+        if (ptl_device_memset(per_launch.get(), 0, sizeof(uint64_t) * (size_t)count, nullptr) != PTL_OK || ptl_device_memset(run.pass_stats.get(), 0, sizeof(ptl_pass_stats_block), nullptr) != PTL_OK)
+            return fail("memset");
+        return 0;
+    }
+    // The host step of sub-frame j of frame i: the camera is stateful, so a frame that is not drawn takes it as well
+    int update(int i, int j) { return ptl_renderer_update(r, subframe_time(i, j, count, o.blur) * seconds, nullptr, nullptr) == PTL_OK ? 0 : fail("update"); }
+    // Sub-frame j of frame i into `target` (an unbatched draw) or into slice j of run.subframes; the float and record slices beside it
+    int draw(int i, int j, void* target, float* ms) {
+        ptl_renderer_set_option(r, "aa_start", j);
+        if (int rc = update(i, j)) return rc;
+        void* target_f32 = with_float ? run.float_subframes[j] : nullptr;  // out_rgba32f of the draw
+        void* block_f32 = with_float ? run.float_subframes[0] : nullptr;   // ... of a batched one: slice z behind slice z - 1
+        float* timed = o.timing ? ms : nullptr;
+        if (batched) {
+            // everything a draw does short of launching; the launch follows behind the last sub-frame, once for all of them
+            if (ptl_renderer_stage_slice(r, &frame, j) != PTL_OK) return fail("stage");
+            const unsigned long long slice_pixels = (unsigned long long)run.width * run.height;
+            if (j == o.blur - 1) {
+                if ((o.clip_adaptive ? ptl_renderer_draw_slices_adaptive(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, timed)
+                     : with_records  ? ptl_renderer_draw_slices_passes(r, &frame, o.blur, run.subframes[0], block_f32, run.record_block.get(), frame_records * (size_t)o.blur, slice_pixels, nullptr, timed)
+                                     : ptl_renderer_draw_slices(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, timed)) != PTL_OK)
+                    return fail("render");
+                if (o.depth_report)
+                    if (int rc = account_passes(i, run.record_block.get(), o.blur)) return rc;
+                if (o.clip_adaptive && o.timing)
+                    if (int rc = account_adaptive(true, o.blur)) return rc;
+            }
+        } else if (o.clip_adaptive) {  // (blur 1, blur > 16, --batch-subframes 0: the single-frame adaptive draw per sub-frame)
+            if (ptl_renderer_draw_adaptive(r, &frame, target, target_f32, nullptr, timed) != PTL_OK) return fail("render");
+            if (o.timing)
+                if (int rc = account_adaptive(false, 1)) return rc;
+        } else if (with_records) {  // (the unbatched sub-frame with its records, and the stats kernel behind it)
+            // --clip-passes: the block keeps ALL sub-frames of a frame (an unbatched sub-frame j draws its records at slice j, where the batched launch
+            // puts them), and one sweep behind the frame's last sub-frame merges them into the frame's pass images (PassImages::make)
+            void* records = static_cast<char*>(run.record_block.get()) + (run.passes.on ? (size_t)j * frame_records : 0);
+            if (ptl_renderer_draw_passes(r, &frame, target, target_f32, records, frame_records, nullptr, nullptr, timed) != PTL_OK) return fail("render");
+            if (o.depth_report)
+                if (int rc = account_passes(i, records, 1)) return rc;
+        } else if (ptl_renderer_draw(r, &frame, target, target_f32, nullptr, nullptr, timed) != PTL_OK) {
+            // (without --timing the launch is not waited for: the host evaluates the next sub-frame's uniforms while this one traces)
+            return fail("render");
+        }
+        ++traced;
+        return 0;
+    }
+    int account_adaptive(bool slices, int n) {
         unsigned int counts[16] = {};
         void* dev_counts = nullptr;
         if ((slices ? ptl_renderer_adaptive_slices_result(r, nullptr, nullptr, &dev_counts) : ptl_renderer_adaptive_result(r, nullptr, &dev_counts)) != PTL_OK ||
@@ -673,39 +541,61 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
         ptl_renderer_adaptive_times(r, ms3);
         for (int p = 0; p < 3; ++p) pass_ms[p] += ms3[p];
         return 0;
-    };
-    if (o.clip_adaptive) ptl_renderer_set_option(r, "adaptive_aa_threshold", o.clip_adaptive_t);
-    ptl_frame frame{run.width, run.height, 0, 1, 0};
-    int last = o.max_frames >= 0 ? std::min(count, o.max_frames) : count;
-    // --depth-report: the stats kernel runs behind every launch into the clip's block; per_launch[i] collects frame i's exhausted paths
-    const size_t frame_records = ptl_pass_record_bytes(run.width, run.height);
-    std::unique_ptr<void, HandleFree> per_launch;
-    if (o.depth_report) {
-        void* counters = nullptr;
-        if (ptl_device_alloc(o.device, sizeof(uint64_t) * (size_t)count, &counters) != PTL_OK) return fail("alloc");
-        per_launch.reset(counters);
-        if (ptl_device_memset(counters, 0, sizeof(uint64_t) * (size_t)count, nullptr) != PTL_OK || ptl_device_memset(run.pass_stats.get(), 0, sizeof(ptl_pass_stats_block), nullptr) != PTL_OK)
-            return fail("memset");
     }
-    auto account_passes = [&](int i, const void* records, int n) {  // the records of the launch that just went out: n sub-frames of frame i, one behind the other
+    int account_passes(int i, const void* records, int n) {  // the records of the launch that just went out: n sub-frames of frame i, one behind the other
         return ptl_pass_stats(o.device, records, (long)n * run.width * run.height, run.pass_stats.get(), per_launch.get(), i, nullptr, nullptr) == PTL_OK ? 0 : fail("pass_stats");
-    };
-    // --clip-passes: the block keeps ALL sub-frames of a frame (an unbatched sub-frame j draws its records at slice j, where the batched launch
-    // puts them), and one sweep behind the frame's last sub-frame merges them into the frame's pass images
-    const ClipPasses& passes = run.passes;
-    const bool with_records = clip_records(o), with_passes = o.have_clip_passes;
-    const long n_px = (long)run.width * run.height;
-    if (with_passes) make_dirs(o.out_dir + "/anim");  // (a Y4M clip has no other use for it)
-    const bool batched = batch_subframes(o), direct = out.draws_result(), with_float = out.wants_float();
+    }
+    int report() {  // at the end of the clip
+        if (o.depth_report) {  // one download, one line: the clip's block, and the frame whose launches cut most paths
+            ptl_pass_stats_block stats{};
+            std::vector<uint64_t> cut((size_t)count, 0);
+            if (ptl_device_download(&stats, run.pass_stats.get(), sizeof stats, nullptr) != PTL_OK || ptl_device_download(cut.data(), per_launch.get(), sizeof(uint64_t) * cut.size(), nullptr) != PTL_OK)
+                return fail("download");
+            const size_t worst = (size_t)(std::max_element(cut.begin(), cut.end()) - cut.begin());
+            print_depth_report(stats, render_depth_of(r, run.width, run.height),
+                               "; `" + clip_name + "`: " + std::to_string(traced) + " sub-frames, worst frame " + std::to_string(worst) + " (" + std::to_string(cut[worst]) + " paths cut)");
+        }
+        if (o.clip_adaptive && o.timing) {
+            const unsigned long long pixels = (unsigned long long)traced * (unsigned long long)run.width * (unsigned long long)run.height;
+            std::printf("adaptive aa: threshold %d, %llu of %llu pixels refined (%.2f %%); GPU ms: one-sample pass %.3f, classification %.3f, refine pass %.3f\n", o.clip_adaptive_t,
+                        refined, pixels, pixels ? 100.0 * (double)refined / (double)pixels : 0.0, pass_ms[0], pass_ms[1], pass_ms[2]);
+        }
+        return 0;
+    }
+};
+
+// render_animation (src/main.rs:1758-1873): every frame of the clip traced, made and handed to the output
+int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
+    const Options& o = run.o;
+    ptl_renderer* r = run.r.get();
+    FramePipeline& pipe = run.pipe;
+    FrameOutput& out = *c.out;
+    PassImages& passes = run.passes;
+    auto started = std::chrono::steady_clock::now();
+    int rejits_before = ptl_renderer_rejit_count(r);
+    if (o.skip_existing && exists(out.video_base + ".mov")) {
+        std::printf("Skip `%s/%s`, because it's already exists\n", run.name.c_str(), clip.name.c_str());
+        return 0;
+    }
+    make_dirs(dir_of(out.video_base));
+    if (int rc = out.open()) return rc;
+    int count = std::max(1, (int)((float)clip.duration * (float)clip.fps));  // ((duration_seconds * fps as f32) as usize).max(1)
+    int last = o.max_frames >= 0 ? std::min(count, o.max_frames) : count;
+    double gpu_ms = 0.0;
+    long drawn_frames = 0;
+    SubframeDraws draws(run, clip, count, out.wants_float());
+    if (int rc = draws.open()) return rc;
+    if (passes.on) make_dirs(passes.anim_dir());  // (a Y4M clip has no other use for it)
+    const bool direct = out.draws_result();
     for (int i = 0; i < last; ++i) {
         if (int rc = out.check()) return rc;
-        if (i % o.shards != o.shard || (out.have(i) && (!with_passes || passes.have(i)))) {  // (a frame with a pass file missing is drawn again, all its files rewritten)
+        if (i % o.shards != o.shard || (out.have(i) && (!passes.on || passes.have(i)))) {  // (a frame with a pass file missing is drawn again, all its files rewritten)
             // Not ours (shard K of N takes every N-th frame) or already on disk.  The camera is stateful -- where it is relative
             // to the portals depends on the path it took (teleport_camera) -- so the host step still runs for every sub-frame:
             // a shard, or a resumed run, then sees exactly the cameras of an uninterrupted run.  (The reference skips the
             // update as well, src/main.rs:1789-1792, and so renders a resumed clip from a different camera history.)
             for (int j = 0; j < o.blur; ++j)
-                if (ptl_renderer_update(r, subframe_time(i, j, count, o.blur) * (double)(float)clip.duration, nullptr, nullptr) != PTL_OK) return fail("update");
+                if (int rc = draws.update(i, j)) return rc;
             continue;
         }
         int slot = (int)(drawn_frames++ % FramePipeline::kRing);
@@ -714,46 +604,14 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
         // frames and NO gain here -- 1080p monoportal 0.0519 ms per sub-frame with one instance, 0.0522 with two, 0.0559 with four; 720p 0.031 -> 0.039;
         // 4K aa 4 0.884 -> 0.885 / 0.908: the cross-stream event waits cost what the overlapped tails save (profiles/r04/concurrent_draws.jsonl)
         for (int j = 0; j < o.blur; ++j) {
-            ptl_renderer_set_option(r, "aa_start", j);
-            if (ptl_renderer_update(r, subframe_time(i, j, count, o.blur) * (double)(float)clip.duration, nullptr, nullptr) != PTL_OK) return fail("update");
             void* target = direct ? pipe.results[slot] : run.subframes[j];
-            void* target_f32 = with_float ? run.float_subframes[j] : nullptr;  // out_rgba32f of the draw
-            void* block_f32 = with_float ? run.float_subframes[0] : nullptr;   // ... of a batched one: slice z behind slice z - 1
             float ms = 0.0f;
-            if (batched) {
-                // everything a draw does short of launching; the launch follows behind the last sub-frame, once for all of them
-                if (ptl_renderer_stage_slice(r, &frame, j) != PTL_OK) return fail("stage");
-                const unsigned long long slice_pixels = (unsigned long long)run.width * run.height;
-                if (j == o.blur - 1) {
-                    if ((o.clip_adaptive  ? ptl_renderer_draw_slices_adaptive(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, o.timing ? &ms : nullptr)
-                         : with_records   ? ptl_renderer_draw_slices_passes(r, &frame, o.blur, run.subframes[0], block_f32, run.record_block.get(), frame_records * (size_t)o.blur, slice_pixels,
-                                                                            nullptr, o.timing ? &ms : nullptr)
-                                          : ptl_renderer_draw_slices(r, &frame, o.blur, run.subframes[0], block_f32, slice_pixels, nullptr, o.timing ? &ms : nullptr)) != PTL_OK)
-                        return fail("render");
-                    if (o.depth_report)
-                        if (int rc = account_passes(i, run.record_block.get(), o.blur)) return rc;
-                    if (o.clip_adaptive && o.timing)
-                        if (int rc = account_adaptive(true, o.blur)) return rc;
-                }
-            } else if (o.clip_adaptive) {  // (blur 1, blur > 16, --batch-subframes 0: the single-frame adaptive draw per sub-frame)
-                if (ptl_renderer_draw_adaptive(r, &frame, target, target_f32, nullptr, o.timing ? &ms : nullptr) != PTL_OK) return fail("render");
-                if (o.timing)
-                    if (int rc = account_adaptive(false, 1)) return rc;
-            } else if (with_records) {  // (the unbatched sub-frame with its records, and the stats kernel behind it)
-                void* records = static_cast<char*>(run.record_block.get()) + (with_passes ? (size_t)j * frame_records : 0);
-                if (ptl_renderer_draw_passes(r, &frame, target, target_f32, records, frame_records, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) return fail("render");
-                if (o.depth_report)
-                    if (int rc = account_passes(i, records, 1)) return rc;
-            } else if (ptl_renderer_draw(r, &frame, target, target_f32, nullptr, nullptr, o.timing ? &ms : nullptr) != PTL_OK) {
-                // (without --timing the launch is not waited for: the host evaluates the next sub-frame's uniforms while this one traces)
-                return fail("render");
-            }
+            if (int rc = draws.draw(i, j, target, &ms)) return rc;
             gpu_ms += ms;
-            ++traced;
             // the clip's stills: sub-frame 0 of the first frame (read behind the launch, which a batched frame has behind its last sub-frame), the
             // last of the last.  The download is on the default stream, like the draws
-            if (i == 0 && j == (batched ? o.blur - 1 : 0))
-                if (int rc = write_still(run, c, batched ? run.subframes[0] : target, out.video_base + ".start.png")) return rc;
+            if (i == 0 && j == (draws.batched ? o.blur - 1 : 0))
+                if (int rc = write_still(run, c, draws.batched ? run.subframes[0] : target, out.video_base + ".start.png")) return rc;
             if (i == count - 1 && j == o.blur - 1)
                 if (int rc = write_still(run, c, target, out.video_base + ".end.png")) return rc;
         }
@@ -762,101 +620,26 @@ int trace_clip(SceneRun& run, ClipRun& c, const Clip& clip) {
             if (int rc = out.make_result(pipe.results[slot], o.timing ? &ms : nullptr)) return rc;
             gpu_ms += ms;
         }
-        if (with_passes) {  // behind the last sub-frame on the tracing stream: before the next frame overwrites the block
-            float lo[16] = {0.0f}, hi[16] = {1.0f}, ms = 0.0f;  // the scene's depth-map bounds, as the last sub-frame's draw uploaded them
-            ptl_renderer_uniform_value(r, run.width, run.height, "_depth_map_min", lo, nullptr);
-            ptl_renderer_uniform_value(r, run.width, run.height, "_depth_map_max", hi, nullptr);
-            char* results = static_cast<char*>(run.pass_results[slot].get());
-            char* planes = passes.gpu ? static_cast<char*>(run.pass_planes.get()) : results;
-            auto plane = [&](int p) -> void* { return passes.want[p] ? planes + passes.index(p) * passes.plane_bytes : nullptr; };
-            if (ptl_pass_slices_to_gray16(o.device, run.record_block.get(), o.blur, (unsigned long long)n_px, n_px, plane(0), plane(1), plane(2), lo[0], hi[0], nullptr,
-                                          o.timing ? &ms : nullptr) != PTL_OK)
-                return fail("pass_slices_to_gray16");
-            gpu_ms += ms;
-            for (int p = 0; p < ClipPasses::kCount && passes.gpu; ++p) {  // the plane's rows as W / 3 RGB pixels: the same bytes, the filter-type bytes in the same places
-                if (!passes.want[p]) continue;
-                if (ptl_png_deflate_rgb48(o.device, plane(p), run.width / 3, run.height, PTL_PNG_CODES_DYNAMIC, results + passes.index(p) * passes.device_stride, nullptr,
-                                          o.timing ? &ms : nullptr) != PTL_OK)
-                    return fail("png_deflate_rgb48");
-                gpu_ms += ms;
-            }
-        }
+        if (passes.on)
+            if (int rc = passes.make(r, run.record_block.get(), o.blur, slot, &gpu_ms)) return rc;
         // hand the finished frame to the copy stream and go on tracing; the host job waits for its own event
         uint8_t* pixels = c.pinned.take();  // blocks while every buffer is still being encoded
-        uint8_t* pass_pixels = with_passes ? c.pass_pinned.take() : nullptr;
-        void *arrived = nullptr, *passes_arrived = nullptr;
-        if (ptl_event_record(pipe.produced, nullptr) != PTL_OK || ptl_stream_wait_event(pipe.copy_stream, pipe.produced) != PTL_OK ||
-            ptl_device_download_async(pixels, pipe.results[slot], run.download_bytes, pipe.copy_stream) != PTL_OK || ptl_event_create(pipe.device, &arrived) != PTL_OK ||
-            ptl_event_record(arrived, pipe.copy_stream) != PTL_OK)
-            return fail("download");
-        if (with_passes) {  // host: the planes in one copy; gpu: of every result buffer the header and the room for the stream
-            const char* results = static_cast<const char*>(run.pass_results[slot].get());
-            for (int k = 0; k < (passes.gpu ? passes.count() : 1); ++k)
-                if (ptl_device_download_async(pass_pixels + (size_t)k * passes.host_stride, results + (size_t)k * passes.device_stride, passes.gpu ? passes.download_bytes : passes.planes_bytes(),
-                                              pipe.copy_stream) != PTL_OK)
-                    return fail("download");
-            if (ptl_event_create(pipe.device, &passes_arrived) != PTL_OK || ptl_event_record(passes_arrived, pipe.copy_stream) != PTL_OK) return fail("download");
-        }
-        if (ptl_event_record(pipe.copied[slot], pipe.copy_stream) != PTL_OK) return fail("download");  // slot is free: the frame and its pass images have left
-        pipe.copy_pending[slot] = true;
+        void* arrived = nullptr;
+        if (int rc = pipe.hand_off(slot, pixels, run.download_bytes, &arrived)) return rc;
+        if (passes.on)
+            if (int rc = passes.copy_out(slot, pipe.copy_stream)) return rc;
+        if (int rc = pipe.slot_left(slot)) return rc;
         out.submit(i, pixels, arrived, c.pool, c.pinned);
-        if (with_passes)
-            c.pool.submit([pass_pixels, passes_arrived, i, &passes, width = run.width, height = run.height, &pinned = c.pass_pinned] {
-                bool ok = ptl_event_synchronize(passes_arrived) == PTL_OK;
-                for (int p = 0; p < ClipPasses::kCount && ok; ++p)
-                    if (passes.want[p]) {
-                        const uint8_t* image = pass_pixels + passes.index(p) * passes.host_stride;
-                        ok = (passes.gpu ? ptl_png_write_stream_gray16(passes.file(p, i).c_str(), image, width, height)
-                                         : ptl_png_write_gray16(passes.file(p, i).c_str(), image, width, height, kFrameDeflateLevel)) == PTL_OK;
-                    }
-                if (!ok) std::fprintf(stderr, "\n%s\n", ptl_last_error());
-                ptl_event_destroy(passes_arrived);
-                pinned.give(pass_pixels);
-            });
+        if (passes.on) passes.submit(i, c.pool);
         std::printf("\r%d/%d done      ", i, count);
         std::fflush(stdout);
     }
     std::printf("\n");
     char gpu_time[96] = "";
-    if (o.timing) std::snprintf(gpu_time, sizeof gpu_time, ", GPU %.1f ms (%.3f ms each),", gpu_ms, traced ? gpu_ms / traced : 0.0);
-    std::printf("Traced `%s/%s`: %ld sub-frames %dx%d%s submitted after %.2f s, kernel rebuilt %d times\n", run.name.c_str(), clip.name.c_str(), traced, run.width,
+    if (o.timing) std::snprintf(gpu_time, sizeof gpu_time, ", GPU %.1f ms (%.3f ms each),", gpu_ms, draws.traced ? gpu_ms / draws.traced : 0.0);
+    std::printf("Traced `%s/%s`: %ld sub-frames %dx%d%s submitted after %.2f s, kernel rebuilt %d times\n", run.name.c_str(), clip.name.c_str(), draws.traced, run.width,
                 run.height, gpu_time, seconds_since(started), ptl_renderer_rejit_count(r) - rejits_before);
-    if (o.depth_report) {  // one download, one line: the clip's block, and the frame whose launches cut most paths
-        ptl_pass_stats_block stats{};
-        std::vector<uint64_t> cut((size_t)count, 0);
-        if (ptl_device_download(&stats, run.pass_stats.get(), sizeof stats, nullptr) != PTL_OK || ptl_device_download(cut.data(), per_launch.get(), sizeof(uint64_t) * cut.size(), nullptr) != PTL_OK)
-            return fail("download");
-        const size_t worst = (size_t)(std::max_element(cut.begin(), cut.end()) - cut.begin());
-        print_depth_report(stats, render_depth_of(r, run.width, run.height),
-                           "; `" + clip.name + "`: " + std::to_string(traced) + " sub-frames, worst frame " + std::to_string(worst) + " (" + std::to_string(cut[worst]) + " paths cut)");
-    }
-    if (o.clip_adaptive && o.timing) {
-        const unsigned long long pixels = (unsigned long long)traced * (unsigned long long)run.width * (unsigned long long)run.height;
-        std::printf("adaptive aa: threshold %d, %llu of %llu pixels refined (%.2f %%); GPU ms: one-sample pass %.3f, classification %.3f, refine pass %.3f\n", o.clip_adaptive_t,
-                    refined, pixels, pixels ? 100.0 * (double)refined / (double)pixels : 0.0, pass_ms[0], pass_ms[1], pass_ms[2]);
-    }
-    return 0;
-}
-
-// --clip-passes, a clip that is whole: its pass files leave anim/ for video/<scene>/<clip>.passes/ before the frames are handed on -- anim/ is
-// removed behind ffmpeg (or parked as <clip>.frames without one), and the next clip must not find this clip's pass files "already there"
-void park_pass_files(const SceneRun& run, const Clip& clip) {
-    const std::string anim = run.o.out_dir + "/anim", parked = run.o.out_dir + "/video/" + run.name + "/" + clip.name + ".passes";
-    std::vector<std::string> names;
-    if (DIR* d = opendir(anim.c_str())) {
-        while (dirent* e = readdir(d)) {
-            const std::string name = e->d_name;
-            for (int p = 0; p < ClipPasses::kCount; ++p)
-                if (name.rfind(std::string(ClipPasses::name(p)) + "_", 0) == 0) names.push_back(name);
-        }
-        closedir(d);
-    }
-    if (names.empty()) return;
-    remove_tree(parked);
-    make_dirs(parked);
-    for (const std::string& name : names)
-        if (::rename((anim + "/" + name).c_str(), (parked + "/" + name).c_str()) != 0) std::fprintf(stderr, "could not move %s to %s\n", name.c_str(), parked.c_str());
-    std::printf("Pass images of `%s` are in `%s`\n", clip.name.c_str(), parked.c_str());
+    return draws.report();
 }
 
 // One clip: its buffers, pools and output for as long as it takes, released on every way out
@@ -864,13 +647,12 @@ int render_clip(SceneRun& run, const Clip& clip) {
     auto clip_start = std::chrono::steady_clock::now();
     // frames in flight between download and encode: one per encoder thread, but no more than ~2 GB of page-locked memory
     int in_flight = (int)std::max<size_t>(4, std::min<size_t>((size_t)run.threads + 2, ((size_t)2 << 30) / run.download_bytes));
-    const bool with_passes = run.o.have_clip_passes;
-    ClipRun c{{run.download_bytes, in_flight}, {std::max<size_t>(16, run.passes.host_bytes()), with_passes ? in_flight : 0}, {run.threads, (size_t)run.threads * 2}, make_output(run, clip, (size_t)in_flight)};
-    if (!c.pinned.ok() || (with_passes && !c.pass_pinned.ok())) return fail("pinned host memory");
+    ClipRun c{{run.download_bytes, in_flight}, {run.threads, (size_t)run.threads * 2}, make_output(run, clip, (size_t)in_flight)};
+    if (!c.pinned.ok() || (run.passes.on && !run.passes.open_clip(in_flight))) return fail("pinned host memory");
     const int rc = trace_clip(run, c, clip);
-    if (with_passes && rc == 0 && run.o.shards == 1 && run.o.max_frames < 0) {
+    if (run.passes.on && rc == 0 && run.o.shards == 1 && run.o.max_frames < 0) {
         c.pool.finish();  // every pass file is on disk
-        park_pass_files(run, clip);
+        run.passes.park(c.out->video_base + ".passes", clip.name);
     }
     return c.out->close(rc, c.pool, clip_start);
 }
@@ -994,38 +776,18 @@ int render_scene(const Options& o, const std::string& path) {
     const std::unique_ptr<FrameOutput> form = make_output(run, Clip{}, 1);  // (an output that is never opened)
     run.result_bytes = form->result_bytes();
     run.download_bytes = form->download_bytes();
-    void* block = nullptr;
-    run.subframes.assign((size_t)std::max(1, o.blur), nullptr);
-    if (ptl_device_alloc(o.device, run.frame_bytes * run.subframes.size(), &block) != PTL_OK) return fail("alloc");
-    run.subframe_block.reset(block);
-    for (size_t j = 0; j < run.subframes.size(); ++j) run.subframes[j] = static_cast<char*>(block) + j * run.frame_bytes;
-    if (form->wants_float()) {
-        const size_t float_bytes = run.frame_bytes * 4;  // RGBA32F
-        void* floats = nullptr;
-        if (ptl_device_alloc(o.device, float_bytes * run.subframes.size(), &floats) != PTL_OK) return fail("alloc");
-        run.float_block.reset(floats);
-        for (size_t j = 0; j < run.subframes.size(); ++j) run.float_subframes.push_back(static_cast<char*>(floats) + j * float_bytes);
+    // one block per kind, sub-frame j at j * its bytes: RGBA8, RGBA32F where the form wants floats (16 bytes per pixel), the pass records
+    const size_t slices = (size_t)std::max(1, o.blur), float_bytes = run.frame_bytes * 4;
+    if (!(run.subframe_block = device_alloc(o.device, run.frame_bytes * slices, "alloc"))) return 1;
+    if (form->wants_float() && !(run.float_block = device_alloc(o.device, float_bytes * slices, "alloc"))) return 1;
+    for (size_t j = 0; j < slices; ++j) {
+        run.subframes.push_back(static_cast<char*>(run.subframe_block.get()) + j * run.frame_bytes);
+        if (run.float_block) run.float_subframes.push_back(static_cast<char*>(run.float_block.get()) + j * float_bytes);
     }
-    if (clip_records(o)) {
-        void* records = nullptr;
-        if (ptl_device_alloc(o.device, ptl_pass_record_bytes(run.width, run.height) * run.subframes.size(), &records) != PTL_OK) return fail("alloc");
-        run.record_block.reset(records);
-    }
-    if (o.depth_report) {
-        void* stats = nullptr;
-        if (ptl_device_alloc(o.device, sizeof(ptl_pass_stats_block), &stats) != PTL_OK) return fail("alloc");
-        run.pass_stats.reset(stats);
-    }
-    for (int k = 0; k < FramePipeline::kRing && o.have_clip_passes; ++k) {
-        void* images = nullptr;
-        if (ptl_device_alloc(o.device, run.passes.device_bytes(), &images) != PTL_OK) return fail("alloc");
-        run.pass_results[k].reset(images);
-    }
-    if (o.have_clip_passes && o.pass_gpu) {
-        void* planes = nullptr;
-        if (ptl_device_alloc(o.device, run.passes.planes_bytes(), &planes) != PTL_OK) return fail("alloc");
-        run.pass_planes.reset(planes);
-    }
+    if (clip_records(o) && !(run.record_block = device_alloc(o.device, ptl_pass_record_bytes(run.width, run.height) * slices, "alloc"))) return 1;
+    if (o.depth_report && !(run.pass_stats = device_alloc(o.device, sizeof(ptl_pass_stats_block), "alloc"))) return 1;
+    if (run.passes.on)
+        if (int rc = run.passes.allocate()) return rc;
     if (!run.pipe.create(o.device, run.result_bytes)) return fail("pipeline");
     Prefetcher prefetch;
     prefetch.start(o, path, todo);

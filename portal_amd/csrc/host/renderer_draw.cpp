@@ -143,12 +143,13 @@ extern "C" int ptl_renderer_stage_slice(ptl_renderer* r, const ptl_frame* frame,
     });
 }
 
-extern "C" int ptl_renderer_draw_slices(ptl_renderer* r, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
-                                        void* stream, float* elapsed_ms) {
-    if (!r || !frame || n < 1 || n > 16) return PTL_ERR_INVALID;
+// A batch of staged slices: one launch per run of slices staged with the same kernel, on the caller's stream.  `out_passes`: the slices' pass
+// records (slice z at out_passes + z * slice_pixels records, `passes_bytes` in all), or null for the launch without them.  `entry`: who says so
+static int draw_staged_slices(const char* entry, ptl_renderer* r, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, void* out_passes, size_t passes_bytes,
+                              unsigned long long slice_pixels, void* stream, float* elapsed_ms) {
     return guarded([&] {
         if (!r->slices.all_staged(n)) {
-            set_last_error("ptl_renderer_draw_slices: slices 0 .. n-1 are not all staged (ptl_renderer_stage_slice) since the last launch");
+            set_last_error(std::string(entry) + ": slices 0 .. n-1 are not all staged (ptl_renderer_stage_slice) since the last launch");
             return (int)PTL_ERR_INVALID;
         }
         if (int jrc = r->lanes.join(stream); jrc != PTL_OK) return jrc;
@@ -158,7 +159,12 @@ extern "C" int ptl_renderer_draw_slices(ptl_renderer* r, const ptl_frame* frame,
             float ms = 0.0f;
             void* out8 = out_rgba8 ? static_cast<unsigned char*>(out_rgba8) + (size_t)j0 * slice_pixels * 4 : nullptr;
             void* out32 = out_rgba32f ? static_cast<float*>(out_rgba32f) + (size_t)j0 * slice_pixels * 4 : nullptr;
-            if (rc == PTL_OK) rc = ptl_kernel_render_slices(k, frame, j1 - j0, out8, out32, slice_pixels, stream, elapsed_ms ? &ms : nullptr);
+            if (rc == PTL_OK && !out_passes) rc = ptl_kernel_render_slices(k, frame, j1 - j0, out8, out32, slice_pixels, stream, elapsed_ms ? &ms : nullptr);
+            if (rc == PTL_OK && out_passes) {
+                void* outp = static_cast<ptl_pass_record*>(out_passes) + (size_t)j0 * slice_pixels;
+                const size_t left = passes_bytes - sizeof(ptl_pass_record) * (size_t)j0 * slice_pixels;
+                rc = ptl_kernel_render_slices_passes(k, frame, j1 - j0, out8, out32, outp, left, slice_pixels, stream, elapsed_ms ? &ms : nullptr);
+            }
             total_ms += ms;
             return rc;
         });
@@ -168,33 +174,18 @@ extern "C" int ptl_renderer_draw_slices(ptl_renderer* r, const ptl_frame* frame,
     });
 }
 
+extern "C" int ptl_renderer_draw_slices(ptl_renderer* r, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, unsigned long long slice_pixels,
+                                        void* stream, float* elapsed_ms) {
+    if (!r || !frame || n < 1 || n > 16) return PTL_ERR_INVALID;
+    return draw_staged_slices("ptl_renderer_draw_slices", r, frame, n, out_rgba8, out_rgba32f, nullptr, 0, slice_pixels, stream, elapsed_ms);
+}
+
 // The same batch with the slices' pass records (renderers with PTL_FLAG_PASSES / option "passes"): slice z at out_passes + z * slice_pixels records.
 extern "C" int ptl_renderer_draw_slices_passes(ptl_renderer* r, const ptl_frame* frame, int n, void* out_rgba8, void* out_rgba32f, void* out_passes, size_t passes_bytes,
                                                unsigned long long slice_pixels, void* stream, float* elapsed_ms) {
     if (!r || !frame || n < 1 || n > 16) return PTL_ERR_INVALID;
     if (!out_passes || passes_bytes < sizeof(ptl_pass_record) * (unsigned long long)(n - 1) * slice_pixels) return PTL_ERR_INVALID;  // (layer 1 checks the last run's share)
-    return guarded([&] {
-        if (!r->slices.all_staged(n)) {
-            set_last_error("ptl_renderer_draw_slices_passes: slices 0 .. n-1 are not all staged (ptl_renderer_stage_slice) since the last launch");
-            return (int)PTL_ERR_INVALID;
-        }
-        if (int jrc = r->lanes.join(stream); jrc != PTL_OK) return jrc;
-        float total_ms = 0.0f;
-        const int rc = r->slices.for_each_run(n, [&](ptl_kernel* k, int j0, int j1) {
-            int rc = r->slices.stage_run(k, j0, j1);
-            float ms = 0.0f;
-            void* out8 = out_rgba8 ? static_cast<unsigned char*>(out_rgba8) + (size_t)j0 * slice_pixels * 4 : nullptr;
-            void* out32 = out_rgba32f ? static_cast<float*>(out_rgba32f) + (size_t)j0 * slice_pixels * 4 : nullptr;
-            void* outp = static_cast<ptl_pass_record*>(out_passes) + (size_t)j0 * slice_pixels;
-            const size_t left = passes_bytes - sizeof(ptl_pass_record) * (size_t)j0 * slice_pixels;
-            if (rc == PTL_OK) rc = ptl_kernel_render_slices_passes(k, frame, j1 - j0, out8, out32, outp, left, slice_pixels, stream, elapsed_ms ? &ms : nullptr);
-            total_ms += ms;
-            return rc;
-        });
-        if (elapsed_ms) *elapsed_ms = total_ms;
-        r->slices.drop();
-        return rc;
-    });
+    return draw_staged_slices("ptl_renderer_draw_slices_passes", r, frame, n, out_rgba8, out_rgba32f, out_passes, passes_bytes, slice_pixels, stream, elapsed_ms);
 }
 
 extern "C" int ptl_renderer_join(ptl_renderer* r, void* stream) {

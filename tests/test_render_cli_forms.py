@@ -168,3 +168,65 @@ def test_resumed_run_equals_an_uninterrupted_one(gpu, tmp_path, default_png, ext
         assert got[name] == data and os.stat(frames / name).st_mtime_ns == mtime, name
     for name in got:
         assert got[name] == default_png[name], name
+
+
+# ---- a frame form and the pass images in the same clip: two rings on the card freed by one event, two kinds of job in one pool ----
+WP = 66  # (the GPU pass encoder takes a row as W / 3 RGB pixels)
+FORMS = {"png": [], "png-gpu-dynamic": ["--png-encoder", "gpu", "--png-codes", "dynamic"], "png16-gpu": ["--png-depth", "16", "--png16-encoder", "gpu"], "y4m": ["--frames", "y4m"]}
+PASSES = ["--clip-passes", "depth,trips,cut"]
+PASS_NAMES = sorted(f"{name}_{i}.png" for name in ("depth", "trips", "cut") for i in range(6))
+
+
+def _form_files(out_dir, extra):
+    """What the frame form of a whole clip leaves behind, as bytes: the parked frames or the stream, and both stills."""
+    if "y4m" not in extra:
+        return _clip_files(out_dir, CLIP, 6)
+    video = out_dir / "video" / "basics"
+    return {name: (video / f"{CLIP}.{name}").read_bytes() for name in ("y4m", "start.png", "end.png")}
+
+
+def _parked_passes(out_dir):
+    parked = out_dir / "video" / "basics" / f"{CLIP}.passes"
+    assert sorted(os.listdir(parked)) == PASS_NAMES
+    return parked
+
+
+@pytest.fixture(scope="module")
+def png_with_passes(gpu, tmp_path_factory):
+    """The form without an option beside the GPU-encoded pass images: (its files, the folder of its pass files)."""
+    out_dir = tmp_path_factory.mktemp("png_with_passes")
+    _render(gpu, out_dir, CLIP, BLURRED + PASSES + ["--pass-encoder", "gpu"], width=WP)
+    return _form_files(out_dir, []), _parked_passes(out_dir)
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_frame_forms_and_pass_images_leave_each_other_alone(gpu, tmp_path, png_with_passes, form):
+    """Every frame form with `--clip-passes depth,trips,cut --pass-encoder gpu` (for the GPU forms: two deflates per frame on one stream):
+    the frames or the stream and both stills are byte for byte those of the form alone, and the pass files are byte for byte those written
+    beside the form without an option."""
+    extra = FORMS[form]
+    _render(gpu, tmp_path / "alone", CLIP, BLURRED + extra, width=WP)
+    alone = _form_files(tmp_path / "alone", extra)
+    both, parked = png_with_passes
+    if extra:
+        _render(gpu, tmp_path / "both", CLIP, BLURRED + extra + PASSES + ["--pass-encoder", "gpu"], width=WP)
+        both, parked = _form_files(tmp_path / "both", extra), _parked_passes(tmp_path / "both")
+    assert sorted(both) == sorted(alone)
+    for name in alone:
+        assert both[name] == alone[name], (form, name)
+    for name in PASS_NAMES:
+        assert (parked / name).read_bytes() == (png_with_passes[1] / name).read_bytes(), (form, name)
+
+
+def test_host_and_gpu_pass_encoders_write_the_same_samples_beside_the_frames(gpu, tmp_path, png_with_passes):
+    from tests import pass_reference as ref
+    from tests import pass_slices_reference as sref
+
+    _render(gpu, tmp_path, CLIP, BLURRED + PASSES + ["--pass-encoder", "host"], width=WP)
+    assert _form_files(tmp_path, []) == png_with_passes[0]
+    host, shown = _parked_passes(tmp_path), set()
+    for name in PASS_NAMES:
+        want, made = ref.read_png_gray16(str(host / name)), sref.read_png_gray16_up(str(png_with_passes[1] / name))
+        assert want.shape == (H, WP) and np.array_equal(want, made), name
+        shown.add(len(np.unique(want)) > 2)
+    assert True in shown
