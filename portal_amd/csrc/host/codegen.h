@@ -247,11 +247,7 @@ bool matrix_breaks_short_chains(const float m[16]);
 bool matrix_is_affine(const float m[16]);
 // (matrix_keeps_rays_affine -- that, or NaN in every element -- is declared in internal.h: layer 1 asks it too)
 inline bool pattern_is_affine(MatrixPattern p) { return (p & ((1ull << 3) | (1ull << 7) | (1ull << 11))) == 0 && ((p >> (16 + 15)) & 1ull) != 0; }
-// Do the scene's GLSL snippets keep rays affine?  True unless one of them builds a Ray from parts that are not spelled `vec4(.., 1.)` /
-// `vec4(.., 0.)`, assigns a ray's `.o` / `.d` in another than a whitelisted form, calls transform() with a matrix that is not a scene uniform
-// (`X_mat`, `X_mat_inv`, `A_to_B_mat_teleport`: the ones whose values are checked), or has an out / inout parameter of type Ray or vec4
-// (KernelOptions::affine_rays; conservative: a refusal only costs the optimisation).  `why` receives the offending text.
-bool snippets_keep_rays_affine(const std::vector<std::string>& codes, std::string* why);
+// (snippets_keep_rays_affine -- what the scene's GLSL may do to a ray -- is declared in glsl_translate.h, with the other snippet passes)
 
 // All scene-derived uniforms: X_mat, X_mat_inv, A_to_B_mat_teleport, user uniforms.
 // `errors` receives the reference's "matrix `x` can't be getted" style messages.

@@ -7,51 +7,12 @@
 #include "glsl_translate.h"
 
 namespace ptl {
-namespace {
-
-struct Sig {  // the significant tokens of a snippet (no white space, comments, directives)
-    std::vector<Token>& toks;
-    std::vector<size_t> at;
-    explicit Sig(std::vector<Token>& t) : toks(t) {
-        for (size_t k = 0; k < t.size(); ++k)
-            if (t[k].kind != Token::Space && t[k].kind != Token::Comment && t[k].kind != Token::Preproc) at.push_back(k);
-    }
-    size_t n() const { return at.size(); }
-    const Token& operator[](size_t i) const { return toks[at[i]]; }
-    bool is(size_t i, const char* text) const { return i < n() && (*this)[i].kind == Token::Punct && (*this)[i].text == text; }
-    bool ident(size_t i, const std::string& text) const { return i < n() && (*this)[i].kind == Token::Ident && (*this)[i].text == text; }
-    bool any_ident(size_t i) const { return i < n() && (*this)[i].kind == Token::Ident; }
-    size_t close_of(size_t open) const {  // matching bracket of the one at `open`, or n()
-        const std::string o = (*this)[open].text, c = o == "(" ? ")" : (o == "{" ? "}" : "]");
-        int depth = 0;
-        for (size_t i = open; i < n(); ++i) {
-            if (is(i, o.c_str())) ++depth;
-            else if (is(i, c.c_str()) && --depth == 0) return i;
-        }
-        return n();
-    }
-    // does the token sequence starting at i spell `words` (identifiers and punctuation alternately, as given)?
-    bool spells(size_t i, std::initializer_list<const char*> words) const {
-        for (const char* w : words) {
-            if (i >= n() || (*this)[i].text != w) return false;
-            ++i;
-        }
-        return true;
-    }
-};
-
-bool is_assignment_op(const Token& t) {
-    if (t.kind != Token::Punct) return false;
-    return t.text == "=" || t.text == "+=" || t.text == "-=" || t.text == "*=" || t.text == "/=" || t.text == "++" || t.text == "--";
-}
-
-}  // namespace
 
 // See glsl_translate.h.  Every condition is checked on the token stream; anything not recognised leaves the snippet as written.
 std::string bound_nearer_blocks(const std::string& glsl_body, const std::set<std::string>& functions_with_out_params, int* bounded) {
     if (bounded) *bounded = 0;
     std::vector<Token> toks = tokenize_glsl(glsl_body);
-    Sig s(toks);
+    const TokenView s(toks);  // (the stream is only read: the one rewrite is applied while the text is put together)
     const size_t n = s.n();
     // (1) the accumulator: exactly one `SceneIntersectionWithMaterial R = ...;`, at brace depth 0, and the body ends in `return R;`
     std::string R;
@@ -61,7 +22,7 @@ std::string bound_nearer_blocks(const std::string& glsl_body, const std::set<std
         for (size_t i = 0; i < n; ++i) {
             if (s.is(i, "{")) ++depth;
             else if (s.is(i, "}")) --depth;
-            else if (s.ident(i, "SceneIntersectionWithMaterial") && s.any_ident(i + 1) && (s.is(i + 2, "=") || s.is(i + 2, ";"))) {
+            else if (s.ident(i, "SceneIntersectionWithMaterial") && s.ident(i + 1) && (s.is(i + 2, "=") || s.is(i + 2, ";"))) {
                 if (!R.empty() || depth != 0) return glsl_body;  // a second accumulator, or one that lives in a block
                 R = s[i + 1].text;
                 decl = i + 1;
@@ -77,7 +38,7 @@ std::string bound_nearer_blocks(const std::string& glsl_body, const std::set<std
     std::vector<Block> blocks;
     for (size_t i = 0; i + 12 < n; ++i) {
         if (!(s.ident(i, "if") && s.is(i + 1, "(") && s.ident(i + 2, "nearer") && s.is(i + 3, "(") && s.ident(i + 4, R))) continue;
-        if (!(s.is(i + 5, ".") && s.ident(i + 6, "scene") && s.is(i + 7, ".") && s.ident(i + 8, "hit") && s.is(i + 9, ",") && s.any_ident(i + 10) && s.is(i + 11, ")") && s.is(i + 12, ")")))
+        if (!(s.is(i + 5, ".") && s.ident(i + 6, "scene") && s.is(i + 7, ".") && s.ident(i + 8, "hit") && s.is(i + 9, ",") && s.ident(i + 10) && s.is(i + 11, ")") && s.is(i + 12, ")")))
             return glsl_body;  // R inside a nearer() of another shape
         const size_t open = i + 13;
         if (!s.is(open, "{")) return glsl_body;
@@ -136,37 +97,32 @@ std::string bound_nearer_blocks(const std::string& glsl_body, const std::set<std
     for (const Block& b : blocks) {
         std::set<std::string> locals;
         for (size_t i = b.open + 1; i + 1 < b.close; ++i)  // `type name =` / `type name;` at the start of a statement
-            if (s.any_ident(i) && s.any_ident(i + 1) && (s.is(i + 2, "=") || s.is(i + 2, ";")) && (s.is(i - 1, ";") || s.is(i - 1, "{") || s.is(i - 1, "}") || s.is(i - 1, ")")) && s[i].text != "return")
+            if (s.ident(i) && s.ident(i + 1) && (s.is(i + 2, "=") || s.is(i + 2, ";")) && (s.is(i - 1, ";") || s.is(i - 1, "{") || s.is(i - 1, "}") || s.is(i - 1, ")")) && s[i].text != "return")
                 locals.insert(s[i + 1].text);
         for (size_t i = b.open + 1; i < b.close; ++i) {
             if (!is_assignment_op(s[i])) continue;
             // the target: `++x` names it behind the operator, everything else in front -- walk back over `.member` and `[index]` to the base name
-            const bool prefix = (s.is(i, "++") || s.is(i, "--")) && !(i > 0 && (s.any_ident(i - 1) || s.is(i - 1, "]")));
+            const bool prefix = (s.is(i, "++") || s.is(i, "--")) && !(i > 0 && (s.ident(i - 1) || s.is(i - 1, "]")));
             size_t t = prefix ? i + 1 : i - 1;
             while (!prefix && t > 0) {
                 if (s.is(t, "]")) {
-                    int depth = 0;
-                    while (t > 0) {
-                        if (s.is(t, "]")) ++depth;
-                        else if (s.is(t, "[") && --depth == 0) break;
-                        --t;
-                    }
-                    if (t == 0) return glsl_body;
-                    --t;
-                } else if (s.any_ident(t) && t >= 2 && s.is(t - 1, ".")) {
+                    const size_t open = s.open_of(t);
+                    if (open == n || open == 0) return glsl_body;  // unbalanced, or nothing in front of the index
+                    t = open - 1;
+                } else if (s.ident(t) && t >= 2 && s.is(t - 1, ".")) {
                     t -= 2;
                 } else {
                     break;
                 }
             }
-            if (!s.any_ident(t)) return glsl_body;
+            if (!s.ident(t)) return glsl_body;
             const std::string& base = s[t].text;
             if (base == b.H) return glsl_body;
             if (base != R && !locals.count(base)) return glsl_body;
         }
         // ... nor through an `out` / `inout` argument: no function that has such parameters is called in a block
         for (size_t i = b.open + 1; i + 1 < b.close; ++i)
-            if (s.any_ident(i) && s.is(i + 1, "(") && functions_with_out_params.count(s[i].text)) return glsl_body;
+            if (s.ident(i) && s.is(i + 1, "(") && functions_with_out_params.count(s[i].text)) return glsl_body;
         // ... nor through control flow: a block that leaves a loop or the function (`break`, `continue`, `return`, `discard`) changes which LATER
         // candidates are reached at all, so skipping it could let a candidate through that the code as written never saw
         for (size_t i = b.open + 1; i < b.close; ++i)
@@ -206,7 +162,7 @@ std::string bound_nearer_blocks(const std::string& glsl_body, const std::set<std
 
     // (6) the rewrite: `nearer(R.scene.hit, H)` -> `nearer(R.scene.hit, H) && !(H.t > ptl_far)` (inserted in front of the condition's `)`)
     std::vector<std::pair<size_t, std::string>> inserts;  // raw token index -> text in front of it
-    for (const Block& b : blocks) inserts.push_back({s.at[b.cond_close], " && !(" + b.H + ".t > ptl_far)"});
+    for (const Block& b : blocks) inserts.push_back({s.raw(b.cond_close), " && !(" + b.H + ".t > ptl_far)"});
     std::string out;
     size_t next = 0;
     for (size_t k = 0; k < toks.size(); ++k) {

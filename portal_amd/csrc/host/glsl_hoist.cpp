@@ -2,7 +2,6 @@
 #include "glsl_hoist.h"
 
 #include <algorithm>
-#include <cstring>
 
 #include "glsl_tokens.h"
 
@@ -35,21 +34,6 @@ bool type_name(const std::string& t) {
     static const std::set<std::string> names = {"float", "int", "uint", "bool", "vec2", "vec3", "vec4", "ivec2", "ivec3", "ivec4", "uvec2", "uvec3",
                                                 "uvec4", "bvec2", "bvec3", "bvec4", "mat2", "mat3", "mat4"};
     return names.count(t) != 0;
-}
-bool swizzle(const std::string& s) {
-    if (s.empty() || s.size() > 4) return false;
-    for (const char* set : {"xyzw", "rgba", "stpq"}) {
-        bool all = true;
-        for (char c : s) all = all && std::strchr(set, c) != nullptr;
-        if (all) return true;
-    }
-    return false;
-}
-bool float_literal(const std::string& t) {
-    if (t.size() > 1 && t[0] == '0' && (t[1] == 'x' || t[1] == 'X')) return false;
-    for (char c : t)
-        if (c == '.' || c == 'e' || c == 'E' || c == 'f' || c == 'F') return true;
-    return false;
 }
 
 // GLSL built-ins (and the two pure helpers of the reference's library every scene uses) with the rule that types their result
@@ -105,42 +89,38 @@ struct PrologueItem {
 
 class Hoister {
   public:
-    Hoister(const std::string& glsl, const HoistParams& params, int& next_member) : P(params), next_member_(next_member) {
-        toks_ = tokenize_glsl(glsl);
-        for (size_t k = 0; k < toks_.size(); ++k)
-            if (toks_[k].kind != Token::Space && toks_[k].kind != Token::Comment) sig_.push_back(k);
-        n_ = sig_.size();
-    }
+    Hoister(const std::string& glsl, const HoistParams& params, int& next_member)
+        : P(params), next_member_(next_member), toks_(tokenize_glsl(glsl)), s_(toks_, TokenView::kLayout) {}
 
     HoistResult run(const std::string& original) {
         HoistResult out;
         out.glsl = original;
-        for (size_t i = 0; i < n_; ++i)
-            if (T(i).kind == Token::Preproc || T(i).kind == Token::Raw) return out;  // macros: the text is not what the compiler will see
+        for (size_t i = 0; i < s_.n(); ++i)
+            if (s_[i].kind == Token::Preproc || s_[i].kind == Token::Raw) return out;  // macros: the text is not what the compiler will see
         struct Fn {
             size_t body_b, body_e;
             std::vector<std::string> params;
         };
         std::vector<Fn> fns;
         if (P.body_only) {
-            fns.push_back({0, n_, P.body_params});
+            fns.push_back({0, s_.n(), P.body_params});
         } else {
             int depth = 0;
-            for (size_t i = 0; i < n_; ++i) {
-                if (is(i, "{")) ++depth;
-                else if (is(i, "}")) --depth;
-                else if (depth == 0 && ident(i) && i + 2 < n_ && ident(i + 1) && is(i + 2, "(") && T(i).text != "return") {
-                    size_t close = match(i + 2, "(", ")");
-                    if (close >= n_ || !is(close + 1, "{")) continue;
-                    size_t end = match(close + 1, "{", "}");
-                    if (end >= n_) continue;
+            for (size_t i = 0; i < s_.n(); ++i) {
+                if (s_.is(i, "{")) ++depth;
+                else if (s_.is(i, "}")) --depth;
+                else if (depth == 0 && s_.ident(i) && i + 2 < s_.n() && s_.ident(i + 1) && s_.is(i + 2, "(") && s_[i].text != "return") {
+                    size_t close = s_.close_of(i + 2);
+                    if (close >= s_.n() || !s_.is(close + 1, "{")) continue;
+                    size_t end = s_.close_of(close + 1);
+                    if (end >= s_.n()) continue;
                     Fn f{close + 2, end, {}};
-                    size_t last_ident = n_;
+                    size_t last_ident = s_.n();
                     for (size_t j = i + 3; j <= close; ++j) {
-                        if (ident(j)) last_ident = j;
-                        if ((is(j, ",") || j == close) && last_ident < n_) {
-                            f.params.push_back(T(last_ident).text);
-                            last_ident = n_;
+                        if (s_.ident(j)) last_ident = j;
+                        if ((s_.is(j, ",") || j == close) && last_ident < s_.n()) {
+                            f.params.push_back(s_[last_ident].text);
+                            last_ident = s_.n();
                         }
                     }
                     fns.push_back(f);
@@ -170,9 +150,8 @@ class Hoister {
   private:
     const HoistParams& P;
     int& next_member_;
-    std::vector<Token> toks_;
-    std::vector<size_t> sig_;
-    size_t n_ = 0;
+    const std::vector<Token> toks_;
+    const TokenView s_;  // keeps directives: run() leaves a text that has one as it is.  The stream is never changed (rebuild() writes a new text).
     std::vector<Node> nodes_;
     std::vector<Replacement> replacements_;
     std::vector<HoistedMember> members_;
@@ -194,30 +173,6 @@ class Hoister {
     std::map<std::string, size_t> hlocals_;   // Ray locals with a uniform origin, written once: name -> index of the declared name
     std::map<std::string, Carried> hcarried_;  // ... and those a canonical loop advances by `V = transform(U, ... V ...)`
 
-    const Token& T(size_t i) const { return toks_[sig_[i]]; }
-    bool is(size_t i, const char* text) const { return i < n_ && T(i).kind == Token::Punct && T(i).text == text; }
-    bool ident(size_t i) const { return i < n_ && T(i).kind == Token::Ident; }
-    bool ident(size_t i, const char* text) const { return ident(i) && T(i).text == text; }
-    size_t match(size_t open, const char* a, const char* b) const {
-        int depth = 0;
-        for (size_t i = open; i < n_; ++i) {
-            if (is(i, a)) ++depth;
-            else if (is(i, b) && --depth == 0) return i;
-        }
-        return n_;
-    }
-    std::string text_of(size_t b, size_t e) const {  // source text of significant tokens [b, e), on one line
-        std::string s;
-        if (b >= e) return s;
-        for (size_t k = sig_[b]; k <= sig_[e - 1]; ++k) {
-            const Token& t = toks_[k];
-            if (t.kind == Token::Comment) s += ' ';
-            else if (t.kind == Token::Space) s += ' ';
-            else s += t.text;
-        }
-        return s;
-    }
-
     // ---- expressions ---------------------------------------------------------------------------------------------------------
     int add(Node nd) {
         nodes_.push_back(std::move(nd));
@@ -232,8 +187,8 @@ class Hoister {
     }
     int parse_expr(size_t& pos, size_t end, int min_prec) {
         int lhs = parse_unary(pos, end);
-        while (pos < end && T(pos).kind == Token::Punct) {
-            const std::string op = T(pos).text;
+        while (pos < end && s_[pos].kind == Token::Punct) {
+            const std::string op = s_[pos].text;
             const int prec = precedence(op);
             if (prec == 0 || prec < min_prec) break;
             ++pos;
@@ -242,7 +197,7 @@ class Hoister {
             nd.text = op;
             if (op == "?") {
                 int mid = parse_expr(pos, end, 1);
-                if (!is(pos, ":")) throw ParseError{};
+                if (!s_.is(pos, ":")) throw ParseError{};
                 ++pos;
                 int rhs = parse_expr(pos, end, 2);
                 nd.kind = Node::Ternary;
@@ -263,8 +218,8 @@ class Hoister {
     }
     int parse_unary(size_t& pos, size_t end) {
         if (pos >= end) throw ParseError{};
-        if (T(pos).kind == Token::Punct) {
-            const std::string op = T(pos).text;
+        if (s_[pos].kind == Token::Punct) {
+            const std::string op = s_[pos].text;
             if (op == "-" || op == "+" || op == "!" || op == "~" || op == "++" || op == "--") {
                 Node nd;
                 nd.kind = Node::Unary;
@@ -283,22 +238,22 @@ class Hoister {
         while (pos < end) {
             Node nd;
             nd.b = nodes_[cur].b;
-            if (is(pos, ".")) {
-                if (!ident(pos + 1) || is(pos + 2, "(")) throw ParseError{};  // (a method call: .length())
+            if (s_.is(pos, ".")) {
+                if (!s_.ident(pos + 1) || s_.is(pos + 2, "(")) throw ParseError{};  // (a method call: .length())
                 nd.kind = Node::Member;
-                nd.text = T(pos + 1).text;
+                nd.text = s_[pos + 1].text;
                 nd.kids = {cur};
                 pos += 2;
-            } else if (is(pos, "[")) {
+            } else if (s_.is(pos, "[")) {
                 ++pos;
                 int idx = parse_expr(pos, end, 1);
-                if (!is(pos, "]")) throw ParseError{};
+                if (!s_.is(pos, "]")) throw ParseError{};
                 ++pos;
                 nd.kind = Node::Index;
                 nd.kids = {cur, idx};
-            } else if (is(pos, "++") || is(pos, "--")) {
+            } else if (s_.is(pos, "++") || s_.is(pos, "--")) {
                 nd.kind = Node::Post;
-                nd.text = T(pos).text;
+                nd.text = s_[pos].text;
                 nd.kids = {cur};
                 ++pos;
             } else {
@@ -313,7 +268,7 @@ class Hoister {
         if (pos >= end) throw ParseError{};
         Node nd;
         nd.b = pos;
-        const Token& t = T(pos);
+        const Token& t = s_[pos];
         if (t.kind == Token::Number) {
             nd.kind = Node::Lit;
             nd.text = t.text;
@@ -322,19 +277,19 @@ class Hoister {
         }
         if (t.kind == Token::Ident) {
             nd.text = t.text;
-            if (is(pos + 1, "(")) {
+            if (s_.is(pos + 1, "(")) {
                 nd.kind = Node::Call;
                 pos += 2;
-                if (is(pos, ")")) {
+                if (s_.is(pos, ")")) {
                     ++pos;
                 } else {
                     for (;;) {
                         nd.kids.push_back(parse_expr(pos, end, 1));
-                        if (is(pos, ",")) {
+                        if (s_.is(pos, ",")) {
                             ++pos;
                             continue;
                         }
-                        if (!is(pos, ")")) throw ParseError{};
+                        if (!s_.is(pos, ")")) throw ParseError{};
                         ++pos;
                         break;
                     }
@@ -346,11 +301,11 @@ class Hoister {
             nd.e = ++pos;
             return add(nd);
         }
-        if (is(pos, "(")) {
+        if (s_.is(pos, "(")) {
             ++pos;
             nd.kind = Node::Paren;
             nd.kids = {parse_expr(pos, end, 1)};
-            if (!is(pos, ")")) throw ParseError{};
+            if (!s_.is(pos, ")")) throw ParseError{};
             nd.e = ++pos;
             return add(nd);
         }
@@ -368,16 +323,16 @@ class Hoister {
     size_t statement_end(size_t pos, size_t end) const {  // the `;` that ends the statement starting at pos (brackets balanced)
         int depth = 0;
         for (size_t i = pos; i < end; ++i) {
-            if (is(i, "(") || is(i, "[")) ++depth;
-            else if (is(i, ")") || is(i, "]")) --depth;
-            else if (is(i, "{") || is(i, "}")) throw ParseError{};
-            else if (is(i, ";") && depth == 0) return i;
+            if (s_.is(i, "(") || s_.is(i, "[")) ++depth;
+            else if (s_.is(i, ")") || s_.is(i, "]")) --depth;
+            else if (s_.is(i, "{") || s_.is(i, "}")) throw ParseError{};
+            else if (s_.is(i, ";") && depth == 0) return i;
         }
         throw ParseError{};
     }
     void controlled(size_t& pos, size_t end, int depth, int loop) {  // the statement an if / else / for / while governs
-        if (is(pos, "{")) {
-            size_t close = match(pos, "{", "}");
+        if (s_.is(pos, "{")) {
+            size_t close = s_.close_of(pos);
             if (close >= end) throw ParseError{};
             block(pos + 1, close, depth + 1, loop);
             pos = close + 1;
@@ -390,26 +345,26 @@ class Hoister {
     }
     void declaration_or_expression(size_t& pos, size_t end, int depth, int loop, bool header) {
         size_t p = pos;
-        while (ident(p, "const") || ident(p, "highp") || ident(p, "mediump") || ident(p, "lowp")) ++p;
-        const bool declares = ident(p) && ident(p + 1) && (is(p + 2, "=") || is(p + 2, ";") || is(p + 2, ",") || is(p + 2, "["));
+        while (s_.ident(p, "const") || s_.ident(p, "highp") || s_.ident(p, "mediump") || s_.ident(p, "lowp")) ++p;
+        const bool declares = s_.ident(p) && s_.ident(p + 1) && (s_.is(p + 2, "=") || s_.is(p + 2, ";") || s_.is(p + 2, ",") || s_.is(p + 2, "["));
         const size_t semi = statement_end(pos, end);
         if (declares) {
-            const std::string type = T(p).text;
+            const std::string type = s_[p].text;
             size_t q = p + 1;
             for (;;) {
-                if (!ident(q)) throw ParseError{};
+                if (!s_.ident(q)) throw ParseError{};
                 Site s;
                 s.depth = depth;
                 s.loop = loop;
                 s.header = header;
                 s.decl_type = type;
-                s.decl_name = T(q).text;
+                s.decl_name = s_[q].text;
                 s.name_at = q;
                 declared_.insert(s.decl_name);
                 ++writes_[s.decl_name];
                 ++q;
-                if (is(q, "[")) throw ParseError{};  // arrays: not handled
-                if (is(q, "=")) {
+                if (s_.is(q, "[")) throw ParseError{};  // arrays: not handled
+                if (s_.is(q, "=")) {
                     ++q;
                     s.kind = Site::DeclInit;
                     s.root = parse_expr(q, semi, 1);
@@ -417,7 +372,7 @@ class Hoister {
                     s.kind = Site::Decl;
                 }
                 sites_.push_back(s);
-                if (is(q, ",")) {
+                if (s_.is(q, ",")) {
                     ++q;
                     continue;
                 }
@@ -437,20 +392,20 @@ class Hoister {
         pos = semi + 1;
     }
     void statement(size_t& pos, size_t end, int depth, int loop) {
-        if (is(pos, ";")) {
+        if (s_.is(pos, ";")) {
             ++pos;
             return;
         }
-        if (is(pos, "{")) {
-            size_t close = match(pos, "{", "}");
+        if (s_.is(pos, "{")) {
+            size_t close = s_.close_of(pos);
             if (close >= end) throw ParseError{};
             block(pos + 1, close, depth + 1, loop);
             pos = close + 1;
             return;
         }
-        if (ident(pos, "if")) {
-            if (!is(pos + 1, "(")) throw ParseError{};
-            size_t close = match(pos + 1, "(", ")");
+        if (s_.ident(pos, "if")) {
+            if (!s_.is(pos + 1, "(")) throw ParseError{};
+            size_t close = s_.close_of(pos + 1);
             if (close >= end) throw ParseError{};
             Site s;
             s.depth = depth;
@@ -459,16 +414,16 @@ class Hoister {
             sites_.push_back(s);
             pos = close + 1;
             controlled(pos, end, depth, loop);
-            if (ident(pos, "else")) {
+            if (s_.ident(pos, "else")) {
                 ++pos;
                 controlled(pos, end, depth, loop);
             }
             return;
         }
-        if (ident(pos, "for") || ident(pos, "while")) {
-            const bool is_for = T(pos).text == "for";
-            if (!is(pos + 1, "(")) throw ParseError{};
-            size_t close = match(pos + 1, "(", ")");
+        if (s_.ident(pos, "for") || s_.ident(pos, "while")) {
+            const bool is_for = s_[pos].text == "for";
+            if (!s_.is(pos + 1, "(")) throw ParseError{};
+            size_t close = s_.close_of(pos + 1);
             if (close >= end) throw ParseError{};
             LoopInfo L;
             L.id = (int)loops_.size() + 1;
@@ -482,14 +437,14 @@ class Hoister {
             if (is_for) {
                 size_t p = pos + 2;
                 // `for (int I = 0; I < BOUND; I++)`, token for token: the only loop shape whose trip number is known to be I
-                if (ident(p, "int") && ident(p + 1) && is(p + 2, "=") && T(p + 3).kind == Token::Number && T(p + 3).text == "0" && is(p + 4, ";") &&
-                    ident(p + 5) && T(p + 5).text == T(p + 1).text && is(p + 6, "<") && (ident(p + 7) || T(p + 7).kind == Token::Number) && is(p + 8, ";") &&
-                    ident(p + 9) && T(p + 9).text == T(p + 1).text && is(p + 10, "++") && p + 11 == close) {
+                if (s_.ident(p, "int") && s_.ident(p + 1) && s_.is(p + 2, "=") && s_[p + 3].kind == Token::Number && s_[p + 3].text == "0" && s_.is(p + 4, ";") &&
+                    s_.ident(p + 5) && s_[p + 5].text == s_[p + 1].text && s_.is(p + 6, "<") && (s_.ident(p + 7) || s_[p + 7].kind == Token::Number) && s_.is(p + 8, ";") &&
+                    s_.ident(p + 9) && s_[p + 9].text == s_[p + 1].text && s_.is(p + 10, "++") && p + 11 == close) {
                     loops_[slot].canonical = true;
-                    loops_[slot].var = T(p + 1).text;
-                    loops_[slot].bound = T(p + 7).text;
+                    loops_[slot].var = s_[p + 1].text;
+                    loops_[slot].bound = s_[p + 7].text;
                 }
-                if (is(p, ";")) ++p;
+                if (s_.is(p, ";")) ++p;
                 else declaration_or_expression(p, close, depth + 1, L.id, true);  // init (ends at its `;`)
                 size_t semi = statement_end(p, close);
                 if (semi > p) {
@@ -518,13 +473,13 @@ class Hoister {
                 sites_.push_back(s);
             }
             pos = close + 1;
-            loops_[slot].braced = is(pos, "{");
+            loops_[slot].braced = s_.is(pos, "{");
             loops_[slot].body_b = pos;
             controlled(pos, end, depth, L.id);
             loops_[slot].body_e = pos;
             return;
         }
-        if (ident(pos, "return")) {
+        if (s_.ident(pos, "return")) {
             const size_t semi = statement_end(pos, end);
             if (semi > pos + 1) {
                 Site s;
@@ -536,15 +491,15 @@ class Hoister {
             pos = semi + 1;
             return;
         }
-        if (ident(pos, "break") || ident(pos, "continue") || ident(pos, "discard")) {
-            if (T(pos).text == "continue")
+        if (s_.ident(pos, "break") || s_.ident(pos, "continue") || s_.ident(pos, "discard")) {
+            if (s_[pos].text == "continue")
                 for (int l = loop; l > 0; l = loops_[l - 1].outer) loops_[l - 1].has_continue = true;  // (only the innermost is skipped, but be strict)
-            if (!is(pos + 1, ";")) throw ParseError{};
+            if (!s_.is(pos + 1, ";")) throw ParseError{};
             pos += 2;
             return;
         }
-        if (ident(pos, "do") || ident(pos, "switch") || ident(pos, "case") || ident(pos, "default") || ident(pos, "struct") || ident(pos, "goto") ||
-            ident(pos, "else"))
+        if (s_.ident(pos, "do") || s_.ident(pos, "switch") || s_.ident(pos, "case") || s_.ident(pos, "default") || s_.ident(pos, "struct") || s_.ident(pos, "goto") ||
+            s_.ident(pos, "else"))
             throw ParseError{};
         declaration_or_expression(pos, end, depth, loop, false);
     }
@@ -575,8 +530,8 @@ class Hoister {
         return false;
     }
     bool tokens_mention(size_t b, size_t e, const std::string& name) const {
-        for (size_t i = b; i < e && i < n_; ++i)
-            if (ident(i) && T(i).text == name && !(i > 0 && is(i - 1, "."))) return true;
+        for (size_t i = b; i < e && i < s_.n(); ++i)
+            if (s_.ident(i) && s_[i].text == name && !(i > 0 && s_.is(i - 1, "."))) return true;
         return false;
     }
 
@@ -606,7 +561,7 @@ class Hoister {
         switch (nd.kind) {
             case Node::Lit:
                 nd.uniform = true;
-                nd.type = float_literal(nd.text) ? "float" : ((nd.text.back() == 'u' || nd.text.back() == 'U') ? "uint" : "int");
+                nd.type = is_float_typed_literal(nd.text) ? "float" : ((nd.text.back() == 'u' || nd.text.back() == 'U') ? "uint" : "int");
                 break;
             case Node::Ident: {
                 if (nd.text == "true" || nd.text == "false") {
@@ -760,7 +715,7 @@ class Hoister {
                     combine(nd, kid(0));
                     break;
                 }
-                if (kid(0).uniform && vec_size(kid(0).type) && swizzle(nd.text)) {
+                if (kid(0).uniform && vec_size(kid(0).type) && !component_indices(nd.text).empty()) {
                     nd.uniform = true;
                     nd.type = vec_of((int)nd.text.size());
                     combine(nd, kid(0));
@@ -816,7 +771,7 @@ class Hoister {
     void hoist_in(int id) {
         const Node& nd = nodes_[id];
         if (half_hoistable(nd)) {
-            const std::string text = text_of(nd.b, nd.e);
+            const std::string text = s_.text_of(nd.b, nd.e);
             HoistedMember m;
             m.type = "vec4";
             m.name = "ptl_hv" + std::to_string(next_member_++);
@@ -839,7 +794,7 @@ class Hoister {
             return;
         }
         if (hoistable(nd)) {
-            const std::string text = text_of(nd.b, nd.e);
+            const std::string text = s_.text_of(nd.b, nd.e);
             replacements_.push_back({nd.b, nd.e, member_for(nd.type, nd, text)});
             return;
         }
@@ -849,7 +804,7 @@ class Hoister {
                 const int which = nd.text == "normalize_normal" ? 0 : 2;
                 const Node& arg = nodes_[nd.kids[which]];
                 replacements_.push_back({nd.b, nd.b + 1, nd.text == "normalize_normal" ? "ptl_normalize_normal_unit" : "ptl_plane_intersect_unit"});
-                replacements_.push_back({arg.b, arg.e, member_for("vec3", arg, "normalize(" + text_of(arg.b, arg.e) + ")")});
+                replacements_.push_back({arg.b, arg.e, member_for("vec3", arg, "normalize(" + s_.text_of(arg.b, arg.e) + ")")});
                 for (int k = 0; k < (int)nd.kids.size(); ++k)
                     if (k != which) hoist_in(nd.kids[k]);
                 return;
@@ -858,7 +813,7 @@ class Hoister {
                 const int which = staged_arg(1) ? 1 : 0;
                 const Node& arg = nodes_[nd.kids[which]];
                 replacements_.push_back({nd.b, nd.b + 1, which == 1 ? "ptl_is_collinear_len" : "ptl_is_collinear_len0"});
-                replacements_.push_back({nd.e - 1, nd.e - 1, ", " + member_for("float", arg, "length(" + text_of(arg.b, arg.e) + ")")});
+                replacements_.push_back({nd.e - 1, nd.e - 1, ", " + member_for("float", arg, "length(" + s_.text_of(arg.b, arg.e) + ")")});
                 for (int k : nd.kids) hoist_in(k);
                 return;
             }
@@ -887,7 +842,7 @@ class Hoister {
             const LoopInfo& L = loops_[u.loop - 1];
             if (!L.canonical || !L.braced || L.outer != 0 || L.depth != 0 || L.has_continue || u.depth != L.depth + 1) return;
             if (writes_[L.var] != 2 || (declared_.count(L.bound) && writes_[L.bound] != 1)) return;
-            if (!(is(L.kw - 1, ";") || is(L.kw - 1, "{") || is(L.kw - 1, "}"))) return;
+            if (!(s_.is(L.kw - 1, ";") || s_.is(L.kw - 1, "{") || s_.is(L.kw - 1, "}"))) return;
             if (tokens_mention(L.header_open, L.header_close, s.decl_name) || tokens_mention(L.body_e, body_e, s.decl_name)) return;
             bool read_in_the_body = false;
             for (size_t k = 0; k < sites_.size(); ++k)
@@ -958,7 +913,7 @@ class Hoister {
                 const LoopInfo& L = loops_[u.loop - 1];
                 if (!L.canonical || !L.braced || L.outer != 0 || L.depth != 0 || L.has_continue || u.depth != L.depth + 1) break;
                 if (writes_[L.var] != 2 || (declared_.count(L.bound) && writes_[L.bound] != 1)) break;
-                if (!(is(L.kw - 1, ";") || is(L.kw - 1, "{") || is(L.kw - 1, "}") || L.kw == body_b)) break;
+                if (!(s_.is(L.kw - 1, ";") || s_.is(L.kw - 1, "{") || s_.is(L.kw - 1, "}") || L.kw == body_b)) break;
                 if (tokens_mention(L.header_open, L.header_close, s.decl_name) || tokens_mention(L.body_e, body_e, s.decl_name)) break;
                 Carried c;
                 c.name = s.decl_name;
@@ -1024,7 +979,7 @@ class Hoister {
             const Site& u = sites_[c.update_site];
             const LoopInfo& L = loops_[c.loop - 1];
             const Node& root = nodes_[u.root];
-            const std::string rhs = text_of(nodes_[root.kids[1]].b, nodes_[root.kids[1]].e);
+            const std::string rhs = s_.text_of(nodes_[root.kids[1]].b, nodes_[root.kids[1]].e);
             HoistedMember m;
             m.type = c.type;
             m.name = "ptl_hv" + std::to_string(next_member_++);
@@ -1048,7 +1003,7 @@ class Hoister {
             const Site& u = sites_[c.update_site];
             const LoopInfo& L = loops_[c.loop - 1];
             const Node& root = nodes_[u.root];
-            const std::string rhs = text_of(nodes_[root.kids[1]].b, nodes_[root.kids[1]].e);
+            const std::string rhs = s_.text_of(nodes_[root.kids[1]].b, nodes_[root.kids[1]].e);
             HoistedMember m;
             m.type = "vec4";
             m.name = "ptl_hv" + std::to_string(next_member_++);
@@ -1078,7 +1033,7 @@ class Hoister {
                 if (s.kind != Site::DeclInit || s.decl_name != u.first || s.name_at != u.second.name_at) continue;
                 PrologueItem decl;
                 decl.at = s.name_at;
-                decl.text = s.decl_type + " " + s.decl_name + " = " + text_of(nodes_[s.root].b, nodes_[s.root].e) + ";";
+                decl.text = s.decl_type + " " + s.decl_name + " = " + s_.text_of(nodes_[s.root].b, nodes_[s.root].e) + ";";
                 items_.push_back(decl);
             }
         }
@@ -1097,7 +1052,7 @@ class Hoister {
                     if (s.kind != Site::DeclInit || s.decl_name != h.first || s.name_at != h.second) continue;
                     PrologueItem decl;
                     decl.at = s.name_at;
-                    decl.text = "Ray " + s.decl_name + " = " + text_of(nodes_[s.root].b, nodes_[s.root].e) + ";";
+                    decl.text = "Ray " + s.decl_name + " = " + s_.text_of(nodes_[s.root].b, nodes_[s.root].e) + ";";
                     items_.push_back(decl);
                 }
             }
@@ -1132,11 +1087,11 @@ class Hoister {
         std::vector<bool> drop(toks_.size(), false);
         for (const Replacement& r : replacements_)
             if (r.e > r.b)
-                for (size_t k = sig_[r.b]; k <= sig_[r.e - 1]; ++k) drop[k] = true;
+                for (size_t k = s_.raw(r.b); k <= s_.raw(r.e - 1); ++k) drop[k] = true;
         std::string out;
         size_t next = 0;
         for (size_t k = 0; k <= toks_.size(); ++k) {
-            while (next < replacements_.size() && (replacements_[next].b >= n_ ? k == toks_.size() : sig_[replacements_[next].b] == k)) out += replacements_[next++].text;
+            while (next < replacements_.size() && (replacements_[next].b >= s_.n() ? k == toks_.size() : s_.raw(replacements_[next].b) == k)) out += replacements_[next++].text;
             if (k == toks_.size()) break;
             if (!drop[k]) out += toks_[k].text;
             else if (toks_[k].kind == Token::Space && toks_[k].text == "\n") out += "\n";  // line for line

@@ -5,8 +5,6 @@
 #include <stdexcept>
 
 #include <algorithm>
-#include <cctype>
-#include <cstring>
 #include <map>
 #include <set>
 #include <vector>
@@ -34,144 +32,7 @@ std::string filter_tagged_lines(const std::string& text, const CodegenFlags& f) 
     return out;
 }
 
-std::vector<Token> tokenize_glsl(const std::string& s) {
-    std::vector<Token> out;
-    size_t i = 0, n = s.size();
-    bool line_start = true;
-    while (i < n) {
-        char c = s[i];
-        if (c == '\n') {
-            out.push_back({Token::Space, "\n"});
-            ++i;
-            line_start = true;
-            continue;
-        }
-        if (c == ' ' || c == '\t' || c == '\r') {
-            size_t j = i;
-            while (j < n && (s[j] == ' ' || s[j] == '\t' || s[j] == '\r')) ++j;
-            out.push_back({Token::Space, s.substr(i, j - i)});
-            i = j;
-            continue;
-        }
-        if (c == '#' && line_start) {  // preprocessor directive: keep the line verbatim ...
-            size_t j = s.find('\n', i);
-            if (j == std::string::npos) j = n;
-            // ... except the replacement text of a `#define`, which is GLSL like any other: its float literals need their suffix and its
-            // divisions are the contract's (rewrite_divisions), e.g. the reference's own `#define PI2 (acos(-1.) / 2.0)`.  The head
-            // (`#define NAME` or `#define NAME(params)`) stays one verbatim token, the rest of the line is tokenised as code.
-            size_t h = i + 1;
-            while (h < j && (s[h] == ' ' || s[h] == '\t')) ++h;
-            if (s.compare(h, 6, "define") == 0 && h + 6 < j && (s[h + 6] == ' ' || s[h + 6] == '\t') && s.find('\\', i) >= j) {
-                h += 6;
-                while (h < j && (s[h] == ' ' || s[h] == '\t')) ++h;
-                while (h < j && (std::isalnum((unsigned char)s[h]) || s[h] == '_')) ++h;
-                if (h < j && s[h] == '(') {  // function-like: the parameter list belongs to the head
-                    size_t close = s.find(')', h);
-                    h = (close == std::string::npos || close >= j) ? j : close + 1;
-                }
-                out.push_back({Token::Preproc, s.substr(i, h - i)});
-                i = h;
-                line_start = false;
-                continue;
-            }
-            out.push_back({Token::Preproc, s.substr(i, j - i)});
-            i = j;
-            continue;
-        }
-        line_start = false;
-        if (c == '/' && i + 1 < n && s[i + 1] == '/') {
-            size_t j = s.find('\n', i);
-            if (j == std::string::npos) j = n;
-            out.push_back({Token::Comment, s.substr(i, j - i)});
-            i = j;
-            continue;
-        }
-        if (c == '/' && i + 1 < n && s[i + 1] == '*') {
-            size_t j = s.find("*/", i + 2);
-            j = j == std::string::npos ? n : j + 2;
-            out.push_back({Token::Comment, s.substr(i, j - i)});
-            i = j;
-            continue;
-        }
-        if (std::isalpha((unsigned char)c) || c == '_') {
-            size_t j = i;
-            while (j < n && (std::isalnum((unsigned char)s[j]) || s[j] == '_')) ++j;
-            out.push_back({Token::Ident, s.substr(i, j - i)});
-            i = j;
-            continue;
-        }
-        if (std::isdigit((unsigned char)c) || (c == '.' && i + 1 < n && std::isdigit((unsigned char)s[i + 1]))) {
-            size_t j = i;
-            if (c == '0' && j + 1 < n && (s[j + 1] == 'x' || s[j + 1] == 'X')) {
-                j += 2;
-                while (j < n && std::isxdigit((unsigned char)s[j])) ++j;
-            } else {
-                while (j < n && std::isdigit((unsigned char)s[j])) ++j;
-                if (j < n && s[j] == '.') {
-                    ++j;
-                    while (j < n && std::isdigit((unsigned char)s[j])) ++j;
-                }
-                if (j < n && (s[j] == 'e' || s[j] == 'E')) {
-                    size_t k = j + 1;
-                    if (k < n && (s[k] == '+' || s[k] == '-')) ++k;
-                    if (k < n && std::isdigit((unsigned char)s[k])) {
-                        while (k < n && std::isdigit((unsigned char)s[k])) ++k;
-                        j = k;
-                    }
-                }
-            }
-            while (j < n && (s[j] == 'f' || s[j] == 'F' || s[j] == 'u' || s[j] == 'U')) ++j;  // suffixes
-            out.push_back({Token::Number, s.substr(i, j - i)});
-            i = j;
-            continue;
-        }
-        // two-character operators that matter for the lvalue-swizzle test
-        static const char* two[] = {"==", "!=", "<=", ">=", "+=", "-=", "*=", "/=", "&&", "||", "++", "--", "<<", ">>"};
-        bool matched = false;
-        for (const char* t : two) {
-            if (s.compare(i, 2, t) == 0) {
-                out.push_back({Token::Punct, t});
-                i += 2;
-                matched = true;
-                break;
-            }
-        }
-        if (matched) continue;
-        out.push_back({Token::Punct, std::string(1, c)});
-        ++i;
-    }
-    return out;
-}
-
 namespace {
-
-std::vector<Token> tokenize(const std::string& s) { return tokenize_glsl(s); }
-
-bool is_float_literal(const std::string& t) {
-    if (t.size() > 1 && t[0] == '0' && (t[1] == 'x' || t[1] == 'X')) return false;
-    for (char c : t)
-        if (c == '.' || c == 'e' || c == 'E') return true;
-    return false;
-}
-
-// .xyzw / .rgba / .stpq selectors -> component indices; empty if `t` is not a swizzle
-std::vector<int> swizzle_indices(const std::string& t) {
-    static const char* sets[] = {"xyzw", "rgba", "stpq"};
-    if (t.size() < 2 || t.size() > 4) return {};
-    for (const char* set : sets) {
-        std::vector<int> idx;
-        for (char c : t) {
-            const char* p = std::strchr(set, c);
-            if (!p) {
-                idx.clear();
-                break;
-            }
-            idx.push_back((int)(p - set));
-        }
-        if (idx.size() == t.size()) return idx;
-    }
-    return {};
-}
 
 const std::set<std::string>& cpp_only_keywords() {
     static const std::set<std::string> k = {
@@ -186,53 +47,33 @@ const std::set<std::string>& cpp_only_keywords() {
 }
 
 bool looks_like_a_uniform(const std::string& name) {
-    auto ends = [&](const char* suffix) {
-        size_t n = std::strlen(suffix);
-        return name.size() > n && name.compare(name.size() - n, n, suffix) == 0;
-    };
-    return ends("_mat") || ends("_mat_inv") || ends("_mat_teleport") || ends("_u") || (name.size() > 1 && name[0] == '_');
-}
-
-bool is_assign_op(const Token& t) {
-    return t.kind == Token::Punct && (t.text == "=" || t.text == "+=" || t.text == "-=" || t.text == "*=" || t.text == "/=" || t.text == "++" || t.text == "--");
+    const bool float_uniform = name.size() > 2 && name.compare(name.size() - 2, 2, "_u") == 0;
+    return is_scene_matrix_name(name) || float_uniform || (name.size() > 1 && name[0] == '_');
 }
 
 // See glsl_translate.h (`defer_loop_updates`).  Works on the significant tokens; every check that fails leaves the loop untouched.
 void defer_loop_carried_updates(std::vector<Token>& toks) {
-    std::vector<size_t> sig;  // indices of the significant tokens
-    for (size_t k = 0; k < toks.size(); ++k)
-        if (toks[k].kind != Token::Space && toks[k].kind != Token::Comment && toks[k].kind != Token::Preproc) sig.push_back(k);
-    const size_t n = sig.size();
-    auto T = [&](size_t i) -> const Token& { return toks[sig[i]]; };
-    auto is = [&](size_t i, const char* text) { return i < n && T(i).kind == Token::Punct && T(i).text == text; };
-    auto ident = [&](size_t i, const char* text) { return i < n && T(i).kind == Token::Ident && T(i).text == text; };
-    auto match = [&](size_t open, const char* a, const char* b) -> size_t {  // index of the bracket closing the one at `open`, or n
-        int depth = 0;
-        for (size_t i = open; i < n; ++i) {
-            if (is(i, a)) ++depth;
-            else if (is(i, b) && --depth == 0) return i;
-        }
-        return n;
-    };
+    const TokenView s(toks);  // the edits are collected and applied once the scan is over: the view never sees a changed stream
+    const size_t n = s.n();
     // identifiers the snippet assigns or declares somewhere: never treated as loop-invariant
     std::set<std::string> written;
     for (size_t i = 0; i < n; ++i) {
-        if (T(i).kind != Token::Ident) continue;
-        bool target = (i + 1 < n && is_assign_op(T(i + 1))) || (i > 0 && (is(i - 1, "++") || is(i - 1, "--")));
-        bool declared = i > 0 && T(i - 1).kind == Token::Ident && i + 1 < n && (is(i + 1, "=") || is(i + 1, ";") || is(i + 1, ",") || is(i + 1, ")") || is(i + 1, "["));
-        if (target || declared) written.insert(T(i).text);
+        if (s[i].kind != Token::Ident) continue;
+        bool target = (i + 1 < n && is_assignment_op(s[i + 1])) || (i > 0 && (s.is(i - 1, "++") || s.is(i - 1, "--")));
+        bool declared = i > 0 && s[i - 1].kind == Token::Ident && i + 1 < n && (s.is(i + 1, "=") || s.is(i + 1, ";") || s.is(i + 1, ",") || s.is(i + 1, ")") || s.is(i + 1, "["));
+        if (target || declared) written.insert(s[i].text);
     }
     for (size_t i = 0; i < n; ++i)
-        if (ident(i, "do") || ident(i, "goto")) return;  // do-while bodies are not tracked as loops: leave such code alone
+        if (s.ident(i, "do") || s.ident(i, "goto")) return;  // do-while bodies are not tracked as loops: leave such code alone
     struct Loop {
         size_t kw, header_open, header_close, body_open, body_close;
     };
     std::vector<Loop> loops;  // every loop with a braced body, `for` and `while`
     for (size_t i = 0; i + 1 < n; ++i) {
-        if (!(ident(i, "for") || ident(i, "while")) || !is(i + 1, "(")) continue;
-        size_t close = match(i + 1, "(", ")");
-        if (close >= n || !is(close + 1, "{")) continue;
-        size_t end = match(close + 1, "{", "}");
+        if (!(s.ident(i, "for") || s.ident(i, "while")) || !s.is(i + 1, "(")) continue;
+        size_t close = s.close_of(i + 1);
+        if (close >= n || !s.is(close + 1, "{")) continue;
+        size_t end = s.close_of(close + 1);
         if (end >= n) continue;
         loops.push_back({i, i + 1, close, close + 1, end});
     }
@@ -244,25 +85,25 @@ void defer_loop_carried_updates(std::vector<Token>& toks) {
     std::vector<std::pair<size_t, size_t>> removed;  // [first, last] significant tokens replaced by the text of the insert at `first`
     int counter = 0;
     for (const Loop& L : loops) {
-        if (!ident(L.kw, "for")) continue;
+        if (!s.ident(L.kw, "for")) continue;
         bool nested = false;
         for (const Loop& O : loops) nested = nested || (O.body_open < L.kw && L.kw < O.body_close);
         if (nested) continue;
-        if (L.kw > 0 && !(is(L.kw - 1, ";") || is(L.kw - 1, "{") || is(L.kw - 1, "}"))) continue;  // `if (c) for ...`: nowhere to declare the counter
+        if (L.kw > 0 && !(s.is(L.kw - 1, ";") || s.is(L.kw - 1, "{") || s.is(L.kw - 1, "}"))) continue;  // `if (c) for ...`: nowhere to declare the counter
         // the enclosing function: for a body-only snippet (loop at brace depth 0) the whole text, else from the brace that opens the
         // function body to the one that closes it
         size_t fn_begin = 0, fn_end = n;
         {
             int depth = 0;
             for (size_t i = 0; i < L.kw; ++i) {
-                if (is(i, "{") && depth++ == 0) fn_begin = i + 1;
-                else if (is(i, "}")) --depth;
+                if (s.is(i, "{") && depth++ == 0) fn_begin = i + 1;
+                else if (s.is(i, "}")) --depth;
             }
             if (depth == 0) fn_begin = 0;
             if (depth > 0) {
                 int d = depth;
                 for (size_t i = L.body_close + 1; i < n; ++i) {
-                    d += is(i, "{") ? 1 : is(i, "}") ? -1 : 0;
+                    d += s.is(i, "{") ? 1 : s.is(i, "}") ? -1 : 0;
                     if (d == 0) {
                         fn_end = i;
                         break;
@@ -278,39 +119,39 @@ void defer_loop_carried_updates(std::vector<Token>& toks) {
         for (size_t i = L.body_open + 1; i < L.body_close; ++i) {
             start_of[i] = stmt_start;
             depth_of[i] = brace;
-            if (is(i, "(")) ++paren;
-            else if (is(i, ")")) --paren;
-            else if (is(i, "{")) { ++brace; if (paren == 0) stmt_start = i + 1; }
-            else if (is(i, "}")) { --brace; if (paren == 0) stmt_start = i + 1; }
-            else if (is(i, ";") && paren == 0) stmt_start = i + 1;
+            if (s.is(i, "(")) ++paren;
+            else if (s.is(i, ")")) --paren;
+            else if (s.is(i, "{")) { ++brace; if (paren == 0) stmt_start = i + 1; }
+            else if (s.is(i, "}")) { --brace; if (paren == 0) stmt_start = i + 1; }
+            else if (s.is(i, ";") && paren == 0) stmt_start = i + 1;
         }
         for (size_t i = L.body_open + 1; i < L.body_close; ++i) {
-            if (depth_of[i] != 0 || start_of[i] != i || T(i).kind != Token::Ident || !is(i + 1, "=")) continue;
-            const std::string X = T(i).text;
+            if (depth_of[i] != 0 || start_of[i] != i || s[i].kind != Token::Ident || !s.is(i + 1, "=")) continue;
+            const std::string X = s[i].text;
             size_t semi = i + 2;
             int p = 0, x_in_rhs = 0;
             bool ok = true;
-            for (; semi < L.body_close && !(is(semi, ";") && p == 0); ++semi) {
-                const Token& t = T(semi);
-                if (is(semi, "(")) ++p;
-                else if (is(semi, ")")) --p;
-                else if (is(semi, ",") || is(semi, "*")) {}
+            for (; semi < L.body_close && !(s.is(semi, ";") && p == 0); ++semi) {
+                const Token& t = s[semi];
+                if (s.is(semi, "(")) ++p;
+                else if (s.is(semi, ")")) --p;
+                else if (s.is(semi, ",") || s.is(semi, "*")) {}
                 else if (t.kind == Token::Ident && t.text == X) ++x_in_rhs;
-                else if (t.kind == Token::Ident && t.text == "transform" && is(semi + 1, "(")) {}
-                else if (t.kind == Token::Ident && looks_like_a_uniform(t.text) && !written.count(t.text) && !(semi > 0 && is(semi - 1, "."))) {}
+                else if (t.kind == Token::Ident && t.text == "transform" && s.is(semi + 1, "(")) {}
+                else if (t.kind == Token::Ident && looks_like_a_uniform(t.text) && !written.count(t.text) && !(semi > 0 && s.is(semi - 1, "."))) {}
                 else ok = false;
             }
             if (!ok || x_in_rhs != 1 || semi >= L.body_close || p != 0) continue;
             // X elsewhere: not in the header, only in nested blocks of the body, never written, never a member name
             std::vector<size_t> uses;
-            for (size_t j = L.header_open; j <= L.header_close && ok; ++j) ok = !(T(j).kind == Token::Ident && T(j).text == X);
+            for (size_t j = L.header_open; j <= L.header_close && ok; ++j) ok = !(s[j].kind == Token::Ident && s[j].text == X);
             for (size_t j = L.body_open + 1; j < L.body_close && ok; ++j) {
                 if (j >= i && j <= semi) continue;
-                if (T(j).kind != Token::Ident || T(j).text != X) continue;
-                if (j > 0 && is(j - 1, ".")) { ok = false; break; }
-                bool target = is_assign_op(T(j + 1)) || is(j - 1, "++") || is(j - 1, "--");
+                if (s[j].kind != Token::Ident || s[j].text != X) continue;
+                if (j > 0 && s.is(j - 1, ".")) { ok = false; break; }
+                bool target = is_assignment_op(s[j + 1]) || s.is(j - 1, "++") || s.is(j - 1, "--");
                 if (depth_of[j] < 1 || target) { ok = false; break; }
-                if (ident(start_of[j], "else") || ident(start_of[j], "case") || ident(start_of[j], "default")) { ok = false; break; }
+                if (s.ident(start_of[j], "else") || s.ident(start_of[j], "case") || s.ident(start_of[j], "default")) { ok = false; break; }
                 uses.push_back(start_of[j]);
             }
             if (!ok || uses.empty()) continue;
@@ -318,13 +159,13 @@ void defer_loop_carried_updates(std::vector<Token>& toks) {
             // its final value out of the function, which a deferred update does not guarantee
             bool local = false;
             for (size_t j = fn_begin + 1; j + 1 < L.kw && !local; ++j)
-                local = T(j).kind == Token::Ident && T(j).text == X && T(j - 1).kind == Token::Ident && (is(j + 1, "=") || is(j + 1, ";") || is(j + 1, ","));
+                local = s[j].kind == Token::Ident && s[j].text == X && s[j - 1].kind == Token::Ident && (s.is(j + 1, "=") || s.is(j + 1, ";") || s.is(j + 1, ","));
             if (!local) continue;
             bool used_after = false;
-            for (size_t j = L.body_close + 1; j < fn_end; ++j) used_after = used_after || (T(j).kind == Token::Ident && T(j).text == X);
+            for (size_t j = L.body_close + 1; j < fn_end; ++j) used_after = used_after || (s[j].kind == Token::Ident && s[j].text == X);
             // the update statement as text, the counter, the flush
             std::string update;
-            for (size_t j = i; j <= semi; ++j) update += T(j).text + (j < semi && T(j).kind == Token::Ident && T(j + 1).kind == Token::Ident ? " " : "");
+            for (size_t j = i; j <= semi; ++j) update += s[j].text + (j < semi && s[j].kind == Token::Ident && s[j + 1].kind == Token::Ident ? " " : "");
             const std::string pend = "ptl_pend_" + std::to_string(counter++);
             const std::string flush = "for (; " + pend + " > 0; --" + pend + ") " + update + " ";
             inserts.push_back({L.kw, "int " + pend + " = 0; "});
@@ -341,12 +182,12 @@ void defer_loop_carried_updates(std::vector<Token>& toks) {
     // rebuild the token list: inserts go in front of their anchor, removed ranges keep only their line breaks
     std::vector<bool> drop(toks.size(), false);
     for (auto& r : removed)
-        for (size_t k = sig[r.first]; k <= sig[r.second]; ++k) drop[k] = true;
+        for (size_t k = s.raw(r.first); k <= s.raw(r.second); ++k) drop[k] = true;
     std::stable_sort(inserts.begin(), inserts.end(), [](const Insert& a, const Insert& b) { return a.at < b.at; });
     std::vector<Token> out;
     size_t next = 0;
     for (size_t k = 0; k <= toks.size(); ++k) {
-        while (next < inserts.size() && (inserts[next].at >= n ? k == toks.size() : sig[inserts[next].at] == k)) out.push_back({Token::Raw, inserts[next++].text});
+        while (next < inserts.size() && (inserts[next].at >= n ? k == toks.size() : s.raw(inserts[next].at) == k)) out.push_back({Token::Raw, inserts[next++].text});
         if (k == toks.size()) break;
         if (!drop[k]) out.push_back(toks[k]);
         else if (toks[k].kind == Token::Space && toks[k].text == "\n") out.push_back(toks[k]);  // line-preserving
@@ -362,15 +203,11 @@ void defer_loop_carried_updates(std::vector<Token>& toks) {
 // earlier divisions of the chain have already been rewritten when a later one is reached, so their text is part of that operand).
 // `x.yz /= e` (a multi-component swizzle as target) stays: the swizzle proxy's own operator/= does the same arithmetic.
 void rewrite_divisions(std::vector<Token>& toks) {
-    std::vector<size_t> sig;
-    for (size_t k = 0; k < toks.size(); ++k)
-        if (toks[k].kind != Token::Space && toks[k].kind != Token::Comment && toks[k].kind != Token::Preproc) sig.push_back(k);
-    const size_t n = sig.size();
-    auto T = [&](size_t i) -> const Token& { return toks[sig[i]]; };
-    auto is = [&](size_t i, const char* text) { return i < n && T(i).kind == Token::Punct && T(i).text == text; };
+    const TokenView s(toks);  // the edits are collected and applied once the scan is over: the view never sees a changed stream
+    const size_t n = s.n();
     auto operand_end = [&](size_t i) {  // can a (sub)expression end with this token?
         if (i >= n) return false;
-        const Token& t = T(i);
+        const Token& t = s[i];
         if (t.kind == Token::Ident) {
             static const std::set<std::string> kw = {"return", "if", "else", "for", "while", "do", "case", "in", "out", "inout", "const"};
             return kw.count(t.text) == 0;
@@ -378,39 +215,21 @@ void rewrite_divisions(std::vector<Token>& toks) {
         if (t.kind == Token::Number) return true;
         return t.kind == Token::Punct && (t.text == ")" || t.text == "]");
     };
-    auto open_of = [&](size_t close) -> size_t {  // index of the bracket the one at `close` closes, or n
-        const std::string c = T(close).text, o = c == ")" ? "(" : "[";
-        int depth = 0;
-        for (size_t i = close + 1; i-- > 0;) {
-            if (is(i, c.c_str())) ++depth;
-            else if (is(i, o.c_str()) && --depth == 0) return i;
-        }
-        return n;
-    };
-    auto close_of = [&](size_t open) -> size_t {
-        const std::string o = T(open).text, c = o == "(" ? ")" : "]";
-        int depth = 0;
-        for (size_t i = open; i < n; ++i) {
-            if (is(i, o.c_str())) ++depth;
-            else if (is(i, c.c_str()) && --depth == 0) return i;
-        }
-        return n;
-    };
     auto is_prefix_op = [&](size_t i) {  // a unary operator: one of - + ! ~ ++ -- that does not follow an operand
-        if (i >= n || T(i).kind != Token::Punct) return false;
-        const std::string& t = T(i).text;
+        if (i >= n || s[i].kind != Token::Punct) return false;
+        const std::string& t = s[i].text;
         if (!(t == "-" || t == "+" || t == "!" || t == "~" || t == "++" || t == "--")) return false;
         return i == 0 || !operand_end(i - 1);
     };
     // start of the unary expression that ends at `e` (inclusive); n when the text is not understood
     auto unary_start = [&](size_t e) -> size_t {
         size_t p = e;
-        if ((is(p, "++") || is(p, "--")) && p > 0 && operand_end(p - 1)) --p;  // postfix increment
+        if ((s.is(p, "++") || s.is(p, "--")) && p > 0 && operand_end(p - 1)) --p;  // postfix increment
         for (;;) {
             if (p >= n) return n;
-            const Token& t = T(p);
+            const Token& t = s[p];
             if (t.kind == Token::Punct && (t.text == ")" || t.text == "]")) {
-                const size_t o = open_of(p);
+                const size_t o = s.open_of(p);
                 if (o == n) return n;
                 if (t.text == "]") {  // base[...]: go on with the base
                     if (o == 0) return n;
@@ -418,12 +237,12 @@ void rewrite_divisions(std::vector<Token>& toks) {
                     continue;
                 }
                 p = o;
-                if (o > 0 && T(o - 1).kind == Token::Ident && operand_end(o - 1)) p = o - 1;  // a call or a constructor
+                if (o > 0 && s[o - 1].kind == Token::Ident && operand_end(o - 1)) p = o - 1;  // a call or a constructor
                 else break;  // a parenthesised expression
             } else if (t.kind != Token::Ident && t.kind != Token::Number) {
                 return n;
             }
-            if (p > 0 && is(p - 1, ".")) {  // member of something: go on with the object
+            if (p > 0 && s.is(p - 1, ".")) {  // member of something: go on with the object
                 if (p < 2) return n;
                 p -= 2;
                 continue;
@@ -438,19 +257,19 @@ void rewrite_divisions(std::vector<Token>& toks) {
         size_t p = b;
         while (is_prefix_op(p)) ++p;
         if (p >= n) return n;
-        if (is(p, "(")) {
-            p = close_of(p);
+        if (s.is(p, "(")) {
+            p = s.close_of(p);
             if (p == n) return n;
-        } else if (T(p).kind != Token::Ident && T(p).kind != Token::Number) {
+        } else if (s[p].kind != Token::Ident && s[p].kind != Token::Number) {
             return n;
         }
         for (;;) {  // postfix chain
-            if (is(p + 1, "(") || is(p + 1, "[")) {
-                p = close_of(p + 1);
+            if (s.is(p + 1, "(") || s.is(p + 1, "[")) {
+                p = s.close_of(p + 1);
                 if (p == n) return n;
-            } else if (is(p + 1, ".") && p + 2 < n && T(p + 2).kind == Token::Ident) {
+            } else if (s.is(p + 1, ".") && p + 2 < n && s[p + 2].kind == Token::Ident) {
                 p += 2;
-            } else if ((is(p + 1, "++") || is(p + 1, "--"))) {
+            } else if ((s.is(p + 1, "++") || s.is(p + 1, "--"))) {
                 p += 1;
             } else {
                 return p;
@@ -463,15 +282,15 @@ void rewrite_divisions(std::vector<Token>& toks) {
     for (size_t k = 0; k < n; ++k) {
         auto fail = [&](const char* what) {
             std::string near;
-            for (size_t i = k > 4 ? k - 4 : 0; i < n && i < k + 5; ++i) near += T(i).text + " ";
+            for (size_t i = k > 4 ? k - 4 : 0; i < n && i < k + 5; ++i) near += s[i].text + " ";
             throw std::runtime_error(std::string("GLSL -> HIP translation: cannot find the ") + what + " operand of the division near `" + near + "`");
         };
-        auto ends_operand = [&](size_t i) { return operand_end(i) || ((is(i, "++") || is(i, "--")) && i > 0 && operand_end(i - 1)); };
-        if (is(k, "/")) {
+        auto ends_operand = [&](size_t i) { return operand_end(i) || ((s.is(i, "++") || s.is(i, "--")) && i > 0 && operand_end(i - 1)); };
+        if (s.is(k, "/")) {
             if (k == 0 || !ends_operand(k - 1)) fail("left");
             size_t left = unary_start(k - 1);
             if (left == n) fail("left");
-            while (left > 1 && (is(left - 1, "*") || is(left - 1, "/") || is(left - 1, "%")) && operand_end(left - 2)) {
+            while (left > 1 && (s.is(left - 1, "*") || s.is(left - 1, "/") || s.is(left - 1, "%")) && operand_end(left - 2)) {
                 const size_t prev = unary_start(left - 2);
                 if (prev == n) break;
                 left = prev;
@@ -481,19 +300,19 @@ void rewrite_divisions(std::vector<Token>& toks) {
             inserts.push_back({left, 0, "ptl_div("});
             retext.push_back({k, ","});
             inserts.push_back({right + 1, 1, ")"});
-        } else if (is(k, "/=")) {
+        } else if (s.is(k, "/=")) {
             if (k == 0 || !operand_end(k - 1)) fail("left");
-            if (T(k - 1).kind == Token::Ident && k >= 2 && is(k - 2, ".") && !swizzle_indices(T(k - 1).text).empty()) continue;  // v.xy /= e
+            if (s[k - 1].kind == Token::Ident && k >= 2 && s.is(k - 2, ".") && !swizzle_indices(s[k - 1].text).empty()) continue;  // v.xy /= e
             const size_t left = unary_start(k - 1);
             if (left == n) fail("left");
             size_t end = k + 1;  // the assignment expression: up to the `;`, `,` or closing bracket of this nesting level
             int depth = 0;
             for (; end < n; ++end) {
-                if (is(end, "(") || is(end, "[")) ++depth;
-                else if (is(end, ")") || is(end, "]")) {
+                if (s.is(end, "(") || s.is(end, "[")) ++depth;
+                else if (s.is(end, ")") || s.is(end, "]")) {
                     if (depth == 0) break;
                     --depth;
-                } else if (depth == 0 && (is(end, ";") || is(end, ","))) break;
+                } else if (depth == 0 && (s.is(end, ";") || s.is(end, ","))) break;
             }
             if (end == k + 1) fail("right");
             inserts.push_back({left, 0, "ptl_div_assign("});
@@ -504,13 +323,13 @@ void rewrite_divisions(std::vector<Token>& toks) {
     if (inserts.empty()) return;
     // an opener and a closer never share a position; several openers or several closers at one place keep their order
     std::stable_sort(inserts.begin(), inserts.end(), [](const Insert& a, const Insert& b) { return a.at < b.at || (a.at == b.at && a.order > b.order); });
-    for (auto& r : retext) toks[sig[r.first]].text = r.second;
+    for (auto& r : retext) toks[s.raw(r.first)].text = r.second;
     std::vector<Token> out;
     out.reserve(toks.size() + inserts.size());
     size_t next = 0;
     for (size_t k = 0; k <= toks.size(); ++k) {
         // a closer belongs right behind the last token of its operand, not behind the white space and comments that follow it
-        while (next < inserts.size() && (inserts[next].at >= n ? k == toks.size() : (inserts[next].order == 1 ? sig[inserts[next].at - 1] + 1 == k : sig[inserts[next].at] == k)))
+        while (next < inserts.size() && (inserts[next].at >= n ? k == toks.size() : (inserts[next].order == 1 ? s.raw(inserts[next].at - 1) + 1 == k : s.raw(inserts[next].at) == k)))
             out.push_back({Token::Raw, inserts[next++].text});
         if (k < toks.size()) out.push_back(toks[k]);
     }
@@ -528,7 +347,6 @@ void rewrite_divisions(std::vector<Token>& toks) {
 // Neither occurs in the reference's scenes (tests/test_host_logic.py runs the corpus through this).  A scene that does either is
 // refused here instead of silently drawing something the reference might not: VERDICT r2 "semantic gaps" #8.
 void check_out_argument_aliasing(const std::vector<std::string>& sources, const std::vector<std::string>& bodies) {
-    struct Sig { const Token* tok; };
     struct Function {
         std::vector<char> out;          // per parameter: out / inout?
         std::set<std::string> names;    // identifiers of the body
@@ -538,61 +356,38 @@ void check_out_argument_aliasing(const std::vector<std::string>& sources, const 
     std::multimap<std::string, Function> functions;
     std::set<std::string> globals;
     std::vector<std::vector<Token>> streams;
-    std::vector<std::vector<size_t>> sigs;        // indices of the tokens that are not white space, per stream
-    std::vector<std::set<size_t>> definitions;    // positions (in sigs) of function names at their definition
-    std::vector<const std::string*> texts;
-    for (const std::string& text : sources) texts.push_back(&text);
-    for (const std::string& text : bodies) texts.push_back(&text);  // statements of a generated function: calls, no definitions
-    for (const std::string* text : texts) {
-        streams.push_back(tokenize(*text));
-        std::vector<size_t> sig;
-        for (size_t k = 0; k < streams.back().size(); ++k) {
-            Token::Kind kind = streams.back()[k].kind;
-            if (kind != Token::Space && kind != Token::Comment && kind != Token::Preproc) sig.push_back(k);
-        }
-        sigs.push_back(std::move(sig));
-        definitions.emplace_back();
-    }
-    auto matching = [](const std::vector<Token>& toks, const std::vector<size_t>& sig, size_t open, const char* o, const char* c) {
-        int depth = 0;
-        for (size_t k = open; k < sig.size(); ++k) {
-            const Token& t = toks[sig[k]];
-            if (t.kind != Token::Punct) continue;
-            if (t.text == o) ++depth;
-            else if (t.text == c && --depth == 0) return k;
-        }
-        return sig.size();
-    };
+    for (const std::string& text : sources) streams.push_back(tokenize_glsl(text));
+    for (const std::string& text : bodies) streams.push_back(tokenize_glsl(text));  // statements of a generated function: calls, no definitions
+    const std::vector<TokenView> views(streams.begin(), streams.end());  // (built once every stream stands where it stays)
+    std::vector<std::set<size_t>> definitions(streams.size());         // positions (in the views) of function names at their definition
     // pass 1: what is defined at file scope
     for (size_t f = 0; f < sources.size(); ++f) {
-        const std::vector<Token>& toks = streams[f];
-        const std::vector<size_t>& sig = sigs[f];
-        auto tk = [&](size_t k) -> const Token& { return toks[sig[k]]; };
-        for (size_t k = 0; k < sig.size();) {
-            if (tk(k).kind == Token::Punct && tk(k).text == "{") {  // a struct body (or anything else braced at file scope)
-                k = matching(toks, sig, k, "{", "}") + 1;
+        const TokenView& s = views[f];
+        for (size_t k = 0; k < s.n();) {
+            if (s.is(k, "{")) {  // a struct body (or anything else braced at file scope)
+                k = s.close_of(k) + 1;
                 continue;
             }
-            bool decl = tk(k).kind == Token::Ident && !not_a_type.count(tk(k).text) && k + 2 < sig.size() && tk(k + 1).kind == Token::Ident && tk(k + 2).kind == Token::Punct;
+            bool decl = s[k].kind == Token::Ident && !not_a_type.count(s[k].text) && k + 2 < s.n() && s[k + 1].kind == Token::Ident && s[k + 2].kind == Token::Punct;
             if (!decl) {
                 ++k;
                 continue;
             }
             bool qualified = false;  // `const float x`, `uniform ...`: nothing a function could write
             for (size_t b = k; b-- > 0;) {
-                if (tk(b).kind == Token::Punct && (tk(b).text == ";" || tk(b).text == "}")) break;
-                if (tk(b).kind == Token::Ident && (tk(b).text == "const" || tk(b).text == "uniform" || tk(b).text == "in")) qualified = true;
+                if (s[b].kind == Token::Punct && (s[b].text == ";" || s[b].text == "}")) break;
+                if (s[b].kind == Token::Ident && (s[b].text == "const" || s[b].text == "uniform" || s[b].text == "in")) qualified = true;
             }
-            const std::string& name = tk(k + 1).text;
-            const std::string& after = tk(k + 2).text;
+            const std::string& name = s[k + 1].text;
+            const std::string& after = s[k + 2].text;
             if (after == "(") {
-                size_t close = matching(toks, sig, k + 2, "(", ")");
-                if (close + 1 < sig.size() && tk(close + 1).kind == Token::Punct && tk(close + 1).text == "{") {
+                size_t close = s.close_of(k + 2);
+                if (s.is(close + 1, "{")) {
                     Function fn;
                     bool is_out = false, any = false;
                     int depth = 0;
                     for (size_t a = k + 3; a < close; ++a) {
-                        const Token& t = tk(a);
+                        const Token& t = s[a];
                         if (t.kind == Token::Punct && (t.text == "(" || t.text == "[")) ++depth;
                         else if (t.kind == Token::Punct && (t.text == ")" || t.text == "]")) --depth;
                         else if (t.kind == Token::Punct && t.text == "," && depth == 0) {
@@ -602,12 +397,12 @@ void check_out_argument_aliasing(const std::vector<std::string>& sources, const 
                         } else if (t.kind == Token::Ident && (t.text == "out" || t.text == "inout")) is_out = true;
                         any = true;
                     }
-                    if (any && !(close == k + 4 && tk(k + 3).text == "void")) fn.out.push_back(is_out);
-                    size_t end = matching(toks, sig, close + 1, "{", "}");
+                    if (any && !(close == k + 4 && s[k + 3].text == "void")) fn.out.push_back(is_out);
+                    size_t end = s.close_of(close + 1);
                     for (size_t a = close + 2; a < end; ++a)
-                        if (tk(a).kind == Token::Ident) {
-                            fn.names.insert(tk(a).text);
-                            if (a + 1 < end && tk(a + 1).kind == Token::Punct && tk(a + 1).text == "(") fn.calls.insert(tk(a).text);
+                        if (s[a].kind == Token::Ident) {
+                            fn.names.insert(s[a].text);
+                            if (a + 1 < end && s.is(a + 1, "(")) fn.calls.insert(s[a].text);
                         }
                     definitions[f].insert(k + 1);
                     functions.emplace(name, std::move(fn));
@@ -622,13 +417,13 @@ void check_out_argument_aliasing(const std::vector<std::string>& sources, const 
                 globals.insert(name);
                 int depth = 0;
                 size_t a = k + 2;
-                for (; a < sig.size(); ++a) {
-                    const Token& t = tk(a);
+                for (; a < s.n(); ++a) {
+                    const Token& t = s[a];
                     if (t.kind != Token::Punct) continue;
                     if (t.text == "(" || t.text == "[" || t.text == "{") ++depth;
                     else if (t.text == ")" || t.text == "]" || t.text == "}") --depth;
                     else if (t.text == ";" && depth == 0) break;
-                    else if (t.text == "," && depth == 0 && a + 1 < sig.size() && tk(a + 1).kind == Token::Ident) globals.insert(tk(a + 1).text);
+                    else if (t.text == "," && depth == 0 && a + 1 < s.n() && s[a + 1].kind == Token::Ident) globals.insert(s[a + 1].text);
                 }
                 k = a + 1;
                 continue;
@@ -659,21 +454,19 @@ void check_out_argument_aliasing(const std::vector<std::string>& sources, const 
     };
     // pass 2: every call of a function with out / inout parameters
     for (size_t f = 0; f < streams.size(); ++f) {
-        const std::vector<Token>& toks = streams[f];
-        const std::vector<size_t>& sig = sigs[f];
-        auto tk = [&](size_t k) -> const Token& { return toks[sig[k]]; };
-        for (size_t k = 0; k + 1 < sig.size(); ++k) {
-            if (tk(k).kind != Token::Ident || !functions.count(tk(k).text) || definitions[f].count(k)) continue;
-            if (!(tk(k + 1).kind == Token::Punct && tk(k + 1).text == "(")) continue;
-            if (k > 0 && tk(k - 1).kind == Token::Punct && tk(k - 1).text == ".") continue;
-            size_t close = matching(toks, sig, k + 1, "(", ")");
+        const TokenView& s = views[f];
+        for (size_t k = 0; k + 1 < s.n(); ++k) {
+            if (s[k].kind != Token::Ident || !functions.count(s[k].text) || definitions[f].count(k)) continue;
+            if (!(s.is(k + 1, "("))) continue;
+            if (k > 0 && s.is(k - 1, ".")) continue;
+            size_t close = s.close_of(k + 1);
             std::vector<std::string> roots, whole;  // first identifier of every argument; the argument without white space
             {
                 int depth = 0;
                 std::string root, text;
                 bool have = false;
                 for (size_t a = k + 2; a < close; ++a) {
-                    const Token& t = tk(a);
+                    const Token& t = s[a];
                     if (t.kind == Token::Punct && (t.text == "(" || t.text == "[")) ++depth;
                     else if (t.kind == Token::Punct && (t.text == ")" || t.text == "]")) --depth;
                     else if (t.kind == Token::Punct && t.text == "," && depth == 0) {
@@ -718,7 +511,7 @@ void check_out_argument_aliasing(const std::vector<std::string>& sources, const 
                     return false;
                 }
             };
-            auto range = functions.equal_range(tk(k).text);
+            auto range = functions.equal_range(s[k].text);
             for (auto it = range.first; it != range.second; ++it) {
                 const Function& fn = it->second;
                 if (fn.out.size() != roots.size()) continue;
@@ -728,15 +521,15 @@ void check_out_argument_aliasing(const std::vector<std::string>& sources, const 
                     if (!fn.out[j] || roots[j].empty()) continue;
                     for (size_t j2 = j + 1; j2 < roots.size(); ++j2)
                         if (fn.out[j2] && roots[j2] == roots[j] && overlap(whole[j], whole[j2]))
-                            throw std::runtime_error("`" + tk(k).text + "(...)`: `" + roots[j] + "` is given to two out / inout parameters of one call; GLSL leaves the order "
+                            throw std::runtime_error("`" + s[k].text + "(...)`: `" + roots[j] + "` is given to two out / inout parameters of one call; GLSL leaves the order "
                                                      "in which they are copied back undefined, so the picture would depend on the GL driver");
                     if (!globals.count(roots[j])) continue;
                     if (!computed) {
-                        touched = reach(tk(k).text);
+                        touched = reach(s[k].text);
                         computed = true;
                     }
                     if (touched.count(roots[j]))
-                        throw std::runtime_error("`" + tk(k).text + "(...)`: the global `" + roots[j] + "` is an out / inout argument of a function that also names it; "
+                        throw std::runtime_error("`" + s[k].text + "(...)`: the global `" + roots[j] + "` is an out / inout argument of a function that also names it; "
                                                  "GLSL copies the argument back at the return, this translation passes a reference -- the two would differ.  Pass a local "
                                                  "and assign it afterwards");
                 }
@@ -749,54 +542,42 @@ void check_out_argument_aliasing(const std::vector<std::string>& sources, const 
 // (Prototypes, struct heads, globals with initialisers and whatever follows a #define are not definitions.)
 static std::set<size_t> definition_heads(const std::vector<Token>& toks) {
     std::set<size_t> heads;
-    auto sig = [&](size_t k) {  // the next token that is neither space nor comment, or toks.size()
-        while (k < toks.size() && (toks[k].kind == Token::Space || toks[k].kind == Token::Comment)) ++k;
-        return k;
-    };
+    auto punct = [&](size_t k, const char* text) { return k < toks.size() && toks[k].kind == Token::Punct && toks[k].text == text; };
     int brace = 0;
     bool in_define = false;
     for (size_t k = 0; k < toks.size(); ++k) {
         const Token& t = toks[k];
         if (t.kind == Token::Preproc) in_define = true;
         if (t.kind == Token::Space && t.text.find('\n') != std::string::npos) in_define = false;
-        if (t.kind == Token::Punct && t.text == "{") ++brace;
-        if (t.kind == Token::Punct && t.text == "}") --brace;
+        if (punct(k, "{")) ++brace;
+        if (punct(k, "}")) --brace;
         if (in_define || brace != 0 || t.kind != Token::Ident) continue;
-        const size_t name = sig(k + 1);
+        const size_t name = next_code(toks, k + 1);
         if (name >= toks.size() || toks[name].kind != Token::Ident) continue;
-        size_t open = sig(name + 1);
-        if (open >= toks.size() || toks[open].kind != Token::Punct || toks[open].text != "(") continue;
+        size_t open = next_code(toks, name + 1);
+        if (!punct(open, "(")) continue;
         int depth = 0;
         size_t close = open;
         for (; close < toks.size(); ++close) {
-            if (toks[close].kind != Token::Punct) continue;
-            if (toks[close].text == "(") ++depth;
-            if (toks[close].text == ")" && --depth == 0) break;
+            if (punct(close, "(")) ++depth;
+            if (punct(close, ")") && --depth == 0) break;
         }
-        const size_t body = sig(close + 1);
-        if (body < toks.size() && toks[body].kind == Token::Punct && toks[body].text == "{") heads.insert(k);
+        if (punct(next_code(toks, close + 1), "{")) heads.insert(k);
     }
     return heads;
 }
 
 std::string translate_glsl(const std::string& glsl, bool defer_loop_updates, bool force_inline_definitions) {
-    std::vector<Token> toks = tokenize(glsl);
-    if (defer_loop_updates) defer_loop_carried_updates(toks);
+    std::vector<Token> toks = tokenize_glsl(glsl);
+    if (defer_loop_updates) defer_loop_carried_updates(toks);  // (each pass builds its own view: the one before it has changed the stream)
     rewrite_divisions(toks);
     const std::set<size_t> heads = force_inline_definitions ? definition_heads(toks) : std::set<size_t>();
     std::string out;
     out.reserve(glsl.size() + glsl.size() / 8);
 
-    auto prev_sig = [&](size_t k) -> const Token* {
-        while (k-- > 0)
-            if (toks[k].kind != Token::Space && toks[k].kind != Token::Comment) return &toks[k];
-        return nullptr;
-    };
-    auto next_sig = [&](size_t k) -> const Token* {
-        for (++k; k < toks.size(); ++k)
-            if (toks[k].kind != Token::Space && toks[k].kind != Token::Comment) return &toks[k];
-        return nullptr;
-    };
+    // the code token in front of / behind toks[k] on the stream (the emitter below walks every token of it), or nullptr
+    auto prev_sig = [&](size_t k) { const size_t p = prev_code(toks, k); return p < toks.size() ? &toks[p] : nullptr; };
+    auto next_sig = [&](size_t k) { const size_t p = next_code(toks, k + 1); return p < toks.size() ? &toks[p] : nullptr; };
 
     // The translation works on tokens, not on types: `.xy` after ANY expression becomes a swizzle call.  A user struct with a field
     // that spells a swizzle (`struct S { vec2 st; }` ... `s.st`) would silently turn into s.sw<0,1>(): refuse it with a message

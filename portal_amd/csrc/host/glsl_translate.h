@@ -76,4 +76,13 @@ void check_out_argument_aliasing(const std::vector<std::string>& sources, const 
 // unchanged (and *bounded = 0) when any of this fails.
 std::string bound_nearer_blocks(const std::string& glsl_body, const std::set<std::string>& functions_with_out_params, int* bounded);
 
+// (glsl_affine.cpp)  A scene uniform that holds a matrix, by its name: `X_mat`, `X_mat_inv`, `A_to_B_mat_teleport` (scene.rs:424-543).
+bool is_scene_matrix_name(const std::string& name);
+
+// Do the scene's GLSL snippets keep rays affine?  True unless one of them builds a Ray from parts that are not spelled `vec4(.., 1.)` /
+// `vec4(.., 0.)`, assigns a ray's `.o` / `.d` in another than a whitelisted form, calls transform() with a matrix that is not a scene uniform
+// (`X_mat`, `X_mat_inv`, `A_to_B_mat_teleport`: the ones whose values are checked), or has an out / inout parameter of type Ray or vec4
+// (KernelOptions::affine_rays; conservative: a refusal only costs the optimisation).  `why` receives the offending text.
+bool snippets_keep_rays_affine(const std::vector<std::string>& codes, std::string* why);
+
 }  // namespace ptl

@@ -6,12 +6,26 @@ commits and comparing the two manifests with `diff`:
 
     python3 tools/source_matrix.py sources before.jsonl      (in a worktree of the parent, with this file copied in)
     python3 tools/source_matrix.py sources after.jsonl
+    python3 tools/source_matrix.py programs before_programs.jsonl   (likewise on both sides; a manifest of its own: each stays a file of moderate size)
     python3 tools/source_matrix.py objects before_obj.jsonl  (slow: twenty hiprtc builds; give each side an empty PTL_CACHE_DIR)
+    python3 tools/source_matrix.py digest before.jsonl       (prints the short form of a manifest, the one to keep under profiles/)
 
 `sources`: for every scene of tests/corpus/scenes/*.ron, every base and every variant below, one JSON line with the sha256 of the
 generated text and the sha256 of the text NORMALISED -- comments removed, every run of white space one space: two sources with the
 same normalised hash are the same tokens in the same order -- or the message with which the generator refuses the combination.
+The bases reach every snippet pass (glsl_translate / glsl_bound / glsl_hoist / glsl_affine) in both of its outcomes: each switch
+that turns one of them on or off is a base of its own, on top of `0` and of `ints|all`, with the variant `none` alone.
 Then one line per text of `ptl_device_source` that tests and tools paste into hand-written kernels.
+
+`programs`: the snippet passes by themselves.  One line per statement template of tests/test_affine_guard_fuzz.py (and per random
+program of its generator) with what `snippets_keep_rays_affine` says of it, verdict and message; one per program of the generators
+of tests/test_glsl_fuzz.py / tests/test_bound_fuzz.py and per mutated corpus snippet with the hashes of what `translate_glsl`,
+`translate_library_glsl`, `hoist_glsl` and `bound_glsl` make of it (or the message they refuse it with).
+
+`digest`: a manifest of `sources` or `programs` is a megabyte of hashes.  Its digest has one line per scene / per kind of program
+with the number of lines and the sha256 of those lines as they stand in the manifest; the few lines that stand for themselves
+(device sources, the affine guard's templates with their messages) are kept whole.  Equal digests are equal manifests; where two
+digests differ, `diff` of the manifests shows the row.
 
 `objects`: two scenes, the five flagged variants, FLAG_QUICK_JIT with and without baked values, compiled for gfx950 without a
 device: sha256 of the disassembly (`llvm-objdump -d --no-show-raw-insn`) and the kernel's registers / scratch / LDS.  The bytes of
@@ -39,23 +53,96 @@ def bases(pa):
             ("patterns", pa.FLAG_SPECIALIZE_PATTERNS)]  # (any specialisation switches KernelOptions::mask_zero_elements on; this is the one left)
 
 
+def pass_bases(pa):
+    switches = [("bounded", pa.FLAG_BOUNDED_SNIPPETS), ("no_deferred", pa.FLAG_NO_DEFERRED_UPDATES), ("no_hoist", pa.FLAG_NO_UNIFORM_HOIST),
+                ("keep_dodges", pa.FLAG_KEEP_TRANSFORM_DODGES), ("no_affine", pa.FLAG_NO_AFFINE_RAYS), ("no_unroll", pa.FLAG_NO_UNROLL)]
+    return [(f"{under_name}|{name}", under | flag) for under_name, under in (("0", 0), ("ints|all", pa.FLAG_SPECIALIZE_INTS | pa.FLAG_SPECIALIZE_ALL)) for name, flag in switches]
+
+
 def variants(pa):
     return [("none", 0), ("slices", pa.FLAG_SLICES), ("passes", pa.FLAG_PASSES), ("slices|passes", pa.FLAG_SLICES | pa.FLAG_PASSES), ("refine", pa.FLAG_REFINE),
             ("refine_slices", pa.FLAG_REFINE_SLICES)]
 
 
+def snippet_passes(pa, code, uniforms=None, **hoist):
+    """sha256 of what each snippet pass makes of `code`, or the message it refuses it with"""
+    if uniforms is None:
+        uniforms = {w: "mat4" for w in re.findall(r"\b\w+_mat(?:_inv|_teleport)?\b", code)} | {w: "float" for w in re.findall(r"\b\w+_u\b", code)}
+    line = {}
+    for name, run in (("translate", lambda: pa.translate_glsl(code)), ("translate_library", lambda: pa.translate_library_glsl(code)),
+                      ("hoist", lambda: "\0".join(pa.hoist_glsl(code, uniforms, **hoist))), ("bound", lambda: "%s\0%d" % pa.bound_glsl(code, ("modf", "bump")))):
+        try:
+            line[name] = sha(run())
+        except pa.PortalError as e:
+            line[name] = "error: " + str(e)
+    return line
+
+
+def programs(pa):
+    """(label, snippet passes of it): the affine guard's templates, the fuzz generators' snippets, mutated corpus snippets"""
+    import random
+    from tests import test_affine_guard_fuzz as ag, test_bound_fuzz as bf, test_glsl_fuzz as gf
+
+    for k, (text, _) in enumerate(ag.TEMPLATES):
+        code = ag.instantiate(text, "r", random.Random(k))
+        library = ag.LIBRARY_CLEAN + "".join(d for needle, d in ag.LIBRARY_DIRTY.items() if needle in code)
+        ok, why = pa.snippets_keep_rays_affine(library + "void f(Ray r, SurfaceIntersection hit) {" + ag.PRELUDE + code + "}")
+        yield {"affine_template": k, "code": code, "ok": ok, "why": why}
+    rng = random.Random(24)
+    for k in range(400):
+        body, library, _ = ag.random_program(rng)
+        ok, why = pa.snippets_keep_rays_affine(library + "MaterialProcessing bend(SurfaceIntersection hit, Ray r) {\n" + ag.PRELUDE + body + "\nreturn material_next(vec3(0.9), r);\n}\n")
+        yield {"affine_program": k, "sha256": sha(library + body), "ok": ok, "why": why}
+    snippet = re.compile(r'\(\("(.*?)"\)\)', re.S)
+    for seed in range(1, 37):
+        for label, make in (("glsl_fuzz", gf.fuzz_scene), ("glsl_fuzz_uniforms", gf.fuzz_scene_with_uniforms)):
+            code = max(snippet.findall(make(seed)[0]), key=len)
+            yield {"program": label, "seed": seed, **snippet_passes(pa, code, params=["hit", "r"])}
+    for seed in range(7000, 7036):
+        code = max(snippet.findall(bf.bound_fuzz_scene(seed)[0]), key=len).replace("\\n", "\n")
+        yield {"program": "bound_fuzz", "seed": seed, **snippet_passes(pa, code, params=["r"])}
+    texts = []  # as tests/test_glsl_fuzz.py::test_hoister_survives_mutated_corpus_snippets mutates them
+    for path in sorted(glob.glob(os.path.join(ROOT, "tests", "corpus", "scenes", "*.ron"))):
+        texts += [m.replace('\\"', '"') for m in snippet.findall(open(path).read()) if len(m) > 40]
+    tok = re.compile(r"\s+|\w+|[^\w\s]")
+    stray = ["(", ")", "{", "}", ";", ",", "for", "if", "else", "=", "++", "?", ":", "[", "]", "return", "continue", "break", ".", "*", "/", "/=", "out", "Ray"]
+    rng = random.Random(2424)
+    for k in range(600):
+        text = rng.choice(texts)
+        toks = tok.findall(text)
+        for _ in range(rng.randrange(0, 6)):
+            if not toks:
+                break
+            i, op = rng.randrange(len(toks)), rng.randrange(5)
+            if op == 0:
+                del toks[i]
+            elif op == 1:
+                toks.insert(i, toks[rng.randrange(len(toks))])
+            elif op == 2:
+                j = rng.randrange(len(toks))
+                toks[i], toks[j] = toks[j], toks[i]
+            elif op == 3:
+                toks = toks[:i]
+            else:
+                toks.insert(i, rng.choice(stray))
+        code = "".join(toks)
+        ok, why = pa.snippets_keep_rays_affine(code)
+        yield {"program": "mutated_corpus", "n": k, "sha256": sha(code), "ok": ok, "why": why,
+               **snippet_passes(pa, code, body_only=not re.search(r"^\s*\w+\s+\w+\s*\(", text), params=["r", "pos", "x", "y", "back", "first", "hit", "i"])}
+
+
 def sources(pa, out):
     for path in sorted(glob.glob(os.path.join(ROOT, "tests", "corpus", "scenes", "*.ron"))):
         name = os.path.splitext(os.path.basename(path))[0]
-        for base_name, base in bases(pa):
-            for variant_name, variant in variants(pa):
-                line = {"scene": name, "base": base_name, "variant": variant_name, "flags": base | variant}
-                try:
-                    text = pa.Scene.from_file(path).generate_source(base | variant)
-                    line.update(sha256=sha(text), normalised_sha256=sha(normalised(text)))
-                except pa.PortalError as e:
-                    line["error"] = str(e)
-                out.write(json.dumps(line) + "\n")
+        rows = [(b, v) for b in bases(pa) for v in variants(pa)] + [(b, variants(pa)[0]) for b in pass_bases(pa)]
+        for (base_name, base), (variant_name, variant) in rows:
+            line = {"scene": name, "base": base_name, "variant": variant_name, "flags": base | variant}
+            try:
+                text = pa.Scene.from_file(path).generate_source(base | variant)
+                line.update(sha256=sha(text), normalised_sha256=sha(normalised(text)))
+            except pa.PortalError as e:
+                line["error"] = str(e)
+            out.write(json.dumps(line) + "\n")
     for which in ("glsl", "library", "entry", "refine_entry", "refine_slices_entry"):
         out.write(json.dumps({"device_source": which, "sha256": sha(pa.device_source(which))}) + "\n")
 
@@ -76,10 +163,29 @@ def objects(pa, out):
                 out.flush()
 
 
+def digest(manifest):
+    groups = {}  # scene / kind of program -> its lines, in the manifest's order
+    for text in manifest:
+        line = json.loads(text)
+        key = next((f"{k} {line[k]}" for k in ("scene", "program") if k in line), "affine_program" if "affine_program" in line else None)
+        if key is None:
+            groups[text] = None
+        else:
+            groups.setdefault(key, []).append(text)
+    for key, lines in groups.items():
+        yield key if lines is None else json.dumps({"group": key, "lines": len(lines), "sha256": sha("".join(lines))}) + "\n"
+
+
 if __name__ == "__main__":
-    if len(sys.argv) != 3 or sys.argv[1] not in ("sources", "objects"):
+    if len(sys.argv) != 3 or sys.argv[1] not in ("sources", "programs", "objects", "digest"):
         sys.exit(__doc__)
+    if sys.argv[1] == "digest":
+        sys.stdout.writelines(digest(open(sys.argv[2])))
+        sys.exit(0)
     import portal_amd as pa
 
     with open(sys.argv[2], "w") as out:
-        (sources if sys.argv[1] == "sources" else objects)(pa, out)
+        if sys.argv[1] == "programs":
+            out.writelines(json.dumps(line) + "\n" for line in programs(pa))
+        else:
+            (sources if sys.argv[1] == "sources" else objects)(pa, out)
