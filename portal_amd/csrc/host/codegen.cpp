@@ -10,7 +10,6 @@
 #include <charconv>
 #include <cmath>
 #include <cstdio>
-#include <regex>
 #include <set>
 #include <sstream>
 #include <tuple>
@@ -370,177 +369,6 @@ std::vector<UniformUpload> evaluate_scene_uniforms(const Scene& scene, std::vect
     return out;
 }
 
-// ------------------------------------------------------------------------------------------
-// what the generator reads out of a GLSL text
-// ------------------------------------------------------------------------------------------
-namespace {
-
-// names of the functions a GLSL text defines (`type name(...) {` at brace depth 0)
-void defined_functions(const std::string& glsl, std::set<std::string>& names) {
-    int depth = 0;
-    for (size_t i = 0; i < glsl.size(); ++i) {
-        const char c = glsl[i];
-        if (c == '{') ++depth;
-        else if (c == '}') --depth;
-        else if (c == '(' && depth == 0) {
-            size_t e = i;
-            while (e > 0 && std::isspace((unsigned char)glsl[e - 1])) --e;
-            size_t b = e;
-            while (b > 0 && (std::isalnum((unsigned char)glsl[b - 1]) || glsl[b - 1] == '_')) --b;
-            size_t t = b;
-            while (t > 0 && std::isspace((unsigned char)glsl[t - 1])) --t;
-            const bool has_type = t > 0 && (std::isalnum((unsigned char)glsl[t - 1]) || glsl[t - 1] == '_');
-            if (e > b && has_type) names.insert(glsl.substr(b, e - b));
-        }
-    }
-}
-
-// names of the functions a GLSL text defines with an `out` / `inout` parameter
-void functions_with_out_params(const std::string& glsl, std::set<std::string>& names) {
-    size_t pos = 0;
-    while ((pos = glsl.find("out", pos)) != std::string::npos) {
-        const bool word_start = pos == 0 || !(std::isalnum((unsigned char)glsl[pos - 1]) || glsl[pos - 1] == '_');
-        const size_t after = pos + 3;
-        const bool word_end = after < glsl.size() && std::isspace((unsigned char)glsl[after]);
-        const bool inout = pos >= 2 && glsl.compare(pos - 2, 2, "in") == 0 && (pos == 2 || !(std::isalnum((unsigned char)glsl[pos - 3]) || glsl[pos - 3] == '_'));
-        if ((word_start || inout) && word_end) {
-            // walk back to the `(` that opens this parameter list; the identifier in front of it is the function
-            int depth = 0;
-            size_t k = pos;
-            while (k > 0) {
-                --k;
-                if (glsl[k] == ')') ++depth;
-                else if (glsl[k] == '(') {
-                    if (depth == 0) break;
-                    --depth;
-                }
-            }
-            size_t e = k;
-            while (e > 0 && std::isspace((unsigned char)glsl[e - 1])) --e;
-            size_t b = e;
-            while (b > 0 && (std::isalnum((unsigned char)glsl[b - 1]) || glsl[b - 1] == '_')) --b;
-            if (e > b) names.insert(glsl.substr(b, e - b));
-        }
-        pos = after;
-    }
-}
-
-}  // namespace
-
-// KernelOptions::mask_zero_elements: the calls that multiply by a masked matrix, in their masked forms (same line, so the line map holds).
-//   transform(NAME, ...)                                  -> ptl_transform_m<PTL_MASK_NAME>(NAME, ...)        (scene snippets, Complex objects)
-//   ptl_plane_cull[_o] / plane_intersect_derived[_o](r, NAME, ...) -> ...<PTL_MASK_NAME>(r, NAME, ...)     (generated plane tests)
-// Every other use of the matrix (a product written out in a snippet, a copy into a local) keeps the full chain: correct, just not shortened.
-static void apply_zero_masks(std::string& src,const std::vector<std::pair<std::string, MatrixPattern>>& masked) {
-    auto ident = [](char c) { return std::isalnum((unsigned char)c) || c == '_'; };
-    for (auto& [name, mask] : masked) {
-        (void)mask;
-        // transform( NAME ,
-        for (size_t at = 0; (at = src.find("transform", at)) != std::string::npos;) {
-            size_t p = at + 9;
-            if ((at > 0 && ident(src[at - 1])) || p >= src.size() || src[p] != '(') {
-                at = p;
-                continue;
-            }
-            size_t q = p + 1;
-            while (q < src.size() && src[q] == ' ') ++q;
-            if (src.compare(q, name.size(), name) != 0) {
-                at = p;
-                continue;
-            }
-            size_t e = q + name.size();
-            while (e < src.size() && src[e] == ' ') ++e;
-            if (e >= src.size() || src[e] != ',' || ident(src[q + name.size()])) {
-                at = p;
-                continue;
-            }
-            std::string repl = "ptl_transform_m<PTL_MASK_" + name + ">";
-            src.replace(at, 9, repl);
-            at += repl.size();
-        }
-        // NAME * <operand>  ->  ptl_mul_m<PTL_MASK_NAME>(NAME, <operand>): a product written out in a snippet (`(b0_mat_inv * pos).z`).  NAME must
-        // be the whole left operand (nothing multiplicative before it); the right operand of `*` is one unary expression: a parenthesised
-        // group, or a name with its call / member / index suffixes.  ptl_mul_m falls back to the plain product for anything but a vec4.
-        for (size_t at = 0; (at = src.find(name, at)) != std::string::npos;) {
-            size_t e = at + name.size();
-            if ((at > 0 && (ident(src[at - 1]) || src[at - 1] == '.')) || (e < src.size() && ident(src[e]))) {
-                at = e;
-                continue;
-            }
-            size_t b = at;
-            while (b > 0 && src[b - 1] == ' ') --b;
-            if (b > 0 && (src[b - 1] == '*' || src[b - 1] == '/' || src[b - 1] == '%')) {
-                at = e;
-                continue;
-            }
-            if (b > 0 && (src[b - 1] == '-' || src[b - 1] == '+')) {  // a UNARY sign on the matrix binds tighter than the product: leave (-M) * v alone
-                size_t c = b - 1;
-                while (c > 0 && src[c - 1] == ' ') --c;
-                if (c == 0 || !(ident(src[c - 1]) || src[c - 1] == ')' || src[c - 1] == ']')) {
-                    at = e;
-                    continue;
-                }
-            }
-            size_t p = e;
-            while (p < src.size() && src[p] == ' ') ++p;
-            if (p + 1 >= src.size() || src[p] != '*' || src[p + 1] == '=') {
-                at = e;
-                continue;
-            }
-            size_t q = p + 1;
-            while (q < src.size() && src[q] == ' ') ++q;
-            auto skip_group = [&](size_t k, char open, char close) {  // k at `open`: one past the matching `close`, npos if unbalanced on this line
-                int depth = 0;
-                for (; k < src.size() && src[k] != '\n'; ++k) {
-                    if (src[k] == open) ++depth;
-                    else if (src[k] == close && --depth == 0) return k + 1;
-                }
-                return std::string::npos;
-            };
-            size_t end = std::string::npos;
-            if (q < src.size() && src[q] == '(') {
-                end = skip_group(q, '(', ')');
-            } else if (q < src.size() && (std::isalpha((unsigned char)src[q]) || src[q] == '_')) {
-                end = q;
-                while (end < src.size() && ident(src[end])) ++end;
-                for (;;) {  // suffixes
-                    if (end < src.size() && src[end] == '(') end = skip_group(end, '(', ')');
-                    else if (end < src.size() && src[end] == '[') end = skip_group(end, '[', ']');
-                    else if (end + 1 < src.size() && src[end] == '.' && (std::isalpha((unsigned char)src[end + 1]) || src[end + 1] == '_')) {
-                        size_t member = ++end;
-                        while (end < src.size() && ident(src[end])) ++end;
-                        std::string m = src.substr(member, end - member);
-                        if ((m == "sw" || m == "swr") && end < src.size() && src[end] == '<') end = skip_group(end, '<', '>');  // a translated swizzle: .sw<0,1,2>()
-                    } else if (end + 2 < src.size() && src[end] == '-' && src[end + 1] == '>' && (std::isalpha((unsigned char)src[end + 2]) || src[end + 2] == '_')) {
-                        end += 2;  // (the generated prologue: `X_mat_inv * out->ptl_dv_origin`)
-                        while (end < src.size() && ident(src[end])) ++end;
-                    } else break;
-                    if (end == std::string::npos) break;
-                }
-            }
-            if (end == std::string::npos) {
-                at = e;
-                continue;
-            }
-            std::string operand = src.substr(q, end - q);
-            std::string repl = "ptl_mul_m<PTL_MASK_" + name + ">(" + name + ", " + operand + ")";
-            src.replace(at, end - at, repl);
-            at += std::string("ptl_mul_m<PTL_MASK_").size() + name.size() + 2 + name.size();  // continue inside the operand: it may hold further products
-        }
-        for (const char* fn : {"ptl_plane_cull_o", "ptl_plane_cull", "plane_intersect_derived_o", "plane_intersect_derived"}) {
-            std::string from = std::string(fn) + "(r, " + name + ",", to = std::string(fn) + "<PTL_MASK_" + name + ">(r, " + name + ",";
-            for (size_t at = 0; (at = src.find(from, at)) != std::string::npos;) {
-                if (at > 0 && ident(src[at - 1])) {
-                    at += from.size();
-                    continue;
-                }
-                src.replace(at, from.size(), to);
-                at += to.size();
-            }
-        }
-    }
-}
-
 MatrixPattern matrix_pattern(const float e[16]) {
     MatrixPattern p = 0;
     for (int k = 0; k < 16; ++k) {
@@ -614,6 +442,7 @@ struct BuildPlan {
     std::map<std::string, int> unroll_bounds;
     bool full_chains = false;  // no matrix product is shortened (GeneratedKernel::full_chains)
     std::vector<std::pair<std::string, MatrixPattern>> masked;
+    std::set<std::string> masked_names;  // ... their names: what every text that multiplies by one of them is written by (masked_call, translate_snippet)
     bool affine_rays = false;
     std::string affine_rays_refused_because;
     bool cheap_transforms = false;     // affine rays: a transform is a few additions, and the two dodges of it are dropped (plan_build):
@@ -945,6 +774,7 @@ BuildPlan plan_build(const Scene& scene, const CodegenFlags& flags, const Kernel
     plan_baked_values(values, opts, plan);
     plan.full_chains = plan_full_chains(values, opts);
     plan.masked = plan_zero_patterns(scene, values, plan.baked, plan.full_chains, opts);
+    for (auto& m : plan.masked) plan.masked_names.insert(m.first);
     plan.snippets = scene_snippets(scene, flags);
     plan.affine_rays = plan_affine_rays(values, plan.snippets, plan.full_chains, opts, &plan.affine_rays_refused_because);
     // Deferred loop updates (glsl_translate.h) and the first-trip copies of the intersection-material snippets (ptl_trace.tpl PTL_FIRST_TRIP)
@@ -973,25 +803,18 @@ BuildPlan plan_build(const Scene& scene, const CodegenFlags& flags, const Kernel
 // ------------------------------------------------------------------------------------------
 
 // GLSL -> C++ as this build wants it.  `file_scope`: a library text, whose function definitions become PTL_FN (force-inlined) like the rest of the kernel.
-std::string translate_snippet(const BuildPlan& plan, const std::string& glsl, bool file_scope = false) {
-    std::string cxx = translate_glsl(glsl, plan.defer_loop_updates, file_scope);
-    if (plan.unroll_bounds.empty()) return cxx;
-    constexpr int kUnrollLimit = 16;
-    static const std::regex loop(R"(for \(int (\w+) = 0; (\w+) < (\w+); (\w+)\+\+\) \{)");
-    std::string out;
-    auto begin = std::sregex_iterator(cxx.begin(), cxx.end(), loop);
-    size_t last = 0;
-    for (auto it = begin; it != std::sregex_iterator(); ++it) {
-        const std::smatch& m = *it;
-        out.append(cxx, last, (size_t)m.position() - last);
-        last = (size_t)m.position();
-        auto b = plan.unroll_bounds.find(m[3].str());
-        if (m[1] == m[2] && m[1] == m[4] && b != plan.unroll_bounds.end() && b->second >= 2 && b->second <= kUnrollLimit) out += "_Pragma(\"unroll\") ";
-    }
-    out.append(cxx, last, std::string::npos);
-    return out;
+// Then what the build compiles in (specialize_translated): the masked forms of the products with plan.masked, the unrolled counting loops.
+std::string translate_snippet(const BuildPlan& plan, const std::string& glsl, bool file_scope = false, int* unrolled = nullptr) {
+    return specialize_translated(translate_glsl(glsl, plan.defer_loop_updates, file_scope), plan.masked_names, plan.unroll_bounds, unrolled);
 }
 std::string translate_snippet(const BuildPlan& plan, const SceneSnippet& s) { return translate_snippet(plan, s.glsl(), s.kind == SceneSnippet::Library); }
+
+// The statements the generator writes itself: a callee that multiplies by matrix `m` / the product `m * operand`, in the masked form where
+// the build knows the matrix's zero / unit pattern (KernelOptions::mask_zero_elements).
+std::string masked_call(const BuildPlan& plan, const std::string& callee, const std::string& m) { return plan.masked_names.count(m) ? masked_callee(callee, m) : callee; }
+std::string masked_product(const BuildPlan& plan, const std::string& m, const std::string& operand) {
+    return plan.masked_names.count(m) ? masked_callee("ptl_mul_m", m) + "(" + m + ", " + operand + ")" : m + " * " + operand;
+}
 
 // The entry variants of a build as the names the device files' sections go by (select_sections); the entry over slices brings the slices entry along.
 // (No section asks for one of the two refine names today -- their text is a whole file, and fills a slot: emit_refine_entry.)
@@ -1154,11 +977,12 @@ std::pair<StringStorage, StringStorage> emit_materials(const Scene& scene, const
         defines.add_string("#define " + m1 + " (USER_MATERIAL_OFFSET + " + std::to_string(counter++) + ")\n");
         defines.add_string("#define " + m2 + " (USER_MATERIAL_OFFSET + " + std::to_string(counter++) + ")\n");
         // material_teleport(hit, r, M) (library.glsl:366-379) spelled as its body: behind the function parameter the product with M is out of
-        // reach of the zero / unit patterns (apply_zero_masks rewrites `transform(<uniform>, ..)` by name) -- the same two calls, same values
+        // reach of the zero / unit patterns (a masked form names the uniform: masked_call) -- the same two calls, same values
+        auto teleport = [&](const std::string& m) { return "return material_teleport_transformed(" + masked_call(plan, "transform", m) + "(" + m + ", r), hit.n);"; };
         processing.add_string("} else if (i.material == " + m1 + ") {\n");
-        processing.add_string("return material_teleport_transformed(transform(" + teleport_name(a, b) + ", r), hit.n);");
+        processing.add_string(teleport(teleport_name(a, b)));
         processing.add_string("} else if (i.material == " + m2 + ") {\n");
-        processing.add_string("return material_teleport_transformed(transform(" + teleport_name(b, a) + ", r), hit.n);");
+        processing.add_string(teleport(teleport_name(b, a)));
     }
     if (opts.material_table != 0) defines.add_string(material_table_text(table, opts.material_table));
     // The prelude needs the uniform accessors, so the library header goes after the uniform
@@ -1198,14 +1022,14 @@ StringStorage emit_intersection_functions(const Scene& scene, const BuildPlan& p
 // teleport material of a portal's side ("": a plain plane).  With a derived entry `d` the unit normal and both is_collinear verdicts come
 // from the prologue kernel (emit_derive evaluates exactly the expressions of the plain form).  The first form takes the transformed origin
 // of this test from the prologue too, through the `_o` variants of the cull and the plane test.
-void emit_plane_test(StringStorage& s, const std::string& p, const std::string& m, int side, const std::string& material, const DerivedPlane* d, bool first_form) {
+void emit_plane_test(StringStorage& s, const BuildPlan& plan, const std::string& p, const std::string& m, int side, const std::string& material, const DerivedPlane* d, bool first_form) {
     const bool portal = !material.empty();
     const std::string inv = inverse_name(m), o = first_form ? "_o" : "";
     const std::string origin = first_form ? ", PTL_U.ptl_dvo_" + p + "_" + std::to_string(side) : "";
-    s.add_string("if (!ptl_plane_cull" + o + "(r, " + inv + origin + ", PTL_BEST_T(i))) {\n");
+    s.add_string("if (!" + masked_call(plan, "ptl_plane_cull" + o, inv) + "(r, " + inv + origin + ", PTL_BEST_T(i))) {\n");
     std::string back;  // is_inside's `back`: the plane is seen from behind
     if (d) {
-        s.add_string("hit = plane_intersect_derived" + o + "(r, " + inv + ", PTL_U." + d->member + "_nrm, flipped" + origin + ");\n");
+        s.add_string("hit = " + masked_call(plan, "plane_intersect_derived" + o, inv) + "(r, " + inv + ", PTL_U." + d->member + "_nrm, flipped" + origin + ");\n");
         back = "((PTL_U." + d->member + "_col >> (flipped ? 1 : 0)) & 1) != 0";
     } else {
         s.add_string(std::string("normal = ") + (side == 0 ? "-" : "") + "get_normal(" + normal_name(m) + ");\n");
@@ -1226,7 +1050,7 @@ StringStorage emit_intersections(const Scene& scene, const BuildPlan& plan, cons
         const Object& o = scene.objects[pos];
         std::string p = std::to_string(pos);
         auto transformed = [&](const std::string& inv) {
-            s.add_string("transformed_ray = transform(" + inv + ", r);\nlen = length(transformed_ray.d);\ntransformed_ray = normalize_ray(transformed_ray);");
+            s.add_string("transformed_ray = " + masked_call(plan, "transform", inv) + "(" + inv + ", r);\nlen = length(transformed_ray.d);\ntransformed_ray = normalize_ray(transformed_ray);");
         };
         if (o.kind != Object::DebugMatrix) {
             if (o.in_subspace == Subspace::Normal) s.add_string("if (r.in_subspace == false) {");
@@ -1243,7 +1067,7 @@ StringStorage emit_intersections(const Scene& scene, const BuildPlan& plan, cons
                 const DerivedPlane* derived = nullptr;
                 for (auto& d : plan.derived)
                     if (d.object == (int)pos && d.side == side && !derived) derived = &d;
-                emit_plane_test(s, p, matrix_name(scene, side == 0 ? o.m0 : o.m1, o), side, material, derived, first_form);
+                emit_plane_test(s, plan, p, matrix_name(scene, side == 0 ? o.m0 : o.m1, o), side, material, derived, first_form);
             };
             if (!o.portal) {
                 test(0, "");
@@ -1281,8 +1105,8 @@ StringStorage emit_derive(const Scene& scene, const BuildPlan& plan, const Kerne
         for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
             const Object& o = scene.objects[pos];
             if (o.kind != Object::Flat) continue;
-            s.add_string("    out->ptl_dvo_" + std::to_string(pos) + "_0 = " + inverse_name(matrix_name(scene, o.m0, o)) + " * out->ptl_dv_origin;\n");
-            if (o.portal) s.add_string("    out->ptl_dvo_" + std::to_string(pos) + "_1 = " + inverse_name(matrix_name(scene, o.m1, o)) + " * out->ptl_dv_origin;\n");
+            s.add_string("    out->ptl_dvo_" + std::to_string(pos) + "_0 = " + masked_product(plan, inverse_name(matrix_name(scene, o.m0, o)), "out->ptl_dv_origin") + ";\n");
+            if (o.portal) s.add_string("    out->ptl_dvo_" + std::to_string(pos) + "_1 = " + masked_product(plan, inverse_name(matrix_name(scene, o.m1, o)), "out->ptl_dv_origin") + ";\n");
         }
     }
     for (auto& d : plan.derived) {
@@ -1292,7 +1116,7 @@ StringStorage emit_derive(const Scene& scene, const BuildPlan& plan, const Kerne
     }
     if (!plan.hoisted_prologue.empty()) {
         s.add_string("    // uniform-only work of the scene snippets (host/glsl_hoist.h)\n");
-        s.add_string(translate_glsl(plan.hoisted_prologue, false));
+        s.add_string(specialize_translated(translate_glsl(plan.hoisted_prologue, false), plan.masked_names, {}));  // (its loops stay rolled)
     }
     return s;
 }
@@ -1381,7 +1205,9 @@ StringStorage emit_skybox_processing(const Scene& scene, const BuildPlan&, const
 bool has_unrolled_snippet_loop(const BuildPlan& plan) {
     for (const SceneSnippet& s : plan.snippets) {
         if (s.kind != SceneSnippet::IntersectionMaterial) continue;
-        if (names_identifier(s.filtered, {"for", "while"}) && translate_snippet(plan, s).find("_Pragma(\"unroll\")") != std::string::npos) return true;
+        int unrolled = 0;
+        if (names_identifier(s.filtered, {"for", "while"})) translate_snippet(plan, s.glsl(), false, &unrolled);
+        if (unrolled > 0) return true;
     }
     return false;
 }
@@ -1465,7 +1291,6 @@ GeneratedKernel generate_kernel_source(const Scene& scene, const CodegenFlags& f
     GeneratedKernel gk = describe_kernel(plan, opts);
     gk.source = std::move(body.storage);
     gk.line_numbers = std::move(body.line_numbers);
-    apply_zero_masks(gk.source, gk.masked);
     return gk;
 }
 

@@ -124,8 +124,10 @@ struct KernelOptions {
     std::map<std::string, int> baked_options;
     // A matrix uniform that stays a run-time value (nothing baked, only Bool / Int baked, animated within the clip, demoted) still has a ZERO
     // PATTERN -- portal matrices are mostly translations and quarter turns -- and the pattern survives where the values move.  With this on
-    // the generator records the pattern of every such matrix (GeneratedKernel::masked, `#define PTL_MASK_<name>`) and writes the
-    // `transform(<name>, ..)` calls of the snippets and the generated plane tests in their masked forms (device/ptl_glsl.h `ptl_mul_m`):
+    // the generator records the pattern of every such matrix (GeneratedKernel::masked, `#define PTL_MASK_<name>`) and writes every
+    // call that multiplies by it in its masked form (device/ptl_glsl.h `ptl_mul_m`) where the text is made: the plane tests, transforms and
+    // prologue products it generates spell it themselves, `transform(<name>, ..)` and `<name> * v` of a snippet get it from the token pass
+    // behind the translator (glsl_translate.h `specialize_translated`) -- nothing walks over the assembled source:
     // the terms with a zero element are neither executed nor loaded -- what a baked matrix gets from ptl_mterm.  Same deviation as there
     // (non-finite vector components); the renderer rebuilds when a masked element stops being zero.  Off for contract 1 and the tolerance mode.
     bool mask_zero_elements = false;

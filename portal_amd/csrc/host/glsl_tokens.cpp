@@ -220,6 +220,29 @@ std::vector<std::pair<size_t, size_t>> TokenView::split_top_level(size_t from, s
     return parts;
 }
 
+void defined_functions(const std::string& glsl, std::set<std::string>& names) {
+    const std::vector<Token> toks = tokenize_glsl(glsl);
+    const TokenView s(toks);
+    int depth = 0;
+    for (size_t i = 0; i < s.n(); ++i) {
+        if (s.is(i, "{")) ++depth;
+        else if (s.is(i, "}")) --depth;
+        else if (depth == 0 && s.is(i, "(") && s.ident(i - 1) && s.ident(i - 2)) names.insert(s[i - 1].text);
+    }
+}
+
+void functions_with_out_params(const std::string& glsl, std::set<std::string>& names) {
+    const std::vector<Token> toks = tokenize_glsl(glsl);
+    const TokenView s(toks);
+    for (size_t i = 0; i < s.n(); ++i) {
+        if (!((s.ident(i, "out") || s.ident(i, "inout")) && s.ident(i + 1))) continue;
+        int depth = 0;
+        size_t open = i;  // back to the `(` that opens this parameter list
+        while (open-- > 0 && !(s.is(open, "(") && depth == 0)) depth += s.is(open, ")") ? 1 : s.is(open, "(") ? -1 : 0;
+        if (s.ident(open - 1)) names.insert(s[open - 1].text);  // (no such `(`: `open` is past every index, and nothing is one)
+    }
+}
+
 static bool is_code(const Token& t) { return t.kind != Token::Space && t.kind != Token::Comment; }
 
 size_t next_code(const std::vector<Token>& stream, size_t k) {

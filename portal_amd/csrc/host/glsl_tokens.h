@@ -1,8 +1,9 @@
 // glsl_tokens.h -- the lexer and the token view shared by every pass over the GLSL snippets of a scene: the GLSL -> C++ rewrite
 // (glsl_translate.cpp), the distance bound (glsl_bound.cpp), the uniform-work hoister (glsl_hoist.cpp), the affine-rays scan
-// (glsl_affine.cpp) and the generator's "does it name X" questions (codegen.cpp).
+// (glsl_affine.cpp), the masked forms and unroll pragmas of a build (glsl_masks.cpp) and the generator's "does it name X" questions (codegen.cpp).
 #pragma once
 #include <initializer_list>
+#include <set>
 #include <string>
 #include <utility>
 #include <vector>
@@ -34,6 +35,11 @@ std::vector<int> swizzle_indices(const std::string& name);
 
 // Is one of `names` an identifier of `glsl` (not part of a comment, a directive or a longer name)?
 bool names_identifier(const std::string& glsl, std::initializer_list<const char*> names);
+
+// The names of the functions a GLSL text defines (`type name(` outside all braces), and of those it defines with an `out` / `inout`
+// parameter (the qualifier in front of a type; the name in front of the `(` that opens its list).  Comments and directives are not code.
+void defined_functions(const std::string& glsl, std::set<std::string>& names);
+void functions_with_out_params(const std::string& glsl, std::set<std::string>& names);
 
 constexpr unsigned token_kinds(std::initializer_list<Token::Kind> kinds) {  // a set of kinds, for TokenView to drop
     unsigned bits = 0;

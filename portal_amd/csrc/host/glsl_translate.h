@@ -12,6 +12,7 @@
 //   * identifiers that are C++ keywords are renamed
 //   * the tagged-line filter of src/gui/scene.rs:1065-1107 (!FOR_NUMBER! etc.)
 #pragma once
+#include <map>
 #include <set>
 #include <string>
 #include <vector>
@@ -49,6 +50,23 @@ std::string filter_tagged_lines(const std::string& text, const CodegenFlags& fla
 // of the kernel.  Without it they are plain inline members that LLVM's bottom-up inliner happens to inline and its module inliner does not
 // (a call with `this` then keeps the tracer object in scratch).
 std::string translate_glsl(const std::string& glsl, bool defer_loop_updates = true, bool force_inline_definitions = false);
+
+// (glsl_masks.cpp)  What the values a build compiles in do to a snippet, on the output of translate_glsl and line-preserving like it.
+// Token shapes, so white space, comments and line breaks between their tokens do not matter, and comment text is never touched.
+//   * `masked`: the matrix uniforms whose zero / unit pattern the build knows (KernelOptions::mask_zero_elements).  The calls that multiply
+//     by one of them get their masked forms (device/ptl_glsl.h):
+//       transform ( M ,    -> ptl_transform_m<PTL_MASK_M>(M,                  (`transform` a name of its own, not a member)
+//       M * <operand>      -> ptl_mul_m<PTL_MASK_M>(M, <operand>)            (`(b0_mat_inv * pos).z`; the deferred loop updates' own text)
+//     M is the whole left operand: not a member, nothing multiplicative (`*`, `/`, `%`) and no unary sign in front of it, and `*` is not
+//     `*=`.  The operand is one unary expression -- a parenthesised group, or a name with its call `(..)`, index `[..]`, member `.m`
+//     (`.sw<..>()`) and `->m` suffixes -- that starts with neither a sign nor a digit; the walk goes on inside it, so `A * (B * v)` nests.
+//     ptl_mul_m falls back to the plain product for anything but a vec4.  Every other use of the matrix (behind a sign, copied into a
+//     local, handed to a function) keeps the full chain: correct, just not shortened.
+//   * `unroll_bounds`: the Int uniforms baked into the build.  `for (int I = 0; I < B; I++) {` with one of them, 2 <= B <= 16, as its
+//     bound gets `_Pragma("unroll")` in front; `*unrolled` receives how many loops did.
+std::string specialize_translated(const std::string& cxx, const std::set<std::string>& masked, const std::map<std::string, int>& unroll_bounds, int* unrolled = nullptr);
+// The masked spelling of a callee that multiplies by matrix M: `callee<PTL_MASK_M>`, and `ptl_transform_m<PTL_MASK_M>` for `transform`.
+std::string masked_callee(const std::string& callee, const std::string& matrix);
 
 // Refuses (std::runtime_error) a scene in which passing `out` / `inout` arguments by reference could differ from GLSL's copy in /
 // copy out: a mutable global handed to a function that also names it, or one variable handed to two out parameters of a call.

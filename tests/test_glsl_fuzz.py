@@ -198,7 +198,7 @@ def test_random_glsl_expressions_over_uniforms_survive_the_hoister(pa, tmp_path,
     w, h = 4 * N_EXPR, 12
     scene = pa.Scene.from_file(str(path))
     # flags 1 (Bool / Int baked): the zero patterns of tilt_mat / back_mat are compiled in and the random products over them are rewritten
-    # into their masked forms by shape (codegen.cpp::apply_zero_masks) -- in the snippet and in what the hoister moved to the prologue
+    # into their masked forms by shape (glsl_masks.cpp::specialize_translated) -- in the snippet and in what the hoister moved to the prologue
     source = scene.generate_source(flags)
     assert source.count("PTL_U.ptl_hv") >= 10 and "ptl_tab_ok_" in source and "for (int ptl_k = 0;" in source
     if flags:

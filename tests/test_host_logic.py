@@ -977,6 +977,135 @@ def test_masked_product_rewrite_follows_the_shape_of_the_operand(pa):
     assert np.array_equal(frames["masked"].view(np.uint32), frames["full"].view(np.uint32))
 
 
+def _basics_with(pa, snippet, library=None, int_uniforms=()):
+    """scenes/basics.ron with one intersection-material snippet, optionally a library text in front of its own and Int uniforms"""
+    text = open(pa.scene_path("basics")).read()
+    text = text.replace("intersection_materials: ([]),", 'intersection_materials: ([\n        (\n            name: "shapes",\n            data: ((("' + snippet + '"))),\n        ),\n    ]),')
+    if library is not None:
+        text = text.replace('library: ([\n', 'library: ([\n        (\n            name: "extra",\n            data: (("' + library + '")),\n        ),\n', 1)
+    for name, value in int_uniforms:
+        text = text.replace("uniforms: ([\n", 'uniforms: ([\n        (\n            name: "%s",\n            data: Int((\n                min: Some(1),\n                max: Some(20),\n                value: %d,\n            )),\n        ),\n' % (name, value), 1)
+    return text
+
+
+def _snippet_body(src):
+    body = src[src.index("intersect_material_0(Ray r, float ptl_far) {"):]
+    return body[:body.index("return result;")]
+
+
+_RESULT_TAIL = """SceneIntersectionWithMaterial result = SceneIntersectionWithMaterial(scene_intersection_none, material_empty());
+if (s > 1e30) result.scene = SceneIntersection(CUSTOM_MATERIAL, SurfaceIntersection(true, 1., 0., 0., vec3(0., 0., 1.)), false);
+return result;"""
+
+_PRODUCT_LAYOUTS = """vec4 p = r.o;
+// note: portal_a_mat_inv * p and transform(portal_b_mat, r) are what the lines below spell out
+vec4 a = portal_a_mat_inv * /* to plane */ p;
+vec4 d = portal_b_mat\t* p;
+vec4 b = portal_a_mat * (portal_b_mat_inv *
+ p);
+Ray q2 = transform(portal_b_mat
+ , r);
+vec4 c = portal_b_mat*p;
+Ray q1 = transform( portal_b_mat , r);
+float s = dot(a + b + c + d + q1.o + q2.o, vec4(1.));
+""" + _RESULT_TAIL
+
+
+def test_masked_forms_are_token_shapes_whatever_the_layout(pa):
+    """glsl_masks.cpp `specialize_translated`: white space, comments and line breaks between the tokens of `M * operand` / `transform(M,` do
+    not matter, comment text is never touched, and every line break stays where it was -- the line map of the masked source is the one of
+    the FLAG_NO_ZERO_MASKS source.  The masked source compiles for gfx950 and its host build draws the bits of the full products."""
+    from oracle import host_build as hb
+
+    flags = pa.FLAG_SPECIALIZE_INTS | pa.FLAG_NO_FIRST_TRIP | pa.FLAG_NO_UNIFORM_HOIST
+    text = _basics_with(pa, _PRODUCT_LAYOUTS)
+    sources, owners = {}, {}
+    for label, f in (("masked", flags), ("full", flags | pa.FLAG_NO_ZERO_MASKS)):
+        scene = pa.Scene.from_text(text)
+        sources[label] = scene.generate_source(f)
+        owners[label] = [scene.source_line_owner(ln) for ln in range(1, sources[label].count("\n") + 2)]
+    body = _snippet_body(sources["masked"])
+    for want in ("\n// note: portal_a_mat_inv * p and transform(portal_b_mat, r) are what the lines below spell out\n",
+                 "\nvec4 a = ptl_mul_m<PTL_MASK_portal_a_mat_inv>(portal_a_mat_inv, /* to plane */ p);\n",
+                 "\nvec4 d = ptl_mul_m<PTL_MASK_portal_b_mat>(portal_b_mat, p);\n",
+                 "\nvec4 b = ptl_mul_m<PTL_MASK_portal_a_mat>(portal_a_mat, (ptl_mul_m<PTL_MASK_portal_b_mat_inv>(portal_b_mat_inv,\n p)));\n",
+                 "\nRay q2 = ptl_transform_m<PTL_MASK_portal_b_mat>(portal_b_mat\n , r);\n",
+                 "\nvec4 c = ptl_mul_m<PTL_MASK_portal_b_mat>(portal_b_mat, p);\n",
+                 "\nRay q1 = ptl_transform_m<PTL_MASK_portal_b_mat>( portal_b_mat , r);\n"):
+        assert want in body, (want, body)
+    # the masked source is longer by the lines of its uniform slot that the other has not -- `#define PTL_MASK_<name>`, and `#define PTL_AFFINE_RAYS 1`,
+    # which only a build that shortens products gets -- all in front of the first scene text, and by nothing else
+    assert "\n#define PTL_AFFINE_RAYS 1\n" in sources["masked"] and "\n#define PTL_AFFINE_RAYS 1\n" not in sources["full"]
+    defines = sources["masked"].count("\n#define PTL_MASK_") + 1
+    assert defines > 1 and sources["masked"].count("\n") == sources["full"].count("\n") + defines
+    first = next(ln for ln, o in enumerate(owners["full"]) if o)
+    assert owners["masked"][first + defines:] == owners["full"][first:] and not any(owners["masked"][:first + defines])
+    mine = [ln for ln, o in enumerate(owners["masked"]) if o and o[1] == "shapes"]
+    assert len(mine) == _PRODUCT_LAYOUTS.count("\n") + 1 and [owners["masked"][ln][2] for ln in mine] == list(range(1, len(mine) + 1))
+    lines = sources["masked"].split("\n")
+    assert lines[mine[1]] == _PRODUCT_LAYOUTS.split("\n")[1] and lines[mine[-1]].startswith("return result;")
+    frames = {}
+    for label, f in (("masked", flags), ("full", flags | pa.FLAG_NO_ZERO_MASKS)):
+        sc = pa.Scene.from_text(text)
+        r = pa.SceneRenderer(sc, device=-1, flags=f)  # hiprtc for gfx950
+        assert r.code_object()[:4] == b"\x7fELF"
+        r.set_option("render_depth", 6)
+        frames[label] = hb.host_kernel_for(r, sc, 48, 27, flags=f).render(48, 27)["rgba32f"].copy()
+    assert np.array_equal(frames["masked"].view(np.uint32), frames["full"].view(np.uint32))
+
+
+def test_products_of_other_shapes_stay_as_written(pa):
+    """... and what is not `M * operand` with M the whole left operand keeps its text: M behind another factor, an operand or a matrix behind a
+    sign, a member that is spelled like the matrix, `*=`, and names that merely contain a masked name.  (Text only: not all of it is GLSL.)"""
+    lines = ["vec4 d = p.x * portal_a_mat * p;", "vec4 e = portal_a_mat * -p;", "vec4 f = -portal_a_mat * p;", "vec4 g = s.portal_a_mat * p;", "portal_b_mat *= m;",
+             "vec4 h = portal_a_mat_x * p;", "vec4 k = my_portal_a_mat * p;", "vec4 l = (-portal_a_mat_inv * p) + (+portal_b_mat * p);"]
+    code = "vec4 p = r.o;\n" + "\n".join(lines) + "\nfloat s = dot(d + e, vec4(1.));\n" + _RESULT_TAIL
+    for flags in (pa.FLAG_SPECIALIZE_INTS | pa.FLAG_NO_FIRST_TRIP, pa.FLAG_SPECIALIZE_INTS | pa.FLAG_NO_FIRST_TRIP | pa.FLAG_NO_UNIFORM_HOIST):
+        src = pa.Scene.from_text(_basics_with(pa, code)).generate_source(flags)
+        assert "#define PTL_MASK_portal_a_mat " in src and "#define PTL_MASK_portal_b_mat " in src
+        body = _snippet_body(src)
+        for line in lines:
+            assert "\n" + line + "\n" in body, (line, body)
+        assert "ptl_mul_m<" not in body and "ptl_transform_m<" not in body
+
+
+def test_counting_loops_over_a_baked_int_are_unrolled_whatever_their_layout(pa):
+    """`for (int I = 0; I < B; I++) {` with B a baked Int uniform of 2 .. 16 gets `_Pragma("unroll")` -- a token shape, so the loop may be written
+    without a single blank; another variable in the condition, a bound of 17 or FLAG_NO_UNROLL leave the loop as it is."""
+    code = """float s = 0.;
+for (int i = 0; i < n_u; i++) { s += 1.; }
+for(int i=0;i<n_u;i++){ s += 2.; }
+int j = 0;
+for (int i = 0; j < n_u; i++) { j += 2; }
+for (int i = 0; i < big_u; i++) { s += 3.; }
+""" + _RESULT_TAIL
+    text = _basics_with(pa, code, int_uniforms=(("n", 3), ("big", 17)))
+    flags = pa.FLAG_SPECIALIZE_INTS | pa.FLAG_NO_FIRST_TRIP | pa.FLAG_NO_UNIFORM_HOIST
+    src = pa.Scene.from_text(text).generate_source(flags)
+    assert "#define n_u (3)" in src and "#define big_u (17)" in src
+    body = _snippet_body(src)
+    assert '\n_Pragma("unroll") for (int i = 0; i < n_u; i++) {' in body and '\n_Pragma("unroll") for(int i=0;i<n_u;i++){' in body
+    assert "\nfor (int i = 0; j < n_u; i++) {" in body and "\nfor (int i = 0; i < big_u; i++) {" in body and body.count("_Pragma") == 2
+    assert "_Pragma" not in _snippet_body(pa.Scene.from_text(text).generate_source(flags | pa.FLAG_NO_UNROLL))
+    assert "_Pragma" not in _snippet_body(pa.Scene.from_text(text).generate_source(pa.FLAG_NO_FIRST_TRIP | pa.FLAG_NO_UNIFORM_HOIST))  # (nothing baked)
+
+
+def test_out_parameters_are_read_from_code_not_from_comments(pa):
+    """glsl_tokens.h `functions_with_out_params`: the word `out` in a comment -- in front of a function, inside its parameter list -- makes no
+    function one with out parameters, so the distance bound goes into a snippet that calls it exactly as without the comment; a real `inout`
+    is found with a comment between the qualifier and the type, and keeps the snippet as written."""
+    snippet = _BOUND_OK.replace("a_mat", "portal_a_mat")
+    plain = "int inside_a(vec4 pos, float u,\n    float v, int size) { return size; }\n"
+    commented = "// fade out the edge\nint inside_a(vec4 pos, float u,  // fade out toward v\n    float v, int size) { return size; }\n"
+    written = "int inside_a(vec4 pos, float u,\n    float v, inout /* counted */ int size) { return size; }\n"
+    bounds = {}
+    for label, library in (("plain", plain), ("commented", commented), ("written", written)):
+        src = pa.Scene.from_text(_basics_with(pa, snippet, library=library)).generate_source(pa.FLAG_BOUNDED_SNIPPETS)
+        assert "PTL_FN int inside_a(vec4 pos, float u," in src, label
+        bounds[label] = src.count("&& !(hit_a.t > ptl_far)")
+    assert bounds["plain"] >= 1 and bounds["commented"] == bounds["plain"] and bounds["written"] == 0, bounds
+
+
 def test_code_object_cache_rejects_foreign_files_and_names_the_toolchain(pa, tmp_path, monkeypatch):
     """The cache key covers source + options + the hiprtc library that compiled it; a truncated or non-ELF file under that name is
     ignored and replaced by a fresh build."""
