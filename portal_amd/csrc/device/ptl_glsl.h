@@ -212,6 +212,8 @@ PTL_FN float sqrt(float x) { return ptl_sqrt_model(x); }
 PTL_FN float ptl_div(float a, float b) { return a / b; }
 #else
 PTL_FN float ptl_div(float a, float b) { return a * ptl_rcp(b); }
+// (a quotient by a frame-uniform divisor may be written as the product with ptl_rcp(divisor) taken from the prologue kernel's table: ptl_trace.tpl)
+#define PTL_DIV_IS_PRODUCT 1
 #endif
 PTL_FN float ptl_div(float a, int b) { return ptl_div(a, (float)b); }
 PTL_FN float ptl_div(int a, float b) { return ptl_div((float)a, b); }

@@ -152,9 +152,22 @@ PTL_FN void derive(ptl_uniform_block* out) {
     out->ptl_dv_tan_half_view = tan(ptl_div(_view_angle, 2.0f));
     out->ptl_dv_pixel_size = ptl_rcp(min(_resolution.x, _resolution.y));
     out->ptl_dv_half_resolution = _resolution / 2.0f;
+    // ... and the arithmetic of the pixel prologue and of a path's final hit whose operands are all builtins: every wave would repeat it
+    // on 64 identical lanes.  Each member is the expression the pixel path spells (under #else there), operand for operand.
+    out->ptl_dv_eye = eye_row(_camera_scale);
+    out->ptl_dv_eye_left = eye_row(_left_eye_scale);
+    out->ptl_dv_eye_right = eye_row(_right_eye_scale);
+    for (int k = 0; k < PTL_AA_TABLE && k < _aa_count; k++) out->ptl_dv_aa_jitter[k] = quasi_random(_aa_start + k) * out->ptl_dv_pixel_size * 2.0f;
+    out->ptl_dv_rcp_aa_count = ptl_rcp(float(_aa_count));
+    out->ptl_dv_rcp_t_range = ptl_rcp(_t_end - _t_start);
 #endif
 //%derive//%
 }
+
+#ifdef PTL_DERIVED_BUILTINS
+// What the final hit of a path needs of an eye's camera scale: (1 / scale, 1 / max(scale, 1e-6), _t_start * scale, _t_end * scale)
+PTL_FN vec4 eye_row(float scale) { return vec4(ptl_rcp(scale), ptl_rcp(max(scale, 1e-6f)), _t_start * scale, _t_end * scale); }
+#endif
 
 // Material id -> what happens to the path. (reference shell: src/frag.glsl:33-50)
 PTL_FN MaterialProcessing material_process(Ray r, const SceneIntersection& i) {
@@ -265,6 +278,31 @@ PTL_FN void ptl_pass_account(const RayTraceResult& path) {
 }
 //%end
 
+// The camera scale of the eye a path belongs to, as the bounce loop is handed it: with derived builtins also that eye's row of the
+// prologue kernel's table (eye_row above), picked with the wave-level eye decision of camera_origin.
+struct EyeScale {
+    float scale;
+#ifdef PTL_DERIVED_BUILTINS
+    vec4 row;
+#endif
+};
+// depth of the final hit, the two darkening thresholds and the darkening ramp (frag.glsl:135-139).  Where a / b is a * ptl_rcp(b) the
+// table's reciprocal takes the place of ptl_rcp(b): the same product, the same roundings one after the other.
+#if defined(PTL_DERIVED_BUILTINS) && defined(PTL_DIV_IS_PRODUCT)
+PTL_FN float eye_depth(float all_t, const EyeScale& eye) { return all_t * eye.row.y; }
+PTL_FN float eye_gray(float t, const EyeScale& eye) { return t * PTL_U.ptl_dv_rcp_t_range * eye.row.x; }
+#else
+PTL_FN float eye_depth(float all_t, const EyeScale& eye) { return ptl_div(all_t, max(eye.scale, 1e-6f)); }
+PTL_FN float eye_gray(float t, const EyeScale& eye) { return ptl_div(ptl_div(t, _t_end - _t_start), eye.scale); }
+#endif
+#ifdef PTL_DERIVED_BUILTINS
+PTL_FN float eye_t_start(const EyeScale& eye) { return eye.row.z; }
+PTL_FN float eye_t_end(const EyeScale& eye) { return eye.row.w; }
+#else
+PTL_FN float eye_t_start(const EyeScale& eye) { return _t_start * eye.scale; }
+PTL_FN float eye_t_end(const EyeScale& eye) { return _t_end * eye.scale; }
+#endif
+
 PTL_FN float normalize_depth_value(float depth) {  // frag.glsl:80-84
     float depth_min = min(_depth_map_min, _depth_map_max);
     float depth_max = max(_depth_map_min, _depth_map_max);
@@ -293,9 +331,9 @@ PTL_FN vec3 sample_depth_gradient(float depth) {  // frag.glsl:101-104
 // its result), false when `r` / `current_color` / `all_t` have been advanced to the next segment.  (frag.glsl:113-156)
 #ifdef PTL_FIRST_TRIP
 // (`first_form`, wave-uniform: r still starts at the camera, so the snippets run in their first-trip form -- see scene_intersect_material_process_first)
-PTL_FN bool trace_segment(Ray& r, vec3& current_color, float& all_t, float camera_scale, const vec3& not_found_color, RayTraceResult& out, bool first_form) {
+PTL_FN bool trace_segment(Ray& r, vec3& current_color, float& all_t, const EyeScale& camera_scale, const vec3& not_found_color, RayTraceResult& out, bool first_form) {
 #else
-PTL_FN bool trace_segment(Ray& r, vec3& current_color, float& all_t, float camera_scale, const vec3& not_found_color, RayTraceResult& out) {
+PTL_FN bool trace_segment(Ray& r, vec3& current_color, float& all_t, const EyeScale& camera_scale, const vec3& not_found_color, RayTraceResult& out) {
 #endif
     r = ptl_affine(r);  // PTL_AFFINE_RAYS: o.w = 1 and d.w = 0 spelled once per trip (ptl_library.h); otherwise nothing
 #if defined(PTL_BOUNDED_SNIPPETS) && !defined(PTL_SNIPPETS_FIRST)
@@ -360,10 +398,10 @@ PTL_FN bool trace_segment(Ray& r, vec3& current_color, float& all_t, float camer
     }
     current_color *= m.mul_to_color;
     if (m.is_final) {
-        float depth = ptl_div(all_t, max(camera_scale, 1e-6f));
-        if (all_t > _t_start * camera_scale && _darken_by_distance == 1) {  // fade to black with distance
-            if (all_t > _t_end * camera_scale) all_t = _t_end * camera_scale;
-            float gray_t = ptl_div(ptl_div(all_t - _t_start * camera_scale, _t_end - _t_start), camera_scale);
+        float depth = eye_depth(all_t, camera_scale);
+        if (all_t > eye_t_start(camera_scale) && _darken_by_distance == 1) {  // fade to black with distance
+            if (all_t > eye_t_end(camera_scale)) all_t = eye_t_end(camera_scale);
+            float gray_t = eye_gray(all_t - eye_t_start(camera_scale), camera_scale);
 //%if passes
             out = RayTraceResult{color(0.0f, 0.0f, 0.0f) * sqr(sqr(gray_t)) + current_color * sqr(sqr(1.0f - gray_t)), depth, true, 0u, PTL_PATH_FINAL};
 //%else
@@ -388,9 +426,9 @@ PTL_FN bool trace_segment(Ray& r, vec3& current_color, float& all_t, float camer
 // soon as a ballot over `alive` comes back empty -- one scalar compare per trip, no lane ever waits for a loop counter it
 // no longer needs.  (-DPTL_NO_WAVE_LOOP: the per-lane form with returns, which the compiler turns into the same shape.)
 #ifdef PTL_FIRST_TRIP
-PTL_FN RayTraceResult ray_tracing(Ray r, float camera_scale, bool origin_is_camera) {  // origin_is_camera: r.o is PTL_U.ptl_dv_origin, bit for bit
+PTL_FN RayTraceResult ray_tracing(Ray r, const EyeScale& camera_scale, bool origin_is_camera) {  // origin_is_camera: r.o is PTL_U.ptl_dv_origin, bit for bit
 #else
-PTL_FN RayTraceResult ray_tracing(Ray r, float camera_scale) {
+PTL_FN RayTraceResult ray_tracing(Ray r, const EyeScale& camera_scale) {
 #endif
     //%skybox_processing//%
 
@@ -616,18 +654,22 @@ PTL_FN vec4 camera_times(const mat4& camera_matrix, int which_eye, vec4 v, bool 
 
 #ifdef PTL_DERIVED_BUILTINS
 // camera_matrix * (0, 0, 0, 1), which the prologue kernel has left behind the uniforms; read like camera_times reads the matrix.
-PTL_FN vec4 camera_origin(int which_eye) {
+// `scale_row`: the same eye's row of camera-scale values (eye_row), fetched under the same decision.
+PTL_FN vec4 camera_origin(int which_eye, vec4& scale_row) {
 #if PTL_DEVICE_BUILD
     vec4 o = vec4(0.0f);
+    scale_row = vec4(0.0f);
     for (bool done = false; !done;) {
         const int eye = __builtin_amdgcn_readfirstlane(which_eye);
         if (which_eye == eye) {
             o = eye == 0 ? PTL_U.ptl_dv_origin : (eye == 1 ? PTL_U.ptl_dv_origin_left : PTL_U.ptl_dv_origin_right);
+            scale_row = eye == 0 ? PTL_U.ptl_dv_eye : (eye == 1 ? PTL_U.ptl_dv_eye_left : PTL_U.ptl_dv_eye_right);
             done = true;
         }
     }
     return o;
 #else
+    scale_row = which_eye == 0 ? PTL_U.ptl_dv_eye : (which_eye == 1 ? PTL_U.ptl_dv_eye_left : PTL_U.ptl_dv_eye_right);
     return which_eye == 0 ? PTL_U.ptl_dv_origin : (which_eye == 1 ? PTL_U.ptl_dv_origin_left : PTL_U.ptl_dv_origin_right);
 #endif
 }
@@ -640,8 +682,10 @@ PTL_FN vec3 get_color2(vec2 image_position, const mat4& camera_matrix, bool in_s
     const float Pi = 3.14159265359f;
     const float Pi05 = Pi * 0.5f;
 #ifdef PTL_DERIVED_BUILTINS
-    vec4 o = camera_origin(which_eye);
+    EyeScale eye_scale = EyeScale{camera_scale, vec4(0.0f)};
+    vec4 o = camera_origin(which_eye, eye_scale.row);
 #else
+    EyeScale eye_scale = EyeScale{camera_scale};
     vec4 o = camera_times(camera_matrix, which_eye, vec4(0.0f, 0.0f, 0.0f, 1.0f), false);
 #endif
     vec4 d;
@@ -690,9 +734,9 @@ PTL_FN vec3 get_color2(vec2 image_position, const mat4& camera_matrix, bool in_s
     }
 
 #ifdef PTL_FIRST_TRIP
-    RayTraceResult trace = ray_tracing(Ray{o, d, 1.0f, in_subspace}, camera_scale, which_eye == 0);
+    RayTraceResult trace = ray_tracing(Ray{o, d, 1.0f, in_subspace}, eye_scale, which_eye == 0);
 #else
-    RayTraceResult trace = ray_tracing(Ray{o, d, 1.0f, in_subspace}, camera_scale);
+    RayTraceResult trace = ray_tracing(Ray{o, d, 1.0f, in_subspace}, eye_scale);
 #endif
 //%if passes
     ptl_pass_account(trace);
@@ -777,22 +821,38 @@ PTL_FN vec2 quasi_random(int i) {
 // FragColor, before the GL RGBA8 conversion.
 PTL_FN vec4 shade_pixel(vec2 position) {
     PTL_PIXEL_RELAUNDER();  // the per-pixel part reads its builtins (camera matrix, projection) through scalar loads as well
-    float coef = min(_resolution.x, _resolution.y);
 #ifdef PTL_DERIVED_BUILTINS
-    vec2 uv_screen = (position - PTL_U.ptl_dv_half_resolution) / coef * 2.0f;
+    // (`.. / coef` is operator/(vec2, float): both components times ptl_rcp(coef), which is the table's pixel size)
     float pixel_size = PTL_U.ptl_dv_pixel_size;
+    vec2 from_centre = position - PTL_U.ptl_dv_half_resolution;
+    vec2 uv_screen = vec2(from_centre.x * pixel_size, from_centre.y * pixel_size) * 2.0f;
 #else
+    float coef = min(_resolution.x, _resolution.y);
     vec2 uv_screen = (position - _resolution / 2.0f) / coef * 2.0f;
     float pixel_size = ptl_rcp(min(_resolution.x, _resolution.y));
 #endif
     vec3 result = vec3(0.0f);
-    const int aa_count = _aa_count, aa_end = aa_count + _aa_start;  // read once: later reads would go through whatever the bounce loop left
-    for (int a = _aa_start; a < aa_end; a++) {
+    const int aa_count = _aa_count, aa_start = _aa_start, aa_end = aa_count + aa_start;  // read once: later reads would go through whatever the bounce loop left
+    for (int a = aa_start; a < aa_end; a++) {
         PTL_PIXEL_RELAUNDER();
+#ifdef PTL_DERIVED_BUILTINS
+        // the sample's sub-pixel offset from the prologue kernel's table, which starts at `_aa_start`; a frame with more samples than
+        // the table has rows evaluates the rest as written
+        vec2 jitter;
+        if (a - aa_start < PTL_AA_TABLE) jitter = PTL_U.ptl_dv_aa_jitter[a - aa_start];
+        else jitter = quasi_random(a) * pixel_size * 2.0f;
+        result += get_color(uv_screen + jitter);
+#else
         vec2 offset = quasi_random(a);
         result += get_color(uv_screen + offset * pixel_size * 2.0f);
+#endif
     }
+#ifdef PTL_DERIVED_BUILTINS
+    const float per_sample = PTL_U.ptl_dv_rcp_aa_count;  // (`result / float(aa_count)`: operator/(vec3, float) again)
+    result = sqrt(vec3(result.x * per_sample, result.y * per_sample, result.z * per_sample));
+#else
     result = sqrt(result / float(aa_count));
+#endif
     return vec4(result, 1.0f);
 }
 

@@ -834,7 +834,10 @@ StringStorage emit_uniforms(const Scene& scene, const BuildPlan& plan, const Ker
     // one without affine rays differ in nothing else)
     if (plan.affine_rays) s.add_string("#define PTL_AFFINE_RAYS 1\n");
     if (opts.check_affine) s.add_string("#define PTL_CHECK_AFFINE 1\n");  // (implies PTL_COUNT_SEGMENTS: the counter counts rays whose w is not 1 / 0)
-    if (opts.derived_uniforms) s.add_string("#define PTL_DERIVED_BUILTINS 1\n");
+    // (PTL_AA_TABLE: rows of the table of sub-pixel offsets, one per sample of a draw from `_aa_start` on.  The CLI's defaults are 1 and 4 samples per
+    // draw, a clip moves `_aa_start` and keeps the count (cli_video.cpp), the benchmark's workloads take 1 and 4; `--aa-count` has no upper bound, and a
+    // draw with more samples evaluates those beyond the table as written.  16 rows = 128 bytes of the block.)
+    if (opts.derived_uniforms) s.add_string("#define PTL_DERIVED_BUILTINS 1\n#define PTL_AA_TABLE 16\n");
     // (trace passes: the define in the text for the same reason, and the record the tracer fills per pixel -- include/portal_amd.h has its contract)
     if (opts.passes)
         s.add_string("#define PTL_PASSES 1\nstruct alignas(16) ptl_pass_record {\n    float depth_near;\n    unsigned int trips;\n    unsigned int final_escaped;\n    unsigned int exhausted_outside;\n};\n");
@@ -845,7 +848,9 @@ StringStorage emit_uniforms(const Scene& scene, const BuildPlan& plan, const Ker
     // written by ptl_derive_kernel (never by the host: uploads stop at uniform_block_size)
     if (opts.derived_uniforms)  // the per-pixel work that depends on the frame's builtins alone (ptl_trace.tpl derive())
         s.add_string("    vec4 ptl_dv_origin;\n    vec4 ptl_dv_origin_left;\n    vec4 ptl_dv_origin_right;\n    vec2 ptl_dv_half_resolution;\n"
-                     "    float ptl_dv_tan_half_view;\n    float ptl_dv_pixel_size;\n");
+                     "    float ptl_dv_tan_half_view;\n    float ptl_dv_pixel_size;\n"
+                     "    vec4 ptl_dv_eye;\n    vec4 ptl_dv_eye_left;\n    vec4 ptl_dv_eye_right;\n    vec2 ptl_dv_aa_jitter[PTL_AA_TABLE];\n"
+                     "    float ptl_dv_rcp_aa_count;\n    float ptl_dv_rcp_t_range;\n");
     for (auto& d : plan.derived) s.add_string("    vec3 " + d.member + "_nrm;\n    int " + d.member + "_col;\n");
     if (plan.first_trip_plane_tests > 0)
         for (size_t pos = 0; pos < scene.objects.size(); ++pos) {
