@@ -24,6 +24,14 @@
 #define PTL_DEVICE_BUILD 0
 #endif
 
+// -DPTL_SPELLED_EXITS (A/B): the text of the template and the generator before their always-executed exits were
+// thinned -- unorm8's early returns, the nearer() adoption of the first snippet's record.  Same values in every field anybody reads;
+// one define per place, so that each can be priced on its own.
+#if defined(PTL_SPELLED_EXITS)
+#define PTL_SPELLED_UNORM8 1
+#define PTL_SPELLED_ADOPTION 1
+#endif
+
 // Counters, compiled in only on request (the kernel's `segments` argument receives the sum): bounce-loop trips (PTL_COUNT_SEGMENTS: segment
 // Mray/s) or -- round 6, PTL_CHECK_AFFINE, the dynamic belt behind codegen.cpp `snippets_keep_rays_affine` -- the number of times a
 // ray half reached a place where a kernel with affine rays ASSUMES its w (the matrix-times-ray products, the bounce loop's `ptl_affine`) with
@@ -239,6 +247,26 @@ PTL_FN int min(int a, int b) { return b < a ? b : a; }
 PTL_FN int max(int a, int b) { return a < b ? b : a; }
 PTL_FN float clamp(float x, float lo, float hi) { return min(max(x, lo), hi); }
 PTL_FN int clamp(int x, int lo, int hi) { return min(max(x, lo), hi); }
+// GL fixed-point conversion of one channel (the frame store's unorm8, ptl_trace.tpl): clamp to [0,1], scale, round to nearest.
+// The spelled form is the definition -- and what the host build runs.  Its two early returns cost every pixel two compares, two exec saves
+// and two branches per channel at the very end of every wave.
+PTL_FN unsigned int ptl_unorm8_spelled(float v) {
+    if (!(v > 0.0f)) return 0u;  // also NaN
+    if (v >= 1.0f) return 255u;
+    return (unsigned int)floor(fma(v, 255.0f, 0.5f));
+}
+#if PTL_DEVICE_BUILD
+// The same function of v without a branch: c = v_med3(v, 0, 1), then the same fma, then the truncating convert.  Input by input:
+//   NaN          v_med3 with a NaN among its operands returns v_min3 of them, and v_min returns the operand that is a number (the rule
+//                ptl_number_or relies on): min3(NaN, 0, 1) = 0, fma gives 0.5, the convert 0 -- the first return;
+//   v <= 0, -0   the median of {v, 0, 1} is a zero of either sign, fma(+-0, 255, 0.5) = 0.5 -> 0 -- the first return (-inf included);
+//   v >= 1       the median is 1, fma(1, 255, 0.5) = 255.5 exactly -> 255 -- the second return (+inf included);
+//   0 < v < 1    the median is v itself (a subnormal v, kept or flushed, gives 0.5 + less than half an ulp = 0.5 either way): the very fma
+//                of the spelled form, whose value lies in [0.5, 255.5], and for a non-negative argument that fits the truncating convert
+//                IS floor followed by the convert.
+// All 2^32 inputs are compared on the device (tests/test_gpu_exit_forms.py), the model of this form on the host (tests/test_exit_forms.py).
+PTL_FN unsigned int ptl_unorm8_clamped(float v) { return (unsigned int)fma(__builtin_amdgcn_fmed3f(v, 0.0f, 1.0f), 255.0f, 0.5f); }
+#endif
 PTL_FN float sign(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
 PTL_FN float step(float edge, float x) { return x < edge ? 0.0f : 1.0f; }
 PTL_FN float mix(float a, float b, float t) { return a * (1.0f - t) + b * t; }

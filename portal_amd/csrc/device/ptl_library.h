@@ -303,15 +303,39 @@ PTL_FN bool ptl_is_collinear_len0(vec3 a, vec3 b, float length_a) {  // is_colli
 // --- colours ------------------------------------------------------- library.glsl:169-288
 PTL_FN vec3 color(float r, float g, float b) { return vec3(r * r, g * g, b * b); }
 
+// color_normal, color_grid and color_grid3 keep the reference's early returns.  Their select forms -- ONE verdict and one select per value,
+// the factor f of `start * f` being 1 where the text returns `start` itself (x * 1.0f is x bit for bit) -- are the same functions
+// (tests/test_exit_forms.py) and stay behind -DPTL_SELECT_COLOR_HELPERS for the record: priced and measured in DESIGN.md 2.1.3, not taken.
+//   color_normal  -69 instructions and -34 branches on the headline kernel, but the two normalisations then live across the toggle:
+//                 monoportal's baked build goes from 60 to 66 VGPRs and loses its eighth wave per SIMD, triple_portal's from 72 to 78 and its seventh;
+//   color_grid3   -127 instructions, -12 branches on the headline for 0.3 % of its time (inside the run-to-run spread), and +0.15 % on C5, whose
+//                 VALU pipes issue 97 % of the time: the selects and the three products run for every lane, the returns skipped them for most waves;
+//   color_grid    no BASELINE build changes by more than a handful of instructions.
+#if defined(PTL_SELECT_COLOR_HELPERS)
+#define PTL_SELECT_COLOR_NORMAL 1
+#define PTL_SELECT_COLOR_GRID 1
+#define PTL_SELECT_COLOR_GRID3 1
+#endif
 PTL_FN float color_normal(vec3 normal, vec4 direction) {
+#if defined(PTL_SELECT_COLOR_NORMAL)
+    const float facing = abs(dot(normalize(direction.sw<0, 1, 2>()), normalize(normal)));
+    return _angle_color_disable == 1 ? 1.0f : facing;
+#else
     if (_angle_color_disable == 1) return 1.0f;
     return abs(dot(normalize(direction.sw<0, 1, 2>()), normalize(normal)));
+#endif
 }
 
 PTL_FN vec3 color_grid(vec3 start, vec2 uv) {
+#if !defined(PTL_SELECT_COLOR_GRID)
     if (_grid_disable == 1) return start;
     uv = fract(uv * 0.25f);
     return start * mix(mix(0.7f, 1.1f, step(uv.x, 0.5f)), mix(1.1f, 0.7f, step(uv.x, 0.5f)), step(uv.y, 0.5f));
+#else
+    uv = fract(uv * 0.25f);
+    const float f = mix(mix(0.7f, 1.1f, step(uv.x, 0.5f)), mix(1.1f, 0.7f, step(uv.x, 0.5f)), step(uv.y, 0.5f));
+    return start * (_grid_disable == 1 ? 1.0f : f);
+#endif
 }
 
 PTL_FN float circle_sdf(vec2 position) {
@@ -329,6 +353,7 @@ PTL_FN vec3 color_grid2(vec3 start, vec2 uv) {
 }
 
 PTL_FN vec3 color_grid3(vec3 start, vec2 uv) {
+#if !defined(PTL_SELECT_COLOR_GRID3)
     if (_grid_disable == 1) return start;
     uv = fract(uv * 0.5f) - vec2(0.5f, 0.5f);
     float dist = max(abs(uv.x), abs(uv.y)) * 2.0f;
@@ -336,6 +361,13 @@ PTL_FN vec3 color_grid3(vec3 start, vec2 uv) {
     if (dist < 0.94f) return start;
     if (uv.x > uv.y) return start * 0.7f;
     return start * 1.2f;
+#else
+    // the verdicts in the order of the returns: a NaN dist fails both border tests and then `uv.x > uv.y` -- 1.2, as with the returns
+    uv = fract(uv * 0.5f) - vec2(0.5f, 0.5f);
+    const float dist = max(abs(uv.x), abs(uv.y)) * 2.0f;
+    const float f = _grid_disable == 1 ? 1.0f : (dist > 0.985f ? 0.4f : (dist < 0.94f ? 1.0f : (uv.x > uv.y ? 0.7f : 1.2f)));
+    return start * f;
+#endif
 }
 
 PTL_FN vec3 color_add_weighted(vec3 a, vec3 b, float coef) { return a * (1.0f - coef) + b * coef; }

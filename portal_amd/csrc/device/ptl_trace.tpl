@@ -373,6 +373,8 @@ PTL_FN bool trace_segment(Ray& r, vec3& current_color, float& all_t, const EyeSc
 
     // `m` is left unset by the reference when a snippet reports hit with t <= 0 (GLSL:
     // undefined value); this build defines that case as the all-zero MaterialProcessing.
+    // (As an initial value it costs nothing: the compiler sinks the 14 fields into the one path that keeps them -- setting the record
+    // there by hand gives the same binary, DESIGN.md 2.1.7.)
     MaterialProcessing m = MaterialProcessing{false, vec3(0.0f), ray_none};
     if (nearer(i.hit, i2.scene.hit)) {
         r.o += r.d * i2.scene.hit.t;
@@ -917,10 +919,14 @@ PTL_FN void derive_uniforms_in(ptl_uniform_block* block) {
 //%end
 
 // GL fixed-point conversion of one channel: clamp to [0,1], scale, round to nearest.
+// (the two forms and the proof that they are one function: ptl_glsl.h.  Alpha is the constant 1 of shade_pixel, but it reaches pack_rgba8 in
+// a register and is converted like the colours: DESIGN.md 2.1.3.)
 PTL_FN unsigned int unorm8(float v) {
-    if (!(v > 0.0f)) return 0u;  // also NaN
-    if (v >= 1.0f) return 255u;
-    return (unsigned int)floor(fma(v, 255.0f, 0.5f));
+#if PTL_DEVICE_BUILD && !defined(PTL_SPELLED_UNORM8)
+    return ptl_unorm8_clamped(v);
+#else
+    return ptl_unorm8_spelled(v);
+#endif
 }
 PTL_FN unsigned int pack_rgba8(vec4 c) {
     return unorm8(c.x) | (unorm8(c.y) << 8) | (unorm8(c.z) << 16) | (unorm8(c.w) << 24);

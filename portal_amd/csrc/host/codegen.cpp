@@ -1149,7 +1149,28 @@ StringStorage emit_intersection_material_processing(const Scene& scene, const Bu
     if (first_form && !plan.any_first_snippet()) return calls;
     for (size_t pos = 0; pos < scene.intersection_materials.size(); ++pos) {
         const bool own = first_form && !plan.snippet(scene.intersection_materials[pos].code).hoisted_first.empty();
-        calls.add_string("hit = intersect_material_" + std::to_string(pos) + (own ? "_first" : "") + "(r, ptl_far);\n");
+        const std::string call = "intersect_material_" + std::to_string(pos) + (own ? "_first" : "") + "(r, ptl_far)";
+        if (pos == 0) {
+            // The first snippet meets `result` = none, for which nearer() is `hit.hit && hit.t > 0`: its record is adopted as it stands, and only the
+            // flag takes the verdict -- one select instead of one per field of the record (15 on every trip of every lane).  A record whose
+            // flag is false is a record nobody reads.  The readers of the returned record (`i2`) in ptl_trace.tpl, and what guards them:
+            //   trace_segment   ptl_bound (-DPTL_SNIPPETS_FIRST)           `.scene.hit.t` behind `.scene.hit.hit &&`
+            //                   nearer(i.hit, i2.scene.hit)                 `.t` behind `current.hit &&` (ptl_library.h)
+            //                   `.scene.hit.t`, `.scene.material`, `.material`, material_process(r, i2.scene): inside that nearer() branch
+            //                   the escape test                             `.scene.hit.hit` alone
+            //   teleport_external_ray: the same nearer() and the same uses inside its branch
+            // (the passes sections of the template read `out` and the trip count, never `i2`), and the snippets after this one:
+            // nearer(result.scene.hit, ..) reads `result.t` behind `!result.hit ||`, and `result = hit` replaces every field.
+            calls.add_string("#if defined(PTL_SPELLED_ADOPTION)\n");
+            calls.add_string("hit = " + call + ";\n");
+            calls.add_string("if (nearer(result.scene.hit, hit.scene.hit)) { result = hit; }\n");
+            calls.add_string("#else\n");
+            calls.add_string("result = " + call + ";\n");
+            calls.add_string("result.scene.hit.hit = result.scene.hit.hit && (result.scene.hit.t > 0.0f);\n");
+            calls.add_string("#endif\n\n");
+            continue;
+        }
+        calls.add_string("hit = " + call + ";\n");
         calls.add_string("if (nearer(result.scene.hit, hit.scene.hit)) { result = hit; }\n\n");
     }
     return calls;

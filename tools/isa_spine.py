@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/isa_spine.py -- the SPINE of a scene snippet: the instructions every wave executes between the conditional regions of one stage.
 
-    python tools/isa_spine.py [--scene portal_in_portal] [--flags 5] [--waves 5] [--stage intersect_material_0]
+    python tools/isa_spine.py [--scene portal_in_portal] [--flags 5] [--waves 5] [--stage intersect_material_0 | trace_segment | pack_rgba8 | shade_pixel]
                               [--hiprtc-flags=-DPTL_EARLY_RETURN_HITS] [--out profiles/r07/isa_spine_<tag>.json]
 
 A snippet loop that the generator unrolls is a chain of candidates: per iteration a plane test, then `if (nearer(best, hit)) { ... }`, a
@@ -11,7 +11,9 @@ instruction stream is checked to be the shipped one), keeps the instructions who
 instruction that a forward branch of the stage jumps over (the conditional regions), and cuts what is left -- the code every wave executes --
 at each remaining forward conditional branch.  Per segment: the source line of the closing branch (the `if` it belongs to) and the
 instruction classes of tools/isa_hist.py.  Consecutive segments closing on the same line are the iterations of an unrolled loop; the summary
-gives the median per closing line.  STATIC counts, mnemonic classes only; no GPU needed."""
+gives the median per closing line.  `--stage` also takes a function of the template itself (trace_segment, pack_rgba8, shade_pixel: what OUR
+text makes every wave execute, whatever it inlines); the code after the last branch of a stage is its last segment, and the totals line gives
+the stage's size and the sum of its always-executed segments.  STATIC counts, mnemonic classes only; no GPU needed."""
 from __future__ import annotations
 
 import argparse
@@ -69,6 +71,10 @@ def spine(ins, where, stage, src_lines):
             cur = collections.Counter()
             continue
         cur[classify(m)] += 1
+    if cur:  # what follows the last branch -- for a stage without a conditional region (the template's pack_rgba8, say) the whole stage
+        valu = sum(c for k, c in cur.items() if k.startswith("valu_"))
+        segments.append({"closing_branch": "(end of stage)", "line": 0, "text": "", "valu": valu, **{k[5:]: cur[k] for k in CLASSES},
+                         "valu_other": valu - sum(cur[k] for k in CLASSES), "salu": cur["salu"]})
     return segments
 
 
@@ -103,12 +109,16 @@ def main():
     for ln, ss in sorted(per_line.items(), key=lambda kv: -len(kv[1])):
         summary.append({"line": ln, "text": ss[0]["text"], "segments": len(ss), **{k: statistics.median(s[k] for s in ss) for k in ("valu", "fp32_arith", "move", "compare", "select", "salu")},
                         "valu_min": min(s["valu"] for s in ss), "valu_max": max(s["valu"] for s in ss)})
+    in_stage = [m for adr, m, _ in ins if any(f == a.stage for f, _, _ in where.get(adr, []))]
+    always = {"valu": sum(s["valu"] for s in segments), "salu": sum(s["salu"] for s in segments), "branches": sum(1 for s in segments if s["closing_branch"].startswith("s_"))}
     result = {"build": f"{os.path.relpath(scene_path, HERE)} flags={a.flags} waves={a.waves} {a.hiprtc_flags}".strip(), "kernel": a.kernel, "stage": a.stage, "instructions": len(ins),
+              "stage_instructions": len(in_stage), "stage_branches": sum(1 for m in in_stage if classify(m) == "branch"), "always_executed": always,
               "same_instruction_stream_as_the_shipped_build": same_stream, "median_per_closing_line": summary, "segments": segments}
     if a.out:
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)
     print(f"{result['build']}: {len(ins)} instructions; same stream as the shipped build: {same_stream}; {len(segments)} always-executed segments of {a.stage}")
+    print(f"  {a.stage}: {len(in_stage)} instructions, {result['stage_branches']} branches; always executed: {always['valu']} VALU, {always['salu']} SALU, {always['branches']} conditional branches")
     for s in summary:
         print(f"  line {s['line']:5d} x{s['segments']:2d}  median VALU {s['valu']:5.1f} ({s['valu_min']}..{s['valu_max']})  arith {s['fp32_arith']:4.1f}  mov {s['move']:4.1f}  cmp {s['compare']:4.1f}  "
               f"sel {s['select']:4.1f}  salu {s['salu']:4.1f} | {s['text']}")
