@@ -1,5 +1,5 @@
 // glsl_tokens.h -- the lexer and the token view shared by every pass over the GLSL snippets of a scene: the GLSL -> C++ rewrite
-// (glsl_translate.cpp), the distance bound (glsl_bound.cpp), the uniform-work hoister (glsl_hoist.cpp), the affine-rays scan
+// (glsl_translate.cpp), the distance bound (glsl_bound.cpp), the uniform-work hoister (glsl_syntax.cpp, glsl_hoist.cpp), the affine-rays scan
 // (glsl_affine.cpp), the masked forms and unroll pragmas of a build (glsl_masks.cpp) and the generator's "does it name X" questions (codegen.cpp).
 #pragma once
 #include <initializer_list>

@@ -1280,6 +1280,58 @@ def test_hoister_does_not_tabulate_what_is_not_a_function_of_the_trip_number(pa,
     assert "ptl_tab_ok_" not in out and "ptl_k" not in prologue, why
 
 
+def _pinned_hoists():
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "hoist", "programs.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("entry", _pinned_hoists()["programs"], ids=lambda e: e["name"])
+def test_hoister_reproduces_the_pinned_programs(pa, entry):
+    """tests/golden/hoist/programs.json: hand-written snippets -- carried chains of values and of ray origins, the staged calls in both phases
+    of a loop, loops that must not be tabulated, a file-scope text with a function that does not parse -- and, byte for byte, what the
+    hoister of the commit named in the file made of each (tools/source_matrix.py hoist_golden), with and without an origin-uniform `r`."""
+    pinned = _pinned_hoists()
+    for label in ("plain", "origin_uniform"):
+        glsl, prologue = pa.hoist_glsl(entry["code"], pinned["uniforms"], params=pinned["params"][label], **entry["keywords"])
+        assert glsl == entry[label]["glsl"], label
+        assert prologue == "".join(entry[label]["members"]) + entry[label]["prologue"], label
+
+
+def test_hoister_on_truncated_snippets_under_sanitizers(tmp_path):
+    """tests/hoist_truncations_main.cpp, a program of its own compiled with the hoister's host units under AddressSanitizer and
+    UndefinedBehaviorSanitizer (runtimes linked statically; run as a plain child process, nothing is loaded into Python): every snippet
+    of the corpus scenes, cut behind each of its first 200 tokens, as a body and as a file-scope text, with and without an origin-uniform
+    `r` -- the parser's failure paths and the dropped functions of a text.  Clean exit, and the digest of all outputs is the one the
+    commit named in tests/golden/hoist/truncations.json printed."""
+    import glob, json, subprocess
+    with open(os.path.join(ROOT, "tests", "golden", "hoist", "truncations.json")) as f:
+        pinned = json.load(f)
+    snippets = []
+    for path in sorted(glob.glob(os.path.join(ROOT, "tests", "corpus", "scenes", "*.ron"))):
+        with open(path) as f:
+            snippets += [m.replace('\\"', '"') for m in re.findall(r'\(\("(.*?)"\)\)', f.read(), re.S)]
+    snippets = list(dict.fromkeys(snippets))  # distinct, in the order of their first appearance
+    with open(tmp_path / "snippets", "wb") as f:
+        for text in snippets:
+            f.write(b"%d\n" % len(text.encode()) + text.encode())
+    host = os.path.join(ROOT, "portal_amd", "csrc", "host")
+    units = [os.path.join(ROOT, "tests", "hoist_truncations_main.cpp")] + [os.path.join(host, unit) for unit in ("glsl_tokens.cpp", "glsl_syntax.cpp", "glsl_binding.cpp", "glsl_hoist.cpp")]
+    cxx = [os.environ.get("CXX", "g++"), "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
+    objects = [str(tmp_path / (os.path.basename(unit) + ".o")) for unit in units]
+    compiles = [subprocess.Popen(cxx + ["-I", ROOT, "-c", unit, "-o", obj], stderr=subprocess.PIPE, text=True) for unit, obj in zip(units, objects)]  # (side by side: most of the test's time)
+    for compile_ in compiles:
+        _, errors = compile_.communicate(timeout=600)
+        assert compile_.returncode == 0, errors
+    exe = tmp_path / "hoist_truncations"
+    build = subprocess.run(cxx + objects + ["-o", str(exe)], capture_output=True, text=True, timeout=600)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([str(exe), str(tmp_path / "snippets"), str(pinned["cuts"])], capture_output=True, text=True, timeout=600)
+    print(run.stdout)
+    assert run.returncode == 0 and "ERROR" not in run.stderr and "runtime error" not in run.stderr, (run.returncode, run.stderr[-2000:])
+    assert run.stdout.strip() == pinned["output"]
+
+
 def test_hoisted_scene_source_is_selfconsistent(pa):
     """Every member the snippets read exists in the block (behind the uploaded part) and is written by derive(); with the scene
     uniforms baked in, or with FLAG_NO_UNIFORM_HOIST / FLAG_NO_DERIVED_UNIFORMS, nothing is hoisted."""

@@ -9,6 +9,7 @@ commits and comparing the two manifests with `diff`:
     python3 tools/source_matrix.py programs before_programs.jsonl   (likewise on both sides; a manifest of its own: each stays a file of moderate size)
     python3 tools/source_matrix.py objects before_obj.jsonl  (slow: twenty hiprtc builds; give each side an empty PTL_CACHE_DIR)
     python3 tools/source_matrix.py digest before.jsonl       (prints the short form of a manifest, the one to keep under profiles/)
+    python3 tools/source_matrix.py hoist_golden tests/golden/hoist/programs.json   (on the PARENT only: what a refactor of the hoister must reproduce)
 
 `sources`: for every scene of tests/corpus/scenes/*.ron, every base and every variant below, one JSON line with the sha256 of the
 generated text and the sha256 of the text NORMALISED -- comments removed, every run of white space one space: two sources with the
@@ -20,7 +21,12 @@ Then one line per text of `ptl_device_source` that tests and tools paste into ha
 `programs`: the snippet passes by themselves.  One line per statement template of tests/test_affine_guard_fuzz.py (and per random
 program of its generator) with what `snippets_keep_rays_affine` says of it, verdict and message; one per program of the generators
 of tests/test_glsl_fuzz.py / tests/test_bound_fuzz.py and per mutated corpus snippet with the hashes of what `translate_glsl`,
-`translate_library_glsl`, `hoist_glsl` and `bound_glsl` make of it (or the message they refuse it with).
+`translate_library_glsl`, `hoist_glsl` and `bound_glsl` make of it (or the message they refuse it with); `hoist_origin_uniform` is
+`hoist_glsl` once more with the ray parameter `r` given as `@r`, a ray whose origin is uniform (the first-trip variants).  Last, one line
+per program of HOIST_PROGRAMS below: hand-written snippets, one for each thing the hoister does with loops, staged calls and functions.
+
+`hoist_golden`: the programs of HOIST_PROGRAMS with what the commit it runs on makes of each, whole texts, as the fixture that
+tests/test_host_logic.py::test_hoister_reproduces_the_pinned_programs compares with.  It records the hash of that commit.
 
 `digest`: a manifest of `sources` or `programs` is a megabyte of hashes.  Its digest has one line per scene / per kind of program
 with the number of lines and the sha256 of those lines as they stand in the manifest; the few lines that stand for themselves
@@ -64,13 +70,60 @@ def variants(pa):
             ("refine_slices", pa.FLAG_REFINE_SLICES)]
 
 
+HOIST_UNIFORMS = {"a_mat": "mat4", "a_mat_inv": "mat4", "b_mat": "mat4", "b_mat_inv": "mat4", "scale_u": "float", "n_u": "int", "dir_u": "vec3"}
+_LOOP = "vec4 nb = b_mat * vec4(0., 0., 1., 0.);\nvec4 acc = r.o;\n%sfor (int i = 0; i < %s; i++) %s\nreturn acc;"
+_STAGED = """{
+	vec3 u0 = normalize_normal(nb.xyz, r.d.xyz);
+	acc.y += plane_intersect(r, a_mat, nb.xyz);
+	if (is_collinear(u0, nb.xyz) || is_collinear(nb.xyz, u0)) { acc.w += 1.; }
+	nb = b_mat * (a_mat_inv * nb);
+	vec3 u1 = normalize_normal(nb.xyz, r.d.xyz);
+	acc.z += plane_intersect(r, a_mat, nb.xyz);
+	if (is_collinear(u1, nb.xyz) || is_collinear(nb.xyz, u1)) { acc.w += 2.; }
+}"""
+# (name, text, keywords of pa.hoist_glsl besides the uniforms and the parameters ["hit", "r"])
+HOIST_PROGRAMS = [
+    ("uniform chain carried through a canonical loop", _LOOP % ("", "n_u", "{\n\tacc += nb * scale_u + vec4(normalize(nb.xyz) * r.d.x, 0.);\n\tnb = b_mat * (a_mat_inv * nb);\n\tacc += nb * length(dir_u);\n}"), {}),
+    ("ray chain carried through a canonical loop", "Ray v = transform(a_mat, r);\nvec4 acc = vec4(0.);\nfor (int i = 0; i < n_u; i++) {\n\tacc += v.d * float(i) + v.o;\n"
+     "\tv = transform(b_mat, transform(a_mat_inv, v));\n\tacc += b_mat * v.o;\n}\nreturn acc;", {}),
+    ("ray chain that the body reads in a nested block only", "Ray v = transform(a_mat, r);\nvec4 acc = vec4(0.);\nfor (int i = 0; i < n_u; i++) {\n\tif (acc.x < 1.) { acc += v.d; }\n"
+     "\tv = transform(b_mat, transform(a_mat_inv, v));\n}\nreturn acc;", {}),
+    ("ray local written once, its origin read by a uniform expression", "Ray q = transform(a_mat, r);\nvec4 k = b_mat * (a_mat_inv * q.o);\nRay w = transform(b_mat_inv, q);\nreturn k + w.d + w.o;", {}),
+    ("two chains, the first reads the second, the second fails", "vec4 p = a_mat * vec4(0., 0., 1., 0.);\nvec4 q = b_mat * vec4(1., 0., 0., 0.);\nvec4 acc = r.o;\nfor (int i = 0; i < n_u; i++) {\n"
+     "\tacc += p * dot(q, r.d);\n\tp = a_mat_inv * (p + q);\n\tq = b_mat_inv * q + r.d;\n}\nreturn acc;", {}),
+    ("two chains, the second reads the first, the first fails", "vec4 q = b_mat * vec4(1., 0., 0., 0.);\nvec4 p = a_mat * vec4(0., 0., 1., 0.);\nvec4 acc = r.o;\nfor (int i = 0; i < n_u; i++) {\n"
+     "\tacc += p * dot(q, r.d);\n\tp = a_mat_inv * (p + q);\n\tq = b_mat_inv * q + r.d;\n}\nreturn acc;", {}),
+    ("two chains, one reads the other, both hold; a ray chain reads one of them", "mat4 m = a_mat * b_mat;\nvec4 p = a_mat * vec4(0., 0., 1., 0.);\nRay v = transform(b_mat, r);\nvec4 acc = r.o;\n"
+     "for (int i = 0; i < n_u; i++) {\n\tacc += p * dot(m[0], v.d) + v.o;\n\tv = transform(m, v);\n\tp = m * (a_mat_inv * p);\n\tm = m * b_mat_inv;\n}\nreturn acc;", {}),
+    ("staged calls before and after the update", _LOOP % ("", "n_u", _STAGED), {}),
+    ("staged calls outside any loop", "vec3 n = (a_mat * vec4(dir_u, 0.)).xyz;\nvec3 u = normalize_normal(n, r.d.xyz);\nfloat t = plane_intersect(r, b_mat, n);\n"
+     "return vec4(u * t, is_collinear(u, n) ? 1. : (is_collinear(n, u) ? 2. : 0.));", {}),
+    ("loop with a continue", _LOOP % ("", "n_u", "{\n\tif (acc.x > 1.) continue;\n\tacc += nb * scale_u;\n\tnb = b_mat * (a_mat_inv * nb);\n}"), {}),
+    ("loop that is not braced", _LOOP % ("", "n_u", "nb = b_mat * (a_mat_inv * nb);\nacc += nb * scale_u * 2.;"), {}),
+    ("loop whose bound is a local written twice", _LOOP % ("int n = n_u;\nn = n + 1;\n", "n", "{\n\tacc += nb * scale_u;\n\tnb = b_mat * (a_mat_inv * nb);\n}"), {}),
+    ("loop whose bound is a local written once; a nested loop with a chain of its own is left alone",
+     _LOOP % ("int n = n_u;\n", "n", "{\n\tacc += nb * scale_u;\n\tnb = b_mat * (a_mat_inv * nb);\n\tfor (int j = 0; j < 2; j++) { acc += a_mat * (b_mat * nb); }\n}"), {}),
+    ("three functions, the second does not parse", "vec4 first(Ray r) {\n\tfloat k = length(dir_u) * scale_u;\n\treturn r.o * k;\n}\n"
+     "vec4 second(Ray r, int m) {\n\tswitch (m) { case 0: return r.o; }\n\treturn r.d * (length(dir_u) * scale_u);\n}\n"
+     "vec4 third(SurfaceIntersection hit, Ray r) {\n\t" + (_LOOP % ("", "n_u", "{\n\tacc += nb * scale_u;\n\tnb = b_mat * (a_mat_inv * nb);\n}")).replace("\n", "\n\t") + "\n}\n", {"body_only": False}),
+    ("only rejected candidates while a chain is carried", "vec4 nb = vec4(dir_u, 0.);\nvec4 acc = r.o;\nfor (int i = 0; i < n_u; i++) {\n\tacc += nb * r.d.x + vec4(scale_u * 2.0);\n\tnb = a_mat_inv * nb;\n}\nreturn acc;", {}),
+    ("a function with an out parameter writes a local", "vec3 n = normalize(dir_u);\nturn(n);\nvec3 m = normalize(dir_u) * scale_u;\nreturn vec4(n * length(dir_u) + m * length(m), 0.0);", {"out_functions": ["turn"]}),
+]
+
+
+def hoist_program(pa, code, origin_uniform, keywords):
+    return pa.hoist_glsl(code, HOIST_UNIFORMS, params=["hit", "@r" if origin_uniform else "r"], **keywords)
+
+
 def snippet_passes(pa, code, uniforms=None, **hoist):
     """sha256 of what each snippet pass makes of `code`, or the message it refuses it with"""
     if uniforms is None:
         uniforms = {w: "mat4" for w in re.findall(r"\b\w+_mat(?:_inv|_teleport)?\b", code)} | {w: "float" for w in re.findall(r"\b\w+_u\b", code)}
     line = {}
+    origin_uniform = dict(hoist, params=["@r" if p == "r" else p for p in hoist["params"]])
     for name, run in (("translate", lambda: pa.translate_glsl(code)), ("translate_library", lambda: pa.translate_library_glsl(code)),
-                      ("hoist", lambda: "\0".join(pa.hoist_glsl(code, uniforms, **hoist))), ("bound", lambda: "%s\0%d" % pa.bound_glsl(code, ("modf", "bump")))):
+                      ("hoist", lambda: "\0".join(pa.hoist_glsl(code, uniforms, **hoist))), ("hoist_origin_uniform", lambda: "\0".join(pa.hoist_glsl(code, uniforms, **origin_uniform))),
+                      ("bound", lambda: "%s\0%d" % pa.bound_glsl(code, ("modf", "bump")))):
         try:
             line[name] = sha(run())
         except pa.PortalError as e:
@@ -129,6 +182,23 @@ def programs(pa):
         ok, why = pa.snippets_keep_rays_affine(code)
         yield {"program": "mutated_corpus", "n": k, "sha256": sha(code), "ok": ok, "why": why,
                **snippet_passes(pa, code, body_only=not re.search(r"^\s*\w+\s+\w+\s*\(", text), params=["r", "pos", "x", "y", "back", "first", "hit", "i"])}
+    for name, code, keywords in HOIST_PROGRAMS:
+        yield {"program": "hoist_hand_written", "name": name, "hoist": sha("\0".join(hoist_program(pa, code, False, keywords))),
+               "hoist_origin_uniform": sha("\0".join(hoist_program(pa, code, True, keywords)))}
+
+
+def hoist_golden(pa):
+    """the fixture: every program of HOIST_PROGRAMS with the whole texts this commit's hoister makes of it"""
+    commit = subprocess.run(["git", "rev-parse", "HEAD"], cwd=ROOT, check=True, capture_output=True, text=True).stdout.strip()
+    entries = []
+    for name, code, keywords in HOIST_PROGRAMS:
+        entry = {"name": name, "code": code, "keywords": keywords}
+        for label, origin_uniform in (("plain", False), ("origin_uniform", True)):
+            glsl, prologue = hoist_program(pa, code, origin_uniform, keywords)
+            members = [l for l in prologue.splitlines(True) if l.startswith("// member:")]
+            entry[label] = {"glsl": glsl, "members": members, "prologue": prologue[len("".join(members)):]}
+        entries.append(entry)
+    return {"recorded_from_commit": commit, "uniforms": HOIST_UNIFORMS, "params": {"plain": ["hit", "r"], "origin_uniform": ["hit", "@r"]}, "programs": entries}
 
 
 def sources(pa, out):
@@ -177,7 +247,7 @@ def digest(manifest):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3 or sys.argv[1] not in ("sources", "programs", "objects", "digest"):
+    if len(sys.argv) != 3 or sys.argv[1] not in ("sources", "programs", "objects", "digest", "hoist_golden"):
         sys.exit(__doc__)
     if sys.argv[1] == "digest":
         sys.stdout.writelines(digest(open(sys.argv[2])))
@@ -185,7 +255,10 @@ if __name__ == "__main__":
     import portal_amd as pa
 
     with open(sys.argv[2], "w") as out:
-        if sys.argv[1] == "programs":
+        if sys.argv[1] == "hoist_golden":
+            json.dump(hoist_golden(pa), out, indent=1)
+            out.write("\n")
+        elif sys.argv[1] == "programs":
             out.writelines(json.dumps(line) + "\n" for line in programs(pa))
         else:
             (sources if sys.argv[1] == "sources" else objects)(pa, out)
