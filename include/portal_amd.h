@@ -1059,6 +1059,10 @@ char* ptl_bound_glsl(const char* glsl_body, const char* out_functions, int* boun
  * *prologue (may be NULL), the GLSL statements for the prologue kernel, one line per created member in front as
  * "// member: type name[count]". */
 char* ptl_hoist_glsl(const char* glsl, const char* uniforms, const char* out_functions, int body_only, const char* params, char** prologue);
+/* What a build's compiled-in values do to a TRANSLATED snippet (host/glsl_translate.h `specialize_translated`), exposed for tests and tools:
+ * `masked` "M;N" names the matrix uniforms whose products get their masked forms, `unroll_bounds` "n=4;m=16" the baked Int uniforms whose
+ * loops get `_Pragma("unroll")`; *unrolled (may be NULL) receives how many did.  malloc'ed (ptl_free). */
+char* ptl_specialize_translated(const char* cxx, const char* masked, const char* unroll_bounds, int* unrolled);
 /* names/values: free variables; returns 0 and *out, 1 if the formula is invalid or unresolvable */
 int ptl_formula_eval(const char* text, const char* const* names, const double* values, int n, double time, double* out);
 

@@ -183,22 +183,40 @@ extern "C" char* ptl_bound_glsl(const char* glsl_body, const char* out_functions
     }
 }
 
+static std::vector<std::string> split(const char* text) {  // "a;b;c", empty parts dropped
+    std::vector<std::string> parts;
+    std::string cur;
+    for (const char* c = text ? text : ""; *c; ++c) {
+        if (*c == ';') {
+            if (!cur.empty()) parts.push_back(cur);
+            cur.clear();
+        } else {
+            cur += *c;
+        }
+    }
+    if (!cur.empty()) parts.push_back(cur);
+    return parts;
+}
+
+extern "C" char* ptl_specialize_translated(const char* cxx, const char* masked, const char* unroll_bounds, int* unrolled) {
+    if (!cxx) return nullptr;
+    try {
+        std::set<std::string> matrices;
+        for (const std::string& m : split(masked)) matrices.insert(m);
+        std::map<std::string, int> bounds;
+        for (const std::string& b : split(unroll_bounds)) {
+            const size_t eq = b.find('=');
+            if (eq != std::string::npos) bounds[b.substr(0, eq)] = std::atoi(b.c_str() + eq + 1);
+        }
+        return strdup(specialize_translated(cxx, matrices, bounds, unrolled).c_str());
+    } catch (const std::exception& e) {
+        set_last_error(std::string("ptl_specialize_translated: ") + e.what());
+        return nullptr;
+    }
+}
+
 extern "C" char* ptl_hoist_glsl(const char* glsl, const char* uniforms, const char* out_functions, int body_only, const char* params, char** prologue) {
     if (!glsl) return nullptr;
-    auto split = [](const char* text) {
-        std::vector<std::string> parts;
-        std::string cur;
-        for (const char* c = text ? text : ""; *c; ++c) {
-            if (*c == ';') {
-                if (!cur.empty()) parts.push_back(cur);
-                cur.clear();
-            } else {
-                cur += *c;
-            }
-        }
-        if (!cur.empty()) parts.push_back(cur);
-        return parts;
-    };
     HoistParams hp;
     for (const std::string& u : split(uniforms)) {
         size_t sp = u.find(' ');

@@ -11,8 +11,8 @@ namespace ptl {
 // See glsl_translate.h.  Every condition is checked on the token stream; anything not recognised leaves the snippet as written.
 std::string bound_nearer_blocks(const std::string& glsl_body, const std::set<std::string>& functions_with_out_params, int* bounded) {
     if (bounded) *bounded = 0;
-    std::vector<Token> toks = tokenize_glsl(glsl_body);
-    const TokenView s(toks);  // (the stream is only read: the one rewrite is applied while the text is put together)
+    const std::vector<Token> toks = tokenize_glsl(glsl_body);
+    const TokenView s(toks);
     const size_t n = s.n();
     // (1) the accumulator: exactly one `SceneIntersectionWithMaterial R = ...;`, at brace depth 0, and the body ends in `return R;`
     std::string R;
@@ -161,16 +161,10 @@ std::string bound_nearer_blocks(const std::string& glsl_body, const std::set<std
     }
 
     // (6) the rewrite: `nearer(R.scene.hit, H)` -> `nearer(R.scene.hit, H) && !(H.t > ptl_far)` (inserted in front of the condition's `)`)
-    std::vector<std::pair<size_t, std::string>> inserts;  // raw token index -> text in front of it
-    for (const Block& b : blocks) inserts.push_back({s.raw(b.cond_close), " && !(" + b.H + ".t > ptl_far)"});
-    std::string out;
-    size_t next = 0;
-    for (size_t k = 0; k < toks.size(); ++k) {
-        while (next < inserts.size() && inserts[next].first == k) out += inserts[next++].second;
-        out += toks[k].text;
-    }
+    TokenEdits edits(toks);
+    for (const Block& b : blocks) edits.before(s, b.cond_close, " && !(" + b.H + ".t > ptl_far)");
     if (bounded) *bounded = (int)blocks.size();
-    return out;
+    return edits.text();
 }
 
 }  // namespace ptl

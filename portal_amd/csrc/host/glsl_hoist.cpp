@@ -11,11 +11,6 @@
 namespace ptl {
 namespace {
 
-struct Replacement {
-    size_t b, e;  // significant tokens [b, e) replaced by `text` (b == e: an insertion in front of b)
-    std::string text;
-};
-
 struct PrologueItem {
     size_t at = 0;
     int loop = 0;  // > 0: belongs into the table loop of that loop; < 0: likewise, behind the tables (the update of a carried local)
@@ -23,7 +18,6 @@ struct PrologueItem {
 };
 
 struct FunctionOutcome {  // what hoisting did to one function
-    std::vector<Replacement> replacements;
     std::vector<HoistedMember> members;
     std::string prologue;  // its block
     int ids_used = 0;      // of the kernel-wide member numbers, from the one it was given on
@@ -50,31 +44,13 @@ std::string prologue_block(std::vector<PrologueItem> items) {
     return text + "}\n";
 }
 
-// The text with the replacements made, line for line.
-std::string rebuild(const std::vector<Token>& toks, const TokenView& s, std::vector<Replacement> replacements) {
-    std::stable_sort(replacements.begin(), replacements.end(), [](const Replacement& a, const Replacement& b) { return a.b < b.b || (a.b == b.b && a.e < b.e); });
-    std::vector<bool> drop(toks.size(), false);
-    for (const Replacement& r : replacements)
-        if (r.e > r.b)
-            for (size_t k = s.raw(r.b); k <= s.raw(r.e - 1); ++k) drop[k] = true;
-    std::string out;
-    size_t next = 0;
-    for (size_t k = 0; k <= toks.size(); ++k) {
-        while (next < replacements.size() && (replacements[next].b >= s.n() ? k == toks.size() : s.raw(replacements[next].b) == k)) out += replacements[next++].text;
-        if (k == toks.size()) break;
-        if (!drop[k]) out += toks[k].text;
-        else if (toks[k].kind == Token::Space && toks[k].text == "\n") out += "\n";  // line for line
-    }
-    return out;
-}
-
 // Hoists the work of one parsed function.  Member numbers are taken in this order, which the generated text shows: the guards of the
 // loops that carry something, the members as the sites are walked, one table per carried local; wherever carried locals are listed,
 // the uniform chains come before the rays, each by name.
 class FunctionHoist {
   public:
-    FunctionHoist(const TokenView& s, const ParsedBody& body, const HoistParams& params, const FunctionSpan& fn, int first_id)
-        : s_(s), body_(body), P(params), fn_(fn), first_id_(first_id), bt_(s, body, params, fn.params, fn.body_e) {}
+    FunctionHoist(const TokenView& s, const ParsedBody& body, const HoistParams& params, const FunctionSpan& fn, int first_id, TokenEdits& edits)
+        : s_(s), body_(body), P(params), fn_(fn), first_id_(first_id), edits_(edits), bt_(s, body, params, fn.param_names(), fn.body_e) {}
 
     FunctionOutcome run() {
         for (bool ray : {false, true})
@@ -102,6 +78,7 @@ class FunctionHoist {
     const HoistParams& P;
     const FunctionSpan& fn_;
     const int first_id_;
+    TokenEdits& edits_;  // of the whole text: the significant tokens [b, e) become `text`, line for line (b == e: `text` goes in front of b)
     BindingTimes bt_;
     FunctionOutcome out_;
     std::vector<PrologueItem> items_;
@@ -132,7 +109,11 @@ class FunctionHoist {
         rays_used_ = rays_used_ || ray;
         return bd.loop > 0 ? "(" + guard_name(bd.loop) + " ? " + value + " : (" + expr + "))" : value;
     }
-    void replace(size_t b, size_t e, const std::string& text) { out_.replacements.push_back({b, e, text}); }
+    void replace(size_t b, size_t e, const std::string& text) {
+        if (b == e) return edits_.before(s_, b, text);
+        edits_.replace(s_.raw(b), text);
+        edits_.drop(s_.raw(b) + 1, s_.raw(e - 1));
+    }
 
     void hoist_in(int id) {
         const Node& nd = body_.nodes[id];
@@ -205,24 +186,31 @@ HoistResult hoist_uniform_work(const std::string& glsl, const HoistParams& param
     out.glsl = glsl;
     try {
         const std::vector<Token> toks = tokenize_glsl(glsl);
-        const TokenView s(toks, TokenView::kLayout);  // keeps directives: a text that has one is left as it is.  The stream is never changed (rebuild() writes a new text).
+        const TokenView s(toks, TokenView::kLayout);  // keeps directives: a text that has one is left as it is
         for (size_t i = 0; i < s.n(); ++i)
             if (s[i].kind == Token::Preproc || s[i].kind == Token::Raw) return out;  // macros: the text is not what the compiler will see
-        const std::vector<FunctionSpan> fns = params.body_only ? std::vector<FunctionSpan>{{0, s.n(), params.body_params}} : function_definitions(s);
-        std::vector<Replacement> replacements;
+        std::vector<FunctionSpan> fns;
+        if (params.body_only) {  // all of the text, with the parameters the caller names
+            fns.emplace_back();
+            fns[0].body_e = s.n();
+            for (const std::string& name : params.body_params) fns[0].params.push_back({0, 0, name, false});
+        } else {
+            for (const FunctionSpan& fn : function_definitions(s))
+                if (fn.body_e < s.n() && s[fn.type_at].text != "return") fns.push_back(fn);  // whole functions, and `return f(x) {` opens none
+        }
+        TokenEdits edits(toks);
         HoistResult hoisted;
         int next = next_member;
         for (const FunctionSpan& fn : fns) {
             const ParsedBody body = parse_body(s, fn.body_b, fn.body_e);
             if (!body.ok) continue;  // leave this function exactly as written
-            const FunctionOutcome f = FunctionHoist(s, body, params, fn, next).run();
-            replacements.insert(replacements.end(), f.replacements.begin(), f.replacements.end());
+            const FunctionOutcome f = FunctionHoist(s, body, params, fn, next, edits).run();
             hoisted.members.insert(hoisted.members.end(), f.members.begin(), f.members.end());
             hoisted.prologue += f.prologue;
             next += f.ids_used;
         }
         if (hoisted.members.empty()) return out;
-        hoisted.glsl = rebuild(toks, s, replacements);
+        hoisted.glsl = edits.text();
         next_member = next;
         return hoisted;
     } catch (...) {  // (never throws: on anything unexpected the text comes back unchanged)

@@ -52,23 +52,21 @@ bool counts_to_small_bound(const TokenView& s, size_t i, const std::map<std::str
 
 }  // namespace
 
-// See glsl_translate.h.  One walk over the tokens collects the edits -- text in front of a token, behind it, in its place -- and the
-// stream is put together once; the walk itself reads the tokens as written, so a product inside an operand is judged by its own neighbours.
+// See glsl_translate.h.  The walk reads the tokens as written (TokenEdits), so a product inside an operand is judged by its own neighbours.
 std::string specialize_translated(const std::string& cxx, const std::set<std::string>& masked, const std::map<std::string, int>& unroll_bounds, int* unrolled) {
     if (unrolled) *unrolled = 0;
     if (masked.empty() && unroll_bounds.empty()) return cxx;
     const std::vector<Token> toks = tokenize_glsl(cxx);
     const TokenView s(toks);
-    std::vector<std::string> front(toks.size()), text(toks.size()), back(toks.size());
-    for (size_t k = 0; k < toks.size(); ++k) text[k] = toks[k].text;
+    TokenEdits edits(toks);
     for (size_t i = 0; i < s.n(); ++i) {
         if (!s.ident(i) || s.is(i - 1, ".")) continue;  // (a member is never the uniform)
         const std::string& word = s[i].text;
         if (word == "for" && counts_to_small_bound(s, i, unroll_bounds)) {
-            front[s.raw(i)] = "_Pragma(\"unroll\") ";
+            edits.before(s, i, "_Pragma(\"unroll\") ");
             if (unrolled) ++*unrolled;
         } else if (word == "transform" && s.is(i + 1, "(") && s.ident(i + 2) && masked.count(s[i + 2].text) && s.is(i + 3, ",")) {
-            text[s.raw(i)] = masked_callee(word, s[i + 2].text);
+            edits.replace(s.raw(i), masked_callee(word, s[i + 2].text));
         } else if (masked.count(word) && s.is(i + 1, "*")) {
             // `word` must be the whole left operand: nothing multiplicative in front of it, and no unary sign (which binds tighter than the
             // product: (-M) * v stays).  A sign is binary behind a name, a literal, `)` or `]`.
@@ -78,18 +76,16 @@ std::string specialize_translated(const std::string& cxx, const std::set<std::st
             if (end == s.n()) continue;
             // M * v -> ptl_mul_m<PTL_MASK_M>(M, v): the blanks around `*` go, comments and line breaks stay where they are
             const size_t star = s.raw(i + 1);
-            front[s.raw(i)] = masked_callee("ptl_mul_m", word) + "(";
+            edits.before(s, i, masked_callee("ptl_mul_m", word) + "(");
             for (size_t k = s.raw(i) + 1; k < star; ++k)
-                if (blank(toks[k])) text[k].clear();
+                if (blank(toks[k])) edits.replace(k, "");
             size_t next = star + 1;
-            if (blank(toks[next])) text[next++].clear();
-            text[star] = toks[next].text == "\n" ? "," : ", ";
-            back[s.raw(end)] += ")";
+            if (blank(toks[next])) edits.replace(next++, "");
+            edits.replace(star, toks[next].text == "\n" ? "," : ", ");
+            edits.behind(s.raw(end), ")");
         }
     }
-    std::string out;
-    for (size_t k = 0; k < toks.size(); ++k) out += front[k] + text[k] + back[k];
-    return out;
+    return edits.text();
 }
 
 }  // namespace ptl

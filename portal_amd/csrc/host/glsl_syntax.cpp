@@ -341,25 +341,33 @@ std::vector<FunctionSpan> function_definitions(const TokenView& s) {
     for (size_t i = 0; i < s.n(); ++i) {
         if (s.is(i, "{")) ++depth;
         else if (s.is(i, "}")) --depth;
-        else if (depth == 0 && s.ident(i) && s.ident(i + 1) && s.is(i + 2, "(") && s[i].text != "return") {
+        else if (depth == 0 && s.ident(i) && s.ident(i + 1) && s.is(i + 2, "(")) {
             const size_t close = s.close_of(i + 2);
-            if (close >= s.n() || !s.is(close + 1, "{")) continue;
-            const size_t end = s.close_of(close + 1);
-            if (end >= s.n()) continue;
-            FunctionSpan f{close + 2, end, {}};
-            size_t last_ident = s.n();
-            for (size_t j = i + 3; j <= close; ++j) {
-                if (s.ident(j)) last_ident = j;
-                if ((s.is(j, ",") || j == close) && last_ident < s.n()) {
-                    f.params.push_back(s[last_ident].text);
-                    last_ident = s.n();
+            if (!s.is(close + 1, "{")) continue;
+            FunctionSpan f;
+            f.type_at = i, f.name_at = i + 1, f.body_b = close + 2, f.body_e = s.close_of(close + 1);
+            if (close > i + 3)
+                for (const auto& [b, e] : s.split_top_level(i + 3, close, ",")) {
+                    FunctionSpan::Param p{b, e, "", false};
+                    for (size_t j = b; j < e; ++j) {
+                        if (s.ident(j)) p.name = s[j].text;
+                        p.out = p.out || s.ident(j, "out") || s.ident(j, "inout");
+                    }
+                    f.params.push_back(p);
                 }
-            }
             fns.push_back(f);
-            i = end;  // (depth stays 0)
+            for (size_t j = i + 3; j < close; ++j) depth += s.is(j, "{") ? 1 : s.is(j, "}") ? -1 : 0;  // (a brace astray in the list counts like any other)
+            i = f.body_e;  // (the body leaves the depth as it is; past an open one there is nothing at depth 0)
         }
     }
     return fns;
+}
+
+std::vector<std::string> FunctionSpan::param_names() const {
+    std::vector<std::string> names;
+    for (const Param& p : params)
+        if (!p.name.empty()) names.push_back(p.name);
+    return names;
 }
 
 }  // namespace ptl

@@ -51,10 +51,19 @@ ParsedBody parse_body(const TokenView& s, size_t b, size_t e);
 bool tokens_mention(const TokenView& s, size_t b, size_t e, const std::string& name);
 
 struct FunctionSpan {
-    size_t body_b, body_e;  // the tokens between its braces
-    std::vector<std::string> params;
+    struct Param {
+        size_t b, e;       // its tokens [b, e)
+        std::string name;  // the last identifier among them ("" if there is none; `void` of `f(void)` is one)
+        bool out;          // `out` / `inout` stands among them
+    };
+    size_t type_at = 0, name_at = 0;  // return type and name
+    std::vector<Param> params;        // the list between the parentheses, cut at its top-level commas; none for `()`
+    size_t body_b = 0, body_e = 0;    // the tokens between its braces; body_e == s.n(): the body is never closed
+    std::vector<std::string> param_names() const;  // of the parameters that have one
 };
-// The function definitions of a file-scope text (`type name(...) {` outside all braces) with their parameter names.
+// The function definitions of a file-scope text: identifier, identifier, `( ... ) {` outside all braces.  That is all the scan asks: the
+// word in front of the name may be `return` or `else`, what follows a `#define` on its line is code like any other, and the last
+// definition may lack its `}` -- whoever minds looks at the span.
 std::vector<FunctionSpan> function_definitions(const TokenView& s);
 
 }  // namespace ptl

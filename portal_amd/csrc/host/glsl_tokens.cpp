@@ -220,6 +220,37 @@ std::vector<std::pair<size_t, size_t>> TokenView::split_top_level(size_t from, s
     return parts;
 }
 
+void TokenEdits::drop(size_t first, size_t last) {
+    for (size_t k = first; k <= last && k < stream_->size(); ++k)
+        if (!((*stream_)[k].kind == Token::Space && (*stream_)[k].text == "\n")) replaced_.emplace(k, "");
+}
+
+std::vector<Token> TokenEdits::tokens() const {
+    std::vector<std::pair<size_t, std::string>> inserts = inserts_;
+    std::stable_sort(inserts.begin(), inserts.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    std::vector<Token> out;
+    out.reserve(stream_->size() + inserts.size());
+    size_t next = 0;
+    auto insert_up_to = [&](size_t slot) {
+        while (next < inserts.size() && inserts[next].first <= slot) out.push_back({Token::Raw, inserts[next++].second});
+    };
+    for (size_t k = 0; k < stream_->size(); ++k) {
+        insert_up_to(2 * k);
+        const auto r = replaced_.find(k);
+        if (r == replaced_.end()) out.push_back((*stream_)[k]);
+        else if (!r->second.empty()) out.push_back({(*stream_)[k].kind, r->second});
+        insert_up_to(2 * k + 1);
+    }
+    insert_up_to(2 * stream_->size());
+    return out;
+}
+
+std::string TokenEdits::text() const {
+    std::string out;
+    for (const Token& t : tokens()) out += t.text;
+    return out;
+}
+
 void defined_functions(const std::string& glsl, std::set<std::string>& names) {
     const std::vector<Token> toks = tokenize_glsl(glsl);
     const TokenView s(toks);

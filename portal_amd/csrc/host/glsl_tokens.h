@@ -1,8 +1,11 @@
-// glsl_tokens.h -- the lexer and the token view shared by every pass over the GLSL snippets of a scene: the GLSL -> C++ rewrite
-// (glsl_translate.cpp), the distance bound (glsl_bound.cpp), the uniform-work hoister (glsl_syntax.cpp, glsl_hoist.cpp), the affine-rays scan
-// (glsl_affine.cpp), the masked forms and unroll pragmas of a build (glsl_masks.cpp) and the generator's "does it name X" questions (codegen.cpp).
+// glsl_tokens.h -- the lexer, the token view and the token edit list shared by every pass over the GLSL snippets of a scene: the GLSL -> C++
+// rewrite (glsl_translate.cpp), the out-argument check (glsl_aliasing.cpp), the distance bound (glsl_bound.cpp), the uniform-work hoister
+// (glsl_syntax.cpp, glsl_hoist.cpp), the affine-rays scan (glsl_affine.cpp), the masked forms and unroll pragmas of a build (glsl_masks.cpp) and
+// the generator's "does it name X" questions (codegen.cpp).  A pass reads through a TokenView and writes through a TokenEdits.
 #pragma once
+#include <algorithm>
 #include <initializer_list>
+#include <map>
 #include <set>
 #include <string>
 #include <utility>
@@ -38,6 +41,7 @@ bool names_identifier(const std::string& glsl, std::initializer_list<const char*
 
 // The names of the functions a GLSL text defines (`type name(` outside all braces), and of those it defines with an `out` / `inout`
 // parameter (the qualifier in front of a type; the name in front of the `(` that opens its list).  Comments and directives are not code.
+// A looser question than glsl_syntax.h's function_definitions answers: a prototype counts as well, and the names are all there is.
 void defined_functions(const std::string& glsl, std::set<std::string>& names);
 void functions_with_out_params(const std::string& glsl, std::set<std::string>& names);
 
@@ -80,6 +84,33 @@ class TokenView {
   private:
     const std::vector<Token>* stream_;
     std::vector<size_t> at_;
+};
+
+// What one pass changes in one stream: text in front of a token, behind it, in its place, and tokens dropped.  Recorded by index in the
+// stream while the pass reads the tokens as written, applied once by text() / tokens(); the stream itself is never touched, and nothing
+// is tokenised again.  Where several texts meet in one slot between two tokens they come out in this order: what stands behind token k,
+// then what stands in front of token k + 1, each in the order it was recorded -- so text put in front of a token that is also replaced
+// or dropped stands in front of the replacement.  Inserted text comes out whether or not the token it is tied to is dropped.
+class TokenEdits {
+  public:
+    explicit TokenEdits(const std::vector<Token>& stream) : stream_(&stream) {}
+
+    void before(size_t k, const std::string& text) { inserts_.push_back({2 * std::min(k, stream_->size()), text}); }  // k at or past the size: the end
+    void behind(size_t k, const std::string& text) { inserts_.push_back({2 * k + 1, text}); }
+    void replace(size_t k, const std::string& text) { replaced_[k] = text; }  // the token keeps its kind; replaced by "" it is gone
+    void drop(size_t first, size_t last);  // [first, last] go, but for the line breaks among them (the text keeps its lines) and for what replace() names
+    // ... by significant-token index of a view of the same stream; at or past s.n() is the end of the stream
+    void before(const TokenView& s, size_t i, const std::string& text) { before(i < s.n() ? s.raw(i) : stream_->size(), text); }
+    void drop(const TokenView& s, size_t first, size_t last) { drop(s.raw(first), s.raw(last)); }
+
+    bool empty() const { return inserts_.empty() && replaced_.empty(); }
+    std::vector<Token> tokens() const;  // every inserted text a Token::Raw of its own: a significant token for the pass that comes next
+    std::string text() const;
+
+  private:
+    const std::vector<Token>* stream_;
+    std::vector<std::pair<size_t, std::string>> inserts_;  // (slot, text): slot 2k in front of token k, 2k + 1 behind it
+    std::map<size_t, std::string> replaced_;  // (a dropped token: replaced by "")
 };
 
 // For the walks that emit every token of a stream and so stay on it: the first index at or after k / the last one before k whose token is code

@@ -1303,7 +1303,9 @@ def test_hoister_on_truncated_snippets_under_sanitizers(tmp_path):
     UndefinedBehaviorSanitizer (runtimes linked statically; run as a plain child process, nothing is loaded into Python): every snippet
     of the corpus scenes, cut behind each of its first 200 tokens, as a body and as a file-scope text, with and without an origin-uniform
     `r` -- the parser's failure paths and the dropped functions of a text.  Clean exit, and the digest of all outputs is the one the
-    commit named in tests/golden/hoist/truncations.json printed."""
+    commit named in tests/golden/hoist/truncations.json printed.  The program's second line is the same for the other passes that write
+    through TokenEdits (translate_glsl four ways, bound_nearer_blocks, specialize_translated of the translation) and for the out-argument
+    check, against the line that the units of `edits_recorded_from_commit` printed."""
     import glob, json, subprocess
     with open(os.path.join(ROOT, "tests", "golden", "hoist", "truncations.json")) as f:
         pinned = json.load(f)
@@ -1316,7 +1318,8 @@ def test_hoister_on_truncated_snippets_under_sanitizers(tmp_path):
         for text in snippets:
             f.write(b"%d\n" % len(text.encode()) + text.encode())
     host = os.path.join(ROOT, "portal_amd", "csrc", "host")
-    units = [os.path.join(ROOT, "tests", "hoist_truncations_main.cpp")] + [os.path.join(host, unit) for unit in ("glsl_tokens.cpp", "glsl_syntax.cpp", "glsl_binding.cpp", "glsl_hoist.cpp")]
+    units = [os.path.join(ROOT, "tests", "hoist_truncations_main.cpp")] + [os.path.join(host, unit) for unit in
+        ("glsl_tokens.cpp", "glsl_syntax.cpp", "glsl_binding.cpp", "glsl_hoist.cpp", "glsl_translate.cpp", "glsl_aliasing.cpp", "glsl_bound.cpp", "glsl_masks.cpp", "glsl_affine.cpp")]
     cxx = [os.environ.get("CXX", "g++"), "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
     objects = [str(tmp_path / (os.path.basename(unit) + ".o")) for unit in units]
     compiles = [subprocess.Popen(cxx + ["-I", ROOT, "-c", unit, "-o", obj], stderr=subprocess.PIPE, text=True) for unit, obj in zip(units, objects)]  # (side by side: most of the test's time)
@@ -1329,7 +1332,7 @@ def test_hoister_on_truncated_snippets_under_sanitizers(tmp_path):
     run = subprocess.run([str(exe), str(tmp_path / "snippets"), str(pinned["cuts"])], capture_output=True, text=True, timeout=600)
     print(run.stdout)
     assert run.returncode == 0 and "ERROR" not in run.stderr and "runtime error" not in run.stderr, (run.returncode, run.stderr[-2000:])
-    assert run.stdout.strip() == pinned["output"]
+    assert run.stdout.splitlines() == [pinned["output"], pinned["edits_output"]]
 
 
 def test_hoisted_scene_source_is_selfconsistent(pa):

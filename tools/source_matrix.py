@@ -21,7 +21,9 @@ Then one line per text of `ptl_device_source` that tests and tools paste into ha
 `programs`: the snippet passes by themselves.  One line per statement template of tests/test_affine_guard_fuzz.py (and per random
 program of its generator) with what `snippets_keep_rays_affine` says of it, verdict and message; one per program of the generators
 of tests/test_glsl_fuzz.py / tests/test_bound_fuzz.py and per mutated corpus snippet with the hashes of what `translate_glsl`,
-`translate_library_glsl`, `hoist_glsl` and `bound_glsl` make of it (or the message they refuse it with); `hoist_origin_uniform` is
+`translate_library_glsl`, `hoist_glsl` and `bound_glsl` make of it (or the message they refuse it with); `specialize` is the
+translation through `specialize_translated` (the test entry ptl_specialize_translated; a parent that lacks it gets it patched into its
+worktree) with the text's matrix names as masked and every identifier as an Int baked to 4; `hoist_origin_uniform` is
 `hoist_glsl` once more with the ray parameter `r` given as `@r`, a ray whose origin is uniform (the first-trip variants).  Last, one line
 per program of HOIST_PROGRAMS below: hand-written snippets, one for each thing the hoister does with loops, staged calls and functions.
 
@@ -115,6 +117,22 @@ def hoist_program(pa, code, origin_uniform, keywords):
     return pa.hoist_glsl(code, HOIST_UNIFORMS, params=["hit", "@r" if origin_uniform else "r"], **keywords)
 
 
+def specialize(pa, cxx, masked, unroll_bounds):
+    """pa has no wrapper for the test entry ptl_specialize_translated: called through the library itself"""
+    import ctypes as C
+    L = pa.lib()
+    L.ptl_specialize_translated.restype = C.c_void_p
+    L.ptl_specialize_translated.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]
+    n = C.c_int()
+    p = L.ptl_specialize_translated(cxx.encode("utf-8"), ";".join(masked).encode(), ";".join(f"{k}={v}" for k, v in unroll_bounds.items()).encode(), C.byref(n))
+    if not p:
+        raise pa.PortalError(L.ptl_last_error().decode())
+    try:
+        return "%s\0%d" % (C.string_at(p).decode("utf-8"), n.value)
+    finally:
+        L.ptl_free(C.c_void_p(p))
+
+
 def snippet_passes(pa, code, uniforms=None, **hoist):
     """sha256 of what each snippet pass makes of `code`, or the message it refuses it with"""
     if uniforms is None:
@@ -123,7 +141,8 @@ def snippet_passes(pa, code, uniforms=None, **hoist):
     origin_uniform = dict(hoist, params=["@r" if p == "r" else p for p in hoist["params"]])
     for name, run in (("translate", lambda: pa.translate_glsl(code)), ("translate_library", lambda: pa.translate_library_glsl(code)),
                       ("hoist", lambda: "\0".join(pa.hoist_glsl(code, uniforms, **hoist))), ("hoist_origin_uniform", lambda: "\0".join(pa.hoist_glsl(code, uniforms, **origin_uniform))),
-                      ("bound", lambda: "%s\0%d" % pa.bound_glsl(code, ("modf", "bump")))):
+                      ("bound", lambda: "%s\0%d" % pa.bound_glsl(code, ("modf", "bump"))),
+                      ("specialize", lambda: specialize(pa, pa.translate_glsl(code), sorted(set(re.findall(r"\b\w+_mat(?:_inv|_teleport)?\b", code))), {w: 4 for w in sorted(set(re.findall(r"\b[A-Za-z_]\w*\b", code)))}))):
         try:
             line[name] = sha(run())
         except pa.PortalError as e:
